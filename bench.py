@@ -2,9 +2,16 @@
 """bench.py -- frame-pairs/s and tracked-features/s of the sparse LK tracking loop on MI355X.
 
     python bench.py --gpus 1 --steps 200 --warmup 10               # BASELINE.json configs[1] (C2), the headline
+    python bench.py --gpus 1 --steps 200 --warmup 10 --full        # ... plus CPU baseline, kernels alone, rooflines
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs D  # ... and the last step's outputs as D/<name>.npy
     python bench.py --config c3                                    # configs[2]: 64 pairs streamed from pinned host memory
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      # configs[3] (C4) shape: sharded sequence + RCCL gather
+
+A plain run sets up, settles and warms up, times the K steps and prints the line.  `--full` adds what the headline does
+not need: the CPU baseline, every kernel once more alone on the device after the timed region (`kernel_rooflines`,
+`iterations_per_feature`) and the `roofline` objects.  `--dump-outputs DIR` writes, after the timed region, what the timed
+path handed its caller in its last step (float32 .npy); the inputs are the same on every run with the same arguments.
 
 A "step" is one pass of the reference's frame loop body (s1_lucaskanade_tracking.py:307-450) over one new frame that is
 already resident in HBM: Gaussian pyramid of the new frame, fused forward + backward pyramidal LK of all live features
@@ -256,6 +263,24 @@ def numa_placement(device_index):
     return out
 
 
+def dump_outputs(out_dir, ctx, archive):
+    """--dump-outputs: what the timed path handed its caller in its last step, as float32 .npy files -- `tracks` and
+    `trackquality`, the np.savez payload of s1:394-395, of the last segment archived inside the timed region (the archive
+    entry as the loop wrote it; C4's archive holds no trackquality; nothing with --no-archive), and `live_tracks` /
+    `live_trackquality`, the segment still open after the last step (icelk_seg_read).  Written after the timed region."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if archive is not None and archive["n"] > 0:
+        s = (archive["n"] - 1) % archive.get("ring", archive["tracks"].shape[0])
+        rows = int(archive["counts"][s].item())
+        arrays["tracks"] = archive["tracks"][s][:rows].cpu().numpy()
+        if "quality" in archive:
+            arrays["trackquality"] = archive["quality"][s][:rows].cpu().numpy()
+    arrays["live_tracks"], arrays["live_trackquality"] = ctx.seg_read()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU), BEFORE anything in
     this process has touched the GPU -- no exec of a process that has initialised HIP, the children are plain child
@@ -299,7 +324,13 @@ def main():
     ap.add_argument("--motion", default="shear", choices=("shear", "translate"),
                     help="frame-to-frame motion of the synthetic sequence: sub-pixel translation plus a slowly varying "
                          "affine deformation of up to 0.5 %% (default), or translation only (the easiest case)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, every kernel alone on the device "
+                         "after the timed region (kernel_rooflines, iterations_per_feature) and the roofline objects")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the timed path handed its caller in its last step as "
+                         "DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="leave out the per-kernel HIP events (and with them the roofline object): shows what they cost")
     ap.add_argument("--time-all-kernels", action="store_true",
@@ -363,9 +394,7 @@ def main():
     cfg = CONFIGS[cname]
     w, h = cfg["w"], cfg["h"]
     W = args.warmup
-    K = args.steps if args.steps is not None else (64 if cname == "c3" else 200)
-    if cname == "c3":
-        K = 64   # BASELINE.json configs[2]: 64 consecutive pairs
+    K = args.steps if args.steps is not None else (64 if cname == "c3" else 200)   # BASELINE.json configs[2]: 64 pairs
     linear = cname in ("c3", "c4")            # a sequence of distinct frames instead of a ping-pong ring
     steps_note = None
     if linear and K % TRACK_LEN:
@@ -374,6 +403,8 @@ def main():
         K_req, K = K, max(TRACK_LEN, K - K % TRACK_LEN)
         steps_note = "--steps %d rounded to %d: %s shards by segments of track_len = %d frames" % (K_req, K, cname, TRACK_LEN)
         sys.stderr.write("bench.py: " + steps_note + "\n")
+    if cname == "c3" and K != 64:
+        cfg = dict(cfg, name="C3: %d consecutive frames (%d pairs) of %s" % (K + 1, K, C2_NAME))
     ring = (W + K + 1) if linear else max(2, min(args.ring, K + W + 1))
     max_pts = max(cfg["max_corners"], 1 << 14) if cfg["max_corners"] > 0 else 1 << 18
     seed = 1234
@@ -417,7 +448,8 @@ def main():
     # candidates, min-distance stages, pyramids and joint launches for the frames that follow) exactly as the warm-up looked
     # ahead for the first timed steps -- the timed region is a window of the steady state: K pairs go out inside it
     settle_max = int(args.settle_ms * 1e3 / 100.0) + 64 if args.settle_ms > 0 else 0   # steps, were a step to last only 100 us
-    order = list(range(ring)) if linear else ping_pong(ring, settle_max + K + W + SegmentTracker.MAX_AHEAD)
+    period = 2 * (ring - 1)     # the ping-pong order repeats itself after this many steps
+    order = list(range(ring)) if linear else ping_pong(ring, settle_max + period + K + W + SegmentTracker.MAX_AHEAD)
     archive = None
     settle = dict(ms_asked=args.settle_ms, ms=0.0, steps=0,
                   note="untimed: the same loop before the W warm-up steps, so that the timed window sees settled clocks")
@@ -481,6 +513,11 @@ def main():
             run_resident(tracker, order, S, 32)
             ctx.sync()
             S += 32
+        if S % period:
+            # the settle phase ends after whole passes over the ring: the warm-up and the timed steps then visit the same
+            # frames, in the same phase of the segments, on every run (--dump-outputs compares runs output for output)
+            run_resident(tracker, order, S, period - S % period)
+            S += period - S % period
         settle["steps"], settle["ms"] = S, (time.perf_counter() - ts0) * 1e3
         run_resident(tracker, order, S, W)
         timed_order = order
@@ -511,6 +548,8 @@ def main():
     n_live, tracked1 = tracker.live()
     elapsed = t1 - t0
     tracked = tracked1 - tracked0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, archive)
     # frame pairs whose tracker launch lies inside the timed region (a joint launch carries two)
     # counted by the tracker itself (the same quantity with and without --no-kernel-timing); the HIP-event table of the
     # tracker launches must agree where it exists
@@ -527,7 +566,7 @@ def main():
     # ---- the same kernels once more, each ALONE on the device (outside the timed region): inside the pipeline their
     # HIP-event durations include waiting for wave slots beside the tracker launch ------------------------------------------
     alone, iters, pcie = {}, None, None
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and args.full and not args.no_kernel_timing:
         bs = DETECT["blockSize"]
         sl = list(range(min(ring, 6)))
         for _ in range(2):   # first pass warms up
@@ -632,7 +671,7 @@ def main():
                     host_us_per_frame=dict(median=float(np.median(step_us[:-1])), longest=float(step_us[:-1].max()),
                                            longest_at=int(step_us[:-1].argmax()), first8=[round(float(x), 1) for x in step_us[:8]],
                                            final_wait=float(step_us[-1])), note="a handle of its own, warmed up with the same W frames; includes the first frame's upload and the first "
-                         "(blocking) detection of the 65-frame batch")
+                         "(blocking) detection of the %d-frame batch" % len(pinned))
         for ptr in pinned_all:
             hctx.host_free(ptr)
         hctx.close()
@@ -706,7 +745,7 @@ def main():
             "segments_archived_in_timed_region": archived if archiving else None, "segments_expected": segments_expected,
             "archive": ("every finished segment compacted on the device inside the timed region (icelk_seg_archive: tracks + "
                         "trackquality of s1:394-395)" if archiving else "off (--no-archive)"),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/int32/f32",
+            "full": bool(args.full), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/int32/f32",
             "data": "synthetic",
             "config": {"workload": cfg["name"], "width": w, "height": h, "max_corners": cfg["max_corners"],
                        "win": list(cfg["win"]), "maxLevel": cfg["max_level"], "pyramid_images": top + 1,
@@ -733,7 +772,8 @@ def main():
             out["pcie_inclusive"] = pcie
         kern = {}
         # tracker launches of the timed region: single segment pairs and joint launches of two (icelk_seg_track_defer)
-        lk_kinds = [prof[k] for k in ("lk_fb", "lk_fb_pair") if prof.get(k) and prof[k]["launches"]]
+        # the roofline objects (and the kernels alone, measured above): --full
+        lk_kinds = [prof[k] for k in ("lk_fb", "lk_fb_pair") if args.full and prof.get(k) and prof[k]["launches"]]
         lkp = None
         if lk_kinds:
             nl = sum(k["launches"] for k in lk_kinds)
@@ -756,7 +796,7 @@ def main():
                                "features_per_launch": n_avg, "frame_pairs_per_launch": lkp["pairs_per_launch"],
                                "note": "LK is VALU-issue-bound (SURVEY.md 8d); HBM fraction reported for completeness, the "
                                        "issue fraction is in valu_issue"}
-        pd = prof.get("pyrdown")
+        pd = prof.get("pyrdown") if args.full else None
         if pd or alone.get("pyrdown"):
             alg = pyramid_algorithmic_bytes(w, h, top)
             kern["pyramid"] = {"bound": "hbm", "algorithmic_bytes_per_frame": alg}
@@ -796,7 +836,7 @@ def main():
                                             rocprof_source="profiles/r04_gray_alone_kernel_stats.csv (tools/gray_alone.py; a committed profile, not this run)")
                 except Exception:
                     pass
-        eg = prof.get("corner_candidates")
+        eg = prof.get("corner_candidates") if args.full else None
         if eg or alone.get("corner_candidates"):
             alg = 1.0 * w * h   # 1 B/px in; the eigenvalue map is never materialised (k_corners.hip)
             kern["corner_candidates"] = {"bound": "hbm", "algorithmic_bytes_per_launch": alg,
@@ -811,7 +851,8 @@ def main():
         if lkp and alone.get("lk_fb"):
             kern["lk_fb"] = {"bound": "valu issue", "avg_launch_us": lkp["avg_us"], "alone_us": alone["lk_fb"]["avg_us"]}
         out["kernels"] = {k: {"launches": v["launches"], "avg_us": round(v["avg_us"], 2)} for k, v in prof.items()}
-        out["kernel_rooflines"] = kern
+        if args.full:
+            out["kernel_rooflines"] = kern
         if iters:
             out["iterations_per_feature"] = iters
         pmc_file = os.path.join(ROOT, "profiles", "pmc_%s.json" % cname)
@@ -875,7 +916,7 @@ def main():
                                     "instructions need at the measured issue rate of their classes / wall time of the period"}
             except Exception as exc:
                 sys.stderr.write("profiles/pmc_%s.json unreadable: %s\n" % (cname, exc))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, args.motion)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if dist is not None:

@@ -21,11 +21,14 @@ class OracleCv:
                                     kw.get("blockSize", 3))
 
 
-def test_npz_name_is_what_s2_parses(tmp_path):
+def test_npz_name_is_what_s2_parses(tmp_path, monkeypatch):
     """s2_cam_to_utm.py:177 takes split('_')[-2].split('sec')[0] as the tracking interval and :197-198
-    split('_')[0] as the timestamp; s1:394 builds '<image without extension>_{T*dt}sec_at_{dt}sec_tracks.npz'."""
+    split('_')[0] as the timestamp; s1:394 builds '<image without extension>_{T*dt}sec_at_{dt}sec_tracks.npz'.
+    s1:394 cuts the whole path at its first '.', so the image is named relative to the temporary directory: where
+    that directory lies (a parent with a '.' in its name) must not decide the outcome."""
     from iceberg_tracking_code_amd import npz_name, save_tracks
-    name = npz_name(str(tmp_path / "20190724-101500.jpg"), 2, 60)
+    monkeypatch.chdir(tmp_path)
+    name = npz_name("20190724-101500.jpg", 2, 60)
     base = os.path.basename(name)
     assert base == "20190724-101500_120sec_at_60sec_tracks.npz"
     assert int(base.split("_")[-2].split("sec")[0]) == 60
