@@ -37,6 +37,15 @@ __device__ __forceinline__ float sum_to_float(long long t)
     return __fadd_rn(__fmul_rn((float)hi, 65536.f), (float)lo);
 }
 
+// floor of a wave-uniform coordinate as an int in a scalar register: v_floor, v_cvt, one readlane.  Written as
+// uni((int)floorf(x)), the compiler read the float back first, converted that in the vector unit and read the int back again.
+__device__ __forceinline__ int floor_uni(float x)
+{
+    int i = (int)floorf(x);
+    asm volatile("" : "+v"(i));
+    return uni(i);
+}
+
 // A template as it travels from the backward pass of one pair to the forward pass of the next (LKBuffers::tmpl_out):
 // the lane's registers, flattened to dwords -- Ineg, then the packed gradient pairs -- in 16-byte pieces.
 template <int WW, int WH>
@@ -288,12 +297,13 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
         if (level == P.top_level) { sx = px; sy = py; }
         else { sx = sx * 2.f; sy = sy * 2.f; }
         px -= half_x; py -= half_y;
-        const int ipx = uni((int)floorf(px)), ipy = uni((int)floorf(py));
+        const int ipx = floor_uni(px), ipy = floor_uni(py);
         if (!origin_ok<WW, WH>(LI, ipx, ipy)) {
             if (level == 0) { Rz.status = 0; Rz.err = 0.f; }
             continue;
         }
-        const Weights wi = bilinear_weights(px - (float)ipx, py - (float)ipy);
+        uint32_t wi0, wi1;
+        packed_weights<false>(px - (float)ipx, py - (float)ipy, wi0, wi1);
 
         // ---- stage the template source patch and (speculatively) the first search tile ---------------
         float nx = sx - half_x, ny = sy - half_y;
@@ -302,7 +312,7 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
         const int ix0 = ipx - 1, iy0 = ipy - 1;
         const bool i_inside = tile_inside(LI, ix0, iy0, C::ITW, C::ITH);
         {
-            const int inx = uni((int)floorf(nx)), iny = uni((int)floorf(ny));
+            const int inx = floor_uni(nx), iny = floor_uni(ny);
             const bool j_ok = origin_ok<WW, WH>(LJ, inx, iny);
             const int tjx = inx - R, tjy = iny - R;
             const bool j_inside = j_ok && tile_inside(LJ, tjx, tjy, C::JTW, C::JTH);
@@ -345,10 +355,10 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
 #pragma unroll
                     for (int q = 0; q < (S + 1) / 2; q++)
                         pmask_l[k][q] = (2 * q < len_l[k] ? 0xffffu : 0u) | (2 * q + 1 < len_l[k] ? 0xffff0000u : 0u);
-                template_pixels<WW, WH, 1, 0>(T, ldsI, (uint32_t)uni((int)pack_weights_lo(wi)), (uint32_t)uni((int)pack_weights_hi(wi)),
+                template_pixels<WW, WH, 1, 0>(T, ldsI, (uint32_t)uni((int)wi0), (uint32_t)uni((int)wi1),
                                               ix0 & 3, i_inside, ipx, ipy, LI.w, LI.h, row_l, col_l, pmask_l, a11, a12, a22, fsum, len_l);
             } else
-            template_pixels<WW, WH, 1, 0>(T, ldsI, (uint32_t)uni((int)pack_weights_lo(wi)), (uint32_t)uni((int)pack_weights_hi(wi)),
+            template_pixels<WW, WH, 1, 0>(T, ldsI, (uint32_t)uni((int)wi0), (uint32_t)uni((int)wi1),
                                           ix0 & 3, i_inside, ipx, ipy, LI.w, LI.h, trow, tcol, pmask, a11, a12, a22, fsum, tlen);
             // |Ix*Ix| <= 4080^2 per pixel: 16-lane sums fit int32 while a lane holds <= 8 pixels
             long long s11, s12, s22;
@@ -389,7 +399,7 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
         // ---- iterations ---------------------------------------------------------------------------
         float pdx = 0.f, pdy = 0.f;
         for (int j = 0; j < P.max_count; j++) {
-            const int inx = uni((int)floorf(nx)), iny = uni((int)floorf(ny));
+            const int inx = floor_uni(nx), iny = floor_uni(ny);
             if (!origin_ok<WW, WH>(LJ, inx, iny)) {
                 if (level == 0) Rz.status = 0;
                 break;
@@ -405,19 +415,20 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
                 staged = true;
             }
             Rz.iters++;
-            const Weights wj = bilinear_weights(nx - (float)inx, ny - (float)iny);
-            const int jb = (iny - jy0) * (C::JPD * 4) + (jx0 & 3) + (inx - jx0);
+            uint32_t wj0, wj1;
+            packed_weights<true>(nx - (float)inx, ny - (float)iny, wj0, wj1);
+            const int jb = uni((iny - jy0) * (C::JPD * 4) + (jx0 & 3) + (inx - jx0));
             int b1, b2;
             if constexpr (kPackSeg) {
                 int row_l[C::TPL], col_l[C::TPL], len_l[C::TPL], joff_l[C::TPL];
                 seg_rows_cols(row_l, col_l, len_l);
 #pragma unroll
                 for (int k = 0; k < C::TPL; k++) joff_l[k] = row_l[k] * (C::JPD * 4) + col_l[k];
-                residual_pixels<WW, WH, 1, 0, false>(T, ldsJ, jb, (uint32_t)uni((int)pack_weights_lo(wj)),
-                                                     (uint32_t)uni((int)pack_weights_hi(wj)), joff_l, len_l, b1, b2, fsum, row_l, col_l);
+                residual_pixels<WW, WH, 1, 0, false>(T, ldsJ, jb, (uint32_t)uni((int)wj0),
+                                                     (uint32_t)uni((int)wj1), joff_l, len_l, b1, b2, fsum, row_l, col_l);
             } else
-            residual_pixels<WW, WH, 1, 0, false>(T, ldsJ, jb, (uint32_t)uni((int)pack_weights_lo(wj)),
-                                                 (uint32_t)uni((int)pack_weights_hi(wj)), joff, tlen, b1, b2, fsum, trow, tcol);
+            residual_pixels<WW, WH, 1, 0, false>(T, ldsJ, jb, (uint32_t)uni((int)wj0),
+                                                 (uint32_t)uni((int)wj1), joff, tlen, b1, b2, fsum, trow, tcol);
             // |diff*Ix| <= 8160*4080 per pixel: 8-lane sums fit int32 while a lane holds <= 8 pixels
             long long t1, t2;
             wave_sum2_i64<kSmall ? 8 : 1>(b1, b2, t1, t2);
@@ -456,7 +467,7 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
         // ---- residual error at level 0 ----------------------------------------------------------------
         if (Rz.status && level == 0 && !(P.flags & ICELK_FLAG_MIN_EIGENVALS)) {
             const float qx = sx - half_x, qy = sy - half_y;
-            const int iqx = uni((int)floorf(qx)), iqy = uni((int)floorf(qy));
+            const int iqx = floor_uni(qx), iqy = floor_uni(qy);
             if (!origin_ok<WW, WH>(LJ, iqx, iqy)) {
                 Rz.status = 0;
                 continue;
@@ -474,19 +485,20 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
                 __syncthreads();
                 staged = true;
             }
-            const Weights we = bilinear_weights(qx - (float)iqx, qy - (float)iqy);
-            const int jb = (iqy - jy0) * (C::JPD * 4) + (jx0 & 3) + (iqx - jx0);
+            uint32_t we0, we1;
+            packed_weights<true>(qx - (float)iqx, qy - (float)iqy, we0, we1);
+            const int jb = uni((iqy - jy0) * (C::JPD * 4) + (jx0 & 3) + (iqx - jx0));
             int es, unused;
             if constexpr (kPackSeg) {
                 int row_l[C::TPL], col_l[C::TPL], len_l[C::TPL], joff_l[C::TPL];
                 seg_rows_cols(row_l, col_l, len_l);
 #pragma unroll
                 for (int k = 0; k < C::TPL; k++) joff_l[k] = row_l[k] * (C::JPD * 4) + col_l[k];
-                residual_pixels<WW, WH, 1, 0, true>(T, ldsJ, jb, (uint32_t)uni((int)pack_weights_lo(we)),
-                                                    (uint32_t)uni((int)pack_weights_hi(we)), joff_l, len_l, es, unused);
+                residual_pixels<WW, WH, 1, 0, true>(T, ldsJ, jb, (uint32_t)uni((int)we0),
+                                                    (uint32_t)uni((int)we1), joff_l, len_l, es, unused);
             } else
-            residual_pixels<WW, WH, 1, 0, true>(T, ldsJ, jb, (uint32_t)uni((int)pack_weights_lo(we)),
-                                                (uint32_t)uni((int)pack_weights_hi(we)), joff, tlen, es, unused);
+            residual_pixels<WW, WH, 1, 0, true>(T, ldsJ, jb, (uint32_t)uni((int)we0),
+                                                (uint32_t)uni((int)we1), joff, tlen, es, unused);
             const float errval = sum_to_float(sum_pick<kSmall, 8>(es));
             Rz.err = __fdiv_rn(__fmul_rn(errval, 1.f), (float)(32 * WW * WH));
         }
@@ -508,8 +520,12 @@ template <int WW, int WH, bool FB, bool SM = false>
 __device__ __forceinline__ void lk_fast_body(const LKJobs& JJ, const LKParams& P)
 {
     using C = Cfg<WW, WH>;
-    __shared__ uint32_t lds[C::LDS_DW];
-    __shared__ uint4 tlds[SM ? 1 : TmplIO<WW, WH>::LDS_Q];   // landing area of one level's stored template
+    // One array: the search tile first, then the template source patch and the landing area of one level's stored template.
+    // The search tile then starts at LDS address 0, and the reads of an iteration (at most 2 * JPD + 2 dwords past the
+    // lane's first one) take their offsets from the instructions' own offset fields instead of three vector adds.
+    constexpr int kTileQ = (C::LDS_DW + 3) / 4;
+    __shared__ uint4 lds_q[kTileQ + (SM ? 1 : TmplIO<WW, WH>::LDS_Q)];
+    uint4* const tlds = lds_q + kTileQ;
     __shared__ float fs_[SM ? 3 * WW * WH : 1];              // "lk_sums" variants: the pixels' products, three planes
     float* const fsum = SM ? fs_ : nullptr;
     int which = 0, b = blockIdx.x;
@@ -543,8 +559,8 @@ __device__ __forceinline__ void lk_fast_body(const LKJobs& JJ, const LKParams& P
     if (f < 0) return;
     if (B.seg_alive && !B.seg_alive[f]) return;
     const int lane = threadIdx.x;
-    uint32_t* ldsI = lds;
-    uint32_t* ldsJ = lds + C::I_DW;
+    uint32_t* ldsJ = reinterpret_cast<uint32_t*>(lds_q);
+    uint32_t* ldsI = ldsJ + C::J_DW;
     const float p0x = B.p_in[2 * f], p0y = B.p_in[2 * f + 1];
     if (lane == 0) stamp(B, 0);
     using IO = TmplIO<WW, WH>;

@@ -282,7 +282,7 @@ __device__ __forceinline__ void track_multi(const Pyramid& PI, const Pyramid& PJ
                 __syncthreads();
             }
             const Weights wj = bilinear_weights(nx - (float)inx, ny - (float)iny);
-            const uint32_t V0u = pack_weights_lo(wj), V1u = pack_weights_hi(wj);
+            const uint32_t V0u = pack_weights_c0(wj), V1u = pack_weights_c1(wj);
             const int jb = (iny - jy0) * (C::JPD * 4) + (jx0 & 3) + (inx - jx0);
 
             // pixel phases
@@ -351,7 +351,7 @@ __device__ __forceinline__ void track_multi(const Pyramid& PI, const Pyramid& PJ
                     __syncthreads();
                 }
                 const Weights we = bilinear_weights(qx - (float)iqx, qy - (float)iqy);
-                const uint32_t V0u = pack_weights_lo(we), V1u = pack_weights_hi(we);
+                const uint32_t V0u = pack_weights_c0(we), V1u = pack_weights_c1(we);
                 const int jb = (iqy - jy0) * (C::JPD * 4) + (jx0 & 3) + (iqx - jx0);
                 static_for<F>([&](auto ff) {
                     constexpr int f = ff, o = f * LPF;

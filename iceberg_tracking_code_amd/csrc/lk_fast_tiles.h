@@ -174,6 +174,15 @@ __device__ __forceinline__ v2s byte_pair(const uint32_t (&X)[NX])
     else return as_v2s(__builtin_amdgcn_perm(X[i + 1 < NX ? i + 1 : i], X[i], 0x0c040c03u));
 }
 
+// byte M of two streams as a pair of 16-bit lanes: (byte M of X0) | (byte M of X1) << 16 -- one column of two rows
+template <int M, int NX>
+__device__ __forceinline__ v2s col_pair(const uint32_t (&X0)[NX], const uint32_t (&X1)[NX])
+{
+    constexpr int i = M / 4, r = M % 4;
+    static_assert(i < NX, "column outside the loaded dwords");
+    return as_v2s(__builtin_amdgcn_perm(X1[i], X0[i], 0x0c000c00u | ((4u + r) << 16) | (uint32_t)r));
+}
+
 // (a.y, b.x): the pair one 16-bit lane further along
 __device__ __forceinline__ v2s pair_shift(v2s a, v2s b)
 {
@@ -191,9 +200,37 @@ __device__ __forceinline__ void static_for(F&& f)
     }
 }
 
-// packed weight pairs (w00 | w01 << 16), (w10 | w11 << 16) for v_dot2_i32_i16
+// packed weight pairs (w00 | w01 << 16), (w10 | w11 << 16) for v_dot2_i32_i16 against row pairs (template_pixels)
 __device__ __forceinline__ uint32_t pack_weights_lo(const Weights& w) { return ((uint32_t)w.w00 & 0xffffu) | ((uint32_t)w.w01 << 16); }
 __device__ __forceinline__ uint32_t pack_weights_hi(const Weights& w) { return ((uint32_t)w.w10 & 0xffffu) | ((uint32_t)w.w11 << 16); }
+// the same weights by column, (w00 | w10 << 16), (w01 | w11 << 16), against column pairs (residual_pixels)
+__device__ __forceinline__ uint32_t pack_weights_c0(const Weights& w) { return ((uint32_t)w.w00 & 0xffffu) | ((uint32_t)w.w10 << 16); }
+__device__ __forceinline__ uint32_t pack_weights_c1(const Weights& w) { return ((uint32_t)w.w01 & 0xffffu) | ((uint32_t)w.w11 << 16); }
+
+// bilinear_weights' four values, bit for bit, already packed: the x / y float work two to an instruction (v_pk_*_f32), and
+// cvRound as one addition of 1.5 * 2^23: for 0 <= v < 2^22 the sum rounds v to the nearest integer, ties to even (the
+// constant is even), and its low 22 bits are that integer.  BY_COLUMN: pack_weights_c0 / _c1, else pack_weights_lo / _hi.
+template <bool BY_COLUMN>
+__device__ __forceinline__ void packed_weights(float a, float b, uint32_t& p0, uint32_t& p1)
+{
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    constexpr float kMagic = 12582912.f;                       // 1.5 * 2^23, bit pattern 0x4b400000
+    constexpr uint32_t kMagicBits = 0x4b400000u;
+    const f2 f = {a, b};
+    const f2 g = 1.f - f;                                      // (1 - a, 1 - b)
+    const f2 fg = f * g.yx;                                    // (a * (1 - b), b * (1 - a))
+    const f2 r = fg * (float)(1 << W_BITS) + kMagic;           // two roundings, as written: -ffp-contract=off
+    const float r00 = (g.x * g.y) * (float)(1 << W_BITS) + kMagic;
+    const uint32_t x00 = __float_as_uint(r00), x01 = __float_as_uint(r.x), x10 = __float_as_uint(r.y);
+    const uint32_t x11 = 3u * kMagicBits + (1u << W_BITS) - x00 - x01 - x10;   // low 16 bits: w11 = 2^14 - w00 - w01 - w10
+    if (BY_COLUMN) {
+        p0 = __builtin_amdgcn_perm(x10, x00, 0x05040100u);
+        p1 = __builtin_amdgcn_perm(x11, x01, 0x05040100u);
+    } else {
+        p0 = __builtin_amdgcn_perm(x01, x00, 0x05040100u);
+        p1 = __builtin_amdgcn_perm(x11, x10, 0x05040100u);
+    }
+}
 
 // ---- pixel work shared by the one-feature-per-wave and the several-features-per-wave kernels ---------------------------
 // The template of a feature: I as a dot2 accumulator seed, Ix / Iy as packed 16-bit pairs of neighbouring pixels.
@@ -350,6 +387,9 @@ __device__ __forceinline__ void template_pixels(Template<WW, WH, F>& T, const ui
 
 // ---- pixel phase: residual of ONE feature at the window origin encoded in `jb` ------------------------------------
 // jb = byte offset of the window's first pixel inside the feature's staged search tile (wave-uniform).
+// V0u, V1u = the weights by column (pack_weights_c0 / _c1).  A sample is taken from the COLUMN pairs (J[y][x], J[y+1][x])
+// and (J[y][x+1], J[y+1][x+1]): neighbouring samples share one, so S + 1 v_perm widen a segment's two rows instead of the
+// 2 S of row pairs.  The four products and the seed are added in another order, exactly (32-bit integers, no overflow).
 // ERR = false: b1 = sum diff*Ix, b2 = sum diff*Iy.   ERR = true: b1 = sum |diff| over the real window pixels.
 // fsum != nullptr: the two products of every window pixel also go to LDS as floats (int32 -> float, as _mm_cvtepi32_ps),
 // in raster order (trow, tcol = the segments' window rows / first columns).
@@ -374,7 +414,7 @@ __device__ __forceinline__ void residual_pixels(const Template<WW, WH, F>& T, co
         static_for<S>([&](auto qq) {
             constexpr int q = qq;
             // ((J bilinear + 256) >> 9) - I, with 256 - (I << 9) as the accumulator seed
-            diff[q] = dot2(byte_pair<q, NXJ>(Y1), as_v2s(V1v), dot2_vsv(byte_pair<q, NXJ>(Y0), V0u, T.Ineg[FI][k][q])) >>
+            diff[q] = dot2(col_pair<q + 1, NXJ>(Y0, Y1), as_v2s(V1v), dot2_vsv(col_pair<q, NXJ>(Y0, Y1), V0u, T.Ineg[FI][k][q])) >>
                       (W_BITS - 5);
         });
         if constexpr (ERR) {
