@@ -29,8 +29,9 @@ namespace {
 using namespace lk;
 using namespace lkf;
 
-// exact int64 -> float for |t| < 2^47: float(t >> 16) * 65536 and float(t & 0xffff) are exact, so the one rounding of
-// their sum is the rounding of t itself (what the oracle's (float)int64 does) -- no double precision involved
+// exact int64 -> float for |t| < 2^40: float(t >> 16) * 65536 and float(t & 0xffff) are exact (t >> 16 fits float's 24
+// bits), so the one rounding of their sum is the rounding of t itself (what the oracle's (float)int64 does) -- no double
+// precision involved.  The largest sum here is 35 * 35 * 8 160 * 4 080 < 2^36 (tests/test_lk_limits.py)
 __device__ __forceinline__ float sum_to_float(long long t)
 {
     const int hi = (int)(t >> 16), lo = (int)(t & 0xffff);
