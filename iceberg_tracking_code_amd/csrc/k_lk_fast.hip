@@ -46,6 +46,15 @@ __device__ __forceinline__ int floor_uni(float x)
     asm volatile("" : "+v"(i));
     return uni(i);
 }
+// ... and floorf(x) itself, for the fraction x - fx of the bilinear weights: where the origin test has passed, the floor is a
+// small integer and x - fx is x - (float)floor_uni(x) without the conversion back (two vector instructions per origin)
+__device__ __forceinline__ int floor_uni(float x, float& fx)
+{
+    fx = floorf(x);
+    int i = (int)fx;
+    asm volatile("" : "+v"(i));
+    return uni(i);
+}
 
 // A template as it travels from the backward pass of one pair to the forward pass of the next (LKBuffers::tmpl_out):
 // the lane's registers, flattened to dwords -- Ineg, then the packed gradient pairs -- in 16-byte pieces.
@@ -246,7 +255,7 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
 
     // this lane's row segments
     int trow[C::TPL], tcol[C::TPL], tlen[C::TPL], joff[C::TPL];
-    uint32_t pmask[C::TPL][(S + 1) / 2];   // which of a segment's pixels belong to the window (packed gradient pairs)
+    uint32_t psel[C::TPL][(S + 1) / 2];    // which of a segment's pixels belong to the window (pair_sel of its gradient pairs)
 #pragma unroll
     for (int k = 0; k < C::TPL; k++) {
         const int t = lane + 64 * k;
@@ -258,7 +267,7 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
         joff[k] = row * C::JPD * 4 + tcol[k];
 #pragma unroll
         for (int q = 0; q < (S + 1) / 2; q++)
-            pmask[k][q] = (2 * q < tlen[k] ? 0xffffu : 0u) | (2 * q + 1 < tlen[k] ? 0xffff0000u : 0u);
+            psel[k][q] = pair_sel(q, tlen[k]);
     }
 
     // The window with three segments per lane (35x35) keeps ONE register per segment -- row | column << 8 | pixels
@@ -290,26 +299,30 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
     float sx = 0.f, sy = 0.f;  // the stored nextPts value
     Template<WW, WH, 1> T;
 
-    for (int level = P.top_level; level >= 0; level--) {
+    // 1.f / (float)(1 << level), which is exactly 2^-level, carried from level to level as its bit pattern: one scalar
+    // addition per level pass, where the division took a dozen vector instructions
+    for (int level = P.top_level, scale_bits = __float_as_int(inv_pow2(P.top_level)); level >= 0;
+         level--, scale_bits += 1 << 23) {
         const Level LI = PI.lv[level];
         const Level LJ = PJ.lv[level];
-        const float scale = 1.f / (float)(1 << level);
+        const float scale = __int_as_float(scale_bits);
         float px = p0x * scale, py = p0y * scale;
         if (level == P.top_level) { sx = px; sy = py; }
         else { sx = sx * 2.f; sy = sy * 2.f; }
         px -= half_x; py -= half_y;
-        const int ipx = floor_uni(px), ipy = floor_uni(py);
+        float fpx, fpy;
+        const int ipx = floor_uni(px, fpx), ipy = floor_uni(py, fpy);
         if (!origin_ok<WW, WH>(LI, ipx, ipy)) {
             if (level == 0) { Rz.status = 0; Rz.err = 0.f; }
             continue;
         }
         uint32_t wi0, wi1;
-        packed_weights<false>(px - (float)ipx, py - (float)ipy, wi0, wi1);
+        packed_weights<false>(px - fpx, py - fpy, wi0, wi1);
 
         // ---- stage the template source patch and (speculatively) the first search tile ---------------
         float nx = sx - half_x, ny = sy - half_y;
-        int jx0 = 0, jy0 = 0;
-        bool staged = false;
+        // origin of the search tile in LDS; kUnstaged: none yet (tile_covers fails for every window origin)
+        int jx0 = kUnstaged, jy0 = kUnstaged;
         const int ix0 = ipx - 1, iy0 = ipy - 1;
         const bool i_inside = tile_inside(LI, ix0, iy0, C::ITW, C::ITH);
         {
@@ -330,7 +343,7 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
             else if (j_ok) tile_issue_reflect(tj, LJ, tjx, tjy, lane);
             if (!reuse) tile_commit(ti, ldsI, lane);
             if (j_ok) tile_commit(tj, ldsJ, lane);
-            if (j_ok) { jx0 = tjx; jy0 = tjy; staged = true; }
+            if (j_ok) { jx0 = tjx; jy0 = tjy; }
             __syncthreads();
         }
 
@@ -349,21 +362,22 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
             int a11, a12, a22;
             if constexpr (kPackSeg) {
                 int row_l[C::TPL], col_l[C::TPL], len_l[C::TPL];
-                uint32_t pmask_l[C::TPL][(S + 1) / 2];
+                uint32_t psel_l[C::TPL][(S + 1) / 2];
                 seg_rows_cols(row_l, col_l, len_l);
 #pragma unroll
                 for (int k = 0; k < C::TPL; k++)
 #pragma unroll
                     for (int q = 0; q < (S + 1) / 2; q++)
-                        pmask_l[k][q] = (2 * q < len_l[k] ? 0xffffu : 0u) | (2 * q + 1 < len_l[k] ? 0xffff0000u : 0u);
+                        psel_l[k][q] = pair_sel(q, len_l[k]);
                 template_pixels<WW, WH, 1, 0>(T, ldsI, (uint32_t)uni((int)wi0), (uint32_t)uni((int)wi1),
-                                              ix0 & 3, i_inside, ipx, ipy, LI.w, LI.h, row_l, col_l, pmask_l, a11, a12, a22, fsum, len_l);
+                                              ix0 & 3, i_inside, ipx, ipy, LI.w, LI.h, row_l, col_l, psel_l, a11, a12, a22, fsum, len_l);
             } else
             template_pixels<WW, WH, 1, 0>(T, ldsI, (uint32_t)uni((int)wi0), (uint32_t)uni((int)wi1),
-                                          ix0 & 3, i_inside, ipx, ipy, LI.w, LI.h, trow, tcol, pmask, a11, a12, a22, fsum, tlen);
+                                          ix0 & 3, i_inside, ipx, ipy, LI.w, LI.h, trow, tcol, psel, a11, a12, a22, fsum, tlen);
             // |Ix*Ix| <= 4080^2 per pixel: 16-lane sums fit int32 while a lane holds <= 8 pixels
             long long s11, s12, s22;
-            wave_sum3_i64<kSmall ? 16 : 1>(a11, a12, a22, s11, s12, s22);
+            if constexpr (kSmall) wave_sum_mat_i64(a11, a12, a22, s11, s12, s22);
+            else wave_sum3_i64<1>(a11, a12, a22, s11, s12, s22);
             A11 = sum_to_float(s11) * FLT_SCALE;
             A12 = sum_to_float(s12) * FLT_SCALE;
             A22 = sum_to_float(s22) * FLT_SCALE;
@@ -382,8 +396,9 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
         // The exact (correctly rounded sqrt and divide) minEig is only needed when it is reported or close
         // to the threshold: the hardware-approximate value differs from it by a few ulp of `tr` / (2wh).
         const float approx = (tr - __builtin_amdgcn_sqrtf(rad)) * (1.f / (float)(2 * WW * WH));
-        const bool clear_pass = approx > P.min_eig_thr + tr * 2e-6f && !(P.flags & ICELK_FLAG_MIN_EIGENVALS);
-        if (!uni(clear_pass)) {
+        const bool clear_pass = __builtin_amdgcn_ballot_w64(approx > P.min_eig_thr + tr * 2e-6f) != 0 &&
+                                !(P.flags & ICELK_FLAG_MIN_EIGENVALS);
+        if (!clear_pass) {
             const float minEig = __fdiv_rn(__fsub_rn(tr, sqrtf(rad)), (float)(2 * WW * WH));
             if (P.flags & ICELK_FLAG_MIN_EIGENVALS) Rz.err = minEig;
             if (minEig < P.min_eig_thr) {
@@ -398,26 +413,31 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
         D = __fdiv_rn(1.f, D);
 
         // ---- iterations ---------------------------------------------------------------------------
-        float pdx = 0.f, pdy = 0.f;
+        // the previous step; NaN before the first one, so that the oscillation test below fails without a test of j
+        float pdx = __builtin_nanf(""), pdy = __builtin_nanf("");
         for (int j = 0; j < P.max_count; j++) {
-            const int inx = floor_uni(nx), iny = floor_uni(ny);
+            float fnx, fny;
+            const int inx = floor_uni(nx, fnx), iny = floor_uni(ny, fny);
             if (!origin_ok<WW, WH>(LJ, inx, iny)) {
                 if (level == 0) Rz.status = 0;
                 break;
             }
-            if (!staged || !tile_covers(jx0, jy0, inx, iny)) {
+            if (!tile_covers(jx0, jy0, inx, iny)) {
                 jx0 = inx - R; jy0 = iny - R;
                 __syncthreads();
                 TileRegs<C::JPD, C::JTH> tj;
-                if (tile_inside(LJ, jx0, jy0, C::JTW, C::JTH)) tile_issue(tj, LJ, jx0, jy0, lane);
-                else tile_issue_reflect(tj, LJ, jx0, jy0, lane);
+                // the level's pitch as an opaque value here: otherwise the loads' per-lane offsets (row * pitch + 4 c) are
+                // hoisted into every level pass, while a restage inside the iterations is the exception
+                Level LR = LJ;
+                asm volatile("" : "+s"(LR.pitch));
+                if (tile_inside(LR, jx0, jy0, C::JTW, C::JTH)) tile_issue(tj, LR, jx0, jy0, lane);
+                else tile_issue_reflect(tj, LR, jx0, jy0, lane);
                 tile_commit(tj, ldsJ, lane);
                 __syncthreads();
-                staged = true;
             }
             Rz.iters++;
             uint32_t wj0, wj1;
-            packed_weights<true>(nx - (float)inx, ny - (float)iny, wj0, wj1);
+            packed_weights<true>(nx - fnx, ny - fny, wj0, wj1);
             const int jb = uni((iny - jy0) * (C::JPD * 4) + (jx0 & 3) + (inx - jx0));
             int b1, b2;
             if constexpr (kPackSeg) {
@@ -449,15 +469,16 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
             // eps^2 (LKParams::eps2_lo / eps2_hi), where the exact form runs
             const float q = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
             bool conv = q < P.eps2_lo;
-            if (uni(!conv && !(q > P.eps2_hi) ? 1 : 0)) {
+            if (__builtin_amdgcn_ballot_w64(!conv && !(q > P.eps2_hi)) != 0) {
                 // a real branch (the values are wave-uniform): flattened, the six double-precision instructions of the exact
-                // form ran in every iteration of every feature for a band that is 2^-19 wide
+                // form ran in every iteration of every feature for a band that is 2^-19 wide.  The ballot's compare mask
+                // decides on the scalar unit; a readfirstlane of the condition cost a v_cndmask and the readlane per iteration
                 asm volatile("" ::: "memory");
                 conv = __dadd_rn(__dmul_rn((double)dx, (double)dx), __dmul_rn((double)dy, (double)dy)) <= P.eps2;
             }
             if (conv) break;
             // fabs((double)t) < 0.01 for a float t  <=>  |t| <= 0.01f, the largest float below 0.01
-            if (j > 0 && fabsf(__fadd_rn(dx, pdx)) <= 0.01f && fabsf(__fadd_rn(dy, pdy)) <= 0.01f) {
+            if (fabsf(__fadd_rn(dx, pdx)) <= 0.01f && fabsf(__fadd_rn(dy, pdy)) <= 0.01f) {
                 sx = __fsub_rn(sx, __fmul_rn(dx, 0.5f));
                 sy = __fsub_rn(sy, __fmul_rn(dy, 0.5f));
                 break;
@@ -476,7 +497,7 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
             // the mean absolute residual itself is only formed for a caller that takes it (the segment loop does not:
             // s1:323 drops `err`): one more search-tile check, 7 bilinear samples per lane and a wave sum saved
             if (!want_err) continue;
-            if (!staged || !tile_covers(jx0, jy0, iqx, iqy)) {
+            if (!tile_covers(jx0, jy0, iqx, iqy)) {
                 jx0 = iqx - R; jy0 = iqy - R;
                 __syncthreads();
                 TileRegs<C::JPD, C::JTH> tj;
@@ -484,7 +505,6 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
                 else tile_issue_reflect(tj, LJ, jx0, jy0, lane);
                 tile_commit(tj, ldsJ, lane);
                 __syncthreads();
-                staged = true;
             }
             uint32_t we0, we1;
             packed_weights<true>(qx - (float)iqx, qy - (float)iqy, we0, we1);

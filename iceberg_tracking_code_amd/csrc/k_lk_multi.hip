@@ -141,13 +141,13 @@ __device__ __forceinline__ void track_multi(const Pyramid& PI, const Pyramid& PJ
         tlen[k] = used ? (WW - tcol[k] < S ? WW - tcol[k] : S) : 0;
         joff[k] = row * C::JPD * 4 + tcol[k];
     }
-    // which of a segment's pixels belong to the window, as masks over the packed gradient pairs
-    uint32_t pmask[C::TPL][(S + 1) / 2];
+    // which of a segment's pixels belong to the window, as pair selectors (pair_sel) of the packed gradient pairs
+    uint32_t psel[C::TPL][(S + 1) / 2];
 #pragma unroll
     for (int k = 0; k < C::TPL; k++)
 #pragma unroll
         for (int q = 0; q < (S + 1) / 2; q++)
-            pmask[k][q] = (2 * q < tlen[k] ? 0xffffu : 0u) | (2 * q + 1 < tlen[k] ? 0xffff0000u : 0u);
+            psel[k][q] = pair_sel(q, tlen[k]);
 
     St.status = 1;
     St.err = 0.f;
@@ -229,7 +229,7 @@ __device__ __forceinline__ void track_multi(const Pyramid& PI, const Pyramid& PJ
             if ((m_lvl >> o) & 1) {
                 int a11, a12, a22;
                 template_pixels<WW, WH, F, f>(T, lds + f * M::TILE_DW, rlu(W0u, o), rlu(W1u, o), rl(ix0, o) & 3,
-                                              (m_iin >> o) & 1, rl(ipx, o), rl(ipy, o), LI.w, LI.h, trow, tcol, pmask, a11,
+                                              (m_iin >> o) & 1, rl(ipx, o), rl(ipy, o), LI.w, LI.h, trow, tcol, psel, a11,
                                               a12, a22);
                 sums[0 * F * 64 + f * 64 + lane] = (uint32_t)a11;
                 sums[1 * F * 64 + f * 64 + lane] = (uint32_t)a12;

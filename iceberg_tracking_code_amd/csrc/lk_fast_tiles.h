@@ -139,7 +139,9 @@ __device__ __forceinline__ bool origin_ok(const Level& L, int x, int y)
     return (unsigned)(x + WW) < (unsigned)(L.w + WW) && (unsigned)(y + WH) < (unsigned)(L.h + WH);
 }
 
-// the staged search tile (origin jx0, jy0, margin R on every side) still covers a window at (x, y)
+// the staged search tile (origin jx0, jy0, margin R on every side) still covers a window at (x, y); an origin of kUnstaged
+// (no tile staged) covers none
+constexpr int kUnstaged = -(1 << 29);
 __device__ __forceinline__ bool tile_covers(int jx0, int jy0, int x, int y)
 {
     return (unsigned)(x - jx0) <= 2u * kMargin && (unsigned)(y - jy0) <= 2u * kMargin;
@@ -247,6 +249,15 @@ __device__ __forceinline__ uint32_t pack16(int lo, int hi)
     return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u);
 }
 
+// v_perm selector that packs the HIGH 16-bit halves of two dwords, perm(hi, lo, sel) = (lo >> 16) | (hi >> 16) << 16, and
+// clears the halves of pixels a segment of `len` pixels does not have (selector byte 0x0c gives 0x00).  Pixel pair q of the
+// segment: template_pixels takes the derivative samples' rounding shift, their packing and the window mask in this one
+// instruction.
+__device__ __forceinline__ uint32_t pair_sel(int q, int len)
+{
+    return (2 * q < len ? 0x0302u : 0x0c0cu) | (2 * q + 1 < len ? 0x07060000u : 0x0c0c0000u);
+}
+
 // v_dot2_i32_i16 in its three-address (VOP3P) form.  The compiler only ever selects the two-address v_dot2c, which
 // overwrites its accumulator: with a seed that is needed again (the template value of the residual, a rounding
 // constant) that costs a v_mov per dot product.  b and c may be scalars (weights, constants): at most one of them is.
@@ -262,9 +273,17 @@ __device__ __forceinline__ int dot2_vvs(v2s a, uint32_t b, int c_scalar)
     asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(as_u32(a)), "v"(b), "s"(c_scalar));
     return d;
 }
+// the first term of a sum: accumulator 0 as an inline constant, not a v_mov of a zero register in front of v_dot2c
+__device__ __forceinline__ int dot2_vv0(v2s a, v2s b)
+{
+    int d;
+    asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(d) : "v"(as_u32(a)), "v"(as_u32(b)));
+    return d;
+}
 
 // ---- pixel phase: template of ONE feature -------------------------------------------------------------------
 // Everything that is the same for all lanes arrives as a scalar (readlane of the owning block's registers).
+// psel: the lane's pair selectors (pair_sel of each segment's pixel pairs and its pixel count in the window).
 // fsum != nullptr (the "lk_sums" variants, LKParams::sum_mode): every window pixel's three products also go to LDS as
 // floats, in raster order, for the lane-ordered float sums of chain_sums (k_lk_fast.hip); tlen = pixels of each segment
 // that lie inside the window.
@@ -272,25 +291,37 @@ template <int WW, int WH, int F, int FI>
 __device__ __forceinline__ void template_pixels(Template<WW, WH, F>& T, const uint32_t* ldsI, uint32_t W0u, uint32_t W1u, int ics,
                                                 bool i_inside, int ipx, int ipy, int liw, int lih,
                                                 const int (&trow)[Cfg<WW, WH>::TPL], const int (&tcol)[Cfg<WW, WH>::TPL],
-                                                const uint32_t (&pmask)[Cfg<WW, WH>::TPL][(Cfg<WW, WH>::S + 1) / 2], int& a11,
+                                                const uint32_t (&psel)[Cfg<WW, WH>::TPL][(Cfg<WW, WH>::S + 1) / 2], int& a11,
                                                 int& a12, int& a22, float* fsum = nullptr, const int* tlen = nullptr)
 {
     using C = Cfg<WW, WH>;
     constexpr int S = C::S;
-    // the second weight pair as a VGPR (a three-address dot2 takes one scalar), the rounding constants as scalars
+    // the second weight pair as a VGPR (a three-address dot2 takes one scalar), the rounding constants as scalars.
+    // The derivatives are formed 4 times too large (|4 Ix| <= 16 320 still fits a 16-bit lane), so that
+    // (4 dx * w + 2^15) >> 16 == (dx * w + 2^13) >> 14 lands in the high half of the dot2 result: one v_perm then
+    // shifts, packs and masks a pixel pair (pair_sel) where two shifts, a pack and a mask AND were needed.
     const uint32_t W1v = W1u;
-    const int kRoundI = 1 << (W_BITS - 6), kRoundD = 1 << (W_BITS - 1);
-    a11 = 0; a12 = 0; a22 = 0;
+    const int kRoundI = 1 << (W_BITS - 6), kRoundD4 = 1 << (W_BITS + 1);
 #pragma unroll
     for (int k = 0; k < C::TPL; k++) {
         constexpr int NP = (S + 4) / 2;   // even-aligned column pairs covering columns 0 .. S+2
         constexpr int ND = (S + 2) / 2;   // derivative pairs covering derivative columns 0 .. S
+        // The pairs come straight out of the dwords as they lie in LDS: pair kk is bytes 2 kk + sh, 2 kk + sh + 1 of the
+        // row, i.e. of the dword pair (d[kk / 2], d[kk / 2 + 1]) at a byte offset below 7, so one v_perm with a per-lane
+        // selector takes them out (no v_alignbyte realignment of the row first)
+        const int off = ics + tcol[k], sh = off & 3;
+        const uint32_t selA = 0x0c010c00u + (uint32_t)sh * 0x00010001u;   // bytes sh, sh + 1 of the pair -> 16-bit lanes
+        const uint32_t selB = selA + 0x00020002u;                          // bytes sh + 2, sh + 3
         v2s E[4][NP];
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-            uint32_t X[3];
-            row_dwords<3>(ldsI + (trow[k] + r) * C::IPD, ics + tcol[k], X);
-            static_for<NP>([&](auto kk) { E[r][kk] = byte_pair<2 * kk, 3>(X); });
+            const uint32_t* p = ldsI + (trow[k] + r) * C::IPD + (off >> 2);
+            uint32_t d[(NP - 1) / 2 + 2];
+#pragma unroll
+            for (int i = 0; i < (NP - 1) / 2 + 2; i++) d[i] = p[i];
+            static_for<NP>([&](auto kk) {
+                E[r][kk] = as_v2s(__builtin_amdgcn_perm(d[kk / 2 + 1], d[kk / 2], kk % 2 ? selB : selA));
+            });
         }
         // I samples first (they need source rows 1 and 2 only): columns (j+1, j+2) are the pair E[.][(j+1)/2] for odd j
         // and the pair one 16-bit lane further along for even j
@@ -305,24 +336,28 @@ __device__ __forceinline__ void template_pixels(Template<WW, WH, F>& T, const ui
             const int iv = dot2(s2, as_v2s(W1v), dot2_vvs(s1, W0u, kRoundI)) >> (W_BITS - 5);
             T.Ineg[FI][k][j] = (1 << (W_BITS - 6)) - (iv << (W_BITS - 5));
         });
-        // Scharr, two columns per instruction: t0 = 3*(a + c) + 10*b, t1 = c - a down the rows, then
-        // dx = t0[i+2] - t0[i], dy = 3*(t1[i+2] + t1[i]) + 10*t1[i+1] along the row
+        // Scharr x 4, two columns per instruction: t0 = 12*(a + c) + 40*b, t1 = c - a down the rows, then
+        // dx = t0[i+2] - t0[i], dy = 12*(t1[i+2] + t1[i]) + 40*t1[i+1] along the row
         v2s dxp[2][ND], dyp[2][ND];
 #pragma unroll
         for (int r = 0; r < 2; r++) {
             v2s t0[NP], t1[NP];
 #pragma unroll
             for (int q = 0; q < NP; q++) {
-                t0[q] = (E[r][q] + E[r + 2][q]) * (short)3 + E[r + 1][q] * (short)10;
+                t0[q] = (E[r][q] + E[r + 2][q]) * (short)12 + E[r + 1][q] * (short)40;
                 t1[q] = E[r + 2][q] - E[r][q];
             }
 #pragma unroll
             for (int d = 0; d < ND; d++) {
                 dxp[r][d] = t0[d + 1] - t0[d];
-                dyp[r][d] = (t1[d + 1] + t1[d]) * (short)3 + pair_shift(t1[d], t1[d + 1]) * (short)10;
+                dyp[r][d] = (t1[d + 1] + t1[d]) * (short)12 + pair_shift(t1[d], t1[d + 1]) * (short)40;
             }
-            if (!i_inside) {
-                // derivative image is zero outside the frame (BORDER_CONSTANT), SURVEY.md A.4
+        }
+        if (!i_inside) {
+            // derivative image is zero outside the frame (BORDER_CONSTANT), SURVEY.md A.4.  Both derivative rows under one
+            // branch: with a branch per row the compiler hoisted their shared column tests into the interior path.
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
                 const int gy = ipy + trow[k] + r;
                 const bool row_in = gy >= 0 && gy < lih;
 #pragma unroll
@@ -335,10 +370,11 @@ __device__ __forceinline__ void template_pixels(Template<WW, WH, F>& T, const ui
                 }
             }
         }
-        int ixs[S], iys[S];
+        // derivative samples, x 2^16: the sample itself is the high half
+        int ixw[S], iyw[S];
         static_for<S>([&](auto jj) {
             constexpr int j = jj;
-            // derivative samples: derivative columns (j, j+1) of derivative rows 0 and 1
+            // derivative columns (j, j+1) of derivative rows 0 and 1
             v2s gx0, gx1, gy0, gy1;
             if constexpr (j % 2 == 0) {
                 gx0 = dxp[0][j / 2]; gx1 = dxp[1][j / 2]; gy0 = dyp[0][j / 2]; gy1 = dyp[1][j / 2];
@@ -346,8 +382,8 @@ __device__ __forceinline__ void template_pixels(Template<WW, WH, F>& T, const ui
                 gx0 = pair_shift(dxp[0][j / 2], dxp[0][j / 2 + 1]); gx1 = pair_shift(dxp[1][j / 2], dxp[1][j / 2 + 1]);
                 gy0 = pair_shift(dyp[0][j / 2], dyp[0][j / 2 + 1]); gy1 = pair_shift(dyp[1][j / 2], dyp[1][j / 2 + 1]);
             }
-            ixs[j] = dot2(gx1, as_v2s(W1v), dot2_vvs(gx0, W0u, kRoundD)) >> W_BITS;
-            iys[j] = dot2(gy1, as_v2s(W1v), dot2_vvs(gy0, W0u, kRoundD)) >> W_BITS;
+            ixw[j] = dot2(gx1, as_v2s(W1v), dot2_vvs(gx0, W0u, kRoundD4));
+            iyw[j] = dot2(gy1, as_v2s(W1v), dot2_vvs(gy0, W0u, kRoundD4));
         });
         if (fsum) {
             constexpr int NPX = WW * WH;
@@ -355,32 +391,31 @@ __device__ __forceinline__ void template_pixels(Template<WW, WH, F>& T, const ui
                 constexpr int j = jj;
                 if (j < tlen[k]) {
                     const int idx = trow[k] * WW + tcol[k] + j;
-                    fsum[idx] = (float)(ixs[j] * ixs[j]);
-                    fsum[NPX + idx] = (float)(ixs[j] * iys[j]);
-                    fsum[2 * NPX + idx] = (float)(iys[j] * iys[j]);
+                    const int ix = ixw[j] >> 16, iy = iyw[j] >> 16;
+                    fsum[idx] = (float)(ix * ix);
+                    fsum[NPX + idx] = (float)(ix * iy);
+                    fsum[2 * NPX + idx] = (float)(iy * iy);
                 }
             });
         }
         // gradient pairs for the dot2 form of the residual sums (pixels beyond the window's right edge and the
-        // surplus lanes' pixels are masked off here, once, with the lane's constant masks), and the 2x2 matrix sums on
+        // surplus lanes' pixels are cleared here, once, by the lane's pair selectors), and the 2x2 matrix sums on
         // the same pairs
         static_for<(S + 1) / 2>([&](auto qq) {
-            constexpr int q = qq;
-            uint32_t px2, py2;
-            if constexpr (2 * q + 1 < S) {
-                px2 = pack16(ixs[2 * q], ixs[2 * q + 1]);
-                py2 = pack16(iys[2 * q], iys[2 * q + 1]);
-            } else {
-                px2 = (uint32_t)ixs[2 * q];
-                py2 = (uint32_t)iys[2 * q];
-            }
-            px2 &= pmask[k][q];
-            py2 &= pmask[k][q];
+            constexpr int q = qq, q1 = 2 * q + 1 < S ? 2 * q + 1 : 2 * q;   // a lone last pixel: its partner half is cleared
+            const uint32_t px2 = __builtin_amdgcn_perm((uint32_t)ixw[q1], (uint32_t)ixw[2 * q], psel[k][q]);
+            const uint32_t py2 = __builtin_amdgcn_perm((uint32_t)iyw[q1], (uint32_t)iyw[2 * q], psel[k][q]);
             T.Ixp[FI][k][q] = px2;
             T.Iyp[FI][k][q] = py2;
-            a11 = dot2(as_v2s(px2), as_v2s(px2), a11);
-            a12 = dot2(as_v2s(px2), as_v2s(py2), a12);
-            a22 = dot2(as_v2s(py2), as_v2s(py2), a22);
+            if (k == 0 && q == 0) {
+                a11 = dot2_vv0(as_v2s(px2), as_v2s(px2));
+                a12 = dot2_vv0(as_v2s(px2), as_v2s(py2));
+                a22 = dot2_vv0(as_v2s(py2), as_v2s(py2));
+            } else {
+                a11 = dot2(as_v2s(px2), as_v2s(px2), a11);
+                a12 = dot2(as_v2s(px2), as_v2s(py2), a12);
+                a22 = dot2(as_v2s(py2), as_v2s(py2), a22);
+            }
         });
     }
 }
