@@ -2764,6 +2764,168 @@ int icelk_grid_bin(icelk_t* h, const double* x, const double* y, const double* u
     return ICELK_OK;
 }
 
+static double from_order_key(unsigned long long k)
+{
+    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double d;
+    memcpy(&d, &b, sizeof d);
+    return d;
+}
+
+int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                           const double* t, int n, const int64_t* file_offset, const int* file_cam, const int* win_f0,
+                           const int* win_f1, int nfiles, const int64_t* t_lo, const int64_t* t_hi, int ncam, int nw,
+                           double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
+                           int* count, double* mean_u, double* mean_v, double* speed, int* sel_count, double* t_min,
+                           double* t_max, double* device_ms)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n < 0 || nfiles < 1 || ncam < 1 || nw < 1 || cols <= 0 || rows <= 0 || !(spacing > 0) || !file_offset ||
+        !file_cam || !win_f0 || !win_f1 || !t_lo || !t_hi || !cell_on || !count || !mean_u || !mean_v || !speed ||
+        !sel_count || !t_min || !t_max || (n > 0 && (!x || !y || !u || !v || !t)))
+        FAIL(c, ICELK_EARG, "bad gridding arguments");
+    const long long ncells_ll = (long long)cols * rows;
+    // keys hold (window * ncells + cell) in their high 32 bits, the point index in the low 32; the key counter and
+    // the 2 n + 1024 key slots are int
+    if (ncells_ll > (1 << 24) || ncells_ll * nw > 0x7fffffffLL || n > (1 << 30))
+        FAIL(c, ICELK_ECAP, "grid x windows or point set too large");
+    if (file_offset[0] != 0 || file_offset[nfiles] != n) FAIL(c, ICELK_EARG, "file offsets must span 0 .. n");
+    for (int f = 0; f < nfiles; f++)
+        if (file_offset[f + 1] < file_offset[f] || file_cam[f] < 0 || file_cam[f] >= ncam ||
+            (f > 0 && file_cam[f] < file_cam[f - 1]))
+            FAIL(c, ICELK_EARG, "bad file table");
+    for (int k = 0; k < ncam; k++)
+        for (int w = 0; w < nw; w++) {
+            const size_t sl = (size_t)k * nw + w;
+            if (t_lo[sl] > t_hi[sl] || (w + 1 < nw && t_hi[sl] > t_lo[sl + 1]))
+                FAIL(c, ICELK_EARG, "window bounds must be ascending and disjoint per camera");
+            if (win_f0[sl] <= win_f1[sl] && (win_f0[sl] < 0 || win_f1[sl] >= nfiles || file_cam[win_f0[sl]] != k ||
+                                             file_cam[win_f1[sl]] != k))
+                FAIL(c, ICELK_EARG, "a window loads files of another camera");
+        }
+    const int ncells = (int)ncells_ll, nseg = ncells * nw, nslot = nw * ncam;
+    const int key_cap = (int)std::min<long long>(2LL * n + 1024, 0x7fffffffLL);
+    memset(count, 0, sizeof(int) * nseg);
+    memset(mean_u, 0, sizeof(double) * nseg);
+    memset(mean_v, 0, sizeof(double) * nseg);
+    memset(speed, 0, sizeof(double) * nseg);
+    memset(sel_count, 0, sizeof(int) * nslot);
+    memset(t_min, 0, sizeof(double) * nslot);
+    memset(t_max, 0, sizeof(double) * nslot);
+    if (device_ms) *device_ms = 0.0;
+    if (n == 0) return ICELK_OK;
+    DevBufs B;
+    const size_t nn = (size_t)n;
+    double* dx = B.get<double>(nn);
+    double* dy = B.get<double>(nn);
+    double* du = B.get<double>(nn);
+    double* dv = B.get<double>(nn);
+    double* dt = B.get<double>(nn);
+    long long* d_off = B.get<long long>((size_t)nfiles + 1);
+    int* d_fcam = B.get<int>((size_t)nfiles);
+    int* d_wf0 = B.get<int>((size_t)nslot);
+    int* d_wf1 = B.get<int>((size_t)nslot);
+    long long* d_lo = B.get<long long>((size_t)nslot);
+    long long* d_hi = B.get<long long>((size_t)nslot);
+    uint8_t* d_on = B.get<uint8_t>((size_t)ncells);
+    unsigned long long* keys = B.get<unsigned long long>((size_t)key_cap);
+    unsigned long long* keys_sorted = B.get<unsigned long long>((size_t)key_cap);
+    int* d_key_count = B.get<int>(1);
+    int* d_count = B.get<int>((size_t)nseg);
+    double* d_mu = B.get<double>((size_t)nseg);
+    double* d_mv = B.get<double>((size_t)nseg);
+    double* d_sp = B.get<double>((size_t)nseg);
+    int* d_sel = B.get<int>((size_t)nslot);
+    unsigned long long* d_tmin = B.get<unsigned long long>((size_t)nslot);
+    unsigned long long* d_tmax = B.get<unsigned long long>((size_t)nslot);
+    if (!dx || !dy || !du || !dv || !dt || !d_off || !d_fcam || !d_wf0 || !d_wf1 || !d_lo || !d_hi || !d_on || !keys ||
+        !keys_sorted || !d_key_count || !d_count || !d_mu || !d_mv || !d_sp || !d_sel || !d_tmin || !d_tmax)
+        FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    // the sort's scratch is sized for the worst case up front: no allocation between the timed kernels
+    int cell_bits = 1;
+    while ((1LL << cell_bits) < (long long)nseg) cell_bits++;
+    const size_t tmp_bytes = sort_keys_asc(c->stream, nullptr, 0, keys, keys_sorted, key_cap, 32 + cell_bits);
+    void* tmp = B.get<uint8_t>(tmp_bytes);
+    if (!tmp) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    const hipStream_t s = c->stream;
+    const size_t nb = sizeof(double) * nn;
+    HIPCHK(c, hipMemcpyAsync(dx, x, nb, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dy, y, nb, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(du, u, nb, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dv, v, nb, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dt, t, nb, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_off, file_offset, sizeof(long long) * ((size_t)nfiles + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_fcam, file_cam, sizeof(int) * nfiles, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_wf0, win_f0, sizeof(int) * nslot, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_wf1, win_f1, sizeof(int) * nslot, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_lo, t_lo, sizeof(long long) * nslot, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_hi, t_hi, sizeof(long long) * nslot, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_on, cell_on, ncells, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(d_key_count, 0, sizeof(int), s));
+    HIPCHK(c, hipMemsetAsync(d_sel, 0, sizeof(int) * nslot, s));
+    HIPCHK(c, hipMemsetAsync(d_tmin, 0xff, sizeof(unsigned long long) * nslot, s));
+    HIPCHK(c, hipMemsetAsync(d_tmax, 0, sizeof(unsigned long long) * nslot, s));
+    // device_ms: assign, then sort + reduce; the key-count read-back between them is not counted
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct EvFree {
+        hipEvent_t* e;
+        ~EvFree()
+        {
+            for (int k = 0; k < 4; k++)
+                if (e[k]) hipEventDestroy(e[k]);
+        }
+    } ev_free{ev};
+    if (device_ms) {
+        for (int k = 0; k < 4; k++) HIPCHK(c, hipEventCreate(&ev[k]));
+        HIPCHK(c, hipEventRecord(ev[0], s));
+    }
+    launch_grid_day_assign(s, dx, dy, dt, n, d_off, d_fcam, d_wf0, d_wf1, nfiles, d_lo, d_hi, ncam, nw, left, top,
+                           spacing, cols, rows, d_on, keys, d_key_count, key_cap, d_sel, d_tmin, d_tmax);
+    int rc = check_launch(c, "grid_day_assign");
+    if (rc) return rc;
+    if (device_ms) HIPCHK(c, hipEventRecord(ev[1], s));
+    // the sort takes the key count from the host, as in icelk_grid_bin
+    int total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, d_key_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (total > key_cap) FAIL(c, ICELK_ECAP, "more than two cells per point on average (all points on cell edges?)");
+    if (device_ms) HIPCHK(c, hipEventRecord(ev[2], s));
+    const unsigned long long* sorted = keys;
+    if (total > 1) {
+        sort_keys_asc(s, tmp, tmp_bytes, keys, keys_sorted, total, 32 + cell_bits);
+        rc = check_launch(c, "grid sort");
+        if (rc) return rc;
+        sorted = keys_sorted;
+    }
+    launch_grid_reduce(s, sorted, d_key_count, du, dv, nseg, d_count, d_mu, d_mv, d_sp);
+    rc = check_launch(c, "grid_reduce");
+    if (rc) return rc;
+    if (device_ms) HIPCHK(c, hipEventRecord(ev[3], s));
+    HIPCHK(c, hipMemcpyAsync(count, d_count, sizeof(int) * nseg, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(mean_u, d_mu, sizeof(double) * nseg, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(mean_v, d_mv, sizeof(double) * nseg, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(speed, d_sp, sizeof(double) * nseg, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(sel_count, d_sel, sizeof(int) * nslot, hipMemcpyDeviceToHost, s));
+    std::vector<unsigned long long> kmin(nslot), kmax(nslot);
+    HIPCHK(c, hipMemcpyAsync(kmin.data(), d_tmin, sizeof(unsigned long long) * nslot, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(kmax.data(), d_tmax, sizeof(unsigned long long) * nslot, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < nslot; k++)
+        if (sel_count[k] > 0) {
+            t_min[k] = from_order_key(kmin[k]);
+            t_max[k] = from_order_key(kmax[k]);
+        }
+    if (device_ms) {
+        float a = 0.0f, b = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&a, ev[0], ev[1]));
+        HIPCHK(c, hipEventElapsedTime(&b, ev[2], ev[3]));
+        *device_ms = (double)a + (double)b;
+    }
+    return ICELK_OK;
+}
+
 // which segment a read-out addresses: the current one, or the one closed by the latest switch
 static int seg_pick(Ctx* c, bool closed, int* set)
 {

@@ -273,6 +273,12 @@ void launch_project_tracks(hipStream_t s, const float* tracks, int n, int nv, co
 void launch_points_in_polygon(hipStream_t s, const double* poly, int n, const double* pts, int m, uint8_t* out);
 void launch_grid_assign(hipStream_t s, const double* x, const double* y, int n, double left, double top, double spacing,
                         int cols, int rows, const uint8_t* cell_on, unsigned long long* keys, int* key_count, int key_cap);
+void launch_grid_day_assign(hipStream_t s, const double* x, const double* y, const double* t, int n,
+                            const long long* file_off, const int* file_cam, const int* win_f0, const int* win_f1,
+                            int nfiles, const long long* t_lo, const long long* t_hi, int ncam, int nw, double left,
+                            double top, double spacing, int cols, int rows, const uint8_t* cell_on,
+                            unsigned long long* keys, int* key_count, int key_cap, int* sel_count,
+                            unsigned long long* t_min, unsigned long long* t_max);
 void launch_grid_reduce(hipStream_t s, const unsigned long long* keys, const int* key_count, const double* u,
                         const double* v, int ncells, int* count, double* mean_u, double* mean_v, double* speed);
 size_t sort_keys_asc(hipStream_t s, void* tmp, size_t tmp_bytes, const unsigned long long* in, unsigned long long* out,

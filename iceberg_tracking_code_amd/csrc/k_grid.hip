@@ -80,16 +80,13 @@ __device__ __forceinline__ unsigned hit_mask(const GridGeom& g, const uint8_t* _
     return m;
 }
 
-__global__ __launch_bounds__(256) void k_grid_assign(const double* __restrict__ x, const double* __restrict__ y, int n,
-                                                     GridGeom g, const uint8_t* __restrict__ cell_on,
-                                                     unsigned long long* __restrict__ keys, int* __restrict__ key_count,
-                                                     int key_cap)
+// writes the keys ((seg_base + cell) << 32) | p of the cells in hit mask m, one block-wide scan for the slots
+__device__ __forceinline__ void append_keys(unsigned m, int i0, int j0, unsigned seg_base, int rows, int p,
+                                            unsigned long long* __restrict__ keys, int* __restrict__ key_count,
+                                            int key_cap)
 {
     __shared__ int wave_tot[4];
     __shared__ int s_base;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    int i0 = 0, j0 = 0;
-    const unsigned m = p < n ? hit_mask(g, cell_on, x[p], y[p], &i0, &j0) : 0u;
     const int cnt = __popc(m);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int inc = cnt;
@@ -111,9 +108,106 @@ __global__ __launch_bounds__(256) void k_grid_assign(const double* __restrict__ 
     for (int k = 0; k < 9; k++)
         if (m & (1u << k)) {
             const int i = i0 + (k % 3) - 1, j = j0 + (k / 3) - 1;
-            if (at < key_cap) keys[at] = ((unsigned long long)(unsigned)(i * g.rows + j) << 32) | (unsigned)p;
+            if (at < key_cap)
+                keys[at] = ((unsigned long long)(seg_base + (unsigned)(i * rows + j)) << 32) | (unsigned)p;
             at++;
         }
+}
+
+__global__ __launch_bounds__(256) void k_grid_assign(const double* __restrict__ x, const double* __restrict__ y, int n,
+                                                     GridGeom g, const uint8_t* __restrict__ cell_on,
+                                                     unsigned long long* __restrict__ keys, int* __restrict__ key_count,
+                                                     int key_cap)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    int i0 = 0, j0 = 0;
+    const unsigned m = p < n ? hit_mask(g, cell_on, x[p], y[p], &i0, &j0) : 0u;
+    append_keys(m, i0, j0, 0u, g.rows, p, keys, key_count, key_cap);
+}
+
+// ---- a whole day of time windows in one pass (icelk_grid_bin_windows) ------------------------------------------
+// The points of every loaded hour file, concatenated; file f holds [file_off[f], file_off[f + 1]) and belongs to
+// camera file_cam[f].  Camera c's window w (slot c * nw + w) loads files win_f0 .. win_f1 (none when f0 > f1) and
+// keeps the times in [t_lo, t_hi) -- int64 epoch seconds compared as float64, as numpy compares the float64 time
+// array with a Python int.  The windows of a camera are disjoint and ascending, so a binary search finds the only one
+// that can hold a time; the point counts only if that window loads its file.  NaN lies in no window.
+struct DayTables {
+    const long long* file_off;
+    const int* file_cam;
+    const int* win_f0;
+    const int* win_f1;
+    const long long* t_lo;
+    const long long* t_hi;
+    int nfiles, ncam, nw;
+};
+
+// float64 -> uint64 with the same order (negative values flipped, positive ones above them)
+__device__ __forceinline__ unsigned long long order_key(double d)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(d);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+__global__ __launch_bounds__(256) void k_grid_day_assign(const double* __restrict__ x, const double* __restrict__ y,
+                                                         const double* __restrict__ t, int n, DayTables D, GridGeom g,
+                                                         const uint8_t* __restrict__ cell_on, int ncells,
+                                                         unsigned long long* __restrict__ keys,
+                                                         int* __restrict__ key_count, int key_cap,
+                                                         int* __restrict__ sel_count,
+                                                         unsigned long long* __restrict__ t_min,
+                                                         unsigned long long* __restrict__ t_max)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    int w = -1, cam = 0;
+    double tp = 0.0;
+    if (p < n) {
+        int f = 0, hi = D.nfiles - 1;                       // last file starting at or before p (empty files skipped)
+        while (f < hi) {
+            const int mid = (f + hi + 1) >> 1;
+            if (D.file_off[mid] <= p) f = mid;
+            else hi = mid - 1;
+        }
+        cam = D.file_cam[f];
+        tp = t[p];
+        const long long* lo = D.t_lo + (size_t)cam * D.nw;
+        int a = 0, b = D.nw;                                // windows starting at or before tp
+        while (a < b) {
+            const int mid = (a + b) >> 1;
+            if ((double)lo[mid] <= tp) a = mid + 1;
+            else b = mid;
+        }
+        const int wc = a - 1;
+        const size_t sl = (size_t)cam * D.nw + wc;
+        if (wc >= 0 && f >= D.win_f0[sl] && f <= D.win_f1[sl] && tp < (double)D.t_hi[sl]) w = wc;
+    }
+    // selected count and time range per (window, camera): lanes of one slot are combined first -- a wave's points are
+    // consecutive, so nearly always one slot per wave and one set of atomics
+    const int slot = w >= 0 ? w * D.ncam + cam : -1;
+    const unsigned long long tk = order_key(tp);
+    unsigned long long pending = __ballot(slot >= 0);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const int s0 = __shfl(slot, leader);
+        const bool mine = slot == s0;
+        int c = mine ? 1 : 0;
+        unsigned long long mn = mine ? tk : ~0ull, mx = mine ? tk : 0ull;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            c += __shfl_xor(c, o);
+            const unsigned long long a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
+            mn = a < mn ? a : mn;
+            mx = b > mx ? b : mx;
+        }
+        if ((threadIdx.x & 63) == leader) {
+            atomicAdd(&sel_count[s0], c);
+            atomicMin(&t_min[s0], mn);
+            atomicMax(&t_max[s0], mx);
+        }
+        pending &= ~__ballot(mine);
+    }
+    int i0 = 0, j0 = 0;
+    const unsigned m = w >= 0 ? hit_mask(g, cell_on, x[p], y[p], &i0, &j0) : 0u;
+    append_keys(m, i0, j0, (unsigned)w * (unsigned)ncells, g.rows, p, keys, key_count, key_cap);
 }
 
 __device__ __forceinline__ double leaf_sum(const unsigned long long* __restrict__ keys, const double* __restrict__ a,
@@ -242,6 +336,20 @@ void launch_grid_assign(hipStream_t s, const double* x, const double* y, int n, 
     const GridGeom g{left, top, spacing, cols, rows};
     hipLaunchKernelGGL(k_grid_assign, dim3((n + 255) / 256), dim3(256), 0, s, x, y, n, g, cell_on, keys, key_count,
                        key_cap);
+}
+
+void launch_grid_day_assign(hipStream_t s, const double* x, const double* y, const double* t, int n,
+                            const long long* file_off, const int* file_cam, const int* win_f0, const int* win_f1,
+                            int nfiles, const long long* t_lo, const long long* t_hi, int ncam, int nw, double left,
+                            double top, double spacing, int cols, int rows, const uint8_t* cell_on,
+                            unsigned long long* keys, int* key_count, int key_cap, int* sel_count,
+                            unsigned long long* t_min, unsigned long long* t_max)
+{
+    if (n <= 0) return;
+    const GridGeom g{left, top, spacing, cols, rows};
+    const DayTables D{file_off, file_cam, win_f0, win_f1, t_lo, t_hi, nfiles, ncam, nw};
+    hipLaunchKernelGGL(k_grid_day_assign, dim3((n + 255) / 256), dim3(256), 0, s, x, y, t, n, D, g, cell_on,
+                       cols * rows, keys, key_count, key_cap, sel_count, t_min, t_max);
 }
 
 void launch_grid_reduce(hipStream_t s, const unsigned long long* keys, const int* key_count, const double* u,

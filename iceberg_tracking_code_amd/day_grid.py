@@ -1,0 +1,284 @@
+"""The day driver of step s3: `utm_to_gridded_utm` of s3_utm_to_gridded_utm.py:222-446 (plot_switch 0) -- camera
+schedule, time windows, clock drift, selection of each window's velocities out of every camera's hourly files, one
+gridded `.npz` per window -- with every window of the day binned in one device pass (`icelk_grid_bin_windows`,
+csrc/k_grid.hip).  The host plans a few dozen windows with plain `datetime`; the points cross PCIe once.
+
+What the reference does, and this module reproduces:
+- schedule: a camera counts only if exactly one row has camera == name and start_day <= day <= end_day; its hours
+  run from start_time ('%H:%M') to start + tracking_duration;
+- windows: np.arange(min start, max end + 0.001, time_window), starts [:-1], ends [1:]; time_window == 24.0 is the one
+  window [min start, max end]; datetimes are day + timedelta(hours=float), microseconds included;
+- drift (trm.correct_time_drift): the first row with cam == name, start_date < day <= end_date; numpy's
+  round(drift_start_sec + days * drift_pday_sec, 1) (the workbook's columns are numpy scalars); anything that fails
+  means 0.  Windows shift by -drift; epoch bounds are int(total_seconds) of the shifted datetimes (truncation);
+- selection: time >= start & time < end per hour file, float64;
+- hour files: the hours start.replace(minute=0, second=0) + k h up to end.replace(minute=0, second=0) (the hours
+  pandas.date_range(..., freq='H') lists, microseconds kept: when the end's microseconds are below the start's, the
+  end's hour drops out); each hour's file is the first of '%Y%m%d_%H00*.npz' in the camera workspace -- the reference
+  takes glob's first, in directory order; here the sorted first.  A file that cannot be read, or lacks one of x, y,
+  u, v, speed, time, counts as missing, as the reference's `except: pass` has it.  A camera without a
+  day_str + '*utm.npz' file is skipped.  A point in a file its window does not load belongs to no window;
+- a window gets a file iff some camera selected a point in it; the points of a window are concatenated camera by
+  camera, hour by hour -- the order of numpy's pairwise per-cell sums;
+- names: '%Y%m%d_%H%M-%H%M_{time_diff}min_{grid_size}m.npz' with time_diff = int(minutes); the full day is named from
+  the first / last selected time (+ drift) rounded to 30 minutes (trm.round_time).
+Times are taken as float64: s2 writes int64 epoch seconds, which float64 holds exactly.
+Not built: plots (plot_switch 1, 2), the xlsx readers (pass the rows pd.read_excel gives), s3:main's process pool.
+"""
+import ctypes as C
+import datetime as dt
+import glob
+import os
+import time
+
+import numpy as np
+
+from . import _lib
+from .context import Context
+from .gridding import cell_table, create_grid_across_fjord, pack_cells
+
+EPOCH = dt.datetime(1970, 1, 1)
+HOUR_KEYS = ("x", "y", "u", "v", "speed", "time")
+SAVED_KEYS = ("grid_size", "topleft", "rows", "cols", "grid_id", "i", "j", "x", "y", "u", "v", "speed", "count",
+              "measured", "not_measured")
+
+
+def _records(table):
+    """A workbook table as a list of row dicts: a list of dicts, or anything with .to_dict('records')."""
+    return table.to_dict("records") if hasattr(table, "to_dict") else list(table)
+
+
+def epoch_seconds(t):
+    """trm.datetime_to_epoch: whole seconds since 1970, truncated toward zero."""
+    return int((t - EPOCH).total_seconds())
+
+
+def round_half_hour(t):
+    """trm.round_time(t, 1800): to the nearest half hour of the day (a tie goes up), microseconds dropped."""
+    s = t.hour * 3600 + t.minute * 60 + t.second
+    r = (s + 900.0) // 1800 * 1800
+    return t.replace(microsecond=0) + dt.timedelta(seconds=r - s)
+
+
+def scheduled_cameras(camnames, schedule, day):
+    """s3:239-262 -> [(name, start hour, end hour)] in camnames order."""
+    d = int(day.strftime("%Y%m%d"))
+    rows = _records(schedule)
+    out = []
+    for name in camnames:
+        match = [r for r in rows if r["camera"] == name and r["start_day"] <= d and r["end_day"] >= d]
+        if len(match) == 1:
+            t = dt.datetime.strptime(match[0]["start_time"], "%H:%M")
+            start = t.hour + t.minute / 60.0
+            out.append((name, start, start + match[0]["tracking_duration"]))
+    return out
+
+
+def time_correction(camname, day, clock_drifts):
+    """trm.correct_time_drift for one camera and day, in seconds; 0 when no row applies or anything fails."""
+    d = int(day.strftime("%Y%m%d"))
+    try:
+        row = [r for r in _records(clock_drifts) if r["cam"] == camname and r["start_date"] < d
+               and r["end_date"] >= d][0]
+        days = (dt.datetime.strptime(str(d), "%Y%m%d") - dt.datetime.strptime(str(row["start_date"]), "%Y%m%d")).days
+        return float(np.round(np.float64(row["drift_start_sec"]) + days * np.float64(row["drift_pday_sec"]), 1))
+    except Exception:
+        return 0
+
+
+def time_windows(starts, ends, time_window):
+    """s3:268-274 -> [(start hour, end hour)]."""
+    edges = list(np.arange(min(starts), max(ends) + 0.001, time_window))
+    if time_window == 24.0:
+        return [(min(starts), max(ends))]
+    return list(zip(edges[:-1], edges[1:]))
+
+
+def hours_between(start, end):
+    """The hours return_velocities_by_time loads for [start, end): start and end with minutes and seconds zeroed
+    (microseconds kept), then start + k hours while <= end."""
+    h, last = start.replace(minute=0, second=0), end.replace(minute=0, second=0)
+    out = []
+    while h <= last:
+        out.append(h)
+        h += dt.timedelta(hours=1)
+    return out
+
+
+class DayPlan:
+    """Everything about a day that does not need the velocities.
+
+    windows[w] = (start, end) datetimes; cameras[c] = dict(name, correction, workspace, has_files, lo, hi, hours, f0,
+    f1): lo / hi the int64 epoch bounds of each window, hours[w] the hour datetimes window w loads, f0[w] .. f1[w] the
+    files it loads (none: f0 > f1); files = the hour files in concatenation order (camera, then hour), dict(cam, hour
+    ('%Y%m%d_%H00'), path)."""
+
+    def __init__(self, day, time_window, grid_size, windows, cameras, files):
+        self.day, self.time_window, self.grid_size = day, time_window, grid_size
+        self.windows, self.cameras, self.files = windows, cameras, files
+
+    def name(self, w, t_min=None, t_max=None):
+        """File name of window w (s3:427-437).  The full day (time_window 24.0) needs t_min / t_max: per camera
+        the smallest / largest selected epoch time, None for a camera that selected nothing."""
+        start, end = self.windows[w]
+        if self.time_window == 24.0:
+            lo = [EPOCH + dt.timedelta(seconds=t) + dt.timedelta(seconds=cam["correction"])
+                  for t, cam in zip(t_min, self.cameras) if t is not None]
+            hi = [EPOCH + dt.timedelta(seconds=t) + dt.timedelta(seconds=cam["correction"])
+                  for t, cam in zip(t_max, self.cameras) if t is not None]
+            return "{}-{}_full_day_{}m.npz".format(round_half_hour(min(lo)).strftime("%Y%m%d_%H%M"),
+                                                   round_half_hour(max(hi)).strftime("%H%M"), self.grid_size)
+        time_diff = int((end - start).total_seconds() / 60.0)
+        return "{}-{}_{}min_{}m.npz".format(start.strftime("%Y%m%d_%H%M"), end.strftime("%H%M"), time_diff,
+                                            self.grid_size)
+
+
+def plan_day(camnames, source_path_head, source_path_tail, schedule, clock_drifts, day, time_window, grid_size):
+    """The bookkeeping of s3:228-322 for one day, from the schedule, the drift table and the file names alone."""
+    day_str = day.strftime("%Y%m%d")
+    cams = scheduled_cameras(camnames, schedule, day)
+    if not cams:
+        return DayPlan(day, time_window, grid_size, [], [], [])
+    windows = [(day + dt.timedelta(hours=a), day + dt.timedelta(hours=b))
+               for a, b in time_windows([c[1] for c in cams], [c[2] for c in cams], time_window)]
+    cameras, files = [], []
+    for ci, (name, _, _) in enumerate(cams):
+        corr = time_correction(name, day, clock_drifts)
+        ws = os.path.join(source_path_head, name, source_path_tail)
+        shift = dt.timedelta(seconds=corr)
+        bounds = [(s - shift, e - shift) for s, e in windows]
+        cam = dict(name=name, correction=corr, workspace=ws,
+                   has_files=len(glob.glob(os.path.join(ws, day_str + "*utm.npz"))) > 0,
+                   lo=[epoch_seconds(s) for s, _ in bounds], hi=[epoch_seconds(e) for _, e in bounds],
+                   hours=[hours_between(s, e) for s, e in bounds], f0=[], f1=[])
+        cameras.append(cam)
+        if not cam["has_files"]:
+            cam["f0"], cam["f1"] = [0] * len(windows), [-1] * len(windows)
+            continue
+        # a window loads consecutive hours, so a contiguous run of the camera's files; the windows loading one file
+        # need not be consecutive (a window inside one hour whose end microseconds lie below its start's loads none)
+        prefixes = sorted({h.strftime("%Y%m%d_%H00") for hours in cam["hours"] for h in hours})
+        index = {}
+        for prefix in prefixes:
+            match = sorted(glob.glob(os.path.join(ws, prefix + "*.npz")))
+            if match:
+                index[prefix] = len(files)
+                files.append(dict(cam=ci, hour=prefix, path=match[0]))
+        for hours in cam["hours"]:
+            got = [index[p] for p in (h.strftime("%Y%m%d_%H00") for h in hours) if p in index]
+            assert got == list(range(got[0], got[-1] + 1)) if got else True
+            cam["f0"].append(got[0] if got else 0)
+            cam["f1"].append(got[-1] if got else -1)
+    return DayPlan(day, time_window, grid_size, windows, cameras, files)
+
+
+def _load_hour_file(path):
+    """x, y, u, v, t of an hourly velocity file as float64, or None where the reference's `except: pass` would
+    skip the file."""
+    try:
+        with np.load(path) as z:
+            a = [np.asarray(z[k]) for k in HOUR_KEYS]
+    except Exception:
+        return None
+    x, y, u, v, _, t = (np.ascontiguousarray(q, dtype=np.float64).ravel() for q in a)
+    if not len(x) == len(y) == len(u) == len(v) == len(t):
+        return None
+    return x, y, u, v, t
+
+
+def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None):
+    """Loads the plan's files, runs the device pass, and packs every window that selected a point.  `timing`: a dict
+    that receives the seconds of each stage and the kernels' milliseconds (tools/grid_day_bench.py)."""
+    clock = time.perf_counter
+    t0 = clock()
+    empty = (np.zeros(0),) * 5
+    parts = [_load_hour_file(f["path"]) or empty for f in plan.files]        # an unreadable file holds no point
+    n = sum(len(p[0]) for p in parts)
+    if n == 0:
+        return []
+    x, y, u, v, t = (np.concatenate([p[k] for p in parts]) for k in range(5))
+    off = np.zeros(len(parts) + 1, np.int64)
+    off[1:] = np.cumsum([len(p[0]) for p in parts])
+    fcam = np.array([f["cam"] for f in plan.files], np.int32)
+    lo, hi = (np.array([c[k] for c in plan.cameras], np.int64) for k in ("lo", "hi"))
+    wf0, wf1 = (np.array([c[k] for c in plan.cameras], np.int32) for k in ("f0", "f1"))
+    ncam, nw = lo.shape
+    grid = create_grid_across_fjord(ctx, fjord, grid_size)
+    topleft, rows, cols = grid[3], grid[4], grid[5]
+    left, top, on, idx = cell_table(grid, fjord)
+    ncells = rows * cols
+    t1 = clock()
+    cnt = np.zeros(nw * ncells, np.int32)
+    mu, mv, sp = (np.zeros(nw * ncells, np.float64) for _ in range(3))
+    sel = np.zeros(nw * ncam, np.int32)
+    tmin, tmax = np.zeros(nw * ncam, np.float64), np.zeros(nw * ncam, np.float64)
+    f64 = lambda a: a.ctypes.data_as(_lib.f64p)               # noqa: E731
+    i32 = lambda a: a.ctypes.data_as(_lib.i32p)               # noqa: E731
+    i64 = lambda a: a.ctypes.data_as(_lib.i64p)               # noqa: E731
+    device_ms = C.c_double(0.0)
+    ctx._ck(ctx._lib.icelk_grid_bin_windows(
+        ctx._h, f64(x), f64(y), f64(u), f64(v), f64(t), n, i64(off), i32(fcam), i32(wf0), i32(wf1), len(parts),
+        i64(lo), i64(hi), ncam, nw, left, top, float(grid_size), cols, rows, on.ctypes.data_as(_lib.u8p), i32(cnt),
+        f64(mu), f64(mv), f64(sp), i32(sel), f64(tmin), f64(tmax), C.byref(device_ms) if timing is not None else None))
+    t2 = clock()
+    sel, tmin, tmax = sel.reshape(nw, ncam), tmin.reshape(nw, ncam), tmax.reshape(nw, ncam)
+    written = []
+    for w in range(nw):
+        if not sel[w].any():
+            continue
+        s = slice(w * ncells, (w + 1) * ncells)
+        r = pack_cells(grid, idx, cnt[s], mu[s], mv[s], sp[s], observation_threshold)
+        r.update(grid_size=grid_size, topleft=topleft, rows=rows, cols=cols)
+        arrays = {k: np.asanyarray(r[k]) for k in SAVED_KEYS}        # what np.savez makes of s3's lists
+        name = plan.name(w, [float(a) if k else None for a, k in zip(tmin[w], sel[w])],
+                         [float(a) if k else None for a, k in zip(tmax[w], sel[w])])
+        written.append((name, arrays))
+    if timing is not None:
+        timing.update(points=n, load_s=t1 - t0, device_call_s=t2 - t1, kernels_ms=device_ms.value,
+                      pack_s=clock() - t2)
+    return written
+
+
+def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts, fjord, day,
+                       time_window, grid_size, observation_threshold, ctx=None, save=True):
+    """One day of hourly velocity files -> one gridded .npz per time window, as s3_utm_to_gridded_utm.utm_to_gridded_utm
+    (s3:222-446) with plot_switch 0.
+
+    `schedule`: the rows of the parameter workbook (camera, start_day, end_day, start_time, tracking_duration);
+    `clock_drifts`: the rows of the clock-drift workbook (cam, start_date, end_date, drift_start_sec, drift_pday_sec)
+    -- each a list of dicts or anything with .to_dict('records'), e.g. what pd.read_excel returns.  `fjord`: dict or
+    npz with 'x' and 'y'.  `day`: datetime.  Returns [(file name, dict of arrays)] in writing order; with `save` the
+    files are written to target_path with np.savez, keys and dtypes as the reference's."""
+    plan = plan_day(camnames, source_path_head, source_path_tail, schedule, clock_drifts, day, time_window, grid_size)
+    if not plan.files:
+        return []
+    own = ctx is None
+    if own:
+        ctx = Context(64, 64, n_slots=1, max_pts=1 << 18)
+    try:
+        written = _grid_day(ctx, plan, fjord, grid_size, observation_threshold)
+    finally:
+        if own:
+            ctx.close()
+    if save:
+        for name, arrays in written:
+            np.savez(os.path.join(target_path, name), **arrays)
+    return written
+
+
+def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts,
+                            fjord, time_window, grid_size, observation_threshold, ctx=None, save=True):
+    """s3:main's loop over days (without its process pool), on one context: the files of every day, in order."""
+    own = ctx is None
+    if own:
+        ctx = Context(64, 64, n_slots=1, max_pts=1 << 18)
+    try:
+        out = []
+        for day in days:
+            out += utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path, schedule,
+                                      clock_drifts, fjord, day, time_window, grid_size, observation_threshold,
+                                      ctx=ctx, save=save)
+        return out
+    finally:
+        if own:
+            ctx.close()

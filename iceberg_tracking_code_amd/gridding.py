@@ -4,7 +4,9 @@ point: `trm.create_grid_across_fjord` (imports/tracking_misc.py:23-56) and the p
 (`icelk_points_in_polygon`, `icelk_grid_bin`, csrc/k_grid.hip); what stays here is the cell geometry of a few hundred
 squares and the packing of the result arrays the reference hands to np.savez (s3:441-445).  No CPU fallback.
 
-Out of scope: the day / camera / time-window bookkeeping around the loop (s3:120-388) and plotting.
+The day driver around the loop -- schedule, time windows, clock drift, selection from the hourly files, every window
+of a day binned in one device pass (`icelk_grid_bin_windows`) -- is day_grid.utm_to_gridded_utm; `pack_cells` and
+`cell_table` here serve both.  Out of scope: plotting.
 """
 import ctypes as C
 import math
@@ -47,18 +49,25 @@ def create_grid_across_fjord(ctx, fjord, spacing):
             [left + 0.5 * spacing, top - 0.5 * spacing], rows, cols]
 
 
+def cell_table(grid, fjord):
+    """(left, top, cell_on, idx) of a grid for the kernels: cell_on[i * rows + j] = 1 for the kept cells, idx = that
+    index of every kept cell in the grid's order."""
+    indices, rows, cols = grid[2], grid[4], grid[5]
+    fx, fy = np.asarray(fjord["x"]), np.asarray(fjord["y"])
+    on = np.zeros(cols * rows, np.uint8)
+    idx = np.array([i * rows + j for i, j in indices], np.int64)
+    on[idx] = 1
+    return float(min(fx)), float(max(fy)), on, idx
+
+
 def bin_velocities(ctx, x, y, u, v, fjord, spacing, observation_threshold, grid=None):
     """The loop of s3:391-421 for one time window.  Returns the dict the reference saves (s3:441-445, without
     `grid_size` / `topleft` / `rows` / `cols`, which the caller has): grid_id, i, j, x, y, u, v, speed, count,
     measured, not_measured."""
     if grid is None:
         grid = create_grid_across_fjord(ctx, fjord, spacing)
-    polygons, centers, indices, _, rows, cols = grid
-    fx, fy = np.asarray(fjord["x"]), np.asarray(fjord["y"])
-    left, top = float(min(fx)), float(max(fy))
-    on = np.zeros(cols * rows, np.uint8)
-    idx = np.array([i * rows + j for i, j in indices], np.int64)
-    on[idx] = 1
+    rows, cols = grid[4], grid[5]
+    left, top, on, idx = cell_table(grid, fjord)
     a = [np.ascontiguousarray(t, dtype=np.float64).ravel() for t in (x, y, u, v)]
     n = len(a[0])
     cnt = np.zeros(cols * rows, np.int32)
@@ -66,6 +75,12 @@ def bin_velocities(ctx, x, y, u, v, fjord, spacing, observation_threshold, grid=
     ctx._ck(ctx._lib.icelk_grid_bin(ctx._h, _f64(a[0]), _f64(a[1]), _f64(a[2]), _f64(a[3]), n, left, top,
                                     float(spacing), cols, rows, on.ctypes.data_as(_lib.u8p),
                                     cnt.ctypes.data_as(_lib.i32p), _f64(mu), _f64(mv), _f64(sp)))
+    return pack_cells(grid, idx, cnt, mu, mv, sp, observation_threshold)
+
+
+def pack_cells(grid, idx, cnt, mu, mv, sp, observation_threshold):
+    """The lists s3:391-421 fills, from per-cell results indexed i * rows + j (idx: that index of every kept cell)."""
+    polygons, centers, indices = grid[:3]
     out = {k: [] for k in ("grid_id", "i", "j", "x", "y", "u", "v", "speed", "count", "measured", "not_measured")}
     for counter, (poly, center, index, c) in enumerate(zip(polygons, centers, indices, idx)):
         nobs = int(cnt[c])

@@ -321,6 +321,24 @@ int icelk_points_in_polygon(icelk_t* h, const double* poly_xy, int n_poly, const
 int icelk_grid_bin(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n, double left,
                    double top, double spacing, int cols, int rows, const uint8_t* cell_on, int* count, double* mean_u,
                    double* mean_v, double* speed);
+/* Every time window of a day in one pass (the loop of s3_utm_to_gridded_utm.py:286-421 around the binning above).
+ * x, y, u, v, t (float64, n): the points of every loaded hour file, concatenated camera by camera, hour by hour.  File
+ * f holds points [file_offset[f], file_offset[f + 1]) (file_offset[0] = 0, [nfiles] = n, non-decreasing) and comes
+ * from camera file_cam[f] (0 .. ncam-1, non-decreasing).  Camera c's window w (slot c * nw + w) loads files
+ * win_f0 .. win_f1 of that camera (none: win_f0 > win_f1) and keeps the points with t_lo <= t < t_hi (int64 epoch
+ * seconds, compared as float64); per camera the windows must be ascending and disjoint (t_lo[w] <= t_hi[w] <=
+ * t_lo[w + 1]).  A point is binned in the window that keeps its time if that window loads its file, else nowhere.
+ * Out, per (window w, cell k) at w * cols * rows + k: count, mean_u, mean_v, speed -- for every window what
+ * icelk_grid_bin gives on that window's points in concatenation order, bit for bit.  Per (window w, camera c) at
+ * w * ncam + c: sel_count = points selected, t_min / t_max = their smallest / largest t (0 when none).
+ * device_ms (may be NULL): HIP-event time of the kernels (assign, sort, reduce); uploads and read-backs excluded.
+ * ICELK_ECAP when nw * cols * rows does not fit 31 bits, cols * rows > 2^24 or n > 2^30. */
+int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                           const double* t, int n, const int64_t* file_offset, const int* file_cam, const int* win_f0,
+                           const int* win_f1, int nfiles, const int64_t* t_lo, const int64_t* t_hi, int ncam, int nw,
+                           double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
+                           int* count, double* mean_u, double* mean_v, double* speed, int* sel_count, double* t_min,
+                           double* t_max, double* device_ms);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the

@@ -1,0 +1,226 @@
+"""GPU: the s3 day driver (day_grid.utm_to_gridded_utm, icelk_grid_bin_windows in csrc/k_grid.hip).
+
+- the golden day: the files the reference's own utm_to_gridded_utm wrote (tests/golden/day_grid_golden.npz), same names,
+  keys, dtypes, shapes and bits, for 30-minute, full-day and 1/7-hour windows;
+- a seeded day of ~2e6 velocities: every window equals the oracle's gridding of that window's points, selected here by
+  a numpy restatement of the selection rule, bit for bit;
+- argument checks of the ABI, and days that write nothing."""
+import datetime as dt
+import os
+
+import numpy as np
+import pytest
+
+import day_grid_golden as G
+from iceberg_tracking_code_amd import _lib, day_grid, utm_to_gridded_utm, utm_to_gridded_utm_days
+from iceberg_tracking_code_amd.gridding import cell_table, create_grid_across_fjord, pack_cells
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def z():
+    return G.load()
+
+
+def assert_same_files(got, want):
+    assert [name for name, _ in got] == [name for name, _ in want]
+    for (name, a), (_, b) in zip(got, want):
+        assert sorted(a) == sorted(b), name
+        for k in b:
+            x, y = np.asarray(a[k]), np.asarray(b[k])
+            assert x.dtype == y.dtype and x.shape == y.shape, (name, k, x.dtype, x.shape, y.dtype, y.shape)
+            assert x.tobytes() == y.tobytes(), (name, k)
+
+
+def read_dir(path):
+    out = {}
+    for name in os.listdir(path):
+        with np.load(os.path.join(path, name)) as f:
+            out[name] = {k: f[k] for k in f.files}
+    return out
+
+
+@pytest.mark.parametrize("r", [0, 1, 2])
+def test_golden_day_equals_reference(ctx, z, tmp_path, r):
+    G.build_tree(z, str(tmp_path / "in"))
+    camnames, schedule, drifts, fjord, day, grid_size, thr = G.args(z)
+    target = tmp_path / "out"
+    target.mkdir()
+    got = utm_to_gridded_utm(camnames, str(tmp_path / "in"), "utm", str(target), schedule, drifts, fjord, day,
+                             float(z["time_windows"][r]), grid_size, thr, ctx=ctx)
+    want = G.outputs(z, r)
+    assert_same_files(got, want)
+    on_disk = read_dir(str(target))
+    assert sorted(on_disk) == sorted(name for name, _ in want)
+    assert_same_files(sorted(on_disk.items()), sorted(want, key=lambda t: t[0]))
+
+
+def test_days_loop(ctx, z, tmp_path):
+    G.build_tree(z, str(tmp_path / "in"))
+    camnames, schedule, drifts, fjord, day, grid_size, thr = G.args(z)
+    days = [day - dt.timedelta(days=1), day, day + dt.timedelta(days=60)]     # before the drift rows, the day, unscheduled
+    got = utm_to_gridded_utm_days(days, camnames, str(tmp_path / "in"), "utm", str(tmp_path), schedule, drifts, fjord,
+                                  0.5, grid_size, thr, ctx=ctx, save=False)
+    assert_same_files(got, G.outputs(z, 0))
+
+
+# ---- a seeded day of ~2e6 velocities against the oracle --------------------------------------------------------------
+
+DAY = dt.datetime(2021, 8, 3)
+CAMS = [("north", "06:00", 6.0, 41.7), ("south", "06:30", 5.5, -17.35), ("ridge", "07:00", 4.0, 1234.5)]
+SPACING = 150
+
+
+def synth_day(root):
+    rng = np.random.default_rng(11)
+    ang = np.sort(rng.uniform(0, 2 * np.pi, 40))
+    rad = rng.uniform(1500, 2600, 40)
+    fjord = {"x": 600000.0 + np.round(1.2 * rad * np.cos(ang), 1), "y": 7000000.0 + np.round(rad * np.sin(ang), 1)}
+    left, top = min(fjord["x"]), max(fjord["y"])
+    files = {}
+    for name, start, dur, _ in CAMS:
+        ws = os.path.join(root, name, "utm")
+        os.makedirs(ws)
+        h0 = int(start[:2])
+        for hr in range(h0 - 1, h0 + int(dur) + 2):
+            e0 = day_grid.epoch_seconds(DAY + dt.timedelta(hours=hr))
+            n = 90000
+            t = np.sort(rng.integers(e0 - 600, e0 + 4200, n)).astype(np.int64)          # spills into both neighbours
+            x = rng.uniform(left - 300, max(fjord["x"]) + 300, n)
+            y = rng.uniform(min(fjord["y"]) - 300, top + 300, n)
+            k = n // 10
+            x[:k] = left + SPACING * rng.integers(0, 40, k)                            # on edges and corners
+            y[k:2 * k] = top - SPACING * rng.integers(0, 40, k)
+            x[2 * k:3 * k] = left + SPACING * rng.integers(0, 40, k)
+            y[2 * k:3 * k] = top - SPACING * rng.integers(0, 40, k)
+            c = rng.random(n) < 0.55                                                   # one crowded cell
+            x[c] = left + SPACING * 17.5 + rng.uniform(-60, 60, int(c.sum()))
+            y[c] = top - SPACING * 16.5 + rng.uniform(-60, 60, int(c.sum()))
+            u = rng.normal(0, 1, n) * 10.0 ** rng.integers(-4, 2, n)
+            v = rng.normal(0, 1, n) * 10.0 ** rng.integers(-4, 2, n)
+            fname = (DAY + dt.timedelta(hours=hr)).strftime("%Y%m%d_%H00") + "_30s_utm.npz"
+            arrays = dict(x=x, y=y, u=u, v=v, speed=np.hypot(u, v), time=t)
+            np.savez(os.path.join(ws, fname), **arrays)
+            files[(name, fname[:13])] = arrays
+    schedule = [dict(camera=n, start_day=20210801, end_day=20210810, start_time=s, tracking_duration=d)
+                for n, s, d, _ in CAMS]
+    drifts = [dict(cam=n, start_date=20210801, end_date=20210810, drift_start_sec=c, drift_pday_sec=0.0)
+              for n, _, _, c in CAMS]
+    return fjord, files, schedule, drifts
+
+
+def select_window(files, start, end):
+    """s3's selection restated with numpy: camera by camera, hour by hour, time >= start & time < end."""
+    parts = []
+    for name, _, _, corr in CAMS:
+        s, e = start - dt.timedelta(seconds=corr), end - dt.timedelta(seconds=corr)
+        lo, hi = int((s - day_grid.EPOCH).total_seconds()), int((e - day_grid.EPOCH).total_seconds())
+        h, last = s.replace(minute=0, second=0), e.replace(minute=0, second=0)
+        while h <= last:
+            a = files.get((name, h.strftime("%Y%m%d_%H00")))
+            if a is not None:
+                m = (a["time"] >= lo) & (a["time"] < hi)
+                parts.append([a[k][m] for k in ("x", "y", "u", "v")])
+            h += dt.timedelta(hours=1)
+    return [np.concatenate([p[k] for p in parts]) for k in range(4)]
+
+
+def test_synthetic_day_equals_oracle(ctx, orc, tmp_path):
+    fjord, files, schedule, drifts = synth_day(str(tmp_path))
+    n_total = sum(len(a["x"]) for a in files.values())
+    assert n_total >= 2_000_000
+    got = utm_to_gridded_utm([c[0] for c in CAMS], str(tmp_path), "utm", str(tmp_path), schedule, drifts, fjord, DAY,
+                             0.5, SPACING, 5, ctx=ctx, save=False)
+    grid = create_grid_across_fjord(ctx, fjord, SPACING)
+    left, top, on, idx = cell_table(grid, fjord)
+    rows, cols = grid[4], grid[5]
+    names = [name for name, _ in got]
+    want_names, peak = [], 0
+    for k in range(12):
+        start = DAY + dt.timedelta(hours=6 + 0.5 * k)
+        end = DAY + dt.timedelta(hours=6.5 + 0.5 * k)
+        x, y, u, v = select_window(files, start, end)
+        if len(x) == 0:
+            continue
+        name = "{}-{}_30min_{}m.npz".format(start.strftime("%Y%m%d_%H%M"), end.strftime("%H%M"), SPACING)
+        want_names.append(name)
+        o = orc.grid_bin(x, y, u, v, left, top, SPACING, cols, rows, on)
+        peak = max(peak, int(o["count"].max()))
+        want = pack_cells(grid, idx, o["count"], o["mean_u"], o["mean_v"], o["speed"], 5)
+        a = got[names.index(name)][1]
+        for key in ("grid_id", "i", "j", "x", "y", "u", "v", "speed", "count", "measured", "not_measured"):
+            w = np.asanyarray(want[key])
+            assert a[key].dtype == w.dtype and a[key].shape == w.shape, (name, key)
+            assert a[key].tobytes() == w.tobytes(), (name, key)
+    assert names == want_names and len(names) == 12
+    assert peak > 50000
+
+
+# ---- ABI checks and empty days --------------------------------------------------------------------------------------
+
+def call(ctx, n=4, off=(0, 4), fcam=(0,), wf=((0,), (0,)), lo=((0,),), hi=((10,),), cols=4, rows=4, nw=None,
+         ncam=None, x=None):
+    x = np.zeros(max(min(n, 64), 1), np.float64) if x is None else x
+    lo, hi = np.array(lo, np.int64), np.array(hi, np.int64)
+    ncam = lo.shape[0] if ncam is None else ncam
+    nw = lo.shape[1] if nw is None else nw
+    off, fcam = np.array(off, np.int64), np.array(fcam, np.int32)
+    wf0, wf1 = (np.array(a, np.int32) for a in wf)
+    on = np.ones(min(cols * rows, 1 << 24), np.uint8)
+    nseg = min(nw * cols * rows, 1 << 20)
+    cnt, sel = np.zeros(nseg, np.int32), np.zeros(64, np.int32)
+    f = np.zeros(nseg, np.float64)
+    t = np.zeros(64, np.float64)
+    p64 = lambda a: a.ctypes.data_as(_lib.f64p)    # noqa: E731
+    return ctx._lib.icelk_grid_bin_windows(
+        ctx._h, p64(x), p64(x), p64(x), p64(x), p64(x), n, off.ctypes.data_as(_lib.i64p),
+        fcam.ctypes.data_as(_lib.i32p), wf0.ctypes.data_as(_lib.i32p), wf1.ctypes.data_as(_lib.i32p), len(fcam),
+        lo.ctypes.data_as(_lib.i64p), hi.ctypes.data_as(_lib.i64p), ncam, nw, 0.0, 0.0, 1.0, cols, rows,
+        on.ctypes.data_as(_lib.u8p), cnt.ctypes.data_as(_lib.i32p), p64(f), p64(f), p64(f),
+        sel.ctypes.data_as(_lib.i32p), p64(t), p64(t), None)
+
+
+def test_abi_arguments(ctx):
+    assert call(ctx) == _lib.OK
+    assert call(ctx, n=0, off=(0, 0)) == _lib.OK
+    assert call(ctx, n=-1) == _lib.EARG
+    assert call(ctx, off=(0, 3)) == _lib.EARG                                   # offsets do not end at n
+    assert call(ctx, off=(0, 5, 4), fcam=(0, 0)) == _lib.EARG                   # decreasing offsets
+    assert call(ctx, fcam=(1,)) == _lib.EARG                                    # no such camera
+    assert call(ctx, n=4, off=(0, 2, 4), fcam=(1, 0), lo=((0,), (0,)), hi=((9,), (9,)),
+                wf=((0, 1), (0, 1))) == _lib.EARG                               # cameras out of order
+    assert call(ctx, lo=((0, 5),), hi=((6, 10),), wf=((0, 0), (0, 0))) == _lib.EARG    # overlapping windows
+    assert call(ctx, lo=((5,),), hi=((4,),)) == _lib.EARG                       # end before start
+    assert call(ctx, wf=((0,), (1,))) == _lib.EARG                              # loads a file past the table
+    assert call(ctx, n=4, off=(0, 2, 4), fcam=(0, 1), lo=((0,), (0,)), hi=((9,), (9,)),
+                wf=((0, 0), (1, 1))) == _lib.EARG                               # camera 0 loads camera 1's file
+    assert call(ctx, wf=((1,), (0,))) == _lib.OK                                # loads nothing
+    assert call(ctx, cols=0) == _lib.EARG
+    assert call(ctx, nw=0, lo=((),), hi=((),), wf=((), ())) == _lib.EARG
+
+
+def test_abi_capacity(ctx):
+    big = 1 << 30
+    assert call(ctx, n=big + 1, off=(0, big + 1)) == _lib.ECAP                  # more points than the keys count
+    # 2^12 x 2^12 cells x 2^7 windows = 2^31 segments (checked before any table is read)
+    assert call(ctx, cols=4096, rows=4096, nw=128) == _lib.ECAP
+    assert call(ctx, cols=8192, rows=4096) == _lib.ECAP                         # more cells than icelk_grid_bin takes
+
+
+def test_empty_days_write_nothing(ctx, z, tmp_path):
+    camnames, schedule, drifts, fjord, day, grid_size, thr = G.args(z)
+    for cam in camnames:
+        os.makedirs(str(tmp_path / "in" / cam / "utm"))
+    target = tmp_path / "out"
+    target.mkdir()
+    assert utm_to_gridded_utm(camnames, str(tmp_path / "in"), "utm", str(target), schedule, drifts, fjord, day, 0.5,
+                              grid_size, thr, ctx=ctx) == []
+    # files, but no point inside any window
+    e0 = day_grid.epoch_seconds(day + dt.timedelta(hours=11))
+    np.savez(str(tmp_path / "in" / "camA" / "utm" / (day.strftime("%Y%m%d") + "_1100_60s_utm.npz")),
+             x=np.zeros(3), y=np.zeros(3), u=np.zeros(3), v=np.zeros(3), speed=np.zeros(3),
+             time=np.array([e0 - 86400, e0 + 86400, e0 + 2 * 86400], np.int64))
+    assert utm_to_gridded_utm(camnames, str(tmp_path / "in"), "utm", str(target), schedule, drifts, fjord, day, 0.5,
+                              grid_size, thr, ctx=ctx) == []
+    assert os.listdir(str(target)) == []
