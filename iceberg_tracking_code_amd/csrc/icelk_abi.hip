@@ -78,12 +78,11 @@ struct Ctx {
           *d_dist = nullptr, *d_corners = nullptr;
     uint8_t *d_st_f = nullptr, *d_st_b = nullptr, *d_valid = nullptr;
 
-    DetectScratch D{};
     size_t ncell_cap = 0;
-    // Output of the corner kernel (candidate regions, per-tile counts, masked maximum), double buffered: the
+    // Output of the corner kernel (candidate regions, per-tile counts, masked maximum), triple buffered: the
     // candidates of a FUTURE detection frame can be produced (icelk_seg_detect_prepare, on eig_stream) while the
-    // min-distance stage of the current one still reads its own.  D.raw / D.blk_count / D.max_key /
-    // D.src_* always mirror eo[eo_active].
+    // min-distance stages of the detections in flight still read their own.  A detector set's D.raw / D.blk_count /
+    // D.max_key / D.src_* always mirror eo[its eo_active] (point_at_eig_out).
     struct EigOut {
         unsigned long long* raw = nullptr;
         int* blk_count = nullptr;
@@ -103,27 +102,24 @@ struct Ctx {
         unsigned long long gen = 0, mask_gen = 0;
         hipEvent_t done = nullptr;
     } eo[3];
-    int eo_active = 0;
     // Two detections may be in flight (begun, not finished): the min-distance stage of frame d+2 is issued before the
     // host round trip of frame d, so that the round trip finds kernels that had a whole tracker launch to finish
-    // instead of standing in a serial loop with them.  The scratch of a detection (D, job, h_counts, the flags below,
-    // eo_active) exists twice; the members of this struct proper are the WORKING COPY of set `dset_cur`
-    // (det_load / det_save), which keeps every detector function written against one set.
+    // instead of standing in a serial loop with them.  Everything a detection owns is in its detector set; every
+    // detector function is handed the set it works on.
     struct DetSet {
-        DetectScratch D{};
+        DetectScratch D{};                // D.eig (the full-frame map of icelk_min_eig_map) is shared by both sets
         DetectJob job{};
-        int* h_counts = nullptr;
+        int* h_counts = nullptr;          // pinned, device-visible: {candidates, accepted, undecided, ...} of the job
         int counts_seq = 0;               // h_counts[kCountsSeq] == counts_seq: the counts published last have arrived
         hipEvent_t counts_ev = nullptr;   // h_counts holds the counts of this set's detection
         hipEvent_t tail_done = nullptr;   // the tail of this set's latest detection (sort, emit, counter reset) is through
-        size_t reset_ncell = 0;
+        size_t reset_ncell = 0;           // the detector counters are known to be zero for grids up to this many cells
         bool counters_clean = false;
-        int eo_active = 0;
+        int eo_active = 0;                // the candidate buffer D points at
     } dset[2];
-    hipEvent_t counts_ev = nullptr, tail_done = nullptr;
-    int counts_seq = 0;
+    // the set of the latest detector call (begin, finish, min_eig_map): icelk_detect_fast_stats reports its candidate buffer
+    int dset_last = 0;
     hipStream_t tail_stream = nullptr;     // see detect_finish
-    int dset_cur = 0;
     unsigned long long job_seq = 0;
     hipStream_t eig_stream = nullptr;
     unsigned long long mask_gen = 0;
@@ -215,10 +211,6 @@ struct Ctx {
 
     int last_candidates = 0, last_accepted = 0;   // of the latest detection
     double prune_factor = 8.0;                    // candidates kept per corner wanted (top-K pruning, detect_begin)
-    DetectJob job{};
-    size_t reset_ncell = 0;    // the detector counters are known to be zero for grids up to this many cells
-    bool counters_clean = false;
-    int* h_counts = nullptr;   // pinned, device-visible: {candidates, accepted, undecided} of the job
 
     // profiling
     bool prof = false;
@@ -663,7 +655,74 @@ static hipError_t create_side_streams(Ctx* c)
     return r;
 }
 
-static void det_save(Ctx* c);
+// ---- candidate buffers and detector sets: allocation and release ----------------------------------------------------
+static int alloc_eig_out(Ctx* c, Ctx::EigOut& e, int cand_cap)
+{
+    const int w = c->max_w, h = c->max_h;
+    int rc;
+    if ((rc = dmalloc(c, &e.max_key, 1)) || (rc = dmalloc(c, &e.raw, (size_t)cand_cap)) ||
+        (rc = dmalloc(c, &e.blk_count, candidate_blocks(w, h) * 4)))
+        return rc;
+    // the two-pass detector's scratch (~20 MB per buffer at 12 MP) only on a handle created with its switch set: a
+    // handle without it runs the strip kernel whatever the switch says later (launch_candidates looks at D.acand)
+    if (getenv("ICELK_TWO_PASS_CORNERS") &&
+        ((rc = dmalloc(c, &e.acand, fast_cand_entries(w, h))) || (rc = dmalloc(c, &e.acount, fast_tiles(w, h))) ||
+         (rc = dmalloc(c, &e.amaxc, fast_max_entries(w, h))) || (rc = dmalloc(c, &e.amaxn, fast_tiles(w, h))) ||
+         (rc = dmalloc(c, &e.aemax, fast_tiles(w, h))) || (rc = dmalloc(c, &e.fmax_key, 8)) ||
+         (rc = dmalloc(c, &e.aties, fast_cand_entries(w, h) + fast_tiles(w, h)))))
+        return rc;
+    if (hipEventCreateWithFlags(&e.done, hipEventDisableTiming) != hipSuccess) FAIL(c, ICELK_EHIP, "hipEventCreate failed");
+    return ICELK_OK;
+}
+
+static void free_eig_out(Ctx::EigOut& e)
+{
+    void* p[] = {e.raw, e.blk_count, e.max_key, e.acand, e.acount, e.amaxc, e.amaxn, e.aemax, e.fmax_key, e.aties};
+    for (void* q : p)
+        if (q) hipFree(q);
+    if (e.done) hipEventDestroy(e.done);
+}
+
+// everything a detection in flight owns but its candidate buffer; D.eig is set by the caller (one map for both sets)
+static int alloc_det_set(Ctx* c, Ctx::DetSet& S, int cand_cap)
+{
+    DetectScratch& D = S.D;
+    D.cand_cap = cand_cap;
+    D.sort_tmp_bytes = sort_tmp_bytes(cand_cap);
+    const size_t nc = c->ncell_cap;
+    int rc;
+    if ((rc = dmalloc(c, &D.cand, (size_t)cand_cap)) || (rc = dmalloc(c, &D.cand_count, 1)) ||
+        (rc = dmalloc(c, &D.cell_count, nc)) || (rc = dmalloc(c, &D.cell_start, nc)) || (rc = dmalloc(c, &D.cell_fill, nc)) ||
+        (rc = dmalloc(c, &D.chunk_tot, (nc / 2048 + 2) * 32)) || (rc = dmalloc(c, &D.cell_cand, (size_t)cand_cap)) ||
+        (rc = dmalloc(c, &D.state, (size_t)cand_cap)) || (rc = dmalloc(c, &D.undecided, 64)) ||
+        (rc = dmalloc(c, &D.acc, (size_t)cand_cap)) || (rc = dmalloc(c, &D.acc_sorted, (size_t)cand_cap)) ||
+        (rc = dmalloc(c, &D.acc_count, 1)) || (rc = dmalloc(c, &D.key_hist, 1 << 16)) || (rc = dmalloc(c, &D.prune_key, 1)) ||
+        (rc = dmalloc(c, (uint8_t**)&D.sort_tmp, D.sort_tmp_bytes)) || (rc = dmalloc(c, &D.tail_ctl, TC_WORDS_)) ||
+        (rc = dmalloc(c, &D.tail_resp, tail_resp_words())) || (rc = dmalloc(c, &D.tail_bins, kTailOrderBins + 2)))
+        return rc;
+    if (hipMemset(D.tail_resp, 0, sizeof(int) * tail_resp_words()) != hipSuccess ||
+        hipMemset(D.tail_ctl, 0, sizeof(int) * TC_WORDS_) != hipSuccess ||
+        hipMemset(D.tail_bins, 0, sizeof(int) * (kTailOrderBins + 2)) != hipSuccess)
+        FAIL(c, ICELK_EHIP, "hipMemset failed");
+    if (hipHostMalloc(reinterpret_cast<void**>(&S.h_counts), 64, hipHostMallocMapped) != hipSuccess ||
+        hipEventCreateWithFlags(&S.counts_ev, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&S.tail_done, hipEventDisableTiming) != hipSuccess)
+        FAIL(c, ICELK_EHIP, "hipHostMalloc failed");
+    memset(S.h_counts, 0, 64);
+    return ICELK_OK;
+}
+
+static void free_det_set(Ctx::DetSet& S)
+{
+    const DetectScratch& D = S.D;
+    void* p[] = {D.cand, D.cand_count, D.cell_count, D.cell_start, D.cell_fill, D.chunk_tot, D.cell_cand, D.state, D.undecided,
+                 D.acc, D.acc_sorted, D.acc_count, D.key_hist, D.prune_key, D.sort_tmp, D.tail_ctl, D.tail_resp, D.tail_bins};
+    for (void* q : p)
+        if (q) hipFree(q);
+    if (S.h_counts) hipHostFree(S.h_counts);
+    if (S.counts_ev) hipEventDestroy(S.counts_ev);
+    if (S.tail_done) hipEventDestroy(S.tail_done);
+}
 
 static void destroy_ctx(Ctx* c)
 {
@@ -708,40 +767,11 @@ static void destroy_ctx(Ctx* c)
     }
     for (auto& e : c->launch_ev)
         if (e) hipEventDestroy(e);
-    for (auto& e : c->eo)
-        if (e.done) hipEventDestroy(e.done);
-    det_save(c);
-    for (auto& S : c->dset) {
-        if (S.h_counts) hipHostFree(S.h_counts);
-        if (S.counts_ev) hipEventDestroy(S.counts_ev);
-        if (S.tail_done) hipEventDestroy(S.tail_done);
-    }
-    {
-        DetectScratch& E = c->dset[c->dset_cur ^ 1].D;     // the other set's own arrays (the working copy's are freed below)
-        void* ep[] = {E.cand, E.cand_count, E.cell_count, E.cell_start, E.cell_fill, E.chunk_tot, E.cell_cand, E.state, E.undecided,
-                      E.acc, E.acc_sorted, E.acc_count, E.key_hist, E.prune_key, E.sort_tmp, E.tail_ctl, E.tail_resp, E.tail_bins};
-        for (void* q : ep)
-            if (q) hipFree(q);
-    }
-    for (auto& e : c->eo) {
-        void* fp[] = {e.acand, e.acount, e.amaxc, e.amaxn, e.aemax, e.fmax_key, e.aties};
-        for (void* q : fp)
-            if (q) hipFree(q);
-    }
-    for (auto& e : c->eo) {   // [0] and [1] are in the list below
-        if (&e == &c->eo[2]) {
-            if (e.raw) hipFree(e.raw);
-            if (e.blk_count) hipFree(e.blk_count);
-            if (e.max_key) hipFree(e.max_key);
-        }
-    }
+    for (auto& e : c->eo) free_eig_out(e);
+    for (auto& S : c->dset) free_det_set(S);
     if (c->h_seg) hipHostFree(c->h_seg);
     void* ptrs[] = {c->d_bgr, c->d_mask, c->d_p0, c->d_p1, c->d_p0r, c->d_err_f, c->d_err_b, c->d_dist, c->d_corners,
-                    c->d_st_f, c->d_st_b, c->d_valid, c->D.eig, c->D.cand, c->D.cand_count,
-                    c->D.cell_count, c->D.cell_start, c->D.cell_fill, c->D.chunk_tot, c->D.cell_cand, c->D.state, c->D.undecided,
-                    c->D.acc, c->D.acc_sorted, c->D.acc_count, c->eo[0].raw, c->eo[1].raw, c->eo[0].blk_count, c->eo[1].blk_count,
-                    c->eo[0].max_key, c->eo[1].max_key, c->D.key_hist, c->D.prune_key, c->D.sort_tmp, c->D.tail_ctl,
-                    c->D.tail_resp, c->D.tail_bins, c->d_tracked,
+                    c->d_st_f, c->d_st_b, c->d_valid, c->dset[0].D.eig, c->d_tracked,
                     c->d_out_tracks, c->d_out_quality, c->d_proj, c->d_keep};
     for (void* p : ptrs)
         if (p) hipFree(p);
@@ -796,40 +826,9 @@ __global__ void k_publish_counts(const int* __restrict__ cand, const int* __rest
     __hip_atomic_store(host_out + kCountsSeq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-static void det_save(Ctx* c)
-{
-    Ctx::DetSet& S = c->dset[c->dset_cur];
-    S.D = c->D;
-    S.job = c->job;
-    S.h_counts = c->h_counts;
-    S.counts_seq = c->counts_seq;
-    S.counts_ev = c->counts_ev;
-    S.tail_done = c->tail_done;
-    S.reset_ncell = c->reset_ncell;
-    S.counters_clean = c->counters_clean;
-    S.eo_active = c->eo_active;
-}
-
-static void det_load(Ctx* c, int k)
-{
-    det_save(c);
-    const Ctx::DetSet& S = c->dset[k];
-    c->D = S.D;
-    c->job = S.job;
-    c->h_counts = S.h_counts;
-    c->counts_seq = S.counts_seq;
-    c->counts_ev = S.counts_ev;
-    c->tail_done = S.tail_done;
-    c->reset_ncell = S.reset_ncell;
-    c->counters_clean = S.counters_clean;
-    c->eo_active = S.eo_active;
-    c->dset_cur = k;
-}
-
 // the set of the oldest detection in flight, or -1
-static int det_oldest(Ctx* c)
+static int det_oldest(const Ctx* c)
 {
-    det_save(c);
     int k = -1;
     for (int i = 0; i < 2; i++)
         if (c->dset[i].job.active && (k < 0 || c->dset[i].job.seq < c->dset[k].job.seq)) k = i;
@@ -837,44 +836,82 @@ static int det_oldest(Ctx* c)
 }
 
 // a set with no detection in flight, or -1
-static int det_free(Ctx* c)
+static int det_free(const Ctx* c)
 {
-    det_save(c);
     for (int i = 0; i < 2; i++)
         if (!c->dset[i].job.active) return i;
     return -1;
 }
 
+// what a candidate buffer must hold to serve a detection of `slot` as it is now
+static Ctx::EigOut eo_want(const Ctx* c, int slot, int use_mask, int block_size)
+{
+    Ctx::EigOut want;
+    want.slot = slot;
+    want.gen = c->slots[slot].gen;
+    want.block_size = block_size;
+    want.use_mask = use_mask;
+    want.mask_gen = c->mask_gen;
+    return want;
+}
+
+// does e hold the prepared candidates `want` asks for (slot, frame generation, blockSize, mask, mask generation)?
+static bool eo_holds(const Ctx::EigOut& e, const Ctx::EigOut& want)
+{
+    return e.valid && e.slot == want.slot && e.gen == want.gen && e.block_size == want.block_size &&
+           e.use_mask == want.use_mask && e.mask_gen == want.mask_gen;
+}
+
 // a candidate buffer no detection in flight reads: the one that holds what `want` asks for if there is one, else one
 // without valid content, else any
-static int eo_free(Ctx* c, const Ctx::EigOut* want)
+static int eo_free(const Ctx* c, const Ctx::EigOut& want)
 {
-    det_save(c);
     bool busy[3] = {false, false, false};
-    for (int i = 0; i < 2; i++)
-        if (c->dset[i].job.active) busy[c->dset[i].eo_active] = true;
+    for (const auto& S : c->dset)
+        if (S.job.active) busy[S.eo_active] = true;
     int pick = -1;
     for (int i = 0; i < 3; i++) {
         if (busy[i]) continue;
         const Ctx::EigOut& e = c->eo[i];
-        if (want && e.valid && e.slot == want->slot && e.gen == want->gen && e.block_size == want->block_size &&
-            e.use_mask == want->use_mask && e.mask_gen == want->mask_gen)
-            return i;
+        if (eo_holds(e, want)) return i;
         if (pick < 0 || (c->eo[pick].valid && !e.valid)) pick = i;
     }
     return pick;
 }
 
-// The counts of the working set's detection go to its pinned host words behind whatever is queued on the detection
-// stream, and an event of the set marks them.  detect_begin ends with this, so the host round trip of that detection
-// waits for ITS kernels only -- not for the min-distance stage of the next detection that may be queued behind them.
-static int publish_counts(Ctx* c)
+// point a detector scratch at candidate buffer e: the stages read (and the non-prepared corner kernel writes) e
+static void point_at_eig_out(DetectScratch& D, const Ctx::EigOut& e)
 {
-    const DetectJob& J = c->job;
-    c->counts_seq = (c->counts_seq + 1) & 0x3fffffff;
-    hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(1), 0, c->det_stream, J.cand_count_ptr, c->D.acc_count,
-                       c->D.undecided + suppress_launch_count() - 1, c->D.prune_key, c->h_counts, c->counts_seq);
-    HIPCHK(c, hipEventRecord(c->counts_ev, c->det_stream));
+    D.raw = e.raw;
+    D.blk_count = e.blk_count;
+    D.max_key = e.max_key;
+    D.acand = e.acand;
+    D.acount = e.acount;
+    D.amaxc = e.amaxc;
+    D.amaxn = e.amaxn;
+    D.aemax = e.aemax;
+    D.fmax_key = e.fmax_key;
+    D.aties = e.aties;
+    D.src_nblk = e.nblk;
+    D.src_region = e.region;
+}
+
+// make eo[idx] the candidate buffer of set S
+static void activate_eig_out(Ctx* c, Ctx::DetSet& S, int idx)
+{
+    S.eo_active = idx;
+    point_at_eig_out(S.D, c->eo[idx]);
+}
+
+// The counts of set S's detection go to its pinned host words behind whatever is queued on the detection stream, and
+// an event of the set marks them.  detect_begin ends with this, so the host round trip of that detection waits for
+// ITS kernels only -- not for the min-distance stage of the next detection that may be queued behind them.
+static int publish_counts(Ctx* c, Ctx::DetSet& S)
+{
+    S.counts_seq = (S.counts_seq + 1) & 0x3fffffff;
+    hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(1), 0, c->det_stream, S.job.cand_count_ptr, S.D.acc_count,
+                       S.D.undecided + suppress_launch_count() - 1, S.D.prune_key, S.h_counts, S.counts_seq);
+    HIPCHK(c, hipEventRecord(S.counts_ev, c->det_stream));
     return ICELK_OK;
 }
 
@@ -886,18 +923,18 @@ static inline bool counts_here(const int* h_counts, int seq)
 
 // Waits for the counts by polling the pinned sequence word; the event is looked at now and then, so that a failed
 // kernel ends the wait with its error instead of hanging it (ICELK_EVENT_WAIT=1: hipEventSynchronize, as before).
-static int fetch_counts(Ctx* c, bool published = false)
+static int fetch_counts(Ctx* c, Ctx::DetSet& S, bool published = false)
 {
     if (!published) {
-        int rc = publish_counts(c);
+        int rc = publish_counts(c, S);
         if (rc) return rc;
     }
     static const bool by_event = getenv("ICELK_EVENT_WAIT") != nullptr;
     if (!by_event) {
         for (unsigned it = 1;; it++) {
-            if (counts_here(c->h_counts, c->counts_seq)) return ICELK_OK;
+            if (counts_here(S.h_counts, S.counts_seq)) return ICELK_OK;
             if ((it & 4095u) == 0) {
-                const hipError_t q = hipEventQuery(c->counts_ev);
+                const hipError_t q = hipEventQuery(S.counts_ev);
                 if (q == hipSuccess) break;             // complete: the synchronize below returns at once
                 if (q != hipErrorNotReady) HIPCHK(c, q);
                 (void)hipGetLastError();
@@ -905,27 +942,8 @@ static int fetch_counts(Ctx* c, bool published = false)
             __builtin_ia32_pause();
         }
     }
-    HIPCHK(c, hipEventSynchronize(c->counts_ev));
+    HIPCHK(c, hipEventSynchronize(S.counts_ev));
     return ICELK_OK;
-}
-
-// make eo[idx] the buffer the detector stages read (and the non-prepared corner kernel writes)
-static void activate_eig_out(Ctx* c, int idx)
-{
-    c->eo_active = idx;
-    const Ctx::EigOut& e = c->eo[idx];
-    c->D.raw = e.raw;
-    c->D.blk_count = e.blk_count;
-    c->D.max_key = e.max_key;
-    c->D.acand = e.acand;
-    c->D.acount = e.acount;
-    c->D.amaxc = e.amaxc;
-    c->D.amaxn = e.amaxn;
-    c->D.aemax = e.aemax;
-    c->D.fmax_key = e.fmax_key;
-    c->D.aties = e.aties;
-    c->D.src_nblk = e.nblk;
-    c->D.src_region = e.region;
 }
 
 // Corner candidates of a frame ahead of its detection (fused kernel only; anything else is left to
@@ -944,31 +962,15 @@ static int detect_prepare(Ctx* c, int slot, int use_mask, int block_size)
         if (c->mask_w != s.w || c->mask_h != s.h) FAIL(c, ICELK_EARG, "mask size differs from the frame");
         mask = c->d_mask;
     }
-    Ctx::EigOut want;
-    want.slot = slot;
-    want.gen = s.gen;
-    want.block_size = block_size;
-    want.use_mask = use_mask;
-    want.mask_gen = c->mask_gen;
-    Ctx::EigOut& e = c->eo[eo_free(c, &want)];
-    if (e.valid && e.slot == slot && e.gen == s.gen && e.block_size == block_size && e.use_mask == use_mask &&
-        e.mask_gen == c->mask_gen)
-        return ICELK_OK;   // already there
+    const Ctx::EigOut want = eo_want(c, slot, use_mask, block_size);
+    Ctx::EigOut& e = c->eo[eo_free(c, want)];
+    if (eo_holds(e, want)) return ICELK_OK;   // already there
     const hipStream_t es = c->eig_stream;
     // level 0 only: `ready` would also wait for a pyramid built ahead, which the detector never reads
     if (int rcw = wait_event(c, es, s.frame_ev)) return rcw;
     HIPCHK(c, hipMemsetAsync(e.max_key, 0, sizeof(unsigned), es));
-    DetectScratch T = c->D;
-    T.raw = e.raw;
-    T.blk_count = e.blk_count;
-    T.max_key = e.max_key;
-    T.acand = e.acand;
-    T.acount = e.acount;
-    T.amaxc = e.amaxc;
-    T.amaxn = e.amaxn;
-    T.aemax = e.aemax;
-    T.fmax_key = e.fmax_key;
-    T.aties = e.aties;
+    DetectScratch T{};   // the corner kernel touches the candidate buffer only
+    point_at_eig_out(T, e);
     // the quality level is not known yet: the one of the latest detection begun on this handle is taken (0 at first: every
     // local maximum gets its exact key); detect_begin adopts the result only if its own level is not lower
     const double prep_quality = c->prep_quality;
@@ -1003,11 +1005,10 @@ static int detect_begin(Ctx* c, int slot, int use_mask, int max_corners, double 
     if (rc) return rc;
     if (!(quality > 0) || min_distance < 0 || block_size <= 0) FAIL(c, ICELK_EARG, "bad detector parameters");
     if (min_eig_lds_bytes(block_size) > 150 * 1024) FAIL(c, ICELK_EARG, "blockSize too large");
-    {
-        const int k = det_free(c);
-        if (k < 0) FAIL(c, ICELK_ESTATE, "two detections are in flight already");
-        det_load(c, k);
-    }
+    const int k = det_free(c);
+    if (k < 0) FAIL(c, ICELK_ESTATE, "two detections are in flight already");
+    c->dset_last = k;
+    Ctx::DetSet& S = c->dset[k];
     Slot& s = c->slots[slot];
     const hipStream_t ds = c->det_stream;
     const int w = s.w, h = s.h;
@@ -1017,7 +1018,7 @@ static int detect_begin(Ctx* c, int slot, int use_mask, int max_corners, double 
         if (c->mask_w != w || c->mask_h != h) FAIL(c, ICELK_EARG, "mask size differs from the frame");
         mask = c->d_mask;
     }
-    DetectScratch& D = c->D;
+    DetectScratch& D = S.D;
     size_t ncell = 0;
     if (min_distance >= 1) {
         const int cell = (int)lrint(min_distance);
@@ -1029,42 +1030,36 @@ static int detect_begin(Ctx* c, int slot, int use_mask, int max_corners, double 
     // the frame must be in the slot, and the tail of this set's previous detection (it sorted this set's accepted keys and
     // reset its counters on the tail stream) must be through
     if (int rcw = wait_event(c, ds, s.frame_ev)) return rcw;   // level 0 only (see detect_prepare)
-    if (int rcw = wait_event(c, ds, c->tail_done)) return rcw;
+    if (int rcw = wait_event(c, ds, S.tail_done)) return rcw;
     const bool generic = getenv("ICELK_GENERIC_CORNERS") != nullptr || c->corner_variant != 0;
     // counters are normally left zeroed by the previous detection (the reset runs after its last kernel,
     // off the critical path); reset here only the first time or when the cell grid grew
-    const bool need_reset = !c->counters_clean || ncell > c->reset_ncell;
-    Ctx::EigOut want;
-    want.slot = slot;
-    want.gen = s.gen;
-    want.block_size = block_size;
-    want.use_mask = use_mask;
-    want.mask_gen = c->mask_gen;
-    const int spare_idx = eo_free(c, &want);
+    const bool need_reset = !S.counters_clean || ncell > S.reset_ncell;
+    const Ctx::EigOut want = eo_want(c, slot, use_mask, block_size);
+    const int spare_idx = eo_free(c, want);
     Ctx::EigOut& spare = c->eo[spare_idx];
-    const bool prepared = spare.valid && spare.slot == slot && spare.gen == s.gen && spare.block_size == block_size &&
-                          spare.use_mask == use_mask && spare.mask_gen == c->mask_gen && !generic && spare.quality <= quality;
+    const bool prepared = eo_holds(spare, want) && !generic && spare.quality <= quality;
     c->prep_quality = quality;
     spare.valid = false;   // adopted below, or overwritten: either way it is not offered again
     if (prepared) {
         if (need_reset) launch_detect_reset(ds, D, (int)ncell, 1);
-        activate_eig_out(c, spare_idx);
+        activate_eig_out(c, S, spare_idx);
         if (int rcw = wait_event(c, ds, spare.done)) return rcw;
     } else {
         ProfScope p(c, K_EIG, ds);
         // this detection's candidates go into a buffer no detection in flight reads; a prepare launch that wrote it
         // (for another frame) must be through, and its maximum starts from zero
-        activate_eig_out(c, spare_idx);
+        activate_eig_out(c, S, spare_idx);
         if (int rcw = wait_event(c, ds, spare.done)) return rcw;
         HIPCHK(c, hipMemsetAsync(spare.max_key, 0, sizeof(unsigned), ds));
         if (need_reset) launch_detect_reset(ds, D, (int)ncell, 1);
         launch_candidates(ds, D, s.lv[0], block_size, mask, c->mask_pitch, quality, generic, nullptr, c->corner_variant);
         HIPCHK(c, hipEventRecord(s.det_used, ds));   // nothing after this launch reads the frame
     }
-    c->counters_clean = false;
+    S.counters_clean = false;
     rc = check_launch(c, "corner candidates");
     if (rc) return rc;
-    DetectJob& J = c->job;
+    DetectJob& J = S.job;
     J.w = w;
     J.h = h;
     J.quality = quality;
@@ -1096,27 +1091,27 @@ static int detect_begin(Ctx* c, int slot, int use_mask, int max_corners, double 
     if (dev_tail) {
         // the set the new segment goes into: behind the current one, the staged one and the one the other detection in
         // flight has reserved (segments are staged and switched to in the order their detections were begun)
-        const Ctx::DetSet& other = c->dset[c->dset_cur ^ 1];
+        const Ctx::DetSet& other = c->dset[k ^ 1];
         const int ahead = (c->seg_staged ? 1 : 0) + (other.job.active ? 1 : 0);
         const int target = (c->sb_cur + 1 + ahead) % kSegSets;
         Ctx::SegBuf& nb = c->sb[target];
         // launches that still touch that set (a segment closed several switches ago) must be through
         if (int rcw = wait_event(c, ds, nb.used)) return rcw;
-        c->counts_seq = (c->counts_seq + 1) & 0x3fffffff;
+        S.counts_seq = (S.counts_seq + 1) & 0x3fffffff;
         {
             ProfScope p(c, K_EMIT, ds);
             launch_tail_device(ds, D, quality, nb.live, nb.alive, nb.tracks, kMaxVert, c->use_order ? nb.order : nullptr,
                                nb.order_border, tail_order_geometry(w, h, c->border_px), tail_reset_of(D, (int)ncell),
-                               c->h_counts, kCountsSeq, c->counts_seq);
+                               S.h_counts, kCountsSeq, S.counts_seq);
         }
         rc = check_launch(c, "tail (device-driven)");
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(nb.ready, ds));
-        HIPCHK(c, hipEventRecord(c->counts_ev, ds));
+        HIPCHK(c, hipEventRecord(S.counts_ev, ds));
         J.dev_tail = true;
         J.seg_set = target;
     } else {
-        rc = publish_counts(c);
+        rc = publish_counts(c, S);
         if (rc) return rc;
     }
     J.active = true;
@@ -1127,43 +1122,44 @@ static int detect_begin(Ctx* c, int slot, int use_mask, int max_corners, double 
 // seg != null (seg_stage): the corners start a segment in that set -- corner list, the segment's tables and the counter
 // reset go out as ONE launch (k_tail) instead of three; *seg_done tells seg_stage that the tables are written
 // *dev_done: the device-driven tail has written everything (tables AND launch order): nothing is left to enqueue
+// *finished: the job of the detection finished here (the oldest in flight)
 static int detect_finish(Ctx* c, int max_corners, int cap, int* n_out, Ctx::SegBuf* seg = nullptr, bool* seg_done = nullptr,
-                         bool* dev_done = nullptr)
+                         bool* dev_done = nullptr, DetectJob* finished = nullptr)
 {
     Range rg("icelk detect_finish (host round trip, sort, corner list)");
     if (seg_done) *seg_done = false;
     if (dev_done) *dev_done = false;
-    {
-        const int k = det_oldest(c);
-        if (k < 0) FAIL(c, ICELK_ESTATE, "no detection in flight");
-        det_load(c, k);
-    }
-    DetectJob& J = c->job;
+    const int k = det_oldest(c);
+    if (k < 0) FAIL(c, ICELK_ESTATE, "no detection in flight");
+    c->dset_last = k;
+    Ctx::DetSet& S = c->dset[k];
+    DetectJob& J = S.job;
     J.active = false;
+    if (finished) *finished = J;
     *n_out = 0;
     const hipStream_t ds = c->det_stream;
     // Everything behind the host round trip -- sort, corner list, the reset of this set's counters, and in seg_stage the
     // new segment's tables -- goes to the tail stream: the detection stream may already hold the min-distance stage of
     // the NEXT detection (the other set), and the two have nothing in common but d_corners, which only tails touch.
     const hipStream_t ts = c->tail_stream;
-    DetectScratch& D = c->D;
-    int rc = fetch_counts(c, true);   // the one host round trip of a detection: {candidates, accepted, undecided}
+    DetectScratch& D = S.D;
+    int rc = fetch_counts(c, S, true);   // the one host round trip of a detection: {candidates, accepted, undecided}
     if (rc) return rc;
     if (J.dev_tail) {
         // the tail ran on the device already; the host adopts its verdict
-        const int status = c->h_counts[5];
+        const int status = S.h_counts[5];
         if (!seg || seg != &c->sb[J.seg_set] || max_corners != J.max_corners)
             FAIL(c, ICELK_ESTATE, "the segment staged is not the one its detection was begun for (set / maxCorners differ)");
         if (status == TAIL_OVERFLOW) FAIL(c, ICELK_ECAP, "more corners than the output capacity (raise max_pts)");
         if (status == TAIL_OK) {
-            const int total = c->h_counts[1], n = c->h_counts[4];
+            const int total = S.h_counts[1], n = S.h_counts[4];
             if (n > cap) FAIL(c, ICELK_ECAP, "more corners than the output capacity (raise max_pts)");
             if (J.prune_want > 0 && max_corners > 0)
-                c->prune_factor = !c->h_counts[3] || total <= 0 ? 8.0 : std::min(8.0, std::max(2.0, 1.5 * (double)c->h_counts[0] / total));
-            c->last_candidates = c->h_counts[0];
+                c->prune_factor = !S.h_counts[3] || total <= 0 ? 8.0 : std::min(8.0, std::max(2.0, 1.5 * (double)S.h_counts[0] / total));
+            c->last_candidates = S.h_counts[0];
             c->last_accepted = total;
-            c->reset_ncell = J.ncell;
-            c->counters_clean = true;    // k_tail_order left them zeroed
+            S.reset_ncell = J.ncell;
+            S.counters_clean = true;    // k_tail_order left them zeroed
             c->tails_dev++;
             *n_out = n;
             if (seg_done) *seg_done = true;
@@ -1177,39 +1173,39 @@ static int detect_finish(Ctx* c, int max_corners, int cap, int* n_out, Ctx::SegB
     int total = 0;
     if (J.min_distance >= 1) {
         auto converge = [&]() -> int {
-            for (int guard = 0; c->h_counts[2] != 0; guard++) {
+            for (int guard = 0; S.h_counts[2] != 0; guard++) {
                 if (guard > 100000) FAIL(c, ICELK_EHIP, "min-distance suppression did not converge");
                 continue_min_distance(ds, D, J.w, J.h, J.min_distance);
-                int r = fetch_counts(c);
+                int r = fetch_counts(c, S);
                 if (r) return r;
             }
             return ICELK_OK;
         };
         if ((rc = converge())) return rc;
         bool redone = false;
-        if (J.prune_want > 0 && c->h_counts[3] && (max_corners <= 0 || c->h_counts[1] < max_corners)) {
+        if (J.prune_want > 0 && S.h_counts[3] && (max_corners <= 0 || S.h_counts[1] < max_corners)) {
             // the pruned candidate set did not yield maxCorners corners: redo the stage on all candidates
             redone = true;
             launch_detect_reset(ds, D, (int)J.ncell, 0);
             launch_min_distance(ds, D, J.w, J.h, J.min_distance, J.quality, 0);
             if ((rc = check_launch(c, "min_distance (unpruned)"))) return rc;
-            if ((rc = fetch_counts(c))) return rc;
+            if ((rc = fetch_counts(c, S))) return rc;
             if ((rc = converge())) return rc;
         }
-        total = c->h_counts[1];
+        total = S.h_counts[1];
         if (J.prune_want > 0 && max_corners > 0) {
             // next time: candidates per accepted corner as seen now, and half as many again; a detection that fell short
             // (it was redone above) or was not pruned at all starts over at 8x
-            const bool fell_short = !c->h_counts[3] || redone;
-            c->prune_factor = fell_short || total <= 0 ? 8.0 : std::min(8.0, std::max(2.0, 1.5 * (double)c->h_counts[0] / total));
+            const bool fell_short = !S.h_counts[3] || redone;
+            c->prune_factor = fell_short || total <= 0 ? 8.0 : std::min(8.0, std::max(2.0, 1.5 * (double)S.h_counts[0] / total));
         }
-        c->last_candidates = c->h_counts[0];
+        c->last_candidates = S.h_counts[0];
         c->last_accepted = total;
         if (total == 0) return ICELK_OK;
         sort_keys_desc(ts, D, D.acc, D.acc_sorted, total);
         sorted = D.acc_sorted;
     } else {
-        total = c->h_counts[0];
+        total = S.h_counts[0];
         c->last_candidates = total;
         c->last_accepted = total;
         if (total == 0) return ICELK_OK;
@@ -1232,7 +1228,7 @@ static int detect_finish(Ctx* c, int max_corners, int cap, int* n_out, Ctx::SegB
         rc = check_launch(c, "tail");
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->det_done, ts));
-        HIPCHK(c, hipEventRecord(c->tail_done, ts));
+        HIPCHK(c, hipEventRecord(S.tail_done, ts));
         *seg_done = true;
     } else {
         {
@@ -1243,10 +1239,10 @@ static int detect_finish(Ctx* c, int max_corners, int cap, int* n_out, Ctx::SegB
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->det_done, ts));
         launch_detect_reset(ts, D, (int)J.ncell, 1);   // for this set's next detection, which waits for tail_done
-        HIPCHK(c, hipEventRecord(c->tail_done, ts));
+        HIPCHK(c, hipEventRecord(S.tail_done, ts));
     }
-    c->reset_ncell = J.ncell;
-    c->counters_clean = true;
+    S.reset_ncell = J.ncell;
+    S.counters_clean = true;
     *n_out = n;
     return ICELK_OK;
 }
@@ -1598,16 +1594,12 @@ int icelk_create(int device, int max_w, int max_h, int n_slots, int max_pts, ice
         hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->copy_stream2, hipStreamNonBlocking) != hipSuccess ||
         create_side_streams(c) != hipSuccess ||
-        hipEventCreateWithFlags(&c->eo[0].done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->eo[1].done, hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&c->h_counts), 64, hipHostMallocMapped) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(&c->h_seg), 64, hipHostMallocMapped) != hipSuccess ||
         hipEventCreateWithFlags(&c->det_done, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->corners_free, hipEventDisableTiming) != hipSuccess) {
         c->err = "hipStreamCreate failed";
         return fail(ICELK_EHIP);
     }
-    memset(c->h_counts, 0, 64);
     c->stream = c->own_stream;
     c->slots.resize(n_slots);
     const size_t sb = slot_bytes(max_w, max_h);
@@ -1646,29 +1638,14 @@ int icelk_create(int device, int max_w, int max_h, int n_slots, int max_pts, ice
     c->bgr_pitch = align_up(3 * max_w, kPitchAlign);
     c->mask_pitch = align_up(max_w, kPitchAlign);
     const size_t np = (size_t)max_pts;
-    DetectScratch& D = c->D;
-    D.cand_cap = (int)std::min<size_t>(candidate_capacity(max_w, max_h), (size_t)1 << 30);
+    const int cand_cap = (int)std::min<size_t>(candidate_capacity(max_w, max_h), (size_t)1 << 30);
     c->ncell_cap = npx + 1;
-    D.sort_tmp_bytes = sort_tmp_bytes(D.cand_cap);
     if ((rc = dmalloc(c, &c->d_bgr, (size_t)c->bgr_pitch * max_h)) || (rc = dmalloc(c, &c->d_mask, (size_t)c->mask_pitch * max_h)) ||
         (rc = dmalloc(c, &c->d_p0, 2 * np)) || (rc = dmalloc(c, &c->d_p1, 2 * np)) || (rc = dmalloc(c, &c->d_p0r, 2 * np)) ||
         (rc = dmalloc(c, &c->d_err_f, np)) || (rc = dmalloc(c, &c->d_err_b, np)) || (rc = dmalloc(c, &c->d_dist, np)) ||
         (rc = dmalloc(c, &c->d_corners, 2 * np)) || (rc = dmalloc(c, &c->d_st_f, np)) || (rc = dmalloc(c, &c->d_st_b, np)) ||
-        (rc = dmalloc(c, &c->d_valid, np)) || (rc = dmalloc(c, &D.eig, npx)) || (rc = dmalloc(c, &c->eo[0].max_key, 1)) || (rc = dmalloc(c, &c->eo[1].max_key, 1)) ||
-        (rc = dmalloc(c, &c->eo[0].raw, (size_t)D.cand_cap)) || (rc = dmalloc(c, &c->eo[1].raw, (size_t)D.cand_cap)) ||
-        (rc = dmalloc(c, &D.cand, (size_t)D.cand_cap)) || (rc = dmalloc(c, &D.cand_count, 1)) ||
-        (rc = dmalloc(c, &D.cell_count, c->ncell_cap)) || (rc = dmalloc(c, &D.cell_start, c->ncell_cap)) ||
-        (rc = dmalloc(c, &D.cell_fill, c->ncell_cap)) || (rc = dmalloc(c, &D.chunk_tot, (c->ncell_cap / 2048 + 2) * 32)) || (rc = dmalloc(c, &D.cell_cand, (size_t)D.cand_cap)) ||
-        (rc = dmalloc(c, &D.state, (size_t)D.cand_cap)) || (rc = dmalloc(c, &D.undecided, 64)) ||
-        (rc = dmalloc(c, &D.acc, (size_t)D.cand_cap)) ||
-        (rc = dmalloc(c, &D.acc_sorted, (size_t)D.cand_cap)) ||
-        (rc = dmalloc(c, &D.acc_count, 1)) || (rc = dmalloc(c, &c->eo[0].blk_count, candidate_blocks(max_w, max_h) * 4)) ||
-        (rc = dmalloc(c, &c->eo[1].blk_count, candidate_blocks(max_w, max_h) * 4)) ||
-        (rc = dmalloc(c, &D.key_hist, 1 << 16)) || (rc = dmalloc(c, &D.prune_key, 1)) || (rc = dmalloc(c, (uint8_t**)&D.sort_tmp, D.sort_tmp_bytes)) ||
-        (rc = dmalloc(c, &D.tail_ctl, TC_WORDS_)) || (rc = dmalloc(c, &D.tail_resp, tail_resp_words())) ||
-        (rc = dmalloc(c, &D.tail_bins, kTailOrderBins + 2)) ||
-        (rc = dmalloc(c, &c->d_tracked, 64)) || (rc = dmalloc(c, &c->d_out_tracks, np * kMaxVert * 2)) ||
-        (rc = dmalloc(c, &c->d_out_quality, np * (kMaxVert - 1))))
+        (rc = dmalloc(c, &c->d_valid, np)) || (rc = dmalloc(c, &c->dset[0].D.eig, npx)) || (rc = dmalloc(c, &c->d_tracked, 64)) ||
+        (rc = dmalloc(c, &c->d_out_tracks, np * kMaxVert * 2)) || (rc = dmalloc(c, &c->d_out_quality, np * (kMaxVert - 1))))
         return fail(rc);
     for (auto& S : c->sb)
         if ((rc = dmalloc(c, &S.live, 2 * np)) || (rc = dmalloc(c, &S.alive, np)) || (rc = dmalloc(c, &S.order, np)) ||
@@ -1702,68 +1679,15 @@ int icelk_create(int device, int max_w, int max_h, int n_slots, int max_pts, ice
         if (!strcmp(k, "generic")) c->lk_kernel_flags = ICELK_FLAG_GENERIC_KERNEL;
         else if (!strcmp(k, "multi")) c->lk_kernel_flags = ICELK_FLAG_MULTI_PER_WAVE;
     }
-    // the third candidate buffer, and the second detector set (everything a detection in flight owns; the full-frame
-    // eigenvalue map of icelk_min_eig_map is shared)
-    if ((rc = dmalloc(c, &c->eo[2].max_key, 1)) || (rc = dmalloc(c, &c->eo[2].raw, (size_t)D.cand_cap)) ||
-        (rc = dmalloc(c, &c->eo[2].blk_count, candidate_blocks(max_w, max_h) * 4)))
-        return fail(rc);
-    // the two-pass detector's scratch (three sets, ~20 MB each at 12 MP) only on a handle created with its switch set: a
-    // handle without it runs the strip kernel whatever the switch says later (launch_candidates looks at D.acand)
-    if (getenv("ICELK_TWO_PASS_CORNERS"))
-      for (auto& e : c->eo)
-        if ((rc = dmalloc(c, &e.acand, fast_cand_entries(max_w, max_h))) || (rc = dmalloc(c, &e.acount, fast_tiles(max_w, max_h))) ||
-            (rc = dmalloc(c, &e.amaxc, fast_max_entries(max_w, max_h))) || (rc = dmalloc(c, &e.amaxn, fast_tiles(max_w, max_h))) ||
-            (rc = dmalloc(c, &e.aemax, fast_tiles(max_w, max_h))) || (rc = dmalloc(c, &e.fmax_key, 8)) ||
-            (rc = dmalloc(c, &e.aties, fast_cand_entries(max_w, max_h) + fast_tiles(max_w, max_h))))
-            return fail(rc);
-    if (hipEventCreateWithFlags(&c->eo[2].done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->counts_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->tail_done, hipEventDisableTiming) != hipSuccess) {
-        c->err = "hipEventCreate failed";
-        return fail(ICELK_EHIP);
-    }
-    activate_eig_out(c, 0);
-    det_save(c);                       // set 0 = what has been allocated so far
-    {
-        Ctx::DetSet& S = c->dset[1];
-        DetectScratch& E = S.D;
-        E = c->D;
-        E.cand = nullptr; E.cand_count = nullptr; E.cell_count = nullptr; E.cell_start = nullptr; E.cell_fill = nullptr;
-        E.chunk_tot = nullptr; E.cell_cand = nullptr; E.state = nullptr; E.undecided = nullptr; E.acc = nullptr;
-        E.acc_sorted = nullptr; E.acc_count = nullptr; E.key_hist = nullptr; E.prune_key = nullptr; E.sort_tmp = nullptr;
-        E.tail_ctl = nullptr; E.tail_resp = nullptr; E.tail_bins = nullptr;
-        if ((rc = dmalloc(c, &E.cand, (size_t)D.cand_cap)) || (rc = dmalloc(c, &E.cand_count, 1)) ||
-            (rc = dmalloc(c, &E.cell_count, c->ncell_cap)) || (rc = dmalloc(c, &E.cell_start, c->ncell_cap)) ||
-            (rc = dmalloc(c, &E.cell_fill, c->ncell_cap)) || (rc = dmalloc(c, &E.chunk_tot, (c->ncell_cap / 2048 + 2) * 32)) ||
-            (rc = dmalloc(c, &E.cell_cand, (size_t)D.cand_cap)) || (rc = dmalloc(c, &E.state, (size_t)D.cand_cap)) ||
-            (rc = dmalloc(c, &E.undecided, 64)) || (rc = dmalloc(c, &E.acc, (size_t)D.cand_cap)) ||
-            (rc = dmalloc(c, &E.acc_sorted, (size_t)D.cand_cap)) || (rc = dmalloc(c, &E.acc_count, 1)) ||
-            (rc = dmalloc(c, &E.key_hist, 1 << 16)) || (rc = dmalloc(c, &E.prune_key, 1)) ||
-            (rc = dmalloc(c, (uint8_t**)&E.sort_tmp, D.sort_tmp_bytes)) || (rc = dmalloc(c, &E.tail_ctl, TC_WORDS_)) ||
-            (rc = dmalloc(c, &E.tail_resp, tail_resp_words())) || (rc = dmalloc(c, &E.tail_bins, kTailOrderBins + 2)))
-            return fail(rc);
-        if (hipMemset(E.tail_resp, 0, sizeof(int) * tail_resp_words()) != hipSuccess ||
-            hipMemset(c->D.tail_resp, 0, sizeof(int) * tail_resp_words()) != hipSuccess ||
-            hipMemset(E.tail_ctl, 0, sizeof(int) * TC_WORDS_) != hipSuccess ||
-            hipMemset(E.tail_bins, 0, sizeof(int) * (kTailOrderBins + 2)) != hipSuccess ||
-            hipMemset(c->D.tail_ctl, 0, sizeof(int) * TC_WORDS_) != hipSuccess ||
-            hipMemset(c->D.tail_bins, 0, sizeof(int) * (kTailOrderBins + 2)) != hipSuccess) {
-            c->err = "hipMemset failed";
-            return fail(ICELK_EHIP);
-        }
-        if (hipHostMalloc(reinterpret_cast<void**>(&S.h_counts), 64, hipHostMallocMapped) != hipSuccess ||
-            hipEventCreateWithFlags(&S.counts_ev, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&S.tail_done, hipEventDisableTiming) != hipSuccess) {
-            c->err = "hipHostMalloc failed";
-            return fail(ICELK_EHIP);
-        }
-        memset(S.h_counts, 0, 64);
-        S.eo_active = 1;
-        E.raw = c->eo[1].raw;
-        E.blk_count = c->eo[1].blk_count;
-        E.max_key = c->eo[1].max_key;
-        E.acand = c->eo[1].acand; E.acount = c->eo[1].acount; E.amaxc = c->eo[1].amaxc; E.amaxn = c->eo[1].amaxn;
-        E.aemax = c->eo[1].aemax; E.fmax_key = c->eo[1].fmax_key; E.aties = c->eo[1].aties;
+    // three candidate buffers and two detector sets (everything a detection in flight owns; the full-frame eigenvalue
+    // map of icelk_min_eig_map is shared)
+    for (auto& e : c->eo)
+        if ((rc = alloc_eig_out(c, e, cand_cap))) return fail(rc);
+    for (int k = 0; k < 2; k++) {
+        Ctx::DetSet& S = c->dset[k];
+        S.D.eig = c->dset[0].D.eig;
+        if ((rc = alloc_det_set(c, S, cand_cap))) return fail(rc);
+        activate_eig_out(c, S, k);
     }
     if (hipMemset(c->d_tracked, 0, 64 * 8) != hipSuccess) {
         c->err = "hipMemset failed";
@@ -1773,11 +1697,12 @@ int icelk_create(int device, int max_w, int max_h, int n_slots, int max_pts, ice
     // ~8 ms (the code object of k_sort.hip is loaded then).  With the device-driven tail that first time was some
     // detection in the MIDDLE of a run -- the first one the device handed back -- and a 64-pair batch lasted 26 ms instead
     // of 17 (profiles/r04_c3_stall.txt).  Paid here instead: 64 keys through the sort, once per handle.
-    if (hipMemsetAsync(c->D.acc, 0, 64 * sizeof(unsigned long long), c->tail_stream) != hipSuccess) {
+    DetectScratch& D0 = c->dset[0].D;
+    if (hipMemsetAsync(D0.acc, 0, 64 * sizeof(unsigned long long), c->tail_stream) != hipSuccess) {
         c->err = "hipMemset failed";
         return fail(ICELK_EHIP);
     }
-    sort_keys_desc(c->tail_stream, c->D, c->D.acc, c->D.acc_sorted, 64);
+    sort_keys_desc(c->tail_stream, D0, D0.acc, D0.acc_sorted, 64);
     if (hipStreamSynchronize(c->tail_stream) != hipSuccess) {
         c->err = "warm-up sort failed";
         return fail(ICELK_EHIP);
@@ -2295,27 +2220,26 @@ int icelk_min_eig_map(icelk_t* h, int slot, int block_size, float* host_out, int
     if (min_eig_lds_bytes(block_size) > 150 * 1024) FAIL(c, ICELK_EARG, "blockSize too large");
     rc = wait_slot(c, slot);
     if (rc) return rc;
-    {
-        const int k = det_free(c);     // scratch of a set no detection in flight owns
-        if (k < 0) FAIL(c, ICELK_ESTATE, "two detections are in flight");
-        det_load(c, k);
-    }
+    const int k = det_free(c);     // scratch of a set no detection in flight owns
+    if (k < 0) FAIL(c, ICELK_ESTATE, "two detections are in flight");
+    c->dset_last = k;
+    Ctx::DetSet& S = c->dset[k];
     HIPCHK(c, hipStreamSynchronize(c->stream));       // the frame is in place
     HIPCHK(c, hipStreamSynchronize(c->det_stream));   // the detector scratch is free
     HIPCHK(c, hipStreamSynchronize(c->tail_stream));
     {
         ProfScope p(c, K_EIG);
-        launch_detect_reset(c->stream, c->D, 0, 3);
-        c->counters_clean = false;
+        launch_detect_reset(c->stream, S.D, 0, 3);
+        S.counters_clean = false;
         if (fused_block_size(block_size) && !getenv("ICELK_GENERIC_CORNERS") && !c->corner_variant) {
-            launch_candidates(c->stream, c->D, s.lv[0], block_size, nullptr, 0, 1.0, false, c->D.eig);
+            launch_candidates(c->stream, S.D, s.lv[0], block_size, nullptr, 0, 1.0, false, S.D.eig);
         } else {
-            launch_min_eig(c->stream, s.lv[0], block_size, c->D.eig, nullptr, 0, c->D.max_key, c->corner_variant);
+            launch_min_eig(c->stream, s.lv[0], block_size, S.D.eig, nullptr, 0, S.D.max_key, c->corner_variant);
         }
     }
     rc = check_launch(c, "min_eig");
     if (rc) return rc;
-    HIPCHK(c, hipMemcpy2DAsync(host_out, sizeof(float) * stride_elems, c->D.eig, sizeof(float) * s.w, sizeof(float) * s.w,
+    HIPCHK(c, hipMemcpy2DAsync(host_out, sizeof(float) * stride_elems, S.D.eig, sizeof(float) * s.w, sizeof(float) * s.w,
                                s.h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ICELK_OK;
@@ -2354,8 +2278,7 @@ int icelk_detect_fast_stats(icelk_t* h, int slot_w, int slot_h, long long* out)
     Ctx* c = C(h);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    det_save(c);
-    const Ctx::EigOut& e = c->eo[c->eo_active];
+    const Ctx::EigOut& e = c->eo[c->dset[c->dset_last].eo_active];
     if (!e.acand) FAIL(c, ICELK_EARG, "the two-pass detector was not enabled when this handle was created (ICELK_TWO_PASS_CORNERS)");
     const size_t nt = fast_tiles(slot_w, slot_h);
     std::vector<int> cnt(nt), mx(nt);
@@ -2404,7 +2327,8 @@ static int seg_stage(Ctx* c, int max_corners, int* out_n)
     // the new segment goes into the set after the current one, on the tail stream right behind the corner list
     Ctx::SegBuf& nb = c->sb[(c->sb_cur + 1) % kSegSets];
     bool tables_written = false, dev_done = false;
-    int rc = detect_finish(c, max_corners, c->max_pts, &n, &nb, &tables_written, &dev_done);
+    DetectJob job;
+    int rc = detect_finish(c, max_corners, c->max_pts, &n, &nb, &tables_written, &dev_done, &job);
     if (rc) return rc;
     if (!dev_done) {
         const hipStream_t ds = c->tail_stream;
@@ -2413,7 +2337,7 @@ static int seg_stage(Ctx* c, int max_corners, int* out_n)
             if (int rcw = wait_event(c, ds, nb.used)) return rcw;
             launch_seg_init(ds, c->d_corners, n, nb.live, nb.alive, nb.tracks, kMaxVert);
         }
-        if (c->use_order) launch_seg_order(ds, c->d_corners, n, c->job.w, c->job.h, c->border_px, nb.order, nb.order_border);
+        if (c->use_order) launch_seg_order(ds, c->d_corners, n, job.w, job.h, c->border_px, nb.order, nb.order_border);
         rc = check_launch(c, "seg_init");
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->corners_free, ds));
@@ -2491,14 +2415,11 @@ int icelk_seg_detect_cancel(icelk_t* h)
     HIPCHK(c, hipStreamSynchronize(c->eig_stream));
     HIPCHK(c, hipStreamSynchronize(c->det_stream));
     HIPCHK(c, hipStreamSynchronize(c->tail_stream));
-    det_save(c);
     for (auto& S : c->dset)
         if (S.job.active) {
             S.job.active = false;
             S.counters_clean = false;   // its counters were never reset by a tail: the next detection of the set resets them
         }
-    c->job = c->dset[c->dset_cur].job;
-    c->counters_clean = c->dset[c->dset_cur].counters_clean;
     for (auto& e : c->eo) e.valid = false;   // prepared candidates are dropped
     c->seg_staged = false;                   // a staged segment is forgotten (its set is simply staged into again)
     return ICELK_OK;

@@ -337,6 +337,67 @@ def test_two_detections_in_flight(synth):
     c.close()
 
 
+def test_min_eig_map_while_detections_are_in_flight(synth):
+    """icelk_min_eig_map works in the scratch of a detector set no detection in flight owns: with one detection begun it
+    gives the map taken with nothing in flight, bit for bit; with two begun it is refused (ICELK_ESTATE); and both
+    detections, finished afterwards, give the corners a detection on its own gives for their frames."""
+    from iceberg_tracking_code_amd import Context
+    from iceberg_tracking_code_amd._lib import IcelkError
+    w, h = 800, 600
+    frames, _ = synth.sequence(w, h, 3, seed=43, max_step_px=2.0)
+    det = (600, 0.007, 8, False, 10)
+    c = Context(w, h, n_slots=3, max_pts=4096)
+    try:
+        for i, f in enumerate(frames):
+            c.upload_gray(i, f)
+        want = [c.good_features(i, *det) for i in range(2)]
+        base = c.min_eig_map(2, 10)
+        c.seg_detect_begin(0, *det)
+        assert np.array_equal(c.min_eig_map(2, 10).view(np.uint32), base.view(np.uint32))
+        c.seg_detect_begin(1, *det)
+        with pytest.raises(IcelkError, match="-5"):
+            c.min_eig_map(2, 10)
+        n0 = c.seg_detect_stage(det[0])
+        c.seg_switch()
+        t0, _ = c.seg_read()
+        n1 = c.seg_detect_finish(det[0])
+        t1, _ = c.seg_read()
+        for n, t, ref in ((n0, t0, want[0]), (n1, t1, want[1])):
+            assert n == len(ref) > 300 and np.array_equal(t[:, 0, :], ref.reshape(-1, 2))
+        assert np.array_equal(c.min_eig_map(2, 10).view(np.uint32), base.view(np.uint32))
+    finally:
+        c.close()
+
+
+def test_fast_stats_follow_the_latest_detector_call(synth, monkeypatch):
+    """icelk_detect_fast_stats reports the candidate buffer of the detector set that the latest begin / finish worked on:
+    with two detections in flight, the one begun or finished last, not the oldest.  This pins the behaviour as it is."""
+    from iceberg_tracking_code_amd import Context
+    monkeypatch.setenv("ICELK_TWO_PASS_CORNERS", "1")
+    w, h = 800, 600
+    det = (600, 0.007, 8, False, 10)
+    c = Context(w, h, n_slots=2, max_pts=4096)
+    try:
+        c.upload_gray(0, synth.frame(w, h, 0, 0, 51))
+        c.upload_gray(1, synth.frame(w, h, 0, 0, 52))
+        alone = []
+        for i in range(2):
+            c.good_features(i, *det)
+            alone.append(c.detect_fast_stats(w, h))
+        assert alone[0] != alone[1]
+        c.seg_detect_begin(0, *det)
+        assert c.detect_fast_stats(w, h) == alone[0]
+        c.seg_detect_begin(1, *det)
+        assert c.detect_fast_stats(w, h) == alone[1]
+        c.seg_detect_stage(det[0])
+        assert c.detect_fast_stats(w, h) == alone[0]
+        c.seg_switch()
+        c.seg_detect_finish(det[0])
+        assert c.detect_fast_stats(w, h) == alone[1]
+    finally:
+        c.close()
+
+
 def test_launch_order_is_invisible(synth, monkeypatch):
     """The spatial launch order of a segment's tracks (k_seg_order + XCD dealing) changes which workgroup tracks
     which feature, never a result: ICELK_NO_ORDER=1 must give identical segments."""
