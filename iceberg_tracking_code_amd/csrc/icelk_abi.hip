@@ -40,18 +40,15 @@ struct DetectJob {
 struct Ctx {
     int device = 0;
     int max_w = 0, max_h = 0, n_slots = 0, max_pts = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr, copy_stream = nullptr;
-    // Asynchronous uploads alternate between two streams: between two copies of ONE stream the runtime spends ~50 us
-    // (completion signal of the first, dependency of the second: 220 us copies came out 270 us apart), which a copy
-    // queued on the other stream fills
-    hipStream_t copy_stream2 = nullptr;
-    // the streams of icelk_upload_gray_async since round 4: created at the first such upload, HIGH priority -- a stream of
-    // the compute stream's class can share its hardware queue, and then the copy's dependencies wait behind a tracker launch
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    // the streams of icelk_upload_gray_async, created at the first such upload.  Uploads alternate between two streams:
+    // between two copies of ONE stream the runtime spends ~50 us (completion signal of the first, dependency of the
+    // second: 220 us copies came out 270 us apart), which a copy queued on the other stream fills.  HIGH priority since
+    // round 4 -- a stream of the compute stream's class can share its hardware queue, and then the copy's dependencies
+    // wait behind a tracker launch
     hipStream_t copy_hi[2] = {nullptr, nullptr};
-    hipStream_t copy_more[2] = {nullptr, nullptr};   // ICELK_COPY_STREAMS=3|4 (A/B measurements)
-    int n_copy_streams = 2;
     unsigned upload_seq = 0;
-    // pyramids built ahead of their step: not on the copy stream, where a 12 MB upload of a LATER frame would stand
+    // pyramids built ahead of their step: not on an upload stream, where a 12 MB upload of a LATER frame would stand
     // between a pyramid and the tracker launch that waits for it
     hipStream_t pyr_stream = nullptr;
     int side_pick[4] = {-1, -1, -1, -1};   // which of the probed candidate streams became detection / candidates / pyramid / tail
@@ -180,13 +177,9 @@ struct Ctx {
     long long tails_dev = 0, tails_host = 0;   // segments staged by the device-driven tail / by the host's
     bool use_order = true;                 // ICELK_NO_ORDER=1 launches in detector order (A/B measurements)
     // features this close to the frame border count as slow (launched first): from the window and pyramid depth of the
-    // latest tracker call; ICELK_NO_BORDER_FIRST=1 turns the class off
+    // latest tracker call
     int border_px = (10 + kLkTileMargin + 2) << 2;
-    bool border_first = true;
     bool pyr_per_level = false;            // ICELK_PYR_PER_LEVEL=1: one pyrDown launch per level (A/B, second statement)
-    // pyramids built ahead (copy stream, beside a tracker launch) use one-wave workgroups, which fit into the slot of a
-    // single retiring tracker wave (k_pyramid.hip); ICELK_PYR_AHEAD_WIDE=1 keeps the 256-thread geometry there too (A/B)
-    bool pyr_ahead_one_wave = true;
     int fb_dist_form = ICELK_FB_HYPOT;     // icelk_set_fb_distance
     int lk_sum_mode = 0;                   // icelk_set_variant "lk_sums"
     int corner_variant = 0;                // icelk_set_variant "sobel_fma" (bits 0-1) | "eig_fma" (bit 2)
@@ -464,7 +457,9 @@ static int build_levels(Ctx* c, Slot& s, int top_level, hipStream_t st)
         {
             ProfScope p(c, K_PYRDOWN, st);
             if (per_level) launch_pyrdown(st, s.lv[l - 1], s.lv[l]);
-            else launch_pyramid_fused(st, s.lv, l - 1, n, c->pyr_ahead_one_wave && st == c->pyr_stream);
+            // pyramids built ahead (beside a tracker launch) use one-wave workgroups, which fit into the slot of a single
+            // retiring tracker wave (k_pyramid.hip)
+            else launch_pyramid_fused(st, s.lv, l - 1, n, st == c->pyr_stream);
         }
         int rc = check_launch(c, "pyramid");
         if (rc) return rc;
@@ -558,7 +553,7 @@ static hipError_t create_priority_stream(hipStream_t* s)
 // together with the filler.  The detection stream must not be held up by the compute stream; the candidates stream
 // (one long kernel per detection) must not hold up the detection stream; the pyramid stream must be held up by neither
 // the compute nor the candidates stream.  Measured on C2: 5 050 pairs/s with the three on pipes of their own, 4 000
-// with the candidates stream behind the tracker's pipe.  ICELK_NO_STREAM_PROBE=1: creation order, no probe.
+// with the candidates stream behind the tracker's pipe.
 __global__ void k_probe_idle(unsigned ticks)
 {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();   // 100 MHz
@@ -598,13 +593,6 @@ static double probe_pair(hipStream_t busy, hipStream_t side, hipEvent_t e_busy, 
 
 static hipError_t create_side_streams(Ctx* c)
 {
-    if (getenv("ICELK_NO_STREAM_PROBE")) {
-        hipError_t r = create_priority_stream(&c->det_stream);
-        if (r == hipSuccess) r = create_priority_stream(&c->pyr_stream);
-        if (r == hipSuccess) r = create_priority_stream(&c->eig_stream);
-        if (r == hipSuccess) r = create_priority_stream(&c->tail_stream);
-        return r;
-    }
     constexpr int NC = 8;
     hipStream_t cand[NC] = {nullptr};
     hipEvent_t ea = nullptr, eb = nullptr;
@@ -786,16 +774,6 @@ static void destroy_ctx(Ctx* c)
             hipStreamSynchronize(q);
             hipStreamDestroy(q);
         }
-    if (c->copy_stream) hipStreamDestroy(c->copy_stream);
-    if (c->copy_stream2) {
-        hipStreamSynchronize(c->copy_stream2);
-        hipStreamDestroy(c->copy_stream2);
-    }
-    for (auto q : c->copy_more)
-        if (q) {
-            hipStreamSynchronize(q);
-            hipStreamDestroy(q);
-        }
     if (c->pyr_stream) {
         hipStreamSynchronize(c->pyr_stream);
         hipStreamDestroy(c->pyr_stream);
@@ -922,25 +900,22 @@ static inline bool counts_here(const int* h_counts, int seq)
 }
 
 // Waits for the counts by polling the pinned sequence word; the event is looked at now and then, so that a failed
-// kernel ends the wait with its error instead of hanging it (ICELK_EVENT_WAIT=1: hipEventSynchronize, as before).
+// kernel ends the wait with its error instead of hanging it.
 static int fetch_counts(Ctx* c, Ctx::DetSet& S, bool published = false)
 {
     if (!published) {
         int rc = publish_counts(c, S);
         if (rc) return rc;
     }
-    static const bool by_event = getenv("ICELK_EVENT_WAIT") != nullptr;
-    if (!by_event) {
-        for (unsigned it = 1;; it++) {
-            if (counts_here(S.h_counts, S.counts_seq)) return ICELK_OK;
-            if ((it & 4095u) == 0) {
-                const hipError_t q = hipEventQuery(S.counts_ev);
-                if (q == hipSuccess) break;             // complete: the synchronize below returns at once
-                if (q != hipErrorNotReady) HIPCHK(c, q);
-                (void)hipGetLastError();
-            }
-            __builtin_ia32_pause();
+    for (unsigned it = 1;; it++) {
+        if (counts_here(S.h_counts, S.counts_seq)) return ICELK_OK;
+        if ((it & 4095u) == 0) {
+            const hipError_t q = hipEventQuery(S.counts_ev);
+            if (q == hipSuccess) break;             // complete: the synchronize below returns at once
+            if (q != hipErrorNotReady) HIPCHK(c, q);
+            (void)hipGetLastError();
         }
+        __builtin_ia32_pause();
     }
     HIPCHK(c, hipEventSynchronize(S.counts_ev));
     return ICELK_OK;
@@ -976,7 +951,7 @@ static int detect_prepare(Ctx* c, int slot, int use_mask, int block_size)
     const double prep_quality = c->prep_quality;
     {
         ProfScope p(c, K_EIG, es);
-        launch_candidates(es, T, s.lv[0], block_size, mask, c->mask_pitch, prep_quality, false, nullptr, 0, true);
+        launch_candidates(es, T, s.lv[0], block_size, mask, c->mask_pitch, prep_quality, false, nullptr);
     }
     rc = check_launch(c, "corner candidates (prepared)");
     if (rc) return rc;
@@ -1217,8 +1192,7 @@ static int detect_finish(Ctx* c, int max_corners, int cap, int* n_out, Ctx::SegB
     int n = total;
     if (max_corners > 0 && n > max_corners) n = max_corners;
     if (n > cap || n > c->max_pts) FAIL(c, ICELK_ECAP, "more corners than the output capacity (raise max_pts)");
-    static const bool split_tail = getenv("ICELK_SPLIT_TAIL") != nullptr;   // A/B: the three launches of before
-    if (seg && !split_tail) {
+    if (seg) {
         // launches that still touch the segment set (a segment closed two switches ago) must be through
         if (int rcw = wait_event(c, ts, seg->used)) return rcw;
         {
@@ -1446,7 +1420,7 @@ static int seg_track_core(Ctx* c, int slot_prev, int slot_next, int win_w, int w
     if (rc) return rc;
     if (S.upper > 0) {
         // tiles (half window + search margin) of a feature this close to the edge reach over it at the upper levels
-        c->border_px = c->border_first ? ((std::max(win_w, win_h) / 2 + kLkTileMargin + 2) << std::max(P.top_level - 1, 0)) : 0;
+        c->border_px = (std::max(win_w, win_h) / 2 + kLkTileMargin + 2) << std::max(P.top_level - 1, 0);
         LKJob job = seg_job(c, c->sb_cur, s0, s1, P, true);
         // workgroup stamps describe ONE job: no pairing while they are on -- unless ICELK_LK_STAMPS_PAIR asks for the
         // stamps of a joint launch (indexed by workgroup: tools/lk_stamps_pair.py tells the jobs apart)
@@ -1590,9 +1564,6 @@ int icelk_create(int device, int max_w, int max_h, int n_slots, int max_pts, ice
         return code;
     };
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        // uploads are DMA copies: normal priority; pyramid, detection and candidates are the high-priority streams
-        hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->copy_stream2, hipStreamNonBlocking) != hipSuccess ||
         create_side_streams(c) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(&c->h_seg), 64, hipHostMallocMapped) != hipSuccess ||
         hipEventCreateWithFlags(&c->det_done, hipEventDisableTiming) != hipSuccess ||
@@ -1652,23 +1623,12 @@ int icelk_create(int device, int max_w, int max_h, int n_slots, int max_pts, ice
             (rc = dmalloc(c, &S.order_border, 1)) || (rc = dmalloc(c, &S.tracks, np * kMaxVert * 2)) ||
             (rc = dmalloc(c, &S.quality, np * (kMaxVert - 1))))
             return fail(rc);
-    if (const char* ncs = getenv("ICELK_COPY_STREAMS")) {
-        c->n_copy_streams = std::min(std::max(atoi(ncs), 1), 4);
-        for (int k = 2; k < c->n_copy_streams; k++)
-            if (hipStreamCreateWithFlags(&c->copy_more[k - 2], hipStreamNonBlocking) != hipSuccess) {
-                c->err = "hipStreamCreate failed";
-                return fail(ICELK_EHIP);
-            }
-    }
     c->use_order = getenv("ICELK_NO_ORDER") == nullptr;
-    c->border_first = getenv("ICELK_NO_BORDER_FIRST") == nullptr;
     c->pyr_per_level = getenv("ICELK_PYR_PER_LEVEL") != nullptr;
-    c->pyr_ahead_one_wave = getenv("ICELK_PYR_AHEAD_WIDE") == nullptr;
     c->tmpl.off = getenv("ICELK_NO_TEMPLATE_REUSE") != nullptr;
     if (const char* tb = getenv("ICELK_TEMPLATE_BUDGET_MB")) c->tmpl.budget = (size_t)std::max(atoll(tb), 0LL) << 20;
     c->host_tail = getenv("ICELK_HOST_TAIL") != nullptr;
     if (const char* fs = getenv("ICELK_TAIL_FORCE_STATUS")) c->tail_force_status = std::min(std::max(atoi(fs), 0), 4);
-    if (!c->border_first) c->border_px = 0;
     if ((rc = dmalloc(c, &c->d_iters, (size_t)max_pts))) return fail(rc);
     if (const char* sp = getenv("ICELK_LK_STAMPS")) {
         c->stamps_path = sp;
@@ -1737,11 +1697,7 @@ int icelk_sync(icelk_t* h)
     if (rcf) return rcf;
     // every stream of the handle: uploads / pyramids built ahead, candidate kernels of a prepared detection
     // (icelk_seg_detect_prepare), the min-distance / sort / emit stage, tracker launches
-    HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-    HIPCHK(c, hipStreamSynchronize(c->copy_stream2));
     for (auto q : c->copy_hi)
-        if (q) HIPCHK(c, hipStreamSynchronize(q));
-    for (auto q : c->copy_more)
         if (q) HIPCHK(c, hipStreamSynchronize(q));
     HIPCHK(c, hipStreamSynchronize(c->pyr_stream));
     HIPCHK(c, hipStreamSynchronize(c->eig_stream));
@@ -1810,16 +1766,14 @@ int icelk_upload_gray_async(icelk_t* h, int slot, const uint8_t* pinned_host, in
     int rc = begin_frame(c, slot, w, h_);
     if (rc) return rc;
     Slot& s = c->slots[slot];
-    // Two streams in turn (see Ctx::copy_stream), of the high-priority class.  With streams of the compute stream's own class
+    // Two streams in turn (see Ctx::copy_hi), of the high-priority class.  With streams of the compute stream's own class
     // every second upload -- always those of ONE of the two streams -- started 60-180 us after the copy before it had
     // ended (profiles/r04_c3_modes.txt): that stream shared its hardware queue with the compute stream, and the barrier
     // that carries an upload's dependencies stood behind a 250-us tracker launch.  C3 with 6 uploads in flight:
-    // 3 650-3 800 -> 4 040-4 110 pairs/s (profiles/r04_c3_copy_prio.txt).  ICELK_COPY_PRIORITY=normal: the streams of before.
-    static const bool copy_normal = getenv("ICELK_COPY_PRIORITY") && !strcmp(getenv("ICELK_COPY_PRIORITY"), "normal");
-    const unsigned useq = c->upload_seq++ % (unsigned)c->n_copy_streams;
-    if (!copy_normal && useq < 2 && !c->copy_hi[useq])
-        HIPCHK(c, create_priority_stream(&c->copy_hi[useq]));
-    const hipStream_t cs = useq >= 2 ? c->copy_more[useq - 2] : (!copy_normal ? c->copy_hi[useq] : (useq == 0 ? c->copy_stream : c->copy_stream2));
+    // 3 650-3 800 -> 4 040-4 110 pairs/s (profiles/r04_c3_copy_prio.txt).
+    const unsigned useq = c->upload_seq++ % 2u;
+    if (!c->copy_hi[useq]) HIPCHK(c, create_priority_stream(&c->copy_hi[useq]));
+    const hipStream_t cs = c->copy_hi[useq];
     // the copy must not overtake the launches that still read this slot (Slot::used / det_used)
     if (int rcw = wait_event(c, cs, s.used)) return rcw;
     if (s.pending) if (int rcw = wait_event(c, cs, s.ready)) return rcw;   // an upload or a pyramid built ahead still in flight

@@ -5,26 +5,31 @@
 // cornerMinEigenVal / goodFeaturesToTrack (OpenCV is not part of /root/reference).
 //
 // Stages
-//   K6+K7 fused (k_eig_nms<BS>, blockSize 3/5/7/10): one tile per workgroup, everything through LDS:
-//         u8 tile -> Sobel -> covariance products -> blockSize^2 box sums (ordered double sums, register
-//         blocked) -> min eigenvalue (+1 px halo) -> 3x3 non-max test, mask, 1-px border -> local maxima
-//         appended as 64-bit keys (response key << 32 | y << 16 | x), plus the masked maximum of the map
+//   K6+K7 fused (k_eig_strip<BS>, blockSize 3/5/7/10): a workgroup walks down a strip of the frame, one thread per
+//         covariance column: Sobel -> covariance products -> blockSize^2 box sums (exact double sums: column sums
+//         rolled down in registers, row sums through LDS) -> min eigenvalue -> 3x3 non-max test, mask, 1-px border ->
+//         local maxima appended as 64-bit keys (response key << 32 | y << 16 | x), plus the masked maximum of the map
 //         (order-preserving atomicMax).  Neither OpenCV's f32 Dx/Dy/covariance images (5 x 4 B/px) nor the
-//         eigenvalue map itself ever exist in HBM: 1 B/px is read, ~8 B per local maximum written.
+//         eigenvalue map itself ever exist in HBM unless the map is asked for (icelk_min_eig_map): 1 B/px is read,
+//         ~8 B per local maximum written.
 //         The quality threshold (max * qualityLevel) is applied to the candidate list afterwards
 //         (k_filter): for max > 0,  v > thr && v == dilate3x3(threshold_tozero(eig))  <=>  v > thr && v >= its
 //         8 raw neighbours; for max <= 0 OpenCV finds no corner either.
-//   K6, K7 separate (k_min_eig, k_nms_collect): any other blockSize, and the eigenvalue-map read-back.
+//         (k_corners_fast.hip: the same candidates in two passes, ICELK_TWO_PASS_CORNERS=1.)
+//   K6, K7 separate (k_min_eig, k_nms_collect): any other blockSize, ICELK_GENERIC_CORNERS=1 and the arithmetic
+//         variants of icelk_set_variant.
 //   K8 min distance: OpenCV accepts candidates greedily in response order.  Equivalent parallel form: a
 //         candidate is accepted iff no ACCEPTED candidate of higher priority lies closer than minDistance;
 //         relax "reject if an accepted stronger neighbour exists / accept if every stronger neighbour is
 //         rejected" to the fixed point over a cell grid of round(minDistance) px (3x3 cell search, as OpenCV's
 //         grid).  Only the accepted set is sorted (k_sort.hip).
-// Candidates live in per-workgroup regions (region b = the local maxima of tile b, count in blk_count[b]):
+// Candidates live in per-workgroup regions (region b = the local maxima of a 16-row band of a strip, or of a workgroup's
+// band of k_nms_collect; count in blk_count[b]):
 // no single-address atomics anywhere on the image-sized passes (one word saturates at ~90 atomics/us on
 // gfx950), and the masked maximum is published with a read-guarded atomicMax.
 // The whole detection is enqueued without host round trips; the host synchronises once, to learn the
 // number of accepted corners.
+#include <algorithm>
 #include <cstdlib>
 
 #include "icelk_internal.h"
@@ -163,216 +168,9 @@ struct CandSrc {
 };
 
 // ------------------------------------------------------------------------------------------------
-// Fused K6+K7, compile-time blockSize: 33 KB of LDS, 4 workgroups per CU.  Only the two derivative planes are kept
-// (the covariance products are formed where they are summed, each with the single f32 rounding OpenCV's stored
-// planes have), and the double row sums of ONE plane at a time: row pass -> barrier -> column pass into registers
-// -> barrier, three times.  (A first form that kept all three covariance planes and their row sums -- 70 KB of LDS,
-// 2 workgroups per CU -- took 337 us alone at 12 MP against 120 us for this one, and beside the tracker launch its
-// workgroups waited for whole CUs to drain: 440 us against 177 us.  It is gone.)
-// ------------------------------------------------------------------------------------------------
-template <int BS>
-struct EigCfg {
-    static constexpr int TW = 64, TH = 16;
-    static constexpr int EW = TW + 2, EH = TH + 2;
-    static constexpr int CW = EW + BS - 1, CH = EH + BS - 1;
-    static constexpr int CWP = (CW + 3) & ~3;
-    static constexpr int UW = CW + 2, UH = CH + 2;
-    static constexpr int UPD = (UW + 2) / 4 + 1;
-    static constexpr int AN = BS / 2;
-    static constexpr int RX = 6, RY = 6;
-    static constexpr int NGX = EW / RX, NGY = EH / RY;
-    static_assert(EW % RX == 0 && EH % RY == 0, "blocking must divide the tile");
-    static_assert(EW * NGY <= 256, "one column task per thread");
-    static constexpr int U_BYTES = (UPD * UH * 4 + 15) & ~15;
-    static constexpr int D_BYTES = 2 * CH * CWP * 4;          // dx, dy
-    static constexpr int A_BYTES = U_BYTES + D_BYTES;         // later reused for the eigenvalue tile
-    static constexpr int HS_BYTES = CH * EW * 8;              // row sums of one plane
-    static constexpr int LDS_BYTES = A_BYTES + HS_BYTES;
-    static_assert(EW * EH * 4 <= A_BYTES, "eigenvalue tile must fit the dead derivative region");
-};
-
-__device__ __forceinline__ void sobel_d(float a0, float b0, float c0, float a1, float c1, float a2, float b2, float c2,
-                                        float k0, float k1, float& dx, float& dy)
-{
-    dx = __fadd_rn(__fmul_rn(__fadd_rn(__fsub_rn(c0, a0), __fsub_rn(c2, a2)), k1), __fmul_rn(__fsub_rn(c1, a1), k0));
-    const float t0 = __fadd_rn(__fadd_rn(__fmul_rn(k1, a0), __fmul_rn(k0, b0)), __fmul_rn(k1, c0));
-    const float t2 = __fadd_rn(__fadd_rn(__fmul_rn(k1, a2), __fmul_rn(k0, b2)), __fmul_rn(k1, c2));
-    dy = __fsub_rn(t2, t0);
-}
-
-__device__ __forceinline__ void sobel_d2(f2 a0, f2 b0, f2 c0, f2 a1, f2 c1, f2 a2, f2 b2, f2 c2, float k0, float k1,
-                                         f2& dx, f2& dy)
-{
-    dx = ((c0 - a0) + (c2 - a2)) * k1 + (c1 - a1) * k0;
-    const f2 t0 = (a0 * k1 + b0 * k0) + c0 * k1;
-    const f2 t2 = (a2 * k1 + b2 * k0) + c2 * k1;
-    dy = t2 - t0;
-}
-
-template <int BS>
-__global__ __launch_bounds__(256) void k_eig_nms(const uint8_t* __restrict__ img, int w, int h, int pitch, float k0,
-                                                  float k1, const uint8_t* __restrict__ mask, int mask_pitch,
-                                                  unsigned* __restrict__ max_key,
-                                                  unsigned long long* __restrict__ raw, int* __restrict__ blk_count,
-                                                  float* __restrict__ eig_out)
-{
-    using C = EigCfg<BS>;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint32_t* U = reinterpret_cast<uint32_t*>(smem);
-    float* D = reinterpret_cast<float*>(smem + C::U_BYTES);        // [2][CH][CWP]: dx, dy
-    double* hs = reinterpret_cast<double*>(smem + C::A_BYTES);     // [CH][EW]
-    float* E = reinterpret_cast<float*>(smem);                     // after the last row pass
-    __shared__ int s_list_n;
-    const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * C::TW, y0 = blockIdx.y * C::TH;
-    const int ux0 = x0 - 2 - C::AN, uy0 = y0 - 2 - C::AN;
-    const bool interior = ux0 >= 0 && uy0 >= 0 && ux0 + C::UW <= w && uy0 + C::UH <= h;
-    constexpr int DP = C::CH * C::CWP;   // plane stride
-
-    if (interior) {
-        const uint8_t* base = img + (size_t)uy0 * pitch + (ux0 & ~3);
-        for (int i = tid; i < C::UPD * C::UH; i += 256) {
-            const int r = i / C::UPD, c = i - r * C::UPD;
-            U[i] = *reinterpret_cast<const uint32_t*>(base + (size_t)r * pitch + 4 * c);
-        }
-        __syncthreads();
-        const int cs = ux0 & 3;
-        constexpr int NQF = C::CW / 4, REM = C::CW - 4 * NQF;
-        for (int t = tid; t < C::CH * NQF; t += 256) {
-            const int cy = t / NQF, q = t - cy * NQF;
-            float F[3][6];
-#pragma unroll
-            for (int r = 0; r < 3; r++) {
-                const uint32_t* p = U + (cy + r) * C::UPD + ((cs + 4 * q) >> 2);
-                const int sh = (cs + 4 * q) & 3;
-                const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
-                const uint32_t e0 = __builtin_amdgcn_alignbyte(d1, d0, sh), e1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
-                F[r][0] = (float)(e0 & 255); F[r][1] = (float)((e0 >> 8) & 255); F[r][2] = (float)((e0 >> 16) & 255);
-                F[r][3] = (float)(e0 >> 24); F[r][4] = (float)(e1 & 255); F[r][5] = (float)((e1 >> 8) & 255);
-            }
-            f2 dx[2], dy[2];
-#pragma unroll
-            for (int i = 0; i < 2; i++) {
-                const int j = 2 * i;
-                sobel_d2(f2{F[0][j], F[0][j + 1]}, f2{F[0][j + 1], F[0][j + 2]}, f2{F[0][j + 2], F[0][j + 3]},
-                         f2{F[1][j], F[1][j + 1]}, f2{F[1][j + 2], F[1][j + 3]},
-                         f2{F[2][j], F[2][j + 1]}, f2{F[2][j + 1], F[2][j + 2]}, f2{F[2][j + 2], F[2][j + 3]},
-                         k0, k1, dx[i], dy[i]);
-            }
-            float* c = D + cy * C::CWP + 4 * q;
-            *reinterpret_cast<float4*>(c) = make_float4(dx[0].x, dx[0].y, dx[1].x, dx[1].y);
-            *reinterpret_cast<float4*>(c + DP) = make_float4(dy[0].x, dy[0].y, dy[1].x, dy[1].y);
-        }
-        if (REM > 0) {
-            const uint8_t* Ub = reinterpret_cast<const uint8_t*>(U);
-            for (int i = tid; i < C::CH * REM; i += 256) {
-                const int cy = i / REM, cx = 4 * NQF + (i - cy * REM);
-                const uint8_t* r0 = Ub + cy * C::UPD * 4 + cs + cx;
-                const uint8_t* r1 = r0 + C::UPD * 4;
-                const uint8_t* r2 = r1 + C::UPD * 4;
-                float dx, dy;
-                sobel_d((float)r0[0], (float)r0[1], (float)r0[2], (float)r1[0], (float)r1[2], (float)r2[0], (float)r2[1],
-                        (float)r2[2], k0, k1, dx, dy);
-                D[cy * C::CWP + cx] = dx;
-                D[DP + cy * C::CWP + cx] = dy;
-            }
-        }
-    } else {
-        for (int i = tid; i < C::CH * C::CW; i += 256) {
-            const int cy = i / C::CW, cx = i - cy * C::CW;
-            const int rx = reflect101(ux0 + 1 + cx, w), ry = reflect101(uy0 + 1 + cy, h);
-            const int xm = reflect101(rx - 1, w), xp = reflect101(rx + 1, w);
-            const int ym = reflect101(ry - 1, h), yp = reflect101(ry + 1, h);
-            const uint8_t* r0 = img + (size_t)ym * pitch;
-            const uint8_t* r1 = img + (size_t)ry * pitch;
-            const uint8_t* r2 = img + (size_t)yp * pitch;
-            float dx, dy;
-            sobel_d((float)r0[xm], (float)r0[rx], (float)r0[xp], (float)r1[xm], (float)r1[xp], (float)r2[xm],
-                    (float)r2[rx], (float)r2[xp], k0, k1, dx, dy);
-            D[cy * C::CWP + cx] = dx;
-            D[DP + cy * C::CWP + cx] = dy;
-        }
-    }
-    __syncthreads();
-
-    // three planes in turn: xx = dx*dx, xy = dx*dy, yy = dy*dy (one f32 rounding each, as the stored planes of the
-    // first form had); row sums left to right into hs, column sums top to bottom into registers
-    const bool col_task = tid < C::EW * C::NGY;
-    const int cg = tid / C::EW, cex = tid - cg * C::EW;   // column task: group of RY rows, column
-    double S[3][C::RY];
-#pragma unroll
-    for (int p = 0; p < 3; p++) {
-        const float* A = D + (p == 2 ? DP : 0);
-        const float* Bp = D + (p == 0 ? 0 : DP);
-        for (int t = tid; t < C::CH * C::NGX; t += 256) {
-            const int cy = t / C::NGX, g = t - cy * C::NGX;
-            const float* a = A + cy * C::CWP + g * C::RX;
-            const float* b = Bp + cy * C::CWP + g * C::RX;
-            double v[C::RX + BS - 1];
-#pragma unroll
-            for (int i = 0; i < C::RX + BS - 1; i++) v[i] = (double)__fmul_rn(a[i], b[i]);
-            double* o = hs + cy * C::EW + g * C::RX;
-            double r[C::RX];
-            window_sums<C::RX, BS>(v, r);
-#pragma unroll
-            for (int i = 0; i < C::RX; i++) o[i] = r[i];
-        }
-        __syncthreads();
-        if (col_task) {
-            double v[C::RY + BS - 1];
-#pragma unroll
-            for (int i = 0; i < C::RY + BS - 1; i++) v[i] = hs[(cg * C::RY + i) * C::EW + cex];
-            window_sums<C::RY, BS>(v, S[p]);
-        }
-        __syncthreads();   // hs is rewritten by the next plane; after the last one D is dead as well
-    }
-
-    unsigned best = 0;
-    if (col_task) {
-#pragma unroll
-        for (int i = 0; i < C::RY; i++) {
-            const float e = min_eig_of(S[0][i], S[1][i], S[2][i]);
-            const int ey = cg * C::RY + i;
-            E[ey * C::EW + cex] = e;
-            const int x = x0 - 1 + cex, y = y0 - 1 + ey;
-            if (cex >= 1 && cex <= C::TW && ey >= 1 && ey <= C::TH && x < w && y < h) {
-                if (eig_out) eig_out[(size_t)y * w + x] = e;
-                if (!mask || mask[(size_t)y * mask_pitch + x]) {
-                    const unsigned k = ordered_key(e);
-                    best = k > best ? k : best;
-                }
-            }
-        }
-    }
-    publish_max(max_key, best, tid);
-    if (tid == 0) s_list_n = 0;
-    __syncthreads();
-
-    const int bid = blockIdx.y * gridDim.x + blockIdx.x;
-    unsigned long long* region = raw + (size_t)bid * (C::TW * C::TH);
-    for (int i = tid; i < C::TW * C::TH; i += 256) {
-        const int oy = i / C::TW, ox = i - oy * C::TW;
-        const int x = x0 + ox, y = y0 + oy;
-        if (x < 1 || y < 1 || x >= w - 1 || y >= h - 1) continue;
-        const float* e = E + (oy + 1) * C::EW + (ox + 1);
-        const float v = e[0];
-        if (!(v > 0.f)) continue;
-        float m = e[-C::EW - 1];
-        m = fmaxf(m, e[-C::EW]); m = fmaxf(m, e[-C::EW + 1]);
-        m = fmaxf(m, e[-1]); m = fmaxf(m, e[1]);
-        m = fmaxf(m, e[C::EW - 1]); m = fmaxf(m, e[C::EW]); m = fmaxf(m, e[C::EW + 1]);
-        if (v < m) continue;
-        if (mask && !mask[(size_t)y * mask_pitch + x]) continue;
-        region[atomicAdd(&s_list_n, 1)] = ((unsigned long long)ordered_key(v) << 32) | pack_xy(x, y);
-    }
-    __syncthreads();
-    if (tid == 0) blk_count[bid] = s_list_n;
-}
-
-// ------------------------------------------------------------------------------------------------
-// K6+K7 in STRIPS (round 3; the default for blockSize 3/5/7/10).  k_eig_nms pays for its 64x16 tile twice: the Sobel stage
-// runs on 27x75 positions and the row sums on 27x66 for 16x64 outputs (1.98x / 1.74x), and its column pass and eigenvalue
-// stage occupy 198 of 256 threads.  Here a workgroup walks DOWN a strip 245 outputs wide (blockSize 10) and 62 high:
+// K6+K7 in STRIPS (round 3; blockSize 3/5/7/10).  Round 2's tile kernel (removed) paid for its 64x16 tile twice: the Sobel
+// stage ran on 27x75 positions and the row sums on 27x66 for 16x64 outputs (1.98x / 1.74x), and its column pass and
+// eigenvalue stage occupied 198 of 256 threads.  Here a workgroup walks DOWN a strip 245 outputs wide (blockSize 10) and 62 high:
 //   * one thread per covariance column.  The Sobel pair rolls down the column in registers (row difference and row
 //     smooth of the two pixel rows above are kept; three byte loads per new row, issued one row ahead; BORDER_REFLECT_101
 //     in x costs nothing: the three column offsets of a thread are fixed).  The COLUMN sums come first: a running double
@@ -395,15 +193,9 @@ __global__ __launch_bounds__(256) void k_eig_nms(const uint8_t* __restrict__ img
 // ------------------------------------------------------------------------------------------------
 constexpr int gcd_c(int a, int b) { return b == 0 ? a : gcd_c(b, a % b); }
 
-// NT_ = 256: four waves, one row of a batch each in the row-sum phase.  NT_ = 64 (round 4): ONE wave per workgroup -- the
-// strip is 53 outputs wide at blockSize 10 (halo 1.21 in x instead of 1.045), the four rows of a batch are row-summed by
-// 4 x 14 lanes at once, and no barrier ever waits for another wave.  What it is for: a four-wave workgroup of 128 VGPRs
-// finds room beside a tracker launch only where tracker waves retire on all four SIMDs of a CU at the same moment -- it
-// took 200-580 us there for 75 us of work, and since the tail of a detection no longer waits for the host (k_tail.hip)
-// that kernel paced the whole C2 pipeline -- whereas a one-wave workgroup takes the place of ANY single retiring wave.
-template <int BS, int NT_ = 256>
+template <int BS>
 struct StripCfg {
-    static constexpr int NT = NT_;                 // threads = covariance columns
+    static constexpr int NT = 256;                 // threads = covariance columns; four waves, one row of a batch each
     static constexpr int AN = BS / 2;
     static constexpr int EW = NT - (BS - 1);       // eigenvalue columns
     static constexpr int TW = EW - 2;              // output columns
@@ -422,7 +214,6 @@ struct StripCfg {
     static constexpr int E_BYTES = 8 * NT * 4;
     static constexpr int LDS_BYTES = V_BYTES + E_BYTES;
     static_assert(EH % R == 0 && NG <= 64 && RX * NG <= NT + RX - 1, "one wave per row of a batch");
-    static_assert(NT == 256 || (NT == 64 && R * NG <= 64), "one-wave form: the rows of a batch side by side in the wave");
     static_assert(RX * (NG - 1) + RX + BS - 2 < VP, "row tasks stay inside a row of column sums");
     static_assert((VP * 8) % 16 == 0, "16-byte reads of the column sums");
 };
@@ -436,13 +227,13 @@ __device__ __forceinline__ float smooth3(float a, float b, float c, float k0, fl
     return __fadd_rn(__fadd_rn(__fmul_rn(k1, a), __fmul_rn(k0, b)), __fmul_rn(k1, c));
 }
 
-template <int BS, bool FRESH, int NT_ = 256>
+template <int BS, bool FRESH>
 __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int w, int h, int pitch, float k0, float k1,
                                            const uint8_t* __restrict__ mask, int mask_pitch, unsigned* __restrict__ max_key,
                                            unsigned long long* __restrict__ raw, int* __restrict__ blk_count,
                                            float* __restrict__ eig_out, uint8_t* smem, int* s_cnt)
 {
-    using C = StripCfg<BS, NT_>;
+    using C = StripCfg<BS>;
     double* Vb = reinterpret_cast<double*>(smem);                 // [R][3][VP]
     float* Er = reinterpret_cast<float*>(smem + C::V_BYTES);      // [8][NT]
     const int tid = threadIdx.x;
@@ -507,8 +298,8 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
     }
 
     unsigned best = 0;
-    // row-sum phase: which row of the batch / which group of RX outputs this thread takes (one-wave form: rows side by side)
-    const int wr = NT_ == 256 ? tid >> 6 : tid / C::NG, g = NT_ == 256 ? tid & 63 : tid % C::NG;
+    // row-sum phase: which row of the batch (= wave) / which group of RX outputs this thread takes
+    const int wr = tid >> 6, g = tid & 63;
     for (int base = 0; base < C::EH; base += C::UNROLL) {
 #pragma unroll
         for (int j = 0; j < C::UNROLL; j++) {
@@ -592,23 +383,6 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
     publish_max(max_key, best, tid);
     __syncthreads();
     if (tid < C::NSUB) blk_count[bid * C::NSUB + tid] = s_cnt[tid];
-}
-
-template <int BS>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(80))) void k_eig_strip1(const uint8_t* __restrict__ img, int w, int h, int pitch, float k0,
-                                                    float k1, const uint8_t* __restrict__ mask, int mask_pitch,
-                                                    unsigned* __restrict__ max_key,
-                                                    unsigned long long* __restrict__ raw, int* __restrict__ blk_count,
-                                                    float* __restrict__ eig_out)
-{
-    using C = StripCfg<BS, 64>;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    __shared__ int s_cnt[C::NSUB];
-    const int ys = (int)blockIdx.y * C::SH - 1 - C::AN;
-    if (ys - 1 >= 0 && ys + C::NROWS <= h - 1)
-        strip_body<BS, false, 64>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
-    else
-        strip_body<BS, true, 64>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
 }
 
 // Registers: what the kernel needs at blockSize 10 is 144 VGPRs.  Until late in round 4 it was held to 128 for a fourth wave
@@ -1124,76 +898,38 @@ void sobel_scale(int block_size, float* k0, float* k1)
 }
 
 template <int BS>
-void launch_fused(hipStream_t s, const Level& img, float k0, float k1, const uint8_t* mask, int mask_pitch,
+void launch_strip(hipStream_t s, const Level& img, float k0, float k1, const uint8_t* mask, int mask_pitch,
                   unsigned* max_key, unsigned long long* raw, int* blk_count, float* eig_out, CandSrc* src)
 {
-    using C = EigCfg<BS>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_eig_nms<BS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            C::LDS_BYTES);
-        attr_set = true;
-    }
-    dim3 grid((img.w + C::TW - 1) / C::TW, (img.h + C::TH - 1) / C::TH);
-    hipLaunchKernelGGL((k_eig_nms<BS>), grid, dim3(256), C::LDS_BYTES, s, img.ptr, img.w, img.h, img.pitch, k0, k1, mask,
+    using C = StripCfg<BS>;
+    dim3 grid((img.w + C::TW - 1) / C::TW, (img.h + C::SH - 1) / C::SH);
+    hipLaunchKernelGGL((k_eig_strip<BS>), grid, dim3(C::NT), C::LDS_BYTES, s, img.ptr, img.w, img.h, img.pitch, k0, k1, mask,
                        mask_pitch, max_key, raw, blk_count, eig_out);
-    src->keys = raw;
-    src->blk_count = blk_count;
-    src->nblk = (int)(grid.x * grid.y);
-    src->region = C::TW * C::TH;
-}
-
-template <int BS>
-void launch_strip(hipStream_t s, const Level& img, float k0, float k1, const uint8_t* mask, int mask_pitch,
-                  unsigned* max_key, unsigned long long* raw, int* blk_count, float* eig_out, CandSrc* src, bool one_wave)
-{
-    if (one_wave) {
-        using C = StripCfg<BS, 64>;
-        dim3 grid((img.w + C::TW - 1) / C::TW, (img.h + C::SH - 1) / C::SH);
-        hipLaunchKernelGGL((k_eig_strip1<BS>), grid, dim3(C::NT), C::LDS_BYTES, s, img.ptr, img.w, img.h, img.pitch, k0, k1, mask,
-                           mask_pitch, max_key, raw, blk_count, eig_out);
-        src->nblk = (int)(grid.x * grid.y) * C::NSUB;
-        src->region = C::TW * C::SUB;
-    } else {
-        using C = StripCfg<BS>;
-        dim3 grid((img.w + C::TW - 1) / C::TW, (img.h + C::SH - 1) / C::SH);
-        hipLaunchKernelGGL((k_eig_strip<BS>), grid, dim3(C::NT), C::LDS_BYTES, s, img.ptr, img.w, img.h, img.pitch, k0, k1, mask,
-                           mask_pitch, max_key, raw, blk_count, eig_out);
-        src->nblk = (int)(grid.x * grid.y) * C::NSUB;
-        src->region = C::TW * C::SUB;
-    }
+    src->nblk = (int)(grid.x * grid.y) * C::NSUB;
+    src->region = C::TW * C::SUB;
     src->keys = raw;
     src->blk_count = blk_count;
 }
 
 // regions / keys the strip layout needs, whichever blockSize is asked for later
-template <int BS, int NT_>
-void strip_geometry1(int w, int h, size_t* regions, size_t* keys)
+template <int BS>
+void strip_geometry(int w, int h, size_t* regions, size_t* keys)
 {
-    using C = StripCfg<BS, NT_>;
+    using C = StripCfg<BS>;
     const size_t r = (size_t)((w + C::TW - 1) / C::TW) * ((h + C::SH - 1) / C::SH) * C::NSUB;
     const size_t k = r * (size_t)(C::TW * C::SUB);
     *regions = r > *regions ? r : *regions;
     *keys = k > *keys ? k : *keys;
 }
-template <int BS>
-void strip_geometry(int w, int h, size_t* regions, size_t* keys)
+void strip_layout(int w, int h, size_t* regions, size_t* keys)
 {
-    strip_geometry1<BS, 256>(w, h, regions, keys);
-    strip_geometry1<BS, 64>(w, h, regions, keys);
+    *regions = *keys = 0;
+    strip_geometry<3>(w, h, regions, keys); strip_geometry<5>(w, h, regions, keys);
+    strip_geometry<7>(w, h, regions, keys); strip_geometry<10>(w, h, regions, keys);
 }
-size_t strip_regions(int w, int h)
-{
-    size_t r = 0, k = 0;
-    strip_geometry<3>(w, h, &r, &k); strip_geometry<5>(w, h, &r, &k); strip_geometry<7>(w, h, &r, &k); strip_geometry<10>(w, h, &r, &k);
-    return r;
-}
-size_t strip_keys(int w, int h)
-{
-    size_t r = 0, k = 0;
-    strip_geometry<3>(w, h, &r, &k); strip_geometry<5>(w, h, &r, &k); strip_geometry<7>(w, h, &r, &k); strip_geometry<10>(w, h, &r, &k);
-    return k;
-}
+
+// k_nms_collect: a workgroup per 256 x NMS_ROWS band of the frame's interior
+dim3 nms_grid(int w, int h) { return dim3((w - 2 + 255) / 256, (h - 2 + NMS_ROWS - 1) / NMS_ROWS); }
 
 }  // namespace
 
@@ -1205,21 +941,23 @@ size_t min_eig_lds_bytes(int block_size)
 
 bool fused_block_size(int bs) { return bs == 3 || bs == 5 || bs == 7 || bs == 10; }
 
-// capacity (in keys) the region layout needs for a w x h frame, whichever kernel produces the candidates
+// capacity (in keys) and regions (blk_count entries) the region layout needs for a w x h frame, whichever kernel produces
+// the candidates: k_eig_strip, k_nms_collect or the two-pass form
 size_t candidate_capacity(int w, int h)
 {
-    const size_t fused = (size_t)((w + 63) / 64) * ((h + 15) / 16) * (64 * 16);
+    size_t strip_r, strip_k;
+    strip_layout(w, h, &strip_r, &strip_k);
     const size_t generic = (size_t)((w + 255) / 256) * ((h + NMS_ROWS - 1) / NMS_ROWS) * (256 * NMS_ROWS);
-    const size_t fast = fast_key_capacity(w, h), strip = strip_keys(w, h);
-    size_t m = fused > generic ? fused : generic;
-    m = m > fast ? m : fast;
-    return (m > strip ? m : strip) + 1024;
+    const size_t m = std::max({generic, fast_key_capacity(w, h), strip_k});
+    return m + 1024;
 }
 size_t candidate_blocks(int w, int h)
 {
-    const size_t a = (size_t)((w + 63) / 64) * ((h + 15) / 16), b = fast_regions(w, h), c = strip_regions(w, h);
-    const size_t m = a > b ? a : b;
-    return (m > c ? m : c) + 16;
+    size_t strip_r, strip_k;
+    strip_layout(w, h, &strip_r, &strip_k);
+    const dim3 g = nms_grid(w, h);
+    const size_t m = std::max({(size_t)g.x * g.y, fast_regions(w, h), strip_r});
+    return m + 16;
 }
 
 // K6 alone, writing the map with the any-blockSize kernel.
@@ -1264,7 +1002,7 @@ void launch_detect_reset(hipStream_t s, DetectScratch& D, int ncell, int mode)
 
 // Candidate collection (K6+K7) into regions of D.raw (stream order, no host sync).
 void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int block_size, const uint8_t* mask,
-                       int mask_pitch, double quality, bool use_generic, float* eig_out_or_null, int variant, bool beside_tracker)
+                       int mask_pitch, double quality, bool use_generic, float* eig_out_or_null, int variant)
 {
     if (variant) use_generic = true;     // the named variants live in the any-blockSize kernel only
     unsigned long long* raw = D.raw;
@@ -1275,32 +1013,14 @@ void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int bl
     if (two_pass && !use_generic && fused_block_size(block_size) && !eig_out_or_null &&
         launch_candidates_fast(s, D, img, block_size, mask, mask_pitch, quality))
         return;
-    // ICELK_TILE_CORNERS=1: round 2's 64x16-tile kernel instead of the strip kernel (same lists; kept for comparison)
-    const bool tiles = getenv("ICELK_TILE_CORNERS") != nullptr;
-    if (!use_generic && fused_block_size(block_size) && !tiles) {
-        float k0, k1;
-        sobel_scale(block_size, &k0, &k1);
-        // ICELK_STRIP_WAVES=1: one-wave strips (k_eig_strip1) for the corner kernel that runs ahead of its detection, beside a
-        // tracker launch (icelk_seg_detect_prepare); =11: everywhere.  Default: round 3's four-wave strips -- measured on one
-        // box, C2 / REF / C5: 5 950 / 766 / 567 pairs/s with one-wave strips against 6 000 / 772 / 569 (the one-wave
-        // workgroups do get onto the CUs at once, and the tracker launch beside them takes 292 us instead of 273)
-        static const char* sw = getenv("ICELK_STRIP_WAVES");
-        const int swv = sw ? atoi(sw) : 0;
-        const bool one_wave = swv == 11 || (swv == 1 && beside_tracker);
-        switch (block_size) {
-            case 3: launch_strip<3>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src, one_wave); break;
-            case 5: launch_strip<5>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src, one_wave); break;
-            case 7: launch_strip<7>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src, one_wave); break;
-            default: launch_strip<10>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src, one_wave); break;
-        }
-    } else if (!use_generic && fused_block_size(block_size)) {
+    if (!use_generic && fused_block_size(block_size)) {
         float k0, k1;
         sobel_scale(block_size, &k0, &k1);
         switch (block_size) {
-            case 3: launch_fused<3>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
-            case 5: launch_fused<5>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
-            case 7: launch_fused<7>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
-            default: launch_fused<10>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
+            case 3: launch_strip<3>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
+            case 5: launch_strip<5>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
+            case 7: launch_strip<7>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
+            default: launch_strip<10>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
         }
     } else {
         launch_min_eig(s, img, block_size, D.eig, mask, mask_pitch, D.max_key, variant);
@@ -1309,7 +1029,7 @@ void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int bl
         g_src.nblk = 0;
         g_src.region = 256 * NMS_ROWS;
         if (img.w >= 3 && img.h >= 3) {
-            dim3 grid((img.w - 2 + 255) / 256, (img.h - 2 + NMS_ROWS - 1) / NMS_ROWS);
+            const dim3 grid = nms_grid(img.w, img.h);
             hipLaunchKernelGGL(k_nms_collect, grid, dim3(256), 0, s, D.eig, img.w, img.h, mask, mask_pitch, D.max_key,
                                quality, raw, D.blk_count);
             g_src.nblk = (int)(grid.x * grid.y);

@@ -4,15 +4,15 @@
 // A third statement of the candidate stage (K6 + K7) of cv2.goodFeaturesToTrack(frame_gray, mask=mask, **feature_params)
 // at s1_lucaskanade_tracking.py:437 for blockSize 3 / 5 / 7 / 10, selected with ICELK_TWO_PASS_CORNERS=1.  Its result --
 // per-region lists of 64-bit keys (response key << 32 | y << 16 | x) of every local maximum, and the masked maximum of the
-// map -- is bit for bit what the one-pass kernel k_eig_nms (k_corners.hip) produces (tests/test_gpu_parity.py::
+// map -- is bit for bit what the one-pass kernel k_eig_strip (k_corners.hip) produces (tests/test_gpu_parity.py::
 // test_two_pass_corner_detector, and the oracle).  NOT the default: measured at C2 it is slower inside the pipeline
 // (DESIGN.md 4.2 has the numbers and the reason), because a textured frame has 2.6 * 10^5 local maxima above
 // max * qualityLevel that all need their exact value before the top-K pruning of the min-distance stage can drop 2/3 of
 // them.  It is kept because the bracket is the tool for that next step (pruning on the bounds, before the exact pass).
 //
-// Idea.  k_eig_nms evaluates OpenCV's float pipeline at every pixel: 243 lane-operations per pixel at blockSize 10 (Sobel
-// in float, three planes of double-precision box sums with a 9-px halo, a correctly rounded sqrtf) -- for a map of which
-// only the local maxima are ever looked at.  Here:
+// Idea.  A one-pass kernel evaluates OpenCV's float pipeline at every pixel (round 2's tile kernel: 243 lane-operations per
+// pixel at blockSize 10 -- Sobel in float, three planes of double-precision box sums with a 9-px halo, a correctly rounded
+// sqrtf) -- for a map of which only the local maxima are ever looked at.  Here:
 //
 //   pass A  k_eig_approx   for every pixel the structure-tensor sums of the UNSCALED integer Sobel derivatives,
 //                          Sxx = sum dxi^2, Sxy = sum dxi dyi, Syy = sum dyi^2 over the blockSize window: exact in int32

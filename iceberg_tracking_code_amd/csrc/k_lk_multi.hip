@@ -26,8 +26,6 @@
 //     fabs((double)t) < 0.01 for a float t is |t| <= 0.01f (0.01f is the largest float below 0.01).
 //   * all global loads of a level -- template patch and search tile of all F features -- are in flight together.
 // Features of a wave that finish a level early simply sit out the remaining pixel phases (scalar branches).
-#include <stdlib.h>
-
 #include "lk_fast_tiles.h"
 
 namespace icelk {
@@ -41,7 +39,7 @@ __device__ __forceinline__ int rl(int v, int lane) { return __builtin_amdgcn_rea
 __device__ __forceinline__ uint32_t rlu(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
 
 // sum over the 64 / F lanes of a block, result in every lane of the block.  16-lane rows: rotations by 8, 4, 2, 1
-// (DPP row_ror); blocks of 32 / 64 lanes add the partner rows through ds_swizzle / ds_bpermute.
+// (DPP row_ror); blocks of 32 lanes (F = 2) add the partner row by a lane shuffle.
 template <int F>
 __device__ __forceinline__ int block_allreduce(int v)
 {
@@ -49,8 +47,7 @@ __device__ __forceinline__ int block_allreduce(int v)
     v += __builtin_amdgcn_update_dpp(0, v, 0x124, 0xf, 0xf, false);  // row_ror:4
     v += __builtin_amdgcn_update_dpp(0, v, 0x122, 0xf, 0xf, false);  // row_ror:2
     v += __builtin_amdgcn_update_dpp(0, v, 0x121, 0xf, 0xf, false);  // row_ror:1
-    if constexpr (F <= 2) v += __shfl_xor(v, 16);
-    if constexpr (F == 1) v += __shfl_xor(v, 32);
+    if constexpr (F == 2) v += __shfl_xor(v, 16);
     return v;
 }
 
@@ -64,14 +61,10 @@ __device__ __forceinline__ float block_sum_f32(const uint32_t* sums, int lane)
         const uint4 v = *reinterpret_cast<const uint4*>(sums + 4 * lane);
         lo = (int)((v.x & 0xffffu) + (v.y & 0xffffu) + (v.z & 0xffffu) + (v.w & 0xffffu));
         hi = ((int)v.x >> 16) + ((int)v.y >> 16) + ((int)v.z >> 16) + ((int)v.w >> 16);
-    } else if constexpr (F == 2) {
+    } else {
         const uint2 v = *reinterpret_cast<const uint2*>(sums + 2 * lane);
         lo = (int)((v.x & 0xffffu) + (v.y & 0xffffu));
         hi = ((int)v.x >> 16) + ((int)v.y >> 16);
-    } else {
-        const uint32_t v = sums[lane];
-        lo = (int)(v & 0xffffu);
-        hi = (int)v >> 16;
     }
     lo = block_allreduce<F>(lo);   // <= 64 * 65535 < 2^24
     hi = block_allreduce<F>(hi);   // |.| <= 64 * 32768 = 2^21
@@ -87,6 +80,7 @@ struct MCfg {
     static constexpr int TILE_DW = C::I_DW + C::J_DW;  // LDS dwords of one feature's two tiles
     static constexpr int SUMS_DW = 3 * F * 64;         // three sums in flight at most (template phase)
     static constexpr int LDS_DW = F * TILE_DW + SUMS_DW + 8;
+    static_assert(F == 2 || F == 4, "two or four features per wave");
 };
 
 // per-feature state kept by every lane of the feature's block
@@ -127,7 +121,7 @@ __device__ __forceinline__ void track_multi(const Pyramid& PI, const Pyramid& PJ
     const float half_x = (WW - 1) * 0.5f, half_y = (WH - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (1 << 20);
     uint32_t* const sums = lds + F * M::TILE_DW;
-    constexpr unsigned long long kOwner = F == 4 ? 0x0001000100010001ull : (F == 2 ? 0x0000000100000001ull : 1ull);
+    constexpr unsigned long long kOwner = F == 4 ? 0x0001000100010001ull : 0x0000000100000001ull;
 
     // this lane's row segments (pixel phases)
     int trow[C::TPL], tcol[C::TPL], tlen[C::TPL], joff[C::TPL];
@@ -404,7 +398,7 @@ constexpr int waves_per_simd()
 }
 
 template <int WW, int WH, int F, bool FB>
-__global__ __launch_bounds__(64, (F == 1 && Cfg<WW, WH>::TPL == 1) ? 4 : 1) void k_lk_multi(Pyramid PI, Pyramid PJ, LKBuffers B, int n, LKParams P)
+__global__ __launch_bounds__(64, 1) void k_lk_multi(Pyramid PI, Pyramid PJ, LKBuffers B, int n, LKParams P)
 {
     using M = MCfg<WW, WH, F>;
     constexpr int LPF = M::LPF;
@@ -472,10 +466,7 @@ bool launch_lk_multi(hipStream_t s, const Pyramid& I, const Pyramid& J, const LK
                      bool fb)
 {
     if (P.flags & ICELK_FLAG_INITIAL_FLOW) return false;
-    static const int exp_f = getenv("ICELK_LK_F") ? atoi(getenv("ICELK_LK_F")) : 0;   // experiments: features per wave
-    if (P.win_w == 21 && P.win_h == 21 && exp_f == 2) launch_multi<21, 21, 2>(s, I, J, B, n, P, fb);
-    else if (P.win_w == 21 && P.win_h == 21 && exp_f == 1) launch_multi<21, 21, 1>(s, I, J, B, n, P, fb);
-    else if (P.win_w == 21 && P.win_h == 21) launch_multi<21, 21, 4>(s, I, J, B, n, P, fb);
+    if (P.win_w == 21 && P.win_h == 21) launch_multi<21, 21, 4>(s, I, J, B, n, P, fb);
     else if (P.win_w == 15 && P.win_h == 15) launch_multi<15, 15, 4>(s, I, J, B, n, P, fb);
     else if (P.win_w == 31 && P.win_h == 31) launch_multi<31, 31, 2>(s, I, J, B, n, P, fb);
     else if (P.win_w == 35 && P.win_h == 35) launch_multi<35, 35, 2>(s, I, J, B, n, P, fb);

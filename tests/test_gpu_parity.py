@@ -321,7 +321,7 @@ def test_large_motion_restage(ctx, orc, synth):
 
 @pytest.mark.parametrize("bs", [3, 5, 7, 10])
 def test_fused_corner_kernel_equals_generic(ctx, orc, synth, bs, monkeypatch):
-    """k_eig_nms<BS> (no eigenvalue map in HBM) vs k_min_eig + k_nms_collect vs oracle."""
+    """k_eig_strip<BS> (no eigenvalue map in HBM) vs k_min_eig + k_nms_collect vs oracle."""
     img = synth.frame(777, 500, 5, 9, 31)
     mask = np.zeros_like(img)
     mask[3:450, 10:700] = 1

@@ -58,7 +58,7 @@ if lk.get("GRBM_GUI_ACTIVE") and lk.get("SQ_ACTIVE_INST_VALU"):
 def insts(prefix):
     b = next((v for k, v in blocks.items() if k.startswith(prefix) and "workgroups" not in k), None)
     return b.get("SQ_INSTS_VALU") if b else None
-out["beside_valu_insts_per_launch"] = {"corner_kernel": insts("k_eig_strip") or insts("k_eig_nms"), "k_pyramid_ahead": insts("k_pyramid<3, 64, 64>"),
+out["beside_valu_insts_per_launch"] = {"corner_kernel": insts("k_eig_strip"), "k_pyramid_ahead": insts("k_pyramid<3, 64, 64>"),
                                        "min_distance_chain": sum(insts(k) or 0 for k in ("k_key_hist", "k_key_select", "k_cell_count", "k_scan",
                                                                  "k_cell_fill", "k_suppress", "k_gather_accepted", "k_seg_order", "k_seg_init",
                                                                  "k_tail_gather", "k_tail_scatter", "k_tail_rank", "k_tail_order"))}

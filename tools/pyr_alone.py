@@ -9,7 +9,7 @@ ctx = Context(w, h, n_slots=4, max_pts=1024)
 for i in range(4):
     ctx.synth_frame(i, w, h, 100 * i, -50 * i, 1234)
 ctx.sync()
-ahead = os.environ.get("PYR_AHEAD") == "1"     # the copy-stream path (one-wave geometry unless ICELK_PYR_AHEAD_WIDE=1)
+ahead = os.environ.get("PYR_AHEAD") == "1"     # the path of pyramids built ahead (pyramid stream, one-wave geometry)
 for rep in range(30):
     ctx.drop_pyramid(rep % 4)
     if ahead:
