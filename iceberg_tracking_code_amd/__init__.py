@@ -16,6 +16,8 @@ from .utm import CameraModel, REF_UTM_FILTER, cam_to_utm, project_segment, proje
 from .sequence import track_image_sequence  # noqa: F401
 from .gridding import bin_velocities, create_grid_across_fjord, points_in_polygon  # noqa: F401
 from .day_grid import utm_to_gridded_utm, utm_to_gridded_utm_days  # noqa: F401
+from .postprocess import (VelocityCube, average_periods, average_spatially_temporally, combine_npzs,  # noqa: F401
+                          daily_averages, npz_to_csv, npz_to_mat, save_csv, velocities_to_regular_grid)
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

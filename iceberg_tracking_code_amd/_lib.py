@@ -89,6 +89,10 @@ SIGNATURES = {
     "icelk_grid_bin_windows": (C.c_int, [handle_p, f64p, f64p, f64p, f64p, f64p, C.c_int, i64p, i32p, i32p, i32p,
                                          C.c_int, i64p, i64p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                          C.c_int, C.c_int, u8p, i32p, f64p, f64p, f64p, i32p, f64p, f64p, f64p]),
+    "icelk_cube_set": (C.c_int, [handle_p, f64p, f64p, f64p, C.c_int, C.c_int]),
+    "icelk_cube_release": (C.c_int, [handle_p]),
+    "icelk_cube_average": (C.c_int, [handle_p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, f64p, f64p, f64p, f64p,
+                                     i32p, f64p]),
     "icelk_seg_read": (C.c_int, [handle_p, f32p, f32p, C.c_int, C.c_int, i32p, i32p]),
     "icelk_prof_enable": (C.c_int, [handle_p, C.c_int]),
     "icelk_prof_reset": (C.c_int, [handle_p]),

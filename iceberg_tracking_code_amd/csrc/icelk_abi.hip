@@ -198,6 +198,9 @@ struct Ctx {
     double* d_proj = nullptr;
     uint8_t* d_keep = nullptr;
     size_t proj_cap = 0;
+    // the velocity cube of icelk_cube_set: u, v, count as [window][cell] float64, resident until release / destroy
+    double *d_cube_u = nullptr, *d_cube_v = nullptr, *d_cube_count = nullptr;
+    int cube_ncells = 0, cube_nt = 0;
     bool seg_active = false;
     bool seg_staged = false;   // the OTHER set holds a new segment waiting for icelk_seg_switch
     int staged_n = 0;
@@ -760,7 +763,8 @@ static void destroy_ctx(Ctx* c)
     if (c->h_seg) hipHostFree(c->h_seg);
     void* ptrs[] = {c->d_bgr, c->d_mask, c->d_p0, c->d_p1, c->d_p0r, c->d_err_f, c->d_err_b, c->d_dist, c->d_corners,
                     c->d_st_f, c->d_st_b, c->d_valid, c->dset[0].D.eig, c->d_tracked,
-                    c->d_out_tracks, c->d_out_quality, c->d_proj, c->d_keep};
+                    c->d_out_tracks, c->d_out_quality, c->d_proj, c->d_keep, c->d_cube_u, c->d_cube_v,
+                    c->d_cube_count};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto& S : c->sb) {
@@ -2797,6 +2801,126 @@ int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const d
         HIPCHK(c, hipEventElapsedTime(&a, ev[0], ev[1]));
         HIPCHK(c, hipEventElapsedTime(&b, ev[2], ev[3]));
         *device_ms = (double)a + (double)b;
+    }
+    return ICELK_OK;
+}
+
+static void cube_free(Ctx* c)
+{
+    for (double** q : {&c->d_cube_u, &c->d_cube_v, &c->d_cube_count}) {
+        if (*q) hipFree(*q);
+        *q = nullptr;
+    }
+    c->cube_ncells = c->cube_nt = 0;
+}
+
+int icelk_cube_set(icelk_t* h, const double* u, const double* v, const double* count, int ncells, int nt)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!u || !v || !count || ncells < 1 || nt < 1) FAIL(c, ICELK_EARG, "bad cube arguments");
+    if ((long long)ncells * nt > 0x7fffffffLL) FAIL(c, ICELK_ECAP, "cells x windows does not fit 31 bits");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    cube_free(c);
+    const size_t bytes = sizeof(double) * (size_t)ncells * (size_t)nt;
+    if (hipMalloc(&c->d_cube_u, bytes) != hipSuccess || hipMalloc(&c->d_cube_v, bytes) != hipSuccess ||
+        hipMalloc(&c->d_cube_count, bytes) != hipSuccess) {
+        cube_free(c);
+        FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    }
+    c->cube_ncells = ncells;
+    c->cube_nt = nt;
+    const hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->d_cube_u, u, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->d_cube_v, v, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->d_cube_count, count, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ICELK_OK;
+}
+
+int icelk_cube_release(icelk_t* h)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    cube_free(c);
+    return ICELK_OK;
+}
+
+int icelk_cube_average(icelk_t* h, const int* sel_offset, const int* sel_index, int nperiods, int rows, int cols,
+                       int coarseness, double* out_u, double* out_v, double* out_speed, double* out_count,
+                       int* out_has_data, double* device_ms)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!sel_offset || nperiods < 1 || rows < 1 || cols < 1 || coarseness < 1 || !out_u || !out_v || !out_speed ||
+        !out_count || !out_has_data)
+        FAIL(c, ICELK_EARG, "bad cube averaging arguments");
+    if (!c->d_cube_u) FAIL(c, ICELK_ESTATE, "icelk_cube_set has not been called");
+    if ((long long)rows * cols != (long long)c->cube_ncells) FAIL(c, ICELK_EARG, "rows x cols is not the cube's cell count");
+    if (sel_offset[0] != 0) FAIL(c, ICELK_EARG, "selection offsets must start at 0");
+    for (int p = 0; p < nperiods; p++)
+        if (sel_offset[p + 1] < sel_offset[p]) FAIL(c, ICELK_EARG, "selection offsets must not decrease");
+    const int nsel = sel_offset[nperiods];
+    if (nsel > 0 && !sel_index) FAIL(c, ICELK_EARG, "bad cube averaging arguments");
+    for (int k = 0; k < nsel; k++)
+        if (sel_index[k] < 0 || sel_index[k] >= c->cube_nt) FAIL(c, ICELK_EARG, "a selected window lies outside the cube");
+    const int ncells = c->cube_ncells;
+    if ((long long)nperiods * ncells > 0x7fffffffLL || coarseness > 32767)
+        FAIL(c, ICELK_ECAP, "periods x cells does not fit 31 bits");
+    const int cr = (rows + coarseness - 1) / coarseness, cc = (cols + coarseness - 1) / coarseness;
+    const size_t nfine = (size_t)nperiods * (size_t)ncells, nout = (size_t)nperiods * (size_t)cr * (size_t)cc;
+    if (device_ms) *device_ms = 0.0;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBufs B;
+    int* d_off = B.get<int>((size_t)nperiods + 1);
+    int* d_idx = B.get<int>((size_t)nsel);
+    int* d_has = B.get<int>((size_t)nperiods);
+    double* d_f = B.get<double>(4 * nfine);
+    double* d_o = coarseness > 1 ? B.get<double>(4 * nout) : d_f;
+    if (!d_off || !d_idx || !d_has || !d_f || !d_o) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    const hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_off, sel_offset, sizeof(int) * ((size_t)nperiods + 1), hipMemcpyHostToDevice, s));
+    if (nsel > 0) HIPCHK(c, hipMemcpyAsync(d_idx, sel_index, sizeof(int) * (size_t)nsel, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(d_has, 0, sizeof(int) * (size_t)nperiods, s));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvFree {
+        hipEvent_t* e;
+        ~EvFree()
+        {
+            for (int k = 0; k < 2; k++)
+                if (e[k]) hipEventDestroy(e[k]);
+        }
+    } ev_free{ev};
+    if (device_ms) {
+        for (int k = 0; k < 2; k++) HIPCHK(c, hipEventCreate(&ev[k]));
+        HIPCHK(c, hipEventRecord(ev[0], s));
+    }
+    // fine fields: u, v, speed, count, one plane of nperiods * ncells each
+    launch_cube_temporal(s, c->d_cube_u, c->d_cube_v, c->d_cube_count, ncells, d_off, d_idx, nperiods, d_f, d_f + nfine,
+                         d_f + 2 * nfine, d_f + 3 * nfine, d_has);
+    int rc = check_launch(c, "cube_temporal");
+    if (rc) return rc;
+    if (coarseness > 1) {
+        launch_cube_spatial(s, d_f, d_f + nfine, d_f + 3 * nfine, rows, cols, coarseness, nperiods, d_o, d_o + nout,
+                            d_o + 2 * nout, d_o + 3 * nout);
+        rc = check_launch(c, "cube_spatial");
+        if (rc) return rc;
+    }
+    if (device_ms) HIPCHK(c, hipEventRecord(ev[1], s));
+    const size_t ob = sizeof(double) * nout;
+    HIPCHK(c, hipMemcpyAsync(out_u, d_o, ob, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(out_v, d_o + nout, ob, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(out_speed, d_o + 2 * nout, ob, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(out_count, d_o + 3 * nout, ob, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(out_has_data, d_has, sizeof(int) * (size_t)nperiods, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (device_ms) {
+        float ms = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        *device_ms = (double)ms;
     }
     return ICELK_OK;
 }

@@ -279,6 +279,13 @@ void launch_grid_day_assign(hipStream_t s, const double* x, const double* y, con
                             unsigned long long* t_min, unsigned long long* t_max);
 void launch_grid_reduce(hipStream_t s, const unsigned long long* keys, const int* key_count, const double* u,
                         const double* v, int ncells, int* count, double* mean_u, double* mean_v, double* speed);
+// averages of the velocity cube (k_cube.hip): the cube [window][cell], the periods' windows as CSR offsets + indices
+void launch_cube_temporal(hipStream_t s, const double* u, const double* v, const double* cnt, int ncells,
+                          const int* sel_offset, const int* sel_index, int nperiods, double* mean_u, double* mean_v,
+                          double* speed, double* count_sum, int* has_data);
+void launch_cube_spatial(hipStream_t s, const double* mean_u, const double* mean_v, const double* count_sum, int rows,
+                         int cols, int coarseness, int nperiods, double* out_u, double* out_v, double* out_speed,
+                         double* out_count);
 size_t sort_keys_asc(hipStream_t s, void* tmp, size_t tmp_bytes, const unsigned long long* in, unsigned long long* out,
                      int n, int end_bit);
 void launch_polygon_mask(hipStream_t s, const double* poly, int n, double crop_left, double crop_top, int w, int h,

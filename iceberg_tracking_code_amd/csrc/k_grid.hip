@@ -12,6 +12,7 @@
 // velocities in numpy's pairwise order (blocks of 128, 8 accumulators, halves aligned to 8) -- float64, bit for bit
 // what np.sum gives -- and takes the hypot (glibc's algorithm, see k_utm.hip).
 #include "icelk_internal.h"
+#include "np_sums.h"
 
 namespace icelk {
 
@@ -210,80 +211,19 @@ __global__ __launch_bounds__(256) void k_grid_day_assign(const double* __restric
     append_keys(m, i0, j0, (unsigned)w * (unsigned)ncells, g.rows, p, keys, key_count, key_cap);
 }
 
-__device__ __forceinline__ double leaf_sum(const unsigned long long* __restrict__ keys, const double* __restrict__ a,
-                                           int start, int n)
-{
-    auto at = [&](int t) { return a[(unsigned)keys[start + t]]; };
-    if (n < 8) {
-        double r = 0.0;
-        for (int t = 0; t < n; t++) r += at(t);
-        return r;
-    }
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) r[j] = at(j);
-    int t = 8;
-    for (; t < n - (n % 8); t += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) r[j] += at(t + j);
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; t < n; t++) res += at(t);
-    return res;
-}
+// element t of the velocities keyed by keys[start + t] (np_sums.h: numpy's pairwise order)
+struct KeyedAt {
+    const unsigned long long* __restrict__ keys;
+    const double* __restrict__ a;
+    int start;
+    __device__ __forceinline__ double operator()(int t) const { return a[(unsigned)keys[start + t]]; }
+};
 
-// numpy's pairwise sum over the velocities of keys[start, start + n), without recursion
-__device__ double pairwise_sum(const unsigned long long* __restrict__ keys, const double* __restrict__ a, int start, int n)
+// numpy's pairwise sum over the velocities of keys[start, start + n)
+__device__ __forceinline__ double pairwise_sum(const unsigned long long* __restrict__ keys,
+                                               const double* __restrict__ a, int start, int n)
 {
-    struct Frame { int start, n, stage; };
-    Frame st[40];
-    double vals[40];
-    int fp = 0, sp = 0;
-    st[fp++] = Frame{start, n, 0};
-    while (fp) {
-        Frame& f = st[fp - 1];
-        if (f.n <= 128) {
-            vals[sp++] = leaf_sum(keys, a, f.start, f.n);
-            fp--;
-            continue;
-        }
-        int n2 = f.n / 2;
-        n2 -= n2 % 8;
-        if (f.stage == 0) {
-            f.stage = 1;
-            st[fp++] = Frame{f.start, n2, 0};
-        } else if (f.stage == 1) {
-            f.stage = 2;
-            st[fp++] = Frame{f.start + n2, f.n - n2, 0};
-        } else {
-            const double r = vals[sp - 2] + vals[sp - 1];
-            sp -= 2;
-            vals[sp++] = r;
-            fp--;
-        }
-    }
-    return vals[0];
-}
-
-__device__ __forceinline__ double hypot_np(double x, double y)   // see k_utm.hip hypot_ref
-{
-    double ax = fabs(x), ay = fabs(y);
-    if (isinf(ax) || isinf(ay)) return HUGE_VAL;
-    if (ax != ax || ay != ay) return ax + ay;
-    if (ax < ay) { const double t = ax; ax = ay; ay = t; }
-    if (ay <= ax * 0x1p-54) return ax + ay;
-    double h = sqrt(ax * ax + ay * ay), t1, t2;
-    if (h <= 2.0 * ay) {
-        const double delta = h - ay;
-        t1 = ax * (2.0 * delta - ax);
-        t2 = (delta - 2.0 * (ax - ay)) * delta;
-    } else {
-        const double delta = h - ax;
-        t1 = 2.0 * delta * (ax - 2.0 * ay);
-        t2 = (4.0 * delta - ay) * ay + delta * delta;
-    }
-    h -= (t1 + t2) / (2.0 * h);
-    return h;
+    return np_pairwise_sum(KeyedAt{keys, a, start}, n);
 }
 
 __device__ __forceinline__ int lower_bound(const unsigned long long* __restrict__ keys, int n, unsigned long long v)

@@ -1,0 +1,88 @@
+// np_sums.h -- numpy's float64 arithmetic restated for the device, shared by k_grid.hip (per-cell sums of a window's
+// velocities, reached through sorted keys) and k_cube.hip (the c x c blocks of spatial_mean, strided).  The caller
+// says what "element t" is with a functor `at(t)`; the order of the additions is numpy's and must not change:
+// np.sum over a contiguous run adds below 8 terms one after the other from 0.0, otherwise in 8 accumulators, in blocks
+// of at most 128 terms, the halves of a longer run aligned to 8 (numpy/core/src/umath/loops_utils.h.src).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace icelk {
+
+template <typename At>
+__device__ __forceinline__ double np_leaf_sum(const At& at, int start, int n)
+{
+    if (n < 8) {
+        double r = 0.0;
+        for (int t = 0; t < n; t++) r += at(start + t);
+        return r;
+    }
+    double r[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) r[j] = at(start + j);
+    int t = 8;
+    for (; t < n - (n % 8); t += 8) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) r[j] += at(start + t + j);
+    }
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; t < n; t++) res += at(start + t);
+    return res;
+}
+
+// numpy's pairwise sum over at(0) .. at(n - 1), without recursion
+template <typename At>
+__device__ double np_pairwise_sum(const At& at, int n)
+{
+    struct Frame { int start, n, stage; };
+    Frame st[40];
+    double vals[40];
+    int fp = 0, sp = 0;
+    st[fp++] = Frame{0, n, 0};
+    while (fp) {
+        Frame& f = st[fp - 1];
+        if (f.n <= 128) {
+            vals[sp++] = np_leaf_sum(at, f.start, f.n);
+            fp--;
+            continue;
+        }
+        int n2 = f.n / 2;
+        n2 -= n2 % 8;
+        if (f.stage == 0) {
+            f.stage = 1;
+            st[fp++] = Frame{f.start, n2, 0};
+        } else if (f.stage == 1) {
+            f.stage = 2;
+            st[fp++] = Frame{f.start + n2, f.n - n2, 0};
+        } else {
+            const double r = vals[sp - 2] + vals[sp - 1];
+            sp -= 2;
+            vals[sp++] = r;
+            fp--;
+        }
+    }
+    return vals[0];
+}
+
+// np.hypot: glibc's algorithm (see k_utm.hip hypot_ref)
+__device__ __forceinline__ double hypot_np(double x, double y)
+{
+    double ax = fabs(x), ay = fabs(y);
+    if (isinf(ax) || isinf(ay)) return HUGE_VAL;
+    if (ax != ax || ay != ay) return ax + ay;
+    if (ax < ay) { const double t = ax; ax = ay; ay = t; }
+    if (ay <= ax * 0x1p-54) return ax + ay;
+    double h = sqrt(ax * ax + ay * ay), t1, t2;
+    if (h <= 2.0 * ay) {
+        const double delta = h - ay;
+        t1 = ax * (2.0 * delta - ax);
+        t2 = (delta - 2.0 * (ax - ay)) * delta;
+    } else {
+        const double delta = h - ax;
+        t1 = 2.0 * delta * (ax - 2.0 * ay);
+        t2 = (4.0 * delta - ay) * ay + delta * delta;
+    }
+    h -= (t1 + t2) / (2.0 * h);
+    return h;
+}
+
+}  // namespace icelk

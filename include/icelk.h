@@ -340,6 +340,28 @@ int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const d
                            int* count, double* mean_u, double* mean_v, double* speed, int* sel_count, double* t_min,
                            double* t_max, double* device_ms);
 
+/* ---- averages of the run-wide velocity cube (s4_postprocess_gridded_utm.py:264-343) -------------------------
+ * The stacked gridded windows of a run: u, v, count (host float64, NaN where a window has no entry for a cell), laid
+ * out [window][cell] with cell = row * cols + col -- nt planes of ncells values.  icelk_cube_set uploads them; they
+ * stay on the device, owned by the handle, until icelk_cube_release, the next icelk_cube_set or icelk_destroy.
+ * ICELK_ECAP when ncells * nt does not fit 31 bits. */
+int icelk_cube_set(icelk_t* h, const double* u, const double* v, const double* count, int ncells, int nt);
+int icelk_cube_release(icelk_t* h);
+/* Every averaging period of a request in one pass.  Period p selects the windows sel_index[sel_offset[p] ..
+ * sel_offset[p + 1]) (offsets from 0, non-decreasing; indices in [0, nt), ascending for the reference's order).  Per
+ * period and cell: np.nanmean of u and of v and np.nansum of count over the selected windows, as numpy computes them
+ * on cube[:, :, mask] (windows added one after the other; NaN where none holds a value); with coarseness > 1 then the
+ * reference's spatial_mean(..., nanmean = 0) of the three fields (zero padding to a multiple of coarseness, divisor
+ * coarseness^2, NaN propagates, numpy's order of additions).  rows * cols must be the cube's ncells.
+ * Out (host), per period p at p * out_cells + k with out_cells = ceil(rows / coarseness) * ceil(cols / coarseness):
+ * out_u, out_v, out_count, and out_speed = np.hypot(out_u, out_v); out_has_data[p] = 1 iff some cell of the period's
+ * uncoarsened fields has a non-NaN speed (the reference's "no data available" test).  device_ms (may be NULL):
+ * HIP-event time of the kernels; uploads and read-backs excluded.  Arguments are checked before anything is issued;
+ * ICELK_ESTATE without a cube, ICELK_ECAP when nperiods * ncells does not fit 31 bits or coarseness > 32767. */
+int icelk_cube_average(icelk_t* h, const int* sel_offset, const int* sel_index, int nperiods, int rows, int cols,
+                       int coarseness, double* out_u, double* out_v, double* out_speed, double* out_count,
+                       int* out_has_data, double* device_ms);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
