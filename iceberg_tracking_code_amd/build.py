@@ -16,8 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "obj")
 LIB = os.path.join(HERE, "libicelk.so")
-SOURCES = ["icelk_abi.hip", "k_image.hip", "k_pyramid.hip", "k_lk.hip", "k_lk_fast.hip", "k_lk_multi.hip", "k_corners.hip", "k_corners_fast.hip", "k_sort.hip", "k_tail.hip", "k_tracks.hip", "k_utm.hip", "k_mask.hip", "k_grid.hip", "k_cube.hip"]
-HEADERS = [os.path.join(CSRC, "icelk_internal.h"), os.path.join(CSRC, "lk_common.h"), os.path.join(CSRC, "lk_fast_tiles.h"), os.path.join(CSRC, "np_sums.h"), os.path.join(HERE, "..", "include", "icelk.h")]
+SOURCES = ["abi_handle.hip", "abi_frames.hip", "abi_lk.hip", "abi_detect.hip", "abi_segments.hip", "abi_post.hip",
+           "k_image.hip", "k_pyramid.hip", "k_lk.hip", "k_lk_fast.hip", "k_lk_multi.hip", "k_corners.hip", "k_corners_fast.hip", "k_sort.hip", "k_tail.hip", "k_tracks.hip", "k_utm.hip", "k_mask.hip", "k_grid.hip", "k_cube.hip"]
+# every header under csrc/ plus the public one: a new header cannot be forgotten by the staleness check
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(HERE, "..", "include", "icelk.h")]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-result", "-Wno-unused-value"]
@@ -37,25 +39,26 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _compile(src, force):
-    obj = os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
+def _compile(src, force, obj_dir, extra_flags):
+    obj = os.path.join(obj_dir, os.path.splitext(src)[0] + ".o")
     path = os.path.join(CSRC, src)
     if force or _stale(obj, [path] + HEADERS):
-        cmd = [_hipcc()] + FLAGS + ["-c", path, "-o", obj]
+        cmd = [_hipcc()] + FLAGS + list(extra_flags) + ["-c", path, "-o", obj]
         subprocess.check_call(cmd)
     return obj
 
 
-def build(force=False, verbose=False):
-    os.makedirs(OBJ, exist_ok=True)
+def build(force=False, verbose=False, lib=LIB, obj_dir=OBJ, extra_flags=()):
+    """lib / obj_dir / extra_flags: a second build beside the package's own (tools/build_variant.sh)."""
+    os.makedirs(obj_dir, exist_ok=True)
     with ThreadPoolExecutor(max_workers=min(6, len(SOURCES))) as ex:
-        objs = list(ex.map(lambda s: _compile(s, force), SOURCES))
-    if force or _stale(LIB, objs):
-        cmd = [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs
+        objs = list(ex.map(lambda s: _compile(s, force, obj_dir, extra_flags), SOURCES))
+    if force or _stale(lib, objs):
+        cmd = [_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs
         subprocess.check_call(cmd)
         if verbose:
-            print("built", LIB)
-    return LIB
+            print("built", lib)
+    return lib
 
 
 if __name__ == "__main__":

@@ -1,0 +1,493 @@
+// abi_post.hip -- after the frame loop: projection, point-in-polygon, gridding (one set / a day of windows),
+// the velocity cube and its averages.
+#include "icelk_ctx.h"
+
+namespace icelk {
+
+struct DevBufs {   // frees whatever was allocated when it goes out of scope; remembers a failed allocation
+    std::vector<void*> p;
+    bool failed = false;
+    ~DevBufs()
+    {
+        for (void* q : p)
+            if (q) hipFree(q);
+    }
+    template <typename T>
+    T* get(size_t count)
+    {
+        void* q = nullptr;
+        if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) return failed = true, nullptr;
+        p.push_back(q);
+        return reinterpret_cast<T*>(q);
+    }
+    bool ok() const { return !failed; }
+};
+
+// n elements on stream s (D and S differ in name at most: int64_t / long long)
+template <typename D, typename S>
+static hipError_t copy_n(D* dst, const S* src, size_t n, hipMemcpyKind kind, hipStream_t s)
+{
+    static_assert(sizeof(D) == sizeof(S), "element sizes differ");
+    return hipMemcpyAsync(dst, src, sizeof(D) * n, kind, s);
+}
+constexpr hipMemcpyKind kH2D = hipMemcpyHostToDevice, kD2H = hipMemcpyDeviceToHost;
+
+// two events around a stretch of a stream: the device_ms of the day gridder and of the cube average
+struct EvPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EvPair()
+    {
+        if (a) hipEventDestroy(a);
+        if (b) hipEventDestroy(b);
+    }
+    int create(Ctx* c)
+    {
+        HIPCHK(c, hipEventCreate(&a));
+        HIPCHK(c, hipEventCreate(&b));
+        return ICELK_OK;
+    }
+};
+
+// ---- what icelk_grid_bin and icelk_grid_bin_windows share ------------------------------------------------------------
+// A key holds its segment (a cell, or window * ncells + cell) in the high 32 bits, the point index in the low 32.
+struct GridDev {
+    const double *du = nullptr, *dv = nullptr;                    // per point (the caller's)
+    unsigned long long *keys = nullptr, *keys_sorted = nullptr;   // key_cap each
+    int *d_key_count = nullptr, *d_count = nullptr;               // 1, nseg
+    double *d_mu = nullptr, *d_mv = nullptr, *d_sp = nullptr;     // nseg each
+    void* sort_tmp = nullptr;
+    size_t sort_tmp_bytes = 0;
+    int key_cap = 0, nseg = 0, key_bits = 0;
+
+    void alloc(DevBufs& B, int key_cap_, int nseg_)
+    {
+        key_cap = key_cap_;
+        nseg = nseg_;
+        keys = B.get<unsigned long long>((size_t)key_cap);
+        keys_sorted = B.get<unsigned long long>((size_t)key_cap);
+        d_key_count = B.get<int>(1);
+        d_count = B.get<int>((size_t)nseg);
+        d_mu = B.get<double>((size_t)nseg);
+        d_mv = B.get<double>((size_t)nseg);
+        d_sp = B.get<double>((size_t)nseg);
+    }
+    // the sort's scratch, for key_cap keys: nothing is allocated between the kernels (the day gridder times them)
+    void alloc_sort(DevBufs& B, hipStream_t s)
+    {
+        for (key_bits = 33; (1LL << (key_bits - 32)) < (long long)nseg;) key_bits++;
+        sort_tmp_bytes = sort_keys_asc(s, nullptr, 0, keys, keys_sorted, key_cap, key_bits);
+        sort_tmp = B.get<uint8_t>(sort_tmp_bytes);
+    }
+};
+
+// Zero the key counter, assign (the caller's launch, with whatever it enqueues in front of it), read the key count back,
+// sort, reduce, and enqueue the copies of the four per-segment outputs; the caller synchronises.  t, if given: t[0]
+// ends behind the assign launch (the caller records its start), t[1] goes around sort + reduce -- the read-back between
+// them is not timed.
+template <typename Assign>
+static int grid_core(Ctx* c, const GridDev& G, Assign assign, const char* assign_name, EvPair* t, int* count,
+                     double* mean_u, double* mean_v, double* speed)
+{
+    const hipStream_t s = c->stream;
+    HIPCHK(c, hipMemsetAsync(G.d_key_count, 0, sizeof(int), s));
+    int rc = assign();
+    if (rc) return rc;
+    rc = check_launch(c, assign_name);
+    if (rc) return rc;
+    if (t) HIPCHK(c, hipEventRecord(t[0].b, s));
+    // the sort takes the key count from the host
+    int total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, G.d_key_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (total > G.key_cap) FAIL(c, ICELK_ECAP, "more than two cells per point on average (all points on cell edges?)");
+    if (t) HIPCHK(c, hipEventRecord(t[1].a, s));
+    const unsigned long long* sorted = G.keys;
+    if (total > 1) {
+        sort_keys_asc(s, G.sort_tmp, G.sort_tmp_bytes, G.keys, G.keys_sorted, total, G.key_bits);
+        rc = check_launch(c, "grid sort");
+        if (rc) return rc;
+        sorted = G.keys_sorted;
+    }
+    launch_grid_reduce(s, sorted, G.d_key_count, G.du, G.dv, G.nseg, G.d_count, G.d_mu, G.d_mv, G.d_sp);
+    rc = check_launch(c, "grid_reduce");
+    if (rc) return rc;
+    if (t) HIPCHK(c, hipEventRecord(t[1].b, s));
+    HIPCHK(c, copy_n(count, G.d_count, (size_t)G.nseg, kD2H, s));
+    HIPCHK(c, copy_n(mean_u, G.d_mu, (size_t)G.nseg, kD2H, s));
+    HIPCHK(c, copy_n(mean_v, G.d_mv, (size_t)G.nseg, kD2H, s));
+    HIPCHK(c, copy_n(speed, G.d_sp, (size_t)G.nseg, kD2H, s));
+    return ICELK_OK;
+}
+
+// run the projection kernel over `n` gathered tracks sitting in d_tracks_in and bring the results to the host
+int project_core(Ctx* c, const float* d_tracks_in, int n, int nv, const icelk_camera_t* cam, const icelk_utm_filter_t* filt,
+                 int host_pitch, double* x, double* y, double* u, double* v, double* speed, uint8_t* keep)
+{
+    const int m = nv - 1;
+    const size_t need = (size_t)n * (m > 0 ? m : 1);
+    if (need > c->post.proj_cap) {
+        if (c->post.d_proj) hipFree(c->post.d_proj);
+        c->post.d_proj = nullptr;
+        c->post.proj_cap = 0;
+        int rc = dmalloc(c, &c->post.d_proj, 5 * need);
+        if (!rc && !c->post.d_keep) rc = dmalloc(c, &c->post.d_keep, (size_t)c->max_pts);   // n <= max_pts always
+        if (rc) return rc;
+        c->post.proj_cap = need;
+    }
+    double* P[5];
+    for (int k = 0; k < 5; k++) P[k] = c->post.d_proj + (size_t)k * c->post.proj_cap;
+    {
+        ProfScope p(c, K_PROJECT);
+        launch_project_tracks(c->stream, d_tracks_in, n, nv, *cam, *filt, P[0], P[1], P[2], P[3], P[4], c->post.d_keep);
+    }
+    int rc = check_launch(c, "project_tracks");
+    if (rc) return rc;
+    double* H[5] = {x, y, u, v, speed};
+    for (int k = 0; k < 5; k++)
+        if (H[k] && m > 0)
+            HIPCHK(c, hipMemcpy2DAsync(H[k], sizeof(double) * host_pitch, P[k], sizeof(double) * m, sizeof(double) * m, n,
+                                       hipMemcpyDeviceToHost, c->stream));
+    if (keep) HIPCHK(c, hipMemcpyAsync(keep, c->post.d_keep, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ICELK_OK;
+}
+
+int check_projection_args(Ctx* c, const icelk_camera_t* cam, const icelk_utm_filter_t* filt)
+{
+    if (!cam || !filt) FAIL(c, ICELK_EARG, "camera / filter missing");
+    if (!(filt->interval_s > 0)) FAIL(c, ICELK_EARG, "tracking interval must be positive");
+    return ICELK_OK;
+}
+
+static double from_order_key(unsigned long long k)
+{
+    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double d;
+    memcpy(&d, &b, sizeof d);
+    return d;
+}
+
+static void cube_free(Ctx* c)
+{
+    for (double** q : {&c->post.d_cube_u, &c->post.d_cube_v, &c->post.d_cube_count}) {
+        if (*q) hipFree(*q);
+        *q = nullptr;
+    }
+    c->post.cube_ncells = c->post.cube_nt = 0;
+}
+
+}  // namespace icelk
+
+using namespace icelk;
+
+extern "C" {
+
+int icelk_project_tracks(icelk_t* h, const float* tracks, int n, int n_vertices, const icelk_camera_t* cam,
+                         const icelk_utm_filter_t* filt, double* x, double* y, double* u, double* v, double* speed,
+                         uint8_t* keep)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = check_projection_args(c, cam, filt);
+    if (rc) return rc;
+    if (n < 0 || n_vertices < 1 || (n > 0 && !tracks)) FAIL(c, ICELK_EARG, "bad track array");
+    if (n > c->max_pts) FAIL(c, ICELK_ECAP, "more tracks than max_pts of icelk_create");
+    if (n_vertices > kMaxVert) FAIL(c, ICELK_ECAP, "more than 17 vertices per track");
+    if (n == 0) return ICELK_OK;
+    HIPCHK(c, hipMemcpyAsync(c->d_out_tracks, tracks, sizeof(float) * 2 * (size_t)n * n_vertices, hipMemcpyHostToDevice,
+                             c->stream));
+    return project_core(c, c->d_out_tracks, n, n_vertices, cam, filt, n_vertices - 1, x, y, u, v, speed, keep);
+}
+
+// ---- gridding of projected velocities (s3_utm_to_gridded_utm.py:391-421) ------------------------
+
+int icelk_points_in_polygon(icelk_t* h, const double* poly_xy, int n_poly, const double* pts_xy, int n_pts,
+                            uint8_t* inside)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_poly < 0 || n_pts < 0 || (n_poly > 0 && !poly_xy) || (n_pts > 0 && (!pts_xy || !inside)))
+        FAIL(c, ICELK_EARG, "bad polygon / point arrays");
+    if (n_pts == 0) return ICELK_OK;
+    DevBufs B;
+    double* d_poly = B.get<double>(2 * (size_t)n_poly);
+    double* d_pts = B.get<double>(2 * (size_t)n_pts);
+    uint8_t* d_out = B.get<uint8_t>((size_t)n_pts);
+    if (!B.ok()) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    if (n_poly > 0) HIPCHK(c, copy_n(d_poly, poly_xy, 2 * (size_t)n_poly, kH2D, c->stream));
+    HIPCHK(c, copy_n(d_pts, pts_xy, 2 * (size_t)n_pts, kH2D, c->stream));
+    launch_points_in_polygon(c->stream, d_poly, n_poly, d_pts, n_pts, d_out);
+    int rc = check_launch(c, "points_in_polygon");
+    if (rc) return rc;
+    HIPCHK(c, copy_n(inside, d_out, (size_t)n_pts, kD2H, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ICELK_OK;
+}
+
+int icelk_grid_bin(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n, double left,
+                   double top, double spacing, int cols, int rows, const uint8_t* cell_on, int* count, double* mean_u,
+                   double* mean_v, double* speed)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n < 0 || cols <= 0 || rows <= 0 || !(spacing > 0) || !cell_on || !count || !mean_u || !mean_v || !speed ||
+        (n > 0 && (!x || !y || !u || !v)))
+        FAIL(c, ICELK_EARG, "bad gridding arguments");
+    if ((long long)cols * rows > (1 << 24) || n > (1 << 27)) FAIL(c, ICELK_ECAP, "grid or point set too large");
+    const int ncells = cols * rows;
+    // a point lies in one cell, or -- exactly on an edge / corner -- in up to four; 2 n + 1024 keys cover any set
+    // whose points are not all on edges, and the count is checked
+    const int key_cap = (int)std::min<long long>(2LL * n + 1024, 0x7fffffffLL);
+    DevBufs B;
+    GridDev G;
+    double* dx = B.get<double>((size_t)n);
+    double* dy = B.get<double>((size_t)n);
+    double* du = B.get<double>((size_t)n);
+    double* dv = B.get<double>((size_t)n);
+    uint8_t* d_on = B.get<uint8_t>((size_t)ncells);
+    const hipStream_t s = c->stream;
+    G.alloc(B, key_cap, ncells);
+    G.alloc_sort(B, s);
+    if (!B.ok()) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    G.du = du;
+    G.dv = dv;
+    if (n > 0) {
+        HIPCHK(c, copy_n(dx, x, (size_t)n, kH2D, s));
+        HIPCHK(c, copy_n(dy, y, (size_t)n, kH2D, s));
+        HIPCHK(c, copy_n(du, u, (size_t)n, kH2D, s));
+        HIPCHK(c, copy_n(dv, v, (size_t)n, kH2D, s));
+    }
+    HIPCHK(c, copy_n(d_on, cell_on, (size_t)ncells, kH2D, s));
+    auto assign = [&]() -> int {
+        launch_grid_assign(s, dx, dy, n, left, top, spacing, cols, rows, d_on, G.keys, G.d_key_count, key_cap);
+        return ICELK_OK;
+    };
+    int rc = grid_core(c, G, assign, "grid_assign", nullptr, count, mean_u, mean_v, speed);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ICELK_OK;
+}
+
+int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                           const double* t, int n, const int64_t* file_offset, const int* file_cam, const int* win_f0,
+                           const int* win_f1, int nfiles, const int64_t* t_lo, const int64_t* t_hi, int ncam, int nw,
+                           double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
+                           int* count, double* mean_u, double* mean_v, double* speed, int* sel_count, double* t_min,
+                           double* t_max, double* device_ms)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n < 0 || nfiles < 1 || ncam < 1 || nw < 1 || cols <= 0 || rows <= 0 || !(spacing > 0) || !file_offset ||
+        !file_cam || !win_f0 || !win_f1 || !t_lo || !t_hi || !cell_on || !count || !mean_u || !mean_v || !speed ||
+        !sel_count || !t_min || !t_max || (n > 0 && (!x || !y || !u || !v || !t)))
+        FAIL(c, ICELK_EARG, "bad gridding arguments");
+    const long long ncells_ll = (long long)cols * rows;
+    // keys hold (window * ncells + cell) in their high 32 bits, the point index in the low 32; the key counter and
+    // the 2 n + 1024 key slots are int
+    if (ncells_ll > (1 << 24) || ncells_ll * nw > 0x7fffffffLL || n > (1 << 30))
+        FAIL(c, ICELK_ECAP, "grid x windows or point set too large");
+    if (file_offset[0] != 0 || file_offset[nfiles] != n) FAIL(c, ICELK_EARG, "file offsets must span 0 .. n");
+    for (int f = 0; f < nfiles; f++)
+        if (file_offset[f + 1] < file_offset[f] || file_cam[f] < 0 || file_cam[f] >= ncam ||
+            (f > 0 && file_cam[f] < file_cam[f - 1]))
+            FAIL(c, ICELK_EARG, "bad file table");
+    for (int k = 0; k < ncam; k++)
+        for (int w = 0; w < nw; w++) {
+            const size_t sl = (size_t)k * nw + w;
+            if (t_lo[sl] > t_hi[sl] || (w + 1 < nw && t_hi[sl] > t_lo[sl + 1]))
+                FAIL(c, ICELK_EARG, "window bounds must be ascending and disjoint per camera");
+            if (win_f0[sl] <= win_f1[sl] && (win_f0[sl] < 0 || win_f1[sl] >= nfiles || file_cam[win_f0[sl]] != k ||
+                                             file_cam[win_f1[sl]] != k))
+                FAIL(c, ICELK_EARG, "a window loads files of another camera");
+        }
+    const int ncells = (int)ncells_ll, nseg = ncells * nw, nslot = nw * ncam;
+    const int key_cap = (int)std::min<long long>(2LL * n + 1024, 0x7fffffffLL);
+    memset(count, 0, sizeof(int) * nseg);
+    memset(mean_u, 0, sizeof(double) * nseg);
+    memset(mean_v, 0, sizeof(double) * nseg);
+    memset(speed, 0, sizeof(double) * nseg);
+    memset(sel_count, 0, sizeof(int) * nslot);
+    memset(t_min, 0, sizeof(double) * nslot);
+    memset(t_max, 0, sizeof(double) * nslot);
+    if (device_ms) *device_ms = 0.0;
+    if (n == 0) return ICELK_OK;
+    DevBufs B;
+    GridDev G;
+    const size_t nn = (size_t)n;
+    double* dx = B.get<double>(nn);
+    double* dy = B.get<double>(nn);
+    double* du = B.get<double>(nn);
+    double* dv = B.get<double>(nn);
+    double* dt = B.get<double>(nn);
+    long long* d_off = B.get<long long>((size_t)nfiles + 1);
+    int* d_fcam = B.get<int>((size_t)nfiles);
+    int* d_wf0 = B.get<int>((size_t)nslot);
+    int* d_wf1 = B.get<int>((size_t)nslot);
+    long long* d_lo = B.get<long long>((size_t)nslot);
+    long long* d_hi = B.get<long long>((size_t)nslot);
+    uint8_t* d_on = B.get<uint8_t>((size_t)ncells);
+    G.alloc(B, key_cap, nseg);
+    int* d_sel = B.get<int>((size_t)nslot);
+    unsigned long long* d_tmin = B.get<unsigned long long>((size_t)nslot);
+    unsigned long long* d_tmax = B.get<unsigned long long>((size_t)nslot);
+    const hipStream_t s = c->stream;
+    G.alloc_sort(B, s);
+    if (!B.ok()) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    G.du = du;
+    G.dv = dv;
+    HIPCHK(c, copy_n(dx, x, nn, kH2D, s));
+    HIPCHK(c, copy_n(dy, y, nn, kH2D, s));
+    HIPCHK(c, copy_n(du, u, nn, kH2D, s));
+    HIPCHK(c, copy_n(dv, v, nn, kH2D, s));
+    HIPCHK(c, copy_n(dt, t, nn, kH2D, s));
+    HIPCHK(c, copy_n(d_off, file_offset, (size_t)nfiles + 1, kH2D, s));
+    HIPCHK(c, copy_n(d_fcam, file_cam, (size_t)nfiles, kH2D, s));
+    HIPCHK(c, copy_n(d_wf0, win_f0, (size_t)nslot, kH2D, s));
+    HIPCHK(c, copy_n(d_wf1, win_f1, (size_t)nslot, kH2D, s));
+    HIPCHK(c, copy_n(d_lo, t_lo, (size_t)nslot, kH2D, s));
+    HIPCHK(c, copy_n(d_hi, t_hi, (size_t)nslot, kH2D, s));
+    HIPCHK(c, copy_n(d_on, cell_on, (size_t)ncells, kH2D, s));
+    // device_ms: assign, then sort + reduce; the key-count read-back between them is not counted
+    EvPair timer[2];
+    auto assign = [&]() -> int {
+        HIPCHK(c, hipMemsetAsync(d_sel, 0, sizeof(int) * nslot, s));
+        HIPCHK(c, hipMemsetAsync(d_tmin, 0xff, sizeof(unsigned long long) * nslot, s));
+        HIPCHK(c, hipMemsetAsync(d_tmax, 0, sizeof(unsigned long long) * nslot, s));
+        if (device_ms) {
+            int rct = timer[0].create(c);
+            if (!rct) rct = timer[1].create(c);
+            if (rct) return rct;
+            HIPCHK(c, hipEventRecord(timer[0].a, s));
+        }
+        launch_grid_day_assign(s, dx, dy, dt, n, d_off, d_fcam, d_wf0, d_wf1, nfiles, d_lo, d_hi, ncam, nw, left, top,
+                               spacing, cols, rows, d_on, G.keys, G.d_key_count, key_cap, d_sel, d_tmin, d_tmax);
+        return ICELK_OK;
+    };
+    int rc = grid_core(c, G, assign, "grid_day_assign", device_ms ? timer : nullptr, count, mean_u, mean_v, speed);
+    if (rc) return rc;
+    HIPCHK(c, copy_n(sel_count, d_sel, (size_t)nslot, kD2H, s));
+    std::vector<unsigned long long> kmin(nslot), kmax(nslot);
+    HIPCHK(c, copy_n(kmin.data(), d_tmin, (size_t)nslot, kD2H, s));
+    HIPCHK(c, copy_n(kmax.data(), d_tmax, (size_t)nslot, kD2H, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    for (int k = 0; k < nslot; k++)
+        if (sel_count[k] > 0) {
+            t_min[k] = from_order_key(kmin[k]);
+            t_max[k] = from_order_key(kmax[k]);
+        }
+    if (device_ms) {
+        float a = 0.0f, b = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&a, timer[0].a, timer[0].b));
+        HIPCHK(c, hipEventElapsedTime(&b, timer[1].a, timer[1].b));
+        *device_ms = (double)a + (double)b;
+    }
+    return ICELK_OK;
+}
+
+int icelk_cube_set(icelk_t* h, const double* u, const double* v, const double* count, int ncells, int nt)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!u || !v || !count || ncells < 1 || nt < 1) FAIL(c, ICELK_EARG, "bad cube arguments");
+    if ((long long)ncells * nt > 0x7fffffffLL) FAIL(c, ICELK_ECAP, "cells x windows does not fit 31 bits");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    cube_free(c);
+    const size_t bytes = sizeof(double) * (size_t)ncells * (size_t)nt;
+    if (hipMalloc(&c->post.d_cube_u, bytes) != hipSuccess || hipMalloc(&c->post.d_cube_v, bytes) != hipSuccess ||
+        hipMalloc(&c->post.d_cube_count, bytes) != hipSuccess) {
+        cube_free(c);
+        FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    }
+    c->post.cube_ncells = ncells;
+    c->post.cube_nt = nt;
+    const hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->post.d_cube_u, u, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->post.d_cube_v, v, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->post.d_cube_count, count, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return ICELK_OK;
+}
+
+int icelk_cube_release(icelk_t* h)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    cube_free(c);
+    return ICELK_OK;
+}
+
+int icelk_cube_average(icelk_t* h, const int* sel_offset, const int* sel_index, int nperiods, int rows, int cols,
+                       int coarseness, double* out_u, double* out_v, double* out_speed, double* out_count,
+                       int* out_has_data, double* device_ms)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!sel_offset || nperiods < 1 || rows < 1 || cols < 1 || coarseness < 1 || !out_u || !out_v || !out_speed ||
+        !out_count || !out_has_data)
+        FAIL(c, ICELK_EARG, "bad cube averaging arguments");
+    if (!c->post.d_cube_u) FAIL(c, ICELK_ESTATE, "icelk_cube_set has not been called");
+    if ((long long)rows * cols != (long long)c->post.cube_ncells) FAIL(c, ICELK_EARG, "rows x cols is not the cube's cell count");
+    if (sel_offset[0] != 0) FAIL(c, ICELK_EARG, "selection offsets must start at 0");
+    for (int p = 0; p < nperiods; p++)
+        if (sel_offset[p + 1] < sel_offset[p]) FAIL(c, ICELK_EARG, "selection offsets must not decrease");
+    const int nsel = sel_offset[nperiods];
+    if (nsel > 0 && !sel_index) FAIL(c, ICELK_EARG, "bad cube averaging arguments");
+    for (int k = 0; k < nsel; k++)
+        if (sel_index[k] < 0 || sel_index[k] >= c->post.cube_nt) FAIL(c, ICELK_EARG, "a selected window lies outside the cube");
+    const int ncells = c->post.cube_ncells;
+    if ((long long)nperiods * ncells > 0x7fffffffLL || coarseness > 32767)
+        FAIL(c, ICELK_ECAP, "periods x cells does not fit 31 bits");
+    const int cr = (rows + coarseness - 1) / coarseness, cc = (cols + coarseness - 1) / coarseness;
+    const size_t nfine = (size_t)nperiods * (size_t)ncells, nout = (size_t)nperiods * (size_t)cr * (size_t)cc;
+    if (device_ms) *device_ms = 0.0;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBufs B;
+    int* d_off = B.get<int>((size_t)nperiods + 1);
+    int* d_idx = B.get<int>((size_t)nsel);
+    int* d_has = B.get<int>((size_t)nperiods);
+    double* d_f = B.get<double>(4 * nfine);
+    double* d_o = coarseness > 1 ? B.get<double>(4 * nout) : d_f;
+    if (!B.ok()) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    const hipStream_t s = c->stream;
+    HIPCHK(c, copy_n(d_off, sel_offset, (size_t)nperiods + 1, kH2D, s));
+    if (nsel > 0) HIPCHK(c, copy_n(d_idx, sel_index, (size_t)nsel, kH2D, s));
+    HIPCHK(c, hipMemsetAsync(d_has, 0, sizeof(int) * (size_t)nperiods, s));
+    EvPair timer;
+    if (device_ms) {
+        if (int rct = timer.create(c)) return rct;
+        HIPCHK(c, hipEventRecord(timer.a, s));
+    }
+    // fine fields: u, v, speed, count, one plane of nperiods * ncells each
+    launch_cube_temporal(s, c->post.d_cube_u, c->post.d_cube_v, c->post.d_cube_count, ncells, d_off, d_idx, nperiods, d_f, d_f + nfine,
+                         d_f + 2 * nfine, d_f + 3 * nfine, d_has);
+    int rc = check_launch(c, "cube_temporal");
+    if (rc) return rc;
+    if (coarseness > 1) {
+        launch_cube_spatial(s, d_f, d_f + nfine, d_f + 3 * nfine, rows, cols, coarseness, nperiods, d_o, d_o + nout,
+                            d_o + 2 * nout, d_o + 3 * nout);
+        rc = check_launch(c, "cube_spatial");
+        if (rc) return rc;
+    }
+    if (device_ms) HIPCHK(c, hipEventRecord(timer.b, s));
+    HIPCHK(c, copy_n(out_u, d_o, nout, kD2H, s));
+    HIPCHK(c, copy_n(out_v, d_o + nout, nout, kD2H, s));
+    HIPCHK(c, copy_n(out_speed, d_o + 2 * nout, nout, kD2H, s));
+    HIPCHK(c, copy_n(out_count, d_o + 3 * nout, nout, kD2H, s));
+    HIPCHK(c, copy_n(out_has_data, d_has, (size_t)nperiods, kD2H, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (device_ms) {
+        float ms = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&ms, timer.a, timer.b));
+        *device_ms = (double)ms;
+    }
+    return ICELK_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,355 @@
+// icelk_ctx.h -- what the host-side translation units (abi_*.hip) share: the handle, the error macros, the
+// profiling / tracing scopes and the few helpers that cross a stage boundary.  The contract with the kernel files
+// is icelk_internal.h.
+#pragma once
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+
+#include "icelk_internal.h"
+
+namespace icelk {
+
+constexpr int kSegSets = 6;
+constexpr int kLaunchEvents = 32;
+constexpr int kMaxVert = 17;  // vertices per track kept on the device (track_len <= 16; reference uses 2)
+
+struct DetectJob {
+    bool active = false;
+    int w = 0, h = 0;
+    double quality = 0, min_distance = 0;
+    size_t ncell = 0;
+    const int* cand_count_ptr = nullptr;
+    int prune_want = 0;   // > 0: top-K pruning is on for this job
+    unsigned long long seq = 0;   // order of icelk_seg_detect_begin calls: the oldest job in flight is finished first
+    // device-driven tail (k_tail.hip): enqueued behind the min-distance stage by detect_begin; the corners of this detection
+    // start a segment in set `seg_set`, cut at max_corners
+    bool dev_tail = false;
+    int seg_set = -1;
+    int max_corners = 0;
+};
+
+struct Ctx {
+    // ---- abi_handle.hip: the handle itself, its switches, diagnostics and the profiling table
+    int device = 0;
+    int max_w = 0, max_h = 0, n_slots = 0, max_pts = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    std::string err;
+    int side_pick[4] = {-1, -1, -1, -1};   // which of the probed candidate streams became detection / candidates / pyramid / tail
+    double probe_limit = 0, probe_quickest = 0;
+    int fb_dist_form = ICELK_FB_HYPOT;     // icelk_set_fb_distance
+    int lk_sum_mode = 0;                   // icelk_set_variant "lk_sums"
+    int corner_variant = 0;                // icelk_set_variant "sobel_fma" (bits 0-1) | "eig_fma" (bit 2)
+    int lk_kernel_flags = 0;               // icelk_set_lk_kernel: ICELK_FLAG_GENERIC_KERNEL / _ONE_PER_WAVE or 0
+    // diagnostics: ICELK_LK_STAMPS=<file> records entry / exit time and placement of every workgroup of the LAST
+    // segment tracker launch and writes them to the file when the handle is destroyed (tools/lk_stamps.py reads it)
+    uint32_t* d_iters = nullptr;   // per-feature iteration counts of the latest tracker launch (while profiling is on)
+    int iters_n = 0;
+    unsigned long long* d_stamps = nullptr;
+    size_t stamps_cap = 0;     // workgroups
+    std::string stamps_path;
+    // profiling
+    bool prof = false;
+    bool prof_tracker_only = false;   // icelk_prof_enable(h, 2): every other kernel goes untimed (no event records on its stream)
+    std::vector<ProfEvt> evts, evt_pool;
+    int prof_launches[K_COUNT_] = {0};
+    double prof_ms[K_COUNT_] = {0};
+
+    // ---- abi_frames.hip: frame slots, pyramids, ingest
+    std::vector<Slot> slots;
+    // the streams of icelk_upload_gray_async, created at the first such upload.  Uploads alternate between two streams:
+    // between two copies of ONE stream the runtime spends ~50 us (completion signal of the first, dependency of the
+    // second: 220 us copies came out 270 us apart), which a copy queued on the other stream fills.  HIGH priority since
+    // round 4 -- a stream of the compute stream's class can share its hardware queue, and then the copy's dependencies
+    // wait behind a tracker launch
+    hipStream_t copy_hi[2] = {nullptr, nullptr};
+    unsigned upload_seq = 0;
+    // pyramids built ahead of their step: not on an upload stream, where a 12 MB upload of a LATER frame would stand
+    // between a pyramid and the tracker launch that waits for it
+    hipStream_t pyr_stream = nullptr;
+    // staging for 3-channel uploads
+    uint8_t* d_bgr = nullptr;
+    int bgr_pitch = 0;
+    bool pyr_per_level = false;            // ICELK_PYR_PER_LEVEL=1: one pyrDown launch per level (A/B, second statement)
+
+    // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
+    float *d_p0 = nullptr, *d_p1 = nullptr, *d_p0r = nullptr, *d_err_f = nullptr, *d_err_b = nullptr, *d_dist = nullptr;
+    uint8_t *d_st_f = nullptr, *d_st_b = nullptr, *d_valid = nullptr;
+
+    // ---- abi_detect.hip: detector streams, mask, candidate buffers, detector sets
+    // Detection (corner candidates, min-distance, sort) runs on its own stream: it only needs the frame,
+    // not the tracker's results, so it overlaps the LK launch of the same frame (s1:323-326 vs s1:437).
+    hipStream_t det_stream = nullptr;
+    hipEvent_t det_done = nullptr;      // corners of the latest detection are in d_corners
+    hipEvent_t corners_free = nullptr;  // the compute stream has consumed d_corners
+    float* d_corners = nullptr;         // (max_pts,2) corner list of the latest detection finished by the host's tail
+    // detector mask
+    uint8_t* d_mask = nullptr;
+    int mask_pitch = 0;
+    bool has_mask = false;
+    int mask_w = 0, mask_h = 0;
+    size_t ncell_cap = 0;
+    // Output of the corner kernel (candidate regions, per-tile counts, masked maximum), triple buffered: the
+    // candidates of a FUTURE detection frame can be produced (icelk_seg_detect_prepare, on eig_stream) while the
+    // min-distance stages of the detections in flight still read their own.  A detector set's D.raw / D.blk_count /
+    // D.max_key / D.src_* always mirror eo[its eo_active] (point_at_eig_out).
+    struct EigOut {
+        unsigned long long* raw = nullptr;
+        int* blk_count = nullptr;
+        unsigned* max_key = nullptr;
+        // scratch of the two-pass detector (DetectScratch::acand ...)
+        uint2* acand = nullptr;
+        int* acount = nullptr;
+        uint2* amaxc = nullptr;
+        int* amaxn = nullptr;
+        float* aemax = nullptr;
+        unsigned* fmax_key = nullptr;
+        unsigned* aties = nullptr;
+        double quality = 0;          // candidates below max * quality were never given their exact key (0: none were cut)
+        int nblk = 0, region = 0;
+        bool valid = false;          // holds the candidates of (slot, gen) for (block_size, use_mask, mask_gen)
+        int slot = -1, block_size = 0, use_mask = 0;
+        unsigned long long gen = 0, mask_gen = 0;
+        hipEvent_t done = nullptr;
+    } eo[3];
+    // Two detections may be in flight (begun, not finished): the min-distance stage of frame d+2 is issued before the
+    // host round trip of frame d, so that the round trip finds kernels that had a whole tracker launch to finish
+    // instead of standing in a serial loop with them.  Everything a detection owns is in its detector set; every
+    // detector function is handed the set it works on.
+    struct DetSet {
+        DetectScratch D{};                // D.eig (the full-frame map of icelk_min_eig_map) is shared by both sets
+        DetectJob job{};
+        int* h_counts = nullptr;          // pinned, device-visible: {candidates, accepted, undecided, ...} of the job
+        int counts_seq = 0;               // h_counts[kCountsSeq] == counts_seq: the counts published last have arrived
+        hipEvent_t counts_ev = nullptr;   // h_counts holds the counts of this set's detection
+        hipEvent_t tail_done = nullptr;   // the tail of this set's latest detection (sort, emit, counter reset) is through
+        size_t reset_ncell = 0;           // the detector counters are known to be zero for grids up to this many cells
+        bool counters_clean = false;
+        int eo_active = 0;                // the candidate buffer D points at
+    } dset[2];
+    // the set of the latest detector call (begin, finish, min_eig_map): icelk_detect_fast_stats reports its candidate buffer
+    int dset_last = 0;
+    hipStream_t tail_stream = nullptr;     // see detect_finish
+    unsigned long long job_seq = 0;
+    hipStream_t eig_stream = nullptr;
+    unsigned long long mask_gen = 0;
+    double prep_quality = 0;   // qualityLevel of the latest detection begun: what icelk_seg_detect_prepare cuts its candidates at
+
+    bool host_tail = false;           // ICELK_HOST_TAIL=1: the tail of every detection through the host, as before round 4 (A/B)
+    int tail_force_status = 0;        // ICELK_TAIL_FORCE_STATUS=1|2: the device verdict is forced to "host's tail" (tests of that path)
+    long long tails_dev = 0, tails_host = 0;   // segments staged by the device-driven tail / by the host's
+    int last_candidates = 0, last_accepted = 0;   // of the latest detection
+    double prune_factor = 8.0;                    // candidates kept per corner wanted (top-K pruning, detect_begin)
+
+    // ---- abi_segments.hip: segment sets, template tables, the deferred pair, read-out buffers
+    // Segment state, six sets (kSegSets).  More than one because, while the tracker launch of a detection frame still
+    // extends the closing segment in one set, the new segment is initialised in another (on the detection stream, right
+    // after the corners are emitted) -- the next tracker launch does not have to wait for an initialisation queued
+    // behind its predecessor.
+    // Six sets rotate: the current segment, the one staged for the next switch (sb_cur + 1), the one closed by the
+    // latest switch (sb_cur - 1), whose last pair may still be waiting (icelk_seg_track_defer) and whose tracks stay
+    // readable (icelk_seg_archive_closed) until the switch after, the one before that, which a tracker launch
+    // may still be working on when the host, a launch ahead of the device, stages the next segment -- and, since the tail
+    // of a detection writes the new segment's tables without the host (k_tail.hip), the sets behind the staged one that
+    // the detections in flight (two at most) have reserved (DetectJob::seg_set).
+    struct SegBuf {
+        float* live = nullptr;      // (max_pts,2) current position of every track of the segment
+        uint8_t* alive = nullptr;   // 1 while the track survives
+        int* order = nullptr;       // spatial launch order of the segment's tracks (k_seg_order)
+        int* order_border = nullptr;   // 1 int: leading entries of `order` that are border features
+        float* tracks = nullptr;    // [track][kMaxVert][2]
+        float* quality = nullptr;   // [track][kMaxVert-1]
+        // last launch on the compute stream that touches this set: own event or a shared launch event (see Slot::used)
+        hipEvent_t used = nullptr, used_own = nullptr;
+        hipEvent_t ready = nullptr;   // the tables of the segment staged in this set are written (detection or tail stream)
+        int vert = 0, upper = 0;    // vertices so far, tracks of the segment (= corners detected)
+        // templates the backward pass of the latest pair left in tmpl.buf[set & 1] serve the forward pass of the pair that
+        // writes vertex `tmpl_for` (with the window / levels of tmpl_key); -1: none
+        int tmpl_for = -1, tmpl_key = 0, tmpl_slot = -1;
+        unsigned long long tmpl_gen = 0;
+    } sb[kSegSets];
+    // Template reuse between the pairs of a segment (LKBuffers::tmpl_out; k_lk_fast.hip).  Consecutive segments use
+    // consecutive sets, and at most two segments have launches in flight: two tables, picked by the parity of the set.
+    struct {
+        void* buf[2] = {nullptr, nullptr};
+        size_t bytes = 0;          // per table
+        size_t row_bytes = 0;      // bytes per track the tables were laid out for (levels x quads x 64 lanes x 16 B)
+        size_t budget = (size_t)8 << 30;   // both tables together (ICELK_TEMPLATE_BUDGET_MB)
+        int quads = 0, levels = 0;
+        bool off = false;          // ICELK_NO_TEMPLATE_REUSE, or the tables could not be allocated
+        bool failed = false;       // ... the latter
+        long long taken = 0, left = 0;   // pairs whose forward pass took templates / whose backward pass left them
+    } tmpl;
+    int track_len_hint = 0;        // icelk_seg_track_len_hint: pairs per segment (0: unknown -- every pair leaves templates)
+    hipEvent_t launch_ev[kLaunchEvents] = {nullptr};   // one per tracker launch, round robin
+    int launch_seq = 0;
+    int sb_cur = 0;
+    bool closed_valid = false;
+    struct Deferred {
+        bool pending = false;
+        int set = 0, slot_prev = 0, slot_next = 0;
+        LKJob job{};
+        LKParams P{};
+    } defer;
+    bool seg_ready_pending = false;   // the compute stream has not been told yet to wait for the current set's tables (SegBuf::ready)
+    bool use_order = true;                 // ICELK_NO_ORDER=1 launches in detector order (A/B measurements)
+    // features this close to the frame border count as slow (launched first): from the window and pyramid depth of the
+    // latest tracker call
+    int border_px = (10 + kLkTileMargin + 2) << 2;
+    bool seg_active = false;
+    bool seg_staged = false;   // the OTHER set holds a new segment waiting for icelk_seg_switch
+    int staged_n = 0;
+    unsigned long long* d_tracked = nullptr;   // 64 sharded counters
+    unsigned long long* h_seg = nullptr;   // pinned: {alive tracks, features tracked}
+    float *d_out_tracks = nullptr, *d_out_quality = nullptr;
+
+    // ---- abi_post.hip: scratch of what runs after the frame loop
+    struct Post {
+        // projection epilogue: outputs x, y, u, v, speed (5 planes of proj_cap doubles) + keep bytes, grown on demand
+        double* d_proj = nullptr;
+        uint8_t* d_keep = nullptr;
+        size_t proj_cap = 0;
+        // the velocity cube of icelk_cube_set: u, v, count as [window][cell] float64, resident until release / destroy
+        double *d_cube_u = nullptr, *d_cube_v = nullptr, *d_cube_count = nullptr;
+        int cube_ncells = 0, cube_nt = 0;
+    } post;
+};
+
+// once per process (defined in abi_handle.hip)
+extern std::string g_create_err;
+extern std::mutex g_mu;
+
+#define HIPCHK(c, expr)                                                                      \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            (c)->err = std::string(#expr) + ": " + hipGetErrorString(e_);                    \
+            return ICELK_EHIP;                                                               \
+        }                                                                                    \
+    } while (0)
+
+#define FAIL(c, code, msg)   \
+    do {                     \
+        (c)->err = (msg);    \
+        return (code);       \
+    } while (0)
+
+inline Ctx* C(icelk_t* h) { return reinterpret_cast<Ctx*>(h); }
+
+inline int check_launch(Ctx* c, const char* what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        c->err = std::string(what) + ": " + hipGetErrorString(e);
+        return ICELK_EHIP;
+    }
+    return ICELK_OK;
+}
+
+// ---- roctx ranges (tracing) --------------------------------------------------------------------
+// ICELK_ROCTX=1: the host calls of the frame loop appear as named ranges in a rocprofv3 --marker-trace (tracker launch,
+// detection begin / stage, candidates ahead, pyramid ahead, upload).  The marker library is looked up at run time
+// (librocprofiler-sdk-roctx.so, else libroctx64.so): no link-time dependency, nothing is called when the variable is unset.
+struct Roctx {
+    int (*push)(const char*) = nullptr;
+    int (*pop)() = nullptr;
+    Roctx();
+};
+Roctx& roctx();   // one per process: abi_handle.hip
+struct Range {
+    bool on;
+    explicit Range(const char* name) : on(roctx().push != nullptr)
+    {
+        if (on) roctx().push(name);
+    }
+    ~Range()
+    {
+        if (on) roctx().pop();
+    }
+};
+
+struct ProfScope {
+    Ctx* c;
+    int id;
+    hipStream_t st;
+    ProfEvt ev{};
+    ProfScope(Ctx* c_, int id_, hipStream_t st_ = nullptr) : c(c_), id(id_), st(st_ ? st_ : c_->stream)
+    {
+        on = c->prof && (!c->prof_tracker_only || id == K_LK_FB || id == K_LK_FB_PAIR || id == K_LK);
+        if (on) {
+            if (!c->evt_pool.empty()) {
+                ev = c->evt_pool.back();
+                c->evt_pool.pop_back();
+            } else {
+                hipEventCreate(&ev.a);
+                hipEventCreate(&ev.b);
+            }
+            ev.id = id;
+            hipEventRecord(ev.a, st);
+        }
+    }
+    ~ProfScope()
+    {
+        if (on) {
+            hipEventRecord(ev.b, st);
+            c->evts.push_back(ev);
+        }
+    }
+    bool on = false;
+};
+
+inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+
+template <typename T>
+int dmalloc(Ctx* c, T** p, size_t count)
+{
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (count ? count : 1));
+    if (e != hipSuccess) {
+        c->err = std::string("hipMalloc: ") + hipGetErrorString(e);
+        return ICELK_ENOMEM;
+    }
+    return ICELK_OK;
+}
+
+// ---- helpers that cross a stage boundary (each defined in the file named) -------------------------------------------
+// abi_handle.hip
+void prof_drain(Ctx* c);
+hipError_t create_priority_stream(hipStream_t* s);
+// abi_frames.hip
+bool layout_ok(const Slot& s);
+void layout_levels(Slot& s, int w, int h);
+size_t slot_bytes(int w, int h);
+int pyramid_top_level(int w, int h, int win_w, int win_h, int max_level);
+int check_slot(Ctx* c, int slot, bool need_image);
+int wait_event(Ctx* c, hipStream_t s, hipEvent_t e);
+int wait_slot(Ctx* c, int slot);
+int ensure_pyramid(Ctx* c, int slot, int top_level);
+Pyramid pyramid_of(const Slot& s);
+// abi_lk.hip
+int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
+                   double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);
+// abi_detect.hip
+int alloc_eig_out(Ctx* c, Ctx::EigOut& e, int cand_cap);
+void free_eig_out(Ctx::EigOut& e);
+int alloc_det_set(Ctx* c, Ctx::DetSet& S, int cand_cap);
+void free_det_set(Ctx::DetSet& S);
+void activate_eig_out(Ctx* c, Ctx::DetSet& S, int idx);
+int detect_prepare(Ctx* c, int slot, int use_mask, int block_size);
+int detect_begin(Ctx* c, int slot, int use_mask, int max_corners, double quality, double min_distance, int block_size,
+                 bool for_segment);
+int detect_finish(Ctx* c, int max_corners, int cap, int* n_out, Ctx::SegBuf* seg = nullptr, bool* seg_done = nullptr,
+                  bool* dev_done = nullptr, DetectJob* finished = nullptr);
+int detect_counts_arrived(Ctx* c, bool* arrived);
+// abi_segments.hip
+int flush_deferred(Ctx* c);
+int flush_deferred_slot(Ctx* c, int slot);
+// abi_post.hip
+int check_projection_args(Ctx* c, const icelk_camera_t* cam, const icelk_utm_filter_t* filt);
+int project_core(Ctx* c, const float* d_tracks_in, int n, int nv, const icelk_camera_t* cam, const icelk_utm_filter_t* filt,
+                 int host_pitch, double* x, double* y, double* u, double* v, double* speed, uint8_t* keep);
+
+}  // namespace icelk

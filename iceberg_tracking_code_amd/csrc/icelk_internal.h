@@ -79,7 +79,7 @@ struct ProfEvt {
     int id;
 };
 
-struct Ctx;  // full definition in icelk_abi.hip
+struct Ctx;  // full definition in icelk_ctx.h
 
 // ---- launchers (each defined in its kernel TU) -------------------------------------------------
 void launch_bgr2gray(hipStream_t s, const uint8_t* src, int src_pitch, uint8_t* dst, int dst_pitch,
@@ -164,7 +164,7 @@ struct DetectScratch {
     int* undecided;        // 1
     unsigned long long* acc;   // accepted keys
     unsigned long long* acc_sorted;
-    unsigned long long* raw;   // candidate regions written by the corner kernel (one of two buffers, see icelk_abi.hip)
+    unsigned long long* raw;   // candidate regions written by the corner kernel (one of three buffers, see Ctx::EigOut in icelk_ctx.h)
     int* acc_count;        // 1
     void* sort_tmp;
     size_t sort_tmp_bytes;
@@ -262,7 +262,6 @@ void launch_fb_filter(hipStream_t s, const float* p0, const float* p0r, int n, f
                       uint8_t* valid);
 void launch_seg_init(hipStream_t s, const float* corners, int n, float* xy, uint8_t* alive, float* tracks,
                      int max_vert);
-// {alive tracks, features tracked so far} -> host_out[0..1] (pinned, 64-bit each)
 // projection epilogue (k_utm.hip); the structs are the public ones
 typedef icelk_camera_t UtmCamera;
 typedef icelk_utm_filter_t UtmFilter;
@@ -291,6 +290,7 @@ size_t sort_keys_asc(hipStream_t s, void* tmp, size_t tmp_bytes, const unsigned 
 void launch_polygon_mask(hipStream_t s, const double* poly, int n, double crop_left, double crop_top, int w, int h,
                          uint8_t* mask, int pitch);
 void launch_seg_order(hipStream_t s, const float* xy, int n, int w, int h, int border_px, int* order, int* border_count);
+// {alive tracks, features tracked so far} -> host_out[0..1] (pinned, 64-bit each)
 void launch_seg_stats(hipStream_t s, const uint8_t* alive, int n, const unsigned long long* tracked_shards,
                       unsigned long long* host_out);
 // rows of the alive tracks, in track order, packed into out_tracks (n_alive, nvert, 2) / out_quality

@@ -546,7 +546,7 @@ def test_named_variants_equal_the_oracles(orc, synth, name, value):
 
 def test_pyramid_of_forty_random_sizes(orc):
     """The one-launch pyramid reads and writes whole dwords and mirrors level borders inside LDS; what keeps that inside every
-    allocation and every region is a property of the slot layout (icelk_abi.hip layout_ok) and of the tile geometry -- not
+    allocation and every region is a property of the slot layout (abi_frames.hip layout_ok) and of the tile geometry -- not
     of the sizes the other tests happen to use.  Forty random frames from 1 x 1 to 300 x 300 (levels narrower than a halo,
     than a dword, than the filter), both geometries, every level against the oracle.  (Round 2 lost a run to a GPU abort
     in a work-in-progress form of this kernel on the 64 x 48 case -- levels narrower than a halo; that form never reached
