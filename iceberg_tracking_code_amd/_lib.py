@@ -93,6 +93,10 @@ SIGNATURES = {
     "icelk_cube_release": (C.c_int, [handle_p]),
     "icelk_cube_average": (C.c_int, [handle_p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, f64p, f64p, f64p, f64p,
                                      i32p, f64p]),
+    "icelk_calib_set": (C.c_int, [handle_p, f64p, C.c_int, f64p, C.c_int, C.c_double, C.c_double]),
+    "icelk_calib_release": (C.c_int, [handle_p]),
+    "icelk_calib_residuals": (C.c_int, [handle_p, f64p, C.c_int, f64p, f64p, f64p, f64p]),
+    "icelk_calib_cost": (C.c_int, [handle_p, f64p, C.c_int, f64p, f64p]),
     "icelk_seg_read": (C.c_int, [handle_p, f32p, f32p, C.c_int, C.c_int, i32p, i32p]),
     "icelk_prof_enable": (C.c_int, [handle_p, C.c_int]),
     "icelk_prof_reset": (C.c_int, [handle_p]),

@@ -4,50 +4,6 @@
 
 namespace icelk {
 
-struct DevBufs {   // frees whatever was allocated when it goes out of scope; remembers a failed allocation
-    std::vector<void*> p;
-    bool failed = false;
-    ~DevBufs()
-    {
-        for (void* q : p)
-            if (q) hipFree(q);
-    }
-    template <typename T>
-    T* get(size_t count)
-    {
-        void* q = nullptr;
-        if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) return failed = true, nullptr;
-        p.push_back(q);
-        return reinterpret_cast<T*>(q);
-    }
-    bool ok() const { return !failed; }
-};
-
-// n elements on stream s (D and S differ in name at most: int64_t / long long)
-template <typename D, typename S>
-static hipError_t copy_n(D* dst, const S* src, size_t n, hipMemcpyKind kind, hipStream_t s)
-{
-    static_assert(sizeof(D) == sizeof(S), "element sizes differ");
-    return hipMemcpyAsync(dst, src, sizeof(D) * n, kind, s);
-}
-constexpr hipMemcpyKind kH2D = hipMemcpyHostToDevice, kD2H = hipMemcpyDeviceToHost;
-
-// two events around a stretch of a stream: the device_ms of the day gridder and of the cube average
-struct EvPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EvPair()
-    {
-        if (a) hipEventDestroy(a);
-        if (b) hipEventDestroy(b);
-    }
-    int create(Ctx* c)
-    {
-        HIPCHK(c, hipEventCreate(&a));
-        HIPCHK(c, hipEventCreate(&b));
-        return ICELK_OK;
-    }
-};
-
 // ---- what icelk_grid_bin and icelk_grid_bin_windows share ------------------------------------------------------------
 // A key holds its segment (a cell, or window * ncells + cell) in the high 32 bits, the point index in the low 32.
 struct GridDev {

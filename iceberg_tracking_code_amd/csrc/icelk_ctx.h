@@ -217,6 +217,14 @@ struct Ctx {
         double *d_cube_u = nullptr, *d_cube_v = nullptr, *d_cube_count = nullptr;
         int cube_ncells = 0, cube_nt = 0;
     } post;
+
+    // ---- abi_calib.hip: the scene of icelk_calib_set, resident until release / destroy
+    struct Calib {
+        double* d_shore = nullptr;   // (M, 2): xi, yi relative to the image centre
+        double* d_water = nullptr;   // (W, 2): waterline vertices
+        int M = 0, W = 0;
+        double E = 0, N = 0;
+    } calib;
 };
 
 // once per process (defined in abi_handle.hip)
@@ -314,6 +322,51 @@ int dmalloc(Ctx* c, T** p, size_t count)
     }
     return ICELK_OK;
 }
+
+// ---- per-call device buffers, copies and timing of the stages after the frame loop (abi_post.hip, abi_calib.hip)
+struct DevBufs {   // frees whatever was allocated when it goes out of scope; remembers a failed allocation
+    std::vector<void*> p;
+    bool failed = false;
+    ~DevBufs()
+    {
+        for (void* q : p)
+            if (q) hipFree(q);
+    }
+    template <typename T>
+    T* get(size_t count)
+    {
+        void* q = nullptr;
+        if (hipMalloc(&q, sizeof(T) * (count ? count : 1)) != hipSuccess) return failed = true, nullptr;
+        p.push_back(q);
+        return reinterpret_cast<T*>(q);
+    }
+    bool ok() const { return !failed; }
+};
+
+// n elements on stream s (D and S differ in name at most: int64_t / long long)
+template <typename D, typename S>
+inline hipError_t copy_n(D* dst, const S* src, size_t n, hipMemcpyKind kind, hipStream_t s)
+{
+    static_assert(sizeof(D) == sizeof(S), "element sizes differ");
+    return hipMemcpyAsync(dst, src, sizeof(D) * n, kind, s);
+}
+constexpr hipMemcpyKind kH2D = hipMemcpyHostToDevice, kD2H = hipMemcpyDeviceToHost;
+
+// two events around a stretch of a stream: the device_ms of the day gridder and of the cube average
+struct EvPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EvPair()
+    {
+        if (a) hipEventDestroy(a);
+        if (b) hipEventDestroy(b);
+    }
+    int create(Ctx* c)
+    {
+        HIPCHK(c, hipEventCreate(&a));
+        HIPCHK(c, hipEventCreate(&b));
+        return ICELK_OK;
+    }
+};
 
 // ---- helpers that cross a stage boundary (each defined in the file named) -------------------------------------------
 // abi_handle.hip

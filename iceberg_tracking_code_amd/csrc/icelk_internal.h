@@ -285,6 +285,13 @@ void launch_cube_temporal(hipStream_t s, const double* u, const double* v, const
 void launch_cube_spatial(hipStream_t s, const double* mean_u, const double* mean_v, const double* count_sum, int rows,
                          int cols, int coarseness, int nperiods, double* out_u, double* out_v, double* out_speed,
                          double* out_count);
+// the calibration misfit (k_calib.hip): candidates of 11 doubles (X, U, V, sigma in pixels, H), shoreline points
+// (xi, yi) relative to the image centre, waterline vertices (x, y); out_tx / out_ty may be null
+void launch_calib_residuals(hipStream_t s, const double* cand, int P, const double* shore, int M, const double* water,
+                            int W, double E, double N, double* out_dist, double* out_tx, double* out_ty);
+void launch_calib_cost(hipStream_t s, const double* cand, int P, const double* shore, int M, const double* water, int W,
+                       double E, double N, double* out_meansq);
+int calib_cost_max_points();   // the most shoreline points launch_calib_cost takes
 size_t sort_keys_asc(hipStream_t s, void* tmp, size_t tmp_bytes, const unsigned long long* in, unsigned long long* out,
                      int n, int end_bit);
 void launch_polygon_mask(hipStream_t s, const double* poly, int n, double crop_left, double crop_top, int w, int h,

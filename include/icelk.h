@@ -362,6 +362,25 @@ int icelk_cube_average(icelk_t* h, const int* sel_offset, const int* sel_index, 
                        int coarseness, double* out_u, double* out_v, double* out_speed, double* out_count,
                        int* out_has_data, double* device_ms);
 
+/* ---- camera calibration: the shoreline misfit (s0_2_camera_calibration.py:117-152, 231-275) -------------------
+ * The scene: M shoreline points digitised on a photo, as (xi, yi) = (x - width / 2, y - height / 2) pairs, the W
+ * vertices of the waterline on the map as (x, y) pairs (finite, or ICELK_EARG), and the camera position E, N.
+ * icelk_calib_set uploads it; it stays on the device, owned by the handle, until icelk_calib_release, the next
+ * icelk_calib_set or icelk_destroy.  ICELK_EARG for M < 1, W < 1 or null pointers. */
+int icelk_calib_set(icelk_t* h, const double* shore_xy, int M, const double* water_xy, int W, double E, double N);
+int icelk_calib_release(icelk_t* h);
+/* P candidates of 11 doubles each: X[3], U[3], V[3] (the direction vectors of photo_to_utm, s0_2:124-136), sigma
+ * scaled to pixels, H.  Per candidate p and point m, at p * M + m: out_dist = the distance from the projected point
+ * (tx, ty) of s0_2:146-150 to the nearest waterline vertex, bit for bit what optimizefun_calibration returns (NaN
+ * where tx or ty is NaN, inf where one is infinite); out_tx, out_ty (each may be NULL): the projected point.
+ * device_ms (may be NULL): HIP-event time of the kernel; uploads and read-backs excluded.  Arguments are checked
+ * before anything is issued; ICELK_ESTATE without a scene, ICELK_ECAP when P * M does not fit 31 bits. */
+int icelk_calib_residuals(icelk_t* h, const double* cand, int P, double* out_dist, double* out_tx, double* out_ty,
+                          double* device_ms);
+/* The same without the (P, M) output: out_meansq[p] = np.mean(residuals[p] ** 2), the squares added in numpy's
+ * pairwise order.  Also ICELK_ECAP for a scene of more than 4096 shoreline points. */
+int icelk_calib_cost(icelk_t* h, const double* cand, int P, double* out_meansq, double* device_ms);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
