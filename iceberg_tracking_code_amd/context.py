@@ -90,7 +90,8 @@ class Context:
 
     def set_variant(self, name, value):
         """A named build-dependent variant of OpenCV's arithmetic: "lk_sums" 0|1|2, "sobel_fma" 0..3, "eig_fma" 0|1
-        (icelk_set_variant; 0 = default).  The oracle has the same switches (oracle.set_variant)."""
+        (icelk_set_variant; 0 = default).  The oracle has the same switches (oracle.set_variant).  "lk_wide_sums" 1 is a
+        testing aid: the tuned tracker kernels take their 64-bit wave sums everywhere; no result changes."""
         self._ck(self._lib.icelk_set_variant(self._h, name.encode(), int(value)))
 
     def set_fb_distance(self, form):

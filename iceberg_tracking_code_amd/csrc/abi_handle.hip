@@ -439,6 +439,7 @@ int icelk_set_variant(icelk_t* h, const char* name, int value)
     if (!h || !name) return ICELK_EARG;
     Ctx* c = C(h);
     if (!strcmp(name, "lk_sums") && value >= 0 && value <= 2) c->lk_sum_mode = value;
+    else if (!strcmp(name, "lk_wide_sums") && (value == 0 || value == 1)) c->lk_wide_sums = value;
     else if (!strcmp(name, "sobel_fma") && value >= 0 && value <= 3) c->corner_variant = (c->corner_variant & 4) | value;
     else if (!strcmp(name, "eig_fma") && (value == 0 || value == 1)) c->corner_variant = (c->corner_variant & 3) | (value << 2);
     else FAIL(c, ICELK_EARG, "unknown variant / value");

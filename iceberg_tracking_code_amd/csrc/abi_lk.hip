@@ -34,6 +34,7 @@ int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, in
     P->margin = 6;
     P->dist_form = c->fb_dist_form;
     P->sum_mode = c->lk_sum_mode;
+    P->sum_guard = c->lk_wide_sums ? 0u : 1u << 26;
     return ICELK_OK;
 }
 

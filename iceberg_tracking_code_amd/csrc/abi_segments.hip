@@ -159,7 +159,8 @@ static bool same_lk_params(const LKParams& a, const LKParams& b)
 {
     return a.win_w == b.win_w && a.win_h == b.win_h && a.top_level == b.top_level && a.max_count == b.max_count &&
            a.eps2 == b.eps2 && a.flags == b.flags && a.min_eig_thr == b.min_eig_thr && a.fb_thr == b.fb_thr &&
-           a.margin == b.margin && a.dist_form == b.dist_form && a.sum_mode == b.sum_mode;
+           a.margin == b.margin && a.dist_form == b.dist_form && a.sum_mode == b.sum_mode &&
+           a.sum_guard == b.sum_guard;
 }
 
 // shared by icelk_seg_track / icelk_seg_track_async / icelk_seg_track_defer

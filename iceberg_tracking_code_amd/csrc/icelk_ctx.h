@@ -43,6 +43,7 @@ struct Ctx {
     double probe_limit = 0, probe_quickest = 0;
     int fb_dist_form = ICELK_FB_HYPOT;     // icelk_set_fb_distance
     int lk_sum_mode = 0;                   // icelk_set_variant "lk_sums"
+    int lk_wide_sums = 0;                  // icelk_set_variant "lk_wide_sums"
     int corner_variant = 0;                // icelk_set_variant "sobel_fma" (bits 0-1) | "eig_fma" (bit 2)
     int lk_kernel_flags = 0;               // icelk_set_lk_kernel: ICELK_FLAG_GENERIC_KERNEL / _ONE_PER_WAVE or 0
     // diagnostics: ICELK_LK_STAMPS=<file> records entry / exit time and placement of every workgroup of the LAST

@@ -38,6 +38,9 @@ struct LKParams {
     // float lanes of OpenCV 3.x's SSE2 block / 4.x's CV_SIMD128 block (oracle/icelk_oracle.c orc_set_variant).  Non-zero
     // runs in the window-generic kernel only.
     int sum_mode;
+    // bound of the narrow-sum guard of the tuned kernels (lk_common.h): 2^26, or 0 under icelk_set_variant "lk_wide_sums" 1,
+    // which no lane passes, so every sum takes the 64-bit arm.  A kernel argument: it sits in a scalar register.
+    unsigned sum_guard;
 };
 
 // kernel ids for the profiling table

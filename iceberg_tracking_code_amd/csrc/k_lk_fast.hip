@@ -375,12 +375,26 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
             template_pixels<WW, WH, 1, 0>(T, ldsI, (uint32_t)uni((int)wi0), (uint32_t)uni((int)wi1),
                                           ix0 & 3, i_inside, ipx, ipy, LI.w, LI.h, trow, tcol, psel, a11, a12, a22, fsum, tlen);
             // |Ix*Ix| <= 4080^2 per pixel: 16-lane sums fit int32 while a lane holds <= 8 pixels
-            long long s11, s12, s22;
-            if constexpr (kSmall) wave_sum_mat_i64(a11, a12, a22, s11, s12, s22);
-            else wave_sum3_i64<1>(a11, a12, a22, s11, s12, s22);
-            A11 = sum_to_float(s11) * FLT_SCALE;
-            A12 = sum_to_float(s12) * FLT_SCALE;
-            A22 = sum_to_float(s22) * FLT_SCALE;
+            // Narrow arm (lk_common.h, "narrow sums behind a guard"): a11, a22 >= 0 below 2^26 and a12 in [-2^25, 2^25) in
+            // every lane -- one OR, since a11 | a22 < 2^26 exactly when both are -- so the totals fit 32 bits.  The ballot's
+            // compare mask decides on the scalar unit (a real branch: the condition is the same for the whole wave).
+            // The 0.7 makes the narrow arm the fall-through and leaves the register allocation alone: a plain
+            // __builtin_expect moved SGPR spills into the 21x21 and 35x35 kernels.
+            const bool wide3 = fsum != nullptr ||
+                __builtin_amdgcn_ballot_w64(((unsigned)a11 | (unsigned)a22 | ((unsigned)a12 + kSumGuardBias)) >= P.sum_guard) != 0;
+            if (__builtin_expect_with_probability(!wide3, 1, 0.7)) {
+                const int n11 = dpp_all_steps(a11), n12 = dpp_all_steps(a12), n22 = dpp_all_steps(a22);
+                A11 = lane63_float_u32(n11) * FLT_SCALE;
+                A12 = lane63_float_i32(n12) * FLT_SCALE;
+                A22 = lane63_float_u32(n22) * FLT_SCALE;
+            } else {
+                long long s11, s12, s22;
+                if constexpr (kSmall) wave_sum_mat_i64(a11, a12, a22, s11, s12, s22);
+                else wave_sum3_i64<1>(a11, a12, a22, s11, s12, s22);
+                A11 = sum_to_float(s11) * FLT_SCALE;
+                A12 = sum_to_float(s12) * FLT_SCALE;
+                A22 = sum_to_float(s22) * FLT_SCALE;
+            }
             if (fsum) {
                 // 3.x: groups of 4 pixels, lanes folded ((l0+l1)+l2)+l3; 4.x: groups of 8, folded (l0+l2)+(l1+l3)
                 float o[3];
@@ -451,10 +465,21 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
             residual_pixels<WW, WH, 1, 0, false>(T, ldsJ, jb, (uint32_t)uni((int)wj0),
                                                  (uint32_t)uni((int)wj1), joff, tlen, b1, b2, fsum, trow, tcol);
             // |diff*Ix| <= 8160*4080 per pixel: 8-lane sums fit int32 while a lane holds <= 8 pixels
-            long long t1, t2;
-            wave_sum2_i64<kSmall ? 8 : 1>(b1, b2, t1, t2);
-            float fb1 = sum_to_float(t1) * FLT_SCALE;
-            float fb2 = sum_to_float(t2) * FLT_SCALE;
+            // Narrow arm: b1 and b2 in [-2^25, 2^25) in every lane (lk_common.h has the proof that the totals then fit int32
+            // and the float is the wide arm's bit for bit); on real content that is nearly every iteration.
+            float fb1, fb2;
+            const bool wide2 = fsum != nullptr ||
+                __builtin_amdgcn_ballot_w64((((unsigned)b1 + kSumGuardBias) | ((unsigned)b2 + kSumGuardBias)) >= P.sum_guard) != 0;
+            if (__builtin_expect_with_probability(!wide2, 1, 0.7)) {
+                const int n1 = dpp_all_steps(b1), n2 = dpp_all_steps(b2);
+                fb1 = lane63_float_i32(n1) * FLT_SCALE;
+                fb2 = lane63_float_i32(n2) * FLT_SCALE;
+            } else {
+                long long t1, t2;
+                wave_sum2_i64<kSmall ? 8 : 1>(b1, b2, t1, t2);
+                fb1 = sum_to_float(t1) * FLT_SCALE;
+                fb2 = sum_to_float(t2) * FLT_SCALE;
+            }
             if (fsum) {
                 // both versions: groups of 8 pixels in 2 x 4 lanes; (q0[k] + q1[k]) pairs = chains (0 + 2) + (1 + 3)
                 float o[3];

@@ -173,6 +173,40 @@ __device__ __forceinline__ void wave_sum_mat_i64(int v0, int v1, int v2, long lo
     s2 = lane63_i64(l2, h2);
 }
 
+// ---- narrow sums behind a guard (round 7) --------------------------------------------------------------------------------
+// The exact sums need 64 bits at the limits of the arithmetic (a 21x21 sum reaches 2^33.8), on real content almost never.
+// Guard (LKParams::sum_guard = 2^26): every lane's partial v satisfies (unsigned)(v + 2^25) < 2^26, i.e. -2^25 <= v < 2^25.
+// Then any sum over k <= 64 lanes -- every prefix the DPP steps form, and the wave total -- lies in [-k 2^25, k (2^25 - 1)],
+// inside [-2^31, 2^31 - 64]: no 32-bit step wraps, and lane 63 ends with the same integer t the 64-bit network gives.
+// A partial that is never negative (sum Ix^2, sum Iy^2) may reach 2^26 - 1: 64 of them stay below 2^32, and the same adds
+// read as unsigned do not wrap.  One v_cvt_f32_i32 / v_cvt_f32_u32 of t rounds it once, to nearest even: the rounding of
+// t that sum_to_float (k_lk_fast.hip) reproduces and the oracle's (float)int64 performs -- the float is the same bit for bit.
+// With sum_guard = 0 (icelk_set_variant "lk_wide_sums" 1) no lane passes and the 64-bit arm runs everywhere.
+constexpr unsigned kSumGuardBias = 1u << 25, kSumGuard = 1u << 26;
+
+// all six steps of wave_sum_i32 without the read-back: lane 63 holds the wave total
+// (unsigned adds: the same instructions, and the totals of the never-negative sums may pass 2^31)
+__device__ __forceinline__ int dpp_all_steps(int s)
+{
+    unsigned v = (unsigned)s;
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);  // row_shr:1
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);  // row_shr:2
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);  // row_shr:4
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);  // row_shr:8
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, true);  // row_bcast15 -> rows 1,3
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true);  // row_bcast31 -> rows 2,3
+    return (int)v;
+}
+// converted in the lane, then one v_readlane of lane 63
+__device__ __forceinline__ float lane63_float_i32(int v)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int((float)v), 63));
+}
+__device__ __forceinline__ float lane63_float_u32(int v)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int((float)(unsigned)v), 63));
+}
+
 // correctly rounded int64 -> float for |t| < 2^52, through one exact double
 __device__ __forceinline__ float i64_to_float(long long t)
 {

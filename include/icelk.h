@@ -90,7 +90,11 @@ int icelk_set_fb_distance(icelk_t* h, int form);
  *   "sobel_fma"  bit 0   the Sobel column pass fused (4.x SymmColumnSmallVec_32f in an FMA3 build); bit 1: the row pass fused
  *   "eig_fma"    1       calcMinEigenVal's (a-c)^2 + b^2 as one fused multiply-add
  * (the corner SET is the same under all of them on the test frames, the order of near-equal corners changes.)
- * A cv2 cross-check that finds one of them to be what the reference's OpenCV build does flips this switch. */
+ * A cv2 cross-check that finds one of them to be what the reference's OpenCV build does flips this switch.
+ * One name is a testing aid and changes no result:
+ *   "lk_wide_sums" 1     the tuned tracker kernels reduce A11 .. b2 in 64 bits everywhere; by default (0) a wave whose lane
+ *                        partials all lie below 2^25 in magnitude takes the 32-bit reduction, which gives the same float bit
+ *                        for bit.  (No switch forces the 32-bit arm: beyond the guard it would be wrong.) */
 int icelk_set_variant(icelk_t* h, const char* name, int value);
 
 /* ---- frame ingest: replaces cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY) at s1:283,311 / s0_1:71,80 */
