@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ICELK_LIBRARY: another build of this same library (A/B measurements of kernel variants: tools/build_variant.sh)
 LIB_PATH = os.environ.get("ICELK_LIBRARY") or os.path.join(_HERE, "libicelk.so")
 
-OK, EARG, ENOMEM, EHIP, ECAP, ESTATE = 0, -1, -2, -3, -4, -5
+OK, EARG, ENOMEM, EHIP, ECAP, ESTATE, EUNSUP = 0, -1, -2, -3, -4, -5, -6
 
 u8p = C.POINTER(C.c_uint8)
 f32p = C.POINTER(C.c_float)
@@ -19,6 +19,18 @@ i64p = C.POINTER(C.c_int64)
 f64p = C.POINTER(C.c_double)
 vp = C.c_void_p
 handle_p = C.c_void_p
+i16p = C.POINTER(C.c_int16)
+
+
+class JpegInfo(C.Structure):
+    """icelk_jpeg_info_t of include/icelk.h"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hmax", C.c_int32), ("vmax", C.c_int32),
+                ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("restart_interval", C.c_int32),
+                ("comp_w", C.c_int32 * 3), ("comp_h", C.c_int32 * 3), ("blocks_x", C.c_int32 * 3), ("blocks_y", C.c_int32 * 3),
+                ("coef_offset", C.c_uint64 * 3), ("coef_count", C.c_uint64), ("quant", (C.c_uint16 * 64) * 3)]
+
+
+jpeg_info_p = C.POINTER(JpegInfo)
 
 # name -> (restype, argtypes); the single source of truth for the symbol-export test as well
 SIGNATURES = {
@@ -32,6 +44,10 @@ SIGNATURES = {
     "icelk_set_lk_kernel": (C.c_int, [handle_p, C.c_int]),
     "icelk_upload_gray": (C.c_int, [handle_p, C.c_int, u8p, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_bgr": (C.c_int, [handle_p, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_jpeg_describe": (C.c_int, [vp, C.c_uint64, jpeg_info_p]),
+    "icelk_jpeg_read_coefficients": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64]),
+    "icelk_upload_jpeg": (C.c_int, [handle_p, C.c_int, jpeg_info_p, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_jpeg_decode_rgb": (C.c_int, [handle_p, jpeg_info_p, vp, u8p, C.c_int]),
     "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

@@ -119,6 +119,21 @@ class Context:
             a = np.ascontiguousarray(a)   # rows must be dense; a row pitch (cropped view) is fine as it is
         self._ck(self._lib.icelk_upload_bgr(self._h, slot, _u8(a), a.shape[1], a.shape[0], a.strides[0], variant))
 
+    def upload_jpeg(self, slot, jpeg, variant=GRAY_CV4, crop=None):
+        """A file read by `jpeg.read_jpeg` -> gray in `slot`, exactly what `upload_bgr(slot, np.array(Image.open(f)),
+        variant, crop)` leaves there: inverse DCT, chroma upsampling, colour conversion, crop and gray run on the device
+        (icelk_upload_jpeg); only the blocks the crop needs are transformed."""
+        left, top, right, bottom = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
+        self._ck(self._lib.icelk_upload_jpeg(self._h, slot, C.byref(jpeg.info), jpeg.coef_ptr, variant, left, top, right,
+                                             bottom))
+
+    def jpeg_decode_rgb(self, jpeg):
+        """The decoded image of a file read by `jpeg.read_jpeg`: H x W x 3 (R G B) or H x W uint8, equal to Pillow's."""
+        i = jpeg.info
+        out = np.empty((i.height, i.width, 3) if i.ncomp == 3 else (i.height, i.width), np.uint8)
+        self._ck(self._lib.icelk_jpeg_decode_rgb(self._h, C.byref(i), jpeg.coef_ptr, _u8(out), out.strides[0]))
+        return out
+
     def set_gray_device(self, slot, dev_ptr, w, h, stride):
         self._ck(self._lib.icelk_set_gray_device(self._h, slot, C.c_void_p(dev_ptr), w, h, stride))
 

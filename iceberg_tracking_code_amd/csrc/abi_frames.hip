@@ -170,6 +170,85 @@ static int end_frame(Ctx* c, Slot& s)
     return ICELK_OK;
 }
 
+// ---- JPEG ingest: coefficients -> planes -> pixels (k_jpeg.hip) ----------------------------------------------------------
+template <typename T>
+static int grow(Ctx* c, T** p, size_t* cap, size_t want)
+{
+    if (*cap >= want) return ICELK_OK;
+    if (*p) HIPCHK(c, hipFree(*p));   // waits for everything that may still use the buffer
+    *p = nullptr;
+    *cap = 0;
+    if (int rc = dmalloc(c, p, want)) return rc;
+    *cap = want;
+    return ICELK_OK;
+}
+
+// Uploads the block rows the pixel box [left, W - right) x [top, H - bottom) needs, transforms the blocks it needs and
+// fills `out` (planes, chroma mode, box) for the output kernel.  The descriptor comes from the caller: nothing in it is
+// trusted beyond what jpeg_info_ok has checked against the image size.
+static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int left, int top, int right, int bottom,
+                       JpegOutArgs* out)
+{
+    if (!I || !coef) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
+    if (!jpeg_info_ok(*I)) FAIL(c, ICELK_EARG, "JPEG descriptor does not describe a supported file");
+    if (left < 0 || top < 0 || right < 0 || bottom < 0 || (long long)left + right >= I->width ||
+        (long long)top + bottom >= I->height)
+        FAIL(c, ICELK_EARG, "crop box leaves no image");
+    const int nc = I->ncomp;
+    const bool sub_x = nc == 3 && I->hmax == 2, sub_y = nc == 3 && I->vmax == 2;
+    // libjpeg filters only planes wider than 2 samples, narrower ones are replicated
+    const bool fancy = I->comp_w[1] > 2;
+    size_t plane_off[3], plane_bytes = 0;
+    for (int k = 0; k < nc; k++) {
+        plane_off[k] = plane_bytes;
+        plane_bytes += (size_t)I->blocks_x[k] * 8 * I->blocks_y[k] * 8;
+    }
+    if (int rc = grow(c, &c->jpeg.d_coef, &c->jpeg.coef_cap, (size_t)I->coef_count)) return rc;
+    if (int rc = grow(c, &c->jpeg.d_planes, &c->jpeg.planes_cap, plane_bytes)) return rc;
+    JpegIdctArgs A{};
+    const int x0 = left, x1 = I->width - right - 1, y0 = top, y1 = I->height - bottom - 1;   // first / last pixel kept
+    A.first[0] = 0;
+    for (int k = 0; k < 3; k++) {
+        if (k >= nc) {
+            A.first[k + 1] = A.first[k];
+            continue;
+        }
+        // samples of this component the box touches: chroma one more on every subsampled side (the filter's neighbour)
+        int sx0 = x0, sx1 = x1, sy0 = y0, sy1 = y1;
+        if (k > 0 && sub_x) sx0 = std::max(x0 / 2 - 1, 0), sx1 = std::min(x1 / 2 + 1, I->comp_w[k] - 1);
+        if (k > 0 && sub_y) sy0 = std::max(y0 / 2 - 1, 0), sy1 = std::min(y1 / 2 + 1, I->comp_h[k] - 1);
+        A.bx0[k] = sx0 / 8;
+        A.by0[k] = sy0 / 8;
+        A.nbx[k] = sx1 / 8 - A.bx0[k] + 1;
+        const int nby = sy1 / 8 - A.by0[k] + 1;
+        A.first[k + 1] = A.first[k] + A.nbx[k] * nby;
+        A.blocks_x[k] = I->blocks_x[k];
+        A.pitch[k] = I->blocks_x[k] * 8;
+        A.coef[k] = c->jpeg.d_coef + I->coef_offset[k];
+        A.plane[k] = c->jpeg.d_planes + plane_off[k];
+        memcpy(A.quant[k], I->quant[k], sizeof(A.quant[k]));
+        // whole block rows by0 .. by0 + nby - 1: contiguous in the layout
+        const size_t row = (size_t)I->blocks_x[k] * 64, from = I->coef_offset[k] + (size_t)A.by0[k] * row;
+        HIPCHK(c, hipMemcpyAsync(c->jpeg.d_coef + from, coef + from, row * nby * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+        out->plane[k] = A.plane[k];
+        out->pitch[k] = A.pitch[k];
+    }
+    {
+        ProfScope p(c, K_JPEG_IDCT);
+        launch_jpeg_idct(c->stream, A);
+    }
+    if (int rc = check_launch(c, "jpeg_idct")) return rc;
+    out->W = I->width;
+    out->cw = I->comp_w[nc - 1];
+    out->ch = I->comp_h[nc - 1];
+    out->mode = !sub_x ? 0 : (sub_y ? (fancy ? 2 : 4) : (fancy ? 1 : 3));
+    out->left = left;
+    out->top = top;
+    out->ow = I->width - left - right;
+    out->oh = I->height - top - bottom;
+    return ICELK_OK;
+}
+
 }  // namespace icelk
 
 using namespace icelk;
@@ -249,6 +328,63 @@ int icelk_upload_bgr(icelk_t* h, int slot, const uint8_t* host, int w, int h_, i
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return end_frame(c, s);
+}
+
+int icelk_upload_jpeg(icelk_t* h, int slot, const icelk_jpeg_info_t* info, const int16_t* coef, int gray_variant,
+                      int crop_left, int crop_top, int crop_right, int crop_bottom)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (gray_variant != ICELK_GRAY_CV3 && gray_variant != ICELK_GRAY_CV4) FAIL(c, ICELK_EARG, "bad gray variant");
+    if (info && info->ncomp != 3) FAIL(c, ICELK_EARG, "expected a 3-component JPEG file");
+    HIPCHK(c, hipSetDevice(c->device));
+    JpegOutArgs O{};
+    int rc = check_slot(c, slot, false);
+    if (!rc) rc = jpeg_planes(c, info, coef, crop_left, crop_top, crop_right, crop_bottom, &O);
+    if (rc) return rc;
+    rc = begin_frame(c, slot, O.ow, O.oh);
+    if (rc) return rc;
+    Slot& s = c->slots[slot];
+    O.dst = s.lv[0].ptr;
+    O.dst_pitch = s.lv[0].pitch;
+    {
+        ProfScope p(c, K_JPEG_OUT);
+        launch_jpeg_gray(c->stream, O, gray_variant);
+    }
+    rc = check_launch(c, "jpeg_out");
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller's coefficient buffer is free again
+    return end_frame(c, s);
+}
+
+int icelk_jpeg_decode_rgb(icelk_t* h, const icelk_jpeg_info_t* info, const int16_t* coef, uint8_t* out, int stride)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!out || !info) FAIL(c, ICELK_EARG, "null output image or descriptor");
+    HIPCHK(c, hipSetDevice(c->device));
+    JpegOutArgs O{};
+    int rc = jpeg_planes(c, info, coef, 0, 0, 0, 0, &O);
+    if (rc) return rc;
+    const size_t row = (size_t)O.ow * info->ncomp;
+    if (stride < 0 || (size_t)stride < row) FAIL(c, ICELK_EARG, "stride smaller than a row of the image");
+    if (info->ncomp == 1) {
+        HIPCHK(c, hipMemcpy2DAsync(out, stride, O.plane[0], O.pitch[0], row, O.oh, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        rc = grow(c, &c->jpeg.d_rgb, &c->jpeg.rgb_cap, row * O.oh);
+        if (rc) return rc;
+        O.dst = c->jpeg.d_rgb;
+        O.dst_pitch = (int)row;
+        {
+            ProfScope p(c, K_JPEG_OUT);
+            launch_jpeg_rgb(c->stream, O);
+        }
+        rc = check_launch(c, "jpeg_out");
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy2DAsync(out, stride, c->jpeg.d_rgb, row, row, O.oh, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ICELK_OK;
 }
 
 int icelk_set_gray_device(icelk_t* h, int slot, const void* dev, int w, int h_, int stride)

@@ -76,6 +76,13 @@ struct Ctx {
     uint8_t* d_bgr = nullptr;
     int bgr_pitch = 0;
     bool pyr_per_level = false;            // ICELK_PYR_PER_LEVEL=1: one pyrDown launch per level (A/B, second statement)
+    // JPEG ingest: coefficients, component planes and (icelk_jpeg_decode_rgb only) the decoded image; grown on demand,
+    // because the file may be larger than max_w x max_h (the crop is what has to fit)
+    struct Jpeg {
+        int16_t* d_coef = nullptr;
+        uint8_t *d_planes = nullptr, *d_rgb = nullptr;
+        size_t coef_cap = 0, planes_cap = 0, rgb_cap = 0;   // elements / bytes / bytes
+    } jpeg;
 
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
     float *d_p0 = nullptr, *d_p1 = nullptr, *d_p0r = nullptr, *d_err_f = nullptr, *d_err_b = nullptr, *d_dist = nullptr;
@@ -383,6 +390,8 @@ int wait_event(Ctx* c, hipStream_t s, hipEvent_t e);
 int wait_slot(Ctx* c, int slot);
 int ensure_pyramid(Ctx* c, int slot, int top_level);
 Pyramid pyramid_of(const Slot& s);
+// abi_jpeg.hip
+bool jpeg_info_ok(const icelk_jpeg_info_t& in);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

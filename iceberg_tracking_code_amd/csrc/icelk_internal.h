@@ -55,6 +55,8 @@ enum KernelId {
     K_PROJECT,
     K_SYNTH,
     K_LK_FB_PAIR,   // two segment pairs in one launch (icelk_seg_track_defer)
+    K_JPEG_IDCT,    // dequantise + inverse DCT (k_jpeg.hip)
+    K_JPEG_OUT,     // upsample + colour + crop + gray / RGB
     K_COUNT_
 };
 
@@ -91,6 +93,30 @@ void launch_pyrdown(hipStream_t s, const Level& src, const Level& dst);
 // lv[first+1 .. first+n] (n = 1..3) from lv[first] in ONE launch (k_pyramid.hip)
 void launch_pyramid_fused(hipStream_t s, const Level* lv, int first, int n, bool one_wave = false);
 void launch_synth(hipStream_t s, const Level& dst, int64_t ux, int64_t uy, uint32_t seed, const int* affine);
+
+// JPEG ingest (k_jpeg.hip).  By-value kernel arguments.
+struct JpegIdctArgs {
+    const int16_t* coef[3];   // device: a component's blocks, raster order over blocks_x[c] per row, 64 values each
+    uint8_t* plane[3];        // device: the component's samples, pitch[c] >= 8 * blocks_x[c] (a multiple of 8)
+    int pitch[3], blocks_x[3];
+    int bx0[3], by0[3], nbx[3];   // the rectangle of blocks to transform
+    int first[4];             // component c owns the launch's blocks first[c] .. first[c+1]-1
+    uint16_t quant[3][64];
+};
+struct JpegOutArgs {
+    const uint8_t* plane[3];
+    int pitch[3];
+    int W;                    // image width = true width of the luma plane
+    int cw, ch;               // true size of the chroma planes
+    int mode;                 // chroma upsampling: 0 none, 1 / 2 triangle filter 2x1 / 2x2, 3 / 4 replication 2x1 / 2x2
+    int left, top, ow, oh;    // output pixel (x, y) is image pixel (x + left, y + top)
+    uint8_t* dst;
+    int dst_pitch;
+    int k0, k1, k2, shift;    // gray weights (launch_jpeg_gray fills them in)
+};
+void launch_jpeg_idct(hipStream_t s, const JpegIdctArgs& A);
+void launch_jpeg_gray(hipStream_t s, JpegOutArgs A, int variant);
+void launch_jpeg_rgb(hipStream_t s, JpegOutArgs A);
 
 // LK.  p_in/p_out etc. are device pointers.  fb = fused forward+backward.
 struct LKBuffers {

@@ -1,0 +1,262 @@
+// k_jpeg.hip -- the device half of the JPEG ingest path for gfx950: quantised DCT coefficients -> pixels.
+//
+//   k_jpeg_idct   dequantise + 8x8 inverse DCT of the blocks a crop needs, into 8-bit component planes
+//   k_jpeg_out    chroma upsampling + YCbCr -> RGB + crop, then either gray into a slot's level 0 or interleaved RGB
+//
+// Arithmetic: libjpeg's default decoder restated from its published description (tests/jpeg_restatement.py is the
+// same in numpy, and is what Pillow's output is compared with): the "islow" inverse DCT -- the factorisation of
+// Loeffler, Ligtenberg and Moschytz in 13-bit fixed point, the column pass keeping 2 extra bits --, "fancy" upsampling
+// (a 3:1 triangle filter in each subsampled direction, edge samples repeated at the TRUE plane edges), and the 16-bit
+// fixed-point colour matrix.  All integer, so equality with the host library is bit for bit.
+//
+// The planes go through HBM between the two kernels (18 MB at 12 MP 4:2:0); each is one pass over its data.
+#include "icelk_internal.h"
+
+namespace icelk {
+
+// 8-point inverse DCT of x[0..7] in place, descaled by `shift` with rounding.  32-bit: an encoder's coefficients times
+// an 8-bit table stay below 2^18 in magnitude, the sums below 2^31.
+template <int shift>
+__device__ __forceinline__ void idct8(int (&x)[8])
+{
+    // even part
+    const int z = (x[2] + x[6]) * 4433;
+    const int e2 = z - x[6] * 15137;
+    const int e3 = z + x[2] * 6270;
+    const int e0 = (x[0] + x[4]) * 8192;
+    const int e1 = (x[0] - x[4]) * 8192;
+    const int a0 = e0 + e3, a3 = e0 - e3, a1 = e1 + e2, a2 = e1 - e2;
+    // odd part
+    const int z5 = (x[7] + x[3] + x[5] + x[1]) * 9633;
+    const int z3 = z5 - (x[7] + x[3]) * 16069;
+    const int z4 = z5 - (x[5] + x[1]) * 3196;
+    const int z1 = -(x[7] + x[1]) * 7373;
+    const int z2 = -(x[5] + x[3]) * 20995;
+    const int o0 = x[7] * 2446 + z1 + z3;
+    const int o1 = x[5] * 16819 + z2 + z4;
+    const int o2 = x[3] * 25172 + z2 + z3;
+    const int o3 = x[1] * 12299 + z1 + z4;
+    constexpr int half = 1 << (shift - 1);
+    x[0] = (a0 + o3 + half) >> shift;
+    x[7] = (a0 - o3 + half) >> shift;
+    x[1] = (a1 + o2 + half) >> shift;
+    x[6] = (a1 - o2 + half) >> shift;
+    x[2] = (a2 + o1 + half) >> shift;
+    x[5] = (a2 - o1 + half) >> shift;
+    x[3] = (a3 + o0 + half) >> shift;
+    x[4] = (a3 - o0 + half) >> shift;
+}
+
+__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// ------------------------------------------------------------------------------------------------
+// Inverse DCT.  8 lanes per block, 32 blocks per 256-thread workgroup.  Lane r of a block loads row r of the
+// coefficients (16 B: a block is 128 contiguous bytes, a wave reads 1 KiB), dequantises, and writes it to the block's
+// LDS tile; the same lane then owns COLUMN r for the column pass (which has to come first: its rounding is part of the
+// result), writes the column back, and owns row r again for the row pass and the 8-byte store into the plane.
+// The tile rows are padded to 9 dwords: 8 lanes x 4 blocks of a half wave then touch 32 different banks in both
+// directions.  The 8 lanes of a block sit in one wave, but the tile is handed over with workgroup barriers all the same.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_jpeg_idct(JpegIdctArgs A)
+{
+    __shared__ int tile[32][8][9];
+    __shared__ uint16_t quant[3][64];
+    if (threadIdx.x < 192) quant[threadIdx.x >> 6][threadIdx.x & 63] = A.quant[threadIdx.x >> 6][threadIdx.x & 63];
+    __syncthreads();
+    const int g = threadIdx.x >> 3, r = threadIdx.x & 7;
+    const int blk = blockIdx.x * 32 + g;
+    const bool live = blk < A.first[3];
+    int c = 0, bx = 0, by = 0;
+    if (live) {
+        c = blk >= A.first[2] ? 2 : (blk >= A.first[1] ? 1 : 0);
+        const int k = blk - A.first[c];
+        by = A.by0[c] + k / A.nbx[c];
+        bx = A.bx0[c] + k % A.nbx[c];
+        const int16_t* src = A.coef[c] + ((size_t)by * A.blocks_x[c] + bx) * 64 + r * 8;
+        const uint4 raw = *reinterpret_cast<const uint4*>(src);
+        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int k2 = 0; k2 < 4; k2++) {
+            tile[g][r][2 * k2] = (int)(int16_t)(w[k2] & 0xffffu) * (int)quant[c][r * 8 + 2 * k2];
+            tile[g][r][2 * k2 + 1] = ((int)w[k2] >> 16) * (int)quant[c][r * 8 + 2 * k2 + 1];
+        }
+    }
+    __syncthreads();
+    int x[8];
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) x[k] = tile[g][k][r];
+        idct8<11>(x);
+#pragma unroll
+        for (int k = 0; k < 8; k++) tile[g][k][r] = x[k];
+    }
+    __syncthreads();
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) x[k] = tile[g][r][k];
+        idct8<18>(x);
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            lo |= (uint32_t)clamp255(x[k] + 128) << (8 * k);
+            hi |= (uint32_t)clamp255(x[k + 4] + 128) << (8 * k);
+        }
+        uint8_t* dst = A.plane[c] + (size_t)(by * 8 + r) * A.pitch[c] + bx * 8;
+        *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+    }
+}
+
+void launch_jpeg_idct(hipStream_t s, const JpegIdctArgs& A)
+{
+    const int nblk = A.first[3];
+    if (nblk <= 0) return;
+    hipLaunchKernelGGL(k_jpeg_idct, dim3((nblk + 31) / 32), dim3(256), 0, s, A);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Upsampling + colour + crop (+ gray).  The chroma sample at image position (X, Y), from a plane of cw x ch samples:
+//   mode 0  no subsampling
+//   mode 1  2x1 "fancy":  (3 near + neighbour + 1) >> 2 at even X (neighbour on the left), + 2 at odd X (on the right)
+//   mode 2  2x2 "fancy":  column sums 3 near row + far row (above at even Y, below at odd Y), then
+//           (3 s[j] + s[j-1] + 8) >> 4 at even X, (3 s[j] + s[j+1] + 7) >> 4 at odd X
+//   mode 3 / 4  2x1 / 2x2 by plain replication: what libjpeg does for planes of 2 samples' width or less
+// Neighbours beyond the plane's edge are the edge sample.
+//
+// A lane makes 4 neighbouring output pixels.  They need 4 luma samples and, in every mode, at most 4 neighbouring
+// chroma samples per row: each group of 4 is ONE dword load at whatever byte address the crop puts it (gfx950 under HSA
+// takes unaligned vector loads).  Loaded byte by byte -- 36 loads per lane at 4:2:0 instead of 5 -- the kernel is bound
+// by the address unit: 53.8 against 26.8 us per 12 MP frame.  Groups that reach over an edge of the plane are loaded
+// byte by byte with the column clamped.
+// ------------------------------------------------------------------------------------------------
+typedef uint32_t u32_a1 __attribute__((aligned(1)));
+
+// v[k] = row[clamp(c + k, 0, n - 1)], k = 0..3
+__device__ __forceinline__ void load4(const uint8_t* __restrict__ row, int c, int n, int (&v)[4])
+{
+    if (c >= 0 && c + 3 < n) {
+        const uint32_t w = *reinterpret_cast<const u32_a1*>(row + c);
+        v[0] = w & 255;
+        v[1] = (w >> 8) & 255;
+        v[2] = (w >> 16) & 255;
+        v[3] = w >> 24;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = row[min(max(c + k, 0), n - 1)];
+    }
+}
+
+// the chroma samples of image pixels X0 .. X0+3 in row Y
+template <int mode>
+__device__ __forceinline__ void chroma4(const uint8_t* __restrict__ p, int pitch, int cw, int ch, int X0, int Y, int (&out)[4])
+{
+    if (mode == 0) {
+        load4(p + (size_t)Y * pitch, X0, cw, out);
+        return;
+    }
+    const int odd = X0 & 1;
+    if (mode == 3 || mode == 4) {
+        int t[4];
+        load4(p + (size_t)(mode == 4 ? Y >> 1 : Y) * pitch, X0 >> 1, cw, t);
+#pragma unroll
+        for (int i = 0; i < 4; i++) out[i] = odd ? t[(i + 1) >> 1] : t[i >> 1];
+        return;
+    }
+    // the window of 4 samples from one left of pixel X0's own: every pixel's sample and neighbour lie inside
+    const int c0 = (X0 >> 1) - 1;
+    int t[4];
+    if (mode == 1) {
+        load4(p + (size_t)Y * pitch, c0, cw, t);
+    } else {
+        const int i = Y >> 1;
+        const int fi = (Y & 1) ? min(i + 1, ch - 1) : max(i - 1, 0);
+        int f[4];
+        load4(p + (size_t)i * pitch, c0, cw, t);
+        load4(p + (size_t)fi * pitch, c0, cw, f);
+#pragma unroll
+        for (int k = 0; k < 4; k++) t[k] = 3 * t[k] + f[k];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        // window index of the pixel's own sample and of its neighbour, for even and for odd X0
+        const int je = 1 + (i >> 1), jo = 1 + ((i + 1) >> 1);
+        const int ne = (i & 1) ? je + 1 : je - 1, no = ((i + 1) & 1) ? jo + 1 : jo - 1;
+        const int own = odd ? t[jo] : t[je], nb = odd ? t[no] : t[ne];
+        const int xodd = (i + odd) & 1;
+        out[i] = mode == 1 ? (3 * own + nb + 1 + xodd) >> 2 : (3 * own + nb + 8 - xodd) >> 4;
+    }
+}
+
+// gray: one dword stored per lane (256 B per wave and row); rgb: 12 bytes
+template <int mode, bool rgb>
+__global__ __launch_bounds__(256) void k_jpeg_out(JpegOutArgs A)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (4 * q >= A.ow || y >= A.oh) return;
+    const int X0 = 4 * q + A.left, Y = y + A.top;
+    const int nx = min(4, A.ow - 4 * q);
+    int lum[4], cb[4], cr[4];
+    load4(A.plane[0] + (size_t)Y * A.pitch[0], X0, A.W, lum);
+    chroma4<mode>(A.plane[1], A.pitch[1], A.cw, A.ch, X0, Y, cb);
+    chroma4<mode>(A.plane[2], A.pitch[2], A.cw, A.ch, X0, Y, cr);
+    const int half = 1 << (A.shift - 1);
+    uint32_t px[4];   // gray: px[0] holds the 4 pixels; rgb: R | G << 8 | B << 16 each
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int u = cb[i] - 128, v = cr[i] - 128;
+        const int R = clamp255(lum[i] + ((91881 * v + 32768) >> 16));
+        const int G = clamp255(lum[i] + ((-22554 * u - 46802 * v + 32768) >> 16));
+        const int B = clamp255(lum[i] + ((116130 * u + 32768) >> 16));
+        // gray: channel 0 (R) takes the "B" weight, as k_bgr2gray gives it to the first byte of PIL's RGB pixels
+        if (rgb) px[i] = (uint32_t)R | (uint32_t)G << 8 | (uint32_t)B << 16;
+        else px[i] = (uint32_t)((R * A.k0 + G * A.k1 + B * A.k2 + half) >> A.shift);
+    }
+    uint8_t* d = A.dst + (size_t)y * A.dst_pitch;
+    if (rgb) {
+        if (nx == 4) {
+            u32_a1* o = reinterpret_cast<u32_a1*>(d + 12 * q);   // a row of 3 * width bytes starts anywhere
+            o[0] = px[0] | px[1] << 24;
+            o[1] = px[1] >> 8 | px[2] << 16;
+            o[2] = px[2] >> 16 | px[3] << 8;
+        } else {
+            for (int i = 0; i < nx; i++) {
+                d[12 * q + 3 * i] = (uint8_t)px[i];
+                d[12 * q + 3 * i + 1] = (uint8_t)(px[i] >> 8);
+                d[12 * q + 3 * i + 2] = (uint8_t)(px[i] >> 16);
+            }
+        }
+    } else {
+        if (nx == 4) *reinterpret_cast<uint32_t*>(d + 4 * q) = px[0] | px[1] << 8 | px[2] << 16 | px[3] << 24;   // level rows are 64-B aligned
+        else
+            for (int i = 0; i < nx; i++) d[4 * q + i] = (uint8_t)px[i];
+    }
+}
+
+template <bool rgb>
+static void launch_out(hipStream_t s, const JpegOutArgs& A)
+{
+    dim3 block(256);
+    dim3 grid(((A.ow + 3) / 4 + 255) / 256, A.oh);
+    switch (A.mode) {
+    case 0: hipLaunchKernelGGL((k_jpeg_out<0, rgb>), grid, block, 0, s, A); break;
+    case 1: hipLaunchKernelGGL((k_jpeg_out<1, rgb>), grid, block, 0, s, A); break;
+    case 2: hipLaunchKernelGGL((k_jpeg_out<2, rgb>), grid, block, 0, s, A); break;
+    case 3: hipLaunchKernelGGL((k_jpeg_out<3, rgb>), grid, block, 0, s, A); break;
+    default: hipLaunchKernelGGL((k_jpeg_out<4, rgb>), grid, block, 0, s, A); break;
+    }
+}
+
+void launch_jpeg_gray(hipStream_t s, JpegOutArgs A, int variant)
+{
+    if (variant == ICELK_GRAY_CV4) { A.k0 = 3735; A.k1 = 19235; A.k2 = 9798; A.shift = 15; }
+    else { A.k0 = 1868; A.k1 = 9617; A.k2 = 4899; A.shift = 14; }
+    launch_out<false>(s, A);
+}
+
+void launch_jpeg_rgb(hipStream_t s, JpegOutArgs A)
+{
+    A.shift = 1;
+    launch_out<true>(s, A);
+}
+
+}  // namespace icelk

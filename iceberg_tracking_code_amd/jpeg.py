@@ -1,0 +1,103 @@
+"""JPEG ingest with the pixel work on the device.
+
+The host reads a baseline JPEG's headers and Huffman-decodes its scan into quantised DCT coefficients (`read_jpeg`:
+csrc/abi_jpeg.hip, no GPU needed, the GIL is released, so a thread pool decodes files side by side); the device
+dequantises, inverse-transforms, upsamples chroma and converts colour (csrc/k_jpeg.hip) -- into a tracker slot as a
+cropped gray frame (`Context.upload_jpeg`, `SegmentTracker.push_jpeg`) or back to the host as pixels (`decode_jpeg`).
+Pixels equal Pillow's (libjpeg's default decoder) bit for bit.
+
+Taken: baseline (SOF0), 8 bit, Huffman coded, one interleaved scan, gray or YCbCr with 4:4:4 / 4:2:2 / 4:2:0 sampling,
+restart markers, width >= 3.  Every other valid file raises `UnsupportedJpeg` -- the caller decodes it another way.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+class UnsupportedJpeg(ValueError):
+    """A valid JPEG file of a kind the device decoder does not take (progressive, arithmetic coding, 12 bit, CMYK, other
+    sampling factors, several scans, ...)."""
+
+
+class JpegCoefficients:
+    """What `read_jpeg` returns: `info` (the icelk_jpeg_info_t: size, sampling, quantisation tables, coefficient layout)
+    and `coef`, the int16 coefficients in that layout."""
+
+    def __init__(self, info, coef):
+        self.info, self.coef = info, coef
+
+    @property
+    def coef_ptr(self):
+        return C.c_void_p(self.coef.ctypes.data)
+
+    @property
+    def width(self):
+        return self.info.width
+
+    @property
+    def height(self):
+        return self.info.height
+
+    @property
+    def ncomp(self):
+        return self.info.ncomp
+
+    def blocks(self, c):
+        """component c as (blocks_y, blocks_x, 8, 8) int16, natural order, not dequantised (a view)"""
+        i = self.info
+        n = i.blocks_x[c] * i.blocks_y[c] * 64
+        return self.coef[i.coef_offset[c]:i.coef_offset[c] + n].reshape(i.blocks_y[c], i.blocks_x[c], 8, 8)
+
+    def quant(self, c):
+        return np.array(self.info.quant[c], np.uint16).reshape(8, 8)
+
+
+def _check(rc, what):
+    if rc == _lib.OK:
+        return
+    if rc == _lib.EUNSUP:
+        raise UnsupportedJpeg("%s: a JPEG file of a kind the device decoder does not take" % what)
+    if rc == _lib.ENOMEM:
+        raise MemoryError(what)
+    raise ValueError("%s: not a JPEG file, or a damaged one (icelk error %d)" % (what, rc))
+
+
+def describe_jpeg(data):
+    """The icelk_jpeg_info_t of a file given as bytes."""
+    data = bytes(data)
+    info = _lib.JpegInfo()
+    _check(_lib.load().icelk_jpeg_describe(data, len(data), C.byref(info)), "icelk_jpeg_describe")
+    return info
+
+
+def read_jpeg(path_or_bytes, out=None):
+    """The host stage: a path or the file's bytes -> JpegCoefficients.  `out`: an int16 array to decode into (e.g. a view
+    of pinned memory from `Context.host_alloc`); it is used when it is large enough, else a new array is made."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, "rb") as f:
+            data = f.read()
+    lib = _lib.load()
+    info = _lib.JpegInfo()
+    _check(lib.icelk_jpeg_describe(data, len(data), C.byref(info)), "icelk_jpeg_describe")
+    n = int(info.coef_count)
+    if out is not None and out.dtype == np.int16 and out.ndim == 1 and out.size >= n and out.flags.c_contiguous:
+        coef = out[:n]
+    else:
+        coef = np.empty(n, np.int16)
+    _check(lib.icelk_jpeg_read_coefficients(data, len(data), C.c_void_p(coef.ctypes.data), n), "icelk_jpeg_read_coefficients")
+    return JpegCoefficients(info, coef)
+
+
+def decode_jpeg(data, ctx=None):
+    """A path, the file's bytes or a JpegCoefficients -> H x W x 3 (R G B) or H x W uint8 array, the pixels
+    np.array(PIL.Image.open(...)) gives, computed on the device.  `ctx`: a Context to run on (default: the one of the
+    cv2-shaped functions, api.default_context)."""
+    j = data if isinstance(data, JpegCoefficients) else read_jpeg(data)
+    if ctx is None:
+        from .api import default_context
+        ctx = default_context(j.width, j.height)
+    return ctx.jpeg_decode_rgb(j)

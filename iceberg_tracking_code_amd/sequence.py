@@ -6,12 +6,15 @@ camtools.py:64-104), list the cropped copies, build the fjord mask (s1:285-294),
 the list: decode (s1:310), cvtColor (s1:311), track / filter / extend (s1:313-359), at every `track_len`-th frame
 check the time gaps and save the segment (s1:362-395), detect new corners (s1:437-448).
 
-Here: JPEG decode stays on the host (PIL, a small thread pool decoding ahead -- it is two orders of magnitude slower
-than the GPU step and is the real end-to-end bound); the crop box is cut during the upload of the decoded frame
-(`Context.upload_bgr(crop=...)`), so the reference's lossy re-save of the crop has no counterpart and pixel values
-are those of the original photo; gray conversion, detection, tracking, filtering and the track table are the
-device-resident loop of `SegmentTracker`; the mask is rasterised on the device from the polygon
-(`icelk_set_mask_polygon`) or uploaded.  Output files carry the reference's names and arrays.
+Here: a small thread pool decodes ahead on the host -- the real end-to-end bound, far slower than the GPU step.  With
+`decoder="pil"` (default) it decodes whole photos with PIL and the crop box is cut during the upload of the decoded
+frame (`Context.upload_bgr(crop=...)`); with `decoder="device"` the pool only Huffman-decodes (`jpeg.read_jpeg`) and
+the device does the inverse DCT, chroma upsampling, colour conversion, crop and gray (`Context.upload_jpeg`), giving
+the same pixels; files the device decoder does not take go through PIL one by one.  Either way the reference's lossy
+re-save of the crop has no counterpart and pixel values are those of the original photo; gray conversion, detection,
+tracking, filtering and the track table are the device-resident loop of `SegmentTracker`; the mask is rasterised on
+the device from the polygon (`icelk_set_mask_polygon`) or uploaded.  Output files carry the reference's names and
+arrays.
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -26,9 +29,35 @@ def _decode(path):
     return np.array(Image.open(path))                     # s1:310 (RGB order; cvtColor is asked for BGR2GRAY)
 
 
+def _read(path):
+    """decoder="device": the host stage only.  A file the device decoder does not take (progressive, CMYK, gray, ...) or
+    cannot parse is decoded by PIL instead -- that file only; PIL then also is the one to complain about a broken file."""
+    from .jpeg import read_jpeg
+    try:
+        j = read_jpeg(path)
+        if j.ncomp == 3:
+            return j
+    except ValueError:                                    # UnsupportedJpeg is one
+        pass
+    return _decode(path)
+
+
+def _image_size(path, decoder):
+    if decoder == "device":
+        from .jpeg import describe_jpeg
+        try:
+            with open(path, "rb") as f:
+                info = describe_jpeg(f.read())
+            return info.width, info.height
+        except ValueError:
+            pass
+    first = _decode(path)
+    return first.shape[1], first.shape[0]
+
+
 def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startlist=(0,), crop=None, mask=None,
                          mask_polygon=None, feature_params=None, lk_params=None, decode_threads=4, decode_ahead=6,
-                         gray_variant=4, device=0, on_segment=None, save=True):
+                         gray_variant=4, device=0, on_segment=None, save=True, decoder="pil"):
     """Track one day's photos.  Returns [(npz path, tracks (n, T+1, 2) f32, trackquality (n, T) f32)] of the
     segments that pass the time-gap rule, in order.
 
@@ -38,18 +67,22 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
     mask_polygon   (maskpoly, cropleft, croptop): rasterised on the device as s1:285-291 / camtools.py:184-211 do
     startlist      offsets into the list, each walked separately (s1:304)
     on_segment     optional callback(npz path, tracks, trackquality), e.g. a projection step
+    decoder        "pil": photos are decoded on the host; "device": only their Huffman decoding is (see above) -- same
+                   outputs, supported files and the per-file fallback are listed in INTEGRATION.md
     """
+    if decoder not in ("pil", "device"):
+        raise ValueError('decoder must be "pil" or "device"')
     imagelist = [str(p) for p in imagelist]
     out = []
     if len(imagelist) <= track_len:                       # s1:267
         return out
     fp = dict(REF_FEATURE_PARAMS if feature_params is None else feature_params)
     lk = dict(REF_LK_PARAMS if lk_params is None else lk_params)
-    first = _decode(imagelist[0])
-    h, w = first.shape[0], first.shape[1]
+    w, h = _image_size(imagelist[0], decoder)
     if crop is not None:
         left, top, right, bottom = (int(v) for v in crop)
         w, h = w - left - right, h - top - bottom
+    load = _read if decoder == "device" else _decode
     trk = None
     try:
         with ThreadPoolExecutor(max_workers=max(1, int(decode_threads))) as pool:
@@ -61,12 +94,15 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                 # into the first step of the next one; nothing is saved from that pair, s1:362-363)
                 trk = SegmentTracker(w, h, track_len, feature_params=fp, lk_params=lk, mask=mask,
                                      mask_polygon=mask_polygon, device=device)
-                pending = [pool.submit(_decode, p) for p in names[:decode_ahead]]
+                pending = [pool.submit(load, p) for p in names[:decode_ahead]]
                 for counter in range(len(names)):
                     frame = pending.pop(0).result()
                     if counter + decode_ahead < len(names):
-                        pending.append(pool.submit(_decode, names[counter + decode_ahead]))
-                    seg = trk.push_bgr(frame, variant=gray_variant, crop=crop)
+                        pending.append(pool.submit(load, names[counter + decode_ahead]))
+                    if isinstance(frame, np.ndarray):
+                        seg = trk.push_bgr(frame, variant=gray_variant, crop=crop)
+                    else:
+                        seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop)
                     if seg is None:
                         continue
                     seg_first, tracks, quality = seg

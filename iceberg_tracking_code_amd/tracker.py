@@ -119,6 +119,13 @@ class SegmentTracker:
         self.ctx.upload_bgr(s, frame, variant, crop)
         return self._step(s, wait)
 
+    def push_jpeg(self, jpeg, wait=True, variant=4, crop=None):
+        """A frame as `jpeg.read_jpeg` returns it (quantised DCT coefficients): decoded, cropped and turned to gray on
+        the device; the step is the one `push_bgr` makes with the file's decoded pixels."""
+        s = self._next_slot()
+        self.ctx.upload_jpeg(s, jpeg, variant, crop)
+        return self._step(s, wait)
+
     def push_device(self, dev_ptr, stride, wait=True):
         s = self._next_slot()
         self.ctx.set_gray_device(s, dev_ptr, self.w, self.h, stride)

@@ -41,6 +41,7 @@ typedef struct icelk_ctx icelk_t;
 #define ICELK_EHIP (-3)    /* HIP runtime error                  -> Python RuntimeError */
 #define ICELK_ECAP (-4)    /* exceeds the capacity given at icelk_create                */
 #define ICELK_ESTATE (-5)  /* slot empty / pyramid missing / segment not started        */
+#define ICELK_EUNSUP (-6)  /* a valid JPEG file of a kind the device decoder does not take */
 
 /* cv2.TERM_CRITERIA_COUNT / cv2.TERM_CRITERIA_EPS (criteria tuple at s1:248) */
 #define ICELK_CRIT_COUNT 1
@@ -384,6 +385,46 @@ int icelk_calib_residuals(icelk_t* h, const double* cand, int P, double* out_dis
 /* The same without the (P, M) output: out_meansq[p] = np.mean(residuals[p] ** 2), the squares added in numpy's
  * pairwise order.  Also ICELK_ECAP for a scene of more than 4096 shoreline points. */
 int icelk_calib_cost(icelk_t* h, const double* cand, int P, double* out_meansq, double* device_ms);
+
+/* ---- JPEG ingest: the host reads the entropy-coded stream, the device does the rest ------------- */
+/* What a baseline JPEG file says about itself, and how its quantised DCT coefficients are laid out in memory.
+ * Coefficients are int16, component after component (coef_offset[c], in int16 units); inside a component the 8x8 blocks
+ * stand in raster order over the MCU-padded block grid (blocks_x[c] x blocks_y[c]), 64 values per block in natural
+ * (row-major, de-zigzagged) order, not yet multiplied by the quantisation table.  quant[c] is the table of component c
+ * in the same natural order.  comp_w / comp_h are the true plane sizes ceil(width * h / hmax), ceil(height * v / vmax):
+ * chroma upsampling replicates the samples at THOSE edges.
+ * Taken: SOF0, 8 bit, Huffman coded, one interleaved scan; 1 component, or 3 (YCbCr) with luma sampling 1x1, 2x1 or 2x2
+ * and chroma 1x1; 8-bit DQT; DRI / RSTn; APPn / COM skipped; width >= 3.  Everything else that is a valid file is
+ * ICELK_EUNSUP (progressive, arithmetic, 12 bit, 4 components, other sampling factors, several scans, DNL, an Adobe
+ * marker with transform != 1, component ids R G B); a stream that breaks off or contradicts itself is ICELK_EARG. */
+typedef struct icelk_jpeg_info {
+    int32_t width, height, ncomp;
+    int32_t hmax, vmax;          /* sampling factors of component 0; the others are 1 x 1 */
+    int32_t mcus_x, mcus_y;
+    int32_t restart_interval;    /* MCUs between RSTn markers, 0: none */
+    int32_t comp_w[3], comp_h[3];
+    int32_t blocks_x[3], blocks_y[3];
+    uint64_t coef_offset[3];
+    uint64_t coef_count;         /* int16 values in all: what icelk_jpeg_read_coefficients writes */
+    uint16_t quant[3][64];
+} icelk_jpeg_info_t;
+/* Host only, no handle, re-entrant (callable from several threads at once, without a GPU): the headers of the file
+ * in data[0 .. len). */
+int icelk_jpeg_describe(const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info);
+/* Host only, no handle, re-entrant: Huffman-decodes the file's scan into coef[0 .. info.coef_count); capacity = int16
+ * values coef has room for (ICELK_ECAP when too few).  No byte outside data[0 .. len) is read; a truncated or malformed
+ * stream gives ICELK_EARG.  coef may be pinned memory of icelk_host_alloc. */
+int icelk_jpeg_read_coefficients(const uint8_t* data, uint64_t len, int16_t* coef, uint64_t capacity);
+/* Coefficients -> gray frame in `slot`, exactly what icelk_upload_bgr leaves there when given the file's decoded RGB
+ * pixels (libjpeg's integer inverse DCT, "fancy" chroma upsampling and YCbCr -> RGB, bit for bit) with crop_* pixels cut
+ * off at the four sides: dequantisation, inverse DCT, upsampling, colour conversion, crop and gray run on the device, RGB
+ * is never stored.  The cropped size must fit max_w x max_h of icelk_create, the file itself need not.  Only the blocks
+ * the crop needs are transformed.  3-component files only (as icelk_upload_bgr takes 3-channel images only). */
+int icelk_upload_jpeg(icelk_t* h, int slot, const icelk_jpeg_info_t* info, const int16_t* coef, int gray_variant,
+                      int crop_left, int crop_top, int crop_right, int crop_bottom);
+/* Coefficients -> the decoded image on the host: interleaved R G B (3 * width bytes per row) for 3 components, the
+ * single plane (width bytes per row) for 1; stride in bytes. */
+int icelk_jpeg_decode_rgb(icelk_t* h, const icelk_jpeg_info_t* info, const int16_t* coef, uint8_t* out, int stride);
 
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the

@@ -1,0 +1,170 @@
+#!/usr/bin/env python3
+"""What the device JPEG ingest path costs and gains, on 4000x3000 4:2:0 photos of the procedural texture.
+
+    python tools/jpeg_ingest.py host   [--out profiles/jpeg_ingest_host.txt]      any CPU, no GPU needed
+    python tools/jpeg_ingest.py device [--out profiles/jpeg_ingest_device.txt]    MI355X: HIP-event times of the two kernels
+    python tools/jpeg_ingest.py e2e [--frames 24] [--threads 16] [--out ...]      MI355X: track_image_sequence, both decoders
+
+host    one thread, best of 5: `read_jpeg` (Huffman decoding into coefficients) against `np.array(Image.open(...))` (what
+        the "pil" decoder does per photo), and Pillow's own 1/8-scale draft decode -- entropy decoding plus a DC-only
+        transform, the yardstick for a tuned entropy decoder -- at quality 75 and 95.
+device  `Context.upload_jpeg` with profiling on: average HIP-event time of k_jpeg_idct and k_jpeg_out against the bytes
+        each has to move, and the host-clock time of the whole call (upload of the coefficients included).
+e2e     photos per second of the folder driver with decoder="pil" and decoder="device", same folder, same threads,
+        the two alternating.
+"""
+import argparse
+import datetime as dt
+import io
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from PIL import Image  # noqa: E402
+
+W, H = 4000, 3000
+
+
+def photo(k=0):
+    """the procedural texture of synth.py as a colour photo (the three channels are shifted copies)"""
+    from iceberg_tracking_code_amd import synth
+    g = synth.frame(W, H, 300 * k, -200 * k)
+    return np.stack([g, np.roll(g, 3, 1), np.roll(g, 2, 0)], 2)
+
+
+def encode(img, quality):
+    b = io.BytesIO()
+    Image.fromarray(img).save(b, "JPEG", quality=quality, subsampling=2)
+    return b.getvalue()
+
+
+def best_ms(f, n=5):
+    best = None
+    for _ in range(n):
+        t = time.perf_counter()
+        f()
+        el = time.perf_counter() - t
+        best = el if best is None else min(best, el)
+    return 1e3 * best
+
+
+def host(out):
+    from iceberg_tracking_code_amd import read_jpeg
+    img = photo()
+    print("host stage, one thread, best of 5, %dx%d 4:2:0, procedural texture" % (W, H), file=out)
+    print("quality  file MB  PIL decode ms  read_jpeg ms  PIL/read_jpeg  draft(1/8) ms  read_jpeg/draft", file=out)
+    for q in (75, 95):
+        data = encode(img, q)
+
+        def draft():
+            im = Image.open(io.BytesIO(data))
+            im.draft("RGB", (W // 8, H // 8))
+            im.load()
+        pil = best_ms(lambda: np.array(Image.open(io.BytesIO(data))))
+        rd = best_ms(lambda: read_jpeg(data))
+        dr = best_ms(draft)
+        print("%7d  %7.2f  %13.1f  %12.1f  %13.2f  %13.1f  %15.2f" % (q, len(data) / 1e6, pil, rd, pil / rd, dr, rd / dr), file=out)
+
+
+def device(out):
+    from iceberg_tracking_code_amd import Context, read_jpeg
+    j = read_jpeg(encode(photo(), 90))
+    i = j.info
+    coef_b = 2 * int(i.coef_count)
+    plane_b = sum(i.blocks_x[c] * i.blocks_y[c] * 64 for c in range(3))
+    gray_b = W * H
+    ctx = Context(W, H, n_slots=2, max_pts=64)
+    try:
+        for _ in range(3):
+            ctx.upload_jpeg(0, j, 4)
+        ctx.prof_reset()
+        ctx.prof_enable(True)
+        n = 20
+        t = time.perf_counter()
+        for _ in range(n):
+            ctx.upload_jpeg(0, j, 4)
+        call_ms = 1e3 * (time.perf_counter() - t) / n
+        ctx.prof_enable(False)
+        tab = ctx.prof_table()
+    finally:
+        ctx.close()
+    idct, outk = tab["jpeg_idct"]["avg_us"], tab["jpeg_out"]["avg_us"]
+    print("device stage, %dx%d 4:2:0, %d uploads, HIP events around each kernel" % (W, H, n), file=out)
+    print("k_jpeg_idct  %8.1f us  reads %.1f MB of coefficients, writes %.1f MB of planes: %.2f TB/s" %
+          (idct, coef_b / 1e6, plane_b / 1e6, (coef_b + plane_b) / idct / 1e6), file=out)
+    print("k_jpeg_out   %8.1f us  reads %.1f MB of planes, writes %.1f MB of gray: %.2f TB/s" %
+          (outk, plane_b / 1e6, gray_b / 1e6, (plane_b + gray_b) / outk / 1e6), file=out)
+    need = (coef_b + gray_b) / 8e12 * 1e6
+    trip = 2 * plane_b / 8e12 * 1e6
+    print("algorithmic bytes (coefficients in + gray out, %.1f MB) at 8 TB/s: %.1f us; the planes' round trip through HBM "
+          "(%.1f MB) another %.1f us" % ((coef_b + gray_b) / 1e6, need, 2 * plane_b / 1e6, trip), file=out)
+    print("both kernels %.1f us: %.1f %% of the algorithmic bound, %.1f %% of the bound with the round trip" %
+          (idct + outk, 100 * need / (idct + outk), 100 * (need + trip) / (idct + outk)), file=out)
+    print("whole upload_jpeg call by the host clock (pageable coefficients across PCIe, both kernels, synchronise): %.2f ms"
+          % call_ms, file=out)
+
+
+def e2e(out, n, threads):
+    from iceberg_tracking_code_amd import track_image_sequence
+    tmp = tempfile.mkdtemp(prefix="icelk_jpeg_")
+    t0 = dt.datetime(2019, 7, 24, 10, 0, 0)
+    names = []
+    for k in range(n):
+        p = os.path.join(tmp, (t0 + dt.timedelta(seconds=60 * k)).strftime("%Y%m%d-%H%M%S") + ".jpg")
+        with open(p, "wb") as f:
+            f.write(encode(photo(k), 90))
+        names.append(p)
+    size = sum(os.path.getsize(p) for p in names) / n / 1e6
+    fp = dict(maxCorners=10000, qualityLevel=0.007, minDistance=10, blockSize=10)
+    lk = dict(winSize=(21, 21), maxLevel=3, criteria=(3, 30, 0.01))
+    print("folder driver, %d photos of %dx%d 4:2:0 quality 90 (%.1f MB each), decode_threads %d, %d usable cores" %
+          (n, W, H, size, threads, len(os.sched_getaffinity(0))), file=out)
+    res = {"pil": [], "device": []}
+    ref = None
+    for rep in range(3):
+        for dec in ("pil", "device"):
+            t = time.perf_counter()
+            got = track_image_sequence(names, tmp, 2, 60, feature_params=fp, lk_params=lk, decode_threads=threads,
+                                       decode_ahead=max(6, 2 * threads), save=False, decoder=dec)
+            res[dec].append(n / (time.perf_counter() - t))
+            if ref is None:
+                ref = got
+            same = len(got) == len(ref) and all(np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) for a, b in zip(got, ref))
+            if not same:
+                raise SystemExit("decoder %s: tracks differ from the first run" % dec)
+    for dec in ("pil", "device"):
+        print('decoder="%s": %s photos/s (runs in order)' %
+              (dec, ", ".join("%.1f" % v for v in res[dec])), file=out)
+    print("ratio of the best runs: %.2f; %d segments, tracks equal in every run" %
+          (max(res["device"]) / max(res["pil"]), len(ref)), file=out)
+    for p in names:
+        os.remove(p)
+    os.rmdir(tmp)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", choices=("host", "device", "e2e"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--frames", type=int, default=24)
+    ap.add_argument("--threads", type=int, default=16)
+    a = ap.parse_args()
+    path = a.out or os.path.join(ROOT, "profiles", "jpeg_ingest_%s.txt" % a.mode)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as out:
+        if a.mode == "host":
+            host(out)
+        elif a.mode == "device":
+            device(out)
+        else:
+            e2e(out, a.frames, min(a.threads, 16))
+    sys.stdout.write(open(path).read())
+
+
+if __name__ == "__main__":
+    main()
