@@ -32,6 +32,24 @@ class JpegInfo(C.Structure):
 
 jpeg_info_p = C.POINTER(JpegInfo)
 
+
+class JpegScan(C.Structure):
+    """icelk_jpeg_scan_t"""
+    _fields_ = [("segments", C.c_uint32), ("blocks_per_mcu", C.c_uint32), ("blocks_per_segment", C.c_uint32),
+                ("total_blocks", C.c_uint32), ("component", C.c_uint8 * 8), ("dc_table", C.c_uint8 * 8), ("ac_table", C.c_uint8 * 8)]
+
+
+class JpegHuffStats(C.Structure):
+    """icelk_jpeg_huff_stats_t"""
+    _fields_ = [("segments", C.c_uint32), ("subsequences", C.c_uint32), ("rounds", C.c_uint32), ("max_hops", C.c_uint32),
+                ("lanes_in_step", C.c_uint32), ("spanning_blocks", C.c_uint32), ("fallback", C.c_uint32), ("reserved", C.c_uint32),
+                ("total_hops", C.c_uint64)]
+
+
+JPEG_TABLE_BYTES = 11328
+JPEG_FALLBACK_NONE, JPEG_FALLBACK_BOUND, JPEG_FALLBACK_STREAM, JPEG_FALLBACK_SIZE = 0, 1, 2, 3
+jpeg_stats_p = C.POINTER(JpegHuffStats)
+
 # name -> (restype, argtypes); the single source of truth for the symbol-export test as well
 SIGNATURES = {
     "icelk_version": (C.c_int, []),
@@ -48,6 +66,13 @@ SIGNATURES = {
     "icelk_jpeg_read_coefficients": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64]),
     "icelk_upload_jpeg": (C.c_int, [handle_p, C.c_int, jpeg_info_p, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_jpeg_decode_rgb": (C.c_int, [handle_p, jpeg_info_p, vp, u8p, C.c_int]),
+    "icelk_jpeg_index": (C.c_int, [vp, C.c_uint64, jpeg_info_p, C.POINTER(JpegScan), vp, vp, C.c_uint64, vp]),
+    "icelk_jpeg_read_coefficients_lanes": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, jpeg_stats_p]),
+    "icelk_jpeg_huff_config": (C.c_int, [handle_p, C.c_int, C.c_int, C.c_int]),
+    "icelk_jpeg_huff_stats": (C.c_int, [handle_p, jpeg_stats_p]),
+    "icelk_upload_jpeg_file": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_jpeg_decode_rgb_file": (C.c_int, [handle_p, vp, C.c_uint64, u8p, C.c_int]),
+    "icelk_jpeg_device_coefficients": (C.c_int, [handle_p, vp, C.c_uint64, vp, C.c_uint64]),
     "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

@@ -134,6 +134,50 @@ class Context:
         self._ck(self._lib.icelk_jpeg_decode_rgb(self._h, C.byref(i), jpeg.coef_ptr, _u8(out), out.strides[0]))
         return out
 
+    # -- JPEG files with the Huffman decoding on the device too (csrc/k_jpeg_huff.hip) ---------------
+    def _ck_jpeg(self, rc):
+        if rc == _lib.EUNSUP:
+            from .jpeg import UnsupportedJpeg
+            raise UnsupportedJpeg("a JPEG file of a kind the device decoder does not take")
+        self._ck(rc)
+
+    def upload_jpeg_file(self, slot, data, variant=GRAY_CV4, crop=None):
+        """The bytes of a JPEG file -> gray in `slot`, as `upload_jpeg(slot, read_jpeg(data), variant, crop)` leaves it:
+        the scan is Huffman-decoded on the device as well (icelk_upload_jpeg_file), the coefficients never visit the
+        host.  The same files are taken as by `read_jpeg`; others raise `UnsupportedJpeg`."""
+        data = bytes(data)
+        left, top, right, bottom = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
+        self._ck_jpeg(self._lib.icelk_upload_jpeg_file(self._h, slot, data, len(data), variant, left, top, right, bottom))
+
+    def jpeg_decode_rgb_file(self, data):
+        """The decoded image of a JPEG file given as bytes, Huffman decoding included on the device."""
+        from .jpeg import describe_jpeg
+        data = bytes(data)
+        i = describe_jpeg(data)
+        out = np.empty((i.height, i.width, 3) if i.ncomp == 3 else (i.height, i.width), np.uint8)
+        self._ck_jpeg(self._lib.icelk_jpeg_decode_rgb_file(self._h, data, len(data), _u8(out), out.strides[0]))
+        return out
+
+    def jpeg_device_coefficients(self, data):
+        """The quantised DCT coefficients of a JPEG file as the device decodes them (`read_jpeg(data).coef`), for tests."""
+        from .jpeg import describe_jpeg
+        data = bytes(data)
+        coef = np.empty(int(describe_jpeg(data).coef_count), np.int16)
+        self._ck_jpeg(self._lib.icelk_jpeg_device_coefficients(self._h, data, len(data), C.c_void_p(coef.ctypes.data), coef.size))
+        return coef
+
+    def jpeg_huff_config(self, subseq_bits=512, max_hops=256, max_rounds=8):
+        """Bits per decoder lane (a multiple of 32) and the work bound of the device's Huffman decoder: a file that needs
+        more is decoded by the host decoder inside the same call (`jpeg_huff_stats()["fallback"]` says so)."""
+        self._ck(self._lib.icelk_jpeg_huff_config(self._h, int(subseq_bits), int(max_hops), int(max_rounds)))
+
+    def jpeg_huff_stats(self):
+        """Of the file decoded last: segments, subsequences, rounds, max_hops, total_hops, lanes_in_step, spanning_blocks,
+        fallback (0: none, 1: work bound, 2: a stream that contradicts itself, 3: size)."""
+        st = _lib.JpegHuffStats()
+        self._ck(self._lib.icelk_jpeg_huff_stats(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in st._fields_ if k != "reserved"}
+
     def set_gray_device(self, slot, dev_ptr, w, h, stride):
         self._ck(self._lib.icelk_set_gray_device(self._h, slot, C.c_void_p(dev_ptr), w, h, stride))
 

@@ -185,11 +185,12 @@ static int grow(Ctx* c, T** p, size_t* cap, size_t want)
 
 // Uploads the block rows the pixel box [left, W - right) x [top, H - bottom) needs, transforms the blocks it needs and
 // fills `out` (planes, chroma mode, box) for the output kernel.  The descriptor comes from the caller: nothing in it is
-// trusted beyond what jpeg_info_ok has checked against the image size.
+// trusted beyond what jpeg_info_ok has checked against the image size.  on_device: Ctx::jpeg.d_coef holds the file's
+// coefficients already (jpeg_huff_device), nothing is uploaded.
 static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int left, int top, int right, int bottom,
-                       JpegOutArgs* out)
+                       JpegOutArgs* out, bool on_device = false)
 {
-    if (!I || !coef) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
+    if (!I || (!coef && !on_device)) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
     if (!jpeg_info_ok(*I)) FAIL(c, ICELK_EARG, "JPEG descriptor does not describe a supported file");
     if (left < 0 || top < 0 || right < 0 || bottom < 0 || (long long)left + right >= I->width ||
         (long long)top + bottom >= I->height)
@@ -229,7 +230,8 @@ static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, 
         memcpy(A.quant[k], I->quant[k], sizeof(A.quant[k]));
         // whole block rows by0 .. by0 + nby - 1: contiguous in the layout
         const size_t row = (size_t)I->blocks_x[k] * 64, from = I->coef_offset[k] + (size_t)A.by0[k] * row;
-        HIPCHK(c, hipMemcpyAsync(c->jpeg.d_coef + from, coef + from, row * nby * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+        if (!on_device)
+            HIPCHK(c, hipMemcpyAsync(c->jpeg.d_coef + from, coef + from, row * nby * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
         out->plane[k] = A.plane[k];
         out->pitch[k] = A.pitch[k];
     }
@@ -246,6 +248,146 @@ static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, 
     out->top = top;
     out->ow = I->width - left - right;
     out->oh = I->height - top - bottom;
+    return ICELK_OK;
+}
+
+// the planes of jpeg_planes -> the decoded image on the host (the tail of icelk_jpeg_decode_rgb and of its _file form)
+static int jpeg_rgb_out(Ctx* c, const icelk_jpeg_info_t& I, JpegOutArgs& O, uint8_t* out, int stride)
+{
+    const size_t row = (size_t)O.ow * I.ncomp;
+    if (stride < 0 || (size_t)stride < row) FAIL(c, ICELK_EARG, "stride smaller than a row of the image");
+    if (I.ncomp == 1) {
+        HIPCHK(c, hipMemcpy2DAsync(out, stride, O.plane[0], O.pitch[0], row, O.oh, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        int rc = grow(c, &c->jpeg.d_rgb, &c->jpeg.rgb_cap, row * O.oh);
+        if (rc) return rc;
+        O.dst = c->jpeg.d_rgb;
+        O.dst_pitch = (int)row;
+        {
+            ProfScope p(c, K_JPEG_OUT);
+            launch_jpeg_rgb(c->stream, O);
+        }
+        rc = check_launch(c, "jpeg_out");
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy2DAsync(out, stride, c->jpeg.d_rgb, row, row, O.oh, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ICELK_OK;
+}
+
+// ---- JPEG ingest: the file's bytes -> coefficients in Ctx::jpeg.d_coef (k_jpeg_huff.hip) ---------------------------------
+// The serial decoder takes the file: when the lanes' work bound was hit, or to have the last word on a stream that
+// contradicts itself.
+static int jpeg_huff_fallback(Ctx* c, const uint8_t* data, uint64_t len, const icelk_jpeg_info_t& I, uint32_t why)
+{
+    c->jpeg.stats.fallback = why;
+    std::vector<int16_t> host;
+    try {
+        host.resize((size_t)I.coef_count);
+    } catch (...) {
+        FAIL(c, ICELK_ENOMEM, "no memory for the coefficients");
+    }
+    if (int rc = jpeg_host_decode(data, (size_t)len, host.data(), I.coef_count)) FAIL(c, rc, "not a JPEG file, or a damaged one");
+    HIPCHK(c, hipMemcpyAsync(c->jpeg.d_coef, host.data(), host.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ICELK_OK;
+}
+
+static int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info)
+{
+    if (!data || !info) FAIL(c, ICELK_EARG, "null JPEG file");
+    Ctx::Jpeg& J = c->jpeg;
+    memset(&J.stats, 0, sizeof(J.stats));
+    JpegIndex X;
+    int rc = jpeg_index(data, (size_t)len, X);
+    if (rc == ICELK_EUNSUP && len >= ((uint64_t)1 << 28)) {
+        rc = icelk_jpeg_describe(data, len, info);
+        if (rc) FAIL(c, rc, "not a JPEG file the decoder takes");
+        if (int r2 = grow(c, &J.d_coef, &J.coef_cap, (size_t)info->coef_count)) return r2;
+        return jpeg_huff_fallback(c, data, len, *info, ICELK_JPEG_FALLBACK_SIZE);
+    }
+    if (rc) FAIL(c, rc, rc == ICELK_EUNSUP ? "a JPEG file of a kind the decoder does not take" : "not a JPEG file, or a damaged one");
+    *info = X.info;
+    jpeg_index_lanes(X, (uint32_t)J.subseq_bits, J.max_hops);
+    const lanes::Scan& A = X.scan;
+    JpegHuffArgs H{};
+    H.A = A;
+    H.ngroups = (A.nlanes + lanes::kGroup - 1) / lanes::kGroup;
+    H.ri_mcus = A.seg_blocks ? A.seg_blocks / (uint32_t)A.bpm : (uint32_t)A.nmcu;
+    H.cps = (H.ri_mcus + kJpegDcChunk - 1) / kJpegDcChunk;
+    if (int r2 = grow(c, &J.d_coef, &J.coef_cap, (size_t)X.info.coef_count)) return r2;
+    if (int r2 = grow(c, &J.d_file, &J.file_cap, (size_t)len)) return r2;
+    if (int r2 = grow(c, &J.d_seg, &J.seg_cap, (size_t)A.nseg + 1)) return r2;
+    if (!J.d_tabs) if (int r2 = dmalloc(c, &J.d_tabs, lanes::kTables)) return r2;
+    if (!J.d_ctl) if (int r2 = dmalloc(c, &J.d_ctl, JH_WORDS)) return r2;
+    if (J.lane_cap < (size_t)A.nlanes + 1) {
+        // the four arrays of the lanes grow together
+        size_t cap = 0;
+        if (int r2 = grow(c, &J.d_T, &cap, (size_t)A.nlanes + 1)) return r2;
+        cap = 0;
+        if (int r2 = grow(c, &J.d_cnt, &cap, (size_t)A.nlanes + 1)) return r2;
+        cap = 0;
+        if (int r2 = grow(c, &J.d_P, &cap, (size_t)A.nlanes + 1)) return r2;
+        J.lane_cap = (size_t)A.nlanes + 1;
+    }
+    if (int r2 = grow(c, &J.d_X, &J.group_cap, (size_t)2 * H.ngroups)) return r2;
+    if (int r2 = grow(c, &J.d_dc, &J.dc_cap, (size_t)3 * A.nseg * H.cps)) return r2;
+    H.data = J.d_file;
+    H.seg = J.d_seg;
+    H.tabs = J.d_tabs;
+    H.T = J.d_T;
+    H.cnt = J.d_cnt;
+    H.P = J.d_P;
+    H.X = J.d_X;
+    H.ctl = J.d_ctl;
+    H.coef = J.d_coef;
+    H.dc = J.d_dc;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(J.d_file, data, (size_t)len, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(J.d_seg, X.seg.data(), X.seg.size() * sizeof(lanes::Seg), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(J.d_tabs, X.tabs, sizeof(X.tabs), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(J.d_ctl, 0, JH_WORDS * sizeof(uint32_t), st));
+    HIPCHK(c, hipMemsetAsync(J.d_coef, 0, (size_t)X.info.coef_count * sizeof(int16_t), st));
+    J.stats.segments = A.nseg;
+    J.stats.subsequences = A.nlanes;
+    uint32_t ctl[JH_WORDS];
+    // Phase 1.  A round that no group takes part in costs a launch of workgroups that return at once, so the rounds go out
+    // a few at a time and the host looks at their flags afterwards: the fixed point is reached when one changed nothing.
+    bool settled = false, bound = false;
+    {
+        ProfScope p(c, K_JPEG_HUFF);
+        launch_jpeg_huff_sync(st, H, 0);
+        int r = 1;
+        while (!settled && !bound && r <= J.max_rounds) {
+            const int r_end = std::min(J.max_rounds, r + 3);
+            for (int q = r; q <= r_end; q++) launch_jpeg_huff_sync(st, H, q);
+            if (int r2 = check_launch(c, "jpeg_huff_sync")) return r2;
+            HIPCHK(c, hipMemcpyAsync(ctl, J.d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            bound = ctl[JH_BOUND] != 0;
+            for (int q = r; q <= r_end && !settled; q++) settled = ctl[JH_ROUND0 + q] == 0;
+            r = r_end + 1;
+        }
+    }
+    J.stats.rounds = 1;
+    for (int q = 1; q <= J.max_rounds && ctl[JH_ROUND0 + q]; q++) J.stats.rounds++;
+    J.stats.max_hops = ctl[JH_MAX_HOPS];
+    J.stats.total_hops = ctl[JH_TOTAL_HOPS];
+    if (bound || !settled) return jpeg_huff_fallback(c, data, len, X.info, ICELK_JPEG_FALLBACK_BOUND);
+    // Phases 2 and 3 and the DC pass.  The DC pass runs on whatever the lanes wrote: were they irregular, the serial
+    // decoder overwrites all of it.
+    {
+        ProfScope p(c, K_JPEG_HUFF);
+        launch_jpeg_huff_scan(st, H);
+        launch_jpeg_huff_write(st, H);
+        launch_jpeg_huff_dc(st, H);
+    }
+    if (int r2 = check_launch(c, "jpeg_huff_write")) return r2;
+    HIPCHK(c, hipMemcpyAsync(ctl, J.d_ctl, JH_ROUND0 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    J.stats.lanes_in_step = ctl[JH_IN_STEP];
+    J.stats.spanning_blocks = ctl[JH_SPANS];
+    if (ctl[JH_IRREGULAR]) return jpeg_huff_fallback(c, data, len, X.info, ICELK_JPEG_FALLBACK_STREAM);
     return ICELK_OK;
 }
 
@@ -366,23 +508,86 @@ int icelk_jpeg_decode_rgb(icelk_t* h, const icelk_jpeg_info_t* info, const int16
     JpegOutArgs O{};
     int rc = jpeg_planes(c, info, coef, 0, 0, 0, 0, &O);
     if (rc) return rc;
-    const size_t row = (size_t)O.ow * info->ncomp;
-    if (stride < 0 || (size_t)stride < row) FAIL(c, ICELK_EARG, "stride smaller than a row of the image");
-    if (info->ncomp == 1) {
-        HIPCHK(c, hipMemcpy2DAsync(out, stride, O.plane[0], O.pitch[0], row, O.oh, hipMemcpyDeviceToHost, c->stream));
-    } else {
-        rc = grow(c, &c->jpeg.d_rgb, &c->jpeg.rgb_cap, row * O.oh);
-        if (rc) return rc;
-        O.dst = c->jpeg.d_rgb;
-        O.dst_pitch = (int)row;
-        {
-            ProfScope p(c, K_JPEG_OUT);
-            launch_jpeg_rgb(c->stream, O);
-        }
-        rc = check_launch(c, "jpeg_out");
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpy2DAsync(out, stride, c->jpeg.d_rgb, row, row, O.oh, hipMemcpyDeviceToHost, c->stream));
+    return jpeg_rgb_out(c, *info, O, out, stride);
+}
+
+int icelk_jpeg_huff_config(icelk_t* h, int subseq_bits, int max_hops, int max_rounds)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!jpeg_huff_config_ok(subseq_bits, max_hops, max_rounds)) FAIL(c, ICELK_EARG, "bad subsequence length or work bound");
+    c->jpeg.subseq_bits = subseq_bits;
+    c->jpeg.max_hops = max_hops;
+    c->jpeg.max_rounds = max_rounds;
+    return ICELK_OK;
+}
+
+int icelk_jpeg_huff_stats(icelk_t* h, icelk_jpeg_huff_stats_t* stats)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!stats) FAIL(c, ICELK_EARG, "null statistics");
+    *stats = c->jpeg.stats;
+    return ICELK_OK;
+}
+
+int icelk_upload_jpeg_file(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left, int crop_top,
+                           int crop_right, int crop_bottom)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (gray_variant != ICELK_GRAY_CV3 && gray_variant != ICELK_GRAY_CV4) FAIL(c, ICELK_EARG, "bad gray variant");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = check_slot(c, slot, false);
+    if (rc) return rc;
+    icelk_jpeg_info_t I;
+    if (data && !icelk_jpeg_describe(data, len, &I) && I.ncomp != 3) FAIL(c, ICELK_EARG, "expected a 3-component JPEG file");
+    rc = jpeg_huff_device(c, data, len, &I);
+    if (rc) return rc;
+    JpegOutArgs O{};
+    rc = jpeg_planes(c, &I, nullptr, crop_left, crop_top, crop_right, crop_bottom, &O, true);
+    if (rc) return rc;
+    rc = begin_frame(c, slot, O.ow, O.oh);
+    if (rc) return rc;
+    Slot& s = c->slots[slot];
+    O.dst = s.lv[0].ptr;
+    O.dst_pitch = s.lv[0].pitch;
+    {
+        ProfScope p(c, K_JPEG_OUT);
+        launch_jpeg_gray(c->stream, O, gray_variant);
     }
+    rc = check_launch(c, "jpeg_out");
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return end_frame(c, s);
+}
+
+int icelk_jpeg_decode_rgb_file(icelk_t* h, const uint8_t* data, uint64_t len, uint8_t* out, int stride)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!out) FAIL(c, ICELK_EARG, "null output image");
+    HIPCHK(c, hipSetDevice(c->device));
+    icelk_jpeg_info_t I;
+    int rc = jpeg_huff_device(c, data, len, &I);
+    if (rc) return rc;
+    JpegOutArgs O{};
+    rc = jpeg_planes(c, &I, nullptr, 0, 0, 0, 0, &O, true);
+    if (rc) return rc;
+    return jpeg_rgb_out(c, I, O, out, stride);
+}
+
+int icelk_jpeg_device_coefficients(icelk_t* h, const uint8_t* data, uint64_t len, int16_t* coef, uint64_t capacity)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!coef) FAIL(c, ICELK_EARG, "null coefficient buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    icelk_jpeg_info_t I;
+    int rc = jpeg_huff_device(c, data, len, &I);
+    if (rc) return rc;
+    if (capacity < I.coef_count) FAIL(c, ICELK_ECAP, "coefficient buffer too small");
+    HIPCHK(c, hipMemcpyAsync(coef, c->jpeg.d_coef, (size_t)I.coef_count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ICELK_OK;
 }

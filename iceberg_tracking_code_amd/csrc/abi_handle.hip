@@ -9,7 +9,7 @@ namespace icelk {
 
 static const char* kKernelNames[K_COUNT_] = {
     "bgr2gray", "pyrdown", "lk", "lk_fb", "corner_candidates", "min_distance", "sort_emit",
-    "project_tracks", "synth", "lk_fb_pair", "jpeg_idct", "jpeg_out",
+    "project_tracks", "synth", "lk_fb_pair", "jpeg_idct", "jpeg_out", "jpeg_huff",
 };
 
 std::string g_create_err;
@@ -206,7 +206,9 @@ static void destroy_ctx(Ctx* c)
     void* ptrs[] = {c->d_bgr, c->d_mask, c->d_p0, c->d_p1, c->d_p0r, c->d_err_f, c->d_err_b, c->d_dist, c->d_corners,
                     c->d_st_f, c->d_st_b, c->d_valid, c->dset[0].D.eig, c->d_tracked,
                     c->d_out_tracks, c->d_out_quality, c->post.d_proj, c->post.d_keep, c->post.d_cube_u, c->post.d_cube_v,
-                    c->post.d_cube_count, c->calib.d_shore, c->calib.d_water, c->jpeg.d_coef, c->jpeg.d_planes, c->jpeg.d_rgb};
+                    c->post.d_cube_count, c->calib.d_shore, c->calib.d_water, c->jpeg.d_coef, c->jpeg.d_planes, c->jpeg.d_rgb,
+                    c->jpeg.d_file, c->jpeg.d_seg, c->jpeg.d_tabs, c->jpeg.d_T, c->jpeg.d_X, c->jpeg.d_cnt, c->jpeg.d_P, c->jpeg.d_ctl,
+                    c->jpeg.d_dc};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto& S : c->sb) {

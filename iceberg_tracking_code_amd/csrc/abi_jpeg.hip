@@ -3,6 +3,10 @@
 // is written after start-up: the decode-ahead threads of sequence.py run it side by side.  The device half is k_jpeg.hip,
 // reached through icelk_upload_jpeg / icelk_jpeg_decode_rgb (abi_frames.hip).
 //
+// For Huffman decoding on the device (k_jpeg_huff.hip) this file also locates the entropy-coded segments and packs the
+// tables (icelk_jpeg_index), and states the parallel algorithm of jpeg_lanes.h serially, phase by phase, on the CPU
+// (icelk_jpeg_read_coefficients_lanes).
+//
 // The stream is outside input: every byte is fetched through a bounds check, every table index is checked before use,
 // and anything that does not add up returns ICELK_EARG.  Nothing here throws or aborts.
 //
@@ -10,8 +14,10 @@
 // F.2.2).  What counts as "YCbCr" follows libjpeg's guess (JFIF marker / Adobe transform / component ids), because the
 // result has to equal Pillow's.
 #include <new>
+#include <vector>
 
 #include "icelk_ctx.h"
+#include "jpeg_lanes.h"
 
 namespace icelk {
 
@@ -368,6 +374,241 @@ int decode_scan(const uint8_t* d, size_t len, const Parsed& P, int16_t* coef)
     return ICELK_OK;
 }
 
+
+// ---- the scan as the lanes see it ---------------------------------------------------------------------------------------
+// the next marker at or behind `from`: the first FF that is not followed by a stuffed zero; len: none
+size_t next_marker(const uint8_t* d, size_t len, size_t from)
+{
+    size_t q = from;
+    while (q < len) {
+        const void* f = memchr(d + q, 0xFF, len - q);
+        if (!f) return len;
+        q = (size_t)((const uint8_t*)f - d);
+        if (q + 1 < len && d[q + 1] == 0) {
+            q += 2;
+            continue;
+        }
+        return q;
+    }
+    return len;
+}
+
+void pack_table(const Huff& H, lanes::HuffTable& T)
+{
+    memset(&T, 0, sizeof(T));
+    for (int i = 0; i < 17; i++) T.maxcode[i] = -1;
+    if (!H.set) return;
+    memcpy(T.look, H.look, sizeof(T.look));
+    for (int len = 1; len <= 16; len++) {
+        T.maxcode[len] = H.maxcode[len];
+        T.valoff[len] = H.valoff[len];
+    }
+    memcpy(T.vals, H.vals, sizeof(T.vals));
+}
+
+}  // namespace
+
+static_assert(sizeof(lanes::HuffTable) * lanes::kTables == ICELK_JPEG_TABLE_BYTES, "the header states the packed tables' size");
+
+// Headers, segments and tables of a file.  The RSTn markers must come in the order D0 .. D7, D0 ... and be as many as
+// the restart interval and the number of MCUs imply; what follows the last segment is not looked at.
+int jpeg_index(const uint8_t* d, size_t len, JpegIndex& X)
+{
+    if (len >= ((size_t)1 << 28)) return ICELK_EUNSUP;   // positions are 32-bit bit offsets
+    Parsed* P = new (std::nothrow) Parsed;
+    if (!P) return ICELK_ENOMEM;
+    int rc = parse_headers(d, len, *P);
+    if (rc) {
+        delete P;
+        return rc;
+    }
+    X.info = P->I;
+    for (int t = 0; t < 4; t++) {
+        pack_table(P->dc[t], X.tabs[t]);
+        pack_table(P->ac[t], X.tabs[4 + t]);
+    }
+    const icelk_jpeg_info_t& I = X.info;
+    lanes::Scan& A = X.scan;
+    memset(&A, 0, sizeof(A));
+    int b = 0;
+    for (int c = 0; c < I.ncomp; c++) {
+        const int hs = c == 0 ? I.hmax : 1, vs = c == 0 ? I.vmax : 1;
+        for (int v = 0; v < vs; v++)
+            for (int u = 0; u < hs; u++, b++) {
+                A.comp_pack |= (uint32_t)c << (2 * b);
+                A.dc_pack |= (uint32_t)P->td[c] << (2 * b);
+                A.ac_pack |= (uint32_t)P->ta[c] << (2 * b);
+                A.u_pack |= (uint32_t)u << (2 * b);
+                A.v_pack |= (uint32_t)v << (2 * b);
+            }
+    }
+    const size_t scan = P->scan;
+    delete P;
+    A.bpm = b;
+    A.nmcu = I.mcus_x * I.mcus_y;
+    A.mcus_x = I.mcus_x;
+    A.total_blocks = (uint32_t)A.nmcu * (uint32_t)b;
+    const uint32_t ri = I.restart_interval > 0 && I.restart_interval < A.nmcu ? (uint32_t)I.restart_interval : 0;
+    A.seg_blocks = ri * (uint32_t)b;
+    A.nseg = ri ? ((uint32_t)A.nmcu + ri - 1) / ri : 1;
+    A.hs = I.hmax;
+    A.vs = I.vmax;
+    A.blocks_x0 = I.blocks_x[0];
+    A.blocks_x1 = I.blocks_x[1];
+    A.off0 = I.coef_offset[0];
+    A.off1 = I.coef_offset[1];
+    A.off2 = I.coef_offset[2];
+    try {
+        X.seg.assign(A.nseg + 1, lanes::Seg{0, 0, 0});
+    } catch (...) {
+        return ICELK_ENOMEM;
+    }
+    size_t pos = scan;
+    for (uint32_t s = 0; s < A.nseg; s++) {
+        const size_t end = next_marker(d, len, pos);
+        X.seg[s].begin = (uint32_t)pos;
+        X.seg[s].end = (uint32_t)end;
+        if (s + 1 < A.nseg) {
+            size_t m = end;
+            while (m + 1 < len && d[m] == 0xFF && d[m + 1] == 0xFF) m++;   // fill bytes in front of the marker
+            if (m + 1 >= len || d[m] != 0xFF || d[m + 1] != 0xD0 + (s & 7)) return ICELK_EARG;
+            pos = m + 2;
+        }
+    }
+    return ICELK_OK;
+}
+
+// cuts the segments into lanes of S bits
+void jpeg_index_lanes(JpegIndex& X, uint32_t S, int max_hops)
+{
+    uint32_t lane = 0;
+    for (uint32_t s = 0; s < X.scan.nseg; s++) {
+        X.seg[s].lane0 = lane;
+        const uint64_t bits = (uint64_t)(X.seg[s].end - X.seg[s].begin) * 8;
+        lane += bits ? (uint32_t)((bits + S - 1) / S) : 1;
+    }
+    X.seg[X.scan.nseg].lane0 = lane;
+    X.scan.nlanes = lane;
+    X.scan.S = S;
+    X.scan.max_hops = max_hops;
+}
+
+bool jpeg_huff_config_ok(int subseq_bits, int max_hops, int max_rounds)
+{
+    return subseq_bits >= 32 && subseq_bits % 32 == 0 && subseq_bits <= (1 << 20) && max_hops >= 1 && max_rounds >= 1 &&
+           max_rounds <= kJpegMaxRounds;
+}
+
+int jpeg_host_decode(const uint8_t* data, size_t len, int16_t* coef, uint64_t capacity)
+{
+    return icelk_jpeg_read_coefficients(data, (uint64_t)len, coef, capacity);
+}
+
+namespace {
+
+// the DC differences of every component summed up in scan order, from zero at every restart interval
+void dc_pass_host(const lanes::Scan& A, int16_t* coef)
+{
+    const uint32_t ri = A.seg_blocks ? A.seg_blocks / (uint32_t)A.bpm : (uint32_t)A.nmcu;
+    int32_t pred[3] = {0, 0, 0};
+    uint32_t g = 0;
+    for (uint32_t mcu = 0; mcu < (uint32_t)A.nmcu; mcu++) {
+        if (mcu % ri == 0) pred[0] = pred[1] = pred[2] = 0;
+        for (int b = 0; b < A.bpm; b++, g++) {
+            const int c = (A.comp_pack >> (2 * b)) & 3;
+            int16_t* p = coef + lanes::block_base(A, g);
+            pred[c] += *p;
+            *p = (int16_t)pred[c];
+        }
+    }
+}
+
+// The phases of k_jpeg_huff.hip, one lane after the other.  false: the work bound was hit, nothing was written.
+bool lanes_decode_host(const uint8_t* data, JpegIndex& X, int max_rounds, int16_t* coef, icelk_jpeg_huff_stats_t& st, bool* irregular)
+{
+    using namespace lanes;
+    const Scan& A = X.scan;
+    const Seg* seg = X.seg.data();
+    const uint32_t n = A.nlanes, ngroups = (n + kGroup - 1) / kGroup;
+    std::vector<uint64_t> T(n), Xs[2];
+    std::vector<uint32_t> cnt(n, 0), P(n + 1, 0);
+    std::vector<Chain> ch(kGroup);
+    Xs[0].assign(ngroups, kNoState);
+    Xs[1].assign(ngroups, kNoState);
+    st.segments = A.nseg;
+    st.subsequences = n;
+    bool bound = false;
+    auto run_steps = [&](uint32_t g, uint32_t first_active, uint32_t last_active, uint64_t* x_out) {
+        const uint32_t g0 = g * kGroup, g1 = std::min(n, g0 + kGroup);
+        for (uint32_t h = 0; h < (uint32_t)kGroup; h++) {
+            bool any = false;
+            for (uint32_t i = first_active; i < last_active; i++) any |= ch[i - g0].active;
+            if (!any) break;
+            for (uint32_t i = first_active; i < last_active; i++)
+                sync_step(A, X.tabs, data, seg, g0, g1, T.data() + g0, cnt.data() + g0, x_out, i, h, ch[i - g0]);
+        }
+        for (uint32_t i = first_active; i < last_active; i++) {
+            const Chain& c = ch[i - g0];
+            st.total_hops += c.hops;
+            st.max_hops = std::max(st.max_hops, c.hops);
+            bound |= c.bound;
+        }
+    };
+    // round 0: every lane from its guess
+    for (uint32_t g = 0; g < ngroups; g++) {
+        const uint32_t g0 = g * kGroup, g1 = std::min(n, g0 + kGroup);
+        for (uint32_t i = g0; i < g1; i++) {
+            Chain& c = ch[i - g0];
+            c.s = T[i] = initial_state(A, data, seg, i, &c.seg);
+            c.hops = 0;
+            c.active = true;
+            c.bound = false;
+        }
+        run_steps(g, g0, g1, &Xs[0][g]);
+    }
+    st.rounds = 1;
+    // rounds 1 ..: a group whose entry the group in front has changed runs one chain from its first lane
+    bool settled = false;
+    for (int r = 1; r <= max_rounds && !bound; r++) {
+        std::vector<uint64_t>&prev = Xs[(r - 1) & 1], &cur = Xs[r & 1];
+        bool changed = false;
+        cur[0] = prev[0];
+        for (uint32_t g = 1; g < ngroups; g++) {
+            const uint32_t g0 = g * kGroup;
+            cur[g] = prev[g];
+            const uint64_t e = prev[g - 1];
+            if (e == kNoState || e == T[g0]) continue;
+            changed = true;
+            Chain& c = ch[0];
+            c.s = T[g0] = e;
+            c.seg = segment_of(seg, A.nseg, g0);
+            c.hops = 0;
+            c.active = true;
+            c.bound = false;
+            run_steps(g, g0, g0 + 1, &cur[g]);
+        }
+        if (!changed) {
+            settled = true;
+            break;
+        }
+        st.rounds++;
+    }
+    if (bound || !settled) return false;
+    // phase 2: blocks completed in front of every lane
+    for (uint32_t j = 0; j < n; j++) P[j + 1] = P[j] + cnt[j];
+    // phase 3
+    *irregular = false;
+    for (uint32_t j = 0; j < n; j++) {
+        const uint32_t s = segment_of(seg, A.nseg, j);
+        const LaneReport rep = write_lane(A, X.tabs, data, seg, j, T[j], P[j] - P[seg[s].lane0], coef);
+        *irregular |= rep.irregular;
+        st.lanes_in_step += rep.in_step;
+        st.spanning_blocks += rep.spans;
+    }
+    if (!*irregular) dc_pass_host(A, coef);
+    return true;
+}
+
 }  // namespace
 
 // the descriptor a caller hands to the device entry points is checked against what its first five fields imply
@@ -417,6 +658,74 @@ int icelk_jpeg_read_coefficients(const uint8_t* data, uint64_t len, int16_t* coe
     if (!rc && capacity < P->I.coef_count) rc = ICELK_ECAP;
     if (!rc) rc = decode_scan(data, (size_t)len, *P, coef);
     delete P;
+    return rc;
+}
+
+int icelk_jpeg_index(const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info, icelk_jpeg_scan_t* scan, uint32_t* seg_begin,
+                     uint32_t* seg_end, uint64_t seg_capacity, void* tables)
+{
+    if (!data || !info || !scan) return ICELK_EARG;
+    JpegIndex* X = new (std::nothrow) JpegIndex;
+    if (!X) return ICELK_ENOMEM;
+    int rc = jpeg_index(data, (size_t)len, *X);
+    if (!rc) {
+        *info = X->info;
+        memset(scan, 0, sizeof(*scan));
+        scan->segments = X->scan.nseg;
+        scan->blocks_per_mcu = (uint32_t)X->scan.bpm;
+        scan->blocks_per_segment = X->scan.seg_blocks;
+        scan->total_blocks = X->scan.total_blocks;
+        for (int b = 0; b < X->scan.bpm; b++) {
+            scan->component[b] = (uint8_t)((X->scan.comp_pack >> (2 * b)) & 3);
+            scan->dc_table[b] = (uint8_t)((X->scan.dc_pack >> (2 * b)) & 3);
+            scan->ac_table[b] = (uint8_t)((X->scan.ac_pack >> (2 * b)) & 3);
+        }
+        if (seg_begin && seg_end) {
+            if (seg_capacity < X->scan.nseg) rc = ICELK_ECAP;
+            for (uint32_t s = 0; !rc && s < X->scan.nseg; s++) {
+                seg_begin[s] = X->seg[s].begin;
+                seg_end[s] = X->seg[s].end;
+            }
+        }
+        if (!rc && tables) memcpy(tables, X->tabs, sizeof(X->tabs));
+    }
+    delete X;
+    return rc;
+}
+
+int icelk_jpeg_read_coefficients_lanes(const uint8_t* data, uint64_t len, int16_t* coef, uint64_t capacity, int subseq_bits,
+                                       int max_hops, int max_rounds, icelk_jpeg_huff_stats_t* stats)
+{
+    if (!data || !coef || !jpeg_huff_config_ok(subseq_bits, max_hops, max_rounds)) return ICELK_EARG;
+    icelk_jpeg_huff_stats_t st;
+    memset(&st, 0, sizeof(st));
+    JpegIndex* X = new (std::nothrow) JpegIndex;
+    if (!X) return ICELK_ENOMEM;
+    int rc = jpeg_index(data, (size_t)len, *X);
+    if (rc == ICELK_EUNSUP && len >= ((uint64_t)1 << 28)) {
+        // too long for 32-bit bit positions: the serial decoder takes it
+        delete X;
+        st.fallback = ICELK_JPEG_FALLBACK_SIZE;
+        if (stats) *stats = st;
+        return icelk_jpeg_read_coefficients(data, len, coef, capacity);
+    }
+    if (!rc && capacity < X->info.coef_count) rc = ICELK_ECAP;
+    if (!rc) {
+        bool irregular = false, done = false;
+        try {
+            jpeg_index_lanes(*X, (uint32_t)subseq_bits, max_hops);
+            memset(coef, 0, (size_t)X->info.coef_count * sizeof(int16_t));
+            done = lanes_decode_host(data, *X, max_rounds, coef, st, &irregular);
+        } catch (...) {
+            rc = ICELK_ENOMEM;
+        }
+        if (!rc && (!done || irregular)) {
+            st.fallback = done ? ICELK_JPEG_FALLBACK_STREAM : ICELK_JPEG_FALLBACK_BOUND;
+            rc = icelk_jpeg_read_coefficients(data, len, coef, capacity);
+        }
+    }
+    delete X;
+    if (stats) *stats = st;
     return rc;
 }
 

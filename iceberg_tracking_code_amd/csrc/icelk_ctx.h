@@ -82,6 +82,16 @@ struct Ctx {
         int16_t* d_coef = nullptr;
         uint8_t *d_planes = nullptr, *d_rgb = nullptr;
         size_t coef_cap = 0, planes_cap = 0, rgb_cap = 0;   // elements / bytes / bytes
+        // Huffman decoding on the device (icelk_upload_jpeg_file ...): the file, its segments and tables, the lanes' arrays
+        uint8_t* d_file = nullptr;
+        lanes::Seg* d_seg = nullptr;
+        lanes::HuffTable* d_tabs = nullptr;
+        uint64_t *d_T = nullptr, *d_X = nullptr;
+        uint32_t *d_cnt = nullptr, *d_P = nullptr, *d_ctl = nullptr;
+        int32_t* d_dc = nullptr;
+        size_t file_cap = 0, seg_cap = 0, lane_cap = 0, group_cap = 0, dc_cap = 0;
+        int subseq_bits = 512, max_hops = lanes::kGroup, max_rounds = 8;   // icelk_jpeg_huff_config
+        icelk_jpeg_huff_stats_t stats{};                                     // of the latest file
     } jpeg;
 
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
@@ -392,6 +402,16 @@ int ensure_pyramid(Ctx* c, int slot, int top_level);
 Pyramid pyramid_of(const Slot& s);
 // abi_jpeg.hip
 bool jpeg_info_ok(const icelk_jpeg_info_t& in);
+struct JpegIndex {   // a file as the lanes of jpeg_lanes.h see it
+    icelk_jpeg_info_t info;
+    lanes::HuffTable tabs[lanes::kTables];
+    lanes::Scan scan;
+    std::vector<lanes::Seg> seg;   // scan.nseg + 1
+};
+int jpeg_index(const uint8_t* d, size_t len, JpegIndex& X);
+void jpeg_index_lanes(JpegIndex& X, uint32_t S, int max_hops);
+bool jpeg_huff_config_ok(int subseq_bits, int max_hops, int max_rounds);
+int jpeg_host_decode(const uint8_t* data, size_t len, int16_t* coef, uint64_t capacity);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

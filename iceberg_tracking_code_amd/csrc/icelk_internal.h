@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/icelk.h"
+#include "jpeg_lanes.h"
 
 namespace icelk {
 
@@ -57,6 +58,7 @@ enum KernelId {
     K_LK_FB_PAIR,   // two segment pairs in one launch (icelk_seg_track_defer)
     K_JPEG_IDCT,    // dequantise + inverse DCT (k_jpeg.hip)
     K_JPEG_OUT,     // upsample + colour + crop + gray / RGB
+    K_JPEG_HUFF,    // Huffman decoding: synchronise, scan, write, DC (k_jpeg_huff.hip)
     K_COUNT_
 };
 
@@ -117,6 +119,39 @@ struct JpegOutArgs {
 void launch_jpeg_idct(hipStream_t s, const JpegIdctArgs& A);
 void launch_jpeg_gray(hipStream_t s, JpegOutArgs A, int variant);
 void launch_jpeg_rgb(hipStream_t s, JpegOutArgs A);
+
+// Huffman decoding on the device (k_jpeg_huff.hip; the algorithm is jpeg_lanes.h).  All pointers are device memory.
+constexpr int kJpegMaxRounds = 255;
+constexpr int kJpegDcChunk = 16;   // MCUs one thread of the DC pass sums up
+enum JpegHuffCtl {                 // words of JpegHuffArgs::ctl
+    JH_BOUND = 0,     // a chain stopped at max_hops
+    JH_IRREGULAR,     // the write phase met a stream that contradicts itself
+    JH_IN_STEP,       // lanes whose guess was the true state
+    JH_SPANS,         // blocks that began in one lane and ended in another
+    JH_MAX_HOPS,
+    JH_TOTAL_HOPS,
+    JH_ROUND0 = 8,    // ctl[JH_ROUND0 + r] != 0: round r changed an entry state
+    JH_WORDS = JH_ROUND0 + kJpegMaxRounds + 1
+};
+struct JpegHuffArgs {
+    lanes::Scan A;
+    const uint8_t* data;            // the file
+    const lanes::Seg* seg;          // A.nseg + 1
+    const lanes::HuffTable* tabs;   // lanes::kTables
+    uint64_t* T;                    // [lane] entry state
+    uint32_t* cnt;                  // [lane] blocks completed in the subsequence
+    uint32_t* P;                    // [lane + 1] exclusive prefix sum of cnt over all lanes
+    uint64_t* X;                    // [2][group] exit state of a group, by the round's parity
+    uint32_t* ctl;
+    int16_t* coef;
+    int32_t* dc;                    // [chunk][3] sums of DC differences, then their prefix inside the restart interval
+    uint32_t ngroups;
+    uint32_t ri_mcus, cps;          // MCUs per restart interval, chunks per restart interval
+};
+void launch_jpeg_huff_sync(hipStream_t s, const JpegHuffArgs& H, int round);
+void launch_jpeg_huff_scan(hipStream_t s, const JpegHuffArgs& H);
+void launch_jpeg_huff_write(hipStream_t s, const JpegHuffArgs& H);
+void launch_jpeg_huff_dc(hipStream_t s, const JpegHuffArgs& H);
 
 // LK.  p_in/p_out etc. are device pointers.  fb = fused forward+backward.
 struct LKBuffers {

@@ -92,10 +92,40 @@ def read_jpeg(path_or_bytes, out=None):
     return JpegCoefficients(info, coef)
 
 
-def decode_jpeg(data, ctx=None):
+def read_jpeg_lanes(data, subseq_bits=512, max_hops=256, max_rounds=8):
+    """`read_jpeg` by the algorithm of the device's Huffman decoder (csrc/jpeg_lanes.h), run lane by lane on the CPU:
+    (JpegCoefficients, statistics as `Context.jpeg_huff_stats` gives them).  No GPU needed; for tests and measurements."""
+    data = bytes(data)
+    lib = _lib.load()
+    info = _lib.JpegInfo()
+    _check(lib.icelk_jpeg_describe(data, len(data), C.byref(info)), "icelk_jpeg_describe")
+    coef = np.empty(int(info.coef_count), np.int16)
+    st = _lib.JpegHuffStats()
+    _check(lib.icelk_jpeg_read_coefficients_lanes(data, len(data), C.c_void_p(coef.ctypes.data), coef.size, int(subseq_bits),
+                                                  int(max_hops), int(max_rounds), C.byref(st)),
+           "icelk_jpeg_read_coefficients_lanes")
+    return JpegCoefficients(info, coef), {k: int(getattr(st, k)) for k, _ in st._fields_ if k != "reserved"}
+
+
+def decode_jpeg(data, ctx=None, huffman="host"):
     """A path, the file's bytes or a JpegCoefficients -> H x W x 3 (R G B) or H x W uint8 array, the pixels
     np.array(PIL.Image.open(...)) gives, computed on the device.  `ctx`: a Context to run on (default: the one of the
-    cv2-shaped functions, api.default_context)."""
+    cv2-shaped functions, api.default_context).  huffman="device": the scan is Huffman-decoded on the device too
+    (a path or bytes only)."""
+    if huffman not in ("host", "device"):
+        raise ValueError('huffman must be "host" or "device"')
+    if huffman == "device":
+        if isinstance(data, JpegCoefficients):
+            raise ValueError('huffman="device" takes a path or the file\'s bytes')
+        if not isinstance(data, (bytes, bytearray, memoryview)):
+            with open(data, "rb") as f:
+                data = f.read()
+        data = bytes(data)
+        if ctx is None:
+            from .api import default_context
+            info = describe_jpeg(data)
+            ctx = default_context(info.width, info.height)
+        return ctx.jpeg_decode_rgb_file(data)
     j = data if isinstance(data, JpegCoefficients) else read_jpeg(data)
     if ctx is None:
         from .api import default_context

@@ -10,8 +10,9 @@ Here: a small thread pool decodes ahead on the host -- the real end-to-end bound
 `decoder="pil"` (default) it decodes whole photos with PIL and the crop box is cut during the upload of the decoded
 frame (`Context.upload_bgr(crop=...)`); with `decoder="device"` the pool only Huffman-decodes (`jpeg.read_jpeg`) and
 the device does the inverse DCT, chroma upsampling, colour conversion, crop and gray (`Context.upload_jpeg`), giving
-the same pixels; files the device decoder does not take go through PIL one by one.  Either way the reference's lossy
-re-save of the crop has no counterpart and pixel values are those of the original photo; gray conversion, detection,
+the same pixels; files the device decoder does not take go through PIL one by one.  With `huffman="device"` on top
+the pool only reads the files and the device Huffman-decodes them as well (`Context.upload_jpeg_file`).  Either way
+the reference's lossy re-save of the crop has no counterpart and pixel values are those of the original photo; gray conversion, detection,
 tracking, filtering and the track table are the device-resident loop of `SegmentTracker`; the mask is rasterised on
 the device from the polygon (`icelk_set_mask_polygon`) or uploaded.  Output files carry the reference's names and
 arrays.
@@ -42,6 +43,20 @@ def _read(path):
     return _decode(path)
 
 
+def _read_bytes(path):
+    """decoder="device", huffman="device": the pool thread reads the file and its headers; a file the device decoder
+    does not take goes through PIL, as in `_read`."""
+    from .jpeg import describe_jpeg
+    try:
+        with open(path, "rb") as f:
+            data = f.read()
+        if describe_jpeg(data).ncomp == 3:
+            return data
+    except ValueError:
+        pass
+    return _decode(path)
+
+
 def _image_size(path, decoder):
     if decoder == "device":
         from .jpeg import describe_jpeg
@@ -57,7 +72,7 @@ def _image_size(path, decoder):
 
 def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startlist=(0,), crop=None, mask=None,
                          mask_polygon=None, feature_params=None, lk_params=None, decode_threads=4, decode_ahead=6,
-                         gray_variant=4, device=0, on_segment=None, save=True, decoder="pil"):
+                         gray_variant=4, device=0, on_segment=None, save=True, decoder="pil", huffman="host"):
     """Track one day's photos.  Returns [(npz path, tracks (n, T+1, 2) f32, trackquality (n, T) f32)] of the
     segments that pass the time-gap rule, in order.
 
@@ -69,9 +84,15 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
     on_segment     optional callback(npz path, tracks, trackquality), e.g. a projection step
     decoder        "pil": photos are decoded on the host; "device": only their Huffman decoding is (see above) -- same
                    outputs, supported files and the per-file fallback are listed in INTEGRATION.md
+    huffman        with decoder="device": "host" (the pool threads Huffman-decode) or "device" (they only read the file
+                   and its headers; the scan is decoded on the device, `Context.upload_jpeg_file`) -- same outputs
     """
     if decoder not in ("pil", "device"):
         raise ValueError('decoder must be "pil" or "device"')
+    if huffman not in ("host", "device"):
+        raise ValueError('huffman must be "host" or "device"')
+    if huffman == "device" and decoder != "device":
+        raise ValueError('huffman="device" needs decoder="device"')
     imagelist = [str(p) for p in imagelist]
     out = []
     if len(imagelist) <= track_len:                       # s1:267
@@ -82,7 +103,7 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
     if crop is not None:
         left, top, right, bottom = (int(v) for v in crop)
         w, h = w - left - right, h - top - bottom
-    load = _read if decoder == "device" else _decode
+    load = (_read_bytes if huffman == "device" else _read) if decoder == "device" else _decode
     trk = None
     try:
         with ThreadPoolExecutor(max_workers=max(1, int(decode_threads))) as pool:
@@ -99,7 +120,12 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                     frame = pending.pop(0).result()
                     if counter + decode_ahead < len(names):
                         pending.append(pool.submit(load, names[counter + decode_ahead]))
-                    if isinstance(frame, np.ndarray):
+                    if isinstance(frame, bytes):
+                        try:
+                            seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop)
+                        except ValueError:                # unsupported or damaged, that file only: PIL has the word
+                            seg = trk.push_bgr(_decode(names[counter]), variant=gray_variant, crop=crop)
+                    elif isinstance(frame, np.ndarray):
                         seg = trk.push_bgr(frame, variant=gray_variant, crop=crop)
                     else:
                         seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop)

@@ -121,9 +121,13 @@ class SegmentTracker:
 
     def push_jpeg(self, jpeg, wait=True, variant=4, crop=None):
         """A frame as `jpeg.read_jpeg` returns it (quantised DCT coefficients): decoded, cropped and turned to gray on
-        the device; the step is the one `push_bgr` makes with the file's decoded pixels."""
+        the device; the step is the one `push_bgr` makes with the file's decoded pixels.  The file's `bytes` instead: the
+        Huffman decoding runs on the device as well (`Context.upload_jpeg_file`)."""
         s = self._next_slot()
-        self.ctx.upload_jpeg(s, jpeg, variant, crop)
+        if isinstance(jpeg, (bytes, bytearray, memoryview)):
+            self.ctx.upload_jpeg_file(s, jpeg, variant, crop)
+        else:
+            self.ctx.upload_jpeg(s, jpeg, variant, crop)
         return self._step(s, wait)
 
     def push_device(self, dev_ptr, stride, wait=True):

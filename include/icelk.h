@@ -426,6 +426,55 @@ int icelk_upload_jpeg(icelk_t* h, int slot, const icelk_jpeg_info_t* info, const
  * single plane (width bytes per row) for 1; stride in bytes. */
 int icelk_jpeg_decode_rgb(icelk_t* h, const icelk_jpeg_info_t* info, const int16_t* coef, uint8_t* out, int stride);
 
+/* ---- Huffman decoding on the device (opt-in) ----------------------------------------------------
+ * The entropy-coded data is cut into subsequences of subseq_bits raw bits, one decoder lane each; lanes that start
+ * out of step fall into step with the true decoder by iterating to a fixed point (self-synchronisation), then every
+ * lane writes the coefficients of its own stretch.  The result equals icelk_jpeg_read_coefficients element for element,
+ * for the same set of files.  The work is bounded: a chain of more than max_hops subsequences in one round, or more than
+ * max_rounds rounds, and the file is decoded by icelk_jpeg_read_coefficients inside the same call; so is a file whose
+ * stream contradicts itself, and then that decoder's verdict (ICELK_EARG, or its coefficients) is the call's. */
+#define ICELK_JPEG_TABLE_BYTES 11328      /* 4 DC + 4 AC tables as the lanes read them */
+#define ICELK_JPEG_FALLBACK_NONE 0
+#define ICELK_JPEG_FALLBACK_BOUND 1       /* the fixed point was not reached within max_hops / max_rounds */
+#define ICELK_JPEG_FALLBACK_STREAM 2      /* the stream contradicts itself: the serial decoder had the last word */
+#define ICELK_JPEG_FALLBACK_SIZE 3        /* a file of 256 MiB or more */
+typedef struct icelk_jpeg_scan {
+    uint32_t segments;                    /* entropy-coded segments: 1, or the restart intervals */
+    uint32_t blocks_per_mcu, blocks_per_segment /* 0: one segment */, total_blocks;
+    uint8_t component[8], dc_table[8], ac_table[8];   /* of every block of an MCU */
+} icelk_jpeg_scan_t;
+typedef struct icelk_jpeg_huff_stats {
+    uint32_t segments, subsequences;
+    uint32_t rounds;                      /* rounds that changed an entry state, the first one included */
+    uint32_t max_hops;                    /* most entry states one chain overwrote in one round */
+    uint32_t lanes_in_step;               /* lanes whose starting guess was the true state */
+    uint32_t spanning_blocks;             /* blocks that begin in one subsequence and end in another */
+    uint32_t fallback;                    /* ICELK_JPEG_FALLBACK_* */
+    uint32_t reserved;
+    uint64_t total_hops;
+} icelk_jpeg_huff_stats_t;
+/* Host only, no handle, re-entrant: headers as icelk_jpeg_describe, then the entropy-coded segments (found with memchr):
+ * seg_begin[s] .. seg_end[s] are the bytes of segment s; the RSTn markers between them must count D0 .. D7 cyclically and
+ * be ceil(MCUs / restart interval) - 1 in number (ICELK_EARG otherwise).  seg_begin / seg_end may be NULL (scan->segments
+ * says how many there are; ICELK_ECAP when seg_capacity is too small); tables: NULL or ICELK_JPEG_TABLE_BYTES bytes. */
+int icelk_jpeg_index(const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info, icelk_jpeg_scan_t* scan, uint32_t* seg_begin,
+                     uint32_t* seg_end, uint64_t seg_capacity, void* tables);
+/* Host only, no handle, re-entrant: icelk_jpeg_read_coefficients by the lanes' algorithm, the same code as the device
+ * runs, phase by phase and lane by lane on the CPU.  subseq_bits: a multiple of 32; stats may be NULL. */
+int icelk_jpeg_read_coefficients_lanes(const uint8_t* data, uint64_t len, int16_t* coef, uint64_t capacity, int subseq_bits,
+                                       int max_hops, int max_rounds, icelk_jpeg_huff_stats_t* stats);
+/* subseq_bits: a multiple of 32, >= 32; max_hops >= 1; 1 <= max_rounds <= 255.  Defaults: 512, 256, 8 (DESIGN.md 7.2 says why). */
+int icelk_jpeg_huff_config(icelk_t* h, int subseq_bits, int max_hops, int max_rounds);
+/* of the file the handle decoded last */
+int icelk_jpeg_huff_stats(icelk_t* h, icelk_jpeg_huff_stats_t* stats);
+/* icelk_upload_jpeg from the file's bytes: the coefficients are decoded on the device and never visit the host. */
+int icelk_upload_jpeg_file(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left, int crop_top,
+                           int crop_right, int crop_bottom);
+/* icelk_jpeg_decode_rgb from the file's bytes. */
+int icelk_jpeg_decode_rgb_file(icelk_t* h, const uint8_t* data, uint64_t len, uint8_t* out, int stride);
+/* The coefficients as the device decodes them, copied back (for tests): coef[0 .. info.coef_count). */
+int icelk_jpeg_device_coefficients(icelk_t* h, const uint8_t* data, uint64_t len, int16_t* coef, uint64_t capacity);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector

@@ -4,6 +4,9 @@
     python tools/jpeg_ingest.py host   [--out profiles/jpeg_ingest_host.txt]      any CPU, no GPU needed
     python tools/jpeg_ingest.py device [--out profiles/jpeg_ingest_device.txt]    MI355X: HIP-event times of the two kernels
     python tools/jpeg_ingest.py e2e [--frames 24] [--threads 16] [--out ...]      MI355X: track_image_sequence, both decoders
+    python tools/jpeg_ingest.py huffman [--out profiles/jpeg_huffman_device.txt]  MI355X: Huffman decoding on the device
+    python tools/jpeg_ingest.py huffman-loop                                      MI355X: the calls for a kernel trace
+    python tools/jpeg_ingest.py e2e-huffman [--frames 24] [--threads 16]          MI355X: huffman="host" against "device"
 
 host    one thread, best of 5: `read_jpeg` (Huffman decoding into coefficients) against `np.array(Image.open(...))` (what
         the "pil" decoder does per photo), and Pillow's own 1/8-scale draft decode -- entropy decoding plus a DC-only
@@ -12,6 +15,12 @@ device  `Context.upload_jpeg` with profiling on: average HIP-event time of k_jpe
         each has to move, and the host-clock time of the whole call (upload of the coefficients included).
 e2e     photos per second of the folder driver with decoder="pil" and decoder="device", same folder, same threads,
         the two alternating.
+huffman `Context.upload_jpeg_file` (Huffman decoding on the device too) at quality 75 and 95: the cost of icelk_jpeg_index
+        on one host thread, then for subsequence lengths 256 .. 4096 the whole call by the host clock (it ends in a
+        synchronise) with rounds, mean and maximum hops, against `read_jpeg` + `upload_jpeg`.
+huffman-loop   20 calls of `upload_jpeg_file` per quality at the default subsequence length and nothing else: run it under
+        `rocprofv3 --kernel-trace --stats --` for the per-kernel times.
+e2e-huffman    the folder driver with decoder="device": huffman="host" against huffman="device", alternating.
 """
 import argparse
 import datetime as dt
@@ -109,7 +118,66 @@ def device(out):
           % call_ms, file=out)
 
 
-def e2e(out, n, threads):
+def mean_ms(f, n=10, warm=2):
+    for _ in range(warm):
+        f()
+    t = time.perf_counter()
+    for _ in range(n):
+        f()
+    return 1e3 * (time.perf_counter() - t) / n
+
+
+def huffman(out):
+    import ctypes as C
+    from iceberg_tracking_code_amd import Context, _lib, read_jpeg
+    lib = _lib.load()
+    files = [(q, k, encode(photo(k), q)) for q in (75, 95) for k in (0, 1)]
+    print("Huffman decoding on the device, %dx%d 4:2:0, procedural texture, two photos per quality" % (W, H), file=out)
+    print("icelk_jpeg_index (headers, memchr for the markers, tables), one host thread, best of 5:", file=out)
+    for q, k, data in files:
+        info, scan = _lib.JpegInfo(), _lib.JpegScan()
+        tables = (C.c_uint8 * _lib.JPEG_TABLE_BYTES)()
+        ms = best_ms(lambda: lib.icelk_jpeg_index(data, len(data), C.byref(info), C.byref(scan), None, None, 0, tables))
+        print("  quality %d photo %d: %.2f MB, %.3f ms (%.1f GB/s)" % (q, k, len(data) / 1e6, ms, len(data) / ms / 1e6), file=out)
+    ctx = Context(W, H, n_slots=2, max_pts=64)
+    try:
+        print("whole call by the host clock, mean of 10, ending in a synchronise:", file=out)
+        print("quality photo  read_jpeg ms  upload_jpeg ms | S: upload_jpeg_file ms, compressed GB/s, lanes, rounds, mean hops, max hops, "
+              "lanes in step, fallback", file=out)
+        for q, k, data in files:
+            j = read_jpeg(data)
+            rd = best_ms(lambda: read_jpeg(data), 3)
+            up = mean_ms(lambda: ctx.upload_jpeg(0, j, 4))
+            ctx.upload_jpeg(0, j, 4)
+            want = ctx.download_level(0, 0)
+            print("%7d %5d  %12.2f  %14.2f" % (q, k, rd, up), file=out)
+            for S in (256, 512, 1024, 2048, 4096):
+                ctx.jpeg_huff_config(S, 256, 255)
+                ms = mean_ms(lambda: ctx.upload_jpeg_file(1, data, 4))
+                st = ctx.jpeg_huff_stats()
+                same = np.array_equal(ctx.download_level(1, 0), want) and np.array_equal(ctx.jpeg_device_coefficients(data), j.coef)
+                print("    S %4d: %7.3f ms  %6.2f GB/s  %6d lanes  %2d rounds  mean %5.2f  max %3d  in step %5d  fallback %d  %s" %
+                      (S, ms, len(data) / ms / 1e6, st["subsequences"], st["rounds"], st["total_hops"] / st["subsequences"],
+                       st["max_hops"], st["lanes_in_step"], st["fallback"], "equal" if same else "DIFFERENT"), file=out)
+                out.flush()
+    finally:
+        ctx.close()
+
+
+def huffman_loop():
+    from iceberg_tracking_code_amd import Context
+    ctx = Context(W, H, n_slots=2, max_pts=64)
+    try:
+        for q in (75, 95):
+            data = encode(photo(), q)
+            for _ in range(20):
+                ctx.upload_jpeg_file(0, data, 4)
+            print("quality %d: %.2f MB, %s" % (q, len(data) / 1e6, ctx.jpeg_huff_stats()))
+    finally:
+        ctx.close()
+
+
+def e2e(out, n, threads, compare="decoder"):
     from iceberg_tracking_code_amd import track_image_sequence
     tmp = tempfile.mkdtemp(prefix="icelk_jpeg_")
     t0 = dt.datetime(2019, 7, 24, 10, 0, 0)
@@ -124,24 +192,28 @@ def e2e(out, n, threads):
     lk = dict(winSize=(21, 21), maxLevel=3, criteria=(3, 30, 0.01))
     print("folder driver, %d photos of %dx%d 4:2:0 quality 90 (%.1f MB each), decode_threads %d, %d usable cores" %
           (n, W, H, size, threads, len(os.sched_getaffinity(0))), file=out)
-    res = {"pil": [], "device": []}
+    # the two sides of the comparison: the decoders, or, with decoder="device", where the Huffman decoding runs
+    word = "decoder" if compare == "decoder" else "huffman"
+    sides = ("pil", "device") if compare == "decoder" else ("host", "device")
+    res = {sides[0]: [], sides[1]: []}
     ref = None
     for rep in range(3):
-        for dec in ("pil", "device"):
+        for side in sides:
+            kw = dict(decoder=side) if compare == "decoder" else dict(decoder="device", huffman=side)
             t = time.perf_counter()
             got = track_image_sequence(names, tmp, 2, 60, feature_params=fp, lk_params=lk, decode_threads=threads,
-                                       decode_ahead=max(6, 2 * threads), save=False, decoder=dec)
-            res[dec].append(n / (time.perf_counter() - t))
+                                       decode_ahead=max(6, 2 * threads), save=False, **kw)
+            res[side].append(n / (time.perf_counter() - t))
             if ref is None:
                 ref = got
             same = len(got) == len(ref) and all(np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) for a, b in zip(got, ref))
             if not same:
-                raise SystemExit("decoder %s: tracks differ from the first run" % dec)
-    for dec in ("pil", "device"):
-        print('decoder="%s": %s photos/s (runs in order)' %
-              (dec, ", ".join("%.1f" % v for v in res[dec])), file=out)
+                raise SystemExit("%s %s: tracks differ from the first run" % (word, side))
+    for side in sides:
+        print('%s="%s": %s photos/s (runs in order)' %
+              (word, side, ", ".join("%.1f" % v for v in res[side])), file=out)
     print("ratio of the best runs: %.2f; %d segments, tracks equal in every run" %
-          (max(res["device"]) / max(res["pil"]), len(ref)), file=out)
+          (max(res[sides[1]]) / max(res[sides[0]]), len(ref)), file=out)
     for p in names:
         os.remove(p)
     os.rmdir(tmp)
@@ -149,18 +221,25 @@ def e2e(out, n, threads):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("host", "device", "e2e"))
+    ap.add_argument("mode", choices=("host", "device", "e2e", "huffman", "huffman-loop", "e2e-huffman"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--threads", type=int, default=16)
     a = ap.parse_args()
-    path = a.out or os.path.join(ROOT, "profiles", "jpeg_ingest_%s.txt" % a.mode)
+    if a.mode == "huffman-loop":
+        return huffman_loop()
+    name = {"huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e"}.get(a.mode, "jpeg_ingest_%s" % a.mode)
+    path = a.out or os.path.join(ROOT, "profiles", name + ".txt")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as out:
         if a.mode == "host":
             host(out)
         elif a.mode == "device":
             device(out)
+        elif a.mode == "huffman":
+            huffman(out)
+        elif a.mode == "e2e-huffman":
+            e2e(out, a.frames, min(a.threads, 16), compare="huffman")
         else:
             e2e(out, a.frames, min(a.threads, 16))
     sys.stdout.write(open(path).read())
