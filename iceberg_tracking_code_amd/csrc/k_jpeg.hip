@@ -14,37 +14,47 @@
 
 namespace icelk {
 
-// 8-point inverse DCT of x[0..7] in place, descaled by `shift` with rounding.  32-bit: an encoder's coefficients times
-// an 8-bit table stay below 2^18 in magnitude, the sums below 2^31.
+// 8-point inverse DCT of x[0..7] in place, descaled by `shift` with rounding.  32 bits are enough for a BLOCK an encoder
+// makes: the forward DCT of 64 8-bit samples, give or take half a quantiser step per coefficient, which is what
+// libjpeg's own analysis of its 32-bit "islow" transform assumes, and there the result equals libjpeg's bit for bit.
+// No bound on the single coefficient says the same: a file may hold any 16-bit value, and +-255 at a table entry of 16
+// (4080, well below 2^18) in every coefficient already carries the row pass's sums past 2^31.  So the products and
+// sums are taken in uint32_t, where they wrap by definition instead of overflowing a signed int, and only the final
+// shift is the arithmetic one of a signed value.  Inside an encoder's range nothing changes; outside it the result is
+// that of two's complement 32-bit arithmetic, which no longer is what libjpeg (or its SIMD paths, which differ from
+// its C code there) makes of the file.
 template <int shift>
-__device__ __forceinline__ void idct8(int (&x)[8])
+__device__ __forceinline__ void idct8(int (&xs)[8])
 {
+    uint32_t x[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) x[k] = (uint32_t)xs[k];
     // even part
-    const int z = (x[2] + x[6]) * 4433;
-    const int e2 = z - x[6] * 15137;
-    const int e3 = z + x[2] * 6270;
-    const int e0 = (x[0] + x[4]) * 8192;
-    const int e1 = (x[0] - x[4]) * 8192;
-    const int a0 = e0 + e3, a3 = e0 - e3, a1 = e1 + e2, a2 = e1 - e2;
+    const uint32_t z = (x[2] + x[6]) * 4433u;
+    const uint32_t e2 = z - x[6] * 15137u;
+    const uint32_t e3 = z + x[2] * 6270u;
+    const uint32_t e0 = (x[0] + x[4]) * 8192u;
+    const uint32_t e1 = (x[0] - x[4]) * 8192u;
+    const uint32_t a0 = e0 + e3, a3 = e0 - e3, a1 = e1 + e2, a2 = e1 - e2;
     // odd part
-    const int z5 = (x[7] + x[3] + x[5] + x[1]) * 9633;
-    const int z3 = z5 - (x[7] + x[3]) * 16069;
-    const int z4 = z5 - (x[5] + x[1]) * 3196;
-    const int z1 = -(x[7] + x[1]) * 7373;
-    const int z2 = -(x[5] + x[3]) * 20995;
-    const int o0 = x[7] * 2446 + z1 + z3;
-    const int o1 = x[5] * 16819 + z2 + z4;
-    const int o2 = x[3] * 25172 + z2 + z3;
-    const int o3 = x[1] * 12299 + z1 + z4;
-    constexpr int half = 1 << (shift - 1);
-    x[0] = (a0 + o3 + half) >> shift;
-    x[7] = (a0 - o3 + half) >> shift;
-    x[1] = (a1 + o2 + half) >> shift;
-    x[6] = (a1 - o2 + half) >> shift;
-    x[2] = (a2 + o1 + half) >> shift;
-    x[5] = (a2 - o1 + half) >> shift;
-    x[3] = (a3 + o0 + half) >> shift;
-    x[4] = (a3 - o0 + half) >> shift;
+    const uint32_t z5 = (x[7] + x[3] + x[5] + x[1]) * 9633u;
+    const uint32_t z3 = z5 - (x[7] + x[3]) * 16069u;
+    const uint32_t z4 = z5 - (x[5] + x[1]) * 3196u;
+    const uint32_t z1 = 0u - (x[7] + x[1]) * 7373u;
+    const uint32_t z2 = 0u - (x[5] + x[3]) * 20995u;
+    const uint32_t o0 = x[7] * 2446u + z1 + z3;
+    const uint32_t o1 = x[5] * 16819u + z2 + z4;
+    const uint32_t o2 = x[3] * 25172u + z2 + z3;
+    const uint32_t o3 = x[1] * 12299u + z1 + z4;
+    constexpr uint32_t half = 1u << (shift - 1);
+    xs[0] = (int)(a0 + o3 + half) >> shift;
+    xs[7] = (int)(a0 - o3 + half) >> shift;
+    xs[1] = (int)(a1 + o2 + half) >> shift;
+    xs[6] = (int)(a1 - o2 + half) >> shift;
+    xs[2] = (int)(a2 + o1 + half) >> shift;
+    xs[5] = (int)(a2 - o1 + half) >> shift;
+    xs[3] = (int)(a3 + o0 + half) >> shift;
+    xs[4] = (int)(a3 - o0 + half) >> shift;
 }
 
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }

@@ -67,6 +67,8 @@ class _Bits:
 
     def restart(self, expect):
         self.n = 0
+        while self.d[self.p] == 0xFF and self.d[self.p + 1] == 0xFF:    # fill bytes in front of the marker (T.81 B.1.1.2)
+            self.p += 1
         if self.d[self.p] != 0xFF or self.d[self.p + 1] != 0xD0 + expect:
             raise ValueError("restart marker missing")
         self.p += 2
