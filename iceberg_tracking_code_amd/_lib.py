@@ -71,6 +71,9 @@ SIGNATURES = {
     "icelk_jpeg_huff_config": (C.c_int, [handle_p, C.c_int, C.c_int, C.c_int]),
     "icelk_jpeg_huff_stats": (C.c_int, [handle_p, jpeg_stats_p]),
     "icelk_upload_jpeg_file": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_upload_jpeg_file_async": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_jpeg_async_poll": (C.c_int, [handle_p, C.c_int, C.POINTER(C.c_int)]),
+    "icelk_jpeg_async_finish": (C.c_int, [handle_p, C.c_int, jpeg_stats_p]),
     "icelk_jpeg_decode_rgb_file": (C.c_int, [handle_p, vp, C.c_uint64, u8p, C.c_int]),
     "icelk_jpeg_device_coefficients": (C.c_int, [handle_p, vp, C.c_uint64, vp, C.c_uint64]),
     "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

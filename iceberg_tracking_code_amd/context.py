@@ -149,6 +149,33 @@ class Context:
         left, top, right, bottom = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
         self._ck_jpeg(self._lib.icelk_upload_jpeg_file(self._h, slot, data, len(data), variant, left, top, right, bottom))
 
+    def upload_jpeg_file_async(self, slot, data, variant=GRAY_CV4, crop=None):
+        """`upload_jpeg_file` ahead of the frame: the host's share and the errors it can see now, every device phase
+        enqueued on a decode stream beside the tracker, no wait (icelk_upload_jpeg_file_async).  `data` is copied by the
+        library and free when the call returns.  The slot holds no usable frame before `jpeg_async_finish(slot)` has
+        returned -- or `jpeg_async_poll(slot)` says 1."""
+        if isinstance(data, bytearray):
+            buf = (C.c_char * len(data)).from_buffer(data)   # as it is: the library takes its own copy
+        else:
+            buf = data = bytes(data)
+        left, top, right, bottom = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
+        self._ck_jpeg(self._lib.icelk_upload_jpeg_file_async(self._h, slot, buf, len(data), variant, left, top, right, bottom))
+
+    def jpeg_async_poll(self, slot):
+        """0: the slot's file is in flight, 1: decoded, 2: the host decoder has to take it (`jpeg_async_finish` does).
+        A look at pinned memory; never blocks."""
+        state = C.c_int(0)
+        self._ck(self._lib.icelk_jpeg_async_poll(self._h, slot, C.byref(state)))
+        return state.value
+
+    def jpeg_async_finish(self, slot):
+        """Waits for the verdict on the slot's file, has the host decoder take it where the device's bounds or the stream
+        ask for that, and returns that file's statistics (the keys of `jpeg_huff_stats`).  Raises as `upload_jpeg_file`
+        does; the slot then holds no frame."""
+        st = _lib.JpegHuffStats()
+        self._ck_jpeg(self._lib.icelk_jpeg_async_finish(self._h, slot, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in st._fields_ if k != "reserved"}
+
     def jpeg_decode_rgb_file(self, data):
         """The decoded image of a JPEG file given as bytes, Huffman decoding included on the device."""
         from .jpeg import describe_jpeg

@@ -93,10 +93,12 @@ static int mark_used(Ctx* c, int slot)
     return ICELK_OK;
 }
 
-static int begin_frame(Ctx* c, int slot, int w, int h)
+int begin_frame(Ctx* c, int slot, int w, int h)
 {
     int rc = check_slot(c, slot, false);
     if (rc) return rc;
+    if (!c->jpeg.slot_job.empty() && c->jpeg.slot_job[slot] >= 0)
+        FAIL(c, ICELK_ESTATE, "the slot's JPEG file is still in flight (icelk_jpeg_async_finish ends it)");
     if (w <= 0 || h <= 0) FAIL(c, ICELK_EARG, "empty image");
     if (w > c->max_w || h > c->max_h) FAIL(c, ICELK_ECAP, "frame larger than max_w x max_h of icelk_create");
     rc = flush_deferred_slot(c, slot);
@@ -171,26 +173,13 @@ static int end_frame(Ctx* c, Slot& s)
 }
 
 // ---- JPEG ingest: coefficients -> planes -> pixels (k_jpeg.hip) ----------------------------------------------------------
-template <typename T>
-static int grow(Ctx* c, T** p, size_t* cap, size_t want)
+// The block rows the pixel box [left, W - right) x [top, H - bottom) needs and the blocks to transform: fills `A` and `out`
+// (planes, chroma mode, box) for the transform and the output kernel, and grows job B's coefficient and plane buffers.
+// The descriptor comes from the caller: nothing in it is trusted beyond what jpeg_info_ok has checked against the image size.
+int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* Ap,
+                    JpegOutArgs* out)
 {
-    if (*cap >= want) return ICELK_OK;
-    if (*p) HIPCHK(c, hipFree(*p));   // waits for everything that may still use the buffer
-    *p = nullptr;
-    *cap = 0;
-    if (int rc = dmalloc(c, p, want)) return rc;
-    *cap = want;
-    return ICELK_OK;
-}
-
-// Uploads the block rows the pixel box [left, W - right) x [top, H - bottom) needs, transforms the blocks it needs and
-// fills `out` (planes, chroma mode, box) for the output kernel.  The descriptor comes from the caller: nothing in it is
-// trusted beyond what jpeg_info_ok has checked against the image size.  on_device: Ctx::jpeg.d_coef holds the file's
-// coefficients already (jpeg_huff_device), nothing is uploaded.
-static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int left, int top, int right, int bottom,
-                       JpegOutArgs* out, bool on_device = false)
-{
-    if (!I || (!coef && !on_device)) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
+    if (!I) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
     if (!jpeg_info_ok(*I)) FAIL(c, ICELK_EARG, "JPEG descriptor does not describe a supported file");
     if (left < 0 || top < 0 || right < 0 || bottom < 0 || (long long)left + right >= I->width ||
         (long long)top + bottom >= I->height)
@@ -204,9 +193,10 @@ static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, 
         plane_off[k] = plane_bytes;
         plane_bytes += (size_t)I->blocks_x[k] * 8 * I->blocks_y[k] * 8;
     }
-    if (int rc = grow(c, &c->jpeg.d_coef, &c->jpeg.coef_cap, (size_t)I->coef_count)) return rc;
-    if (int rc = grow(c, &c->jpeg.d_planes, &c->jpeg.planes_cap, plane_bytes)) return rc;
-    JpegIdctArgs A{};
+    if (int rc = grow(c, &B.d_coef, &B.coef_cap, (size_t)I->coef_count)) return rc;
+    if (int rc = grow(c, &B.d_planes, &B.planes_cap, plane_bytes)) return rc;
+    JpegIdctArgs& A = *Ap;
+    A = JpegIdctArgs{};
     const int x0 = left, x1 = I->width - right - 1, y0 = top, y1 = I->height - bottom - 1;   // first / last pixel kept
     A.first[0] = 0;
     for (int k = 0; k < 3; k++) {
@@ -225,21 +215,12 @@ static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, 
         A.first[k + 1] = A.first[k] + A.nbx[k] * nby;
         A.blocks_x[k] = I->blocks_x[k];
         A.pitch[k] = I->blocks_x[k] * 8;
-        A.coef[k] = c->jpeg.d_coef + I->coef_offset[k];
-        A.plane[k] = c->jpeg.d_planes + plane_off[k];
+        A.coef[k] = B.d_coef + I->coef_offset[k];
+        A.plane[k] = B.d_planes + plane_off[k];
         memcpy(A.quant[k], I->quant[k], sizeof(A.quant[k]));
-        // whole block rows by0 .. by0 + nby - 1: contiguous in the layout
-        const size_t row = (size_t)I->blocks_x[k] * 64, from = I->coef_offset[k] + (size_t)A.by0[k] * row;
-        if (!on_device)
-            HIPCHK(c, hipMemcpyAsync(c->jpeg.d_coef + from, coef + from, row * nby * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
         out->plane[k] = A.plane[k];
         out->pitch[k] = A.pitch[k];
     }
-    {
-        ProfScope p(c, K_JPEG_IDCT);
-        launch_jpeg_idct(c->stream, A);
-    }
-    if (int rc = check_launch(c, "jpeg_idct")) return rc;
     out->W = I->width;
     out->cw = I->comp_w[nc - 1];
     out->ch = I->comp_h[nc - 1];
@@ -249,6 +230,28 @@ static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, 
     out->ow = I->width - left - right;
     out->oh = I->height - top - bottom;
     return ICELK_OK;
+}
+
+// jpeg_plane_args for the synchronous job, then: uploads the block rows the box needs and transforms its blocks on the
+// compute stream.  on_device: the job's d_coef holds the file's coefficients already (jpeg_huff_device), nothing is uploaded.
+static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int left, int top, int right, int bottom,
+                       JpegOutArgs* out, bool on_device = false)
+{
+    if (!I || (!coef && !on_device)) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
+    Ctx::JpegJob& B = c->jpeg.sync;
+    JpegIdctArgs A;
+    if (int rc = jpeg_plane_args(c, B, I, left, top, right, bottom, &A, out)) return rc;
+    for (int k = 0; k < I->ncomp && !on_device; k++) {
+        // whole block rows by0 .. by0 + nby - 1: contiguous in the layout
+        const int nby = (A.first[k + 1] - A.first[k]) / A.nbx[k];
+        const size_t row = (size_t)I->blocks_x[k] * 64, from = I->coef_offset[k] + (size_t)A.by0[k] * row;
+        HIPCHK(c, hipMemcpyAsync(B.d_coef + from, coef + from, row * nby * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    }
+    {
+        ProfScope p(c, K_JPEG_IDCT);
+        launch_jpeg_idct(c->stream, A);
+    }
+    return check_launch(c, "jpeg_idct");
 }
 
 // the planes of jpeg_planes -> the decoded image on the host (the tail of icelk_jpeg_decode_rgb and of its _file form)
@@ -275,7 +278,7 @@ static int jpeg_rgb_out(Ctx* c, const icelk_jpeg_info_t& I, JpegOutArgs& O, uint
     return ICELK_OK;
 }
 
-// ---- JPEG ingest: the file's bytes -> coefficients in Ctx::jpeg.d_coef (k_jpeg_huff.hip) ---------------------------------
+// ---- JPEG ingest: the file's bytes -> coefficients in the synchronous job's d_coef (k_jpeg_huff.hip) ---------------------------------
 // The serial decoder takes the file: when the lanes' work bound was hit, or to have the last word on a stream that
 // contradicts itself.
 static int jpeg_huff_fallback(Ctx* c, const uint8_t* data, uint64_t len, const icelk_jpeg_info_t& I, uint32_t why)
@@ -288,50 +291,41 @@ static int jpeg_huff_fallback(Ctx* c, const uint8_t* data, uint64_t len, const i
         FAIL(c, ICELK_ENOMEM, "no memory for the coefficients");
     }
     if (int rc = jpeg_host_decode(data, (size_t)len, host.data(), I.coef_count)) FAIL(c, rc, "not a JPEG file, or a damaged one");
-    HIPCHK(c, hipMemcpyAsync(c->jpeg.d_coef, host.data(), host.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->jpeg.sync.d_coef, host.data(), host.size() * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ICELK_OK;
 }
 
-static int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info)
+// The buffers of job J for a file of `len` bytes indexed as X (jpeg_index, jpeg_index_lanes), and the kernels' arguments.
+// headroom: what grows with the file's length is taken a quarter larger than this file needs -- growing a buffer frees
+// it, which waits for the whole device, and the photos of a folder all differ a little in length (asynchronous jobs).
+int jpeg_huff_setup(Ctx* c, Ctx::JpegJob& J, const JpegIndex& X, uint64_t len, JpegHuffArgs* Hp, bool headroom)
 {
-    if (!data || !info) FAIL(c, ICELK_EARG, "null JPEG file");
-    Ctx::Jpeg& J = c->jpeg;
-    memset(&J.stats, 0, sizeof(J.stats));
-    JpegIndex X;
-    int rc = jpeg_index(data, (size_t)len, X);
-    if (rc == ICELK_EUNSUP && len >= ((uint64_t)1 << 28)) {
-        rc = icelk_jpeg_describe(data, len, info);
-        if (rc) FAIL(c, rc, "not a JPEG file the decoder takes");
-        if (int r2 = grow(c, &J.d_coef, &J.coef_cap, (size_t)info->coef_count)) return r2;
-        return jpeg_huff_fallback(c, data, len, *info, ICELK_JPEG_FALLBACK_SIZE);
-    }
-    if (rc) FAIL(c, rc, rc == ICELK_EUNSUP ? "a JPEG file of a kind the decoder does not take" : "not a JPEG file, or a damaged one");
-    *info = X.info;
-    jpeg_index_lanes(X, (uint32_t)J.subseq_bits, J.max_hops);
     const lanes::Scan& A = X.scan;
-    JpegHuffArgs H{};
+    auto pad = [&](size_t n) { return headroom ? n + n / 4 : n; };
+    JpegHuffArgs& H = *Hp;
     H.A = A;
     H.ngroups = (A.nlanes + lanes::kGroup - 1) / lanes::kGroup;
     H.ri_mcus = A.seg_blocks ? A.seg_blocks / (uint32_t)A.bpm : (uint32_t)A.nmcu;
     H.cps = (H.ri_mcus + kJpegDcChunk - 1) / kJpegDcChunk;
     if (int r2 = grow(c, &J.d_coef, &J.coef_cap, (size_t)X.info.coef_count)) return r2;
-    if (int r2 = grow(c, &J.d_file, &J.file_cap, (size_t)len)) return r2;
-    if (int r2 = grow(c, &J.d_seg, &J.seg_cap, (size_t)A.nseg + 1)) return r2;
+    if (int r2 = grow(c, &J.d_file, &J.file_cap, pad((size_t)len))) return r2;
+    if (int r2 = grow(c, &J.d_seg, &J.seg_cap, pad((size_t)A.nseg + 1))) return r2;
     if (!J.d_tabs) if (int r2 = dmalloc(c, &J.d_tabs, lanes::kTables)) return r2;
     if (!J.d_ctl) if (int r2 = dmalloc(c, &J.d_ctl, JH_WORDS)) return r2;
     if (J.lane_cap < (size_t)A.nlanes + 1) {
         // the four arrays of the lanes grow together
+        const size_t want = pad((size_t)A.nlanes + 1);
         size_t cap = 0;
-        if (int r2 = grow(c, &J.d_T, &cap, (size_t)A.nlanes + 1)) return r2;
+        if (int r2 = grow(c, &J.d_T, &cap, want)) return r2;
         cap = 0;
-        if (int r2 = grow(c, &J.d_cnt, &cap, (size_t)A.nlanes + 1)) return r2;
+        if (int r2 = grow(c, &J.d_cnt, &cap, want)) return r2;
         cap = 0;
-        if (int r2 = grow(c, &J.d_P, &cap, (size_t)A.nlanes + 1)) return r2;
-        J.lane_cap = (size_t)A.nlanes + 1;
+        if (int r2 = grow(c, &J.d_P, &cap, want)) return r2;
+        J.lane_cap = want;
     }
-    if (int r2 = grow(c, &J.d_X, &J.group_cap, (size_t)2 * H.ngroups)) return r2;
-    if (int r2 = grow(c, &J.d_dc, &J.dc_cap, (size_t)3 * A.nseg * H.cps)) return r2;
+    if (int r2 = grow(c, &J.d_X, &J.group_cap, pad((size_t)2 * H.ngroups))) return r2;
+    if (int r2 = grow(c, &J.d_dc, &J.dc_cap, pad((size_t)3 * A.nseg * H.cps))) return r2;
     H.data = J.d_file;
     H.seg = J.d_seg;
     H.tabs = J.d_tabs;
@@ -342,12 +336,35 @@ static int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpe
     H.ctl = J.d_ctl;
     H.coef = J.d_coef;
     H.dc = J.d_dc;
+    return ICELK_OK;
+}
+
+static int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info)
+{
+    if (!data || !info) FAIL(c, ICELK_EARG, "null JPEG file");
+    Ctx::Jpeg& J = c->jpeg;
+    Ctx::JpegJob& B = J.sync;
+    memset(&J.stats, 0, sizeof(J.stats));
+    JpegIndex X;
+    int rc = jpeg_index(data, (size_t)len, X);
+    if (rc == ICELK_EUNSUP && len >= ((uint64_t)1 << 28)) {
+        rc = icelk_jpeg_describe(data, len, info);
+        if (rc) FAIL(c, rc, "not a JPEG file the decoder takes");
+        if (int r2 = grow(c, &B.d_coef, &B.coef_cap, (size_t)info->coef_count)) return r2;
+        return jpeg_huff_fallback(c, data, len, *info, ICELK_JPEG_FALLBACK_SIZE);
+    }
+    if (rc) FAIL(c, rc, rc == ICELK_EUNSUP ? "a JPEG file of a kind the decoder does not take" : "not a JPEG file, or a damaged one");
+    *info = X.info;
+    jpeg_index_lanes(X, (uint32_t)J.subseq_bits, J.max_hops);
+    const lanes::Scan& A = X.scan;
+    JpegHuffArgs H{};
+    if (int r2 = jpeg_huff_setup(c, B, X, len, &H, false)) return r2;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(J.d_file, data, (size_t)len, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(J.d_seg, X.seg.data(), X.seg.size() * sizeof(lanes::Seg), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(J.d_tabs, X.tabs, sizeof(X.tabs), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(J.d_ctl, 0, JH_WORDS * sizeof(uint32_t), st));
-    HIPCHK(c, hipMemsetAsync(J.d_coef, 0, (size_t)X.info.coef_count * sizeof(int16_t), st));
+    HIPCHK(c, hipMemcpyAsync(B.d_file, data, (size_t)len, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(B.d_seg, X.seg.data(), X.seg.size() * sizeof(lanes::Seg), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(B.d_tabs, X.tabs, sizeof(X.tabs), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(B.d_ctl, 0, JH_WORDS * sizeof(uint32_t), st));
+    HIPCHK(c, hipMemsetAsync(B.d_coef, 0, (size_t)X.info.coef_count * sizeof(int16_t), st));
     J.stats.segments = A.nseg;
     J.stats.subsequences = A.nlanes;
     uint32_t ctl[JH_WORDS];
@@ -362,7 +379,7 @@ static int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpe
             const int r_end = std::min(J.max_rounds, r + 3);
             for (int q = r; q <= r_end; q++) launch_jpeg_huff_sync(st, H, q);
             if (int r2 = check_launch(c, "jpeg_huff_sync")) return r2;
-            HIPCHK(c, hipMemcpyAsync(ctl, J.d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(ctl, B.d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
             HIPCHK(c, hipStreamSynchronize(st));
             bound = ctl[JH_BOUND] != 0;
             for (int q = r; q <= r_end && !settled; q++) settled = ctl[JH_ROUND0 + q] == 0;
@@ -383,7 +400,7 @@ static int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpe
         launch_jpeg_huff_dc(st, H);
     }
     if (int r2 = check_launch(c, "jpeg_huff_write")) return r2;
-    HIPCHK(c, hipMemcpyAsync(ctl, J.d_ctl, JH_ROUND0 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(ctl, B.d_ctl, JH_ROUND0 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     J.stats.lanes_in_step = ctl[JH_IN_STEP];
     J.stats.spanning_blocks = ctl[JH_SPANS];
@@ -587,7 +604,7 @@ int icelk_jpeg_device_coefficients(icelk_t* h, const uint8_t* data, uint64_t len
     int rc = jpeg_huff_device(c, data, len, &I);
     if (rc) return rc;
     if (capacity < I.coef_count) FAIL(c, ICELK_ECAP, "coefficient buffer too small");
-    HIPCHK(c, hipMemcpyAsync(coef, c->jpeg.d_coef, (size_t)I.coef_count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(coef, c->jpeg.sync.d_coef, (size_t)I.coef_count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ICELK_OK;
 }

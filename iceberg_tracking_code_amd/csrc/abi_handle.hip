@@ -162,6 +162,7 @@ static void destroy_ctx(Ctx* c)
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
+    jpeg_async_destroy(c);   // before the slots go: files in flight write into them
     prof_drain(c);
     for (auto& e : c->evt_pool) {
         hipEventDestroy(e.a);
@@ -206,9 +207,11 @@ static void destroy_ctx(Ctx* c)
     void* ptrs[] = {c->d_bgr, c->d_mask, c->d_p0, c->d_p1, c->d_p0r, c->d_err_f, c->d_err_b, c->d_dist, c->d_corners,
                     c->d_st_f, c->d_st_b, c->d_valid, c->dset[0].D.eig, c->d_tracked,
                     c->d_out_tracks, c->d_out_quality, c->post.d_proj, c->post.d_keep, c->post.d_cube_u, c->post.d_cube_v,
-                    c->post.d_cube_count, c->calib.d_shore, c->calib.d_water, c->jpeg.d_coef, c->jpeg.d_planes, c->jpeg.d_rgb,
-                    c->jpeg.d_file, c->jpeg.d_seg, c->jpeg.d_tabs, c->jpeg.d_T, c->jpeg.d_X, c->jpeg.d_cnt, c->jpeg.d_P, c->jpeg.d_ctl,
-                    c->jpeg.d_dc};
+                    c->post.d_cube_count, c->calib.d_shore, c->calib.d_water, c->jpeg.d_rgb};
+    const Ctx::JpegJob& jb = c->jpeg.sync;
+    void* jp[] = {jb.d_coef, jb.d_planes, jb.d_file, jb.d_seg, jb.d_tabs, jb.d_T, jb.d_X, jb.d_cnt, jb.d_P, jb.d_ctl, jb.d_dc};
+    for (void* p : jp)
+        if (p) hipFree(p);
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto& S : c->sb) {
@@ -414,10 +417,11 @@ int icelk_sync(icelk_t* h)
     HIPCHK(c, hipSetDevice(c->device));
     int rcf = flush_deferred(c);   // a pair waiting for a partner counts as issued work
     if (rcf) return rcf;
-    // every stream of the handle: uploads / pyramids built ahead, candidate kernels of a prepared detection
+    // every stream of the handle: uploads / JPEG files decoded ahead / pyramids built ahead, candidate kernels of a prepared detection
     // (icelk_seg_detect_prepare), the min-distance / sort / emit stage, tracker launches
     for (auto q : c->copy_hi)
         if (q) HIPCHK(c, hipStreamSynchronize(q));
+    if (int rcj = jpeg_async_sync(c)) return rcj;
     HIPCHK(c, hipStreamSynchronize(c->pyr_stream));
     HIPCHK(c, hipStreamSynchronize(c->eig_stream));
     HIPCHK(c, hipStreamSynchronize(c->det_stream));

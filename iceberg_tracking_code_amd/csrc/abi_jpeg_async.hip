@@ -1,0 +1,389 @@
+// abi_jpeg_async.hip -- JPEG files decoded ahead of their frame: icelk_upload_jpeg_file_async / _poll / _finish.
+//
+// icelk_upload_jpeg_file (abi_frames.hip) decodes on the compute stream and has the host look at the decoder's flags
+// three times per file, so a photo's decoding never runs beside the tracker step of the photo before it.  Here the same
+// kernels go out in one piece on a decode stream of their own, into a slot the frame loop reaches later:
+//
+//   start    the host's share (index, lanes, the checks of descriptor, crop and slot), the file's bytes into pinned
+//            memory of the job, then H2D copies, rounds 0 .. max_rounds, scan, write, DC, inverse DCT, the output kernel
+//            into the slot's level 0, the verdict kernel (k_jpeg_huff.hip), the slot's events.  No wait.
+//   poll     a look at the job's pinned verdict words.
+//   finish   waits for the verdict.  "Decoded": nothing left to do.  Otherwise the host decoder reads the retained
+//            bytes, its coefficients go into the job's own buffer and the transform and the output kernel run again.
+//
+// What runs on a file that does not settle.  The host cannot stop the chain, so scan, write, DC pass, transform and
+// output kernel run on whatever the rounds left.  That is safe by the construction of jpeg_lanes.h, which is what is
+// relied on here: decode() is total and reads no byte outside its segment; a lane decodes the bits of its own
+// subsequence only, so its loop ends; write_lane clamps its first block to the segment's blocks and every store goes
+// to block_base(g) with g < total_blocks, at a zigzag position < 64; the DC pass and the transform walk the image's
+// blocks, not the stream.  What they leave in the job's buffers and in the slot is garbage that nobody may consume:
+// the slot counts as filled only after finish has returned ICELK_OK, and finish overwrites all of it.
+//
+// Jobs.  Every file in flight owns one Ctx::JpegJob (device buffers as the synchronous calls' job, plus the pinned
+// staging area and the pinned verdict words) from start to finish; the ring grows when every job is in flight and is
+// never sized by the frame maximum.  A job's kernels are through when its verdict has arrived (the verdict kernel is
+// the last of the chain) or finish has synchronised its stream, so a freed job can go out on the other stream at once.
+#include "icelk_ctx.h"
+
+namespace icelk {
+
+static void free_job(Ctx::JpegJob* B)
+{
+    void* p[] = {B->d_coef, B->d_planes, B->d_file, B->d_seg, B->d_tabs, B->d_T, B->d_X, B->d_cnt, B->d_P, B->d_ctl, B->d_dc};
+    for (void* q : p)
+        if (q) hipFree(q);
+    if (B->h_stage) hipHostFree(B->h_stage);
+    if (B->h_verdict) hipHostFree(B->h_verdict);
+    if (B->done) hipEventDestroy(B->done);
+    delete B;
+}
+
+// icelk_destroy: files in flight are waited for, nobody will finish them
+void jpeg_async_destroy(Ctx* c)
+{
+    for (auto& q : c->jpeg.dec)
+        if (q) {
+            hipStreamSynchronize(q);
+            hipStreamDestroy(q);
+            q = nullptr;
+        }
+    for (Ctx::JpegJob* B : c->jpeg.ring) free_job(B);
+    c->jpeg.ring.clear();
+}
+
+// icelk_sync: the decode streams count as streams of the handle; the jobs stay their slots' until finish
+int jpeg_async_sync(Ctx* c)
+{
+    for (auto q : c->jpeg.dec)
+        if (q) HIPCHK(c, hipStreamSynchronize(q));
+    return ICELK_OK;
+}
+
+// a job no slot owns; a new one when all are in flight
+static int take_job(Ctx* c, int* idx)
+{
+    Ctx::Jpeg& J = c->jpeg;
+    for (size_t k = 0; k < J.ring.size(); k++)
+        if (J.ring[k]->slot < 0) return *idx = (int)k, ICELK_OK;
+    Ctx::JpegJob* B = new (std::nothrow) Ctx::JpegJob;
+    if (!B) FAIL(c, ICELK_ENOMEM, "no memory for a JPEG job");
+    if (hipHostMalloc(reinterpret_cast<void**>(&B->h_verdict), JV_WORDS * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
+        hipEventCreateWithFlags(&B->done, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        free_job(B);
+        FAIL(c, ICELK_ENOMEM, "no pinned memory for a JPEG job");
+    }
+    memset(B->h_verdict, 0, JV_WORDS * sizeof(uint32_t));
+    try {
+        J.ring.push_back(B);
+    } catch (...) {
+        free_job(B);
+        FAIL(c, ICELK_ENOMEM, "no memory for a JPEG job");
+    }
+    return *idx = (int)J.ring.size() - 1, ICELK_OK;
+}
+
+// the decode streams, created at the first asynchronous file: two in turn, as Ctx::copy_hi (abi_frames.hip)
+static int decode_stream(Ctx* c, hipStream_t* out)
+{
+    Ctx::Jpeg& J = c->jpeg;
+    const unsigned k = J.dec_seq++ % (unsigned)J.dec_streams;
+    if (!J.dec[k]) {
+        if (J.dec_high) HIPCHK(c, create_priority_stream(&J.dec[k]));
+        else HIPCHK(c, hipStreamCreateWithFlags(&J.dec[k], hipStreamNonBlocking));
+    }
+    *out = J.dec[k];
+    return ICELK_OK;
+}
+
+// inverse DCT and output kernel of job B into its slot's level 0, then the slot's events: the slot is left as
+// icelk_upload_gray_async leaves it
+static int transform_into_slot(Ctx* c, Ctx::JpegJob& B)
+{
+    Slot& s = c->slots[B.slot];
+    {
+        ProfScope p(c, K_JPEG_IDCT, B.st);
+        launch_jpeg_idct(B.st, B.idct);
+    }
+    if (int rc = check_launch(c, "jpeg_idct")) return rc;
+    JpegOutArgs O = B.out;
+    O.dst = s.lv[0].ptr;
+    O.dst_pitch = s.lv[0].pitch;
+    {
+        ProfScope p(c, K_JPEG_OUT, B.st);
+        launch_jpeg_gray(B.st, O, B.variant);
+    }
+    return check_launch(c, "jpeg_out");
+}
+
+static int record_frame(Ctx* c, Ctx::JpegJob& B)
+{
+    Slot& s = c->slots[B.slot];
+    HIPCHK(c, hipEventRecord(s.ready, B.st));
+    HIPCHK(c, hipEventRecord(s.frame_ev, B.st));
+    s.pending = true;
+    s.levels_built = 1;
+    return ICELK_OK;
+}
+
+// the job leaves its slot; `state`: what icelk_jpeg_async_poll keeps answering for the slot
+static void release_job(Ctx* c, Ctx::JpegJob& B, int state)
+{
+    c->jpeg.slot_state[B.slot] = state;
+    c->jpeg.slot_job[B.slot] = -1;
+    B.slot = -1;
+}
+
+static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uint64_t len, JpegIndex& X, int left, int top, int right,
+                     int bottom)
+{
+    Ctx::Jpeg& J = c->jpeg;
+    const bool host_only = B.host_only;
+    if (int rc = jpeg_plane_args(c, B, &B.info, left, top, right, bottom, &B.idct, &B.out)) return rc;
+    // begin_frame's check, taken before anything is allocated for the file
+    if (B.out.ow > c->max_w || B.out.oh > c->max_h) FAIL(c, ICELK_ECAP, "frame larger than max_w x max_h of icelk_create");
+    JpegHuffArgs H{};
+    size_t seg_bytes = 0;
+    if (!host_only) {
+        jpeg_index_lanes(X, (uint32_t)J.subseq_bits, J.max_hops);
+        if (int rc = jpeg_huff_setup(c, B, X, len, &H, true)) return rc;
+        seg_bytes = X.seg.size() * sizeof(lanes::Seg);
+    }
+    // the pinned staging area: tables | segment table | file.  The copies below read it when the stream gets there, and
+    // the host decoder reads the file from it at finish: the caller's buffer is free when this call returns
+    const size_t file_off = (sizeof(X.tabs) + seg_bytes + 255) & ~(size_t)255, want = file_off + (size_t)len;
+    if (B.stage_cap < want) {
+        const size_t take = want + want / 4;   // headroom as jpeg_huff_setup's
+        if (B.h_stage) HIPCHK(c, hipHostFree(B.h_stage));
+        B.h_stage = nullptr;
+        B.stage_cap = 0;
+        if (hipHostMalloc(reinterpret_cast<void**>(&B.h_stage), take, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            FAIL(c, ICELK_ENOMEM, "no pinned memory for the JPEG file");
+        }
+        B.stage_cap = take;
+    }
+    B.file_off = file_off;
+    B.len = len;
+    memcpy(B.h_stage + file_off, data, (size_t)len);
+    if (int rc = decode_stream(c, &B.st)) return rc;
+    // from here on the slot is taken: whatever fails below leaves it without a frame
+    if (int rc = begin_frame(c, slot, B.out.ow, B.out.oh)) return rc;
+    B.slot = slot;
+    Slot& s = c->slots[slot];
+    const hipStream_t st = B.st;
+    // the output kernel must not overtake the launches that still read this slot (as icelk_upload_gray_async)
+    if (int rc = wait_event(c, st, s.used)) return rc;
+    if (s.pending) if (int rc = wait_event(c, st, s.ready)) return rc;
+    if (int rc = wait_event(c, st, s.det_used)) return rc;
+    if (int rc = wait_event(c, st, s.eig_used)) return rc;
+    if (host_only) return ICELK_OK;   // nothing goes out before finish, which has the host decoder take the file
+    memcpy(B.h_stage, X.tabs, sizeof(X.tabs));
+    memcpy(B.h_stage + sizeof(X.tabs), X.seg.data(), seg_bytes);
+    B.segments = X.scan.nseg;
+    B.subsequences = X.scan.nlanes;
+    HIPCHK(c, hipMemcpyAsync(B.d_file, B.h_stage + file_off, (size_t)len, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(B.d_seg, B.h_stage + sizeof(X.tabs), seg_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(B.d_tabs, B.h_stage, sizeof(X.tabs), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(B.d_ctl, 0, JH_WORDS * sizeof(uint32_t), st));
+    HIPCHK(c, hipMemsetAsync(B.d_coef, 0, (size_t)B.info.coef_count * sizeof(int16_t), st));
+    {
+        // every round at once: one that no group takes part in returns after two loads per workgroup
+        ProfScope p(c, K_JPEG_HUFF, st);
+        for (int q = 0; q <= J.max_rounds; q++) launch_jpeg_huff_sync(st, H, q);
+        launch_jpeg_huff_scan(st, H);
+        launch_jpeg_huff_write(st, H);
+        launch_jpeg_huff_dc(st, H);
+    }
+    if (int rc = check_launch(c, "jpeg_huff")) return rc;
+    if (int rc = transform_into_slot(c, B)) return rc;
+    B.seq = (B.seq + 1) & 0x3fffffffu;
+    launch_jpeg_huff_verdict(st, B.d_ctl, J.max_rounds, B.h_verdict, B.seq);
+    if (int rc = check_launch(c, "jpeg_huff_verdict")) return rc;
+    HIPCHK(c, hipEventRecord(B.done, st));
+    return record_frame(c, B);
+}
+
+static inline bool verdict_here(const Ctx::JpegJob& B)
+{
+    return __atomic_load_n(B.h_verdict + JV_SEQ, __ATOMIC_ACQUIRE) == B.seq;
+}
+
+// Waits for the verdict by polling the pinned sequence word, as fetch_counts (abi_detect.hip): the event is looked at
+// now and then, so that a failed launch ends the wait with its error instead of hanging it.
+static int await_verdict(Ctx* c, Ctx::JpegJob& B)
+{
+    for (unsigned it = 1;; it++) {
+        if (verdict_here(B)) return ICELK_OK;
+        if ((it & 4095u) == 0) {
+            const hipError_t q = hipEventQuery(B.done);
+            if (q == hipSuccess) break;
+            if (q != hipErrorNotReady) HIPCHK(c, q);
+            (void)hipGetLastError();
+        }
+        __builtin_ia32_pause();
+    }
+    HIPCHK(c, hipEventSynchronize(B.done));
+    if (!verdict_here(B)) FAIL(c, ICELK_EHIP, "the JPEG verdict did not arrive");
+    return ICELK_OK;
+}
+
+// the serial decoder takes the job's file (from the pinned copy): its coefficients replace the lanes', the transform and
+// the output kernel run again
+static int host_takes_job(Ctx* c, Ctx::JpegJob& B)
+{
+    std::vector<int16_t> host;
+    try {
+        host.resize((size_t)B.info.coef_count);
+    } catch (...) {
+        FAIL(c, ICELK_ENOMEM, "no memory for the coefficients");
+    }
+    if (int rc = jpeg_host_decode(B.h_stage + B.file_off, (size_t)B.len, host.data(), B.info.coef_count))
+        FAIL(c, rc, "not a JPEG file, or a damaged one");
+    HIPCHK(c, hipMemcpyAsync(B.d_coef, host.data(), host.size() * sizeof(int16_t), hipMemcpyHostToDevice, B.st));
+    if (int rc = transform_into_slot(c, B)) return rc;
+    if (int rc = record_frame(c, B)) return rc;
+    HIPCHK(c, hipStreamSynchronize(B.st));   // `host` is free again, and so is everything the job owns
+    return ICELK_OK;
+}
+
+static int job_of(Ctx* c, int slot, Ctx::JpegJob** B)
+{
+    *B = nullptr;
+    if (int rc = check_slot(c, slot, false)) return rc;
+    const Ctx::Jpeg& J = c->jpeg;
+    if (!J.slot_job.empty() && J.slot_job[slot] >= 0) *B = J.ring[J.slot_job[slot]];
+    return ICELK_OK;
+}
+
+}  // namespace icelk
+
+using namespace icelk;
+
+extern "C" {
+
+int icelk_upload_jpeg_file_async(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left,
+                                 int crop_top, int crop_right, int crop_bottom)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    Range rg("icelk upload_jpeg_file_async");
+    if (gray_variant != ICELK_GRAY_CV3 && gray_variant != ICELK_GRAY_CV4) FAIL(c, ICELK_EARG, "bad gray variant");
+    HIPCHK(c, hipSetDevice(c->device));
+    Ctx::JpegJob* old = nullptr;
+    if (int rc = job_of(c, slot, &old)) return rc;
+    if (old) FAIL(c, ICELK_ESTATE, "the slot's JPEG file is still in flight (icelk_jpeg_async_finish ends it)");
+    if (!data) FAIL(c, ICELK_EARG, "null JPEG file");
+    Ctx::Jpeg& J = c->jpeg;
+    JpegIndex* X = new (std::nothrow) JpegIndex;
+    if (!X) FAIL(c, ICELK_ENOMEM, "no memory for the file's index");
+    struct Drop {
+        JpegIndex* p;
+        ~Drop() { delete p; }
+    } drop{X};
+    icelk_jpeg_info_t info;
+    bool host_only = false;
+    int rc = jpeg_index(data, (size_t)len, *X);
+    if (rc == ICELK_EUNSUP && len >= ((uint64_t)1 << 28)) {
+        // the lanes' positions are 32 bits: such a file takes the host decoder at once
+        rc = icelk_jpeg_describe(data, len, &info);
+        if (rc) FAIL(c, rc, "not a JPEG file the decoder takes");
+        host_only = true;
+    } else {
+        if (rc) FAIL(c, rc, rc == ICELK_EUNSUP ? "a JPEG file of a kind the decoder does not take" : "not a JPEG file, or a damaged one");
+        info = X->info;
+    }
+    if (info.ncomp != 3) FAIL(c, ICELK_EARG, "expected a 3-component JPEG file");
+    if (J.slot_job.empty()) {
+        if (const char* e = getenv("ICELK_JPEG_ASYNC_STREAMS")) J.dec_streams = atoi(e) == 1 ? 1 : 2;
+        if (const char* e = getenv("ICELK_JPEG_ASYNC_PRIO")) J.dec_high = !strcmp(e, "high");
+        try {
+            J.slot_job.assign(c->n_slots, -1);
+            J.slot_state.assign(c->n_slots, -1);
+        } catch (...) {
+            J.slot_job.clear();
+            FAIL(c, ICELK_ENOMEM, "no memory for the JPEG jobs");
+        }
+    }
+    int idx = -1;
+    if ((rc = take_job(c, &idx))) return rc;
+    Ctx::JpegJob& B = *J.ring[idx];
+    B.info = info;
+    B.variant = gray_variant;
+    B.host_only = host_only;
+    B.slot = -1;
+    rc = start_job(c, B, slot, data, len, *X, crop_left, crop_top, crop_right, crop_bottom);
+    if (rc) {
+        // what went out before the failure may still use the job's buffers
+        if (B.slot >= 0) hipStreamSynchronize(B.st);
+        B.slot = -1;
+        return rc;
+    }
+    J.slot_job[slot] = idx;
+    J.slot_state[slot] = 0;
+    return ICELK_OK;
+}
+
+int icelk_jpeg_async_poll(icelk_t* h, int slot, int* state)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!state) FAIL(c, ICELK_EARG, "null state");
+    Ctx::JpegJob* B = nullptr;
+    if (int rc = job_of(c, slot, &B)) return rc;
+    if (!B) {
+        if (c->jpeg.slot_state.empty() || c->jpeg.slot_state[slot] < 0) FAIL(c, ICELK_ESTATE, "no JPEG file was started into this slot");
+        *state = c->jpeg.slot_state[slot];
+        return ICELK_OK;
+    }
+    if (B->host_only) *state = 2;
+    else if (!verdict_here(*B)) *state = 0;
+    else *state = B->h_verdict[JV_VERDICT] == JV_DECODED ? 1 : 2;
+    return ICELK_OK;
+}
+
+int icelk_jpeg_async_finish(icelk_t* h, int slot, icelk_jpeg_huff_stats_t* stats)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    Range rg("icelk jpeg_async_finish");
+    HIPCHK(c, hipSetDevice(c->device));
+    Ctx::JpegJob* Bp = nullptr;
+    if (int rc = job_of(c, slot, &Bp)) return rc;
+    if (!Bp) FAIL(c, ICELK_ESTATE, "no JPEG file in flight in this slot");
+    Ctx::JpegJob& B = *Bp;
+    icelk_jpeg_huff_stats_t st;
+    memset(&st, 0, sizeof(st));
+    uint32_t why = ICELK_JPEG_FALLBACK_SIZE;
+    if (!B.host_only) {
+        if (int rc = await_verdict(c, B)) {
+            // a failed launch: nothing of the slot or the job can be relied on
+            hipStreamSynchronize(B.st);
+            c->slots[slot].levels_built = 0;
+            release_job(c, B, 2);
+            return rc;
+        }
+        const uint32_t* v = B.h_verdict;
+        st.segments = B.segments;
+        st.subsequences = B.subsequences;
+        st.rounds = v[JV_ROUNDS];
+        st.max_hops = v[JV_MAX_HOPS];
+        st.total_hops = v[JV_TOTAL_HOPS];
+        st.lanes_in_step = v[JV_IN_STEP];
+        st.spanning_blocks = v[JV_SPANS];
+        why = v[JV_VERDICT] == JV_DECODED ? ICELK_JPEG_FALLBACK_NONE : v[JV_VERDICT];
+    }
+    st.fallback = why;
+    int rc = ICELK_OK;
+    if (why != ICELK_JPEG_FALLBACK_NONE) {
+        rc = host_takes_job(c, B);
+        // after an error the slot holds no frame; what the chain wrote into it is ordered in front of the next upload by
+        // the slot's `ready` event, which stays pending
+        if (rc) c->slots[slot].levels_built = 0;
+    }
+    release_job(c, B, why == ICELK_JPEG_FALLBACK_NONE ? 1 : 2);
+    if (!rc && stats) *stats = st;
+    return rc;
+}
+
+}  // extern "C"

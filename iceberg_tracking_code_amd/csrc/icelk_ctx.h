@@ -76,13 +76,14 @@ struct Ctx {
     uint8_t* d_bgr = nullptr;
     int bgr_pitch = 0;
     bool pyr_per_level = false;            // ICELK_PYR_PER_LEVEL=1: one pyrDown launch per level (A/B, second statement)
-    // JPEG ingest: coefficients, component planes and (icelk_jpeg_decode_rgb only) the decoded image; grown on demand,
-    // because the file may be larger than max_w x max_h (the crop is what has to fit)
-    struct Jpeg {
+    // JPEG ingest.  What ONE file owns while it is decoded: coefficients, component planes, and for the Huffman decoding
+    // on the device (icelk_upload_jpeg_file ...) the file, its segments and tables and the lanes' arrays; grown on demand,
+    // because the file may be larger than max_w x max_h (the crop is what has to fit).  The synchronous calls share one
+    // job; every file of icelk_upload_jpeg_file_async has its own until icelk_jpeg_async_finish (abi_jpeg_async.hip).
+    struct JpegJob {
         int16_t* d_coef = nullptr;
-        uint8_t *d_planes = nullptr, *d_rgb = nullptr;
-        size_t coef_cap = 0, planes_cap = 0, rgb_cap = 0;   // elements / bytes / bytes
-        // Huffman decoding on the device (icelk_upload_jpeg_file ...): the file, its segments and tables, the lanes' arrays
+        uint8_t* d_planes = nullptr;
+        size_t coef_cap = 0, planes_cap = 0;   // elements / bytes
         uint8_t* d_file = nullptr;
         lanes::Seg* d_seg = nullptr;
         lanes::HuffTable* d_tabs = nullptr;
@@ -90,8 +91,36 @@ struct Ctx {
         uint32_t *d_cnt = nullptr, *d_P = nullptr, *d_ctl = nullptr;
         int32_t* d_dc = nullptr;
         size_t file_cap = 0, seg_cap = 0, lane_cap = 0, group_cap = 0, dc_cap = 0;
+        // ---- asynchronous jobs only
+        uint8_t* h_stage = nullptr;      // pinned: tables | segment table | the file's bytes (what the host decoder reads)
+        size_t stage_cap = 0, file_off = 0;
+        uint32_t* h_verdict = nullptr;   // pinned, device-visible: JpegVerdictWord
+        uint32_t seq = 0;                // h_verdict[JV_SEQ] == seq: the verdict of the file in flight has arrived
+        hipEvent_t done = nullptr;       // behind the verdict kernel
+        hipStream_t st = nullptr;        // the decode stream the file went out on
+        int slot = -1;                   // the slot that owns the job, -1: free
+        bool host_only = false;          // nothing was enqueued (a file of 256 MiB or more): the host decoder takes it
+        uint64_t len = 0;
+        int variant = 0;
+        uint32_t segments = 0, subsequences = 0;
+        icelk_jpeg_info_t info{};
+        JpegIdctArgs idct{};             // of the file and its crop: what a second transform after the host decoder runs on
+        JpegOutArgs out{};
+    };
+    struct Jpeg {
+        JpegJob sync;                                          // the working set of every synchronous call
+        uint8_t* d_rgb = nullptr;                              // the decoded image (icelk_jpeg_decode_rgb only)
+        size_t rgb_cap = 0;
         int subseq_bits = 512, max_hops = lanes::kGroup, max_rounds = 8;   // icelk_jpeg_huff_config
-        icelk_jpeg_huff_stats_t stats{};                                     // of the latest file
+        icelk_jpeg_huff_stats_t stats{};                                     // of the latest synchronous file
+        // asynchronous ingest: a small ring of jobs (allocated at first use, grown when all are in flight), which job a
+        // slot owns (-1: none), what icelk_jpeg_async_poll answers for a slot whose job is finished, and the decode streams
+        std::vector<JpegJob*> ring;
+        std::vector<int> slot_job, slot_state;
+        hipStream_t dec[2] = {nullptr, nullptr};
+        unsigned dec_seq = 0;
+        int dec_streams = 2;                                   // ICELK_JPEG_ASYNC_STREAMS=1|2 (A/B)
+        bool dec_high = false;                                 // ICELK_JPEG_ASYNC_PRIO=high|normal
     } jpeg;
 
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
@@ -341,6 +370,18 @@ int dmalloc(Ctx* c, T** p, size_t count)
     return ICELK_OK;
 }
 
+template <typename T>
+int grow(Ctx* c, T** p, size_t* cap, size_t want)
+{
+    if (*cap >= want) return ICELK_OK;
+    if (*p) HIPCHK(c, hipFree(*p));   // waits for everything that may still use the buffer
+    *p = nullptr;
+    *cap = 0;
+    if (int rc = dmalloc(c, p, want)) return rc;
+    *cap = want;
+    return ICELK_OK;
+}
+
 // ---- per-call device buffers, copies and timing of the stages after the frame loop (abi_post.hip, abi_calib.hip)
 struct DevBufs {   // frees whatever was allocated when it goes out of scope; remembers a failed allocation
     std::vector<void*> p;
@@ -400,6 +441,10 @@ int wait_event(Ctx* c, hipStream_t s, hipEvent_t e);
 int wait_slot(Ctx* c, int slot);
 int ensure_pyramid(Ctx* c, int slot, int top_level);
 Pyramid pyramid_of(const Slot& s);
+int begin_frame(Ctx* c, int slot, int w, int h);
+int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* A,
+                    JpegOutArgs* out);
+int jpeg_huff_setup(Ctx* c, Ctx::JpegJob& B, const struct JpegIndex& X, uint64_t len, JpegHuffArgs* H, bool headroom);
 // abi_jpeg.hip
 bool jpeg_info_ok(const icelk_jpeg_info_t& in);
 struct JpegIndex {   // a file as the lanes of jpeg_lanes.h see it
@@ -412,6 +457,9 @@ int jpeg_index(const uint8_t* d, size_t len, JpegIndex& X);
 void jpeg_index_lanes(JpegIndex& X, uint32_t S, int max_hops);
 bool jpeg_huff_config_ok(int subseq_bits, int max_hops, int max_rounds);
 int jpeg_host_decode(const uint8_t* data, size_t len, int16_t* coef, uint64_t capacity);
+// abi_jpeg_async.hip
+void jpeg_async_destroy(Ctx* c);
+int jpeg_async_sync(Ctx* c);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

@@ -152,6 +152,19 @@ void launch_jpeg_huff_sync(hipStream_t s, const JpegHuffArgs& H, int round);
 void launch_jpeg_huff_scan(hipStream_t s, const JpegHuffArgs& H);
 void launch_jpeg_huff_write(hipStream_t s, const JpegHuffArgs& H);
 void launch_jpeg_huff_dc(hipStream_t s, const JpegHuffArgs& H);
+// What k_jpeg_huff_verdict publishes about a file to pinned host words, the sequence word last
+enum JpegVerdictWord {
+    JV_VERDICT = 0,   // JV_DECODED, or the ICELK_JPEG_FALLBACK_* reason the host decoder has to take the file for
+    JV_ROUNDS,
+    JV_MAX_HOPS,
+    JV_TOTAL_HOPS,
+    JV_IN_STEP,
+    JV_SPANS,
+    JV_SEQ = 8,
+    JV_WORDS = 16
+};
+constexpr uint32_t JV_DECODED = 0x100;
+void launch_jpeg_huff_verdict(hipStream_t s, const uint32_t* ctl, int max_rounds, uint32_t* host_words, uint32_t seq);
 
 // LK.  p_in/p_out etc. are device pointers.  fb = fused forward+backward.
 struct LKBuffers {

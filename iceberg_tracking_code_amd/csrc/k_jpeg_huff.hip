@@ -13,6 +13,8 @@
 //                       non-zero coefficients as 2-byte stores, DC as the difference.
 //   k_jpeg_dc_*         the DC differences summed up in scan order inside every restart interval: per-chunk sums, a
 //                       prefix sum of the chunk sums, and the pass that writes the values.
+//   k_jpeg_huff_verdict the asynchronous ingest only (abi_jpeg_async.hip): what the host reads from ctl[] between the
+//                       phases of a synchronous file, worked out at the end of the chain and published to pinned words.
 //
 // Divergence.  Lanes of a wave decode different bits, so they diverge at every symbol by nature; what is kept uniform
 // is everything around it.  The Huffman tables (8 x 1416 B) sit in LDS; a lane's bit window is refilled with one
@@ -228,6 +230,44 @@ __global__ __launch_bounds__(256) void k_jpeg_dc_scan(JpegHuffArgs H)
             __syncthreads();
         }
     }
+}
+
+// ---- the verdict ----------------------------------------------------------------------------------------------------
+// One wave behind everything else of a file that went out without the host looking in between: rounds 0 .. max_rounds,
+// scan, write, DC.  The verdict is the synchronous call's: the host decoder takes the file when a chain hit the work
+// bound or no round in 1 .. max_rounds changed nothing (then the later phases ran on untrue states and what they wrote
+// and counted means nothing), or when the write phase met a stream that contradicts itself.  A round that changed
+// nothing is followed only by such rounds, so the first one is both the fixed point and the count of rounds.
+// Publication as k_publish_counts (abi_detect.hip): plain stores to the pinned words, a system-scope fence, the sequence
+// word last -- the host polls that word and reads the others only behind it.
+__global__ __launch_bounds__(64) void k_jpeg_huff_verdict(const uint32_t* __restrict__ ctl, int max_rounds, uint32_t* __restrict__ out,
+                                                          uint32_t seq)
+{
+    __shared__ uint32_t first_quiet;   // the first round in 1 .. max_rounds that changed nothing, max_rounds + 1: none
+    if (threadIdx.x == 0) first_quiet = (uint32_t)max_rounds + 1u;
+    __syncthreads();
+    for (uint32_t q = 1 + threadIdx.x; q <= (uint32_t)max_rounds; q += blockDim.x)
+        if (ctl[JH_ROUND0 + q] == 0) atomicMin(&first_quiet, q);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const bool settled = first_quiet <= (uint32_t)max_rounds;
+    const bool bound = ctl[JH_BOUND] != 0;
+    uint32_t verdict = JV_DECODED;
+    if (bound || !settled) verdict = ICELK_JPEG_FALLBACK_BOUND;
+    else if (ctl[JH_IRREGULAR]) verdict = ICELK_JPEG_FALLBACK_STREAM;
+    out[JV_VERDICT] = verdict;
+    out[JV_ROUNDS] = first_quiet;   // round 0 and the first_quiet - 1 rounds behind it changed an entry state
+    out[JV_MAX_HOPS] = ctl[JH_MAX_HOPS];
+    out[JV_TOTAL_HOPS] = ctl[JH_TOTAL_HOPS];
+    out[JV_IN_STEP] = ctl[JH_IN_STEP];
+    out[JV_SPANS] = ctl[JH_SPANS];
+    __threadfence_system();
+    __hip_atomic_store(out + JV_SEQ, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+void launch_jpeg_huff_verdict(hipStream_t s, const uint32_t* ctl, int max_rounds, uint32_t* host_words, uint32_t seq)
+{
+    hipLaunchKernelGGL(k_jpeg_huff_verdict, dim3(1), dim3(64), 0, s, ctl, max_rounds, host_words, seq);
 }
 
 void launch_jpeg_huff_sync(hipStream_t s, const JpegHuffArgs& H, int round)

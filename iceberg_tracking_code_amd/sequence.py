@@ -11,7 +11,9 @@ Here: a small thread pool decodes ahead on the host -- the real end-to-end bound
 frame (`Context.upload_bgr(crop=...)`); with `decoder="device"` the pool only Huffman-decodes (`jpeg.read_jpeg`) and
 the device does the inverse DCT, chroma upsampling, colour conversion, crop and gray (`Context.upload_jpeg`), giving
 the same pixels; files the device decoder does not take go through PIL one by one.  With `huffman="device"` on top
-the pool only reads the files and the device Huffman-decodes them as well (`Context.upload_jpeg_file`).  Either way
+the pool only reads the files and the device Huffman-decodes them as well (`Context.upload_jpeg_file`); with
+`pipeline=True` on top of that the files are decoded ahead of their frame, beside the tracker steps of the frames in
+front of them (`SegmentTracker.prefetch_jpeg`).  Either way
 the reference's lossy re-save of the crop has no counterpart and pixel values are those of the original photo; gray conversion, detection,
 tracking, filtering and the track table are the device-resident loop of `SegmentTracker`; the mask is rasterised on
 the device from the polygon (`icelk_set_mask_polygon`) or uploaded.  Output files carry the reference's names and
@@ -70,9 +72,14 @@ def _image_size(path, decoder):
     return first.shape[1], first.shape[0]
 
 
+# frame slots of the pipelined driver: previous and current frame plus the files decoded ahead
+PIPELINE_SLOTS = 6
+
+
 def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startlist=(0,), crop=None, mask=None,
                          mask_polygon=None, feature_params=None, lk_params=None, decode_threads=4, decode_ahead=6,
-                         gray_variant=4, device=0, on_segment=None, save=True, decoder="pil", huffman="host"):
+                         gray_variant=4, device=0, on_segment=None, save=True, decoder="pil", huffman="host", pipeline=False,
+                         n_slots=PIPELINE_SLOTS):
     """Track one day's photos.  Returns [(npz path, tracks (n, T+1, 2) f32, trackquality (n, T) f32)] of the
     segments that pass the time-gap rule, in order.
 
@@ -86,6 +93,9 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                    outputs, supported files and the per-file fallback are listed in INTEGRATION.md
     huffman        with decoder="device": "host" (the pool threads Huffman-decode) or "device" (they only read the file
                    and its headers; the scan is decoded on the device, `Context.upload_jpeg_file`) -- same outputs
+    pipeline       with decoder="device", huffman="device": up to n_slots - 2 files are decoded ahead of their frame on
+                   streams of their own (`SegmentTracker.prefetch_jpeg` / `push_prefetched`) -- same outputs
+    n_slots        frame slots of the pipelined driver, at least 5
     """
     if decoder not in ("pil", "device"):
         raise ValueError('decoder must be "pil" or "device"')
@@ -93,6 +103,10 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
         raise ValueError('huffman must be "host" or "device"')
     if huffman == "device" and decoder != "device":
         raise ValueError('huffman="device" needs decoder="device"')
+    if pipeline and (decoder != "device" or huffman != "device"):
+        raise ValueError('pipeline=True needs decoder="device" and huffman="device"')
+    if pipeline and int(n_slots) < 5:
+        raise ValueError("n_slots must be at least 5")
     imagelist = [str(p) for p in imagelist]
     out = []
     if len(imagelist) <= track_len:                       # s1:267
@@ -114,21 +128,42 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                 # a fresh loop state per start offset (the reference carries the last frame of the previous pass
                 # into the first step of the next one; nothing is saved from that pair, s1:362-363)
                 trk = SegmentTracker(w, h, track_len, feature_params=fp, lk_params=lk, mask=mask,
-                                     mask_polygon=mask_polygon, device=device)
+                                     mask_polygon=mask_polygon, device=device, n_slots=int(n_slots) if pipeline else 3)
                 pending = [pool.submit(load, p) for p in names[:decode_ahead]]
+                fed = 0                                   # pipeline=True: frames handed to the tracker's prefetch queue
                 for counter in range(len(names)):
-                    frame = pending.pop(0).result()
-                    if counter + decode_ahead < len(names):
-                        pending.append(pool.submit(load, names[counter + decode_ahead]))
-                    if isinstance(frame, bytes):
+                    if pipeline:
+                        # previous and current frame stay resident, every other slot holds a frame on its way
+                        while fed < len(names) and fed - counter < trk.n_slots - 2:
+                            frame = pending.pop(0).result()
+                            if fed + decode_ahead < len(names):
+                                pending.append(pool.submit(load, names[fed + decode_ahead]))
+                            if isinstance(frame, bytes):
+                                try:
+                                    trk.prefetch_jpeg(frame, variant=gray_variant, crop=crop)
+                                except ValueError:        # what the host sees of an unsupported or damaged file ...
+                                    trk.prefetch_bgr(_decode(names[fed]), variant=gray_variant, crop=crop)
+                            else:
+                                trk.prefetch_bgr(frame, variant=gray_variant, crop=crop)
+                            fed += 1
                         try:
-                            seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop)
-                        except ValueError:                # unsupported or damaged, that file only: PIL has the word
-                            seg = trk.push_bgr(_decode(names[counter]), variant=gray_variant, crop=crop)
-                    elif isinstance(frame, np.ndarray):
-                        seg = trk.push_bgr(frame, variant=gray_variant, crop=crop)
+                            seg = trk.push_prefetched()
+                        except ValueError:                # ... and what only the decoder sees: PIL has the word
+                            trk.replace_prefetched_bgr(_decode(names[counter]), variant=gray_variant, crop=crop)
+                            seg = trk.push_prefetched()
                     else:
-                        seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop)
+                        frame = pending.pop(0).result()
+                        if counter + decode_ahead < len(names):
+                            pending.append(pool.submit(load, names[counter + decode_ahead]))
+                        if isinstance(frame, bytes):
+                            try:
+                                seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop)
+                            except ValueError:            # unsupported or damaged, that file only: PIL has the word
+                                seg = trk.push_bgr(_decode(names[counter]), variant=gray_variant, crop=crop)
+                        elif isinstance(frame, np.ndarray):
+                            seg = trk.push_bgr(frame, variant=gray_variant, crop=crop)
+                        else:
+                            seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop)
                     if seg is None:
                         continue
                     seg_first, tracks, quality = seg

@@ -76,6 +76,7 @@ class SegmentTracker:
         self.active = False
         self.n_detected = 0
         self._prefetched = []     # slots holding frames whose upload was started ahead of time
+        self._jpeg_jobs = set()   # ... those of them whose JPEG file is still to be finished (`prefetch_jpeg`)
         self.lookahead = bool(lookahead)
         self.pair_launch = bool(pair_launch) and self.lookahead   # see `_step`: joint launch across a segment change
         self._pyr_ahead = set()   # slots whose pyramid was enqueued ahead of their step
@@ -144,19 +145,61 @@ class SegmentTracker:
         """Start the upload of a FUTURE frame from pinned host memory (BASELINE.json configs[2]: hipMemcpyAsync
         double buffering).  Frames are consumed in prefetch order by `push_prefetched`; with n_slots slots at
         most n_slots - 2 uploads may be in flight (previous and current frame stay resident)."""
+        s = self._next_prefetch_slot()
+        self.ctx.upload_gray_async(s, pinned_ptr, self.w, self.h, stride)
+        self._prefetched.append(s)
+
+    def _next_prefetch_slot(self):
         if len(self._prefetched) >= self.n_slots - 2:
             raise RuntimeError("too many frames in flight for %d slots" % self.n_slots)
         last = self._prefetched[-1] if self._prefetched else self.cur
-        s = (last + 1) % self.n_slots
-        self.ctx.upload_gray_async(s, pinned_ptr, self.w, self.h, stride)
+        return (last + 1) % self.n_slots
+
+    def prefetch_jpeg(self, data, variant=4, crop=None):
+        """Start the decoding of a FUTURE frame from the bytes of its JPEG file (`Context.upload_jpeg_file_async`): it
+        runs on the device beside the steps of the frames in front of it.  Slots, order and the n_slots - 2 limit are
+        `prefetch_pinned`'s.  What the host can see of a bad file raises here (ValueError), and no slot is taken; the
+        rest comes out of `push_prefetched`."""
+        s = self._next_prefetch_slot()
+        self.ctx.upload_jpeg_file_async(s, data, variant, crop)
         self._prefetched.append(s)
+        self._jpeg_jobs.add(s)
+
+    def prefetch_bgr(self, frame, variant=4, crop=None):
+        """A host-decoded frame into the next prefetch slot (a plain `upload_bgr`): the file of a folder that the device
+        decoder does not take, between files that it does."""
+        s = self._next_prefetch_slot()
+        self.ctx.upload_bgr(s, frame, variant, crop)
+        self._prefetched.append(s)
+
+    def replace_prefetched_bgr(self, frame, variant=4, crop=None):
+        """After `push_prefetched` has raised for the JPEG file at the head of the queue: fill its slot from the
+        host-decoded frame instead; `push_prefetched` may then be called again."""
+        if not self._prefetched:
+            raise RuntimeError("no prefetched frame")
+        s = self._prefetched[0]
+        if s in self._jpeg_jobs:
+            raise RuntimeError("the frame at the head of the queue has not failed")
+        self.ctx.upload_bgr(s, frame, variant, crop)
 
     def push_prefetched(self, wait=True):
         if not self._prefetched:
             raise RuntimeError("no prefetched frame")
-        s = self._prefetched.pop(0)
+        s = self._prefetched[0]
+        if s in self._jpeg_jobs:
+            # the verdict on the file, the host decoder if it is asked for.  A file that raises leaves the queue as it is
+            # and its slot empty (`replace_prefetched_bgr`)
+            self._jpeg_jobs.discard(s)
+            self.ctx.jpeg_async_finish(s)
+        self._prefetched.pop(0)
         q = self._prefetched
-        return self._step(s, wait, *q[:self.MAX_AHEAD])
+        # nothing is built or detected ahead on a frame whose verdict is still out: the list ends in front of it
+        ahead = []
+        for s_k in q[:self.MAX_AHEAD]:
+            if s_k in self._jpeg_jobs and self.ctx.jpeg_async_poll(s_k) != 1:
+                break
+            ahead.append(s_k)
+        return self._step(s, wait, *ahead)
 
     def push_slot(self, slot, wait=True, *ahead):
         """Use a frame that already sits in `slot` (level 0 resident in HBM); its pyramid is rebuilt.
@@ -333,6 +376,13 @@ class SegmentTracker:
         number of frames consumed so far."""
         self.ctx.seg_flush()
         self.ctx.seg_detect_cancel()
+        for s in sorted(self._jpeg_jobs):
+            # JPEG files in flight are dropped: finished for their working set's sake, whatever they end as
+            try:
+                self.ctx.jpeg_async_finish(s)
+            except ValueError:
+                pass
+        self._jpeg_jobs = set()
         if self._advanced:
             # a joint launch has already tracked the pair into the frame announced for the next step (it sat in its slot):
             # that frame counts as consumed -- it is never a detection frame (track_len >= 2 wherever pairs are joined)

@@ -470,6 +470,29 @@ int icelk_jpeg_huff_stats(icelk_t* h, icelk_jpeg_huff_stats_t* stats);
 /* icelk_upload_jpeg from the file's bytes: the coefficients are decoded on the device and never visit the host. */
 int icelk_upload_jpeg_file(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left, int crop_top,
                            int crop_right, int crop_bottom);
+/* ---- icelk_upload_jpeg_file ahead of the frame (opt-in) ----
+ * Starts the decoding of a file into `slot` and returns without waiting: the host's share is done in the call (the
+ * file's index, the checks of descriptor, crop and slot -- their errors are returned here, with the codes of
+ * icelk_upload_jpeg_file), the bytes are copied into pinned memory of the library (the caller's buffer is free on return)
+ * and every device phase, the verdict on the file included, is enqueued on a decode stream that is not the compute stream,
+ * behind the launches that still read the slot.  The file owns a working set of its own until icelk_jpeg_async_finish
+ * (at 12 MP: ~36 MB of coefficients, 18 MB of planes and the file; the sets are kept and reused).  Between this call
+ * and a finish that returns ICELK_OK the slot holds NO frame the caller may use -- unless icelk_jpeg_async_poll says 1.
+ * ICELK_ESTATE when the slot's previous file has not been finished; every other upload call into such a slot fails the
+ * same way. */
+int icelk_upload_jpeg_file_async(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left,
+                                 int crop_top, int crop_right, int crop_bottom);
+/* Never blocks, no runtime call: *state = 0 the file is in flight, 1 it is decoded (the slot's frame may be used by calls
+ * of this handle: they wait for it on the device), 2 the host decoder has to take it (icelk_jpeg_async_finish does).
+ * After finish the slot keeps answering what its last file ended as.  ICELK_ESTATE for a slot that never had a file. */
+int icelk_jpeg_async_poll(icelk_t* h, int slot, int* state);
+/* Waits for the verdict on the slot's file.  Decoded: ICELK_OK and, if stats is not NULL, the statistics of THIS file
+ * (icelk_jpeg_huff_stats keeps reporting the latest synchronous file).  Work bound hit, not settled or a stream that
+ * contradicts itself: the host decoder reads the library's copy of the bytes, its coefficients are transformed into the
+ * slot, stats->fallback names the reason and the host decoder's verdict is the call's, as in icelk_upload_jpeg_file.
+ * After ICELK_OK the slot is as icelk_upload_gray_async leaves it; after an error it holds no frame and any upload call
+ * may fill it.  Either way the file's working set is free again.  ICELK_ESTATE without a file in flight. */
+int icelk_jpeg_async_finish(icelk_t* h, int slot, icelk_jpeg_huff_stats_t* stats_or_null);
 /* icelk_jpeg_decode_rgb from the file's bytes. */
 int icelk_jpeg_decode_rgb_file(icelk_t* h, const uint8_t* data, uint64_t len, uint8_t* out, int stride);
 /* The coefficients as the device decodes them, copied back (for tests): coef[0 .. info.coef_count). */

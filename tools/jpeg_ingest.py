@@ -7,6 +7,8 @@
     python tools/jpeg_ingest.py huffman [--out profiles/jpeg_huffman_device.txt]  MI355X: Huffman decoding on the device
     python tools/jpeg_ingest.py huffman-loop                                      MI355X: the calls for a kernel trace
     python tools/jpeg_ingest.py e2e-huffman [--frames 24] [--threads 16]          MI355X: huffman="host" against "device"
+    python tools/jpeg_ingest.py e2e-pipeline [--frames 24] [--threads 16]         MI355X: pipeline=False against True
+    python tools/jpeg_ingest.py pipeline-loop [--frames 24]                       MI355X: pipelined runs for a kernel trace
 
 host    one thread, best of 5: `read_jpeg` (Huffman decoding into coefficients) against `np.array(Image.open(...))` (what
         the "pil" decoder does per photo), and Pillow's own 1/8-scale draft decode -- entropy decoding plus a DC-only
@@ -21,6 +23,11 @@ huffman `Context.upload_jpeg_file` (Huffman decoding on the device too) at quali
 huffman-loop   20 calls of `upload_jpeg_file` per quality at the default subsequence length and nothing else: run it under
         `rocprofv3 --kernel-trace --stats --` for the per-kernel times.
 e2e-huffman    the folder driver with decoder="device": huffman="host" against huffman="device", alternating.
+e2e-pipeline   the folder driver with decoder="device", huffman="device": pipeline=False (the yardstick) against
+        pipeline=True, alternating, three runs each behind one untimed run, tracks compared in every run; then
+        pipeline=True over n_slots 5 / 6 / 8, one decode stream against two, normal against high priority
+        (ICELK_JPEG_ASYNC_STREAMS / ICELK_JPEG_ASYNC_PRIO), and where a photo's time goes by the host clock.
+pipeline-loop  one plain and two pipelined runs of the same folder and nothing else, for `rocprofv3 --kernel-trace --stats --`.
 """
 import argparse
 import datetime as dt
@@ -219,16 +226,154 @@ def e2e(out, n, threads, compare="decoder"):
     os.rmdir(tmp)
 
 
+def folder(n):
+    """n photos as the e2e modes use them -> (directory, paths)"""
+    tmp = tempfile.mkdtemp(prefix="icelk_jpeg_")
+    t0 = dt.datetime(2019, 7, 24, 10, 0, 0)
+    names = []
+    for k in range(n):
+        p = os.path.join(tmp, (t0 + dt.timedelta(seconds=60 * k)).strftime("%Y%m%d-%H%M%S") + ".jpg")
+        with open(p, "wb") as f:
+            f.write(encode(photo(k), 90))
+        names.append(p)
+    return tmp, names
+
+
+PIPE_FP = dict(maxCorners=10000, qualityLevel=0.007, minDistance=10, blockSize=10)
+PIPE_LK = dict(winSize=(21, 21), maxLevel=3, criteria=(3, 30, 0.01))
+
+
+def run_folder(names, tmp, threads, **kw):
+    """one run of the folder driver with the device decoder -> (photos/s, segments)"""
+    from iceberg_tracking_code_amd import track_image_sequence
+    t = time.perf_counter()
+    got = track_image_sequence(names, tmp, 2, 60, feature_params=PIPE_FP, lk_params=PIPE_LK, decode_threads=threads,
+                               decode_ahead=max(6, 2 * threads), save=False, decoder="device", huffman="device", **kw)
+    return len(names) / (time.perf_counter() - t), got
+
+
+def same_tracks(got, ref):
+    return len(got) == len(ref) and all(np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) for a, b in zip(got, ref))
+
+
+class Stopwatch:
+    """host-clock time spent inside the named callables of one run (class attributes are wrapped and put back)"""
+
+    def __init__(self, targets):
+        self.targets, self.total, self.calls, self.saved = targets, {}, {}, []
+
+    def __enter__(self):
+        import threading
+        lock = threading.Lock()
+        for label, (owner, attr) in self.targets.items():
+            f = getattr(owner, attr)
+            self.saved.append((owner, attr, f))
+            self.total[label], self.calls[label] = 0.0, 0
+
+            def timed(*a, _f=f, _label=label, **kw):
+                t = time.perf_counter()
+                try:
+                    return _f(*a, **kw)
+                finally:
+                    el = time.perf_counter() - t
+                    with lock:
+                        self.total[_label] += el
+                        self.calls[_label] += 1
+            setattr(owner, attr, timed)
+        return self
+
+    def __exit__(self, *exc):
+        for owner, attr, f in self.saved:
+            setattr(owner, attr, f)
+
+
+def pipeline(out, n, threads):
+    from iceberg_tracking_code_amd import context, sequence, tracker
+    tmp, names = folder(n)
+    size = sum(os.path.getsize(p) for p in names) / n / 1e6
+    print("folder driver, decoder=\"device\", huffman=\"device\": %d photos of %dx%d 4:2:0 quality 90 (%.1f MB each), "
+          "decode_threads %d, %d usable cores" % (n, W, H, size, threads, len(os.sched_getaffinity(0))), file=out)
+    for v in ("ICELK_JPEG_ASYNC_STREAMS", "ICELK_JPEG_ASYNC_PRIO"):
+        os.environ.pop(v, None)
+    _, ref = run_folder(names, tmp, threads)                 # untimed: cold files, code objects, clocks
+    res = {False: [], True: []}
+    for rep in range(3):
+        for pipe in (False, True):
+            rate, got = run_folder(names, tmp, threads, pipeline=pipe)
+            if not same_tracks(got, ref):
+                raise SystemExit("pipeline=%s: tracks differ from the first run" % pipe)
+            res[pipe].append(rate)
+    for pipe in (False, True):
+        print("pipeline=%s: %s photos/s (runs in order)" % (pipe, ", ".join("%.1f" % v for v in res[pipe])), file=out)
+    lo, hi = min(res[False]), max(res[False])
+    print("ratio of the medians: %.2f (of the best runs: %.2f); spread of pipeline=False: %.1f%% of its median; %d segments, "
+          "tracks equal in every run" % (sorted(res[True])[1] / sorted(res[False])[1], max(res[True]) / max(res[False]),
+                                         100 * (hi - lo) / sorted(res[False])[1], len(ref)), file=out)
+    print("pipeline=True by slots, decode streams and their priority (three runs each, in order):", file=out)
+    for prio in ("normal", "high"):
+        for streams in (1, 2):
+            for slots in (5, 6, 8):
+                os.environ["ICELK_JPEG_ASYNC_STREAMS"], os.environ["ICELK_JPEG_ASYNC_PRIO"] = str(streams), prio
+                rates = []
+                for rep in range(3):
+                    rate, got = run_folder(names, tmp, threads, pipeline=True, n_slots=slots)
+                    if not same_tracks(got, ref):
+                        raise SystemExit("n_slots %d, %d streams, %s: tracks differ" % (slots, streams, prio))
+                    rates.append(rate)
+                print("  n_slots %d, %d stream%s, %-6s  %s" % (slots, streams, " " if streams == 1 else "s", prio,
+                                                             ", ".join("%.1f" % v for v in rates)), file=out)
+    for v in ("ICELK_JPEG_ASYNC_STREAMS", "ICELK_JPEG_ASYNC_PRIO"):
+        os.environ.pop(v, None)
+    # where a photo's time goes (defaults).  The file reads run on the pool's threads beside the loop; the other three
+    # are the loop's own thread, one after the other
+    targets = {"file read + headers (pool threads)": (sequence, "_read_bytes"),
+               "start: index, pinned copy, enqueue": (context.Context, "upload_jpeg_file_async"),
+               "finish: wait for the verdict": (context.Context, "jpeg_async_finish"),
+               "tracker step": (tracker.SegmentTracker, "_step")}
+    with Stopwatch(targets) as sw:
+        rate, got = run_folder(names, tmp, threads, pipeline=True)
+    print("one more pipelined run under a stopwatch: %.1f photos/s = %.2f ms per photo, of which by the host clock" %
+          (rate, 1e3 / rate), file=out)
+    for label in targets:
+        print("  %-36s %6.2f ms per photo (%d calls)" % (label, 1e3 * sw.total[label] / n, sw.calls[label]), file=out)
+    targets = {"file read + headers (pool threads)": (sequence, "_read_bytes"),
+               "upload_jpeg_file (decode, 3 host waits)": (context.Context, "upload_jpeg_file"),
+               "tracker step": (tracker.SegmentTracker, "_step")}
+    with Stopwatch(targets) as sw:
+        rate, got = run_folder(names, tmp, threads, pipeline=False)
+    print("and a plain one: %.1f photos/s = %.2f ms per photo" % (rate, 1e3 / rate), file=out)
+    for label in targets:
+        print("  %-36s %6.2f ms per photo (%d calls)" % (label, 1e3 * sw.total[label] / n, sw.calls[label]), file=out)
+    for p in names:
+        os.remove(p)
+    os.rmdir(tmp)
+
+
+def pipeline_loop(n):
+    tmp, names = folder(n)
+    _, ref = run_folder(names, tmp, 16)
+    for rep in range(2):
+        rate, got = run_folder(names, tmp, 16, pipeline=True)
+        print("pipeline=True: %.1f photos/s, tracks %s" % (rate, "equal" if same_tracks(got, ref) else "DIFFER"))
+    for p in names:
+        os.remove(p)
+    os.rmdir(tmp)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("host", "device", "e2e", "huffman", "huffman-loop", "e2e-huffman"))
+    ap.add_argument("mode", choices=("host", "device", "e2e", "huffman", "huffman-loop", "e2e-huffman", "e2e-pipeline",
+                                         "pipeline-loop"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--threads", type=int, default=16)
     a = ap.parse_args()
     if a.mode == "huffman-loop":
         return huffman_loop()
-    name = {"huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e"}.get(a.mode, "jpeg_ingest_%s" % a.mode)
+    if a.mode == "pipeline-loop":
+        return pipeline_loop(a.frames)
+    name = {"huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e", "e2e-pipeline": "jpeg_pipeline_e2e"}.get(
+        a.mode, "jpeg_ingest_%s" % a.mode)
     path = a.out or os.path.join(ROOT, "profiles", name + ".txt")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as out:
@@ -240,6 +385,8 @@ def main():
             huffman(out)
         elif a.mode == "e2e-huffman":
             e2e(out, a.frames, min(a.threads, 16), compare="huffman")
+        elif a.mode == "e2e-pipeline":
+            pipeline(out, a.frames, min(a.threads, 16))
         else:
             e2e(out, a.frames, min(a.threads, 16))
     sys.stdout.write(open(path).read())
