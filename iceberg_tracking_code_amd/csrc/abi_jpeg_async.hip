@@ -16,7 +16,8 @@
 // relied on here: decode() is total and reads no byte outside its segment; a lane decodes the bits of its own
 // subsequence only, so its loop ends; write_lane clamps its first block to the segment's blocks and every store goes
 // to block_base(g) with g < total_blocks, at a zigzag position < 64; the DC pass and the transform walk the image's
-// blocks, not the stream.  What they leave in the job's buffers and in the slot is garbage that nobody may consume:
+// blocks, not the stream (tests/jpeg_lanes_states.cpp runs this order and arbitrary states on the CPU, under the host's
+// sanitizers).  What they leave in the job's buffers and in the slot is garbage that nobody may consume:
 // the slot counts as filled only after finish has returned ICELK_OK, and finish overwrites all of it.
 //
 // Jobs.  Every file in flight owns one Ctx::JpegJob (device buffers as the synchronous calls' job, plus the pinned

@@ -1,8 +1,10 @@
 """GPU: JPEG files decoded ahead of their frame (csrc/abi_jpeg_async.hip, k_jpeg_huff_verdict) against the synchronous
 call on the same bytes under the same `jpeg_huff_config`: one file, several in flight and their working sets reused,
-the caller's buffer, damaged and unsupported files, the tracker fed by `prefetch_jpeg`, the pipelined folder driver.
+the caller's buffer, damaged and unsupported files, the tracker fed by `prefetch_jpeg`, the pipelined folder driver;
+the verdict kernel on the edges of its bounds (the round a file settles in, more than 64 rounds, the longest chain)
+against the CPU statement of the lanes as well, and the calls that may come between a start and its finish.
 Every comparison is exact; which files fall back to the host decoder is never written down here, the synchronous call
-says it."""
+and the CPU statement say it."""
 import datetime as dt
 import io
 import os
@@ -330,3 +332,194 @@ def test_pipelined_folder_equals_the_plain_drivers(synth, tmp_path):
         assert [os.path.basename(p) for p, _, _ in got] == [os.path.basename(p) for p, _, _ in ref], other
         for (_, ta, qa), (_, tb, qb) in zip(got, ref):
             assert ta.shape == tb.shape and np.array_equal(ta, tb) and np.array_equal(qa, qb), other
+
+
+# ---- the edges of the verdict, and the calls between start and finish -------------------------------------------------------
+# No round count, hop count or fallback is written down below: the CPU statement of the lanes (`read_jpeg_lanes` under the
+# same three parameters) and the synchronous call say them, and the asynchronous file has to agree with both.
+GENEROUS = dict(max_hops=256, max_rounds=255)
+
+
+def _bgr_gray(ctx, slot, key, rgb):
+    """what `upload_bgr` makes of a file's Pillow pixels: right without any decoder of this project; once per file"""
+    if key not in _bgr_gray.cache:
+        ctx.upload_bgr(slot, rgb)
+        _bgr_gray.cache[key] = ctx.download_level(slot, 0)
+    return _bgr_gray.cache[key]
+
+
+_bgr_gray.cache = {}
+
+
+def _pillow_of(label):
+    """the decoded pixels of a catalogue stream an 8-bit encoder can make, else None"""
+    return js.pillow(label) if js.stream(label).tier == "pixels" else None
+
+
+def _three_way(ctx, label, data, S, max_hops, max_rounds, rgb=None, slots=(0, 1, 2)):
+    """The file under one configuration by the asynchronous call, the synchronous call and the CPU statement: `fallback`
+    always agrees, every field where nothing fell back, pixels always; against `upload_bgr(rgb)` too where the file's
+    pixels are Pillow's business.  Returns the CPU statement's fallback."""
+    from iceberg_tracking_code_amd import read_jpeg_lanes
+    a, s, b = slots
+    ctx.jpeg_huff_config(S, max_hops, max_rounds)
+    _, cpu = read_jpeg_lanes(data, S, max_hops, max_rounds)
+    want, st_sync = _sync(ctx, s, data)
+    ctx.upload_jpeg_file_async(a, data)
+    st = ctx.jpeg_async_finish(a)
+    got = ctx.download_level(a, 0)
+    what = (label, S, max_hops, max_rounds)
+    print(what, "cpu", cpu, "sync", st_sync, "async", st)
+    assert st["fallback"] == st_sync["fallback"] == cpu["fallback"], (what, st, st_sync, cpu)
+    if cpu["fallback"] == 0:
+        assert st == cpu and st_sync == cpu, (what, st, st_sync, cpu)
+    assert got.shape == want.shape and np.array_equal(got, want), (what, int(np.count_nonzero(got != want)))
+    if rgb is not None:
+        assert np.array_equal(got, _bgr_gray(ctx, b, label, rgb)), what
+    return cpu["fallback"]
+
+
+ROUND_FILES = ("flat black 420 531x397", "out-of-range 1023 q1 420 48x48", "flat black 420 736x736", "big-interval b 444 528x512")
+
+
+def test_round_bound(hctx):
+    """max_rounds one below, at and one above the rounds a file needs: the verdict kernel's `first_quiet <= max_rounds`"""
+    from iceberg_tracking_code_amd import read_jpeg_lanes
+    needs = {}
+    for label in ROUND_FILES:
+        data = js.stream(label).data
+        _, st = read_jpeg_lanes(data, 32, **GENEROUS)
+        R = needs[label] = st["rounds"]
+        assert st["fallback"] == 0 and 2 <= R < 255, (label, st)
+        outcome = {m: _three_way(hctx, label, data, 32, 256, m, _pillow_of(label)) for m in (R - 1, R, R + 1, 255)}
+        assert outcome[R - 1] != 0 and outcome[R] == 0 and outcome[R + 1] == 0 and outcome[255] == 0, (label, R, outcome)
+    print("rounds needed:", needs)
+    assert any(R >= 4 for R in needs.values()) and any(R >= 16 for R in needs.values()), needs
+
+
+def test_more_than_64_rounds():
+    """a black 2112 x 2112 frame: 69 groups of lanes that hand their state on one group per round, so the verdict kernel's
+    64 threads find the first quiet round in the second pass of their loop"""
+    from iceberg_tracking_code_amd import Context, read_jpeg_lanes
+    data = jc.encode(np.zeros((2112, 2112, 3), np.uint8), quality=85, subsampling=2)
+    _, st = read_jpeg_lanes(data, 32, **GENEROUS)
+    R = st["rounds"]
+    print("2112x2112 black: %d bytes, %d lanes, R = %d" % (len(data), st["subsequences"], R))
+    assert st["fallback"] == 0 and 64 < R < 255, st
+    rgb = jc.pil_decode(data)
+    with Context(2112, 2112, n_slots=3, max_pts=1 << 12) as ctx:
+        outcome = {m: _three_way(ctx, "black 2112x2112", data, 32, 256, m, rgb) for m in (R - 1, R, 255)}
+        ctx.sync()
+    assert outcome[R - 1] != 0 and outcome[R] == 0 and outcome[255] == 0, (R, outcome)
+
+
+def test_hop_bound(hctx):
+    """max_hops around the longest chain of a file: the work bound of a chain, `hops >= max_hops`, as the verdict sees it"""
+    from iceberg_tracking_code_amd import read_jpeg_lanes
+    files = [("photo 120x88 420", _photo(2), jc.pil_decode(_photo(2)))]
+    files += [(label, js.stream(label).data, _pillow_of(label)) for label in ("ri-edges ri-uneven", "ri-edges fill-rst")]
+    longest = {}
+    for label, data, rgb in files:
+        _, st = read_jpeg_lanes(data, 32, **GENEROUS)
+        M = longest[label] = st["max_hops"]
+        assert st["fallback"] == 0 and 2 <= M < 255 and 1 < st["rounds"] <= 8, (label, st)
+        outcome = {m: _three_way(hctx, label, data, 32, m, 8, rgb) for m in (M - 1, M, M + 1, M + 2)}
+        assert outcome[M - 1] != 0 and outcome[M] != 0 and outcome[M + 1] == 0 and outcome[M + 2] == 0, (label, M, outcome)
+    print("longest chains:", longest)
+
+
+def _right(ctx, slot, free_slot, label, px, rgb):
+    """the slot holds `px`, which is also what Pillow's pixels give"""
+    got = ctx.download_level(slot, 0)
+    assert got.shape == px.shape and np.array_equal(got, px), label
+    assert np.array_equal(got, _bgr_gray(ctx, free_slot, label, rgb)), label
+
+
+def test_between_start_and_finish():
+    """a configuration change and a synchronous file between the start and the finish of asynchronous ones: every file is
+    decoded under the configuration at its start, in its own working set"""
+    from iceberg_tracking_code_amd import Context
+    c1, c2 = (32, 256, 8), (512, 256, 8)
+    A = ("photo 120x88 420", _photo(2), jc.pil_decode(_photo(2)))
+    B = ("flat black 420 736x736", js.stream("flat black 420 736x736").data, js.pillow("flat black 420 736x736"))
+    Cf = ("big-interval b 444 528x512", js.stream("big-interval b 444 528x512").data, js.pillow("big-interval b 444 528x512"))
+    with Context(1024, 768, n_slots=6, max_pts=1 << 12) as ctx:
+        want = {}
+        for name, f, cfg in (("A1", A, c1), ("B1", B, c1), ("A2", A, c2), ("C2", Cf, c2)):
+            ctx.jpeg_huff_config(*cfg)
+            want[name] = _sync(ctx, 4, f[1])
+        print({name: st["fallback"] for name, (_, st) in want.items()})
+        assert sorted([want["A1"][1]["fallback"] != 0, want["B1"][1]["fallback"] != 0]) == [False, True], want
+        ctx.jpeg_huff_config(*c1)
+        ctx.upload_jpeg_file_async(0, A[1])
+        ctx.upload_jpeg_file_async(2, B[1])
+        ctx.jpeg_huff_config(*c2)
+        ctx.upload_jpeg_file(1, Cf[1])
+        ctx.upload_jpeg_file_async(3, A[1])
+        stats = {k: ctx.jpeg_async_finish(k) for k in (3, 2, 0)}
+        assert ctx.jpeg_huff_stats() == want["C2"][1]
+        for slot, name, f in ((0, "A1", A), (2, "B1", B), (1, "C2", Cf), (3, "A2", A)):
+            _right(ctx, slot, 5, f[0], want[name][0], f[2])
+            if slot != 1:
+                _compare_stats((name, slot), stats[slot], want[name][1])
+        ctx.sync()
+
+
+def test_sync_and_close_with_files_in_flight():
+    from iceberg_tracking_code_amd import Context
+    files = [("photo 120x88 420", _photo(2), jc.pil_decode(_photo(2)))]
+    files += [(label, js.stream(label).data, js.pillow(label)) for label in ("flat black 420 736x736", "ri-1 420 256x256")]
+    with Context(1024, 768, n_slots=6, max_pts=1 << 12) as ctx:
+        ctx.jpeg_huff_config(32)
+        want = [_sync(ctx, 4, data) for _, data, _ in files]
+        for k, (_, data, _) in enumerate(files):
+            ctx.upload_jpeg_file_async(k, data)
+        ctx.sync()
+        states = [ctx.jpeg_async_poll(k) for k in range(3)]       # one look each: the decode streams are the handle's
+        assert all(s in (1, 2) for s in states), states
+        for k, (label, _, rgb) in enumerate(files):
+            st = ctx.jpeg_async_finish(k)
+            assert (states[k] == 1) == (st["fallback"] == 0), (label, states[k], st)
+            _compare_stats(label, st, want[k][1])
+            _right(ctx, k, 5, label, want[k][0], rgb)
+        for k, (_, data, _) in enumerate(files):
+            ctx.upload_jpeg_file_async(k, data)
+        # nobody finishes these: close() waits for them
+    with Context(1024, 768, n_slots=3, max_pts=1 << 12) as ctx:
+        ctx.jpeg_huff_config(32)
+        for label, data, rgb in files:
+            px, _ = _sync(ctx, 1, data)
+            assert np.array_equal(_async_whole(ctx, 0, data), px), label
+            _right(ctx, 0, 2, label, px, rgb)
+        ctx.sync()
+
+
+def test_start_calls_that_fail_late(hctx):
+    """errors that a start call finds after the host's share (index and lanes) is done leave no job owning the slot; with
+    another file in flight beside them"""
+    from iceberg_tracking_code_amd import IcelkError
+    photo, rgb = _photo(2), jc.pil_decode(_photo(2))
+    other, other_rgb = js.stream("ri-1 420 256x256").data, js.pillow("ri-1 420 256x256")
+    good, _ = _sync(hctx, 1, photo)
+    beside, st_beside = _sync(hctx, 1, other)
+    frame = jc.photo(64, 48, 3)
+    hctx.upload_bgr(1, frame)
+    frame_gray = hctx.download_level(1, 0)
+    cases = [("larger than the context", js.stream("big-interval c 420 1056x1024 ri4100").data, None),
+             ("one component", js.stream("big-interval a gray 1032x512").data, None),
+             ("a crop that leaves less than nothing", photo, (70, 0, 60, 0))]
+    hctx.upload_jpeg_file_async(2, other)
+    for label, data, crop in cases:
+        kind_want, want = _outcome(lambda: hctx.upload_jpeg_file(1, data, 4, crop))
+        kind, got = _outcome(lambda: hctx.upload_jpeg_file_async(0, data, 4, crop))
+        print(label, kind_want, want, kind, got)
+        assert kind_want == "raised" and kind == "raised" and got is want, (label, kind, got, kind_want, want)
+        hctx.upload_bgr(0, frame)                                     # no job was left owning the slot
+        assert np.array_equal(hctx.download_level(0, 0), frame_gray), label
+        with pytest.raises(IcelkError, match="-5"):
+            hctx.jpeg_async_finish(0)
+        assert np.array_equal(_async_whole(hctx, 0, photo), good), label
+    st = hctx.jpeg_async_finish(2)
+    _compare_stats("beside", st, st_beside)
+    _right(hctx, 2, 1, "ri-1 420 256x256", beside, other_rgb)
+    _right(hctx, 0, 1, "photo 120x88 420", good, rgb)
