@@ -19,7 +19,8 @@ from .day_grid import utm_to_gridded_utm, utm_to_gridded_utm_days  # noqa: F401
 from .postprocess import (VelocityCube, average_periods, average_spatially_temporally, combine_npzs,  # noqa: F401
                           daily_averages, npz_to_csv, npz_to_mat, save_csv, velocities_to_regular_grid)
 from .calibration import CalibrationResult, ShorelineScene, calibrate, run_calibration  # noqa: F401
-from .jpeg import JpegCoefficients, UnsupportedJpeg, decode_jpeg, read_jpeg, read_jpeg_lanes  # noqa: F401
+from .jpeg import (JpegCoefficients, UnsupportedJpeg, decode_jpeg, read_jpeg, read_jpeg_lanes, resave_coefficients,  # noqa: F401
+                   resave_rgb, resave_tables)
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

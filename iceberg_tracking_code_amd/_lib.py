@@ -76,6 +76,14 @@ SIGNATURES = {
     "icelk_jpeg_async_finish": (C.c_int, [handle_p, C.c_int, jpeg_stats_p]),
     "icelk_jpeg_decode_rgb_file": (C.c_int, [handle_p, vp, C.c_uint64, u8p, C.c_int]),
     "icelk_jpeg_device_coefficients": (C.c_int, [handle_p, vp, C.c_uint64, vp, C.c_uint64]),
+    "icelk_jpeg_resave_tables": (C.c_int, [C.c_int, vp, vp]),
+    "icelk_jpeg_resave_coefficients_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, jpeg_info_p, vp, C.c_uint64]),
+    "icelk_jpeg_resave_divide_host": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, vp]),
+    "icelk_jpeg_resave_rgb": (C.c_int, [handle_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
+    "icelk_jpeg_resave_device_coefficients": (C.c_int, [handle_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_uint64]),
+    "icelk_upload_bgr_resave": (C.c_int, [handle_p, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_upload_jpeg_resave": (C.c_int, [handle_p, C.c_int, jpeg_info_p, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_upload_jpeg_file_resave": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

@@ -103,10 +103,12 @@ class Context:
         a = _gray2d(img)
         self._ck(self._lib.icelk_upload_gray(self._h, slot, _u8(a), a.shape[1], a.shape[0], a.strides[0]))
 
-    def upload_bgr(self, slot, img, variant=GRAY_CV4, crop=None):
+    def upload_bgr(self, slot, img, variant=GRAY_CV4, crop=None, resave=None):
         """3-channel frame -> gray in `slot` (s1:310-311).  `crop` = (left, top, right, bottom) pixels to drop, the
         box `Camera.crop_image` cuts (camtools.py:213-231): only the kept region crosses PCIe, straight out of the
-        decoded frame (the reference's lossy JPEG re-save of the crop, s1:272, has no counterpart)."""
+        decoded frame.  `resave`: None -- pixel values are those of the frame -- or "reference" / a JPEG quality: the
+        reference's lossy re-save of the crop (s1:272) is reproduced on the device, for a frame in R G B order, and the slot
+        holds what `upload_bgr(slot, np.array(Image.open(re-saved crop)), variant)` leaves (icelk_upload_bgr_resave)."""
         a = np.asarray(img)
         if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("expected HxWx3 uint8 image")
@@ -117,13 +119,30 @@ class Context:
             a = a[top:a.shape[0] - bottom, left:a.shape[1] - right]
         if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
             a = np.ascontiguousarray(a)   # rows must be dense; a row pitch (cropped view) is fine as it is
+        quality = self._resave_quality(resave)
+        if quality is not None:
+            self._ck(self._lib.icelk_upload_bgr_resave(self._h, slot, _u8(a), a.shape[1], a.shape[0], a.strides[0], variant, quality))
+            return
         self._ck(self._lib.icelk_upload_bgr(self._h, slot, _u8(a), a.shape[1], a.shape[0], a.strides[0], variant))
 
-    def upload_jpeg(self, slot, jpeg, variant=GRAY_CV4, crop=None):
+    @staticmethod
+    def _resave_quality(resave):
+        if resave is None:
+            return None
+        from .jpeg import resave_quality
+        return resave_quality(resave)
+
+    def upload_jpeg(self, slot, jpeg, variant=GRAY_CV4, crop=None, resave=None):
         """A file read by `jpeg.read_jpeg` -> gray in `slot`, exactly what `upload_bgr(slot, np.array(Image.open(f)),
-        variant, crop)` leaves there: inverse DCT, chroma upsampling, colour conversion, crop and gray run on the device
-        (icelk_upload_jpeg); only the blocks the crop needs are transformed."""
+        variant, crop, resave)` leaves there: inverse DCT, chroma upsampling, colour conversion, crop and gray run on the
+        device (icelk_upload_jpeg); only the blocks the crop needs are transformed.  `resave`: as `upload_bgr`
+        (icelk_upload_jpeg_resave)."""
         left, top, right, bottom = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
+        quality = self._resave_quality(resave)
+        if quality is not None:
+            self._ck(self._lib.icelk_upload_jpeg_resave(self._h, slot, C.byref(jpeg.info), jpeg.coef_ptr, variant, left, top,
+                                                        right, bottom, quality))
+            return
         self._ck(self._lib.icelk_upload_jpeg(self._h, slot, C.byref(jpeg.info), jpeg.coef_ptr, variant, left, top, right,
                                              bottom))
 
@@ -141,12 +160,18 @@ class Context:
             raise UnsupportedJpeg("a JPEG file of a kind the device decoder does not take")
         self._ck(rc)
 
-    def upload_jpeg_file(self, slot, data, variant=GRAY_CV4, crop=None):
-        """The bytes of a JPEG file -> gray in `slot`, as `upload_jpeg(slot, read_jpeg(data), variant, crop)` leaves it:
-        the scan is Huffman-decoded on the device as well (icelk_upload_jpeg_file), the coefficients never visit the
-        host.  The same files are taken as by `read_jpeg`; others raise `UnsupportedJpeg`."""
+    def upload_jpeg_file(self, slot, data, variant=GRAY_CV4, crop=None, resave=None):
+        """The bytes of a JPEG file -> gray in `slot`, as `upload_jpeg(slot, read_jpeg(data), variant, crop, resave)`
+        leaves it: the scan is Huffman-decoded on the device as well (icelk_upload_jpeg_file), the coefficients never
+        visit the host.  The same files are taken as by `read_jpeg`; others raise `UnsupportedJpeg`.  `resave`: as
+        `upload_bgr` (icelk_upload_jpeg_file_resave)."""
         data = bytes(data)
         left, top, right, bottom = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
+        quality = self._resave_quality(resave)
+        if quality is not None:
+            self._ck_jpeg(self._lib.icelk_upload_jpeg_file_resave(self._h, slot, data, len(data), variant, left, top, right,
+                                                                  bottom, quality))
+            return
         self._ck_jpeg(self._lib.icelk_upload_jpeg_file(self._h, slot, data, len(data), variant, left, top, right, bottom))
 
     def upload_jpeg_file_async(self, slot, data, variant=GRAY_CV4, crop=None):
@@ -184,6 +209,26 @@ class Context:
         out = np.empty((i.height, i.width, 3) if i.ncomp == 3 else (i.height, i.width), np.uint8)
         self._ck_jpeg(self._lib.icelk_jpeg_decode_rgb_file(self._h, data, len(data), _u8(out), out.strides[0]))
         return out
+
+    def jpeg_resave_rgb(self, rgb, quality=75):
+        """H x W x 3 (R G B) uint8 -> the pixels of the image saved as JPEG at `quality` and opened again (`jpeg.resave_rgb`)."""
+        a = np.asarray(rgb)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("expected HxWx3 uint8 image")
+        a = np.ascontiguousarray(a)
+        out = np.empty(a.shape, np.uint8)
+        self._ck(self._lib.icelk_jpeg_resave_rgb(self._h, _u8(a), a.shape[1], a.shape[0], a.strides[0], int(quality), _u8(out),
+                                                 out.strides[0]))
+        return out
+
+    def jpeg_resave_device_coefficients(self, rgb, quality=75):
+        """The coefficients `jpeg.resave_coefficients(rgb, quality).coef` as the device's forward kernel makes them, for tests."""
+        from .jpeg import resave_coefficients
+        a = np.ascontiguousarray(rgb)
+        coef = np.empty(resave_coefficients(a, quality).coef.size, np.int16)
+        self._ck(self._lib.icelk_jpeg_resave_device_coefficients(self._h, _u8(a), a.shape[1], a.shape[0], a.strides[0], int(quality),
+                                                                 C.c_void_p(coef.ctypes.data), coef.size))
+        return coef
 
     def jpeg_device_coefficients(self, data):
         """The quantised DCT coefficients of a JPEG file as the device decodes them (`read_jpeg(data).coef`), for tests."""

@@ -164,7 +164,7 @@ Pyramid pyramid_of(const Slot& s)
 }
 
 // the counterpart of begin_frame for the ingest paths of the compute stream: level 0 of the slot is written (enqueued)
-static int end_frame(Ctx* c, Slot& s)
+int end_frame(Ctx* c, Slot& s)
 {
     HIPCHK(c, hipEventRecord(s.frame_ev, c->stream));
     s.levels_built = 1;
@@ -234,8 +234,8 @@ int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int lef
 
 // jpeg_plane_args for the synchronous job, then: uploads the block rows the box needs and transforms its blocks on the
 // compute stream.  on_device: the job's d_coef holds the file's coefficients already (jpeg_huff_device), nothing is uploaded.
-static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int left, int top, int right, int bottom,
-                       JpegOutArgs* out, bool on_device = false)
+int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int left, int top, int right, int bottom, JpegOutArgs* out,
+                bool on_device)
 {
     if (!I || (!coef && !on_device)) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
     Ctx::JpegJob& B = c->jpeg.sync;
@@ -255,7 +255,7 @@ static int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, 
 }
 
 // the planes of jpeg_planes -> the decoded image on the host (the tail of icelk_jpeg_decode_rgb and of its _file form)
-static int jpeg_rgb_out(Ctx* c, const icelk_jpeg_info_t& I, JpegOutArgs& O, uint8_t* out, int stride)
+int jpeg_rgb_out(Ctx* c, const icelk_jpeg_info_t& I, JpegOutArgs& O, uint8_t* out, int stride)
 {
     const size_t row = (size_t)O.ow * I.ncomp;
     if (stride < 0 || (size_t)stride < row) FAIL(c, ICELK_EARG, "stride smaller than a row of the image");
@@ -339,7 +339,7 @@ int jpeg_huff_setup(Ctx* c, Ctx::JpegJob& J, const JpegIndex& X, uint64_t len, J
     return ICELK_OK;
 }
 
-static int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info)
+int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info)
 {
     if (!data || !info) FAIL(c, ICELK_EARG, "null JPEG file");
     Ctx::Jpeg& J = c->jpeg;

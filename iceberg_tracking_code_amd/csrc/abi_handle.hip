@@ -9,7 +9,7 @@ namespace icelk {
 
 static const char* kKernelNames[K_COUNT_] = {
     "bgr2gray", "pyrdown", "lk", "lk_fb", "corner_candidates", "min_distance", "sort_emit",
-    "project_tracks", "synth", "lk_fb_pair", "jpeg_idct", "jpeg_out", "jpeg_huff",
+    "project_tracks", "synth", "lk_fb_pair", "jpeg_idct", "jpeg_out", "jpeg_huff", "jpeg_fwd",
 };
 
 std::string g_create_err;
@@ -163,6 +163,7 @@ static void destroy_ctx(Ctx* c)
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     jpeg_async_destroy(c);   // before the slots go: files in flight write into them
+    jpeg_resave_destroy(c);
     prof_drain(c);
     for (auto& e : c->evt_pool) {
         hipEventDestroy(e.a);

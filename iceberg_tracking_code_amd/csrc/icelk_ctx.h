@@ -109,6 +109,11 @@ struct Ctx {
     };
     struct Jpeg {
         JpegJob sync;                                          // the working set of every synchronous call
+        // the re-save (abi_jpeg_resave.hip), allocated at first use: the cropped R G B image the forward kernel reads
+        // (rows 3 * width bytes apart), and the coefficients and planes of the re-saved file
+        JpegJob resave;
+        uint8_t* d_src = nullptr;
+        size_t src_cap = 0;
         uint8_t* d_rgb = nullptr;                              // the decoded image (icelk_jpeg_decode_rgb only)
         size_t rgb_cap = 0;
         int subseq_bits = 512, max_hops = lanes::kGroup, max_rounds = 8;   // icelk_jpeg_huff_config
@@ -445,6 +450,11 @@ int begin_frame(Ctx* c, int slot, int w, int h);
 int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* A,
                     JpegOutArgs* out);
 int jpeg_huff_setup(Ctx* c, Ctx::JpegJob& B, const struct JpegIndex& X, uint64_t len, JpegHuffArgs* H, bool headroom);
+int end_frame(Ctx* c, Slot& s);
+int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int left, int top, int right, int bottom, JpegOutArgs* out,
+                bool on_device = false);
+int jpeg_rgb_out(Ctx* c, const icelk_jpeg_info_t& I, JpegOutArgs& O, uint8_t* out, int stride);
+int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info);
 // abi_jpeg.hip
 bool jpeg_info_ok(const icelk_jpeg_info_t& in);
 struct JpegIndex {   // a file as the lanes of jpeg_lanes.h see it
@@ -457,6 +467,8 @@ int jpeg_index(const uint8_t* d, size_t len, JpegIndex& X);
 void jpeg_index_lanes(JpegIndex& X, uint32_t S, int max_hops);
 bool jpeg_huff_config_ok(int subseq_bits, int max_hops, int max_rounds);
 int jpeg_host_decode(const uint8_t* data, size_t len, int16_t* coef, uint64_t capacity);
+// abi_jpeg_resave.hip
+void jpeg_resave_destroy(Ctx* c);
 // abi_jpeg_async.hip
 void jpeg_async_destroy(Ctx* c);
 int jpeg_async_sync(Ctx* c);

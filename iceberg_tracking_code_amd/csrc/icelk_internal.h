@@ -59,6 +59,7 @@ enum KernelId {
     K_JPEG_IDCT,    // dequantise + inverse DCT (k_jpeg.hip)
     K_JPEG_OUT,     // upsample + colour + crop + gray / RGB
     K_JPEG_HUFF,    // Huffman decoding: synchronise, scan, write, DC (k_jpeg_huff.hip)
+    K_JPEG_FWD,     // the re-save's forward half: colour, downsampling, forward DCT, quantisation (k_jpeg_fwd.hip)
     K_COUNT_
 };
 
@@ -119,6 +120,19 @@ struct JpegOutArgs {
 void launch_jpeg_idct(hipStream_t s, const JpegIdctArgs& A);
 void launch_jpeg_gray(hipStream_t s, JpegOutArgs A, int variant);
 void launch_jpeg_rgb(hipStream_t s, JpegOutArgs A);
+
+// The forward half of the re-save (k_jpeg_fwd.hip; the arithmetic is jpeg_fwd.h): interleaved R G B -> quantised
+// coefficients of a 4:2:0 file in the layout of icelk_jpeg_info_t.  By-value kernel arguments.
+struct JpegFwdArgs {
+    const uint8_t* rgb;       // device: h rows of w pixels, 3 bytes each, `pitch` bytes apart
+    int pitch, w, h;
+    int16_t* coef[3];         // device: the components' blocks, 16-byte aligned
+    int mcus_x, mcus_y;       // luma has 2 mcus_x x 2 mcus_y blocks, chroma mcus_x x mcus_y
+    int real_bx, real_by;     // luma blocks that hold samples: ceil(w / 8), ceil(h / 8); the others are dummies
+    uint16_t quant[2][64];    // luma, chroma
+    uint32_t recip[2][64];    // fwd::reciprocal(8 * quant)
+};
+void launch_jpeg_fwd(hipStream_t s, const JpegFwdArgs& A);
 
 // Huffman decoding on the device (k_jpeg_huff.hip; the algorithm is jpeg_lanes.h).  All pointers are device memory.
 constexpr int kJpegMaxRounds = 255;

@@ -6,6 +6,11 @@ dequantises, inverse-transforms, upsamples chroma and converts colour (csrc/k_jp
 cropped gray frame (`Context.upload_jpeg`, `SegmentTracker.push_jpeg`) or back to the host as pixels (`decode_jpeg`).
 Pixels equal Pillow's (libjpeg's default decoder) bit for bit.
 
+The reference's lossy re-save of the crop (s1:272: every photo is cropped with Pillow and saved again as JPEG, and the
+loop tracks on those files) without the file: `resave_tables`, `resave_coefficients` (host) and `resave_rgb` (device)
+give the tables, coefficients and pixels of `Image.fromarray(rgb).save(f, "JPEG", quality=...)`, bit for bit; the
+uploads take it as `resave=` (`Context.upload_bgr` ...).
+
 Taken: baseline (SOF0), 8 bit, Huffman coded, one interleaved scan, gray or YCbCr with 4:4:4 / 4:2:2 / 4:2:0 sampling,
 restart markers, width >= 3.  Every other valid file raises `UnsupportedJpeg` -- the caller decodes it another way.
 """
@@ -131,3 +136,61 @@ def decode_jpeg(data, ctx=None, huffman="host"):
         from .api import default_context
         ctx = default_context(j.width, j.height)
     return ctx.jpeg_decode_rgb(j)
+
+
+# ---- the reference's re-save of the crop -----------------------------------------------------------------------------
+REFERENCE_RESAVE_QUALITY = 75   # Pillow's default: `img_crop.save(outpath)` names none (camtools.py:64-104)
+
+
+def resave_quality(resave):
+    """The `resave=` keyword of the uploads and drivers -> a JPEG quality, or None for no re-save: None, "reference"
+    (Pillow's default, 75, what the reference's crop pool writes) or an int in 1 .. 100."""
+    if resave is None:
+        return None
+    if resave == "reference":
+        return REFERENCE_RESAVE_QUALITY
+    if isinstance(resave, (bool, str)) or int(resave) != resave or not 1 <= int(resave) <= 100:
+        raise ValueError('resave must be None, "reference" or a JPEG quality in 1 .. 100')
+    return int(resave)
+
+
+def _rgb3(rgb):
+    a = np.asarray(rgb)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("expected HxWx3 uint8 image")
+    if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def resave_tables(quality=75):
+    """(luma, chroma): the 8 x 8 uint16 quantisation tables, natural order, of the file Pillow writes at `quality`."""
+    quality = resave_quality(quality)
+    luma, chroma = np.empty((8, 8), np.uint16), np.empty((8, 8), np.uint16)
+    _check(_lib.load().icelk_jpeg_resave_tables(quality, C.c_void_p(luma.ctypes.data), C.c_void_p(chroma.ctypes.data)),
+           "icelk_jpeg_resave_tables")
+    return luma, chroma
+
+
+def resave_coefficients(rgb, quality=75):
+    """H x W x 3 (R G B) uint8 -> what `read_jpeg` returns for the file `Image.fromarray(rgb).save(f, "JPEG",
+    quality=quality)` writes, computed on the host without writing it (csrc/jpeg_fwd.h): a JpegCoefficients that
+    `Context.upload_jpeg` and `decode_jpeg` take as they take a file's."""
+    a, quality = _rgb3(rgb), resave_quality(quality)
+    lib = _lib.load()
+    info = _lib.JpegInfo()
+    args = (a.ctypes.data_as(_lib.u8p), a.shape[1], a.shape[0], a.strides[0], quality, C.byref(info))
+    _check(lib.icelk_jpeg_resave_coefficients_host(*args, None, 0), "icelk_jpeg_resave_coefficients_host")
+    coef = np.empty(int(info.coef_count), np.int16)
+    _check(lib.icelk_jpeg_resave_coefficients_host(*args, C.c_void_p(coef.ctypes.data), coef.size), "icelk_jpeg_resave_coefficients_host")
+    return JpegCoefficients(info, coef)
+
+
+def resave_rgb(rgb, quality=75, ctx=None):
+    """H x W x 3 (R G B) uint8 -> the pixels np.array(Image.open(f)) gives after `Image.fromarray(rgb).save(f, "JPEG",
+    quality=quality)`, computed on the device (csrc/k_jpeg_fwd.hip, then the decoder's kernels).  `ctx`: as `decode_jpeg`."""
+    a, quality = _rgb3(rgb), resave_quality(quality)
+    if ctx is None:
+        from .api import default_context
+        ctx = default_context(a.shape[1], a.shape[0])
+    return ctx.jpeg_resave_rgb(a, quality)

@@ -14,7 +14,8 @@ the same pixels; files the device decoder does not take go through PIL one by on
 the pool only reads the files and the device Huffman-decodes them as well (`Context.upload_jpeg_file`); with
 `pipeline=True` on top of that the files are decoded ahead of their frame, beside the tracker steps of the frames in
 front of them (`SegmentTracker.prefetch_jpeg`).  Either way
-the reference's lossy re-save of the crop has no counterpart and pixel values are those of the original photo; gray conversion, detection,
+pixel values are those of the original photo unless `resave` asks for the reference's lossy re-save of the crop, which
+then runs on the device between crop and gray conversion (csrc/k_jpeg_fwd.hip; not with `pipeline=True`); gray conversion, detection,
 tracking, filtering and the track table are the device-resident loop of `SegmentTracker`; the mask is rasterised on
 the device from the polygon (`icelk_set_mask_polygon`) or uploaded.  Output files carry the reference's names and
 arrays.
@@ -79,7 +80,7 @@ PIPELINE_SLOTS = 6
 def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startlist=(0,), crop=None, mask=None,
                          mask_polygon=None, feature_params=None, lk_params=None, decode_threads=4, decode_ahead=6,
                          gray_variant=4, device=0, on_segment=None, save=True, decoder="pil", huffman="host", pipeline=False,
-                         n_slots=PIPELINE_SLOTS):
+                         n_slots=PIPELINE_SLOTS, resave=None):
     """Track one day's photos.  Returns [(npz path, tracks (n, T+1, 2) f32, trackquality (n, T) f32)] of the
     segments that pass the time-gap rule, in order.
 
@@ -96,6 +97,10 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
     pipeline       with decoder="device", huffman="device": up to n_slots - 2 files are decoded ahead of their frame on
                    streams of their own (`SegmentTracker.prefetch_jpeg` / `push_prefetched`) -- same outputs
     n_slots        frame slots of the pipelined driver, at least 5
+    resave         None: pixel values are those of the photos.  "reference": the tracker sees what the reference's tracker
+                   sees, the crop saved by Pillow as a new JPEG (quality 75, s1:272) and opened again -- reproduced on the
+                   device, no file is written; an int: that quality.  Not with pipeline=True.  A file the device decoder
+                   does not take goes through PIL, that file only, and is re-saved on the device all the same
     """
     if decoder not in ("pil", "device"):
         raise ValueError('decoder must be "pil" or "device"')
@@ -105,6 +110,10 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
         raise ValueError('huffman="device" needs decoder="device"')
     if pipeline and (decoder != "device" or huffman != "device"):
         raise ValueError('pipeline=True needs decoder="device" and huffman="device"')
+    from .jpeg import resave_quality
+    resave = resave_quality(resave)
+    if pipeline and resave is not None:
+        raise ValueError("resave is not available with pipeline=True")
     if pipeline and int(n_slots) < 5:
         raise ValueError("n_slots must be at least 5")
     imagelist = [str(p) for p in imagelist]
@@ -157,13 +166,13 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                             pending.append(pool.submit(load, names[counter + decode_ahead]))
                         if isinstance(frame, bytes):
                             try:
-                                seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop)
+                                seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop, resave=resave)
                             except ValueError:            # unsupported or damaged, that file only: PIL has the word
-                                seg = trk.push_bgr(_decode(names[counter]), variant=gray_variant, crop=crop)
+                                seg = trk.push_bgr(_decode(names[counter]), variant=gray_variant, crop=crop, resave=resave)
                         elif isinstance(frame, np.ndarray):
-                            seg = trk.push_bgr(frame, variant=gray_variant, crop=crop)
+                            seg = trk.push_bgr(frame, variant=gray_variant, crop=crop, resave=resave)
                         else:
-                            seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop)
+                            seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop, resave=resave)
                     if seg is None:
                         continue
                     seg_first, tracks, quality = seg

@@ -114,21 +114,23 @@ class SegmentTracker:
         self.ctx.upload_gray(s, frame_gray)
         return self._step(s, wait)
 
-    def push_bgr(self, frame, wait=True, variant=4, crop=None):
-        """`crop` = (left, top, right, bottom): the box of camtools.py:213-231, cut during the upload."""
+    def push_bgr(self, frame, wait=True, variant=4, crop=None, resave=None):
+        """`crop` = (left, top, right, bottom): the box of camtools.py:213-231, cut during the upload.  `resave`: None,
+        "reference" or a JPEG quality -- the reference's lossy re-save of the crop, reproduced on the device
+        (`Context.upload_bgr`)."""
         s = self._next_slot()
-        self.ctx.upload_bgr(s, frame, variant, crop)
+        self.ctx.upload_bgr(s, frame, variant, crop, resave)
         return self._step(s, wait)
 
-    def push_jpeg(self, jpeg, wait=True, variant=4, crop=None):
+    def push_jpeg(self, jpeg, wait=True, variant=4, crop=None, resave=None):
         """A frame as `jpeg.read_jpeg` returns it (quantised DCT coefficients): decoded, cropped and turned to gray on
         the device; the step is the one `push_bgr` makes with the file's decoded pixels.  The file's `bytes` instead: the
-        Huffman decoding runs on the device as well (`Context.upload_jpeg_file`)."""
+        Huffman decoding runs on the device as well (`Context.upload_jpeg_file`).  `resave`: as `push_bgr`."""
         s = self._next_slot()
         if isinstance(jpeg, (bytes, bytearray, memoryview)):
-            self.ctx.upload_jpeg_file(s, jpeg, variant, crop)
+            self.ctx.upload_jpeg_file(s, jpeg, variant, crop, resave)
         else:
-            self.ctx.upload_jpeg(s, jpeg, variant, crop)
+            self.ctx.upload_jpeg(s, jpeg, variant, crop, resave)
         return self._step(s, wait)
 
     def push_device(self, dev_ptr, stride, wait=True):

@@ -498,6 +498,46 @@ int icelk_jpeg_decode_rgb_file(icelk_t* h, const uint8_t* data, uint64_t len, ui
 /* The coefficients as the device decodes them, copied back (for tests): coef[0 .. info.coef_count). */
 int icelk_jpeg_device_coefficients(icelk_t* h, const uint8_t* data, uint64_t len, int16_t* coef, uint64_t capacity);
 
+/* ---- the reference's lossy re-save of the crop (opt-in) -----------------------------------------
+ * The reference never tracks on the pixels of the photos it is given: every photo is cropped with Pillow and written back
+ * with `img_crop.save(outpath)` (s1:272, camtools.py:64-104) -- a new baseline JPEG at Pillow's defaults (quality 75, 4:2:0
+ * chroma, libjpeg's standard tables) -- and the loop decodes THOSE files.  The entropy coder is lossless, so the pixels of
+ * "save, then open" are a function of the cropped R G B alone: colour conversion, padding and 2x2 downsampling, libjpeg's
+ * integer forward DCT and quantisation (csrc/jpeg_fwd.h; on the device k_jpeg_fwd.hip), then the decoder of the section
+ * above on those coefficients.  No file is written.  Everything equals Pillow (libjpeg) bit for bit; nothing below changes
+ * what the calls above do.  quality: 1 .. 100, Pillow's `quality=` (its default, the reference's, is 75). */
+/* Host only, no handle, re-entrant: the two quantisation tables of that file (the Annex K tables scaled by libjpeg's
+ * rule), 64 entries each in natural order. */
+int icelk_jpeg_resave_tables(int quality, uint16_t* luma, uint16_t* chroma);
+/* Host only, no handle, re-entrant: the quantised coefficients of the file Pillow would write for the w x h_ image at rgb
+ * (interleaved R G B, stride in bytes), and in *info what icelk_jpeg_describe would say about that file -- so that
+ * icelk_upload_jpeg / icelk_jpeg_decode_rgb take them as they take a file's.  The same code as the device runs, on the
+ * CPU.  coef may be NULL (the descriptor only); capacity in int16 values (ICELK_ECAP when too few).  The dummy blocks of
+ * the MCU-padded grid are written as the encoder writes them (AC 0, DC of the block before), so that whole planes compare. */
+int icelk_jpeg_resave_coefficients_host(const uint8_t* rgb, int w, int h_, int stride, int quality, icelk_jpeg_info_t* info,
+                                        int16_t* coef, uint64_t capacity);
+/* Host only: out[i] = (first + i) / (8 q), truncating, by the multiply-shift the quantiser uses on the host and on the
+ * device (for tests: it is exact for every numerator up to 2^17, far beyond what the transform of 8-bit samples gives). */
+int icelk_jpeg_resave_divide_host(int q, uint32_t first, uint32_t count, uint32_t* out);
+/* R G B in, the R G B of the re-saved image out (both on the host, strides in bytes), computed on the device.
+ * w >= 3, as for the decoder. */
+int icelk_jpeg_resave_rgb(icelk_t* h, const uint8_t* rgb, int w, int h_, int stride, int quality, uint8_t* out, int out_stride);
+/* The coefficients as the device's forward kernel makes them, copied back (for tests): the layout of
+ * icelk_jpeg_resave_coefficients_host. */
+int icelk_jpeg_resave_device_coefficients(icelk_t* h, const uint8_t* rgb, int w, int h_, int stride, int quality, int16_t* coef,
+                                          uint64_t capacity);
+/* icelk_upload_bgr, icelk_upload_jpeg and icelk_upload_jpeg_file with the re-save between the crop and the gray
+ * conversion: the slot holds what icelk_upload_bgr leaves there when given the pixels of Image.open(re-saved crop).  The
+ * arguments are the parents' plus quality.  The cropped R G B is made on the device (or copied there), re-saved by the
+ * forward kernel and decoded by the kernels of the section above with the re-save's tables.  Checked before anything is
+ * enqueued: quality 1 .. 100, cropped width >= 3, the sizes as in the parents.  Scratch buffers are allocated at first
+ * use and freed with the handle.  There is no _resave form of icelk_upload_jpeg_file_async. */
+int icelk_upload_bgr_resave(icelk_t* h, int slot, const uint8_t* host, int w, int h_, int stride, int gray_variant, int quality);
+int icelk_upload_jpeg_resave(icelk_t* h, int slot, const icelk_jpeg_info_t* info, const int16_t* coef, int gray_variant,
+                             int crop_left, int crop_top, int crop_right, int crop_bottom, int quality);
+int icelk_upload_jpeg_file_resave(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left,
+                                  int crop_top, int crop_right, int crop_bottom, int quality);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector

@@ -9,6 +9,7 @@
     python tools/jpeg_ingest.py e2e-huffman [--frames 24] [--threads 16]          MI355X: huffman="host" against "device"
     python tools/jpeg_ingest.py e2e-pipeline [--frames 24] [--threads 16]         MI355X: pipeline=False against True
     python tools/jpeg_ingest.py pipeline-loop [--frames 24]                       MI355X: pipelined runs for a kernel trace
+    python tools/jpeg_ingest.py resave [--frames 24] [--out profiles/jpeg_resave.txt]  MI355X: the reference's re-save of the crop
 
 host    one thread, best of 5: `read_jpeg` (Huffman decoding into coefficients) against `np.array(Image.open(...))` (what
         the "pil" decoder does per photo), and Pillow's own 1/8-scale draft decode -- entropy decoding plus a DC-only
@@ -27,6 +28,10 @@ e2e-pipeline   the folder driver with decoder="device", huffman="device": pipeli
         pipeline=True, alternating, three runs each behind one untimed run, tracks compared in every run; then
         pipeline=True over n_slots 5 / 6 / 8, one decode stream against two, normal against high priority
         (ICELK_JPEG_ASYNC_STREAMS / ICELK_JPEG_ASYNC_PRIO), and where a photo's time goes by the host clock.
+resave  `Context.upload_bgr(resave="reference")` on a 4000x3000 crop with profiling on: average HIP-event time of k_jpeg_fwd
+        (the forward half of the re-save) against its algorithmic bytes, and of k_jpeg_idct and k_jpeg_out on the re-saved
+        coefficients; the three uploads by the host clock with and without the re-save; then photos per second of the
+        folder driver with resave=None against resave="reference", alternating, three runs each.
 pipeline-loop  one plain and two pipelined runs of the same folder and nothing else, for `rocprofv3 --kernel-trace --stats --`.
 """
 import argparse
@@ -349,6 +354,74 @@ def pipeline(out, n, threads):
     os.rmdir(tmp)
 
 
+def resave(out, n, threads):
+    from iceberg_tracking_code_amd import Context, read_jpeg, resave_rgb
+    img = photo()
+    data = encode(img, 90)
+    j = read_jpeg(data)
+    i = j.info
+    rgb_b, coef_b = 3 * W * H, 2 * int(i.coef_count)
+    plane_b = sum(i.blocks_x[c] * i.blocks_y[c] * 64 for c in range(3))
+    ctx = Context(W, H, n_slots=2, max_pts=64)
+    try:
+        same = np.array_equal(resave_rgb(img, ctx=ctx), np.array(Image.open(io.BytesIO(encode_default(img)))))
+        for _ in range(3):
+            ctx.upload_bgr(0, img, 4, resave="reference")
+        ctx.prof_reset()
+        ctx.prof_enable(True)
+        reps = 20
+        for _ in range(reps):
+            ctx.upload_bgr(0, img, 4, resave="reference")
+        ctx.prof_enable(False)
+        tab = ctx.prof_table()
+        calls = []
+        for label, f in (("upload_bgr", lambda **kw: ctx.upload_bgr(0, img, 4, **kw)), ("upload_jpeg", lambda **kw: ctx.upload_jpeg(0, j, 4, **kw)),
+                         ("upload_jpeg_file", lambda **kw: ctx.upload_jpeg_file(0, data, 4, **kw))):
+            calls.append((label, mean_ms(lambda: f()), mean_ms(lambda: f(resave="reference"))))
+    finally:
+        ctx.close()
+    fwd, idct, outk = (tab[k]["avg_us"] for k in ("jpeg_fwd", "jpeg_idct", "jpeg_out"))
+    print("the reference's re-save of the crop on the device, %dx%d crop, quality 75, %d uploads (upload_bgr), HIP events around "
+          "each kernel; pixels %s Pillow's" % (W, H, reps, "equal" if same else "DIFFER FROM"), file=out)
+    print("k_jpeg_fwd   %8.1f us  reads %.1f MB of RGB, writes %.1f MB of coefficients: %.2f TB/s; those bytes at 8 TB/s: %.1f us" %
+          (fwd, rgb_b / 1e6, coef_b / 1e6, (rgb_b + coef_b) / fwd / 1e6, (rgb_b + coef_b) / 8e12 * 1e6), file=out)
+    print("k_jpeg_idct  %8.1f us  reads %.1f MB of coefficients, writes %.1f MB of planes: %.2f TB/s" %
+          (idct, coef_b / 1e6, plane_b / 1e6, (coef_b + plane_b) / idct / 1e6), file=out)
+    print("k_jpeg_out   %8.1f us  reads %.1f MB of planes, writes %.1f MB of gray: %.2f TB/s" %
+          (outk, plane_b / 1e6, W * H / 1e6, (plane_b + W * H) / outk / 1e6), file=out)
+    print("forward kernel / (k_jpeg_idct + k_jpeg_out): %.2f" % (fwd / (idct + outk)), file=out)
+    print("whole call by the host clock, mean of 10, ending in a synchronise: resave=None, resave=\"reference\"", file=out)
+    for label, a, b in calls:
+        print("  %-17s %7.2f ms  %7.2f ms  (+%.2f ms)" % (label, a, b, b - a), file=out)
+    out.flush()
+    tmp, names = folder(n)
+    print("folder driver, decoder=\"device\", huffman=\"device\": %d photos of %dx%d 4:2:0 quality 90, decode_threads %d, %d usable cores" %
+          (n, W, H, threads, len(os.sched_getaffinity(0))), file=out)
+    run_folder(names, tmp, threads)                          # untimed: cold files, code objects, clocks
+    res, segs = {None: [], "reference": []}, {}
+    for rep_ in range(3):
+        for side in (None, "reference"):
+            rate, got = run_folder(names, tmp, threads, resave=side)
+            if side in segs and not same_tracks(got, segs[side]):
+                raise SystemExit("resave=%s: tracks differ between runs" % side)
+            segs[side] = got
+            res[side].append(rate)
+    for side in (None, "reference"):
+        print("resave=%s: %s photos/s (runs in order)" % (repr(side), ", ".join("%.1f" % v for v in res[side])), file=out)
+    print("ratio of the medians: %.2f; %d segments; tracks equal between the two: %s (they are not meant to be)" %
+          (sorted(res["reference"])[1] / sorted(res[None])[1], len(segs[None]), same_tracks(segs[None], segs["reference"])), file=out)
+    for p in names:
+        os.remove(p)
+    os.rmdir(tmp)
+
+
+def encode_default(img):
+    """Pillow's defaults, as the reference's crop pool saves"""
+    b = io.BytesIO()
+    Image.fromarray(img).save(b, "JPEG")
+    return b.getvalue()
+
+
 def pipeline_loop(n):
     tmp, names = folder(n)
     _, ref = run_folder(names, tmp, 16)
@@ -363,7 +436,7 @@ def pipeline_loop(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("mode", choices=("host", "device", "e2e", "huffman", "huffman-loop", "e2e-huffman", "e2e-pipeline",
-                                         "pipeline-loop"))
+                                         "pipeline-loop", "resave"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--threads", type=int, default=16)
@@ -372,7 +445,7 @@ def main():
         return huffman_loop()
     if a.mode == "pipeline-loop":
         return pipeline_loop(a.frames)
-    name = {"huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e", "e2e-pipeline": "jpeg_pipeline_e2e"}.get(
+    name = {"resave": "jpeg_resave", "huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e", "e2e-pipeline": "jpeg_pipeline_e2e"}.get(
         a.mode, "jpeg_ingest_%s" % a.mode)
     path = a.out or os.path.join(ROOT, "profiles", name + ".txt")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -385,6 +458,8 @@ def main():
             huffman(out)
         elif a.mode == "e2e-huffman":
             e2e(out, a.frames, min(a.threads, 16), compare="huffman")
+        elif a.mode == "resave":
+            resave(out, a.frames, min(a.threads, 16))
         elif a.mode == "e2e-pipeline":
             pipeline(out, a.frames, min(a.threads, 16))
         else:
