@@ -20,7 +20,7 @@ from .postprocess import (VelocityCube, average_periods, average_spatially_tempo
                           daily_averages, npz_to_csv, npz_to_mat, save_csv, velocities_to_regular_grid)
 from .calibration import CalibrationResult, ShorelineScene, calibrate, run_calibration  # noqa: F401
 from .jpeg import (JpegCoefficients, UnsupportedJpeg, decode_jpeg, read_jpeg, read_jpeg_lanes, resave_coefficients,  # noqa: F401
-                   resave_rgb, resave_tables)
+                   resave_rgb, resave_tables, encode_jpeg, resave_bytes, source_comment)
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

@@ -84,6 +84,12 @@ SIGNATURES = {
     "icelk_upload_bgr_resave": (C.c_int, [handle_p, C.c_int, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_jpeg_resave": (C.c_int, [handle_p, C.c_int, jpeg_info_p, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_jpeg_file_resave": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_jpeg_encode_header": (C.c_int, [jpeg_info_p, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_jpeg_encode_coefficients_host": (C.c_int, [jpeg_info_p, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_jpeg_resave_file_host": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_uint64, vp, C.c_uint64,
+                                              C.POINTER(C.c_uint64)]),
+    "icelk_jpeg_encode_coefficients": (C.c_int, [handle_p, jpeg_info_p, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_jpeg_resave_encode": (C.c_int, [handle_p, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

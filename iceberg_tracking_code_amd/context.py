@@ -221,6 +221,38 @@ class Context:
                                                  out.strides[0]))
         return out
 
+    def jpeg_resave_file(self, comment=None):
+        """The bytes of the JPEG file of the handle's most recent re-save (an upload with `resave=`, `jpeg_resave_rgb`,
+        `jpeg_resave_device_coefficients`): what Pillow's `crop.save(path)` writes for that crop, entropy-coded on the device
+        from the coefficients the re-save left there (icelk_jpeg_resave_encode).  No slot is touched.  `comment`: the
+        source's comment (`jpeg.source_comment`), which Pillow carries over, or None.  IcelkError (code ICELK_ESTATE) when
+        the handle has never re-saved."""
+        from .jpeg import _comment_args, _encode_call
+        com, ncom = _comment_args(comment)
+        guess = getattr(self, "_resave_file_guess", 1 << 16) + ncom
+        data = _encode_call(lambda out, cap, n: self._lib.icelk_jpeg_resave_encode(self._h, com, ncom, out, cap, n), guess,
+                            "icelk_jpeg_resave_encode", self._h)
+        self._resave_file_guess = max(1 << 16, len(data) + len(data) // 4)   # the next photo of a folder is about as large
+        return data
+
+    def jpeg_encode(self, info, coef_ptr, comment, comment_len, guess):
+        """`jpeg.encode_jpeg` on the device (icelk_jpeg_encode_coefficients)."""
+        from .jpeg import _encode_call
+        return _encode_call(lambda out, cap, n: self._lib.icelk_jpeg_encode_coefficients(self._h, C.byref(info), coef_ptr, comment,
+                                                                                         comment_len, out, cap, n), guess,
+                            "icelk_jpeg_encode_coefficients", self._h)
+
+    def jpeg_resave_bytes(self, rgb, quality=75, comment=None):
+        """`jpeg.resave_bytes` on the device: forward transform (the coefficients come back too; this is the form for
+        tests and single images -- the uploads with `resave=` followed by `jpeg_resave_file` move only the file)."""
+        a = np.ascontiguousarray(rgb)
+        info = _lib.JpegInfo()
+        args = (_u8(a), a.shape[1], a.shape[0], a.strides[0], int(quality))
+        self._ck(self._lib.icelk_jpeg_resave_coefficients_host(*args, C.byref(info), None, 0))
+        coef = np.empty(int(info.coef_count), np.int16)
+        self._ck(self._lib.icelk_jpeg_resave_device_coefficients(self._h, *args, C.c_void_p(coef.ctypes.data), coef.size))
+        return self.jpeg_resave_file(comment)
+
     def jpeg_resave_device_coefficients(self, rgb, quality=75):
         """The coefficients `jpeg.resave_coefficients(rgb, quality).coef` as the device's forward kernel makes them, for tests."""
         from .jpeg import resave_coefficients

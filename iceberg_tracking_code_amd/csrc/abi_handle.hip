@@ -10,6 +10,7 @@ namespace icelk {
 static const char* kKernelNames[K_COUNT_] = {
     "bgr2gray", "pyrdown", "lk", "lk_fb", "corner_candidates", "min_distance", "sort_emit",
     "project_tracks", "synth", "lk_fb_pair", "jpeg_idct", "jpeg_out", "jpeg_huff", "jpeg_fwd",
+    "jpeg_enc_count", "jpeg_enc_scan", "jpeg_enc_pack", "jpeg_enc_ff", "jpeg_enc_stuff",
 };
 
 std::string g_create_err;
@@ -164,6 +165,7 @@ static void destroy_ctx(Ctx* c)
     if (c->stream) hipStreamSynchronize(c->stream);
     jpeg_async_destroy(c);   // before the slots go: files in flight write into them
     jpeg_resave_destroy(c);
+    jpeg_enc_destroy(c);
     prof_drain(c);
     for (auto& e : c->evt_pool) {
         hipEventDestroy(e.a);

@@ -80,6 +80,9 @@ int resave_forward(Ctx* c, int w, int h, int quality, icelk_jpeg_info_t* I, Jpeg
         launch_jpeg_fwd(c->stream, F);
     }
     if (int rc = check_launch(c, "jpeg_fwd")) return rc;
+    c->jpeg.enc.resaved = true;   // what icelk_jpeg_resave_encode writes the file of
+    c->jpeg.enc.stream_ok = false;
+    c->jpeg.enc.info = *I;
     if (!with_planes) return ICELK_OK;
     {
         ProfScope p(c, K_JPEG_IDCT);

@@ -114,6 +114,21 @@ struct Ctx {
         JpegJob resave;
         uint8_t* d_src = nullptr;
         size_t src_cap = 0;
+        // the JPEG writer (abi_jpeg_enc.hip), allocated at first use and grown to what a file measures: the tables, the
+        // blocks' bit lengths, the groups' offsets, the packed and the stuffed stream; `resaved` / `info`: the handle has
+        // run the forward kernel, and for which file; `stream_ok`: d_out holds that file's scan (stream_len bytes)
+        struct Enc {
+            uint32_t* d_codes = nullptr;
+            int16_t* d_coef = nullptr;     // of icelk_jpeg_encode_coefficients only
+            uint16_t* d_bits = nullptr;
+            uint32_t *d_group = nullptr, *d_ctl = nullptr, *d_packed = nullptr, *d_ff = nullptr;
+            uint8_t* d_out = nullptr;
+            uint32_t* h_ctl = nullptr;     // pinned
+            size_t coef_cap = 0, bits_cap = 0, group_cap = 0, packed_cap = 0, ff_cap = 0, out_cap = 0;   // elements
+            bool resaved = false, stream_ok = false;
+            icelk_jpeg_info_t info{};
+            uint64_t stream_len = 0;
+        } enc;
         uint8_t* d_rgb = nullptr;                              // the decoded image (icelk_jpeg_decode_rgb only)
         size_t rgb_cap = 0;
         int subseq_bits = 512, max_hops = lanes::kGroup, max_rounds = 8;   // icelk_jpeg_huff_config
@@ -469,6 +484,8 @@ bool jpeg_huff_config_ok(int subseq_bits, int max_hops, int max_rounds);
 int jpeg_host_decode(const uint8_t* data, size_t len, int16_t* coef, uint64_t capacity);
 // abi_jpeg_resave.hip
 void jpeg_resave_destroy(Ctx* c);
+// abi_jpeg_enc.hip
+void jpeg_enc_destroy(Ctx* c);
 // abi_jpeg_async.hip
 void jpeg_async_destroy(Ctx* c);
 int jpeg_async_sync(Ctx* c);

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/icelk.h"
+#include "jpeg_enc.h"
 #include "jpeg_lanes.h"
 
 namespace icelk {
@@ -60,6 +61,11 @@ enum KernelId {
     K_JPEG_OUT,     // upsample + colour + crop + gray / RGB
     K_JPEG_HUFF,    // Huffman decoding: synchronise, scan, write, DC (k_jpeg_huff.hip)
     K_JPEG_FWD,     // the re-save's forward half: colour, downsampling, forward DCT, quantisation (k_jpeg_fwd.hip)
+    K_JPEG_ENC_COUNT,   // the JPEG writer (k_jpeg_enc.hip): bit length of every block
+    K_JPEG_ENC_SCAN,    // ... prefix sums (bit offsets of the groups, FF counts of the stretches)
+    K_JPEG_ENC_PACK,    // ... the blocks' bits at their offsets
+    K_JPEG_ENC_FF,      // ... FF bytes of the packed stream
+    K_JPEG_ENC_STUFF,   // ... the stream with a 00 behind every FF
     K_COUNT_
 };
 
@@ -133,6 +139,26 @@ struct JpegFwdArgs {
     uint32_t recip[2][64];    // fwd::reciprocal(8 * quant)
 };
 void launch_jpeg_fwd(hipStream_t s, const JpegFwdArgs& A);
+
+// The JPEG writer's entropy coder (k_jpeg_enc.hip; the arithmetic is jpeg_enc.h).  All pointers are device memory.
+constexpr int kJpegEncGroup = 64;        // blocks (lanes) per workgroup of count and pack: one wave
+constexpr int kJpegEncScanPass = 1024;   // entries the prefix sum takes per pass of its loop
+constexpr int kJpegEncChunk = 64;        // bytes of the packed stream per lane of ff and stuff; 256 lanes per workgroup
+enum JpegEncCtl { JE_TOTAL_BITS = 0, JE_INVALID, JE_FF_TOTAL, JE_WORDS = 4 };   // words of JpegEncArgs::ctl
+struct JpegEncArgs {
+    enc::Layout L;
+    const int16_t* coef;      // 16-byte aligned
+    const uint32_t* codes;    // enc::Codes
+    uint16_t* bits;           // per block of the scan: its length
+    uint32_t* group;          // per kJpegEncGroup blocks: the sum of their lengths, after the scan the bit offset of the first
+    uint32_t* ctl;            // JpegEncCtl
+    uint32_t* packed;         // the unstuffed stream, zero-filled to whole chunks before pack runs
+};
+void launch_jpeg_enc_count(hipStream_t s, const JpegEncArgs& A);
+void launch_jpeg_enc_scan(hipStream_t s, uint32_t* v, uint32_t n, uint32_t* total);   // in place, exclusive
+void launch_jpeg_enc_pack(hipStream_t s, const JpegEncArgs& A);
+void launch_jpeg_enc_ff(hipStream_t s, const uint32_t* packed, uint32_t nchunks, uint32_t* wg_ff);
+void launch_jpeg_enc_stuff(hipStream_t s, const uint32_t* packed, uint32_t nbytes, uint32_t nchunks, const uint32_t* wg_off, uint8_t* out);
 
 // Huffman decoding on the device (k_jpeg_huff.hip; the algorithm is jpeg_lanes.h).  All pointers are device memory.
 constexpr int kJpegMaxRounds = 255;

@@ -1,0 +1,214 @@
+// jpeg_enc_host.h -- the host statement of the JPEG writer: the header Pillow's `img.save(path)` writes, and the scan
+// coded serially with jpeg_enc.h, the code the device kernels run.  Plain C++ without the HIP runtime: abi_jpeg_enc.hip
+// exports it (icelk_jpeg_encode_header, icelk_jpeg_encode_coefficients_host, icelk_jpeg_resave_file_host), and a
+// stand-alone program can include it as it is (tests/jpeg_enc_host_main.cpp).  No global state that is written after the
+// tables are built once: re-entrant.
+//
+// The file, in libjpeg's order: SOI, APP0 (JFIF 1.01, density 1 : 1 without a unit -- what `crop().save()` writes whatever
+// the source said), one COM segment if a comment is given, a DQT segment per table slot (0, and 1 with three components),
+// SOF0, a DHT segment per table in the order DC0, AC0, DC1, AC1 (the first two only with one component), SOS, the scan
+// with a 00 stuffed behind every FF and the last byte filled with 1-bits, EOI.
+#pragma once
+#include <string.h>
+
+#include "../../include/icelk.h"
+#include "jpeg_enc.h"
+
+namespace icelk {
+namespace enc {
+
+static const uint8_t kZigzag[64] = ICELK_ENC_ZIGZAG;
+
+inline const Codes& codes()
+{
+    static const Codes C = [] {
+        Codes c;
+        build_codes(&c);
+        return c;
+    }();
+    return C;
+}
+
+// The scan's layout of a descriptor, which must be laid out as icelk_jpeg_describe lays files out.  ICELK_EARG: not such a
+// descriptor; ICELK_EUNSUP: restart intervals, or a third quantisation table; ICELK_ECAP: blocks * 1660 bits do not fit
+// 32 bits (bit offsets are carried in 32 bits, on the host as on the device)
+inline int layout_of(const icelk_jpeg_info_t* I, Layout* L)
+{
+    if (!I) return ICELK_EARG;
+    if (I->ncomp != 1 && I->ncomp != 3) return ICELK_EARG;
+    if (I->width < 1 || I->height < 1 || I->width > 65535 || I->height > 65535) return ICELK_EARG;
+    const int hs = I->hmax, vs = I->vmax;
+    if (I->ncomp == 1 ? (hs != 1 || vs != 1) : !((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return ICELK_EARG;
+    const int mx = (I->width + 8 * hs - 1) / (8 * hs), my = (I->height + 8 * vs - 1) / (8 * vs);
+    if (I->mcus_x != mx || I->mcus_y != my) return ICELK_EARG;
+    uint64_t off = 0;
+    for (int c = 0; c < 3; c++) {
+        const bool on = c < I->ncomp;
+        const int bx = on ? mx * (c ? 1 : hs) : 0, by = on ? my * (c ? 1 : vs) : 0;
+        if (I->blocks_x[c] != bx || I->blocks_y[c] != by || I->coef_offset[c] != off) return ICELK_EARG;
+        off += (uint64_t)bx * by * 64;
+        if (on)
+            for (int i = 0; i < 64; i++)
+                if (I->quant[c][i] < 1 || I->quant[c][i] > 255) return ICELK_EARG;   // an 8-bit DQT
+    }
+    if (I->coef_count != off) return ICELK_EARG;
+    if (I->restart_interval != 0) return ICELK_EUNSUP;
+    if (I->ncomp == 3 && memcmp(I->quant[1], I->quant[2], sizeof(I->quant[1]))) return ICELK_EUNSUP;   // slots 0 and 1 only
+    const uint64_t bpm = (uint64_t)(I->ncomp == 1 ? 1 : hs * vs + 2), blocks = bpm * mx * my;
+    if (blocks * kMaxBlockBits >= ((uint64_t)1 << 32)) return ICELK_ECAP;
+    L->ncomp = I->ncomp;
+    L->hs = hs;
+    L->vs = vs;
+    L->mcus_x = mx;
+    L->bpm = (uint32_t)bpm;
+    L->blocks = (uint32_t)blocks;
+    L->luma_bx = (uint32_t)I->blocks_x[0];
+    L->off0 = (uint32_t)I->coef_offset[0];
+    L->off1 = (uint32_t)I->coef_offset[1];
+    L->off2 = (uint32_t)I->coef_offset[2];
+    return ICELK_OK;
+}
+
+// bytes that are written only while they fit; `n` counts them all the same
+struct Bytes {
+    uint8_t* out;
+    uint64_t cap, n = 0;
+    Bytes(uint8_t* o, uint64_t c) : out(o), cap(o ? c : 0) {}
+    void put(uint8_t b)
+    {
+        if (n < cap) out[n] = b;
+        n++;
+    }
+    void put16(unsigned v)
+    {
+        put((uint8_t)(v >> 8));
+        put((uint8_t)v);
+    }
+    void put(const void* p, size_t k)
+    {
+        for (size_t i = 0; i < k; i++) put(((const uint8_t*)p)[i]);
+    }
+};
+
+inline bool comment_ok(const uint8_t* comment, uint64_t comment_len) { return comment_len <= 65533 && (comment || comment_len == 0); }
+
+// SOI .. the end of SOS into B (the descriptor has passed layout_of)
+inline void header_bytes(const icelk_jpeg_info_t& I, const uint8_t* comment, uint64_t comment_len, Bytes& B)
+{
+    static const uint8_t app0[] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    B.put16(0xFFD8);
+    B.put(app0, sizeof(app0));
+    if (comment) {   // an empty comment is a segment too
+        B.put16(0xFFFE);
+        B.put16((unsigned)comment_len + 2);
+        B.put(comment, (size_t)comment_len);
+    }
+    const int nt = I.ncomp == 1 ? 1 : 2;
+    for (int t = 0; t < nt; t++) {
+        B.put16(0xFFDB);
+        B.put16(67);
+        B.put((uint8_t)t);
+        for (int k = 0; k < 64; k++) B.put((uint8_t)I.quant[t][kZigzag[k]]);
+    }
+    B.put16(0xFFC0);
+    B.put16(8 + 3 * I.ncomp);
+    B.put(8);
+    B.put16((unsigned)I.height);
+    B.put16((unsigned)I.width);
+    B.put((uint8_t)I.ncomp);
+    for (int c = 0; c < I.ncomp; c++) {
+        B.put((uint8_t)(c + 1));
+        B.put((uint8_t)(c ? 0x11 : I.hmax << 4 | I.vmax));
+        B.put((uint8_t)(c ? 1 : 0));
+    }
+    for (int t = 0; t < nt; t++)
+        for (int ac = 0; ac < 2; ac++) {
+            const HuffSpec& S = kSpec[ac ? SPEC_AC0 + t : SPEC_DC0 + t];
+            B.put16(0xFFC4);
+            B.put16(19 + S.nval);
+            B.put((uint8_t)(ac << 4 | t));
+            B.put(S.bits, 16);
+            B.put(S.val, (size_t)S.nval);
+        }
+    B.put16(0xFFDA);
+    B.put16(6 + 2 * I.ncomp);
+    B.put((uint8_t)I.ncomp);
+    for (int c = 0; c < I.ncomp; c++) {
+        B.put((uint8_t)(c + 1));
+        B.put((uint8_t)(c ? 0x11 : 0x00));
+    }
+    B.put(0);
+    B.put(63);
+    B.put(0);
+}
+
+inline int header_host(const icelk_jpeg_info_t* info, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity,
+                       uint64_t* len)
+{
+    Layout L;
+    if (!len || !comment_ok(comment, comment_len)) return ICELK_EARG;
+    if (int rc = layout_of(info, &L)) return rc;
+    Bytes B(out, capacity);
+    header_bytes(*info, comment, comment_len, B);
+    *len = B.n;
+    return out && B.n <= capacity ? ICELK_OK : ICELK_ECAP;
+}
+
+// bits -> bytes, most significant first, a 00 behind every FF
+struct ByteSink {
+    Bytes& B;
+    uint64_t acc = 0;
+    int n = 0;
+    explicit ByteSink(Bytes& b) : B(b) {}
+    void put(uint32_t v, int k)
+    {
+        acc = acc << k | v;
+        n += k;
+        while (n >= 8) {
+            n -= 8;
+            const uint8_t b = (uint8_t)(acc >> n);
+            B.put(b);
+            if (b == 0xFF) B.put(0);
+        }
+        acc &= ((uint64_t)1 << n) - 1;
+    }
+    void pad()
+    {
+        if (n) put((1u << (8 - n)) - 1u, 8 - n);
+    }
+};
+
+struct HostBlock {
+    const int16_t* blk;
+    int operator()(int k) const { return blk[kZigzag[k]]; }
+};
+
+// the whole file.  ICELK_ECAP: out is too small (or NULL), *len says what it takes; ICELK_EARG: a coefficient without a
+// code -- found by a counting pass before anything is written
+inline int encode_host(const icelk_jpeg_info_t* info, const int16_t* coef, const uint8_t* comment, uint64_t comment_len, uint8_t* out,
+                       uint64_t capacity, uint64_t* len)
+{
+    Layout L;
+    if (!len || !coef || !comment_ok(comment, comment_len)) return ICELK_EARG;
+    if (int rc = layout_of(info, &L)) return rc;
+    const Codes& C = codes();
+    for (uint32_t s = 0; s < L.blocks; s++) {
+        const Place P = place(L, s);
+        CountSink n;
+        if (!encode_block(HostBlock{coef + P.at}, P.pred == kNoPred ? 0 : coef[P.pred], C.dc[P.table], C.ac[P.table], n)) return ICELK_EARG;
+    }
+    Bytes B(out, capacity);
+    header_bytes(*info, comment, comment_len, B);
+    ByteSink S(B);
+    for (uint32_t s = 0; s < L.blocks; s++) {
+        const Place P = place(L, s);
+        encode_block(HostBlock{coef + P.at}, P.pred == kNoPred ? 0 : coef[P.pred], C.dc[P.table], C.ac[P.table], S);
+    }
+    S.pad();
+    B.put16(0xFFD9);
+    *len = B.n;
+    return out && B.n <= capacity ? ICELK_OK : ICELK_ECAP;
+}
+
+}  // namespace enc
+}  // namespace icelk

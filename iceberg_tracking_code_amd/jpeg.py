@@ -194,3 +194,102 @@ def resave_rgb(rgb, quality=75, ctx=None):
         from .api import default_context
         ctx = default_context(a.shape[1], a.shape[0])
     return ctx.jpeg_resave_rgb(a, quality)
+
+
+# ---- the re-saved crop as a file ---------------------------------------------------------------------------------------
+def _encode_error(rc, what, message=""):
+    """The exception of a writer call that returned `rc`, with the code in its `code` attribute: ValueError (ICELK_EARG: a
+    coefficient the standard tables have no code for, or a descriptor the writer does not take), UnsupportedJpeg (restart
+    intervals, a third quantisation table), IcelkError (ICELK_ECAP: more blocks than 32-bit bit offsets take; ...)."""
+    text = "%s: icelk error %d%s" % (what, rc, ": " + message if message else "")
+    e = {_lib.EARG: ValueError, _lib.EUNSUP: UnsupportedJpeg, _lib.ENOMEM: MemoryError}.get(rc, _lib.IcelkError)(text)
+    e.code = rc
+    return e
+
+
+def _encode_call(call, guess, what, handle=None):
+    """call(out, capacity, byref(len)) -> rc, into a buffer of `guess` bytes and, when the call says it takes more, into one
+    of that size"""
+    n, cap = C.c_uint64(0), int(guess)
+    for _ in range(2):
+        buf = np.empty(cap, np.uint8)
+        rc = call(C.c_void_p(buf.ctypes.data), cap, C.byref(n))
+        if rc == _lib.OK:
+            return buf[:n.value].tobytes()
+        if rc != _lib.ECAP or n.value <= cap:
+            break
+        cap = n.value
+    msg = _lib.load().icelk_last_error(handle) if handle is not None else None
+    raise _encode_error(rc, what, msg.decode() if msg else "")
+
+
+def _comment_args(comment):
+    if comment is None:
+        return None, 0
+    comment = bytes(comment)
+    return comment, len(comment)
+
+
+def source_comment(data):
+    """The comment Pillow reports for a JPEG file given as bytes (`Image.open(f).info.get("comment")`): the body of the
+    last COM segment in front of the scan, or None.  `crop().save()` carries it over into the re-saved crop, so the
+    writers below take it as `comment=`."""
+    data = bytes(data)
+    found, pos = None, 2
+    if data[:2] != b"\xff\xd8":
+        return None
+    while pos + 4 <= len(data) and data[pos] == 0xFF:
+        m = data[pos + 1]
+        if m == 0xFF:                                      # a fill byte
+            pos += 1
+            continue
+        n = data[pos + 2] << 8 | data[pos + 3]
+        if n < 2 or pos + 2 + n > len(data):
+            break
+        if m == 0xFE:
+            found = data[pos + 4:pos + 2 + n]
+        if m == 0xDA:
+            break
+        pos += 2 + n
+    return found
+
+
+def encode_header(info, comment=None):
+    """SOI up to the end of the SOS segment of the file `encode_jpeg` writes for a descriptor (host)."""
+    com, ncom = _comment_args(comment)
+    lib = _lib.load()
+    return _encode_call(lambda out, cap, n: lib.icelk_jpeg_encode_header(C.byref(info), com, ncom, out, cap, n), 1024 + ncom,
+                        "icelk_jpeg_encode_header")
+
+
+def encode_jpeg(coefficients, comment=None, ctx=None):
+    """A JpegCoefficients -> the bytes of the baseline JPEG file libjpeg writes for them at its defaults (the Huffman tables
+    of T.81 Annex K, no restart intervals, JFIF 1.01 without a density; csrc/jpeg_enc.h): `encode_jpeg(read_jpeg(f)) == f`
+    for a file Pillow wrote without optimize=True.  Without `ctx` the scan is coded on the host, with a Context on the
+    device (csrc/k_jpeg_enc.hip); the bytes are the same.  `comment`: the body of a COM segment, or None."""
+    j = coefficients
+    coef = np.ascontiguousarray(j.coef, np.int16)
+    if coef.size < int(j.info.coef_count):
+        raise ValueError("fewer coefficients than the descriptor counts")
+    com, ncom = _comment_args(comment)
+    ptr, guess = C.c_void_p(coef.ctypes.data), 4096 + ncom + coef.size
+    if ctx is not None:
+        return ctx.jpeg_encode(j.info, ptr, com, ncom, guess)
+    lib = _lib.load()
+    return _encode_call(lambda out, cap, n: lib.icelk_jpeg_encode_coefficients_host(C.byref(j.info), ptr, com, ncom, out, cap, n), guess,
+                        "icelk_jpeg_encode_coefficients_host")
+
+
+def resave_bytes(rgb, quality=75, comment=None, ctx=None):
+    """H x W x 3 (R G B) uint8 -> the bytes `Image.fromarray(rgb).save(f, "JPEG", quality=quality)` writes, byte for byte.
+    Without `ctx` on the host (csrc/jpeg_fwd.h, csrc/jpeg_enc.h); with a Context forward transform and entropy coder run
+    on the device and only the file comes back (width >= 3 there).  `comment`: what Pillow carries over from the source of a
+    crop (`source_comment`), or None."""
+    a, quality = _rgb3(rgb), resave_quality(quality)
+    com, ncom = _comment_args(comment)
+    if ctx is not None:
+        return ctx.jpeg_resave_bytes(a, quality, comment)
+    lib = _lib.load()
+    args = (a.ctypes.data_as(_lib.u8p), a.shape[1], a.shape[0], a.strides[0], quality, com, ncom)
+    return _encode_call(lambda out, cap, n: lib.icelk_jpeg_resave_file_host(*args, out, cap, n), 4096 + ncom + a.shape[0] * a.shape[1],
+                        "icelk_jpeg_resave_file_host")

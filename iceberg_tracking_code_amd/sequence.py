@@ -60,6 +60,38 @@ def _read_bytes(path):
     return _decode(path)
 
 
+# the same loaders with the photo's comment (Pillow's `im.info.get("comment")`: `crop().save()` carries it into the crop's file)
+def _decode_c(path):
+    from PIL import Image
+    im = Image.open(path)
+    return np.array(im), im.info.get("comment")
+
+
+def _read_c(path):
+    from .jpeg import read_jpeg, source_comment
+    try:
+        with open(path, "rb") as f:
+            data = f.read()
+        j = read_jpeg(data)
+        if j.ncomp == 3:
+            return j, source_comment(data)
+    except ValueError:
+        pass
+    return _decode_c(path)
+
+
+def _read_bytes_c(path):
+    from .jpeg import describe_jpeg, source_comment
+    try:
+        with open(path, "rb") as f:
+            data = f.read()
+        if describe_jpeg(data).ncomp == 3:
+            return data, source_comment(data)
+    except ValueError:
+        pass
+    return _decode_c(path)
+
+
 def _image_size(path, decoder):
     if decoder == "device":
         from .jpeg import describe_jpeg
@@ -80,7 +112,7 @@ PIPELINE_SLOTS = 6
 def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startlist=(0,), crop=None, mask=None,
                          mask_polygon=None, feature_params=None, lk_params=None, decode_threads=4, decode_ahead=6,
                          gray_variant=4, device=0, on_segment=None, save=True, decoder="pil", huffman="host", pipeline=False,
-                         n_slots=PIPELINE_SLOTS, resave=None):
+                         n_slots=PIPELINE_SLOTS, resave=None, save_crops=None):
     """Track one day's photos.  Returns [(npz path, tracks (n, T+1, 2) f32, trackquality (n, T) f32)] of the
     segments that pass the time-gap rule, in order.
 
@@ -101,6 +133,11 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                    sees, the crop saved by Pillow as a new JPEG (quality 75, s1:272) and opened again -- reproduced on the
                    device, no file is written; an int: that quality.  Not with pipeline=True.  A file the device decoder
                    does not take goes through PIL, that file only, and is re-saved on the device all the same
+    save_crops     with resave: a directory that receives `<basename of the photo>` for every photo ingested, the file the
+                   reference's crop step writes into its target folder (`Image.open(p).crop(box).save(out)`, the source's
+                   comment carried over), entropy-coded on the device (csrc/k_jpeg_enc.hip) right after the upload and
+                   written on the calling thread once the photo's step is enqueued; once per photo, however many entries
+                   of startlist visit it.  Not with pipeline=True.  The tracks do not change
     """
     if decoder not in ("pil", "device"):
         raise ValueError('decoder must be "pil" or "device"')
@@ -114,6 +151,10 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
     resave = resave_quality(resave)
     if pipeline and resave is not None:
         raise ValueError("resave is not available with pipeline=True")
+    if save_crops is not None and resave is None:
+        raise ValueError("save_crops needs resave: the files written are the re-saved crops")
+    if save_crops is not None and pipeline:
+        raise ValueError("save_crops is not available with pipeline=True")
     if pipeline and int(n_slots) < 5:
         raise ValueError("n_slots must be at least 5")
     imagelist = [str(p) for p in imagelist]
@@ -127,6 +168,10 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
         left, top, right, bottom = (int(v) for v in crop)
         w, h = w - left - right, h - top - bottom
     load = (_read_bytes if huffman == "device" else _read) if decoder == "device" else _decode
+    if save_crops is not None:
+        load = {_read_bytes: _read_bytes_c, _read: _read_c, _decode: _decode_c}[load]
+        os.makedirs(save_crops, exist_ok=True)
+    written = set()                                       # photos whose crop has been written
     trk = None
     try:
         with ThreadPoolExecutor(max_workers=max(1, int(decode_threads))) as pool:
@@ -164,15 +209,21 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                         frame = pending.pop(0).result()
                         if counter + decode_ahead < len(names):
                             pending.append(pool.submit(load, names[counter + decode_ahead]))
+                        kw = dict(variant=gray_variant, crop=crop, resave=resave)
+                        if save_crops is not None:
+                            frame, comment = frame
+                            if names[counter] not in written:
+                                kw.update(crop_file=os.path.join(save_crops, os.path.basename(names[counter])), comment=comment)
                         if isinstance(frame, bytes):
                             try:
-                                seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop, resave=resave)
+                                seg = trk.push_jpeg(frame, **kw)
                             except ValueError:            # unsupported or damaged, that file only: PIL has the word
-                                seg = trk.push_bgr(_decode(names[counter]), variant=gray_variant, crop=crop, resave=resave)
+                                seg = trk.push_bgr(_decode(names[counter]), **kw)
                         elif isinstance(frame, np.ndarray):
-                            seg = trk.push_bgr(frame, variant=gray_variant, crop=crop, resave=resave)
+                            seg = trk.push_bgr(frame, **kw)
                         else:
-                            seg = trk.push_jpeg(frame, variant=gray_variant, crop=crop, resave=resave)
+                            seg = trk.push_jpeg(frame, **kw)
+                        written.add(names[counter])
                     if seg is None:
                         continue
                     seg_first, tracks, quality = seg

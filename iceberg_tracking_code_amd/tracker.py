@@ -114,24 +114,52 @@ class SegmentTracker:
         self.ctx.upload_gray(s, frame_gray)
         return self._step(s, wait)
 
-    def push_bgr(self, frame, wait=True, variant=4, crop=None, resave=None):
+    def _crop_bytes(self, crop_file, comment):
+        """The file of the re-save the upload just ran (`Context.jpeg_resave_file`), or None when none is asked for.  Taken
+        before the step is enqueued, so that the call's synchronisations wait for the upload alone."""
+        return None if crop_file is None else self.ctx.jpeg_resave_file(comment)
+
+    @staticmethod
+    def _write_crop(crop_file, data):
+        """Written on the calling thread once the step is enqueued: the device tracks meanwhile."""
+        if crop_file is not None:
+            with open(crop_file, "wb") as f:
+                f.write(data)
+
+    @staticmethod
+    def _check_crop_file(resave, crop_file):
+        if crop_file is not None and resave is None:
+            raise ValueError("crop_file needs resave: the file written is the re-saved crop")
+
+    def push_bgr(self, frame, wait=True, variant=4, crop=None, resave=None, crop_file=None, comment=None):
         """`crop` = (left, top, right, bottom): the box of camtools.py:213-231, cut during the upload.  `resave`: None,
         "reference" or a JPEG quality -- the reference's lossy re-save of the crop, reproduced on the device
-        (`Context.upload_bgr`)."""
+        (`Context.upload_bgr`).  `crop_file`: with `resave`, a path to write that re-saved crop to, the file the
+        reference's `img_crop.save(outpath)` writes: coded after the upload, written once the step is enqueued; `comment`: the source photo's comment, which
+        Pillow carries into that file (`jpeg.source_comment`, or `im.info.get("comment")`)."""
+        self._check_crop_file(resave, crop_file)
         s = self._next_slot()
         self.ctx.upload_bgr(s, frame, variant, crop, resave)
-        return self._step(s, wait)
+        data = self._crop_bytes(crop_file, comment)
+        seg = self._step(s, wait)
+        self._write_crop(crop_file, data)
+        return seg
 
-    def push_jpeg(self, jpeg, wait=True, variant=4, crop=None, resave=None):
+    def push_jpeg(self, jpeg, wait=True, variant=4, crop=None, resave=None, crop_file=None, comment=None):
         """A frame as `jpeg.read_jpeg` returns it (quantised DCT coefficients): decoded, cropped and turned to gray on
         the device; the step is the one `push_bgr` makes with the file's decoded pixels.  The file's `bytes` instead: the
-        Huffman decoding runs on the device as well (`Context.upload_jpeg_file`).  `resave`: as `push_bgr`."""
+        Huffman decoding runs on the device as well (`Context.upload_jpeg_file`).  `resave`, `crop_file`, `comment`: as
+        `push_bgr`."""
+        self._check_crop_file(resave, crop_file)
         s = self._next_slot()
         if isinstance(jpeg, (bytes, bytearray, memoryview)):
             self.ctx.upload_jpeg_file(s, jpeg, variant, crop, resave)
         else:
             self.ctx.upload_jpeg(s, jpeg, variant, crop, resave)
-        return self._step(s, wait)
+        data = self._crop_bytes(crop_file, comment)
+        seg = self._step(s, wait)
+        self._write_crop(crop_file, data)
+        return seg
 
     def push_device(self, dev_ptr, stride, wait=True):
         s = self._next_slot()

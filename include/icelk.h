@@ -538,6 +538,39 @@ int icelk_upload_jpeg_resave(icelk_t* h, int slot, const icelk_jpeg_info_t* info
 int icelk_upload_jpeg_file_resave(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left,
                                   int crop_top, int crop_right, int crop_bottom, int quality);
 
+/* ---- the re-saved crop as a file (opt-in) --------------------------------------------------------
+ * The bytes `img.save(path)` writes (Pillow, libjpeg at its defaults: baseline, the Huffman tables of T.81 Annex K.3, no
+ * restart intervals) are a function of the quantised coefficients: SOI, APP0 (JFIF 1.01, density 1 : 1 without a unit,
+ * whatever the source said: `crop().save()` carries neither dpi nor Exif over), one COM segment if a comment is given
+ * (comment != NULL; Pillow carries the source's last one over), one DQT segment per table slot, SOF0, one DHT segment per
+ * table in the order DC0, AC0, DC1, AC1, SOS, the scan with a 00 behind every FF and its last byte filled with 1-bits, EOI.
+ * Descriptors: laid out as icelk_jpeg_describe lays a file out; 1 component, or 3 with luma 1x1, 2x1 or 2x2; table slot 0
+ * is quant[0], slot 1 is quant[1], which quant[2] must equal (else ICELK_EUNSUP); restart_interval != 0 is ICELK_EUNSUP.
+ * A DC difference beyond +-2047 or an AC value beyond +-1023 has no code in those tables: ICELK_EARG, nothing is written.
+ * ICELK_ECAP: `out` is too small (or NULL) and *len says what the file takes -- or the scan has so many blocks that
+ * blocks * 1660 bits do not fit the 32 bits that bit offsets are carried in (2.58 million blocks; 12 MP have 281 000). */
+/* Host only, no handle, re-entrant: SOI up to the end of the SOS segment. */
+int icelk_jpeg_encode_header(const icelk_jpeg_info_t* info, const uint8_t* comment, uint64_t comment_len, uint8_t* out,
+                             uint64_t capacity, uint64_t* len);
+/* Host only, no handle, re-entrant: the whole file, the scan walked serially (csrc/jpeg_enc.h, the code of the device). */
+int icelk_jpeg_encode_coefficients_host(const icelk_jpeg_info_t* info, const int16_t* coef, const uint8_t* comment,
+                                        uint64_t comment_len, uint8_t* out, uint64_t capacity, uint64_t* len);
+/* Host only: icelk_jpeg_resave_coefficients_host, then the call above -- what Image.fromarray(rgb).save(f, "JPEG",
+ * quality=quality) writes. */
+int icelk_jpeg_resave_file_host(const uint8_t* rgb, int w, int h_, int stride, int quality, const uint8_t* comment,
+                                uint64_t comment_len, uint8_t* out, uint64_t capacity, uint64_t* len);
+/* icelk_jpeg_encode_coefficients_host on the device (csrc/k_jpeg_enc.hip): the coefficients are copied up and entropy-coded
+ * there; the same bytes and the same error codes.  For tests, and for coefficients from icelk_jpeg_read_coefficients. */
+int icelk_jpeg_encode_coefficients(icelk_t* h, const icelk_jpeg_info_t* info, const int16_t* coef, const uint8_t* comment,
+                                   uint64_t comment_len, uint8_t* out, uint64_t capacity, uint64_t* len);
+/* The file of the handle's most recent re-save -- the last call that ran the forward kernel: icelk_upload_bgr_resave,
+ * icelk_upload_jpeg_resave, icelk_upload_jpeg_file_resave, icelk_jpeg_resave_rgb, icelk_jpeg_resave_device_coefficients --
+ * coded straight from the coefficients that call left on the device.  No slot is touched.  ICELK_ESTATE: the handle has
+ * never re-saved.  After ICELK_ECAP the call can be repeated with a larger buffer: the coded scan is kept until the next
+ * re-save (or icelk_jpeg_encode_coefficients).  Buffers are allocated at first use and freed with the handle. */
+int icelk_jpeg_resave_encode(icelk_t* h, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity,
+                             uint64_t* len);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector

@@ -10,6 +10,7 @@
     python tools/jpeg_ingest.py e2e-pipeline [--frames 24] [--threads 16]         MI355X: pipeline=False against True
     python tools/jpeg_ingest.py pipeline-loop [--frames 24]                       MI355X: pipelined runs for a kernel trace
     python tools/jpeg_ingest.py resave [--frames 24] [--out profiles/jpeg_resave.txt]  MI355X: the reference's re-save of the crop
+    python tools/jpeg_ingest.py resave-file [--frames 24] [--out profiles/jpeg_resave_file.txt]  MI355X: ... written as files
 
 host    one thread, best of 5: `read_jpeg` (Huffman decoding into coefficients) against `np.array(Image.open(...))` (what
         the "pil" decoder does per photo), and Pillow's own 1/8-scale draft decode -- entropy decoding plus a DC-only
@@ -32,6 +33,12 @@ resave  `Context.upload_bgr(resave="reference")` on a 4000x3000 crop with profil
         (the forward half of the re-save) against its algorithmic bytes, and of k_jpeg_idct and k_jpeg_out on the re-saved
         coefficients; the three uploads by the host clock with and without the re-save; then photos per second of the
         folder driver with resave=None against resave="reference", alternating, three runs each.
+resave-file    the re-saved crop as a file (`Context.jpeg_resave_file`, csrc/k_jpeg_enc.hip) at quality 75 and 95: first the
+        yardstick, the reference's own step `Image.open -> crop -> save` per photo on one thread and on a pool of 16
+        processes (host only, before the GPU is touched); then 20 calls with profiling on: HIP-event time of every encoder
+        kernel against the bytes it moves, the whole call by the host clock split into kernels, the rest (two
+        synchronisations, the copy to the host, the header) and the file write; then photos per second of the folder
+        driver with resave="reference", without and with save_crops, alternating, three runs each.
 pipeline-loop  one plain and two pipelined runs of the same folder and nothing else, for `rocprofv3 --kernel-trace --stats --`.
 """
 import argparse
@@ -415,6 +422,117 @@ def resave(out, n, threads):
     os.rmdir(tmp)
 
 
+def _reference_step(args):
+    """camtools.py:64-104 for one photo: open, crop (the whole frame here), save at Pillow's defaults"""
+    src, dst = args
+    im = Image.open(src)
+    w, h = im.size
+    im.crop((0, 0, w, h)).save(dst)
+    return os.path.getsize(dst)
+
+
+def resave_file(out, n, threads):
+    import multiprocessing as mp
+    tmp, names = folder(n)
+    crops = os.path.join(tmp, "crops")
+    os.makedirs(crops)
+    jobs = [(p, os.path.join(crops, os.path.basename(p))) for p in names]
+    print("the re-saved crop as a file, %d photos of %dx%d 4:2:0 quality 90, %d usable cores" % (n, W, H, len(os.sched_getaffinity(0))), file=out)
+    print("yardstick, the reference's step on the host (Image.open -> crop -> save, quality 75), photos/s, three runs each:", file=out)
+    _reference_step(jobs[0])                                 # untimed
+    one = []
+    for _ in range(3):
+        t = time.perf_counter()
+        for j in jobs:
+            _reference_step(j)
+        one.append(n / (time.perf_counter() - t))
+    print("  one thread:          %s" % ", ".join("%.1f" % v for v in one), file=out)
+    with mp.get_context("fork").Pool(16) as pool:            # before this process touches the GPU
+        pool.map(_reference_step, jobs)
+        many = []
+        for _ in range(3):
+            t = time.perf_counter()
+            pool.map(_reference_step, jobs)
+            many.append(n / (time.perf_counter() - t))
+    print("  pool of 16 processes: %s" % ", ".join("%.1f" % v for v in many), file=out)
+    out.flush()
+
+    from iceberg_tracking_code_amd import Context
+    img = photo()
+    kernels = ("jpeg_enc_count", "jpeg_enc_scan", "jpeg_enc_pack", "jpeg_enc_ff", "jpeg_enc_stuff")
+    ctx = Context(W, H, n_slots=2, max_pts=64)
+    try:
+        for q in (75, 95):
+            want = io.BytesIO()
+            Image.fromarray(img).save(want, "JPEG", quality=q)
+            want = want.getvalue()
+            blocks = 6 * ((W + 15) // 16) * ((H + 15) // 16)
+            coef_b = 128 * blocks
+            for _ in range(3):
+                ctx.upload_bgr(0, img, 4, resave=q)
+                got = ctx.jpeg_resave_file()
+            ctx.prof_reset()
+            ctx.prof_enable(True)
+            reps, call, write = 20, [], []
+            for _ in range(reps):
+                ctx.upload_bgr(0, img, 4, resave=q)
+                t = time.perf_counter()
+                got = ctx.jpeg_resave_file()
+                call.append(time.perf_counter() - t)
+                t = time.perf_counter()
+                with open(os.path.join(crops, "one.jpg"), "wb") as f:
+                    f.write(got)
+                write.append(time.perf_counter() - t)
+            ctx.prof_enable(False)
+            tab = ctx.prof_table()
+            stream = len(got) - (got.index(b"\xff\xda") + 14) - 2   # header and EOI aside
+            packed = stream - got.count(b"\xff\x00")
+            moved = {"jpeg_enc_count": (coef_b, 2 * blocks), "jpeg_enc_scan": (4 * (blocks // 64), 4 * (blocks // 64)),
+                     "jpeg_enc_pack": (coef_b + 2 * blocks, packed), "jpeg_enc_ff": (packed, 4 * (packed // 16384 + 1)),
+                     "jpeg_enc_stuff": (packed, stream)}
+            print("quality %d: file %.2f MB, %s Pillow's; %d blocks; %d calls, HIP events around each kernel (scan runs twice per "
+                  "call: the bytes are the first's)" % (q, len(got) / 1e6, "equals" if got == want else "DIFFERS FROM", blocks, reps), file=out)
+            total = 0.0
+            for k in kernels:
+                us, launches = tab[k]["avg_us"], tab[k]["launches"]
+                total += us * launches / reps
+                rd, wr = moved[k]
+                print("  k_%-15s %7.1f us  reads %8.3f MB, writes %8.3f MB: %6.3f TB/s, %5.2f %% of 8 TB/s" %
+                      (k, us, rd / 1e6, wr / 1e6, (rd + wr) / us / 1e6, 100 * (rd + wr) / us / 1e6 / 8), file=out)
+            call, write = sorted(call), sorted(write)
+            print("  jpeg_resave_file() by the host clock, median of %d (min .. max): %.3f ms (%.3f .. %.3f); kernels %.3f ms; the rest "
+                  "(two synchronisations, %.2f MB to the host, header, bytes object) %.3f ms; file write %.3f ms (%.3f .. %.3f)" %
+                  (reps, 1e3 * call[reps // 2], 1e3 * call[0], 1e3 * call[-1], total / 1e3, len(got) / 1e6, 1e3 * call[reps // 2] - total / 1e3,
+                   1e3 * write[reps // 2], 1e3 * write[0], 1e3 * write[-1]), file=out)
+            out.flush()
+    finally:
+        ctx.close()
+    print("folder driver, decoder=\"device\", huffman=\"device\", resave=\"reference\", decode_threads %d: photos/s (runs in order)" % threads,
+          file=out)
+    run_folder(names, tmp, threads, resave="reference")      # untimed: cold files, code objects, clocks
+    run_folder(names, tmp, threads, resave="reference", save_crops=crops)   # ... and the writer's buffers
+    res, segs = {False: [], True: []}, {}
+    for rep_ in range(3):
+        for side in (False, True):
+            kw = dict(save_crops=crops) if side else {}
+            rate, got = run_folder(names, tmp, threads, resave="reference", **kw)
+            if segs and not same_tracks(got, segs[0]):
+                raise SystemExit("save_crops=%s: tracks differ" % side)
+            segs[0] = got
+            res[side].append(rate)
+    print("  without save_crops: %s" % ", ".join("%.1f" % v for v in res[False]), file=out)
+    print("  with save_crops:    %s" % ", ".join("%.1f" % v for v in res[True]), file=out)
+    print("  ratio of the medians: %.2f; tracks equal in every run; against the yardstick's medians: %.2f x one thread, %.2f x "
+          "the pool of 16 (the driver also decodes, re-saves, detects and tracks)" %
+          (sorted(res[True])[1] / sorted(res[False])[1], sorted(res[True])[1] / sorted(one)[1], sorted(res[True])[1] / sorted(many)[1]), file=out)
+    for f in os.listdir(crops):
+        os.remove(os.path.join(crops, f))
+    os.rmdir(crops)
+    for p in names:
+        os.remove(p)
+    os.rmdir(tmp)
+
+
 def encode_default(img):
     """Pillow's defaults, as the reference's crop pool saves"""
     b = io.BytesIO()
@@ -436,7 +554,7 @@ def pipeline_loop(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("mode", choices=("host", "device", "e2e", "huffman", "huffman-loop", "e2e-huffman", "e2e-pipeline",
-                                         "pipeline-loop", "resave"))
+                                         "pipeline-loop", "resave", "resave-file"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--threads", type=int, default=16)
@@ -445,7 +563,7 @@ def main():
         return huffman_loop()
     if a.mode == "pipeline-loop":
         return pipeline_loop(a.frames)
-    name = {"resave": "jpeg_resave", "huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e", "e2e-pipeline": "jpeg_pipeline_e2e"}.get(
+    name = {"resave": "jpeg_resave", "resave-file": "jpeg_resave_file", "huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e", "e2e-pipeline": "jpeg_pipeline_e2e"}.get(
         a.mode, "jpeg_ingest_%s" % a.mode)
     path = a.out or os.path.join(ROOT, "profiles", name + ".txt")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -460,6 +578,8 @@ def main():
             e2e(out, a.frames, min(a.threads, 16), compare="huffman")
         elif a.mode == "resave":
             resave(out, a.frames, min(a.threads, 16))
+        elif a.mode == "resave-file":
+            resave_file(out, a.frames, min(a.threads, 16))
         elif a.mode == "e2e-pipeline":
             pipeline(out, a.frames, min(a.threads, 16))
         else:
