@@ -9,6 +9,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f32p, u8p
+from .jpeg import (UnsupportedJpeg, _comment_args, _encode_call, _rgb3, _stats_dict, describe_jpeg, resave_coefficients,
+                   resave_quality)
 
 TERM_CRITERIA_COUNT = 1
 TERM_CRITERIA_MAX_ITER = 1
@@ -40,6 +42,11 @@ def _gray2d(img, name="image"):
     if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
         a = np.ascontiguousarray(a)
     return a
+
+
+def _crop4(crop):
+    """(left, top, right, bottom) pixels to drop as four ints; None: nothing is dropped"""
+    return (0, 0, 0, 0) if crop is None else tuple(int(v) for v in crop)
 
 
 def _criteria(criteria):
@@ -109,36 +116,25 @@ class Context:
         decoded frame.  `resave`: None -- pixel values are those of the frame -- or "reference" / a JPEG quality: the
         reference's lossy re-save of the crop (s1:272) is reproduced on the device, for a frame in R G B order, and the slot
         holds what `upload_bgr(slot, np.array(Image.open(re-saved crop)), variant)` leaves (icelk_upload_bgr_resave)."""
-        a = np.asarray(img)
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError("expected HxWx3 uint8 image")
+        a = _rgb3(img)                    # rows are dense; the row pitch of a cropped view is fine as it is
         if crop is not None:
-            left, top, right, bottom = (int(v) for v in crop)
+            left, top, right, bottom = _crop4(crop)
             if min(left, top, right, bottom) < 0 or left + right >= a.shape[1] or top + bottom >= a.shape[0]:
                 raise ValueError("crop box leaves no image")
             a = a[top:a.shape[0] - bottom, left:a.shape[1] - right]
-        if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
-            a = np.ascontiguousarray(a)   # rows must be dense; a row pitch (cropped view) is fine as it is
-        quality = self._resave_quality(resave)
+        quality = resave_quality(resave)
         if quality is not None:
             self._ck(self._lib.icelk_upload_bgr_resave(self._h, slot, _u8(a), a.shape[1], a.shape[0], a.strides[0], variant, quality))
             return
         self._ck(self._lib.icelk_upload_bgr(self._h, slot, _u8(a), a.shape[1], a.shape[0], a.strides[0], variant))
-
-    @staticmethod
-    def _resave_quality(resave):
-        if resave is None:
-            return None
-        from .jpeg import resave_quality
-        return resave_quality(resave)
 
     def upload_jpeg(self, slot, jpeg, variant=GRAY_CV4, crop=None, resave=None):
         """A file read by `jpeg.read_jpeg` -> gray in `slot`, exactly what `upload_bgr(slot, np.array(Image.open(f)),
         variant, crop, resave)` leaves there: inverse DCT, chroma upsampling, colour conversion, crop and gray run on the
         device (icelk_upload_jpeg); only the blocks the crop needs are transformed.  `resave`: as `upload_bgr`
         (icelk_upload_jpeg_resave)."""
-        left, top, right, bottom = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
-        quality = self._resave_quality(resave)
+        left, top, right, bottom = _crop4(crop)
+        quality = resave_quality(resave)
         if quality is not None:
             self._ck(self._lib.icelk_upload_jpeg_resave(self._h, slot, C.byref(jpeg.info), jpeg.coef_ptr, variant, left, top,
                                                         right, bottom, quality))
@@ -156,7 +152,6 @@ class Context:
     # -- JPEG files with the Huffman decoding on the device too (csrc/k_jpeg_huff.hip) ---------------
     def _ck_jpeg(self, rc):
         if rc == _lib.EUNSUP:
-            from .jpeg import UnsupportedJpeg
             raise UnsupportedJpeg("a JPEG file of a kind the device decoder does not take")
         self._ck(rc)
 
@@ -166,8 +161,8 @@ class Context:
         visit the host.  The same files are taken as by `read_jpeg`; others raise `UnsupportedJpeg`.  `resave`: as
         `upload_bgr` (icelk_upload_jpeg_file_resave)."""
         data = bytes(data)
-        left, top, right, bottom = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
-        quality = self._resave_quality(resave)
+        left, top, right, bottom = _crop4(crop)
+        quality = resave_quality(resave)
         if quality is not None:
             self._ck_jpeg(self._lib.icelk_upload_jpeg_file_resave(self._h, slot, data, len(data), variant, left, top, right,
                                                                   bottom, quality))
@@ -183,7 +178,7 @@ class Context:
             buf = (C.c_char * len(data)).from_buffer(data)   # as it is: the library takes its own copy
         else:
             buf = data = bytes(data)
-        left, top, right, bottom = (0, 0, 0, 0) if crop is None else (int(v) for v in crop)
+        left, top, right, bottom = _crop4(crop)
         self._ck_jpeg(self._lib.icelk_upload_jpeg_file_async(self._h, slot, buf, len(data), variant, left, top, right, bottom))
 
     def jpeg_async_poll(self, slot):
@@ -199,11 +194,10 @@ class Context:
         does; the slot then holds no frame."""
         st = _lib.JpegHuffStats()
         self._ck_jpeg(self._lib.icelk_jpeg_async_finish(self._h, slot, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in st._fields_ if k != "reserved"}
+        return _stats_dict(st)
 
     def jpeg_decode_rgb_file(self, data):
         """The decoded image of a JPEG file given as bytes, Huffman decoding included on the device."""
-        from .jpeg import describe_jpeg
         data = bytes(data)
         i = describe_jpeg(data)
         out = np.empty((i.height, i.width, 3) if i.ncomp == 3 else (i.height, i.width), np.uint8)
@@ -212,10 +206,7 @@ class Context:
 
     def jpeg_resave_rgb(self, rgb, quality=75):
         """H x W x 3 (R G B) uint8 -> the pixels of the image saved as JPEG at `quality` and opened again (`jpeg.resave_rgb`)."""
-        a = np.asarray(rgb)
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError("expected HxWx3 uint8 image")
-        a = np.ascontiguousarray(a)
+        a = np.ascontiguousarray(_rgb3(rgb))
         out = np.empty(a.shape, np.uint8)
         self._ck(self._lib.icelk_jpeg_resave_rgb(self._h, _u8(a), a.shape[1], a.shape[0], a.strides[0], int(quality), _u8(out),
                                                  out.strides[0]))
@@ -227,7 +218,6 @@ class Context:
         from the coefficients the re-save left there (icelk_jpeg_resave_encode).  No slot is touched.  `comment`: the
         source's comment (`jpeg.source_comment`), which Pillow carries over, or None.  IcelkError (code ICELK_ESTATE) when
         the handle has never re-saved."""
-        from .jpeg import _comment_args, _encode_call
         com, ncom = _comment_args(comment)
         guess = getattr(self, "_resave_file_guess", 1 << 16) + ncom
         data = _encode_call(lambda out, cap, n: self._lib.icelk_jpeg_resave_encode(self._h, com, ncom, out, cap, n), guess,
@@ -237,7 +227,6 @@ class Context:
 
     def jpeg_encode(self, info, coef_ptr, comment, comment_len, guess):
         """`jpeg.encode_jpeg` on the device (icelk_jpeg_encode_coefficients)."""
-        from .jpeg import _encode_call
         return _encode_call(lambda out, cap, n: self._lib.icelk_jpeg_encode_coefficients(self._h, C.byref(info), coef_ptr, comment,
                                                                                          comment_len, out, cap, n), guess,
                             "icelk_jpeg_encode_coefficients", self._h)
@@ -255,7 +244,6 @@ class Context:
 
     def jpeg_resave_device_coefficients(self, rgb, quality=75):
         """The coefficients `jpeg.resave_coefficients(rgb, quality).coef` as the device's forward kernel makes them, for tests."""
-        from .jpeg import resave_coefficients
         a = np.ascontiguousarray(rgb)
         coef = np.empty(resave_coefficients(a, quality).coef.size, np.int16)
         self._ck(self._lib.icelk_jpeg_resave_device_coefficients(self._h, _u8(a), a.shape[1], a.shape[0], a.strides[0], int(quality),
@@ -264,7 +252,6 @@ class Context:
 
     def jpeg_device_coefficients(self, data):
         """The quantised DCT coefficients of a JPEG file as the device decodes them (`read_jpeg(data).coef`), for tests."""
-        from .jpeg import describe_jpeg
         data = bytes(data)
         coef = np.empty(int(describe_jpeg(data).coef_count), np.int16)
         self._ck_jpeg(self._lib.icelk_jpeg_device_coefficients(self._h, data, len(data), C.c_void_p(coef.ctypes.data), coef.size))
@@ -280,7 +267,7 @@ class Context:
         fallback (0: none, 1: work bound, 2: a stream that contradicts itself, 3: size)."""
         st = _lib.JpegHuffStats()
         self._ck(self._lib.icelk_jpeg_huff_stats(self._h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in st._fields_ if k != "reserved"}
+        return _stats_dict(st)
 
     def set_gray_device(self, slot, dev_ptr, w, h, stride):
         self._ck(self._lib.icelk_set_gray_device(self._h, slot, C.c_void_p(dev_ptr), w, h, stride))

@@ -1,7 +1,7 @@
 // abi_jpeg.hip -- the host half of the JPEG ingest path: headers and Huffman decoding of a baseline file into quantised
 // DCT coefficients (icelk_jpeg_describe, icelk_jpeg_read_coefficients).  Host code only, no handle, no global state that
 // is written after start-up: the decode-ahead threads of sequence.py run it side by side.  The device half is k_jpeg.hip,
-// reached through icelk_upload_jpeg / icelk_jpeg_decode_rgb (abi_frames.hip).
+// reached through icelk_upload_jpeg / icelk_jpeg_decode_rgb (abi_jpeg_ingest.hip).
 //
 // For Huffman decoding on the device (k_jpeg_huff.hip) this file also locates the entropy-coded segments and packs the
 // tables (icelk_jpeg_index), and states the parallel algorithm of jpeg_lanes.h serially, phase by phase, on the CPU
@@ -109,6 +109,13 @@ void fill_layout(icelk_jpeg_info_t& I)
     I.coef_count = off;
 }
 
+// the component counts and luma sampling factors the decoder takes (chroma is 1 x 1)
+bool sampling_ok(int ncomp, int hs, int vs)
+{
+    if (ncomp == 1) return hs == 1 && vs == 1;
+    return ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2));
+}
+
 int parse_headers(const uint8_t* d, size_t len, Parsed& P)
 {
     memset(&P.I, 0, sizeof(P.I));
@@ -210,14 +217,10 @@ int parse_headers(const uint8_t* d, size_t len, Parsed& P)
         if (adobe && adobe_transform != 1) return ICELK_EUNSUP;
         if (!jfif && !adobe && comp_id[0] == 'R' && comp_id[1] == 'G' && comp_id[2] == 'B') return ICELK_EUNSUP;
         if (P.comp_hs[1] != 1 || P.comp_vs[1] != 1 || P.comp_hs[2] != 1 || P.comp_vs[2] != 1) return ICELK_EUNSUP;
-        const int hs = P.comp_hs[0], vs = P.comp_vs[0];
-        if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return ICELK_EUNSUP;
-        I.hmax = hs;
-        I.vmax = vs;
-    } else {
-        if (P.comp_hs[0] != 1 || P.comp_vs[0] != 1) return ICELK_EUNSUP;
-        I.hmax = I.vmax = 1;
     }
+    if (!sampling_ok(I.ncomp, P.comp_hs[0], P.comp_vs[0])) return ICELK_EUNSUP;
+    I.hmax = P.comp_hs[0];
+    I.vmax = P.comp_vs[0];
     if (I.width < 3) return ICELK_EUNSUP;   // libjpeg's own result depends on its padding when a chroma plane is one sample wide
     fill_layout(I);
     for (int c = 0; c < I.ncomp; c++) memcpy(I.quant[c], P.qt[comp_tq[c]], sizeof(I.quant[c]));
@@ -478,6 +481,17 @@ int jpeg_index(const uint8_t* d, size_t len, JpegIndex& X)
     return ICELK_OK;
 }
 
+// jpeg_index, or the news that only the serial decoder takes the file: the lanes' positions are 32 bits, so for a file of
+// 256 MiB or more *host_only is set and *info alone is filled (icelk_jpeg_describe)
+int jpeg_open_core(const uint8_t* data, uint64_t len, JpegIndex& X, icelk_jpeg_info_t* info, bool* host_only)
+{
+    int rc = jpeg_index(data, (size_t)len, X);
+    *host_only = rc == ICELK_EUNSUP && len >= ((uint64_t)1 << 28);
+    if (*host_only) return icelk_jpeg_describe(data, len, info);
+    if (!rc) *info = X.info;
+    return rc;
+}
+
 // cuts the segments into lanes of S bits
 void jpeg_index_lanes(JpegIndex& X, uint32_t S, int max_hops)
 {
@@ -615,13 +629,7 @@ bool lanes_decode_host(const uint8_t* data, JpegIndex& X, int max_rounds, int16_
 bool jpeg_info_ok(const icelk_jpeg_info_t& in)
 {
     if (in.width < 3 || in.height < 1 || in.width > 65535 || in.height > 65535) return false;
-    if (in.ncomp == 1) {
-        if (in.hmax != 1 || in.vmax != 1) return false;
-    } else if (in.ncomp == 3) {
-        if (!((in.hmax == 1 && in.vmax == 1) || (in.hmax == 2 && in.vmax == 1) || (in.hmax == 2 && in.vmax == 2))) return false;
-    } else {
-        return false;
-    }
+    if (!sampling_ok(in.ncomp, in.hmax, in.vmax)) return false;
     icelk_jpeg_info_t t = in;
     fill_layout(t);
     if (t.mcus_x != in.mcus_x || t.mcus_y != in.mcus_y || t.coef_count != in.coef_count) return false;
@@ -701,9 +709,10 @@ int icelk_jpeg_read_coefficients_lanes(const uint8_t* data, uint64_t len, int16_
     memset(&st, 0, sizeof(st));
     JpegIndex* X = new (std::nothrow) JpegIndex;
     if (!X) return ICELK_ENOMEM;
-    int rc = jpeg_index(data, (size_t)len, *X);
-    if (rc == ICELK_EUNSUP && len >= ((uint64_t)1 << 28)) {
-        // too long for 32-bit bit positions: the serial decoder takes it
+    icelk_jpeg_info_t info;
+    bool host_only = false;
+    int rc = jpeg_open_core(data, len, *X, &info, &host_only);
+    if (host_only) {
         delete X;
         st.fallback = ICELK_JPEG_FALLBACK_SIZE;
         if (stats) *stats = st;

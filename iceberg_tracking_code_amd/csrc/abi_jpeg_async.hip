@@ -1,6 +1,6 @@
 // abi_jpeg_async.hip -- JPEG files decoded ahead of their frame: icelk_upload_jpeg_file_async / _poll / _finish.
 //
-// icelk_upload_jpeg_file (abi_frames.hip) decodes on the compute stream and has the host look at the decoder's flags
+// icelk_upload_jpeg_file (abi_jpeg_ingest.hip) decodes on the compute stream and has the host look at the decoder's flags
 // three times per file, so a photo's decoding never runs beside the tracker step of the photo before it.  Here the same
 // kernels go out in one piece on a decode stream of their own, into a slot the frame loop reaches later:
 //
@@ -97,34 +97,11 @@ static int decode_stream(Ctx* c, hipStream_t* out)
     return ICELK_OK;
 }
 
-// inverse DCT and output kernel of job B into its slot's level 0, then the slot's events: the slot is left as
-// icelk_upload_gray_async leaves it
+// inverse DCT and output kernel of job B into its slot's level 0, on the job's stream
 static int transform_into_slot(Ctx* c, Ctx::JpegJob& B)
 {
-    Slot& s = c->slots[B.slot];
-    {
-        ProfScope p(c, K_JPEG_IDCT, B.st);
-        launch_jpeg_idct(B.st, B.idct);
-    }
-    if (int rc = check_launch(c, "jpeg_idct")) return rc;
-    JpegOutArgs O = B.out;
-    O.dst = s.lv[0].ptr;
-    O.dst_pitch = s.lv[0].pitch;
-    {
-        ProfScope p(c, K_JPEG_OUT, B.st);
-        launch_jpeg_gray(B.st, O, B.variant);
-    }
-    return check_launch(c, "jpeg_out");
-}
-
-static int record_frame(Ctx* c, Ctx::JpegJob& B)
-{
-    Slot& s = c->slots[B.slot];
-    HIPCHK(c, hipEventRecord(s.ready, B.st));
-    HIPCHK(c, hipEventRecord(s.frame_ev, B.st));
-    s.pending = true;
-    s.levels_built = 1;
-    return ICELK_OK;
+    if (int rc = jpeg_idct_on(c, B.st, B.idct)) return rc;
+    return jpeg_gray_on(c, B.st, B.out, c->slots[B.slot], B.variant);
 }
 
 // the job leaves its slot; `state`: what icelk_jpeg_async_poll keeps answering for the slot
@@ -173,28 +150,18 @@ static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uin
     B.slot = slot;
     Slot& s = c->slots[slot];
     const hipStream_t st = B.st;
-    // the output kernel must not overtake the launches that still read this slot (as icelk_upload_gray_async)
-    if (int rc = wait_event(c, st, s.used)) return rc;
-    if (s.pending) if (int rc = wait_event(c, st, s.ready)) return rc;
-    if (int rc = wait_event(c, st, s.det_used)) return rc;
-    if (int rc = wait_event(c, st, s.eig_used)) return rc;
+    if (int rc = foreign_write_begin(c, s, st)) return rc;   // the slot is left as icelk_upload_gray_async leaves it
     if (host_only) return ICELK_OK;   // nothing goes out before finish, which has the host decoder take the file
     memcpy(B.h_stage, X.tabs, sizeof(X.tabs));
     memcpy(B.h_stage + sizeof(X.tabs), X.seg.data(), seg_bytes);
     B.segments = X.scan.nseg;
     B.subsequences = X.scan.nlanes;
-    HIPCHK(c, hipMemcpyAsync(B.d_file, B.h_stage + file_off, (size_t)len, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(B.d_seg, B.h_stage + sizeof(X.tabs), seg_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(B.d_tabs, B.h_stage, sizeof(X.tabs), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(B.d_ctl, 0, JH_WORDS * sizeof(uint32_t), st));
-    HIPCHK(c, hipMemsetAsync(B.d_coef, 0, (size_t)B.info.coef_count * sizeof(int16_t), st));
+    if (int rc = jpeg_huff_stage(c, B, X, B.h_stage + file_off, B.h_stage + sizeof(X.tabs), B.h_stage, len, st)) return rc;
     {
         // every round at once: one that no group takes part in returns after two loads per workgroup
         ProfScope p(c, K_JPEG_HUFF, st);
         for (int q = 0; q <= J.max_rounds; q++) launch_jpeg_huff_sync(st, H, q);
-        launch_jpeg_huff_scan(st, H);
-        launch_jpeg_huff_write(st, H);
-        launch_jpeg_huff_dc(st, H);
+        jpeg_huff_finish_phases(st, H);
     }
     if (int rc = check_launch(c, "jpeg_huff")) return rc;
     if (int rc = transform_into_slot(c, B)) return rc;
@@ -202,7 +169,7 @@ static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uin
     launch_jpeg_huff_verdict(st, B.d_ctl, J.max_rounds, B.h_verdict, B.seq);
     if (int rc = check_launch(c, "jpeg_huff_verdict")) return rc;
     HIPCHK(c, hipEventRecord(B.done, st));
-    return record_frame(c, B);
+    return foreign_write_end(c, s, st);
 }
 
 static inline bool verdict_here(const Ctx::JpegJob& B)
@@ -234,16 +201,9 @@ static int await_verdict(Ctx* c, Ctx::JpegJob& B)
 static int host_takes_job(Ctx* c, Ctx::JpegJob& B)
 {
     std::vector<int16_t> host;
-    try {
-        host.resize((size_t)B.info.coef_count);
-    } catch (...) {
-        FAIL(c, ICELK_ENOMEM, "no memory for the coefficients");
-    }
-    if (int rc = jpeg_host_decode(B.h_stage + B.file_off, (size_t)B.len, host.data(), B.info.coef_count))
-        FAIL(c, rc, "not a JPEG file, or a damaged one");
-    HIPCHK(c, hipMemcpyAsync(B.d_coef, host.data(), host.size() * sizeof(int16_t), hipMemcpyHostToDevice, B.st));
+    if (int rc = jpeg_host_into_job(c, B, B.h_stage + B.file_off, B.len, B.info, B.st, host)) return rc;
     if (int rc = transform_into_slot(c, B)) return rc;
-    if (int rc = record_frame(c, B)) return rc;
+    if (int rc = foreign_write_end(c, c->slots[B.slot], B.st)) return rc;
     HIPCHK(c, hipStreamSynchronize(B.st));   // `host` is free again, and so is everything the job owns
     return ICELK_OK;
 }
@@ -269,7 +229,7 @@ int icelk_upload_jpeg_file_async(icelk_t* h, int slot, const uint8_t* data, uint
     if (!h) return ICELK_EARG;
     Ctx* c = C(h);
     Range rg("icelk upload_jpeg_file_async");
-    if (gray_variant != ICELK_GRAY_CV3 && gray_variant != ICELK_GRAY_CV4) FAIL(c, ICELK_EARG, "bad gray variant");
+    if (int rc = check_gray_variant(c, gray_variant)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     Ctx::JpegJob* old = nullptr;
     if (int rc = job_of(c, slot, &old)) return rc;
@@ -284,16 +244,8 @@ int icelk_upload_jpeg_file_async(icelk_t* h, int slot, const uint8_t* data, uint
     } drop{X};
     icelk_jpeg_info_t info;
     bool host_only = false;
-    int rc = jpeg_index(data, (size_t)len, *X);
-    if (rc == ICELK_EUNSUP && len >= ((uint64_t)1 << 28)) {
-        // the lanes' positions are 32 bits: such a file takes the host decoder at once
-        rc = icelk_jpeg_describe(data, len, &info);
-        if (rc) FAIL(c, rc, "not a JPEG file the decoder takes");
-        host_only = true;
-    } else {
-        if (rc) FAIL(c, rc, rc == ICELK_EUNSUP ? "a JPEG file of a kind the decoder does not take" : "not a JPEG file, or a damaged one");
-        info = X->info;
-    }
+    int rc = jpeg_open(c, data, len, *X, &info, &host_only);
+    if (rc) return rc;
     if (info.ncomp != 3) FAIL(c, ICELK_EARG, "expected a 3-component JPEG file");
     if (J.slot_job.empty()) {
         if (const char* e = getenv("ICELK_JPEG_ASYNC_STREAMS")) J.dec_streams = atoi(e) == 1 ? 1 : 2;

@@ -43,7 +43,7 @@ int resave_check(Ctx* c, int w, int h, int quality)
 
 int resave_slot_check(Ctx* c, int slot, int w, int h, int quality, int gray_variant)
 {
-    if (gray_variant != ICELK_GRAY_CV3 && gray_variant != ICELK_GRAY_CV4) FAIL(c, ICELK_EARG, "bad gray variant");
+    if (int rc = check_gray_variant(c, gray_variant)) return rc;
     if (int rc = check_slot(c, slot, false)) return rc;
     if (int rc = resave_check(c, w, h, quality)) return rc;
     if (w > c->max_w || h > c->max_h) FAIL(c, ICELK_ECAP, "frame larger than max_w x max_h of icelk_create");
@@ -51,6 +51,14 @@ int resave_slot_check(Ctx* c, int slot, int w, int h, int quality, int gray_vari
 }
 
 int grow_src(Ctx* c, int w, int h) { return grow(c, &c->jpeg.d_src, &c->jpeg.src_cap, (size_t)3 * w * h); }
+
+// a host image in R G B order -> d_src
+int rgb_to_src(Ctx* c, const uint8_t* rgb, int w, int h, int stride)
+{
+    if (int rc = grow_src(c, w, h)) return rc;
+    HIPCHK(c, hipMemcpy2DAsync(c->jpeg.d_src, 3 * (size_t)w, rgb, stride, 3 * (size_t)w, h, hipMemcpyHostToDevice, c->stream));
+    return ICELK_OK;
+}
 
 // d_src (w x h, rows 3 w bytes apart) -> the re-saved file's coefficients in the re-save job's d_coef; with_planes: and
 // its component planes, `O` ready for k_jpeg_out
@@ -84,11 +92,7 @@ int resave_forward(Ctx* c, int w, int h, int quality, icelk_jpeg_info_t* I, Jpeg
     c->jpeg.enc.stream_ok = false;
     c->jpeg.enc.info = *I;
     if (!with_planes) return ICELK_OK;
-    {
-        ProfScope p(c, K_JPEG_IDCT);
-        launch_jpeg_idct(c->stream, D);
-    }
-    return check_launch(c, "jpeg_idct");
+    return jpeg_idct_on(c, c->stream, D);
 }
 
 // the tail of the three uploads: d_src -> gray of the re-saved image in `slot`
@@ -96,21 +100,8 @@ int resave_into_slot(Ctx* c, int slot, int w, int h, int quality, int gray_varia
 {
     icelk_jpeg_info_t I;
     JpegOutArgs O{};
-    int rc = resave_forward(c, w, h, quality, &I, &O);
-    if (rc) return rc;
-    rc = begin_frame(c, slot, w, h);
-    if (rc) return rc;
-    Slot& s = c->slots[slot];
-    O.dst = s.lv[0].ptr;
-    O.dst_pitch = s.lv[0].pitch;
-    {
-        ProfScope p(c, K_JPEG_OUT);
-        launch_jpeg_gray(c->stream, O, gray_variant);
-    }
-    rc = check_launch(c, "jpeg_out");
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller's buffer is free again
-    return end_frame(c, s);
+    if (int rc = resave_forward(c, w, h, quality, &I, &O)) return rc;
+    return planes_to_gray_slot(c, slot, O, gray_variant);   // O.ow x O.oh is w x h
 }
 
 // the cropped R G B of a decoded file (planes of the synchronous job, `O` of jpeg_planes) -> d_src
@@ -125,17 +116,13 @@ int planes_to_src(Ctx* c, JpegOutArgs& O)
     return check_launch(c, "jpeg_out");
 }
 
-// the crop box of a described file, as jpeg_plane_args checks it; the cropped size
+// descriptor and crop box of a described file, as jpeg_plane_args checks them; the cropped size
 int cropped_size(Ctx* c, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, int* w, int* h)
 {
     if (!I) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
     if (I->ncomp != 3) FAIL(c, ICELK_EARG, "expected a 3-component JPEG file");
     if (!jpeg_info_ok(*I)) FAIL(c, ICELK_EARG, "JPEG descriptor does not describe a supported file");
-    if (left < 0 || top < 0 || right < 0 || bottom < 0 || (long long)left + right >= I->width || (long long)top + bottom >= I->height)
-        FAIL(c, ICELK_EARG, "crop box leaves no image");
-    *w = I->width - left - right;
-    *h = I->height - top - bottom;
-    return ICELK_OK;
+    return check_crop_box(c, *I, left, top, right, bottom, w, h);
 }
 
 }  // namespace
@@ -174,8 +161,7 @@ int icelk_jpeg_resave_rgb(icelk_t* h, const uint8_t* rgb, int w, int h_, int str
     if (!rgb || !out || stride < 3 * w || out_stride < 3 * w) FAIL(c, ICELK_EARG, "bad host image");
     if (int rc = resave_check(c, w, h_, quality)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = grow_src(c, w, h_)) return rc;
-    HIPCHK(c, hipMemcpy2DAsync(c->jpeg.d_src, 3 * (size_t)w, rgb, stride, 3 * (size_t)w, h_, hipMemcpyHostToDevice, c->stream));
+    if (int rc = rgb_to_src(c, rgb, w, h_, stride)) return rc;
     icelk_jpeg_info_t I;
     JpegOutArgs O{};
     if (int rc = resave_forward(c, w, h_, quality, &I, &O)) return rc;
@@ -193,8 +179,7 @@ int icelk_jpeg_resave_device_coefficients(icelk_t* h, const uint8_t* rgb, int w,
     resave_info(w, h_, quality, &I);
     if (capacity < I.coef_count) FAIL(c, ICELK_ECAP, "coefficient buffer too small");
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = grow_src(c, w, h_)) return rc;
-    HIPCHK(c, hipMemcpy2DAsync(c->jpeg.d_src, 3 * (size_t)w, rgb, stride, 3 * (size_t)w, h_, hipMemcpyHostToDevice, c->stream));
+    if (int rc = rgb_to_src(c, rgb, w, h_, stride)) return rc;
     JpegOutArgs O{};
     if (int rc = resave_forward(c, w, h_, quality, &I, &O, false)) return rc;
     HIPCHK(c, hipMemcpyAsync(coef, c->jpeg.resave.d_coef, (size_t)I.coef_count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
@@ -209,8 +194,7 @@ int icelk_upload_bgr_resave(icelk_t* h, int slot, const uint8_t* host, int w, in
     if (!host || stride < 3 * w) FAIL(c, ICELK_EARG, "bad host image");
     if (int rc = resave_slot_check(c, slot, w, h_, quality, gray_variant)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = grow_src(c, w, h_)) return rc;
-    HIPCHK(c, hipMemcpy2DAsync(c->jpeg.d_src, 3 * (size_t)w, host, stride, 3 * (size_t)w, h_, hipMemcpyHostToDevice, c->stream));
+    if (int rc = rgb_to_src(c, host, w, h_, stride)) return rc;
     return resave_into_slot(c, slot, w, h_, quality, gray_variant);
 }
 
@@ -238,8 +222,7 @@ int icelk_upload_jpeg_file_resave(icelk_t* h, int slot, const uint8_t* data, uin
     Ctx* c = C(h);
     if (!data) FAIL(c, ICELK_EARG, "null JPEG file");
     icelk_jpeg_info_t I;
-    if (int rc = icelk_jpeg_describe(data, len, &I))
-        FAIL(c, rc, rc == ICELK_EUNSUP ? "a JPEG file of a kind the decoder does not take" : "not a JPEG file, or a damaged one");
+    if (int rc = icelk_jpeg_describe(data, len, &I)) FAIL(c, rc, jpeg_open_error(rc));
     int w = 0, h_ = 0;
     if (int rc = cropped_size(c, &I, crop_left, crop_top, crop_right, crop_bottom, &w, &h_)) return rc;
     if (int rc = resave_slot_check(c, slot, w, h_, quality, gray_variant)) return rc;

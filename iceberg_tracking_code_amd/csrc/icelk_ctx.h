@@ -60,7 +60,7 @@ struct Ctx {
     int prof_launches[K_COUNT_] = {0};
     double prof_ms[K_COUNT_] = {0};
 
-    // ---- abi_frames.hip: frame slots, pyramids, ingest
+    // ---- abi_frames.hip: frame slots, pyramids, ingest (the JPEG jobs: abi_jpeg_ingest.hip and the files behind it)
     std::vector<Slot> slots;
     // the streams of icelk_upload_gray_async, created at the first such upload.  Uploads alternate between two streams:
     // between two copies of ONE stream the runtime spends ~50 us (completion signal of the first, dependency of the
@@ -377,6 +377,12 @@ struct ProfScope {
     bool on = false;
 };
 
+inline int check_gray_variant(Ctx* c, int gray_variant)
+{
+    if (gray_variant != ICELK_GRAY_CV3 && gray_variant != ICELK_GRAY_CV4) FAIL(c, ICELK_EARG, "bad gray variant");
+    return ICELK_OK;
+}
+
 inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 template <typename T>
@@ -462,14 +468,9 @@ int wait_slot(Ctx* c, int slot);
 int ensure_pyramid(Ctx* c, int slot, int top_level);
 Pyramid pyramid_of(const Slot& s);
 int begin_frame(Ctx* c, int slot, int w, int h);
-int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* A,
-                    JpegOutArgs* out);
-int jpeg_huff_setup(Ctx* c, Ctx::JpegJob& B, const struct JpegIndex& X, uint64_t len, JpegHuffArgs* H, bool headroom);
 int end_frame(Ctx* c, Slot& s);
-int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int left, int top, int right, int bottom, JpegOutArgs* out,
-                bool on_device = false);
-int jpeg_rgb_out(Ctx* c, const icelk_jpeg_info_t& I, JpegOutArgs& O, uint8_t* out, int stride);
-int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info);
+int foreign_write_begin(Ctx* c, Slot& s, hipStream_t st);
+int foreign_write_end(Ctx* c, Slot& s, hipStream_t st);
 // abi_jpeg.hip
 bool jpeg_info_ok(const icelk_jpeg_info_t& in);
 struct JpegIndex {   // a file as the lanes of jpeg_lanes.h see it
@@ -479,9 +480,29 @@ struct JpegIndex {   // a file as the lanes of jpeg_lanes.h see it
     std::vector<lanes::Seg> seg;   // scan.nseg + 1
 };
 int jpeg_index(const uint8_t* d, size_t len, JpegIndex& X);
+int jpeg_open_core(const uint8_t* data, uint64_t len, JpegIndex& X, icelk_jpeg_info_t* info, bool* host_only);
 void jpeg_index_lanes(JpegIndex& X, uint32_t S, int max_hops);
 bool jpeg_huff_config_ok(int subseq_bits, int max_hops, int max_rounds);
 int jpeg_host_decode(const uint8_t* data, size_t len, int16_t* coef, uint64_t capacity);
+// abi_jpeg_ingest.hip: the ingest steps (listed at the head of that file)
+int check_crop_box(Ctx* c, const icelk_jpeg_info_t& I, int left, int top, int right, int bottom, int* w, int* h);
+int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* A,
+                    JpegOutArgs* out);
+int jpeg_idct_on(Ctx* c, hipStream_t st, const JpegIdctArgs& A);
+int jpeg_gray_on(Ctx* c, hipStream_t st, JpegOutArgs O, const Slot& s, int gray_variant);
+int planes_to_gray_slot(Ctx* c, int slot, const JpegOutArgs& O, int gray_variant);
+int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int left, int top, int right, int bottom, JpegOutArgs* out,
+                bool on_device = false);
+int jpeg_rgb_out(Ctx* c, const icelk_jpeg_info_t& I, JpegOutArgs& O, uint8_t* out, int stride);
+const char* jpeg_open_error(int rc);
+int jpeg_open(Ctx* c, const uint8_t* data, uint64_t len, JpegIndex& X, icelk_jpeg_info_t* info, bool* host_only);
+int jpeg_host_into_job(Ctx* c, Ctx::JpegJob& J, const uint8_t* data, uint64_t len, const icelk_jpeg_info_t& I, hipStream_t st,
+                       std::vector<int16_t>& keep);
+int jpeg_huff_setup(Ctx* c, Ctx::JpegJob& B, const JpegIndex& X, uint64_t len, JpegHuffArgs* H, bool headroom);
+int jpeg_huff_stage(Ctx* c, Ctx::JpegJob& J, const JpegIndex& X, const uint8_t* file, const void* seg, const void* tabs, uint64_t len,
+                    hipStream_t st);
+void jpeg_huff_finish_phases(hipStream_t st, const JpegHuffArgs& H);
+int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info);
 // abi_jpeg_resave.hip
 void jpeg_resave_destroy(Ctx* c);
 // abi_jpeg_enc.hip

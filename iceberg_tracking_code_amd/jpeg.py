@@ -69,6 +69,11 @@ def _check(rc, what):
     raise ValueError("%s: not a JPEG file, or a damaged one (icelk error %d)" % (what, rc))
 
 
+def _stats_dict(st):
+    """an icelk_jpeg_huff_stats_t as `Context.jpeg_huff_stats` returns it"""
+    return {k: int(getattr(st, k)) for k, _ in st._fields_ if k != "reserved"}
+
+
 def describe_jpeg(data):
     """The icelk_jpeg_info_t of a file given as bytes."""
     data = bytes(data)
@@ -109,7 +114,7 @@ def read_jpeg_lanes(data, subseq_bits=512, max_hops=256, max_rounds=8):
     _check(lib.icelk_jpeg_read_coefficients_lanes(data, len(data), C.c_void_p(coef.ctypes.data), coef.size, int(subseq_bits),
                                                   int(max_hops), int(max_rounds), C.byref(st)),
            "icelk_jpeg_read_coefficients_lanes")
-    return JpegCoefficients(info, coef), {k: int(getattr(st, k)) for k, _ in st._fields_ if k != "reserved"}
+    return JpegCoefficients(info, coef), _stats_dict(st)
 
 
 def decode_jpeg(data, ctx=None, huffman="host"):

@@ -28,68 +28,26 @@ import numpy as np
 from .tracker import REF_FEATURE_PARAMS, REF_LK_PARAMS, SegmentTracker, npz_name, save_tracks, segment_time_ok
 
 
-def _decode(path):
-    from PIL import Image
-    return np.array(Image.open(path))                     # s1:310 (RGB order; cvtColor is asked for BGR2GRAY)
-
-
-def _read(path):
-    """decoder="device": the host stage only.  A file the device decoder does not take (progressive, CMYK, gray, ...) or
-    cannot parse is decoded by PIL instead -- that file only; PIL then also is the one to complain about a broken file."""
-    from .jpeg import read_jpeg
-    try:
-        j = read_jpeg(path)
-        if j.ncomp == 3:
-            return j
-    except ValueError:                                    # UnsupportedJpeg is one
-        pass
-    return _decode(path)
-
-
-def _read_bytes(path):
-    """decoder="device", huffman="device": the pool thread reads the file and its headers; a file the device decoder
-    does not take goes through PIL, as in `_read`."""
-    from .jpeg import describe_jpeg
-    try:
-        with open(path, "rb") as f:
-            data = f.read()
-        if describe_jpeg(data).ncomp == 3:
-            return data
-    except ValueError:
-        pass
-    return _decode(path)
-
-
-# the same loaders with the photo's comment (Pillow's `im.info.get("comment")`: `crop().save()` carries it into the crop's file)
-def _decode_c(path):
+def _load(path, kind, with_comment):
+    """What a pool thread makes of one photo.  kind "pixels": `np.array(Image.open(path))` (s1:310; RGB order, cvtColor is
+    asked for BGR2GRAY).  "coefficients" (decoder="device"): the host stage only, `jpeg.read_jpeg`.  "bytes"
+    (huffman="device" on top): the file as it is, its headers looked at.  A file the device decoder does not take
+    (progressive, CMYK, gray, ...) or cannot parse is decoded by PIL instead -- that file only; PIL then also is the one to
+    complain about a broken file.  with_comment: (frame, the photo's comment), Pillow's `im.info.get("comment")`, which
+    `crop().save()` carries into the crop's file."""
+    if kind != "pixels":
+        from .jpeg import describe_jpeg, read_jpeg, source_comment
+        try:
+            with open(path, "rb") as f:
+                data = f.read()
+            frame = read_jpeg(data) if kind == "coefficients" else data
+            if (frame.ncomp if kind == "coefficients" else describe_jpeg(data).ncomp) == 3:
+                return (frame, source_comment(data)) if with_comment else frame
+        except ValueError:                                # UnsupportedJpeg is one
+            pass
     from PIL import Image
     im = Image.open(path)
-    return np.array(im), im.info.get("comment")
-
-
-def _read_c(path):
-    from .jpeg import read_jpeg, source_comment
-    try:
-        with open(path, "rb") as f:
-            data = f.read()
-        j = read_jpeg(data)
-        if j.ncomp == 3:
-            return j, source_comment(data)
-    except ValueError:
-        pass
-    return _decode_c(path)
-
-
-def _read_bytes_c(path):
-    from .jpeg import describe_jpeg, source_comment
-    try:
-        with open(path, "rb") as f:
-            data = f.read()
-        if describe_jpeg(data).ncomp == 3:
-            return data, source_comment(data)
-    except ValueError:
-        pass
-    return _decode_c(path)
+    return (np.array(im), im.info.get("comment")) if with_comment else np.array(im)
 
 
 def _image_size(path, decoder):
@@ -101,7 +59,7 @@ def _image_size(path, decoder):
             return info.width, info.height
         except ValueError:
             pass
-    first = _decode(path)
+    first = _load(path, "pixels", False)
     return first.shape[1], first.shape[0]
 
 
@@ -167,9 +125,11 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
     if crop is not None:
         left, top, right, bottom = (int(v) for v in crop)
         w, h = w - left - right, h - top - bottom
-    load = (_read_bytes if huffman == "device" else _read) if decoder == "device" else _decode
+    kind = ("bytes" if huffman == "device" else "coefficients") if decoder == "device" else "pixels"
+
+    def load(path):
+        return _load(path, kind, save_crops is not None)
     if save_crops is not None:
-        load = {_read_bytes: _read_bytes_c, _read: _read_c, _decode: _decode_c}[load]
         os.makedirs(save_crops, exist_ok=True)
     written = set()                                       # photos whose crop has been written
     trk = None
@@ -196,14 +156,14 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                                 try:
                                     trk.prefetch_jpeg(frame, variant=gray_variant, crop=crop)
                                 except ValueError:        # what the host sees of an unsupported or damaged file ...
-                                    trk.prefetch_bgr(_decode(names[fed]), variant=gray_variant, crop=crop)
+                                    trk.prefetch_bgr(_load(names[fed], "pixels", False), variant=gray_variant, crop=crop)
                             else:
                                 trk.prefetch_bgr(frame, variant=gray_variant, crop=crop)
                             fed += 1
                         try:
                             seg = trk.push_prefetched()
                         except ValueError:                # ... and what only the decoder sees: PIL has the word
-                            trk.replace_prefetched_bgr(_decode(names[counter]), variant=gray_variant, crop=crop)
+                            trk.replace_prefetched_bgr(_load(names[counter], "pixels", False), variant=gray_variant, crop=crop)
                             seg = trk.push_prefetched()
                     else:
                         frame = pending.pop(0).result()
@@ -218,7 +178,7 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                             try:
                                 seg = trk.push_jpeg(frame, **kw)
                             except ValueError:            # unsupported or damaged, that file only: PIL has the word
-                                seg = trk.push_bgr(_decode(names[counter]), **kw)
+                                seg = trk.push_bgr(_load(names[counter], "pixels", False), **kw)
                         elif isinstance(frame, np.ndarray):
                             seg = trk.push_bgr(frame, **kw)
                         else:

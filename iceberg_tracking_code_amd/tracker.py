@@ -126,10 +126,16 @@ class SegmentTracker:
             with open(crop_file, "wb") as f:
                 f.write(data)
 
-    @staticmethod
-    def _check_crop_file(resave, crop_file):
+    def _push_upload(self, upload, frame, wait, variant, crop, resave, crop_file, comment):
+        """The body of `push_bgr` and `push_jpeg`: `upload` is the Context method that fills the slot."""
         if crop_file is not None and resave is None:
             raise ValueError("crop_file needs resave: the file written is the re-saved crop")
+        s = self._next_slot()
+        upload(s, frame, variant, crop, resave)
+        data = self._crop_bytes(crop_file, comment)
+        seg = self._step(s, wait)
+        self._write_crop(crop_file, data)
+        return seg
 
     def push_bgr(self, frame, wait=True, variant=4, crop=None, resave=None, crop_file=None, comment=None):
         """`crop` = (left, top, right, bottom): the box of camtools.py:213-231, cut during the upload.  `resave`: None,
@@ -137,29 +143,15 @@ class SegmentTracker:
         (`Context.upload_bgr`).  `crop_file`: with `resave`, a path to write that re-saved crop to, the file the
         reference's `img_crop.save(outpath)` writes: coded after the upload, written once the step is enqueued; `comment`: the source photo's comment, which
         Pillow carries into that file (`jpeg.source_comment`, or `im.info.get("comment")`)."""
-        self._check_crop_file(resave, crop_file)
-        s = self._next_slot()
-        self.ctx.upload_bgr(s, frame, variant, crop, resave)
-        data = self._crop_bytes(crop_file, comment)
-        seg = self._step(s, wait)
-        self._write_crop(crop_file, data)
-        return seg
+        return self._push_upload(self.ctx.upload_bgr, frame, wait, variant, crop, resave, crop_file, comment)
 
     def push_jpeg(self, jpeg, wait=True, variant=4, crop=None, resave=None, crop_file=None, comment=None):
         """A frame as `jpeg.read_jpeg` returns it (quantised DCT coefficients): decoded, cropped and turned to gray on
         the device; the step is the one `push_bgr` makes with the file's decoded pixels.  The file's `bytes` instead: the
         Huffman decoding runs on the device as well (`Context.upload_jpeg_file`).  `resave`, `crop_file`, `comment`: as
         `push_bgr`."""
-        self._check_crop_file(resave, crop_file)
-        s = self._next_slot()
-        if isinstance(jpeg, (bytes, bytearray, memoryview)):
-            self.ctx.upload_jpeg_file(s, jpeg, variant, crop, resave)
-        else:
-            self.ctx.upload_jpeg(s, jpeg, variant, crop, resave)
-        data = self._crop_bytes(crop_file, comment)
-        seg = self._step(s, wait)
-        self._write_crop(crop_file, data)
-        return seg
+        upload = self.ctx.upload_jpeg_file if isinstance(jpeg, (bytes, bytearray, memoryview)) else self.ctx.upload_jpeg
+        return self._push_upload(upload, jpeg, wait, variant, crop, resave, crop_file, comment)
 
     def push_device(self, dev_ptr, stride, wait=True):
         s = self._next_slot()

@@ -153,3 +153,54 @@ def test_bench_starts_its_own_ranks(tmp_path):
     env["ICELK_BENCH_SHARED_DEVICE"] = "1"
     subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=120)
     assert [json.load(open(tmp_path / ("rank_%d.json" % r)))["LOCAL_RANK"] for r in range(3)] == ["0", "0", "0"]
+
+
+def test_sequence_loader_kinds_and_fallback(tmp_path):
+    """`sequence._load`, the one loader of the folder driver's pool threads: per kind the type the driver dispatches on, PIL's
+    array for the files the device decoder does not take (that file only), PIL's complaint for a broken one, and the photo's
+    comment when asked for.  The expectation comes from PIL and `jpeg.read_jpeg` directly."""
+    import io
+    from PIL import Image
+    from iceberg_tracking_code_amd import jpeg, sequence
+    rng = np.random.default_rng(7)
+    rgb = rng.integers(0, 256, (24, 40, 3), dtype=np.uint8)
+
+    def save(name, img, cut=None, **kw):
+        f = io.BytesIO()
+        Image.fromarray(img).save(f, "JPEG", comment=b"abc", **kw)
+        data = f.getvalue()
+        with open(tmp_path / name, "wb") as out:
+            out.write(data if cut is None else data[:int(cut * len(data))])
+        return str(tmp_path / name)
+
+    files = {"baseline": save("b.jpg", rgb, subsampling=2), "progressive": save("p.jpg", rgb, progressive=True),
+             "gray": save("g.jpg", rgb[:, :, 0]), "truncated": save("t.jpg", rgb, cut=0.6, quality=95, subsampling=2)}
+    # which kinds hand the file on as it is: the others get PIL's word
+    taken = {"baseline": ("coefficients", "bytes"), "progressive": (), "gray": (), "truncated": ("bytes",)}
+    for label, path in files.items():
+        with open(path, "rb") as f:
+            data = f.read()
+        try:
+            pil = np.array(Image.open(path))
+        except Exception as e:
+            pil = type(e)
+        assert (label == "truncated") == isinstance(pil, type), label
+        for kind in ("pixels", "coefficients", "bytes"):
+            for with_comment in (False, True):
+                what = (label, kind, with_comment)
+                if kind not in taken[label] and isinstance(pil, type):
+                    with pytest.raises(pil):
+                        sequence._load(path, kind, with_comment)
+                    continue
+                got = sequence._load(path, kind, with_comment)
+                if with_comment:
+                    assert isinstance(got, tuple) and len(got) == 2 and got[1] == b"abc", what
+                    got = got[0]
+                if kind not in taken[label]:
+                    assert isinstance(got, np.ndarray) and got.shape == pil.shape and np.array_equal(got, pil), what
+                elif kind == "bytes":
+                    assert type(got) is bytes and got == data, what
+                else:
+                    want = jpeg.read_jpeg(data)
+                    assert isinstance(got, jpeg.JpegCoefficients) and got.ncomp == 3, what
+                    assert bytes(got.info) == bytes(want.info) and np.array_equal(got.coef, want.coef), what

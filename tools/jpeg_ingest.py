@@ -338,7 +338,7 @@ def pipeline(out, n, threads):
         os.environ.pop(v, None)
     # where a photo's time goes (defaults).  The file reads run on the pool's threads beside the loop; the other three
     # are the loop's own thread, one after the other
-    targets = {"file read + headers (pool threads)": (sequence, "_read_bytes"),
+    targets = {"file read + headers (pool threads)": (sequence, "_load"),
                "start: index, pinned copy, enqueue": (context.Context, "upload_jpeg_file_async"),
                "finish: wait for the verdict": (context.Context, "jpeg_async_finish"),
                "tracker step": (tracker.SegmentTracker, "_step")}
@@ -348,7 +348,7 @@ def pipeline(out, n, threads):
           (rate, 1e3 / rate), file=out)
     for label in targets:
         print("  %-36s %6.2f ms per photo (%d calls)" % (label, 1e3 * sw.total[label] / n, sw.calls[label]), file=out)
-    targets = {"file read + headers (pool threads)": (sequence, "_read_bytes"),
+    targets = {"file read + headers (pool threads)": (sequence, "_load"),
                "upload_jpeg_file (decode, 3 host waits)": (context.Context, "upload_jpeg_file"),
                "tracker step": (tracker.SegmentTracker, "_step")}
     with Stopwatch(targets) as sw:
