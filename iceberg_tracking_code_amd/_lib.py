@@ -46,6 +46,12 @@ class JpegHuffStats(C.Structure):
                 ("total_hops", C.c_uint64)]
 
 
+class JpegCropStats(C.Structure):
+    """icelk_jpeg_crop_stats_t"""
+    _fields_ = [("huff", JpegHuffStats), ("route", C.c_uint32), ("blocks", C.c_uint32), ("budget", C.c_uint64), ("stream_len", C.c_uint64)]
+
+
+JPEG_CROP_ROUTES = ("device", "host-huffman", "over-budget")   # ICELK_JPEG_CROP_*
 JPEG_TABLE_BYTES = 11328
 JPEG_FALLBACK_NONE, JPEG_FALLBACK_BOUND, JPEG_FALLBACK_STREAM, JPEG_FALLBACK_SIZE = 0, 1, 2, 3
 jpeg_stats_p = C.POINTER(JpegHuffStats)
@@ -90,6 +96,14 @@ SIGNATURES = {
                                               C.POINTER(C.c_uint64)]),
     "icelk_jpeg_encode_coefficients": (C.c_int, [handle_p, jpeg_info_p, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "icelk_jpeg_resave_encode": (C.c_int, [handle_p, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_jpeg_enc_budget": (C.c_int, [C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "icelk_jpeg_encode_budgeted_host": (C.c_int, [jpeg_info_p, vp, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, vp, C.c_uint64, vp, C.c_uint64,
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "icelk_jpeg_crop_config": (C.c_int, [handle_p, C.c_int]),
+    "icelk_jpeg_crop_start": (C.c_int, [handle_p, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p]),
+    "icelk_jpeg_crop_poll": (C.c_int, [handle_p, C.c_int, i32p]),
+    "icelk_jpeg_crop_finish": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(JpegCropStats)]),
+    "icelk_jpeg_crop_cancel": (C.c_int, [handle_p, C.c_int]),
     "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

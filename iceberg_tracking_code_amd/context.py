@@ -62,6 +62,7 @@ class Context:
         self._h = C.c_void_p()
         self.max_w, self.max_h, self.n_slots, self.max_pts, self.device = max_w, max_h, n_slots, max_pts, device
         check(self._lib.icelk_create(device, max_w, max_h, n_slots, max_pts, C.byref(self._h)), None)
+        self._crop_file_guess = 1 << 16                   # bytes `jpeg_crop_finish` offers first: about the last file's
 
     # -- lifetime -----------------------------------------------------------------------------
     def close(self):
@@ -195,6 +196,59 @@ class Context:
         st = _lib.JpegHuffStats()
         self._ck_jpeg(self._lib.icelk_jpeg_async_finish(self._h, slot, C.byref(st)))
         return _stats_dict(st)
+
+    # -- the crop step on its own: decode, crop, re-save and encode in one enqueued piece (csrc/abi_jpeg_crop.hip) --
+    def jpeg_crop_config(self, stream_bytes_per_block=48):
+        """Bytes of stuffed scan per block (1 .. 416) that a crop job started from now on may take on the device; a scan
+        that takes more is coded again at `jpeg_crop_finish` with host-read sizes (route "over-budget"), same bytes."""
+        self._ck(self._lib.icelk_jpeg_crop_config(self._h, int(stream_bytes_per_block)))
+
+    def jpeg_crop_start(self, data, crop=None, quality=75):
+        """Starts the reference's crop step for one photo given as bytes -- Huffman decoding, inverse DCT, the crop box,
+        the re-save at `quality` ("reference" or 1 .. 100) and the entropy coder, enqueued on a decode stream without a wait
+        (icelk_jpeg_crop_start) -- and returns its ticket.  No frame slot is touched and the handle's max_w x max_h bound
+        nothing.  `data` is copied by the library.  Raises as `upload_jpeg_file(resave=)` does; no ticket is taken then."""
+        quality = resave_quality(quality)
+        if quality is None:
+            raise ValueError('quality must be "reference" or a JPEG quality in 1 .. 100')
+        if isinstance(data, bytearray):
+            buf = (C.c_char * len(data)).from_buffer(data)
+        else:
+            buf = data = bytes(data)
+        left, top, right, bottom = _crop4(crop)
+        ticket = C.c_int(0)
+        self._ck_jpeg(self._lib.icelk_jpeg_crop_start(self._h, buf, len(data), left, top, right, bottom, quality, C.byref(ticket)))
+        return ticket.value
+
+    def jpeg_crop_poll(self, ticket):
+        """0: the job is in flight, 1: its file is coded on the device, 2: `jpeg_crop_finish` has host work to do (the host
+        decoder, or a scan over the budget).  A look at pinned memory; never blocks."""
+        state = C.c_int(0)
+        self._ck(self._lib.icelk_jpeg_crop_poll(self._h, int(ticket), C.byref(state)))
+        return state.value
+
+    def jpeg_crop_finish(self, ticket, comment=None):
+        """Waits for the job and returns (the bytes of the file Pillow's `Image.open(f).crop(box).save(out)` writes, a
+        dictionary: the keys of `jpeg_huff_stats` for the source file, "route" -- "device", "host-huffman" or
+        "over-budget" --, "blocks", "budget" and "stream_len").  `comment`: the source's comment (`jpeg.source_comment`),
+        which Pillow carries over, or None.  The ticket is gone afterwards, also when the call raises."""
+        com, ncom = _comment_args(comment)
+        st = _lib.JpegCropStats()
+        try:
+            data = _encode_call(lambda out, cap, n: self._lib.icelk_jpeg_crop_finish(self._h, int(ticket), com, ncom, out, cap, n, C.byref(st)),
+                                self._crop_file_guess + ncom, "icelk_jpeg_crop_finish", self._h)
+        except _lib.IcelkError as e:
+            if getattr(e, "code", None) == _lib.ECAP:     # the library keeps a ticket whose file did not fit: drop it here
+                self._lib.icelk_jpeg_crop_cancel(self._h, int(ticket))
+            raise
+        self._crop_file_guess = max(1 << 16, len(data) + len(data) // 4)   # the next photo of a folder is about as large
+        stats = _stats_dict(st.huff)
+        stats.update(route=_lib.JPEG_CROP_ROUTES[st.route], blocks=int(st.blocks), budget=int(st.budget), stream_len=int(st.stream_len))
+        return data, stats
+
+    def jpeg_crop_cancel(self, ticket):
+        """Waits for what the job has enqueued and drops the ticket."""
+        self._ck(self._lib.icelk_jpeg_crop_cancel(self._h, int(ticket)))
 
     def jpeg_decode_rgb_file(self, data):
         """The decoded image of a JPEG file given as bytes, Huffman decoding included on the device."""

@@ -30,9 +30,11 @@ namespace icelk {
 
 static void free_job(Ctx::JpegJob* B)
 {
-    void* p[] = {B->d_coef, B->d_planes, B->d_file, B->d_seg, B->d_tabs, B->d_T, B->d_X, B->d_cnt, B->d_P, B->d_ctl, B->d_dc};
+    void* p[] = {B->d_coef, B->d_planes, B->d_file, B->d_seg, B->d_tabs, B->d_T, B->d_X, B->d_cnt, B->d_P, B->d_ctl, B->d_dc, B->d_rgb, B->d_rcoef};
     for (void* q : p)
         if (q) hipFree(q);
+    jpeg_enc_free(B->enc);
+    if (B->h_out) hipHostFree(B->h_out);
     if (B->h_stage) hipHostFree(B->h_stage);
     if (B->h_verdict) hipHostFree(B->h_verdict);
     if (B->done) hipEventDestroy(B->done);
@@ -48,6 +50,11 @@ void jpeg_async_destroy(Ctx* c)
             hipStreamDestroy(q);
             q = nullptr;
         }
+    if (c->jpeg.fetch) {
+        hipStreamSynchronize(c->jpeg.fetch);
+        hipStreamDestroy(c->jpeg.fetch);
+        c->jpeg.fetch = nullptr;
+    }
     for (Ctx::JpegJob* B : c->jpeg.ring) free_job(B);
     c->jpeg.ring.clear();
 }
@@ -60,12 +67,12 @@ int jpeg_async_sync(Ctx* c)
     return ICELK_OK;
 }
 
-// a job no slot owns; a new one when all are in flight
-static int take_job(Ctx* c, int* idx)
+// a job that neither a slot nor a ticket (abi_jpeg_crop.hip) owns; a new one when all are in flight
+int jpeg_take_job(Ctx* c, int* idx)
 {
     Ctx::Jpeg& J = c->jpeg;
     for (size_t k = 0; k < J.ring.size(); k++)
-        if (J.ring[k]->slot < 0) return *idx = (int)k, ICELK_OK;
+        if (J.ring[k]->slot < 0 && J.ring[k]->ticket < 0) return *idx = (int)k, ICELK_OK;
     Ctx::JpegJob* B = new (std::nothrow) Ctx::JpegJob;
     if (!B) FAIL(c, ICELK_ENOMEM, "no memory for a JPEG job");
     if (hipHostMalloc(reinterpret_cast<void**>(&B->h_verdict), JV_WORDS * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
@@ -85,7 +92,7 @@ static int take_job(Ctx* c, int* idx)
 }
 
 // the decode streams, created at the first asynchronous file: two in turn, as Ctx::copy_hi (abi_frames.hip)
-static int decode_stream(Ctx* c, hipStream_t* out)
+int jpeg_decode_stream(Ctx* c, hipStream_t* out)
 {
     Ctx::Jpeg& J = c->jpeg;
     const unsigned k = J.dec_seq++ % (unsigned)J.dec_streams;
@@ -112,23 +119,11 @@ static void release_job(Ctx* c, Ctx::JpegJob& B, int state)
     B.slot = -1;
 }
 
-static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uint64_t len, JpegIndex& X, int left, int top, int right,
-                     int bottom)
+// The job's pinned staging area: tables | segment table | file.  The copies of a start read it when the stream gets there,
+// and the host decoder reads the file from it at finish: the caller's buffer is free when the start returns.  The tables
+// and the segment table are copied in by the caller once it knows that something goes out.
+int jpeg_stage_file(Ctx* c, Ctx::JpegJob& B, const JpegIndex& X, size_t seg_bytes, const uint8_t* data, uint64_t len)
 {
-    Ctx::Jpeg& J = c->jpeg;
-    const bool host_only = B.host_only;
-    if (int rc = jpeg_plane_args(c, B, &B.info, left, top, right, bottom, &B.idct, &B.out)) return rc;
-    // begin_frame's check, taken before anything is allocated for the file
-    if (B.out.ow > c->max_w || B.out.oh > c->max_h) FAIL(c, ICELK_ECAP, "frame larger than max_w x max_h of icelk_create");
-    JpegHuffArgs H{};
-    size_t seg_bytes = 0;
-    if (!host_only) {
-        jpeg_index_lanes(X, (uint32_t)J.subseq_bits, J.max_hops);
-        if (int rc = jpeg_huff_setup(c, B, X, len, &H, true)) return rc;
-        seg_bytes = X.seg.size() * sizeof(lanes::Seg);
-    }
-    // the pinned staging area: tables | segment table | file.  The copies below read it when the stream gets there, and
-    // the host decoder reads the file from it at finish: the caller's buffer is free when this call returns
     const size_t file_off = (sizeof(X.tabs) + seg_bytes + 255) & ~(size_t)255, want = file_off + (size_t)len;
     if (B.stage_cap < want) {
         const size_t take = want + want / 4;   // headroom as jpeg_huff_setup's
@@ -144,7 +139,26 @@ static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uin
     B.file_off = file_off;
     B.len = len;
     memcpy(B.h_stage + file_off, data, (size_t)len);
-    if (int rc = decode_stream(c, &B.st)) return rc;
+    return ICELK_OK;
+}
+
+static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uint64_t len, JpegIndex& X, int left, int top, int right,
+                     int bottom)
+{
+    Ctx::Jpeg& J = c->jpeg;
+    const bool host_only = B.host_only;
+    if (int rc = jpeg_plane_args(c, B, &B.info, left, top, right, bottom, &B.idct, &B.out)) return rc;
+    // begin_frame's check, taken before anything is allocated for the file
+    if (B.out.ow > c->max_w || B.out.oh > c->max_h) FAIL(c, ICELK_ECAP, "frame larger than max_w x max_h of icelk_create");
+    JpegHuffArgs H{};
+    size_t seg_bytes = 0;
+    if (!host_only) {
+        jpeg_index_lanes(X, (uint32_t)J.subseq_bits, J.max_hops);
+        if (int rc = jpeg_huff_setup(c, B, X, len, &H, true)) return rc;
+        seg_bytes = X.seg.size() * sizeof(lanes::Seg);
+    }
+    if (int rc = jpeg_stage_file(c, B, X, seg_bytes, data, len)) return rc;
+    if (int rc = jpeg_decode_stream(c, &B.st)) return rc;
     // from here on the slot is taken: whatever fails below leaves it without a frame
     if (int rc = begin_frame(c, slot, B.out.ow, B.out.oh)) return rc;
     B.slot = slot;
@@ -156,7 +170,7 @@ static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uin
     memcpy(B.h_stage + sizeof(X.tabs), X.seg.data(), seg_bytes);
     B.segments = X.scan.nseg;
     B.subsequences = X.scan.nlanes;
-    if (int rc = jpeg_huff_stage(c, B, X, B.h_stage + file_off, B.h_stage + sizeof(X.tabs), B.h_stage, len, st)) return rc;
+    if (int rc = jpeg_huff_stage(c, B, X, B.h_stage + B.file_off, B.h_stage + sizeof(X.tabs), B.h_stage, len, st)) return rc;
     {
         // every round at once: one that no group takes part in returns after two loads per workgroup
         ProfScope p(c, K_JPEG_HUFF, st);
@@ -172,17 +186,17 @@ static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uin
     return foreign_write_end(c, s, st);
 }
 
-static inline bool verdict_here(const Ctx::JpegJob& B)
+bool jpeg_verdict_here(const Ctx::JpegJob& B)
 {
     return __atomic_load_n(B.h_verdict + JV_SEQ, __ATOMIC_ACQUIRE) == B.seq;
 }
 
 // Waits for the verdict by polling the pinned sequence word, as fetch_counts (abi_detect.hip): the event is looked at
 // now and then, so that a failed launch ends the wait with its error instead of hanging it.
-static int await_verdict(Ctx* c, Ctx::JpegJob& B)
+int jpeg_await_verdict(Ctx* c, Ctx::JpegJob& B)
 {
     for (unsigned it = 1;; it++) {
-        if (verdict_here(B)) return ICELK_OK;
+        if (jpeg_verdict_here(B)) return ICELK_OK;
         if ((it & 4095u) == 0) {
             const hipError_t q = hipEventQuery(B.done);
             if (q == hipSuccess) break;
@@ -192,8 +206,21 @@ static int await_verdict(Ctx* c, Ctx::JpegJob& B)
         __builtin_ia32_pause();
     }
     HIPCHK(c, hipEventSynchronize(B.done));
-    if (!verdict_here(B)) FAIL(c, ICELK_EHIP, "the JPEG verdict did not arrive");
+    if (!jpeg_verdict_here(B)) FAIL(c, ICELK_EHIP, "the JPEG verdict did not arrive");
     return ICELK_OK;
+}
+
+// the decoder's statistics of the job's file, from the verdict that has arrived (fallback is the caller's to fill in)
+void jpeg_huff_stats_of(const Ctx::JpegJob& B, icelk_jpeg_huff_stats_t* st)
+{
+    const uint32_t* v = B.h_verdict;
+    st->segments = B.segments;
+    st->subsequences = B.subsequences;
+    st->rounds = v[JV_ROUNDS];
+    st->max_hops = v[JV_MAX_HOPS];
+    st->total_hops = v[JV_TOTAL_HOPS];
+    st->lanes_in_step = v[JV_IN_STEP];
+    st->spanning_blocks = v[JV_SPANS];
 }
 
 // the serial decoder takes the job's file (from the pinned copy): its coefficients replace the lanes', the transform and
@@ -259,7 +286,7 @@ int icelk_upload_jpeg_file_async(icelk_t* h, int slot, const uint8_t* data, uint
         }
     }
     int idx = -1;
-    if ((rc = take_job(c, &idx))) return rc;
+    if ((rc = jpeg_take_job(c, &idx))) return rc;
     Ctx::JpegJob& B = *J.ring[idx];
     B.info = info;
     B.variant = gray_variant;
@@ -290,7 +317,7 @@ int icelk_jpeg_async_poll(icelk_t* h, int slot, int* state)
         return ICELK_OK;
     }
     if (B->host_only) *state = 2;
-    else if (!verdict_here(*B)) *state = 0;
+    else if (!jpeg_verdict_here(*B)) *state = 0;
     else *state = B->h_verdict[JV_VERDICT] == JV_DECODED ? 1 : 2;
     return ICELK_OK;
 }
@@ -309,7 +336,7 @@ int icelk_jpeg_async_finish(icelk_t* h, int slot, icelk_jpeg_huff_stats_t* stats
     memset(&st, 0, sizeof(st));
     uint32_t why = ICELK_JPEG_FALLBACK_SIZE;
     if (!B.host_only) {
-        if (int rc = await_verdict(c, B)) {
+        if (int rc = jpeg_await_verdict(c, B)) {
             // a failed launch: nothing of the slot or the job can be relied on
             hipStreamSynchronize(B.st);
             c->slots[slot].levels_built = 0;
@@ -317,13 +344,7 @@ int icelk_jpeg_async_finish(icelk_t* h, int slot, icelk_jpeg_huff_stats_t* stats
             return rc;
         }
         const uint32_t* v = B.h_verdict;
-        st.segments = B.segments;
-        st.subsequences = B.subsequences;
-        st.rounds = v[JV_ROUNDS];
-        st.max_hops = v[JV_MAX_HOPS];
-        st.total_hops = v[JV_TOTAL_HOPS];
-        st.lanes_in_step = v[JV_IN_STEP];
-        st.spanning_blocks = v[JV_SPANS];
+        jpeg_huff_stats_of(B, &st);
         why = v[JV_VERDICT] == JV_DECODED ? ICELK_JPEG_FALLBACK_NONE : v[JV_VERDICT];
     }
     st.fallback = why;

@@ -19,19 +19,18 @@
 
 namespace icelk {
 
-void jpeg_enc_destroy(Ctx* c)
+void jpeg_enc_free(Ctx::JpegEnc& E)
 {
-    Ctx::Jpeg::Enc& E = c->jpeg.enc;
     void* p[] = {E.d_codes, E.d_coef, E.d_bits, E.d_group, E.d_ctl, E.d_packed, E.d_ff, E.d_out};
     for (void* q : p)
         if (q) hipFree(q);
     if (E.h_ctl) hipHostFree(E.h_ctl);
-    E = Ctx::Jpeg::Enc{};
+    E = Ctx::JpegEnc{};
 }
 
-namespace {
+void jpeg_enc_destroy(Ctx* c) { jpeg_enc_free(c->jpeg.enc); }
 
-int enc_rc(Ctx* c, int rc)
+int jpeg_enc_rc(Ctx* c, int rc)
 {
     switch (rc) {
         case ICELK_OK: return rc;
@@ -41,11 +40,9 @@ int enc_rc(Ctx* c, int rc)
     }
 }
 
-// the scan of the coefficients at d_coef (laid out as L says) -> E.d_out, E.stream_len
-int encode_device(Ctx* c, const enc::Layout& L, const int16_t* d_coef)
+// what every coder has whatever the file: the control words on the device, their pinned copy, the tables
+int jpeg_enc_prepare(Ctx* c, Ctx::JpegEnc& E)
 {
-    Ctx::Jpeg::Enc& E = c->jpeg.enc;
-    E.stream_ok = false;
     if (!E.d_ctl)
         if (int rc = dmalloc(c, &E.d_ctl, (size_t)JE_WORDS)) return rc;
     if (!E.h_ctl) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&E.h_ctl), JE_WORDS * sizeof(uint32_t)));
@@ -59,6 +56,16 @@ int encode_device(Ctx* c, const enc::Layout& L, const int16_t* d_coef)
         }
         E.d_codes = codes;
     }
+    return ICELK_OK;
+}
+
+// The scan of the coefficients at d_coef (laid out as L says) -> E.d_out, E.stream_len, on stream st with the host reading
+// the two sizes in between.  The synchronous calls run it on the handle's coder and compute stream, a crop job
+// (abi_jpeg_crop.hip) on its own where its budget did not hold the scan.
+int jpeg_encode_on(Ctx* c, Ctx::JpegEnc& E, hipStream_t st, const enc::Layout& L, const int16_t* d_coef)
+{
+    E.stream_ok = false;
+    if (int rc = jpeg_enc_prepare(c, E)) return rc;
     const uint32_t groups = (L.blocks + kJpegEncGroup - 1) / kJpegEncGroup;
     if (int rc = grow(c, &E.d_bits, &E.bits_cap, (size_t)L.blocks)) return rc;
     if (int rc = grow(c, &E.d_group, &E.group_cap, (size_t)groups)) return rc;
@@ -69,53 +76,57 @@ int encode_device(Ctx* c, const enc::Layout& L, const int16_t* d_coef)
     A.bits = E.d_bits;
     A.group = E.d_group;
     A.ctl = E.d_ctl;
-    HIPCHK(c, hipMemsetAsync(E.d_ctl, 0, JE_WORDS * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(E.d_ctl, 0, JE_WORDS * sizeof(uint32_t), st));
     {
-        ProfScope p(c, K_JPEG_ENC_COUNT);
-        launch_jpeg_enc_count(c->stream, A);
+        ProfScope p(c, K_JPEG_ENC_COUNT, st);
+        launch_jpeg_enc_count(st, A);
     }
     if (int rc = check_launch(c, "jpeg_enc_count")) return rc;
     {
-        ProfScope p(c, K_JPEG_ENC_SCAN);
-        launch_jpeg_enc_scan(c->stream, E.d_group, groups, E.d_ctl + JE_TOTAL_BITS);
+        ProfScope p(c, K_JPEG_ENC_SCAN, st);
+        launch_jpeg_enc_scan(st, E.d_group, groups, E.d_ctl + JE_TOTAL_BITS);
     }
     if (int rc = check_launch(c, "jpeg_enc_scan")) return rc;
-    HIPCHK(c, hipMemcpyAsync(E.h_ctl, E.d_ctl, JE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(E.h_ctl, E.d_ctl, JE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
     if (E.h_ctl[JE_INVALID]) FAIL(c, ICELK_EARG, "a coefficient that the standard Huffman tables have no code for");
     const uint32_t nbytes = (uint32_t)(((uint64_t)E.h_ctl[JE_TOTAL_BITS] + 7) / 8);
     const uint32_t nchunks = (nbytes + kJpegEncChunk - 1) / kJpegEncChunk, nwg = (nchunks + 255) / 256;
     if (int rc = grow(c, &E.d_packed, &E.packed_cap, (size_t)nchunks * (kJpegEncChunk / 4))) return rc;
     if (int rc = grow(c, &E.d_ff, &E.ff_cap, (size_t)nwg)) return rc;
     A.packed = E.d_packed;
-    HIPCHK(c, hipMemsetAsync(E.d_packed, 0, (size_t)nchunks * kJpegEncChunk, c->stream));
+    HIPCHK(c, hipMemsetAsync(E.d_packed, 0, (size_t)nchunks * kJpegEncChunk, st));
     {
-        ProfScope p(c, K_JPEG_ENC_PACK);
-        launch_jpeg_enc_pack(c->stream, A);
+        ProfScope p(c, K_JPEG_ENC_PACK, st);
+        launch_jpeg_enc_pack(st, A);
     }
     if (int rc = check_launch(c, "jpeg_enc_pack")) return rc;
     {
-        ProfScope p(c, K_JPEG_ENC_FF);
-        launch_jpeg_enc_ff(c->stream, E.d_packed, nchunks, E.d_ff);
+        ProfScope p(c, K_JPEG_ENC_FF, st);
+        launch_jpeg_enc_ff(st, E.d_packed, nchunks, E.d_ff);
     }
     if (int rc = check_launch(c, "jpeg_enc_ff")) return rc;
     {
-        ProfScope p(c, K_JPEG_ENC_SCAN);
-        launch_jpeg_enc_scan(c->stream, E.d_ff, nwg, E.d_ctl + JE_FF_TOTAL);
+        ProfScope p(c, K_JPEG_ENC_SCAN, st);
+        launch_jpeg_enc_scan(st, E.d_ff, nwg, E.d_ctl + JE_FF_TOTAL);
     }
     if (int rc = check_launch(c, "jpeg_enc_scan")) return rc;
-    HIPCHK(c, hipMemcpyAsync(E.h_ctl, E.d_ctl, JE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(E.h_ctl, E.d_ctl, JE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
     const uint64_t len = (uint64_t)nbytes + E.h_ctl[JE_FF_TOTAL];
     if (int rc = grow(c, &E.d_out, &E.out_cap, (size_t)len)) return rc;
     {
-        ProfScope p(c, K_JPEG_ENC_STUFF);
-        launch_jpeg_enc_stuff(c->stream, E.d_packed, nbytes, nchunks, E.d_ff, E.d_out);
+        ProfScope p(c, K_JPEG_ENC_STUFF, st);
+        launch_jpeg_enc_stuff(st, E.d_packed, nbytes, nchunks, E.d_ff, E.d_out);
     }
     if (int rc = check_launch(c, "jpeg_enc_stuff")) return rc;
     E.stream_len = len;
     return ICELK_OK;
 }
+
+namespace {
+
+int encode_device(Ctx* c, const enc::Layout& L, const int16_t* d_coef) { return jpeg_encode_on(c, c->jpeg.enc, c->stream, L, d_coef); }
 
 // header, E.d_out and EOI into the caller's buffer
 int deliver(Ctx* c, const icelk_jpeg_info_t& I, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity, uint64_t* len)
@@ -176,7 +187,7 @@ int icelk_jpeg_encode_coefficients(icelk_t* h, const icelk_jpeg_info_t* info, co
     Ctx* c = C(h);
     if (!coef || !len || !enc::comment_ok(comment, comment_len)) FAIL(c, ICELK_EARG, "null coefficients or length, or a comment no segment holds");
     enc::Layout L;
-    if (int rc = enc_rc(c, enc::layout_of(info, &L))) return rc;
+    if (int rc = jpeg_enc_rc(c, enc::layout_of(info, &L))) return rc;
     Ctx::Jpeg::Enc& E = c->jpeg.enc;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = grow(c, &E.d_coef, &E.coef_cap, (size_t)info->coef_count)) return rc;
@@ -195,7 +206,7 @@ int icelk_jpeg_resave_encode(icelk_t* h, const uint8_t* comment, uint64_t commen
     HIPCHK(c, hipSetDevice(c->device));
     if (!E.stream_ok) {
         enc::Layout L;
-        if (int rc = enc_rc(c, enc::layout_of(&E.info, &L))) return rc;
+        if (int rc = jpeg_enc_rc(c, enc::layout_of(&E.info, &L))) return rc;
         if (int rc = encode_device(c, L, c->jpeg.resave.d_coef)) return rc;
         E.stream_ok = true;   // kept until the next re-save, so that a call with a larger buffer need not encode again
     }

@@ -30,10 +30,8 @@ void jpeg_resave_destroy(Ctx* c)
     J.d_src = nullptr;
 }
 
-namespace {
-
 // what the device entry points accept, checked before anything is enqueued
-int resave_check(Ctx* c, int w, int h, int quality)
+int jpeg_resave_check(Ctx* c, int w, int h, int quality)
 {
     if (quality < 1 || quality > 100) FAIL(c, ICELK_EARG, "re-save quality outside 1 .. 100");
     if (w < 3) FAIL(c, ICELK_EARG, "re-save of an image less than 3 pixels wide");   // as the decoder: libjpeg's padding decides there
@@ -41,11 +39,40 @@ int resave_check(Ctx* c, int w, int h, int quality)
     return ICELK_OK;
 }
 
+// The forward kernel on stream st: the w x h image at d_src (rows 3 w bytes apart) -> the coefficients of the re-saved
+// file that I describes (resave_info) at d_coef.  The synchronous calls run it on the handle's re-save job, a crop job
+// (abi_jpeg_crop.hip) on its own buffers.
+int jpeg_fwd_on(Ctx* c, hipStream_t st, const uint8_t* d_src, int16_t* d_coef, int w, int h, const icelk_jpeg_info_t& I)
+{
+    JpegFwdArgs F{};
+    F.rgb = d_src;
+    F.pitch = 3 * w;
+    F.w = w;
+    F.h = h;
+    for (int k = 0; k < 3; k++) F.coef[k] = d_coef + I.coef_offset[k];
+    F.mcus_x = I.mcus_x;
+    F.mcus_y = I.mcus_y;
+    F.real_bx = (w + 7) / 8;
+    F.real_by = (h + 7) / 8;
+    for (int t = 0; t < 2; t++)
+        for (int i = 0; i < 64; i++) {
+            F.quant[t][i] = I.quant[t][i];
+            F.recip[t][i] = fwd::reciprocal((uint32_t)I.quant[t][i] << 3);
+        }
+    {
+        ProfScope p(c, K_JPEG_FWD, st);
+        launch_jpeg_fwd(st, F);
+    }
+    return check_launch(c, "jpeg_fwd");
+}
+
+namespace {
+
 int resave_slot_check(Ctx* c, int slot, int w, int h, int quality, int gray_variant)
 {
     if (int rc = check_gray_variant(c, gray_variant)) return rc;
     if (int rc = check_slot(c, slot, false)) return rc;
-    if (int rc = resave_check(c, w, h, quality)) return rc;
+    if (int rc = jpeg_resave_check(c, w, h, quality)) return rc;
     if (w > c->max_w || h > c->max_h) FAIL(c, ICELK_ECAP, "frame larger than max_w x max_h of icelk_create");
     return ICELK_OK;
 }
@@ -68,26 +95,7 @@ int resave_forward(Ctx* c, int w, int h, int quality, icelk_jpeg_info_t* I, Jpeg
     resave_info(w, h, quality, I);
     JpegIdctArgs D;
     if (int rc = jpeg_plane_args(c, B, I, 0, 0, 0, 0, &D, O)) return rc;   // grows d_coef and d_planes
-    JpegFwdArgs F{};
-    F.rgb = c->jpeg.d_src;
-    F.pitch = 3 * w;
-    F.w = w;
-    F.h = h;
-    for (int k = 0; k < 3; k++) F.coef[k] = B.d_coef + I->coef_offset[k];
-    F.mcus_x = I->mcus_x;
-    F.mcus_y = I->mcus_y;
-    F.real_bx = (w + 7) / 8;
-    F.real_by = (h + 7) / 8;
-    for (int t = 0; t < 2; t++)
-        for (int i = 0; i < 64; i++) {
-            F.quant[t][i] = I->quant[t][i];
-            F.recip[t][i] = fwd::reciprocal((uint32_t)I->quant[t][i] << 3);
-        }
-    {
-        ProfScope p(c, K_JPEG_FWD);
-        launch_jpeg_fwd(c->stream, F);
-    }
-    if (int rc = check_launch(c, "jpeg_fwd")) return rc;
+    if (int rc = jpeg_fwd_on(c, c->stream, c->jpeg.d_src, B.d_coef, w, h, *I)) return rc;
     c->jpeg.enc.resaved = true;   // what icelk_jpeg_resave_encode writes the file of
     c->jpeg.enc.stream_ok = false;
     c->jpeg.enc.info = *I;
@@ -159,7 +167,7 @@ int icelk_jpeg_resave_rgb(icelk_t* h, const uint8_t* rgb, int w, int h_, int str
     if (!h) return ICELK_EARG;
     Ctx* c = C(h);
     if (!rgb || !out || stride < 3 * w || out_stride < 3 * w) FAIL(c, ICELK_EARG, "bad host image");
-    if (int rc = resave_check(c, w, h_, quality)) return rc;
+    if (int rc = jpeg_resave_check(c, w, h_, quality)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = rgb_to_src(c, rgb, w, h_, stride)) return rc;
     icelk_jpeg_info_t I;
@@ -174,7 +182,7 @@ int icelk_jpeg_resave_device_coefficients(icelk_t* h, const uint8_t* rgb, int w,
     if (!h) return ICELK_EARG;
     Ctx* c = C(h);
     if (!rgb || !coef || stride < 3 * w) FAIL(c, ICELK_EARG, "bad host image or null coefficient buffer");
-    if (int rc = resave_check(c, w, h_, quality)) return rc;
+    if (int rc = jpeg_resave_check(c, w, h_, quality)) return rc;
     icelk_jpeg_info_t I;
     resave_info(w, h_, quality, &I);
     if (capacity < I.coef_count) FAIL(c, ICELK_ECAP, "coefficient buffer too small");

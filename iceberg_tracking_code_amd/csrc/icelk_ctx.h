@@ -80,6 +80,22 @@ struct Ctx {
     // on the device (icelk_upload_jpeg_file ...) the file, its segments and tables and the lanes' arrays; grown on demand,
     // because the file may be larger than max_w x max_h (the crop is what has to fit).  The synchronous calls share one
     // job; every file of icelk_upload_jpeg_file_async has its own until icelk_jpeg_async_finish (abi_jpeg_async.hip).
+    // The JPEG writer (abi_jpeg_enc.hip), allocated at first use: the tables, the blocks' bit lengths, the groups' offsets,
+    // the packed and the stuffed stream -- grown to what a file measures by the synchronous calls, which share one
+    // (Jpeg::enc), allocated to the job's budget by a crop job, which has its own.  `resaved` / `info`: the handle has run
+    // the forward kernel, and for which file; `stream_ok`: d_out holds that file's scan (stream_len bytes)
+    struct JpegEnc {
+        uint32_t* d_codes = nullptr;
+        int16_t* d_coef = nullptr;     // of icelk_jpeg_encode_coefficients only
+        uint16_t* d_bits = nullptr;
+        uint32_t *d_group = nullptr, *d_ctl = nullptr, *d_packed = nullptr, *d_ff = nullptr;
+        uint8_t* d_out = nullptr;
+        uint32_t* h_ctl = nullptr;     // pinned
+        size_t coef_cap = 0, bits_cap = 0, group_cap = 0, packed_cap = 0, ff_cap = 0, out_cap = 0;   // elements
+        bool resaved = false, stream_ok = false;
+        icelk_jpeg_info_t info{};
+        uint64_t stream_len = 0;
+    };
     struct JpegJob {
         int16_t* d_coef = nullptr;
         uint8_t* d_planes = nullptr;
@@ -106,6 +122,19 @@ struct Ctx {
         icelk_jpeg_info_t info{};
         JpegIdctArgs idct{};             // of the file and its crop: what a second transform after the host decoder runs on
         JpegOutArgs out{};
+        // ---- crop jobs only (abi_jpeg_crop.hip): decode -> crop -> re-save -> encode, owned by a ticket instead of a slot
+        int ticket = -1;                 // the ticket that owns the job, -1: none
+        uint8_t* d_rgb = nullptr;        // the cropped R G B, rows 3 * width bytes apart
+        int16_t* d_rcoef = nullptr;      // the re-save's coefficients (described by rinfo)
+        size_t rgb_cap = 0, rcoef_cap = 0;
+        JpegEnc enc;                     // the coder's buffers, at the job's budget
+        uint8_t* h_out = nullptr;        // pinned: the finished scan
+        size_t hout_cap = 0;
+        uint32_t budget = 0;             // bytes the stuffed scan may take on the device
+        icelk_jpeg_info_t rinfo{};       // of the re-saved file
+        bool have_scan = false;          // h_out holds the scan (scan_len bytes): finish has done its waiting
+        uint64_t scan_len = 0;
+        icelk_jpeg_crop_stats_t cstats{};
     };
     struct Jpeg {
         JpegJob sync;                                          // the working set of every synchronous call
@@ -114,21 +143,9 @@ struct Ctx {
         JpegJob resave;
         uint8_t* d_src = nullptr;
         size_t src_cap = 0;
-        // the JPEG writer (abi_jpeg_enc.hip), allocated at first use and grown to what a file measures: the tables, the
-        // blocks' bit lengths, the groups' offsets, the packed and the stuffed stream; `resaved` / `info`: the handle has
-        // run the forward kernel, and for which file; `stream_ok`: d_out holds that file's scan (stream_len bytes)
-        struct Enc {
-            uint32_t* d_codes = nullptr;
-            int16_t* d_coef = nullptr;     // of icelk_jpeg_encode_coefficients only
-            uint16_t* d_bits = nullptr;
-            uint32_t *d_group = nullptr, *d_ctl = nullptr, *d_packed = nullptr, *d_ff = nullptr;
-            uint8_t* d_out = nullptr;
-            uint32_t* h_ctl = nullptr;     // pinned
-            size_t coef_cap = 0, bits_cap = 0, group_cap = 0, packed_cap = 0, ff_cap = 0, out_cap = 0;   // elements
-            bool resaved = false, stream_ok = false;
-            icelk_jpeg_info_t info{};
-            uint64_t stream_len = 0;
-        } enc;
+        // the JPEG writer of the synchronous calls (JpegEnc above)
+        using Enc = JpegEnc;
+        Enc enc;
         uint8_t* d_rgb = nullptr;                              // the decoded image (icelk_jpeg_decode_rgb only)
         size_t rgb_cap = 0;
         int subseq_bits = 512, max_hops = lanes::kGroup, max_rounds = 8;   // icelk_jpeg_huff_config
@@ -141,6 +158,9 @@ struct Ctx {
         unsigned dec_seq = 0;
         int dec_streams = 2;                                   // ICELK_JPEG_ASYNC_STREAMS=1|2 (A/B)
         bool dec_high = false;                                 // ICELK_JPEG_ASYNC_PRIO=high|normal
+        int crop_bytes_per_block = enc::kDefaultBytesPerBlock;   // icelk_jpeg_crop_config
+        int crop_next_ticket = 1;
+        hipStream_t fetch = nullptr;                           // D2H copies of finished scans (abi_jpeg_crop.hip: fetch_scan)
     } jpeg;
 
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
@@ -505,11 +525,23 @@ void jpeg_huff_finish_phases(hipStream_t st, const JpegHuffArgs& H);
 int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info);
 // abi_jpeg_resave.hip
 void jpeg_resave_destroy(Ctx* c);
+int jpeg_resave_check(Ctx* c, int w, int h, int quality);
+int jpeg_fwd_on(Ctx* c, hipStream_t st, const uint8_t* d_src, int16_t* d_coef, int w, int h, const icelk_jpeg_info_t& I);
 // abi_jpeg_enc.hip
 void jpeg_enc_destroy(Ctx* c);
+void jpeg_enc_free(Ctx::JpegEnc& E);
+int jpeg_enc_rc(Ctx* c, int rc);
+int jpeg_enc_prepare(Ctx* c, Ctx::JpegEnc& E);
+int jpeg_encode_on(Ctx* c, Ctx::JpegEnc& E, hipStream_t st, const enc::Layout& L, const int16_t* d_coef);
 // abi_jpeg_async.hip
 void jpeg_async_destroy(Ctx* c);
 int jpeg_async_sync(Ctx* c);
+int jpeg_take_job(Ctx* c, int* idx);
+int jpeg_decode_stream(Ctx* c, hipStream_t* out);
+int jpeg_stage_file(Ctx* c, Ctx::JpegJob& B, const JpegIndex& X, size_t seg_bytes, const uint8_t* data, uint64_t len);
+bool jpeg_verdict_here(const Ctx::JpegJob& B);
+int jpeg_await_verdict(Ctx* c, Ctx::JpegJob& B);
+void jpeg_huff_stats_of(const Ctx::JpegJob& B, icelk_jpeg_huff_stats_t* st);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

@@ -66,6 +66,11 @@ enum KernelId {
     K_JPEG_ENC_PACK,    // ... the blocks' bits at their offsets
     K_JPEG_ENC_FF,      // ... FF bytes of the packed stream
     K_JPEG_ENC_STUFF,   // ... the stream with a 00 behind every FF
+    K_JPEG_ENC_PACK_BUDGET,    // the device-sized forms of a crop job (abi_jpeg_crop.hip)
+    K_JPEG_ENC_FF_BUDGET,
+    K_JPEG_ENC_STUFF_BUDGET,
+    K_JPEG_CROP_RGB,           // the crop box of the decoded planes as R G B into the job
+    K_JPEG_CROP_VERDICT,
     K_COUNT_
 };
 
@@ -159,6 +164,15 @@ void launch_jpeg_enc_scan(hipStream_t s, uint32_t* v, uint32_t n, uint32_t* tota
 void launch_jpeg_enc_pack(hipStream_t s, const JpegEncArgs& A);
 void launch_jpeg_enc_ff(hipStream_t s, const uint32_t* packed, uint32_t nchunks, uint32_t* wg_ff);
 void launch_jpeg_enc_stuff(hipStream_t s, const uint32_t* packed, uint32_t nbytes, uint32_t nchunks, const uint32_t* wg_off, uint8_t* out);
+// The device-sized forms of a crop job (abi_jpeg_crop.hip): `cap` bytes are allocated for the stuffed scan, packed (whole
+// chunks of it, zeroed) and out; the sizes come from ctl, where count and the scans left them.  wg_ff has
+// enc::groups_of(enc::chunks_of(cap)) entries, which the second scan runs over.
+void launch_jpeg_enc_pack_budget(hipStream_t s, const JpegEncArgs& A, uint32_t cap);
+void launch_jpeg_enc_ff_budget(hipStream_t s, const uint32_t* packed, const uint32_t* ctl, uint32_t cap, uint32_t* wg_ff);
+void launch_jpeg_enc_stuff_budget(hipStream_t s, const uint32_t* packed, const uint32_t* ctl, uint32_t cap, const uint32_t* wg_off, uint8_t* out);
+// last in a crop job's chain: the words of JpegVerdictWord (below) to the job's pinned words, the sequence word last
+void launch_jpeg_crop_verdict(hipStream_t s, const uint32_t* huff_ctl, int max_rounds, const uint32_t* enc_ctl, uint32_t cap, uint32_t* host_words,
+                              uint32_t seq);
 
 // Huffman decoding on the device (k_jpeg_huff.hip; the algorithm is jpeg_lanes.h).  All pointers are device memory.
 constexpr int kJpegMaxRounds = 255;
@@ -200,11 +214,36 @@ enum JpegVerdictWord {
     JV_TOTAL_HOPS,
     JV_IN_STEP,
     JV_SPANS,
+    JV_ENC_VERDICT,   // crop jobs (k_jpeg_crop_verdict): enc::Verdict of the budgeted coder
+    JV_ENC_LEN,       // ... bytes of the stuffed scan when it is enc::kCoded
     JV_SEQ = 8,
     JV_WORDS = 16
 };
 constexpr uint32_t JV_DECODED = 0x100;
 void launch_jpeg_huff_verdict(hipStream_t s, const uint32_t* ctl, int max_rounds, uint32_t* host_words, uint32_t seq);
+// The decoder's words of a verdict (JV_VERDICT .. JV_SPANS) from its control words, by the one wave of a verdict kernel
+// (k_jpeg_huff_verdict, k_jpeg_crop_verdict): lane 0 stores them; the caller fences and stores the sequence word.
+__device__ __forceinline__ void jpeg_huff_verdict_words(const uint32_t* __restrict__ ctl, int max_rounds, uint32_t* __restrict__ out)
+{
+    __shared__ uint32_t first_quiet;   // the first round in 1 .. max_rounds that changed nothing, max_rounds + 1: none
+    if (threadIdx.x == 0) first_quiet = (uint32_t)max_rounds + 1u;
+    __syncthreads();
+    for (uint32_t q = 1 + threadIdx.x; q <= (uint32_t)max_rounds; q += blockDim.x)
+        if (ctl[JH_ROUND0 + q] == 0) atomicMin(&first_quiet, q);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const bool settled = first_quiet <= (uint32_t)max_rounds;
+    const bool bound = ctl[JH_BOUND] != 0;
+    uint32_t verdict = JV_DECODED;
+    if (bound || !settled) verdict = ICELK_JPEG_FALLBACK_BOUND;
+    else if (ctl[JH_IRREGULAR]) verdict = ICELK_JPEG_FALLBACK_STREAM;
+    out[JV_VERDICT] = verdict;
+    out[JV_ROUNDS] = first_quiet;   // round 0 and the first_quiet - 1 rounds behind it changed an entry state
+    out[JV_MAX_HOPS] = ctl[JH_MAX_HOPS];
+    out[JV_TOTAL_HOPS] = ctl[JH_TOTAL_HOPS];
+    out[JV_IN_STEP] = ctl[JH_IN_STEP];
+    out[JV_SPANS] = ctl[JH_SPANS];
+}
 
 // LK.  p_in/p_out etc. are device pointers.  fb = fused forward+backward.
 struct LKBuffers {

@@ -184,5 +184,42 @@ ICELK_ENC_FN bool encode_block(Get get, int pred, const uint32_t* dc, const uint
     return ok;
 }
 
+// ---- the budget of a scan whose sizes stay on the device (the crop jobs: abi_jpeg_crop.hip) ----------------------------
+// Such a job may take `cap` = bytes per block x blocks bytes for the stuffed scan; the packed and the stuffed stream are
+// allocated to that before anything is enqueued, and the kernels read the sizes the count and the scans left in the
+// control words.  Every decision they take on those words is one of the functions below, which the host walk
+// (jpeg_enc_host.h: encode_budgeted_host) takes too.
+constexpr int kChunkBytes = 64;          // bytes of the packed stream one lane of ff / stuff takes
+constexpr int kChunksPerGroup = 256;     // lanes of a workgroup of ff / stuff: 16 KiB of the packed stream
+constexpr int kMinBytesPerBlock = 1, kMaxBytesPerBlock = 2 * ((kMaxBlockBits + 7) / 8);   // 416: every byte of a block stuffed
+constexpr int kDefaultBytesPerBlock = 48;
+enum Verdict : uint32_t { kCoded = 1, kOverBudget = 2, kInvalid = 3 };
+
+// blocks * kMaxBlockBits < 2^32 (layout_of) and bytes_per_block <= 416: below 2^31
+ICELK_ENC_FN uint32_t budget_cap(uint32_t blocks, int bytes_per_block) { return blocks * (uint32_t)bytes_per_block; }
+ICELK_ENC_FN uint32_t packed_bytes(uint32_t bits) { return (uint32_t)(((uint64_t)bits + 7u) >> 3); }
+ICELK_ENC_FN uint32_t chunks_of(uint32_t bytes) { return (uint32_t)(((uint64_t)bytes + (kChunkBytes - 1)) / kChunkBytes); }
+ICELK_ENC_FN uint32_t groups_of(uint32_t chunks) { return (chunks + (kChunksPerGroup - 1)) / kChunksPerGroup; }
+// pack runs: every coefficient has a code and the packed stream is inside the capacity
+ICELK_ENC_FN bool packed_fits(uint32_t total_bits, uint32_t invalid, uint32_t cap) { return !invalid && packed_bytes(total_bits) <= cap; }
+// bytes of the packed stream that ff and stuff walk: none of a stream that pack did not write
+ICELK_ENC_FN uint32_t live_bytes(uint32_t total_bits, uint32_t invalid, uint32_t cap)
+{
+    return packed_fits(total_bits, invalid, cap) ? packed_bytes(total_bits) : 0u;
+}
+// stuff runs: the stream with its stuffed bytes is inside the capacity
+ICELK_ENC_FN bool stuffed_fits(uint32_t total_bits, uint32_t invalid, uint32_t ff_total, uint32_t cap)
+{
+    return packed_fits(total_bits, invalid, cap) && (uint64_t)packed_bytes(total_bits) + ff_total <= cap;
+}
+// the stretch of bits that ends at `end_bits` lies in the first `cap` bytes (pack: per workgroup)
+ICELK_ENC_FN bool stretch_inside(uint32_t start_bits, uint32_t end_bits, uint32_t cap) { return end_bits >= start_bits && packed_bytes(end_bits) <= cap; }
+// `n` output bytes from `at` on lie in the first `cap` bytes (stuff: per lane)
+ICELK_ENC_FN bool bytes_inside(uint64_t at, uint32_t n, uint32_t cap) { return at + n <= cap; }
+ICELK_ENC_FN uint32_t budget_verdict(uint32_t total_bits, uint32_t invalid, uint32_t ff_total, uint32_t cap)
+{
+    return invalid ? (uint32_t)kInvalid : (stuffed_fits(total_bits, 0, ff_total, cap) ? (uint32_t)kCoded : (uint32_t)kOverBudget);
+}
+
 }  // namespace enc
 }  // namespace icelk

@@ -11,6 +11,8 @@
 #pragma once
 #include <string.h>
 
+#include <new>
+
 #include "../../include/icelk.h"
 #include "jpeg_enc.h"
 
@@ -208,6 +210,151 @@ inline int encode_host(const icelk_jpeg_info_t* info, const int16_t* coef, const
     B.put16(0xFFD9);
     *len = B.n;
     return out && B.n <= capacity ? ICELK_OK : ICELK_ECAP;
+}
+
+// ---- the budgeted chain of a crop job (abi_jpeg_crop.hip), in the kernels' order --------------------------------------------
+// count, scan, pack, ff, scan, stuff and the verdict as k_jpeg_enc.hip runs them when the sizes stay on the device, with
+// the decisions of jpeg_enc.h: `packed` and `out` hold exactly cap = bytes_per_block x blocks bytes and nothing is read
+// or written outside them, whatever the control words say.  force / force_mask: words of ctl (bit JE_* of the mask) that
+// are overwritten after the scan that writes them -- what a test uses to show that no contents of ctl lead outside.
+struct BudgetWalk {
+    uint32_t cap, chunks, groups;            // capacity in bytes, in chunks, in workgroups of ff / stuff
+    uint32_t total_bits, invalid, ff_total;  // the control words as the verdict saw them
+    uint32_t verdict;                        // enc::Verdict
+    uint32_t stuffed;                        // bytes in `out` when the verdict is kCoded, else 0
+    uint32_t packed_stores, out_stores;      // bytes pack / stuff stored
+};
+
+// bits OR-ed into a zeroed byte buffer at a bit offset, most significant first
+struct PackSink {
+    uint8_t* p;
+    uint64_t at;
+    void put(uint32_t v, int k)
+    {
+        for (int i = k - 1; i >= 0; i--, at++)
+            if (v >> i & 1u) p[at >> 3] |= (uint8_t)(0x80u >> (at & 7u));
+    }
+};
+
+// ICELK_OK with W filled (the verdict is in W, not in the code); ICELK_EARG / _EUNSUP / _ECAP as layout_of; ICELK_ENOMEM
+inline int encode_budgeted_host(const icelk_jpeg_info_t* info, const int16_t* coef, int bytes_per_block, const uint32_t* force,
+                                uint32_t force_mask, uint8_t* packed, uint8_t* out, BudgetWalk* W)
+{
+    constexpr uint32_t kGroupBlocks = 64;    // blocks per workgroup of count and pack
+    enum { TOTAL_BITS = 0, INVALID = 1, FF_TOTAL = 2 };   // JpegEncCtl (icelk_internal.h)
+    Layout L;
+    if (!coef || !W || !packed || !out || bytes_per_block < kMinBytesPerBlock || bytes_per_block > kMaxBytesPerBlock) return ICELK_EARG;
+    if (force_mask && !force) return ICELK_EARG;
+    if (int rc = layout_of(info, &L)) return rc;
+    const Codes& C = codes();
+    const uint32_t cap = budget_cap(L.blocks, bytes_per_block), chunks = chunks_of(cap), groups = groups_of(chunks);
+    *W = BudgetWalk{};
+    W->cap = cap;
+    W->chunks = chunks;
+    W->groups = groups;
+    uint32_t ctl[3] = {0, 0, 0};
+    auto forced = [&](int k) {
+        if (force_mask >> k & 1u) ctl[k] = force[k];
+    };
+    // count
+    const uint32_t ngroups = (L.blocks + kGroupBlocks - 1) / kGroupBlocks;
+    uint16_t* bits = new (std::nothrow) uint16_t[L.blocks];
+    uint32_t* group = new (std::nothrow) uint32_t[ngroups];
+    uint32_t* wg_ff = new (std::nothrow) uint32_t[groups ? groups : 1];
+    struct Drop {
+        uint16_t* a;
+        uint32_t *b, *c;
+        ~Drop()
+        {
+            delete[] a;
+            delete[] b;
+            delete[] c;
+        }
+    } drop{bits, group, wg_ff};
+    if (!bits || !group || !wg_ff) return ICELK_ENOMEM;
+    for (uint32_t g = 0; g < ngroups; g++) group[g] = 0;
+    for (uint32_t s = 0; s < L.blocks; s++) {
+        const Place P = place(L, s);
+        CountSink n;
+        if (!encode_block(HostBlock{coef + P.at}, P.pred == kNoPred ? 0 : coef[P.pred], C.dc[P.table], C.ac[P.table], n)) ctl[INVALID] |= 1u;
+        bits[s] = (uint16_t)n.bits;
+        group[s / kGroupBlocks] += n.bits;
+    }
+    // scan: exclusive, in place; the total
+    uint32_t run = 0;
+    for (uint32_t g = 0; g < ngroups; g++) {
+        const uint32_t x = group[g];
+        group[g] = run;
+        run += x;
+    }
+    ctl[TOTAL_BITS] = run;
+    forced(TOTAL_BITS);
+    forced(INVALID);
+    // pack: the packed stream is zeroed over its whole capacity first
+    memset(packed, 0, cap);
+    if (packed_fits(ctl[TOTAL_BITS], ctl[INVALID], cap)) {
+        for (uint32_t g = 0; g < ngroups; g++) {
+            const uint32_t s0 = g * kGroupBlocks, s1 = s0 + kGroupBlocks < L.blocks ? s0 + kGroupBlocks : L.blocks;
+            uint32_t sum = 0;
+            for (uint32_t s = s0; s < s1; s++) sum += bits[s];
+            const uint32_t start = group[g];
+            uint32_t end = start + sum;
+            const uint32_t fill = g == ngroups - 1 ? (0u - end) & 7u : 0u;
+            end += fill;
+            if (!stretch_inside(start, end, cap)) continue;
+            PackSink S{packed, start};
+            for (uint32_t s = s0; s < s1; s++) {
+                const Place P = place(L, s);
+                encode_block(HostBlock{coef + P.at}, P.pred == kNoPred ? 0 : coef[P.pred], C.dc[P.table], C.ac[P.table], S);
+            }
+            if (fill) S.put((1u << fill) - 1u, (int)fill);
+            W->packed_stores += packed_bytes(end) - packed_bytes(start);   // a byte two stretches share counts for the first
+        }
+    }
+    // ff: per workgroup of the capacity, over the live bytes only
+    const uint32_t live = live_bytes(ctl[TOTAL_BITS], ctl[INVALID], cap);
+    const uint32_t wg_bytes = (uint32_t)kChunkBytes * kChunksPerGroup;
+    for (uint32_t g = 0; g < groups; g++) {
+        uint32_t n = 0;
+        for (uint64_t i = (uint64_t)g * wg_bytes; i < (uint64_t)(g + 1) * wg_bytes && i < live; i++) n += packed[i] == 0xFF;
+        wg_ff[g] = n;
+    }
+    // scan
+    run = 0;
+    for (uint32_t g = 0; g < groups; g++) {
+        const uint32_t x = wg_ff[g];
+        wg_ff[g] = run;
+        run += x;
+    }
+    ctl[FF_TOTAL] = run;
+    forced(FF_TOTAL);
+    // stuff: a lane per chunk
+    if (stuffed_fits(ctl[TOTAL_BITS], ctl[INVALID], ctl[FF_TOTAL], cap)) {
+        const uint32_t nbytes = packed_bytes(ctl[TOTAL_BITS]), nchunks = chunks_of(nbytes);
+        uint32_t before = 0;
+        for (uint32_t ch = 0; ch < nchunks; ch++) {
+            if (ch % kChunksPerGroup == 0) before = wg_ff[ch / kChunksPerGroup];
+            const uint32_t at = ch * (uint32_t)kChunkBytes, n = nbytes - at < (uint32_t)kChunkBytes ? nbytes - at : (uint32_t)kChunkBytes;
+            uint32_t ff = 0;
+            for (uint32_t j = 0; j < n; j++) ff += packed[at + j] == 0xFF;
+            if (bytes_inside((uint64_t)at + before, n + ff, cap)) {
+                uint8_t* dst = out + at + before;
+                for (uint32_t j = 0; j < n; j++) {
+                    *dst++ = packed[at + j];
+                    if (packed[at + j] == 0xFF) *dst++ = 0;
+                }
+                W->out_stores += n + ff;
+            }
+            before += ff;
+        }
+    }
+    // verdict
+    W->total_bits = ctl[TOTAL_BITS];
+    W->invalid = ctl[INVALID];
+    W->ff_total = ctl[FF_TOTAL];
+    W->verdict = budget_verdict(ctl[TOTAL_BITS], ctl[INVALID], ctl[FF_TOTAL], cap);
+    W->stuffed = W->verdict == kCoded ? packed_bytes(ctl[TOTAL_BITS]) + ctl[FF_TOTAL] : 0u;
+    return ICELK_OK;
 }
 
 }  // namespace enc

@@ -24,6 +24,12 @@
 //           place, a 00 behind every FF.  Byte stores: a lane's output has no alignment to speak of
 // Lanes diverge per coefficient in count and pack (zero or not, ZRL or not), as the decoder's lanes do per symbol; the
 // loop counter, the table addresses and everything between the walks are uniform.  No scratch in any kernel.
+//
+// The device-sized forms (k_jpeg_enc_pack_budget, _ff_budget, _stuff_budget; the crop jobs of abi_jpeg_crop.hip) run the
+// same bodies with the sizes read from the control words instead of from the host: packed and stuffed stream are
+// allocated to a capacity of `cap` bytes beforehand, and each of the three leaves the whole grid -- a uniform branch on
+// two loaded words -- when the stream does not fit it (jpeg_enc.h: packed_fits, live_bytes, stuffed_fits).  Behind them
+// k_jpeg_crop_verdict, one wave, publishes the decoder's and the coder's verdict and the stuffed length to pinned words.
 #include "icelk_internal.h"
 
 namespace icelk {
@@ -35,6 +41,7 @@ constexpr int kTilePitch = 66;   // halfwords per lane: 33 dwords, so the lanes 
 // dwords of a group's stretch at most: up to 31 bits of the dword it begins in, its blocks, the 7 bits of padding
 constexpr int kStretchDwords = (31 + kGroup * enc::kMaxBlockBits + 7 + 31) / 32;
 constexpr int kChunk = kJpegEncChunk;   // bytes of the packed stream per lane of ff / stuff
+static_assert(kChunk == enc::kChunkBytes && enc::kChunksPerGroup == 256, "jpeg_enc.h sizes the capacity by these");
 
 constexpr uint8_t kZz[64] = ICELK_ENC_ZIGZAG;
 constexpr int zigzag_of(int natural)
@@ -186,7 +193,10 @@ __global__ __launch_bounds__(kJpegEncScanPass) void k_jpeg_enc_scan(uint32_t* v,
     if (t == 0) *total = carry_s;
 }
 
-__global__ __launch_bounds__(kJpegEncGroup) void k_jpeg_enc_pack(JpegEncArgs A)
+// the body of pack.  Budget: the workgroup leaves before any store when its stretch does not end inside `cap` bytes --
+// with control words that the chain itself wrote the grid's exit in k_jpeg_enc_pack_budget has decided that already
+template <bool Budget>
+__device__ __forceinline__ void pack_group(const JpegEncArgs& A, uint32_t cap)
 {
     __shared__ uint16_t tile[kGroup][kTilePitch];
     __shared__ uint32_t codes[enc::kCodeWords];
@@ -210,6 +220,7 @@ __global__ __launch_bounds__(kJpegEncGroup) void k_jpeg_enc_pack(JpegEncArgs A)
     const bool last_group = blockIdx.x == gridDim.x - 1;
     const uint32_t fill = last_group ? (0u - end) & 7u : 0u;       // the 1-bits that complete the stream's last byte
     end += fill;
+    if (Budget && !enc::stretch_inside(start, end, cap)) return;   // uniform: start and end are the workgroup's
     const uint32_t first_dw = start >> 5, ndw = ((end + 31u) >> 5) - first_dw;   // <= kStretchDwords; >= 1: a block has bits
     for (uint32_t i = lane; i < ndw; i += kGroup) stream[i] = 0u;
     __syncthreads();
@@ -231,7 +242,15 @@ __global__ __launch_bounds__(kJpegEncGroup) void k_jpeg_enc_pack(JpegEncArgs A)
     }
 }
 
-__global__ __launch_bounds__(256) void k_jpeg_enc_ff(const uint32_t* packed, uint32_t nchunks, uint32_t* wg_ff)
+__global__ __launch_bounds__(kJpegEncGroup) void k_jpeg_enc_pack(JpegEncArgs A) { pack_group<false>(A, 0u); }
+
+__global__ __launch_bounds__(kJpegEncGroup) void k_jpeg_enc_pack_budget(JpegEncArgs A, uint32_t cap)
+{
+    if (!enc::packed_fits(A.ctl[JE_TOTAL_BITS], A.ctl[JE_INVALID], cap)) return;   // the whole grid: nothing is stored
+    pack_group<true>(A, cap);
+}
+
+__device__ __forceinline__ void ff_group(const uint32_t* packed, uint32_t nchunks, uint32_t* wg_ff)
 {
     __shared__ uint32_t wave_sum[4];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
@@ -244,8 +263,19 @@ __global__ __launch_bounds__(256) void k_jpeg_enc_ff(const uint32_t* packed, uin
     if (t == 0) wg_ff[blockIdx.x] = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
 }
 
-__global__ __launch_bounds__(256) void k_jpeg_enc_stuff(const uint32_t* packed, uint32_t nbytes, uint32_t nchunks, const uint32_t* wg_off,
-                                                        uint8_t* out)
+__global__ __launch_bounds__(256) void k_jpeg_enc_ff(const uint32_t* packed, uint32_t nchunks, uint32_t* wg_ff) { ff_group(packed, nchunks, wg_ff); }
+
+// the grid covers the capacity; a workgroup behind the live chunks (all of them when pack left) counts 0
+__global__ __launch_bounds__(256) void k_jpeg_enc_ff_budget(const uint32_t* packed, const uint32_t* ctl, uint32_t cap, uint32_t* wg_ff)
+{
+    ff_group(packed, enc::chunks_of(enc::live_bytes(ctl[JE_TOTAL_BITS], ctl[JE_INVALID], cap)), wg_ff);
+}
+
+// the body of stuff.  Budget: a lane leaves when its bytes would not end inside `cap` -- as in pack_group, with control
+// words of the chain's own the grid's exit has decided that already
+template <bool Budget>
+__device__ __forceinline__ void stuff_group(const uint32_t* packed, uint32_t nbytes, uint32_t nchunks, const uint32_t* wg_off, uint8_t* out,
+                                            uint32_t cap)
 {
     __shared__ uint32_t wave_sum[4];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
@@ -260,6 +290,7 @@ __global__ __launch_bounds__(256) void k_jpeg_enc_stuff(const uint32_t* packed, 
     uint32_t before = wg_off[blockIdx.x] + inc - ff;
     for (int k = 0; k < wv; k++) before += wave_sum[k];
     const uint32_t at = chunk * (uint32_t)kChunk;
+    if (Budget && !enc::bytes_inside((uint64_t)at + before, min((uint32_t)kChunk, nbytes - at) + ff, cap)) return;   // live: at < nbytes
     uint8_t* dst = out + (size_t)at + before;
 #pragma unroll
     for (int j = 0; j < kChunk; j++) {
@@ -269,6 +300,37 @@ __global__ __launch_bounds__(256) void k_jpeg_enc_stuff(const uint32_t* packed, 
             if (b == 0xffu) *dst++ = 0;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_jpeg_enc_stuff(const uint32_t* packed, uint32_t nbytes, uint32_t nchunks, const uint32_t* wg_off,
+                                                        uint8_t* out)
+{
+    stuff_group<false>(packed, nbytes, nchunks, wg_off, out, 0u);
+}
+
+__global__ __launch_bounds__(256) void k_jpeg_enc_stuff_budget(const uint32_t* packed, const uint32_t* ctl, uint32_t cap, const uint32_t* wg_off,
+                                                               uint8_t* out)
+{
+    const uint32_t bits = ctl[JE_TOTAL_BITS];
+    if (!enc::stuffed_fits(bits, ctl[JE_INVALID], ctl[JE_FF_TOTAL], cap)) return;   // the whole grid: nothing is stored
+    const uint32_t nbytes = enc::packed_bytes(bits);
+    stuff_group<true>(packed, nbytes, enc::chunks_of(nbytes), wg_off, out, cap);
+}
+
+// One wave behind the whole chain of a crop job: the decoder's verdict and statistics as k_jpeg_huff_verdict publishes
+// them, the coder's verdict and the stuffed length, then the sequence word -- plain stores to the pinned words, a
+// system-scope fence, a release store.
+__global__ __launch_bounds__(64) void k_jpeg_crop_verdict(const uint32_t* __restrict__ huff_ctl, int max_rounds, const uint32_t* __restrict__ enc_ctl,
+                                                          uint32_t cap, uint32_t* __restrict__ out, uint32_t seq)
+{
+    jpeg_huff_verdict_words(huff_ctl, max_rounds, out);
+    if (threadIdx.x != 0) return;
+    const uint32_t bits = enc_ctl[JE_TOTAL_BITS], invalid = enc_ctl[JE_INVALID], ff = enc_ctl[JE_FF_TOTAL];
+    const uint32_t verdict = enc::budget_verdict(bits, invalid, ff, cap);
+    out[JV_ENC_VERDICT] = verdict;
+    out[JV_ENC_LEN] = verdict == enc::kCoded ? enc::packed_bytes(bits) + ff : 0u;
+    __threadfence_system();
+    __hip_atomic_store(out + JV_SEQ, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 void launch_jpeg_enc_count(hipStream_t s, const JpegEncArgs& A)
@@ -294,6 +356,28 @@ void launch_jpeg_enc_ff(hipStream_t s, const uint32_t* packed, uint32_t nchunks,
 void launch_jpeg_enc_stuff(hipStream_t s, const uint32_t* packed, uint32_t nbytes, uint32_t nchunks, const uint32_t* wg_off, uint8_t* out)
 {
     hipLaunchKernelGGL(k_jpeg_enc_stuff, dim3((nchunks + 255) / 256), dim3(256), 0, s, packed, nbytes, nchunks, wg_off, out);
+}
+
+// ---- the device-sized forms: grids by the capacity `cap`, sizes from A.ctl --------------------------------------------
+void launch_jpeg_enc_pack_budget(hipStream_t s, const JpegEncArgs& A, uint32_t cap)
+{
+    hipLaunchKernelGGL(k_jpeg_enc_pack_budget, dim3((A.L.blocks + kGroup - 1) / kGroup), dim3(kGroup), 0, s, A, cap);
+}
+
+void launch_jpeg_enc_ff_budget(hipStream_t s, const uint32_t* packed, const uint32_t* ctl, uint32_t cap, uint32_t* wg_ff)
+{
+    hipLaunchKernelGGL(k_jpeg_enc_ff_budget, dim3(enc::groups_of(enc::chunks_of(cap))), dim3(256), 0, s, packed, ctl, cap, wg_ff);
+}
+
+void launch_jpeg_enc_stuff_budget(hipStream_t s, const uint32_t* packed, const uint32_t* ctl, uint32_t cap, const uint32_t* wg_off, uint8_t* out)
+{
+    hipLaunchKernelGGL(k_jpeg_enc_stuff_budget, dim3(enc::groups_of(enc::chunks_of(cap))), dim3(256), 0, s, packed, ctl, cap, wg_off, out);
+}
+
+void launch_jpeg_crop_verdict(hipStream_t s, const uint32_t* huff_ctl, int max_rounds, const uint32_t* enc_ctl, uint32_t cap, uint32_t* host_words,
+                              uint32_t seq)
+{
+    hipLaunchKernelGGL(k_jpeg_crop_verdict, dim3(1), dim3(64), 0, s, huff_ctl, max_rounds, enc_ctl, cap, host_words, seq);
 }
 
 }  // namespace icelk

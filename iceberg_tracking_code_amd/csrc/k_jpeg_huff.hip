@@ -243,24 +243,8 @@ __global__ __launch_bounds__(256) void k_jpeg_dc_scan(JpegHuffArgs H)
 __global__ __launch_bounds__(64) void k_jpeg_huff_verdict(const uint32_t* __restrict__ ctl, int max_rounds, uint32_t* __restrict__ out,
                                                           uint32_t seq)
 {
-    __shared__ uint32_t first_quiet;   // the first round in 1 .. max_rounds that changed nothing, max_rounds + 1: none
-    if (threadIdx.x == 0) first_quiet = (uint32_t)max_rounds + 1u;
-    __syncthreads();
-    for (uint32_t q = 1 + threadIdx.x; q <= (uint32_t)max_rounds; q += blockDim.x)
-        if (ctl[JH_ROUND0 + q] == 0) atomicMin(&first_quiet, q);
-    __syncthreads();
+    jpeg_huff_verdict_words(ctl, max_rounds, out);
     if (threadIdx.x != 0) return;
-    const bool settled = first_quiet <= (uint32_t)max_rounds;
-    const bool bound = ctl[JH_BOUND] != 0;
-    uint32_t verdict = JV_DECODED;
-    if (bound || !settled) verdict = ICELK_JPEG_FALLBACK_BOUND;
-    else if (ctl[JH_IRREGULAR]) verdict = ICELK_JPEG_FALLBACK_STREAM;
-    out[JV_VERDICT] = verdict;
-    out[JV_ROUNDS] = first_quiet;   // round 0 and the first_quiet - 1 rounds behind it changed an entry state
-    out[JV_MAX_HOPS] = ctl[JH_MAX_HOPS];
-    out[JV_TOTAL_HOPS] = ctl[JH_TOTAL_HOPS];
-    out[JV_IN_STEP] = ctl[JH_IN_STEP];
-    out[JV_SPANS] = ctl[JH_SPANS];
     __threadfence_system();
     __hip_atomic_store(out + JV_SEQ, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }

@@ -90,7 +90,9 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
     resave         None: pixel values are those of the photos.  "reference": the tracker sees what the reference's tracker
                    sees, the crop saved by Pillow as a new JPEG (quality 75, s1:272) and opened again -- reproduced on the
                    device, no file is written; an int: that quality.  Not with pipeline=True.  A file the device decoder
-                   does not take goes through PIL, that file only, and is re-saved on the device all the same
+                   does not take goes through PIL, that file only, and is re-saved on the device all the same.  The
+                   two-pass route gets the same tracks with pipeline=True: `crop.crop_image_sequence` writes the re-saved
+                   crops first, and this function then runs on those files with no crop and no resave
     save_crops     with resave: a directory that receives `<basename of the photo>` for every photo ingested, the file the
                    reference's crop step writes into its target folder (`Image.open(p).crop(box).save(out)`, the source's
                    comment carried over), entropy-coded on the device (csrc/k_jpeg_enc.hip) right after the upload and

@@ -571,6 +571,62 @@ int icelk_jpeg_encode_coefficients(icelk_t* h, const icelk_jpeg_info_t* info, co
 int icelk_jpeg_resave_encode(icelk_t* h, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity,
                              uint64_t* len);
 
+/* ---- the crop step on its own: decode, crop, re-save and encode with no host wait (opt-in) -------
+ * The reference's crop_image_parallel (camtools.py:64-104, 237-258) writes a folder of re-saved crops before anything is
+ * tracked.  A crop job makes one such file: icelk_jpeg_crop_start does the host's share (as icelk_upload_jpeg_file_async:
+ * index, lanes, the checks of descriptor, crop box, quality and cropped size -- their errors are returned there), copies
+ * the bytes into pinned memory of the library and enqueues, on a decode stream and without a wait, the Huffman decoding,
+ * the inverse DCT, the crop box as R G B, the re-save's forward kernel, the entropy coder and a verdict.  No frame slot
+ * is touched and max_w x max_h of icelk_create bound neither the photo nor the crop.  Every job in flight owns a working
+ * set of its own (at 12 MP and 48 bytes per block ~160 MB: the decoder's set, the cropped R G B, the re-save's coefficients
+ * and 27 MB for the coder; the sets are kept and reused).
+ * The coder's sizes stay on the device: the job may take stream_bytes_per_block x blocks bytes for the stuffed scan
+ * (icelk_jpeg_crop_config; 1 .. 416, default 48: a 12 MP photo takes 7 at quality 75 and 17 at 95, uniform noise at
+ * quality 100 takes 84).  A scan that does not fit is coded again by icelk_jpeg_crop_finish with the sizes read by the
+ * host; a file the device's Huffman decoder does not settle is decoded by the host decoder there.  The bytes are the same
+ * on every route: those of icelk_upload_jpeg_file_resave followed by icelk_jpeg_resave_encode. */
+#define ICELK_JPEG_CROP_DEVICE 0          /* coded on the device within the budget, no host wait before the verdict */
+#define ICELK_JPEG_CROP_HOST_HUFFMAN 1    /* the host decoder took the file (huff.fallback says why); the chain ran again */
+#define ICELK_JPEG_CROP_OVER_BUDGET 2     /* the scan did not fit the budget: coded again with host-read sizes */
+typedef struct icelk_jpeg_crop_stats {
+    icelk_jpeg_huff_stats_t huff;         /* of the source file's decoding */
+    uint32_t route;                       /* ICELK_JPEG_CROP_* */
+    uint32_t blocks;                      /* of the re-saved file's scan */
+    uint64_t budget;                      /* bytes the stuffed scan could take on the device */
+    uint64_t stream_len;                  /* bytes of the stuffed scan */
+} icelk_jpeg_crop_stats_t;
+/* Host only, no handle: the decisions the device-sized kernels take on their control words (csrc/jpeg_enc.h), for tests.
+ * out[0 .. 8) = capacity in bytes, its chunks of 64 bytes, its workgroups of 256 chunks, bytes of the packed stream,
+ * 1 if pack runs, bytes ff and stuff walk, 1 if stuff runs, the verdict (1 coded, 2 over budget, 3 invalid). */
+int icelk_jpeg_enc_budget(uint32_t blocks, int stream_bytes_per_block, uint32_t total_bits, uint32_t invalid, uint32_t ff_total,
+                          uint32_t* out);
+/* Host only, no handle, re-entrant: the budgeted chain in the kernels' order on the CPU (csrc/jpeg_enc_host.h), with
+ * buffers of exactly the capacity.  Coded: the whole file as icelk_jpeg_encode_coefficients_host writes it, ICELK_OK.
+ * Over budget or invalid: nothing is written, *len = 0, ICELK_OK.  report (may be NULL): 8 words -- capacity, total bits,
+ * invalid, FF count, verdict, stuffed bytes, bytes pack stored, bytes stuff stored.  force / force_mask: control words
+ * (bit k of the mask: word k of total bits, invalid, FF count) overwritten behind the scan that wrote them; NULL / 0: none.
+ * ICELK_ECAP: `out` is too small, *len says what it takes. */
+int icelk_jpeg_encode_budgeted_host(const icelk_jpeg_info_t* info, const int16_t* coef, int stream_bytes_per_block, const uint32_t* force,
+                                    uint32_t force_mask, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity,
+                                    uint64_t* len, uint32_t* report);
+/* 1 .. 416 bytes of stuffed scan per block that a crop job started from now on may take on the device. */
+int icelk_jpeg_crop_config(icelk_t* h, int stream_bytes_per_block);
+/* Starts a crop job for the file and returns its ticket without waiting; `file` is free on return.  crop_*: pixels to
+ * drop on each side; quality 1 .. 100; the cropped width must be >= 3.  Error codes as icelk_upload_jpeg_file_resave, and
+ * ICELK_ECAP for a crop of so many blocks that blocks * 1660 bits do not fit 32 bits; no ticket is taken then. */
+int icelk_jpeg_crop_start(icelk_t* h, const uint8_t* file, uint64_t len, int crop_left, int crop_top, int crop_right, int crop_bottom,
+                          int quality, int* ticket);
+/* Never blocks: *state = 0 in flight, 1 coded on the device, 2 icelk_jpeg_crop_finish has host work to do. */
+int icelk_jpeg_crop_poll(icelk_t* h, int ticket, int* state);
+/* Waits for the job's verdict, takes the routes named above, and writes the file -- header (with one COM segment when
+ * comment != NULL), scan, EOI -- into out.  ICELK_ECAP: out is too small (or NULL), *len says what the file takes and the
+ * ticket stays valid: the call can be repeated.  After ICELK_OK or any other error the ticket is gone and its working set
+ * free.  stats may be NULL.  ICELK_ESTATE: no such ticket in flight. */
+int icelk_jpeg_crop_finish(icelk_t* h, int ticket, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity,
+                           uint64_t* len, icelk_jpeg_crop_stats_t* stats);
+/* Waits for what the job has enqueued and drops the ticket. */
+int icelk_jpeg_crop_cancel(icelk_t* h, int ticket);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector

@@ -11,6 +11,8 @@
     python tools/jpeg_ingest.py pipeline-loop [--frames 24]                       MI355X: pipelined runs for a kernel trace
     python tools/jpeg_ingest.py resave [--frames 24] [--out profiles/jpeg_resave.txt]  MI355X: the reference's re-save of the crop
     python tools/jpeg_ingest.py resave-file [--frames 24] [--out profiles/jpeg_resave_file.txt]  MI355X: ... written as files
+    python tools/jpeg_ingest.py crop-folder [--frames 96] [--out profiles/jpeg_crop_folder.txt]  MI355X: the crop step on its own
+    python tools/jpeg_ingest.py crop-folder-loop [--frames 24]                    MI355X: the calls for a kernel trace
 
 host    one thread, best of 5: `read_jpeg` (Huffman decoding into coefficients) against `np.array(Image.open(...))` (what
         the "pil" decoder does per photo), and Pillow's own 1/8-scale draft decode -- entropy decoding plus a DC-only
@@ -39,6 +41,12 @@ resave-file    the re-saved crop as a file (`Context.jpeg_resave_file`, csrc/k_j
         kernel against the bytes it moves, the whole call by the host clock split into kernels, the rest (two
         synchronisations, the copy to the host, the header) and the file write; then photos per second of the folder
         driver with resave="reference", without and with save_crops, alternating, three runs each.
+crop-folder    the crop step on its own (`crop_image_sequence`, csrc/abi_jpeg_crop.hip) on the folder of resave-file: the same
+        yardstick first (one thread, a pool of 16 processes forked before the GPU is touched); then, alternating behind
+        untimed runs, three runs each of (a) the synchronous way to the same folder -- `upload_jpeg_file(resave=)`,
+        `jpeg_resave_file()` and the write, photo by photo on the calling thread -- and (b) `crop_image_sequence`; every
+        file of (b) is compared with Pillow's before a rate counts; then where a photo's time goes in (b), one job at a time.
+crop-folder-loop   two runs of `crop_image_sequence` and nothing else, for `rocprofv3 --kernel-trace --stats --`.
 pipeline-loop  one plain and two pipelined runs of the same folder and nothing else, for `rocprofv3 --kernel-trace --stats --`.
 """
 import argparse
@@ -533,6 +541,139 @@ def resave_file(out, n, threads):
     os.rmdir(tmp)
 
 
+def _median(v):
+    return sorted(v)[len(v) // 2]
+
+
+def _remove_tree(tmp, dirs, names):
+    for d in dirs:
+        if not os.path.isdir(d):
+            continue
+        for f in os.listdir(d):
+            os.remove(os.path.join(d, f))
+        os.rmdir(d)
+    for p in names:
+        os.remove(p)
+    os.rmdir(tmp)
+
+
+def crop_folder(out, n):
+    import multiprocessing as mp
+    tmp, names = folder(n)
+    dirs = [os.path.join(tmp, d) for d in ("crops_pillow", "crops_a", "crops_b")]
+    for d in dirs:
+        os.makedirs(d)
+    pillow_dir, a_dir, b_dir = dirs
+    try:                                                     # the tree goes whatever happens: 96 photos of 12 MP
+        jobs = [(p, os.path.join(pillow_dir, os.path.basename(p))) for p in names]
+        print("the crop step on its own, %d photos of %dx%d 4:2:0 quality 90, %d usable cores" % (n, W, H, len(os.sched_getaffinity(0))), file=out)
+        print("yardstick, the reference's step on the host (Image.open -> crop -> save, quality 75), photos/s, three runs each:", file=out)
+        _reference_step(jobs[0])                                 # untimed
+        one = []
+        for _ in range(3):
+            t = time.perf_counter()
+            for j in jobs:
+                _reference_step(j)
+            one.append(n / (time.perf_counter() - t))
+        print("  one thread:           %s" % ", ".join("%.1f" % v for v in one), file=out)
+        with mp.get_context("fork").Pool(16) as pool:            # before this process touches the GPU
+            pool.map(_reference_step, jobs)
+            many = []
+            for _ in range(3):
+                t = time.perf_counter()
+                pool.map(_reference_step, jobs)
+                many.append(n / (time.perf_counter() - t))
+        print("  pool of 16 processes: %s" % ", ".join("%.1f" % v for v in many), file=out)
+        out.flush()
+
+        from iceberg_tracking_code_amd import Context, crop_image_sequence, source_comment
+        ctx = Context(W, H, n_slots=2, max_pts=64)
+
+        def run_a():
+            """the synchronous way, everything on the calling thread"""
+            t = time.perf_counter()
+            for p in names:
+                with open(p, "rb") as f:
+                    data = f.read()
+                ctx.upload_jpeg_file(0, data, 4, None, resave="reference")
+                got = ctx.jpeg_resave_file(source_comment(data))
+                with open(os.path.join(a_dir, os.path.basename(p)), "wb") as f:
+                    f.write(got)
+            return n / (time.perf_counter() - t)
+
+        def run_b():
+            t = time.perf_counter()
+            done = crop_image_sequence(names, b_dir, ctx=ctx)
+            return n / (time.perf_counter() - t), done
+
+        try:
+            run_a()                                              # untimed: cold files, code objects, clocks, the jobs' buffers
+            _, done = run_b()
+            routes = {}
+            for (path, nbytes, route), (_, want) in zip(done, jobs):
+                routes[route] = routes.get(route, 0) + 1
+                for mine in (path, os.path.join(a_dir, os.path.basename(path))):
+                    with open(mine, "rb") as f, open(want, "rb") as g:
+                        if f.read() != g.read():
+                            raise SystemExit("%s differs from Pillow's file" % mine)
+            print("all %d files of (a) and of (b) equal Pillow's; routes of (b): %s" % (n, routes), file=out)
+            res = {"a": [], "b": []}
+            for _ in range(3):
+                res["a"].append(run_a())
+                res["b"].append(run_b()[0])
+            print("(a) upload_jpeg_file(resave=) + jpeg_resave_file() + write, calling thread, photos/s (runs in order): %s" %
+                  ", ".join("%.1f" % v for v in res["a"]), file=out)
+            print("(b) crop_image_sequence, 4 readers, 2 writers, 4 in flight, photos/s:                               %s" %
+                  ", ".join("%.1f" % v for v in res["b"]), file=out)
+            ma, mb, mo, mm = (_median(v) for v in (res["a"], res["b"], one, many))
+
+            def verdict(x, y):
+                return "no difference (below the 10 %% spread between runs)" if abs(x / y - 1) < 0.10 else "%.2f x" % (x / y)
+            print("medians: (a) %.1f, (b) %.1f, one thread %.1f, pool of 16 %.1f; (b) against (a): %s; (b) against the pool: %s" %
+                  (ma, mb, mo, mm, verdict(mb, ma), verdict(mb, mm)), file=out)
+            # where a photo's time goes in (b): one job at a time, by the host clock
+            parts = {k: [] for k in ("read", "start", "device", "finish", "write")}
+            for p in names:
+                t0 = time.perf_counter()
+                with open(p, "rb") as f:
+                    data = f.read()
+                comment = source_comment(data)
+                t1 = time.perf_counter()
+                ticket = ctx.jpeg_crop_start(data, None, 75)
+                t2 = time.perf_counter()
+                while ctx.jpeg_crop_poll(ticket) == 0:
+                    pass
+                t3 = time.perf_counter()
+                got, _ = ctx.jpeg_crop_finish(ticket, comment)
+                t4 = time.perf_counter()
+                with open(os.path.join(b_dir, os.path.basename(p)), "wb") as f:
+                    f.write(got)
+                t5 = time.perf_counter()
+                for k, v in zip(("read", "start", "device", "finish", "write"), (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4)):
+                    parts[k].append(1e3 * v)
+            print("one job at a time, median ms per photo: " + ", ".join("%s %.3f" % (k, _median(v)) for k, v in parts.items()) +
+                  " (start: index, lanes, the copy into pinned memory, the enqueue; device: polling until the verdict; finish: the copy "
+                  "of the scan, header, bytes object)", file=out)
+        finally:
+            ctx.close()
+    finally:
+        _remove_tree(tmp, dirs, names)
+
+
+def crop_folder_loop(n):
+    from iceberg_tracking_code_amd import crop_image_sequence
+    tmp, names = folder(n)
+    d = os.path.join(tmp, "crops")
+    os.makedirs(d)
+    try:
+        for rep in range(2):
+            t = time.perf_counter()
+            done = crop_image_sequence(names, d)
+            print("crop_image_sequence: %.1f photos/s, routes %s" % (n / (time.perf_counter() - t), sorted({r for _, _, r in done})))
+    finally:
+        _remove_tree(tmp, [d], names)
+
+
 def encode_default(img):
     """Pillow's defaults, as the reference's crop pool saves"""
     b = io.BytesIO()
@@ -554,16 +695,20 @@ def pipeline_loop(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("mode", choices=("host", "device", "e2e", "huffman", "huffman-loop", "e2e-huffman", "e2e-pipeline",
-                                         "pipeline-loop", "resave", "resave-file"))
+                                         "pipeline-loop", "resave", "resave-file", "crop-folder", "crop-folder-loop"))
     ap.add_argument("--out", default=None)
-    ap.add_argument("--frames", type=int, default=24)
+    ap.add_argument("--frames", type=int, default=None)
     ap.add_argument("--threads", type=int, default=16)
     a = ap.parse_args()
+    if a.frames is None:
+        a.frames = 96 if a.mode == "crop-folder" else 24
     if a.mode == "huffman-loop":
         return huffman_loop()
     if a.mode == "pipeline-loop":
         return pipeline_loop(a.frames)
-    name = {"resave": "jpeg_resave", "resave-file": "jpeg_resave_file", "huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e", "e2e-pipeline": "jpeg_pipeline_e2e"}.get(
+    if a.mode == "crop-folder-loop":
+        return crop_folder_loop(a.frames)
+    name = {"resave": "jpeg_resave", "resave-file": "jpeg_resave_file", "crop-folder": "jpeg_crop_folder", "huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e", "e2e-pipeline": "jpeg_pipeline_e2e"}.get(
         a.mode, "jpeg_ingest_%s" % a.mode)
     path = a.out or os.path.join(ROOT, "profiles", name + ".txt")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -580,6 +725,8 @@ def main():
             resave(out, a.frames, min(a.threads, 16))
         elif a.mode == "resave-file":
             resave_file(out, a.frames, min(a.threads, 16))
+        elif a.mode == "crop-folder":
+            crop_folder(out, a.frames)
         elif a.mode == "e2e-pipeline":
             pipeline(out, a.frames, min(a.threads, 16))
         else:
