@@ -22,6 +22,7 @@ from .postprocess import (VelocityCube, average_periods, average_spatially_tempo
 from .calibration import CalibrationResult, ShorelineScene, calibrate, run_calibration  # noqa: F401
 from .jpeg import (JpegCoefficients, UnsupportedJpeg, decode_jpeg, read_jpeg, read_jpeg_lanes, resave_coefficients,  # noqa: F401
                    resave_rgb, resave_tables, encode_jpeg, resave_bytes, source_comment)
+from .plot import plot_glyph, plot_name, plot_overlay_host, plot_size, plot_stamp  # noqa: F401
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f32p, u8p
+from .plot import PLOT_QUALITY, PLOT_WIDTH, _stamp_arg, _tracks3, plot_size
 from .jpeg import (UnsupportedJpeg, _comment_args, _encode_call, _rgb3, _stats_dict, describe_jpeg, resave_coefficients,
                    resave_quality)
 
@@ -572,6 +573,39 @@ class Context:
             self._ck(fn(self._h, _f32(tracks), _f32(quality), n.value, nv.value, C.byref(n),
                                               C.byref(nv)))
         return tracks, quality
+
+    # -- the picture of a segment (s1:397-434) --------------------------------------------------
+    def _plot_call(self, slot, width, want_rgb, call, what):
+        """call(rgb pointer, rgb stride, out, capacity, byref(len)) -> rc; the file's bytes, with the R G B if asked for"""
+        rgb, rgb_ptr, stride = None, None, 0
+        if want_rgb:
+            w, h = C.c_int(0), C.c_int(0)
+            self._ck(self._lib.icelk_download_level(self._h, int(slot), 0, None, 0, C.byref(w), C.byref(h)))
+            ow, oh = plot_size(w.value, h.value, width)
+            rgb = np.empty((oh, ow, 3), np.uint8)
+            rgb_ptr, stride = _u8(rgb), rgb.strides[0]
+        guess = getattr(self, "_plot_file_guess", 1 << 18)
+        data = _encode_call(lambda out, cap, n: call(rgb_ptr, stride, out, cap, n), guess, what, self._h)
+        self._plot_file_guess = max(1 << 16, len(data) + len(data) // 4)   # the next picture of a day is about as large
+        return (data, rgb) if want_rgb else data
+
+    def plot_tracks(self, slot, tracks, width=PLOT_WIDTH, stamp="", quality=PLOT_QUALITY, want_rgb=False):
+        """The picture of the frame in `slot` with `tracks` (n, vertices, 2) drawn on it -- red lines, a red dot at every
+        track's end, `stamp` in a corner -- `width` pixels wide, as the bytes of a JPEG file (icelk_plot_tracks; the rules
+        are DESIGN.md 7.6).  Rasterised and coded on the device; the file is what `Image.fromarray(rgb).save(f, "JPEG",
+        quality=quality)` writes for the picture's R G B.  want_rgb: (bytes, that R G B (Ho, Wo, 3) uint8), for tests.
+        IcelkError (code ICELK_ESTATE) for an empty slot."""
+        t = _tracks3(tracks)
+        text = _stamp_arg(stamp)
+        return self._plot_call(slot, width, want_rgb, lambda rgb, stride, out, cap, n: self._lib.icelk_plot_tracks(
+            self._h, int(slot), _f32(t), t.shape[0], t.shape[1], int(width), text, int(quality), rgb, stride, out, cap, n), "icelk_plot_tracks")
+
+    def seg_plot(self, slot, closed=False, width=PLOT_WIDTH, stamp="", quality=PLOT_QUALITY, want_rgb=False):
+        """`plot_tracks` with the surviving tracks of the current segment (`closed`: of the segment the latest switch
+        closed), gathered on the device: no track data crosses PCIe (icelk_seg_plot)."""
+        text = _stamp_arg(stamp)
+        return self._plot_call(slot, width, want_rgb, lambda rgb, stride, out, cap, n: self._lib.icelk_seg_plot(
+            self._h, int(slot), int(bool(closed)), int(width), text, int(quality), rgb, stride, out, cap, n, None), "icelk_seg_plot")
 
     # -- measurement ----------------------------------------------------------------------------
     def prof_enable(self, on=True):

@@ -547,6 +547,25 @@ static int seg_read_core(Ctx* c, bool closed, float* tracks, float* quality, int
     return ICELK_OK;
 }
 
+}  // extern "C"
+
+// The surviving tracks of the current segment (closed: of the one the latest switch closed), packed (n, vertices, 2) in
+// the handle's read-out buffer d_out_tracks, on the compute stream: what the read-outs copy to the host, for a consumer
+// on the device (abi_plot.hip).  A pair of the segment that still waits goes out first.  Waits for the count.
+int icelk::seg_gather_packed(Ctx* c, bool closed, int* out_n, int* out_vertices)
+{
+    int n = 0;
+    if (int rc = seg_live_core(c, closed, &n, nullptr)) return rc;
+    Ctx::SegBuf& S = c->sb[closed ? (c->sb_cur + kSegSets - 1) % kSegSets : c->sb_cur];
+    *out_n = n;
+    *out_vertices = S.vert;
+    if (n == 0) return ICELK_OK;
+    launch_seg_gather(c->stream, S.alive, S.upper, S.tracks, S.quality, S.vert, kMaxVert, c->d_out_tracks, c->d_out_quality);
+    return check_launch(c, "seg_gather");
+}
+
+extern "C" {
+
 int icelk_seg_read(icelk_t* h, float* tracks, float* quality, int cap, int max_vertices, int* out_n, int* out_vertices)
 {
     if (!h) return ICELK_EARG;

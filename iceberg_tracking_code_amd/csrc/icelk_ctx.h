@@ -163,6 +163,18 @@ struct Ctx {
         hipStream_t fetch = nullptr;                           // D2H copies of finished scans (abi_jpeg_crop.hip: fetch_scan)
     } jpeg;
 
+    // ---- abi_plot.hip: the segment picture, allocated at first use.  A working set that belongs to plotting alone: the
+    // re-save's and the crop jobs' buffers are never touched, so crops and pictures can be asked for together.  Of `job`
+    // only d_rgb (what k_plot_resolve writes and the forward kernel reads), d_rcoef and enc are used
+    struct Plot {
+        JpegJob job;
+        uint8_t* d_bg = nullptr;        // Wo x Ho gray plane, padded to four pixels
+        uint32_t* d_counts = nullptr;   // lines | dots, each padded to four pixels
+        uint32_t* d_tables = nullptr;   // TL | TD
+        float* d_tracks = nullptr;      // the caller's tracks (icelk_plot_tracks)
+        size_t bg_cap = 0, counts_cap = 0, tracks_cap = 0;
+    } plot;
+
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
     float *d_p0 = nullptr, *d_p1 = nullptr, *d_p0r = nullptr, *d_err_f = nullptr, *d_err_b = nullptr, *d_dist = nullptr;
     uint8_t *d_st_f = nullptr, *d_st_b = nullptr, *d_valid = nullptr;
@@ -542,6 +554,8 @@ int jpeg_stage_file(Ctx* c, Ctx::JpegJob& B, const JpegIndex& X, size_t seg_byte
 bool jpeg_verdict_here(const Ctx::JpegJob& B);
 int jpeg_await_verdict(Ctx* c, Ctx::JpegJob& B);
 void jpeg_huff_stats_of(const Ctx::JpegJob& B, icelk_jpeg_huff_stats_t* st);
+// abi_plot.hip
+void plot_destroy(Ctx* c);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);
@@ -560,6 +574,7 @@ int detect_counts_arrived(Ctx* c, bool* arrived);
 // abi_segments.hip
 int flush_deferred(Ctx* c);
 int flush_deferred_slot(Ctx* c, int slot);
+int seg_gather_packed(Ctx* c, bool closed, int* out_n, int* out_vertices);
 // abi_post.hip
 int check_projection_args(Ctx* c, const icelk_camera_t* cam, const icelk_utm_filter_t* filt);
 int project_core(Ctx* c, const float* d_tracks_in, int n, int nv, const icelk_camera_t* cam, const icelk_utm_filter_t* filt,

@@ -8,6 +8,7 @@
 #include "../../include/icelk.h"
 #include "jpeg_enc.h"
 #include "jpeg_lanes.h"
+#include "plot_raster.h"
 
 namespace icelk {
 
@@ -71,6 +72,10 @@ enum KernelId {
     K_JPEG_ENC_STUFF_BUDGET,
     K_JPEG_CROP_RGB,           // the crop box of the decoded planes as R G B into the job
     K_JPEG_CROP_VERDICT,
+    K_PLOT_BACKGROUND,         // the segment picture (k_plot.hip): area-averaged gray plane
+    K_PLOT_CLEAR,              // ... the count planes zeroed
+    K_PLOT_SCATTER,            // ... lines and dots counted
+    K_PLOT_RESOLVE,            // ... counts, background, tables and stamp -> R G B
     K_COUNT_
 };
 
@@ -244,6 +249,15 @@ __device__ __forceinline__ void jpeg_huff_verdict_words(const uint32_t* __restri
     out[JV_IN_STEP] = ctl[JH_IN_STEP];
     out[JV_SPANS] = ctl[JH_SPANS];
 }
+
+// The segment picture (k_plot.hip; the arithmetic is plot_raster.h).  All pointers are device memory.  bg (bytes) and the
+// two count planes (words) are padded to a multiple of four pixels; counts = lines | dots, `words` in all; tables = TL | TD,
+// plot::kTable words each; rgb: rows 3 Wo bytes apart.  tracks: (n, nv, 2) float32.
+void launch_plot_background(hipStream_t s, const Level& src, int Wo, int Ho, uint8_t* bg);
+void launch_plot_clear(hipStream_t s, uint32_t* counts, size_t words);
+void launch_plot_scatter(hipStream_t s, const float* tracks, int n, int nv, int W, int H, int Wo, int Ho, uint32_t* lines, uint32_t* dots);
+void launch_plot_resolve(hipStream_t s, const uint8_t* bg, const uint32_t* lines, const uint32_t* dots, const uint32_t* tables,
+                         const plot::Stamp& stamp, int Wo, int Ho, uint8_t* rgb);
 
 // LK.  p_in/p_out etc. are device pointers.  fb = fused forward+backward.
 struct LKBuffers {

@@ -25,6 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from .plot import PLOT_QUALITY, PLOT_WIDTH, plot_name, plot_stamp
 from .tracker import REF_FEATURE_PARAMS, REF_LK_PARAMS, SegmentTracker, npz_name, save_tracks, segment_time_ok
 
 
@@ -70,7 +71,8 @@ PIPELINE_SLOTS = 6
 def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startlist=(0,), crop=None, mask=None,
                          mask_polygon=None, feature_params=None, lk_params=None, decode_threads=4, decode_ahead=6,
                          gray_variant=4, device=0, on_segment=None, save=True, decoder="pil", huffman="host", pipeline=False,
-                         n_slots=PIPELINE_SLOTS, resave=None, save_crops=None):
+                         n_slots=PIPELINE_SLOTS, resave=None, save_crops=None, plots=None, plot_width=PLOT_WIDTH,
+                         plot_quality=PLOT_QUALITY):
     """Track one day's photos.  Returns [(npz path, tracks (n, T+1, 2) f32, trackquality (n, T) f32)] of the
     segments that pass the time-gap rule, in order.
 
@@ -98,6 +100,14 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                    comment carried over), entropy-coded on the device (csrc/k_jpeg_enc.hip) right after the upload and
                    written on the calling thread once the photo's step is enqueued; once per photo, however many entries
                    of startlist visit it.  Not with pipeline=True.  The tracks do not change
+    plots          a directory (created) that receives, for every segment that passes the time-gap rule, the picture the
+                   reference draws of it (s1:397-434): the segment's last frame `plot_width` pixels wide, its tracks as red
+                   lines, their ends as red dots, '<last photo> <track_len * track_len_sec>/<track_len_sec>' in a corner --
+                   rasterised and coded on the device (`SegmentTracker.plot_closed`) as
+                   '<basename of the segment's last photo>_<track_len * track_len_sec>sec.jpg', the reference's name
+                   (s1:429) with .jpg for .png, at JPEG quality `plot_quality`.  With every decoder / huffman / pipeline /
+                   resave / save_crops combination; the returned list and the .npz files do not change.  None: nothing
+                   of it runs and nothing is allocated
     """
     if decoder not in ("pil", "device"):
         raise ValueError('decoder must be "pil" or "device"')
@@ -133,6 +143,8 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
         return _load(path, kind, save_crops is not None)
     if save_crops is not None:
         os.makedirs(save_crops, exist_ok=True)
+    if plots is not None:
+        os.makedirs(plots, exist_ok=True)
     written = set()                                       # photos whose crop has been written
     trk = None
     try:
@@ -195,6 +207,9 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                     npz = os.path.join(target_dir, npz_name(os.path.basename(seg_names[0]), track_len, track_len_sec))
                     if save:
                         save_tracks(npz, tracks, quality)
+                    if plots is not None:
+                        with open(plot_name(plots, seg_names[-1], track_len, track_len_sec), "wb") as f:
+                            f.write(trk.plot_closed(plot_width, plot_stamp(seg_names[-1], track_len, track_len_sec), plot_quality))
                     if on_segment is not None:
                         on_segment(npz, tracks, quality)
                     out.append((npz, tracks, quality))

@@ -14,6 +14,7 @@ import os
 import numpy as np
 
 from .context import Context, TERM_CRITERIA_COUNT, TERM_CRITERIA_EPS
+from .plot import PLOT_QUALITY, PLOT_WIDTH
 
 # parameter literals of the reference (s1:240-248, s0_1:37-45)
 REF_FEATURE_PARAMS = dict(maxCorners=50000000, qualityLevel=0.007, minDistance=10, blockSize=10)
@@ -102,6 +103,7 @@ class SegmentTracker:
         self._staged_for = None   # ... the detection frame it belongs to
         self._staged_n = 0
         self.pairs_launched = 0   # frame pairs handed to the tracker kernels so far (a joint launch carries two)
+        self._closed_now = False  # the latest step closed a segment: `plot_closed` may draw it on that step's frame
 
     # -- frame sources --------------------------------------------------------------------------
     def _next_slot(self):
@@ -268,6 +270,7 @@ class SegmentTracker:
         ONE tracker launch and step d+1 has no pair left to launch.  Results are those of the serial order in every
         case."""
         out = None
+        self._closed_now = False
         prev = self.cur
         T = self.track_len
         c = self.counter
@@ -378,9 +381,18 @@ class SegmentTracker:
             if self._prep_upto <= self._begun_upto and 1 <= d - c <= self.prepare_ahead and slot_of.get(d - c) is not None:
                 self.ctx.seg_detect_prepare(slot_of[d - c], self.use_mask, bs)
                 self._prep_upto = d
+        self._closed_now = detect and c > 0
         self.cur = slot
         self.counter += 1
         return out
+
+    def plot_closed(self, width=PLOT_WIDTH, stamp="", quality=PLOT_QUALITY):
+        """The picture of the segment the latest push closed (the one it returned), drawn on the frame of that push -- the
+        segment's last frame -- as the bytes of a JPEG file: `Context.seg_plot(self.cur, closed=True, ...)`, the tracks
+        gathered on the device.  RuntimeError when the latest push closed no segment."""
+        if not self._closed_now:
+            raise RuntimeError("no segment has been closed by the latest push")
+        return self.ctx.seg_plot(self.cur, True, width, stamp, quality)
 
     def flush(self):
         """Nothing of a pushed frame is held back across steps any more; kept so that callers can mark the end of a

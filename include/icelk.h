@@ -627,6 +627,45 @@ int icelk_jpeg_crop_finish(icelk_t* h, int ticket, const uint8_t* comment, uint6
 /* Waits for what the job has enqueued and drops the ticket. */
 int icelk_jpeg_crop_cancel(icelk_t* h, int ticket);
 
+/* ---- the picture of a segment (opt-in) -----------------------------------------------------------
+ * At every segment it saves the reference draws a picture (s1:397-434, plot_switch = 1): the segment's last gray frame,
+ * 1200 pixels wide, every surviving track as a red line of alpha 0.4, its end point as a red dot of alpha 0.6, the frame's
+ * time in a corner.  Here the same content is rasterised on the device, where frame and tracks already are, and written as
+ * a baseline JPEG file by the writer of the sections above.  The pixels are this library's, not matplotlib's; the rules
+ * are csrc/plot_raster.h (DESIGN.md 7.6 states them and lists the differences), integer arithmetic that the device, the
+ * host statement below and tests/plot_restatement.py compute byte for byte alike:
+ *   size        Wo = min(out_width, w), Ho = max(1, (2 Wo h + w) / (2 w)); out_width < 8 is ICELK_EARG
+ *   background  the exact area average of the gray frame, R = G = B
+ *   tracks      (n, vertices, 2) float32 in frame pixels, pixel centres at integers; vertices 1 .. 17, n <= 2^24; one
+ *               pixel wide lines without antialiasing, a 5-pixel plus sign at the last vertex; a track with a vertex that
+ *               is not finite or has |x| or |y| >= 2^20 is left out whole; n == 0 gives the bare frame
+ *   stamp       NULL or up to 48 characters of 0-9 - : . / and space (else ICELK_EARG), a 5 x 7 bitmap font, opaque
+ *   file        what Image.fromarray(rgb).save(f, "JPEG", quality=quality) writes for that R G B; quality 1 .. 100 */
+/* Host only, no handle, re-entrant: the size of the picture of a w x h frame. */
+int icelk_plot_size(int w, int h_, int out_width, int* ow, int* oh);
+/* Host only: the 7 rows of the glyph of character ch, top first, bit 4 = the leftmost of its 5 pixels; ICELK_EARG for a
+ * character without a glyph. */
+int icelk_plot_glyph(int ch, uint8_t* rows);
+/* Host only, no handle, re-entrant: the picture's R G B (Wo x Ho, interleaved, rgb_stride bytes per row) of the gray frame
+ * at gray (stride bytes per row), by the code the device runs, on the CPU. */
+int icelk_plot_overlay_host(const uint8_t* gray, int w, int h_, int stride, const float* tracks, int n, int vertices, int out_width,
+                            const char* stamp, uint8_t* rgb, int rgb_stride);
+/* The picture of the frame `slot` holds (ICELK_ESTATE when it holds none) with the tracks at `tracks` (host), as a file.
+ * Four kernels (csrc/k_plot.hip), the re-save's forward kernel and the entropy coder run on the handle's compute stream,
+ * on a working set that belongs to plotting alone -- the "most recent re-save" of icelk_jpeg_resave_encode and the crop
+ * jobs are untouched; it is allocated at first use (at 1200 x 800: 1 MB gray, 7.7 MB counts, 2.9 MB R G B, 2.9 MB
+ * coefficients and the coder's buffers) and freed with the handle.  The call waits for the device.  Arguments are checked
+ * before anything is enqueued; after an error nothing has been written.  ICELK_ECAP: `file` is too small (or NULL), *len
+ * says what the file takes and the call can be repeated.  rgb_or_null: receives the R G B the writer was given (tests). */
+int icelk_plot_tracks(icelk_t* h, int slot, const float* tracks, int n, int vertices, int out_width, const char* stamp, int quality,
+                      uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len);
+/* The same with the surviving tracks of the current segment (closed = 0) or of the segment the latest switch closed
+ * (closed = 1), gathered on the device as icelk_seg_archive / _closed gather them, into a buffer of the library's: no track
+ * data crosses PCIe.  A pair of that segment still waiting inside the library goes out first.  *out_n (may be NULL): the
+ * tracks drawn. */
+int icelk_seg_plot(icelk_t* h, int slot, int closed, int out_width, const char* stamp, int quality, uint8_t* rgb_or_null, int rgb_stride,
+                   uint8_t* file, uint64_t capacity, uint64_t* len, int* out_n);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
