@@ -23,6 +23,8 @@ from .calibration import CalibrationResult, ShorelineScene, calibrate, run_calib
 from .jpeg import (JpegCoefficients, UnsupportedJpeg, decode_jpeg, read_jpeg, read_jpeg_lanes, resave_coefficients,  # noqa: F401
                    resave_rgb, resave_tables, encode_jpeg, resave_bytes, source_comment)
 from .plot import plot_glyph, plot_name, plot_overlay_host, plot_size, plot_stamp  # noqa: F401
+from .velocity_map import (gist_rainbow_table, map_descriptor, map_glyph, map_layout, map_name, map_overlay_host, map_picture,  # noqa: F401
+                           map_strings, map_texts, map_view, scaled_arrows)
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

@@ -51,6 +51,29 @@ class JpegCropStats(C.Structure):
     _fields_ = [("huff", JpegHuffStats), ("route", C.c_uint32), ("blocks", C.c_uint32), ("budget", C.c_uint64), ("stream_len", C.c_uint64)]
 
 
+class MapPanel(C.Structure):
+    """icelk_map_panel_t"""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("bar_x0", C.c_int32), ("bar_w", C.c_int32),
+                ("xmin", C.c_double), ("xmax", C.c_double), ("ymin", C.c_double), ("ymax", C.c_double),
+                ("cells", C.c_void_p), ("measured", C.c_void_p), ("n_cells", C.c_int32), ("n_outline", C.c_int32),
+                ("outline", C.c_void_p), ("arrows", C.c_void_p), ("n_arrows", C.c_int32), ("resident", C.c_int32),
+                ("group", C.c_int32), ("pivot", C.c_int32), ("width", C.c_double), ("alpha", C.c_double), ("vmax", C.c_double),
+                ("cameras", C.c_void_p), ("n_cameras", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MapText(C.Structure):
+    """icelk_map_text_t"""
+    _fields_ = [("px", C.c_int32), ("py", C.c_int32), ("text", C.c_char * 56)]
+
+
+class MapDesc(C.Structure):
+    """icelk_map_desc_t"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_panels", C.c_int32), ("n_texts", C.c_int32), ("quality", C.c_int32),
+                ("reserved", C.c_int32), ("panel", MapPanel * 2), ("text", MapText * 16), ("table", C.c_void_p)]
+
+
+map_desc_p = C.POINTER(MapDesc)
+
 JPEG_CROP_ROUTES = ("device", "host-huffman", "over-budget")   # ICELK_JPEG_CROP_*
 JPEG_TABLE_BYTES = 11328
 JPEG_FALLBACK_NONE, JPEG_FALLBACK_BOUND, JPEG_FALLBACK_STREAM, JPEG_FALLBACK_SIZE = 0, 1, 2, 3
@@ -111,6 +134,11 @@ SIGNATURES = {
                                     C.POINTER(C.c_uint64)]),
     "icelk_seg_plot": (C.c_int, [handle_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, u8p, C.c_int, vp, C.c_uint64,
                                  C.POINTER(C.c_uint64), i32p]),
+    "icelk_map_glyph": (C.c_int, [C.c_int, u8p]),
+    "icelk_map_overlay_host": (C.c_int, [map_desc_p, f64p, i32p, C.c_int, u8p, C.c_int]),
+    "icelk_map_arrows_set": (C.c_int, [handle_p, f64p, i32p, C.c_int]),
+    "icelk_map_arrows_release": (C.c_int, [handle_p]),
+    "icelk_map_draw": (C.c_int, [handle_p, map_desc_p, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

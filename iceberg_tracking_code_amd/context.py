@@ -10,6 +10,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, f32p, u8p
 from .plot import PLOT_QUALITY, PLOT_WIDTH, _stamp_arg, _tracks3, plot_size
+from .velocity_map import _resident_args, map_descriptor
 from .jpeg import (UnsupportedJpeg, _comment_args, _encode_call, _rgb3, _stats_dict, describe_jpeg, resave_coefficients,
                    resave_quality)
 
@@ -606,6 +607,35 @@ class Context:
         text = _stamp_arg(stamp)
         return self._plot_call(slot, width, want_rgb, lambda rgb, stride, out, cap, n: self._lib.icelk_seg_plot(
             self._h, int(slot), int(bool(closed)), int(width), text, int(quality), rgb, stride, out, cap, n, None), "icelk_seg_plot")
+
+    # -- the velocity map of a gridded window (s3:449-465) ---------------------------------------
+    def map_arrows_set(self, arrows, group=None):
+        """A day's arrows (n, 5) x, y, dx, dy, speed and, if given, the group (the window, say) of each, copied to the
+        device, where they stay until the next set, `map_arrows_release` or `close` (icelk_map_arrows_set): a panel with
+        resident=True draws them, all or one group."""
+        a, g, _, n = _resident_args(np.zeros((0, 5)) if arrows is None else arrows, group)
+        self._ck(self._lib.icelk_map_arrows_set(self._h, a.ctypes.data_as(_lib.f64p), None if g is None else g.ctypes.data_as(_lib.i32p), n))
+
+    def map_arrows_release(self):
+        self._ck(self._lib.icelk_map_arrows_release(self._h))
+
+    def map_draw(self, picture, want_rgb=False):
+        """The picture a dict of velocity_map describes (`velocity_map.map_picture` makes one of a window), as the bytes of a
+        JPEG file (icelk_map_draw; the rules are DESIGN.md 7.7).  Rasterised and coded on the device; the file is what
+        `Image.fromarray(rgb).save(f, "JPEG", quality=quality)` writes for the picture's R G B.  want_rgb: (bytes, that
+        R G B (height, width, 3) uint8), for tests.  IcelkError (code ICELK_ESTATE) when a panel draws the resident arrows
+        and none are set."""
+        d, keep = map_descriptor(picture)
+        rgb, rgb_ptr, stride = None, None, 0
+        if want_rgb:
+            rgb = np.empty((max(d.height, 1), max(d.width, 1), 3), np.uint8)
+            rgb_ptr, stride = _u8(rgb), rgb.strides[0]
+        guess = getattr(self, "_map_file_guess", 1 << 18)
+        data = _encode_call(lambda out, cap, n: self._lib.icelk_map_draw(self._h, C.byref(d), rgb_ptr, stride, out, cap, n), guess,
+                            "icelk_map_draw", self._h)
+        self._map_file_guess = max(1 << 16, len(data) + len(data) // 4)   # the next window's picture is about as large
+        del keep
+        return (data, rgb) if want_rgb else data
 
     # -- measurement ----------------------------------------------------------------------------
     def prof_enable(self, on=True):

@@ -13,6 +13,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "jpeg_enc_count", "jpeg_enc_scan", "jpeg_enc_pack", "jpeg_enc_ff", "jpeg_enc_stuff",
     "jpeg_enc_pack_budget", "jpeg_enc_ff_budget", "jpeg_enc_stuff_budget", "jpeg_crop_rgb", "jpeg_crop_verdict",
     "plot_background", "plot_clear", "plot_scatter", "plot_resolve",
+    "map_clear", "map_cells", "map_polyline", "map_arrows", "map_resolve",
 };
 
 std::string g_create_err;
@@ -169,6 +170,7 @@ static void destroy_ctx(Ctx* c)
     jpeg_resave_destroy(c);
     jpeg_enc_destroy(c);
     plot_destroy(c);
+    map_destroy(c);
     prof_drain(c);
     for (auto& e : c->evt_pool) {
         hipEventDestroy(e.a);

@@ -175,6 +175,23 @@ struct Ctx {
         size_t bg_cap = 0, counts_cap = 0, tracks_cap = 0;
     } plot;
 
+    // ---- abi_map.hip: the velocity map, allocated at first use.  A working set of its own, as the segment picture's: of
+    // `job` only d_rgb (what k_map_resolve writes and the forward kernel reads), d_rcoef and enc are used.  The day's arrows
+    // of icelk_map_arrows_set stay resident until release / destroy
+    struct Map {
+        JpegJob job;
+        uint32_t* d_planes = nullptr;   // base | top | count, each padded to four pixels
+        double* d_items = nullptr;      // per call: cells, outline and the caller's arrows of every panel
+        uint8_t* d_measured = nullptr;
+        map::Scene* d_scene = nullptr;
+        map::Scene* h_scene = nullptr;  // what the copy into d_scene reads: lives as long as the handle
+        size_t planes_cap = 0, items_cap = 0, measured_cap = 0;
+        double* d_arrows = nullptr;     // resident: (n, 5)
+        int32_t* d_group = nullptr;     // resident: NULL or n
+        int n_arrows = 0;
+        bool have_arrows = false;
+    } map;
+
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
     float *d_p0 = nullptr, *d_p1 = nullptr, *d_p0r = nullptr, *d_err_f = nullptr, *d_err_b = nullptr, *d_dist = nullptr;
     uint8_t *d_st_f = nullptr, *d_st_b = nullptr, *d_valid = nullptr;
@@ -556,6 +573,8 @@ int jpeg_await_verdict(Ctx* c, Ctx::JpegJob& B);
 void jpeg_huff_stats_of(const Ctx::JpegJob& B, icelk_jpeg_huff_stats_t* st);
 // abi_plot.hip
 void plot_destroy(Ctx* c);
+// abi_map.hip
+void map_destroy(Ctx* c);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

@@ -9,6 +9,7 @@
 #include "jpeg_enc.h"
 #include "jpeg_lanes.h"
 #include "plot_raster.h"
+#include "map_raster.h"
 
 namespace icelk {
 
@@ -76,6 +77,11 @@ enum KernelId {
     K_PLOT_CLEAR,              // ... the count planes zeroed
     K_PLOT_SCATTER,            // ... lines and dots counted
     K_PLOT_RESOLVE,            // ... counts, background, tables and stamp -> R G B
+    K_MAP_CLEAR,               // the velocity map (k_map.hip): the three planes zeroed
+    K_MAP_CELLS,               // ... unmeasured cells filled, cell edges
+    K_MAP_POLYLINE,            // ... the outline
+    K_MAP_ARROWS,              // ... shafts and heads: top index and hit count
+    K_MAP_RESOLVE,             // ... planes, cameras, bars and texts -> R G B
     K_COUNT_
 };
 
@@ -258,6 +264,16 @@ void launch_plot_clear(hipStream_t s, uint32_t* counts, size_t words);
 void launch_plot_scatter(hipStream_t s, const float* tracks, int n, int nv, int W, int H, int Wo, int Ho, uint32_t* lines, uint32_t* dots);
 void launch_plot_resolve(hipStream_t s, const uint8_t* bg, const uint32_t* lines, const uint32_t* dots, const uint32_t* tables,
                          const plot::Stamp& stamp, int Wo, int Ho, uint8_t* rgb);
+
+// k_map.hip: the velocity map.  planes: base | top | count, each padded to four pixels; cells (n, 3), xy (n, 2), arrows
+// (n, 5) float64 on the device; group: NULL or one int32 per arrow; d_scene: a map::Scene in device memory
+void launch_map_clear(hipStream_t s, uint32_t* planes, size_t words);
+void launch_map_cells(hipStream_t s, const map::View& V, const double* cells, const uint8_t* measured, int n, int Wo, uint32_t* base);
+void launch_map_polyline(hipStream_t s, const map::View& V, const double* xy, int n, int Wo, uint32_t* base);
+void launch_map_arrows(hipStream_t s, const map::View& V, int w, bool pivot_mid, const double* arrows, const int32_t* group, int want, int n,
+                       int Wo, uint32_t* top, uint32_t* count);
+void launch_map_resolve(hipStream_t s, const map::Scene* d_scene, int Wo, int Ho, const uint32_t* base, const uint32_t* top,
+                        const uint32_t* count, uint8_t* rgb);
 
 // LK.  p_in/p_out etc. are device pointers.  fb = fused forward+backward.
 struct LKBuffers {

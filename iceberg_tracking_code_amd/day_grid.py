@@ -23,7 +23,11 @@ What the reference does, and this module reproduces:
 - names: '%Y%m%d_%H%M-%H%M_{time_diff}min_{grid_size}m.npz' with time_diff = int(minutes); the full day is named from
   the first / last selected time (+ drift) rounded to 30 minutes (trm.round_time).
 Times are taken as float64: s2 writes int64 epoch seconds, which float64 holds exactly.
-Not built: plots (plot_switch 1, 2), the xlsx readers (pass the rows pd.read_excel gives), s3:main's process pool.
+With `plots=directory` every window that writes an `.npz` also writes its map (plot_switch 1 and 2, s3:449-465), drawn on
+the device as a JPEG file (velocity_map.py); with plot_switch 2 the day's selected vectors are uploaded once
+and each window's picture draws its group of them.
+Not built: the inset photographs and the movie of the plots, the xlsx readers (pass the rows pd.read_excel gives),
+s3:main's process pool.
 """
 import ctypes as C
 import datetime as dt
@@ -36,6 +40,7 @@ import numpy as np
 from . import _lib
 from .context import Context
 from .gridding import cell_table, create_grid_across_fjord, pack_cells
+from .velocity_map import MAP_QUALITY, MAP_WIDTH, map_name, map_picture, map_strings
 
 EPOCH = dt.datetime(1970, 1, 1)
 HOUR_KEYS = ("x", "y", "u", "v", "speed", "time")
@@ -172,27 +177,70 @@ def plan_day(camnames, source_path_head, source_path_tail, schedule, clock_drift
     return DayPlan(day, time_window, grid_size, windows, cameras, files)
 
 
-def _load_hour_file(path):
-    """x, y, u, v, t of an hourly velocity file as float64, or None where the reference's `except: pass` would
-    skip the file."""
+def _load_hour_file(path, with_speed=False):
+    """x, y, u, v, t (and, asked for, speed) of an hourly velocity file as float64, or None where the reference's
+    `except: pass` would skip the file."""
     try:
         with np.load(path) as z:
             a = [np.asarray(z[k]) for k in HOUR_KEYS]
     except Exception:
         return None
-    x, y, u, v, _, t = (np.ascontiguousarray(q, dtype=np.float64).ravel() for q in a)
+    x, y, u, v, speed, t = (np.ascontiguousarray(q, dtype=np.float64).ravel() for q in a)
     if not len(x) == len(y) == len(u) == len(v) == len(t):
         return None
+    if with_speed:
+        return (x, y, u, v, t, speed) if len(speed) == len(x) else None
     return x, y, u, v, t
 
 
-def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None):
+def tracking_interval(workspace, day_str):
+    """The camera's tracking interval in seconds, from the name of its first file of the day (s3:318,340)."""
+    npzs = sorted(glob.glob(os.path.join(workspace, day_str + "*utm.npz")))
+    return float(os.path.basename(npzs[0]).split("_")[2].split("s")[0])
+
+
+def window_of_points(t, off, fcam, lo, hi, wf0, wf1):
+    """The window of every point of the concatenated hour files, -1 for none, by the rule of the device pass
+    (k_grid_day_assign): the last window of the point's camera that starts at or before its time, if the window loads the
+    point's file and ends after the time."""
+    group = np.full(len(t), -1, np.int32)
+    for f in range(len(off) - 1):
+        a, b, c = int(off[f]), int(off[f + 1]), int(fcam[f])
+        if b == a:
+            continue
+        tp = t[a:b]
+        w = np.searchsorted(lo[c].astype(np.float64), tp, side="right") - 1
+        wc = np.maximum(w, 0)
+        ok = (w >= 0) & (wf0[c][wc] <= f) & (f <= wf1[c][wc]) & (tp < hi[c][wc].astype(np.float64))
+        group[a:b] = np.where(ok, w, -1)
+    return group
+
+
+def camera_positions(camnames, cameras, day):
+    """[(easting, northing)] of the cameras with exactly one row for the day, in camnames order, and the position the
+    'Camera(s)' label goes beside (the first name's, s3:538-559), or None."""
+    d = int(day.strftime("%Y%m%d"))
+    rows = _records(cameras) if cameras is not None else []
+    out, label = [], None
+    for name in camnames:
+        match = [r for r in rows if r["camera"] == name and r["start_day"] <= d and r["end_day"] >= d and "easting" in r and "northing" in r]
+        if len(match) == 1:
+            out.append((float(match[0]["easting"]), float(match[0]["northing"])))
+            if name == camnames[0]:
+                label = out[-1]
+    return out, label
+
+
+def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, maps=None):
     """Loads the plan's files, runs the device pass, and packs every window that selected a point.  `timing`: a dict
-    that receives the seconds of each stage and the kernels' milliseconds (tools/grid_day_bench.py)."""
+    that receives the seconds of each stage and the kernels' milliseconds (tools/grid_day_bench.py).  `maps`: None, or
+    what the windows' pictures need (utm_to_gridded_utm's plot keywords); the written list then carries each picture's
+    name and bytes as a third and fourth entry."""
     clock = time.perf_counter
     t0 = clock()
-    empty = (np.zeros(0),) * 5
-    parts = [_load_hour_file(f["path"]) or empty for f in plan.files]        # an unreadable file holds no point
+    vectors = maps is not None and maps["plot_switch"] == 2
+    empty = (np.zeros(0),) * (6 if vectors else 5)
+    parts = [_load_hour_file(f["path"], vectors) or empty for f in plan.files]        # an unreadable file holds no point
     n = sum(len(p[0]) for p in parts)
     if n == 0:
         return []
@@ -222,6 +270,17 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None):
         f64(mu), f64(mv), f64(sp), i32(sel), f64(tmin), f64(tmax), C.byref(device_ms) if timing is not None else None))
     t2 = clock()
     sel, tmin, tmax = sel.reshape(nw, ncam), tmin.reshape(nw, ncam), tmax.reshape(nw, ncam)
+    if maps is not None:
+        day_str = plan.day.strftime("%Y%m%d")
+        names = [c["name"] for c in plan.cameras]
+        positions, label = camera_positions(names, maps["cameras"], plan.day)
+        if vectors:            # the day's vectors go to the device once; every window's picture draws its group
+            speed = np.concatenate([p[5] for p in parts])
+            seconds = np.zeros(n)
+            for f, c in enumerate(fcam):
+                if off[f + 1] > off[f]:
+                    seconds[off[f]:off[f + 1]] = tracking_interval(plan.cameras[c]["workspace"], day_str)
+            ctx.map_arrows_set(np.column_stack([x, y, u * seconds, v * seconds, speed]), window_of_points(t, off, fcam, lo, hi, wf0, wf1))
     written = []
     for w in range(nw):
         if not sel[w].any():
@@ -232,7 +291,20 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None):
         arrays = {k: np.asanyarray(r[k]) for k in SAVED_KEYS}        # what np.savez makes of s3's lists
         name = plan.name(w, [float(a) if k else None for a, k in zip(tmin[w], sel[w])],
                          [float(a) if k else None for a, k in zip(tmax[w], sel[w])])
-        written.append((name, arrays))
+        if maps is None:
+            written.append((name, arrays))
+            continue
+        lo_t = [EPOCH + dt.timedelta(seconds=float(a)) + dt.timedelta(seconds=cam["correction"]) for a, k, cam in zip(tmin[w], sel[w], plan.cameras) if k]
+        hi_t = [EPOCH + dt.timedelta(seconds=float(a)) + dt.timedelta(seconds=cam["correction"]) for a, k, cam in zip(tmax[w], sel[w], plan.cameras) if k]
+        when = dict(time_window=plan.time_window, min_time=round_half_hour(min(lo_t)), max_time=round_half_hour(max(hi_t)))
+        start, end = plan.windows[w]
+        strings = map_strings(plan.day, start, end, [nm for nm, k in zip(names, sel[w]) if k], grid_size, **when)
+        picture = map_picture(fjord, grid_size, r["measured"], r["not_measured"], r["x"], r["y"], r["u"], r["v"], r["speed"], strings,
+                              cameras=positions, label=label, n_camnames=len(names), plot_switch=maps["plot_switch"], group=w,
+                              speedthreshold_cbar=maps["speedthreshold_cbar"], out_width=maps["out_width"], quality=maps["quality"])
+        written.append((name, arrays, map_name(maps["dir"], start, end, **when), ctx.map_draw(picture)))
+    if vectors:
+        ctx.map_arrows_release()
     if timing is not None:
         timing.update(points=n, load_s=t1 - t0, device_call_s=t2 - t1, kernels_ms=device_ms.value,
                       pack_s=clock() - t2)
@@ -240,7 +312,8 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None):
 
 
 def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts, fjord, day,
-                       time_window, grid_size, observation_threshold, ctx=None, save=True):
+                       time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None, plot_switch=1,
+                       speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY):
     """One day of hourly velocity files -> one gridded .npz per time window, as s3_utm_to_gridded_utm.utm_to_gridded_utm
     (s3:222-446) with plot_switch 0.
 
@@ -248,7 +321,16 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
     `clock_drifts`: the rows of the clock-drift workbook (cam, start_date, end_date, drift_start_sec, drift_pday_sec)
     -- each a list of dicts or anything with .to_dict('records'), e.g. what pd.read_excel returns.  `fjord`: dict or
     npz with 'x' and 'y'.  `day`: datetime.  Returns [(file name, dict of arrays)] in writing order; with `save` the
-    files are written to target_path with np.savez, keys and dtypes as the reference's."""
+    files are written to target_path with np.savez, keys and dtypes as the reference's.
+
+    `plots`: a directory; every window that writes an .npz also gets its map there (s3:449-465), '%Y%m%d_%H%M-%H%M.jpg',
+    drawn and coded on the device.  plot_switch 1: the gridded map; 2: the all-vectors panel beside it.
+    `cameras`: the parameter workbook's rows with camera, start_day, end_day, easting, northing (None: `schedule`, whose
+    rows may carry them); `speedthreshold_cbar`: the speed at the colour bar's end.  plots=None calls nothing of this."""
+    if plots is not None and plot_switch not in (1, 2):
+        raise ValueError("plot_switch must be 1 or 2")
+    maps = None if plots is None else dict(dir=str(plots), plot_switch=plot_switch, speedthreshold_cbar=speedthreshold_cbar,
+                                           cameras=schedule if cameras is None else cameras, out_width=out_width, quality=quality)
     plan = plan_day(camnames, source_path_head, source_path_tail, schedule, clock_drifts, day, time_window, grid_size)
     if not plan.files:
         return []
@@ -256,10 +338,16 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
     if own:
         ctx = Context(64, 64, n_slots=1, max_pts=1 << 18)
     try:
-        written = _grid_day(ctx, plan, fjord, grid_size, observation_threshold)
+        written = _grid_day(ctx, plan, fjord, grid_size, observation_threshold, maps=maps)
     finally:
         if own:
             ctx.close()
+    if maps is not None:
+        os.makedirs(maps["dir"], exist_ok=True)
+        for _, _, path, data in written:
+            with open(path, "wb") as f:
+                f.write(data)
+        written = [(name, arrays) for name, arrays, _, _ in written]
     if save:
         for name, arrays in written:
             np.savez(os.path.join(target_path, name), **arrays)
@@ -267,8 +355,10 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
 
 
 def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts,
-                            fjord, time_window, grid_size, observation_threshold, ctx=None, save=True):
-    """s3:main's loop over days (without its process pool), on one context: the files of every day, in order."""
+                            fjord, time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None,
+                            plot_switch=1, speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY):
+    """s3:main's loop over days (without its process pool), on one context: the files of every day, in order.  The plot
+    keywords are utm_to_gridded_utm's."""
     own = ctx is None
     if own:
         ctx = Context(64, 64, n_slots=1, max_pts=1 << 18)
@@ -277,7 +367,9 @@ def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, 
         for day in days:
             out += utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path, schedule,
                                       clock_drifts, fjord, day, time_window, grid_size, observation_threshold,
-                                      ctx=ctx, save=save)
+                                      ctx=ctx, save=save, plots=plots, plot_switch=plot_switch,
+                                      speedthreshold_cbar=speedthreshold_cbar, cameras=cameras, out_width=out_width,
+                                      quality=quality)
         return out
     finally:
         if own:

@@ -6,7 +6,7 @@ squares and the packing of the result arrays the reference hands to np.savez (s3
 
 The day driver around the loop -- schedule, time windows, clock drift, selection from the hourly files, every window
 of a day binned in one device pass (`icelk_grid_bin_windows`) -- is day_grid.utm_to_gridded_utm; `pack_cells` and
-`cell_table` here serve both.  Out of scope: plotting.
+`cell_table` here serve both.  The map of a window is velocity_map.py.
 """
 import ctypes as C
 import math

@@ -666,6 +666,82 @@ int icelk_plot_tracks(icelk_t* h, int slot, const float* tracks, int n, int vert
 int icelk_seg_plot(icelk_t* h, int slot, int closed, int out_width, const char* stamp, int quality, uint8_t* rgb_or_null, int rgb_stride,
                    uint8_t* file, uint64_t capacity, uint64_t* len, int* out_n);
 
+/* ---- the velocity map of a gridded window (opt-in) ----------------------------------------------
+ * For every time window the reference draws a map of the fjord (s3:449-465, plot_switch 1: plot_velocities_one_map,
+ * s3:471-641; plot_switch 2: plot_velocities_two_maps, s3:644-844): the grid with its unmeasured cells filled, one arrow
+ * per measured cell coloured by speed, with switch 2 a second panel with every velocity vector of the window, the fjord's
+ * outline, the cameras, four strings and a colour bar.  Here the same content is rasterised on the device and written as a
+ * baseline JPEG file.  The pixels are this library's, not matplotlib's; the rules are csrc/map_raster.h (DESIGN.md 7.7
+ * states them and lists the differences), which the device, the host statement below and tests/map_restatement.py compute
+ * byte for byte alike:
+ *   picture     width 64 .. 16384, height 1 .. 16384 (else ICELK_EARG); one or two panels, each a rectangle of the picture
+ *               (the view) with world limits and, beside it, a colour bar; everything a panel draws is clipped to its view
+ *   cells       (n, 3) float64 left, top, size and one byte each: measured or not.  Unmeasured cells are filled light gray;
+ *               every cell's four sides are dark gray lines
+ *   outline     (n, 2) float64, a black polyline
+ *   arrows      (n, 5) float64 x, y, dx, dy, speed in world units (dy points north): a shaft of the panel's width and a
+ *               triangular head, pivot at the tail or the middle, coloured table[min(255, floor(speed / vmax * 256))]; where
+ *               arrows overlap the highest index gives the colour and the opacity is 1 - (1 - alpha)^min(hits, 31); an arrow
+ *               with a coordinate that is not finite or beyond 2^20 pixels, or a speed that is negative or not finite, is
+ *               left out; n <= 2^27.  resident != 0: the arrows of icelk_map_arrows_set instead (arrows is ignored); with
+ *               group >= 0 only those whose group is `group`
+ *   cameras     (n, 2) float64, n <= 8: opaque red discs
+ *   texts       at most 16 items of at most 48 characters of 0-9 - : . / space A-Z a-z , ( ) (else ICELK_EARG); a 5 x 7
+ *               bitmap font, lower case drawn as capitals, opaque black, (px, py) the top-left corner in the picture
+ *   file        what Image.fromarray(rgb).save(f, "JPEG", quality=quality) writes for that R G B; quality 1 .. 100 */
+typedef struct {
+    int32_t x0, y0, w, h;          /* the view: inside the picture, w, h >= 1 */
+    int32_t bar_x0, bar_w;         /* the colour bar: columns [bar_x0, bar_x0 + bar_w) of the view's rows; bar_w 0: none */
+    double xmin, xmax, ymin, ymax; /* world limits, xmin < xmax, ymin < ymax */
+    const double* cells;
+    const uint8_t* measured;
+    int32_t n_cells;
+    int32_t n_outline;
+    const double* outline;
+    const double* arrows;
+    int32_t n_arrows;
+    int32_t resident;
+    int32_t group;
+    int32_t pivot;                 /* 0: the tail, 1: the middle */
+    double width;                  /* of the shaft in world units, finite, > 0 */
+    double alpha;                  /* 0 < alpha <= 1 */
+    double vmax;                   /* the speed of the colour table's end, finite, > 0 */
+    const double* cameras;
+    int32_t n_cameras;
+    int32_t reserved;
+} icelk_map_panel_t;
+typedef struct {
+    int32_t px, py;                /* |px|, |py| <= 2^20 */
+    char text[56];                 /* NUL-terminated */
+} icelk_map_text_t;
+typedef struct {
+    int32_t width, height, n_panels, n_texts, quality, reserved;
+    icelk_map_panel_t panel[2];
+    icelk_map_text_t text[16];
+    const uint8_t* table;          /* 256 x 3 bytes R G B */
+} icelk_map_desc_t;
+/* Host only: the 7 rows of the glyph of character ch in a map's texts, as icelk_plot_glyph gives a stamp's. */
+int icelk_map_glyph(int ch, uint8_t* rows);
+/* Host only, no handle, re-entrant: the picture's R G B (width x height, interleaved, rgb_stride bytes per row) by the code
+ * the device runs, on the CPU.  resident (n_resident, 5) and group (NULL or n_resident) stand for what
+ * icelk_map_arrows_set holds; a panel with resident != 0 while resident is NULL is ICELK_ESTATE. */
+int icelk_map_overlay_host(const icelk_map_desc_t* d, const double* resident, const int32_t* group, int n_resident, uint8_t* rgb,
+                           int rgb_stride);
+/* A day's arrows (n, 5) and, if not NULL, the group (the window, say) of each, copied to the device, where they stay until
+ * the next set, icelk_map_arrows_release or icelk_destroy: every picture of the day draws from the one upload.  n <= 2^27. */
+int icelk_map_arrows_set(icelk_t* h, const double* arrows, const int32_t* group_or_null, int n);
+int icelk_map_arrows_release(icelk_t* h);
+/* The picture d describes, as a file.  k_map_clear, k_map_cells, k_map_polyline, k_map_arrows and k_map_resolve
+ * (csrc/k_map.hip), then the re-save's forward kernel and the entropy coder run on the handle's compute stream, on a
+ * working set that belongs to the map alone -- the segment picture, the "most recent re-save" of icelk_jpeg_resave_encode
+ * and the crop jobs are untouched; it is allocated at first use (at 1400 x 1000: 16.8 MB planes, 4.2 MB R G B, 4.2 MB
+ * coefficients, the call's items and the coder's buffers) and freed with the handle.  The call waits for the device.
+ * Every argument is checked before anything is enqueued or allocated; after an error nothing has been written.
+ * ICELK_ESTATE: a panel asks for resident arrows and none are set.  ICELK_ECAP: `file` is too small (or NULL), *len says
+ * what the file takes and the call can be repeated.  rgb_or_null: receives the R G B the writer was given (tests). */
+int icelk_map_draw(icelk_t* h, const icelk_map_desc_t* d, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
+                   uint64_t* len);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
