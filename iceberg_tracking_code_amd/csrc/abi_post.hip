@@ -1,6 +1,7 @@
 // abi_post.hip -- after the frame loop: projection, point-in-polygon, gridding (one set / a day of windows),
 // the velocity cube and its averages.
 #include "icelk_ctx.h"
+#include "cube_means.h"
 
 namespace icelk {
 
@@ -398,8 +399,9 @@ int icelk_cube_average(icelk_t* h, const int* sel_offset, const int* sel_index, 
     for (int k = 0; k < nsel; k++)
         if (sel_index[k] < 0 || sel_index[k] >= c->post.cube_nt) FAIL(c, ICELK_EARG, "a selected window lies outside the cube");
     const int ncells = c->post.cube_ncells;
-    if ((long long)nperiods * ncells > 0x7fffffffLL || coarseness > 32767)
-        FAIL(c, ICELK_ECAP, "periods x cells does not fit 31 bits");
+    if ((long long)nperiods * ncells > 0x7fffffffLL) FAIL(c, ICELK_ECAP, "periods x cells does not fit 31 bits");
+    // numpy's order of additions changes with the length of a block's rows; beyond this it has not been checked
+    if (coarseness > kMaxCoarseness) FAIL(c, ICELK_ECAP, "coarseness above 8193: not checked against numpy");
     const int cr = (rows + coarseness - 1) / coarseness, cc = (cols + coarseness - 1) / coarseness;
     const size_t nfine = (size_t)nperiods * (size_t)ncells, nout = (size_t)nperiods * (size_t)cr * (size_t)cc;
     if (device_ms) *device_ms = 0.0;

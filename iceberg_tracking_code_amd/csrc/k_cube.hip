@@ -9,17 +9,26 @@
 // - u[:, :, mask] comes out of numpy's fancy indexing with the window axis SLOWEST in memory, so np.sum over that axis
 //   is the plain element-wise loop out += a[t]: per cell the windows are added one after the other, ascending, from
 //   0.0 -- no pairwise blocks.  NaN counts as +0.0 (and is still added), the mean is sum / (number of non-NaN terms),
-//   0.0 / 0 = NaN where a cell was never measured.
-// - np.mean(axis = (1, 3)) of the zero-padded (R/c, c, C/c, c) view: per coarse cell, from 0.0, one row of the block
-//   after the other, each row of c terms by numpy's pairwise routine (np_sums.h: sequential below 8 terms, 8
-//   accumulators from there); when a single coarse column is left the two block axes merge and the c * c terms are one
-//   pairwise run.  The divisor is c * c whatever the padding, NaN propagates.
+//   0.0 / 0 = NaN where a cell was never measured.  A cube of ONE cell is the exception: its selection is a
+//   contiguous run, which numpy adds as np.sum adds one (np_sums.h: np_sum).
+// - np.mean(axis = (1, 3)) of the zero-padded (R/c, c, C/c, c) view: cube_means.h, shared with the host test.
 #include "icelk_internal.h"
-#include "np_sums.h"
+#include "cube_means.h"
 
 namespace icelk {
 
 namespace {
+
+// NaN-replaced element t of a one-cell cube's selection
+struct SelectedAt {
+    const double* __restrict__ a;
+    const int* __restrict__ sel;
+    __device__ __forceinline__ double operator()(int t) const
+    {
+        const double x = a[sel[t]];
+        return x == x ? x : 0.0;
+    }
+};
 
 // one thread per (period, cell); a workgroup lies inside one period, so the window list is read with scalar loads
 // and a wave reads 512 contiguous bytes of every selected window
@@ -48,6 +57,11 @@ __global__ __launch_bounds__(256) void k_cube_temporal(const double* __restrict_
         nu += ua ? 1 : 0;
         nv += vb ? 1 : 0;
     }
+    if (ncells == 1) {   // numpy's order over a contiguous run; nu and nv stand
+        su = np_sum(SelectedAt{u, sel_index + k0}, k1 - k0);
+        sv = np_sum(SelectedAt{v, sel_index + k0}, k1 - k0);
+        sc = np_sum(SelectedAt{cnt, sel_index + k0}, k1 - k0);
+    }
     const double mu = su / (double)nu, mv = sv / (double)nv;
     const double sp = hypot_np(mu, mv);
     const size_t o = (size_t)p * (size_t)ncells + (size_t)cell;
@@ -56,40 +70,6 @@ __global__ __launch_bounds__(256) void k_cube_temporal(const double* __restrict_
     speed[o] = sp;
     count_sum[o] = sc;
     if (sp == sp) has_data[p] = 1;   // every writer stores the same value
-}
-
-// element b of block row r, columns from c0: the field inside, the zero padding outside
-struct RowAt {
-    const double* __restrict__ f;
-    int rows, cols, r, c0;
-    __device__ __forceinline__ double operator()(int b) const
-    {
-        const int col = c0 + b;
-        return r < rows && col < cols ? f[(size_t)r * cols + col] : 0.0;
-    }
-};
-
-// element t of a whole c x c block in row-major order (a single coarse column: numpy merges the two block axes)
-struct BlockAt {
-    const double* __restrict__ f;
-    int rows, cols, r0, c;
-    __device__ __forceinline__ double operator()(int t) const
-    {
-        const int r = r0 + t / c, col = t % c;
-        return r < rows && col < cols ? f[(size_t)r * cols + col] : 0.0;
-    }
-};
-
-__device__ double block_mean(const double* __restrict__ f, int rows, int cols, int c, int coarse_cols, int bi, int bj)
-{
-    double acc;
-    if (coarse_cols == 1) {
-        acc = 0.0 + np_pairwise_sum(BlockAt{f, rows, cols, bi * c, c}, c * c);
-    } else {
-        acc = 0.0;
-        for (int a = 0; a < c; a++) acc = acc + np_pairwise_sum(RowAt{f, rows, cols, bi * c + a, bj * c}, c);
-    }
-    return acc / (double)(c * c);
 }
 
 // one thread per (period, coarse cell): the three fields and the speed of the coarse u, v

@@ -9,8 +9,8 @@
 // reference forms them (left + i * spacing, top - j * spacing, + / - spacing), so points exactly on edges and corners
 // land where contains_points puts them (in one, two or no cell).  The (cell, point index) pairs are sorted (rocPRIM
 // radix sort, k_sort.hip), which restores the point order inside every cell, and one thread per cell adds its
-// velocities in numpy's pairwise order (blocks of 128, 8 accumulators, halves aligned to 8) -- float64, bit for bit
-// what np.sum gives -- and takes the hypot (glibc's algorithm, see k_utm.hip).
+// velocities in numpy's pairwise order (blocks of 128, 8 accumulators, halves aligned to 8; beyond 8192 terms in the
+// chunks of numpy's iterator buffer, np_sums.h) -- float64, bit for bit what np.sum gives -- and takes the hypot (glibc's algorithm, see k_utm.hip).
 #include "icelk_internal.h"
 #include "np_sums.h"
 
@@ -219,11 +219,11 @@ struct KeyedAt {
     __device__ __forceinline__ double operator()(int t) const { return a[(unsigned)keys[start + t]]; }
 };
 
-// numpy's pairwise sum over the velocities of keys[start, start + n)
-__device__ __forceinline__ double pairwise_sum(const unsigned long long* __restrict__ keys,
-                                               const double* __restrict__ a, int start, int n)
+// np.sum over the velocities of keys[start, start + n): pairwise, in the chunks of numpy's buffer beyond 8192 terms
+__device__ __forceinline__ double keyed_sum(const unsigned long long* __restrict__ keys,
+                                            const double* __restrict__ a, int start, int n)
 {
-    return np_pairwise_sum(KeyedAt{keys, a, start}, n);
+    return np_sum(KeyedAt{keys, a, start}, n);
 }
 
 __device__ __forceinline__ int lower_bound(const unsigned long long* __restrict__ keys, int n, unsigned long long v)
@@ -252,8 +252,8 @@ __global__ __launch_bounds__(64) void k_grid_reduce(const unsigned long long* __
     count[c] = n;
     double mu = 0.0, mv = 0.0, sp = 0.0;
     if (n > 0) {
-        mu = (0.0 + pairwise_sum(keys, u, b, n)) / (double)n;
-        mv = (0.0 + pairwise_sum(keys, v, b, n)) / (double)n;
+        mu = keyed_sum(keys, u, b, n) / (double)n;
+        mv = keyed_sum(keys, v, b, n) / (double)n;
         sp = hypot_np(mu, mv);
     }
     mean_u[c] = mu;

@@ -3,13 +3,23 @@
 // says what "element t" is with a functor `at(t)`; the order of the additions is numpy's and must not change:
 // np.sum over a contiguous run adds below 8 terms one after the other from 0.0, otherwise in 8 accumulators, in blocks
 // of at most 128 terms, the halves of a longer run aligned to 8 (numpy/core/src/umath/loops_utils.h.src).
+// Plain C++ for the host and the device alike: tests/np_sums_main.cpp runs this text on the CPU against numpy itself.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define ICELK_SUMS_FN __host__ __device__ inline
+#define ICELK_SUMS_INLINE_FN __host__ __device__ __forceinline__
+#else
+#include <math.h>
+#include <stddef.h>
+#define ICELK_SUMS_FN inline
+#define ICELK_SUMS_INLINE_FN inline
+#endif
 
 namespace icelk {
 
 template <typename At>
-__device__ __forceinline__ double np_leaf_sum(const At& at, int start, int n)
+ICELK_SUMS_INLINE_FN double np_leaf_sum(const At& at, int start, int n)
 {
     if (n < 8) {
         double r = 0.0;
@@ -29,15 +39,15 @@ __device__ __forceinline__ double np_leaf_sum(const At& at, int start, int n)
     return res;
 }
 
-// numpy's pairwise sum over at(0) .. at(n - 1), without recursion
+// numpy's pairwise sum over at(first) .. at(first + n - 1), without recursion
 template <typename At>
-__device__ double np_pairwise_sum(const At& at, int n)
+ICELK_SUMS_FN double np_pairwise_sum(const At& at, int n, int first = 0)
 {
     struct Frame { int start, n, stage; };
     Frame st[40];
     double vals[40];
     int fp = 0, sp = 0;
-    st[fp++] = Frame{0, n, 0};
+    st[fp++] = Frame{first, n, 0};
     while (fp) {
         Frame& f = st[fp - 1];
         if (f.n <= 128) {
@@ -63,8 +73,29 @@ __device__ double np_pairwise_sum(const At& at, int n)
     return vals[0];
 }
 
+// np.sum (np.add.reduce, np.mean's sum) over a contiguous run at(0) .. at(n - 1).  numpy's reduction runs through its
+// buffered iterator, so the pairwise routine never sees more than the buffer's 8192 elements at a time: from 0.0, one
+// chunk of at most 8192 consecutive terms after the other, each chunk pairwise.  Up to 8192 terms that is
+// 0.0 + np_pairwise_sum; beyond, one pairwise run over all n terms gives other bits (numpy 2.2).
+constexpr int kNpBufferSize = 8192;
+
+// acc + the terms at(0) .. at(n - 1) of one inner loop of a numpy reduction, chunk by chunk
+template <typename At>
+ICELK_SUMS_FN double np_sum_onto(double acc, const At& at, int n)
+{
+    for (int first = 0; first < n; first += kNpBufferSize)
+        acc = acc + np_pairwise_sum(at, n - first < kNpBufferSize ? n - first : kNpBufferSize, first);
+    return acc;
+}
+
+template <typename At>
+ICELK_SUMS_FN double np_sum(const At& at, int n)
+{
+    return np_sum_onto(0.0, at, n);
+}
+
 // np.hypot: glibc's algorithm (see k_utm.hip hypot_ref)
-__device__ __forceinline__ double hypot_np(double x, double y)
+ICELK_SUMS_INLINE_FN double hypot_np(double x, double y)
 {
     double ax = fabs(x), ay = fabs(y);
     if (isinf(ax) || isinf(ay)) return HUGE_VAL;

@@ -362,7 +362,8 @@ int icelk_cube_release(icelk_t* h);
  * out_u, out_v, out_count, and out_speed = np.hypot(out_u, out_v); out_has_data[p] = 1 iff some cell of the period's
  * uncoarsened fields has a non-NaN speed (the reference's "no data available" test).  device_ms (may be NULL):
  * HIP-event time of the kernels; uploads and read-backs excluded.  Arguments are checked before anything is issued;
- * ICELK_ESTATE without a cube, ICELK_ECAP when nperiods * ncells does not fit 31 bits or coarseness > 32767. */
+ * ICELK_ESTATE without a cube, ICELK_ECAP when nperiods * ncells does not fit 31 bits or coarseness > 8193 (the largest
+ * checked against numpy: the project answers as numpy does or refuses). */
 int icelk_cube_average(icelk_t* h, const int* sel_offset, const int* sel_index, int nperiods, int rows, int cols,
                        int coarseness, double* out_u, double* out_v, double* out_speed, double* out_count,
                        int* out_has_data, double* device_ms);

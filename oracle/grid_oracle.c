@@ -15,7 +15,8 @@
  * camera files and cannot be run here.  So (a) is pinned by the reference, (b) by the primitives it calls.
  *
  * Restated primitives: matplotlib's contains_points rule (see mask_oracle.c), numpy's pairwise summation
- * (numpy/core/src/umath/loops_utils.h.src: blocks of 128, 8 accumulators, halves aligned to 8) and glibc 2.35's
+ * (numpy/core/src/umath/loops_utils.h.src: blocks of 128, 8 accumulators, halves aligned to 8; np.sum hands it at
+ * most the 8192 elements of its iterator buffer at a time) and glibc 2.35's
  * generic hypot (see utm_oracle.c).
  */
 #include <math.h>
@@ -70,6 +71,15 @@ static double pairwise(const double* a, size_t n)
     return pairwise(a, n2) + pairwise(a + n2, n - n2);
 }
 
+/* np.sum over a contiguous run: numpy's reduction is buffered, the pairwise routine sees at most 8192 elements at a
+ * time -- from 0.0, chunk after chunk (numpy 2.2; one pairwise run over more than 8192 terms gives other bits) */
+static double np_sum(const double* a, size_t n)
+{
+    double acc = 0.0;
+    for (size_t s = 0; s < n; s += 8192) acc = acc + pairwise(a + s, n - s < 8192 ? n - s : 8192);
+    return acc;
+}
+
 static double hypot_glibc(double x, double y)
 {
     double ax = fabs(x), ay = fabs(y);
@@ -115,8 +125,8 @@ int orc_grid_bin(const double* x, const double* y, const double* u, const double
                 if (contains(poly, 4, x[p], y[p])) { bu[k] = u[p]; bv[k] = v[p]; k++; }
             count[c] = k;
             if (k > 0) {
-                mean_u[c] = (0.0 + pairwise(bu, (size_t)k)) / (double)k;
-                mean_v[c] = (0.0 + pairwise(bv, (size_t)k)) / (double)k;
+                mean_u[c] = np_sum(bu, (size_t)k) / (double)k;
+                mean_v[c] = np_sum(bv, (size_t)k) / (double)k;
                 speed[c] = hypot_glibc(mean_u[c], mean_v[c]);
             }
         }

@@ -4,6 +4,7 @@
   keys, dtypes, shapes and bits, for 30-minute, full-day and 1/7-hour windows;
 - a seeded day of ~2e6 velocities: every window equals the oracle's gridding of that window's points, selected here by
   a numpy restatement of the selection rule, bit for bit;
+- window edges, the file table and empty files against a numpy statement of the selection rule;
 - argument checks of the ABI, and days that write nothing."""
 import datetime as dt
 import os
@@ -155,6 +156,89 @@ def test_synthetic_day_equals_oracle(ctx, orc, tmp_path):
             assert a[key].tobytes() == w.tobytes(), (name, key)
     assert names == want_names and len(names) == 12
     assert peak > 50000
+
+
+# ---- window edges, the file table and empty files, against a numpy statement of the rule ---------------------------------
+
+def test_window_edges_and_empty_files(ctx):
+    """A point of file f, camera k, counts in window w of that camera iff w loads f (win_f0 <= f <= win_f1) and
+    (t >= t_lo) & (t < t_hi) on float64 -- k_grid.hip's header comment, stated here with numpy.  Times on and one ulp
+    below every bound, between integers, NaN, +-inf, before the first and after the last window; files that a window
+    of another time range loads; a window that loads nothing; empty files first, twice in the middle and last; two
+    cameras whose windows differ."""
+    ncam, nw, cols, rows = 2, 3, 4, 4
+    left, top, sp = 1000.0, 2000.0, 100.0
+    ncells = cols * rows
+    #            empty   .      empty  empty  .      .      .      empty
+    file_cam = np.array([0, 0, 0, 0, 0, 1, 1, 1], np.int32)
+    lo = np.array([[100, 200, 350], [110, 210, 400]], np.int64)
+    hi = np.array([[200, 300, 400], [210, 260, 500]], np.int64)
+    wf0 = np.array([[0, 1, 1], [5, 5, 6]], np.int32)
+    wf1 = np.array([[1, 4, 0], [5, 6, 7]], np.int32)             # camera 0's last window loads nothing (f0 > f1)
+    rng = np.random.default_rng(23)
+    t_parts, sizes = [], []
+    for f, k in enumerate(file_cam):
+        if f in (0, 2, 3, 7):
+            sizes.append(0)
+            continue
+        edges = np.concatenate([lo[k], hi[k]]).astype(np.float64)
+        special = np.concatenate([edges, np.nextafter(edges, -np.inf), np.nextafter(edges, np.inf),
+                                  [150.5, 255.25, 375.75, 450.5, np.nan, np.inf, -np.inf, 50.0, 99.0, 1000.0, -200.0, 0.0]])
+        t_parts.append(rng.permutation(special))
+        sizes.append(len(special))
+    t = np.concatenate(t_parts)
+    n = len(t)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    assert 60 < n < 200 and off[0] == off[1] == 0 and off[2] == off[3] == off[4] and off[7] == off[8] == n
+    cell = rng.integers(0, ncells, n)
+    x = left + sp * (cell // rows + rng.uniform(0.1, 0.9, n))
+    y = top - sp * (cell % rows + rng.uniform(0.1, 0.9, n))
+    u = rng.normal(0, 1, n) * 10.0 ** rng.integers(-4, 3, n)
+    v = rng.normal(0, 1, n) * 10.0 ** rng.integers(-4, 3, n)
+    on = np.ones(ncells, np.uint8)
+    cnt, sel = np.full(nw * ncells, -1, np.int32), np.full(nw * ncam, -1, np.int32)
+    mu, mv, spd = (np.full(nw * ncells, 7.0) for _ in range(3))
+    tmin, tmax = np.full(nw * ncam, 7.0), np.full(nw * ncam, 7.0)
+    p64 = lambda a: a.ctypes.data_as(_lib.f64p)    # noqa: E731
+    p32 = lambda a: a.ctypes.data_as(_lib.i32p)    # noqa: E731
+    pi64 = lambda a: a.ctypes.data_as(_lib.i64p)   # noqa: E731
+    rc = ctx._lib.icelk_grid_bin_windows(ctx._h, p64(x), p64(y), p64(u), p64(v), p64(t), n, pi64(off), p32(file_cam),
+                                         p32(wf0), p32(wf1), len(file_cam), pi64(lo), pi64(hi), ncam, nw, left, top, sp,
+                                         cols, rows, on.ctypes.data_as(_lib.u8p), p32(cnt), p64(mu), p64(mv), p64(spd),
+                                         p32(sel), p64(tmin), p64(tmax), None)
+    assert rc == _lib.OK
+    # the rule, with numpy
+    file_of = np.repeat(np.arange(len(file_cam)), sizes)
+    window_of = np.full(n, -1)
+    for k in range(ncam):
+        for w in range(nw):
+            with np.errstate(invalid="ignore"):
+                m = (file_cam[file_of] == k) & (file_of >= wf0[k, w]) & (file_of <= wf1[k, w]) & (t >= int(lo[k, w])) & (t < int(hi[k, w]))
+            assert (window_of[m] == -1).all()
+            window_of[m] = w
+            assert sel[w * ncam + k] == m.sum(), (k, w)
+            assert tmin[w * ncam + k] == (t[m].min() if m.any() else 0.0) and tmax[w * ncam + k] == (t[m].max() if m.any() else 0.0), (k, w)
+    # what the cases are there for
+    cam_of = file_cam[file_of]
+    assert (window_of[(cam_of == 0) & (t == 100.0) & (file_of == 1)] == 0).all()             # exactly t_lo: in
+    assert (window_of[(cam_of == 0) & (t == 200.0) & (file_of == 1)] == 1).all()             # exactly t_hi: the next one's
+    assert (window_of[(cam_of == 0) & (t == np.nextafter(200.0, 0)) & (file_of == 1)] == 0).all()
+    assert (window_of[(cam_of == 0) & (t == np.nextafter(100.0, 0))] == -1).all()
+    assert (window_of[(file_of == 4) & (t >= 100.0) & (t < 200.0)] == -1).all() and ((file_of == 4) & (t == 150.5)).any()
+    assert (window_of[(cam_of == 0) & (t >= 350.0) & (t < 400.0)] == -1).all()               # the window without files
+    assert (window_of[(cam_of == 1) & (t == 100.0)] == -1).all() and (window_of[(file_of == 6) & (t == 450.5)] == 2).all()
+    assert (window_of[~np.isfinite(t)] == -1).all() and 20 < (window_of >= 0).sum() < n - 20
+    want_cnt = np.zeros(nw * ncells, np.int32)
+    want_u, want_v = np.zeros(nw * ncells), np.zeros(nw * ncells)
+    for w in range(nw):
+        for c in range(ncells):
+            m = (window_of == w) & (cell == c)
+            if m.any():
+                want_cnt[w * ncells + c] = m.sum()
+                want_u[w * ncells + c], want_v[w * ncells + c] = np.sum(u[m]) / m.sum(), np.sum(v[m]) / m.sum()
+    assert np.array_equal(cnt, want_cnt) and cnt.max() >= 2
+    assert mu.tobytes() == want_u.tobytes() and mv.tobytes() == want_v.tobytes()
+    assert spd.tobytes() == np.hypot(want_u, want_v).tobytes()
 
 
 # ---- ABI checks and empty days --------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@
 - the chain utm_to_gridded_utm (golden day) -> combine_npzs -> averages equals the golden;
 - daily_averages: the __main__ loop, its csv files byte for byte;
 - a seeded season against numpy itself on the host (np.nanmean, np.nansum, spatial_mean restated below);
+- small cubes at the geometries where numpy changes its order of additions, and cubes of one and two cells;
 - the ABI's argument checks on a live handle.
 Equality is bit for bit on every non-NaN float64, NaN in the same places (G.same_floats); no tolerance anywhere."""
 import datetime as dt
@@ -209,6 +210,86 @@ def test_seeded_season_equals_numpy():
     assert {"no window", "no data", "data", "long", "short"} <= seen, seen
 
 
+# ---- the geometries at which numpy changes its order of additions --------------------------------------------------------
+
+# (rows, cols, c): one coarse column with three and five coarse rows, two coarse columns, one coarse row, the smallest
+# fields, the first c whose single-column block exceeds numpy's buffer of 8192 elements and larger ones, 128 (where
+# the halves of one pairwise run are the buffer's chunks), and rows of more than 128 terms with two coarse columns
+GEOMETRIES = [(23, 5, 8), (23, 5, 5), (23, 6, 5), (5, 23, 8), (1, 1, 2), (1, 40, 7), (40, 1, 7), (94, 90, 91),
+              (130, 100, 127), (150, 64, 128), (263, 17, 129), (300, 2, 300), (20, 260, 129)]
+
+
+def small_cube(rows, cols, nt, rng, hole_share=0.3, keep=None):
+    """A cube over seven decades with NaN holes.  count is not made of integers here: the device treats it as any
+    float64, and integers would add up to the same bits in any order.  keep: windows of which every cell keeps at
+    least one value, so that a coarse mean over them is a number and not the NaN a single empty cell makes of it."""
+    t0 = dt.datetime(2021, 5, 1)
+    time = np.array([postprocess.epoch_seconds(t0 + dt.timedelta(minutes=30 * k)) for k in range(nt)], np.float64)
+    shape = (rows, cols, nt)
+    u = rng.normal(0.1, 0.3, shape) * 10.0 ** rng.integers(-3, 2, shape)
+    v = rng.normal(-0.05, 0.2, shape) * 10.0 ** rng.integers(-3, 2, shape)
+    count = rng.uniform(0.5, 3000.0, shape) * 10.0 ** rng.integers(-3, 2, shape)
+    hole = rng.random(shape) < hole_share
+    if keep is not None:
+        empty = hole[:, :, keep].all(axis=2)
+        hole[:, :, keep[0]] &= ~empty
+    for a in (u, v, count):
+        a[hole] = np.nan
+    yy, xx = np.meshgrid(7000000.0 - 200.0 * np.arange(rows), 500000.0 + 200.0 * np.arange(cols), indexing="ij")
+    at = lambda k: t0 + dt.timedelta(minutes=30 * k)        # noqa: E731
+    return dict(x=xx, y=yy, u=u, v=v, count=count, time=time), at
+
+
+def check_periods_against_numpy(own, data, periods, coarseness, tag):
+    with VelocityCube(data, own) as cube:
+        got = average_periods(cube, periods, coarseness)
+    time = data["time"]
+    finite = 0
+    for r, (start, end) in zip(got, periods):
+        mask = (time >= postprocess.epoch_seconds(start)) & (time < postprocess.epoch_seconds(end))
+        assert mask.any()
+        um, vm, cs = numpy_averages(data, mask)
+        with np.errstate(all="ignore"):
+            has = not np.isnan(np.hypot(um, vm)).all()
+        want = dict(u=um, v=vm, count=cs)
+        if coarseness > 1:
+            want = {k: spatial_mean_numpy(a, coarseness) for k, a in want.items()}
+        with np.errstate(all="ignore"):
+            want["speed"] = np.hypot(want["u"], want["v"])
+        assert r["has_data"] == has, (tag, int(mask.sum()))
+        for k, a in want.items():
+            assert r[k].shape == a.shape and G.same_floats(r[k], a), (k, tag, int(mask.sum()))
+        finite += int(np.isfinite(want["u"]).sum())
+    return finite
+
+
+def test_spatial_mean_geometry_equals_numpy():
+    """Two periods per cube, all windows but the last and the last alone, about 30 % NaN: u, v, count and speed equal
+    np.nanmean / np.nansum / np.mean of the padded blocks at every geometry of the table above."""
+    rng = np.random.default_rng(97)
+    with Context(64, 64, n_slots=1, max_pts=1024) as own:
+        for n, (rows, cols, c) in enumerate(GEOMETRIES):
+            nt = 3 + n % 3
+            data, at = small_cube(rows, cols, nt, rng, keep=list(range(nt - 1)))
+            periods = [(at(0), at(nt - 1)), (at(nt - 1), at(nt))]
+            assert 0.2 < np.isnan(data["u"]).mean() < 0.4 or rows * cols < 50
+            finite = check_periods_against_numpy(own, data, periods, c, (rows, cols, c))
+            assert finite >= -(-rows // c) * -(-cols // c)          # the long period's coarse means are numbers
+
+
+def test_one_cell_cube_equals_numpy():
+    """A cube of one cell is a contiguous run to numpy, added pairwise and not window after window; its neighbours of
+    two cells are not.  1000 windows, 30 % NaN, periods of 1, 7, 8, 9, 128, 129, 300 and 900 windows."""
+    rng = np.random.default_rng(98)
+    spans = [(0, 1), (1, 8), (10, 18), (20, 29), (100, 228), (300, 429), (500, 800), (50, 950)]
+    with Context(64, 64, n_slots=1, max_pts=1024) as own:
+        for rows, cols in ((1, 1), (1, 2), (2, 1)):
+            data, at = small_cube(rows, cols, 1000, rng)
+            data["u"][:, :, 0] = 0.25                                 # the period of one window holds a value
+            periods = [(at(a), at(b)) for a, b in spans]
+            check_periods_against_numpy(own, data, periods, 1, (rows, cols))
+
+
 # ---- the ABI on a live handle -------------------------------------------------------------------------------------
 
 def test_abi_argument_checks():
@@ -248,6 +329,13 @@ def test_abi_argument_checks():
         assert average(idx=np.array([0, -1, 2, 3, 4], np.int32)) == _lib.EARG
         assert average(o=out[:3] + [None]) == _lib.EARG
         assert average(c=40000) == _lib.ECAP
+        assert average(c=8194) == _lib.ECAP                   # above the largest coarseness checked against numpy
+        assert b"coarseness" in lib.icelk_last_error(h)
+        coarse = [np.zeros(2) for _ in range(4)]
+        assert average(c=8193, o=coarse) == _lib.OK           # at it: one coarse cell per period, mostly padding
+        w = a.reshape(nt, rows, cols)
+        fine_u = [(0.0 + w[0] + w[1]) / 2, (0.0 + w[2] + w[3] + w[4]) / 3]
+        assert G.same_floats(coarse[0], np.array([spatial_mean_numpy(f, 8193)[0, 0] for f in fine_u]))
         assert b"" != lib.icelk_last_error(h)
         # results of the small cube: period 0 = windows 0, 1; period 1 = windows 2, 3, 4
         assert average() == _lib.OK
