@@ -6,7 +6,7 @@
 //
 // Stages
 //   K6+K7 fused (k_eig_strip<BS>, blockSize 3/5/7/10): a workgroup walks down a strip of the frame, one thread per
-//         covariance column: Sobel -> covariance products -> blockSize^2 box sums (exact double sums: column sums
+//         covariance column: Sobel -> covariance products -> blockSize^2 box sums (double sums: column sums
 //         rolled down in registers, row sums through LDS) -> min eigenvalue -> 3x3 non-max test, mask, 1-px border ->
 //         local maxima appended as 64-bit keys (response key << 32 | y << 16 | x), plus the masked maximum of the map
 //         (order-preserving atomicMax).  Neither OpenCV's f32 Dx/Dy/covariance images (5 x 4 B/px) nor the
@@ -110,11 +110,16 @@ __device__ __forceinline__ void sobel_cov2(f2 a0, f2 b0, f2 c0, f2 a1, f2 c1, f2
     yy = dy * dy;
 }
 
-// N consecutive window sums of BS terms each over v[0 .. N+BS-2].  Every term is a float product of derivative
-// values of an 8-bit image: magnitudes in [2^-27, 2^-3] with 24-bit mantissas, so ANY sum of up to a few hundred of
-// them is exact in double (tests/test_oracle_kat.py::test_box_sums_of_the_covariance_planes_are_exact_in_double) --
-// a sliding sum (drop the oldest term, add the next) therefore gives bit for bit the value of OpenCV's running
-// RowSum / ColumnSum and of the term-by-term sum the oracle forms, with 2 additions per output instead of BS - 1.
+// N consecutive window sums of BS terms each over v[0 .. N+BS-2]: a sliding sum (drop the oldest term, add the next), 2
+// additions per output instead of BS - 1.  NOT the order of the oracle, the restatement and k_min_eig, which add term by
+// term.  Where every derivative is integer * scale the products lie in [2^-30, 2^-4] with 24-bit mantissas and any sum of a few
+// hundred of them is exact in double (tests/test_oracle_kat.py::test_box_sums_of_the_covariance_planes_are_exact_in_double),
+// so the order cannot show.  Real dy values are not all of that form: where two pixel rows nearly cancel, dy is a rounding
+// residue down to 2^-28, its products reach below 2^-60, and a sum that also holds ordinary products rounds.  The sliding
+// sum then differs from the term-by-term one by at most N_add * 2^-53 * (largest sum), which the float32 map shows in a few
+// pixels per frame at the 1e-12 level (the bound, its derivation, the measured counts;
+// tests/box_sum_frames.py, tests/test_gpu_box_sums.py).  OpenCV's own RowSum / ColumnSum are running sums too: their
+// result depends on their history in the same way, and is not the term-by-term value either.
 template <int N, int BS>
 __device__ __forceinline__ void window_sums(const double (&v)[N + BS - 1], double (&out)[N])
 {
@@ -175,8 +180,12 @@ struct CandSrc {
 //     smooth of the two pixel rows above are kept; three byte loads per new row, issued one row ahead; BORDER_REFLECT_101
 //     in x costs nothing: the three column offsets of a thread are fixed).  The COLUMN sums come first: a running double
 //     sum per plane, + the new product, - the one blockSize rows up, kept as f32 in a register ring (static indices: the
-//     row loop is unrolled by lcm(blockSize, 4)).  All of these sums are exact (window_sums' note), so summing columns
-//     first and sliding the window give bit for bit the value of OpenCV's row-then-column running sums.
+//     row loop is unrolled by lcm(blockSize, 4)).  These sums are exact for derivatives of the form integer * scale and
+//     round where a dy is a rounding residue (window_sums' note): the running sum carries such an error down the strip
+//     until the strip ends (over an exactly constant band, where every later term is 0, it stays visible as a map value of
+//     ~1e-19 in place of 0), so columns-first-and-sliding equals the term-by-term sum, and OpenCV's row-then-column running
+//     sums, only up to the bound of DESIGN.md 4.2: (blockSize - 1) + 2 EH additions here, (blockSize - 1) + 2 (RX - 1) in
+//     the row window.
 //   * every 4 rows: the column sums of the 4 rows (LDS, 24 KB) -> row sums by threads that own 4 consecutive outputs of
 //     one row (sliding window, 15 additions per plane) -> min eigenvalue -> an 8-row ring of the eigenvalue map (LDS);
 //     then the 3x3 non-max test, one thread per column, for the 4 rows whose lower neighbour now exists.

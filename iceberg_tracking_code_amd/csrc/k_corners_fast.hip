@@ -37,7 +37,9 @@
 //   |dx - k1 dxi| <= 2.0001 u k1 (|r0 + r2| + 2 |r1|) <= k1 ex,  ex = 2040.2 u = 1.216e-4
 //   |t - k1 (a + 2b + c)| <= 3.0001 u k1 1020;  |dy - k1 dyi| <= k1 ey,  ey = (2 * 3060.1 + 1020) u = 4.256e-4
 //   products: |fl(dx dx) - k1^2 dxi^2| <= k1^2 (2 ex |dxi| + ex^2 + u (|dxi| + ex)^2), likewise the other two;
-//   box sums are exact in double (k_corners.hip), so with N = blockSize^2, T = Sxx + Syy and Cauchy-Schwarz
+//   box sums in double add at most N 2^-53 (largest sum) whatever their order (exact for integer * scale derivatives, not
+//   where a dy is a rounding residue: k_corners.hip, window_sums) -- nine orders of magnitude below the terms that
+//   follow, and inside the slack of eps; so with N = blockSize^2, T = Sxx + Syy and Cauchy-Schwarz
 //   sum |dxi| <= sqrt(N Sxx) <= sqrt(N T):
 //     |Sxx_f - k1^2 Sxx| <= k1^2 (2 ex sqrt(N T) + N ex^2 + u T)   (yy with ey;  xy: (ex + ey) sqrt(N T) + N ex ey + u T / 2)
 //   the smaller eigenvalue of a symmetric 2x2 matrix moves by at most the spectral norm of a perturbation,
@@ -379,7 +381,8 @@ __device__ __forceinline__ float min_eig_exact(double s0, double s1, double s2)
 }
 
 // The same value at ONE pixel by FOUR neighbouring lanes (a quad): each forms a quarter of the window's derivative rows and
-// their box-sum share, the three double sums are added across the quad (exact in double: any order) -- a quarter of the
+// their box-sum share, the three double sums are added across the quad (row by row, then four partial sums: one more order
+// of addition, equal to the term-by-term sum up to the bound of DESIGN.md 4.2 where a sum rounds) -- a quarter of the
 // dependent instruction chain per lane, ~100 registers, and four times as many waves to hide the load latency with.
 // Every lane of the quad returns the value.
 __device__ __forceinline__ double quad_sum(double v)

@@ -226,10 +226,14 @@ def test_fb_distance_is_numpy_hypot_on_float32(orc):
 
 
 def test_box_sums_of_the_covariance_planes_are_exact_in_double():
-    """cornerMinEigenVal's boxFilter keeps double sums of float32 products.  For 8-bit input every such
-    product lies in [2^-30, 2^-4] with a 24-bit mantissa, so any sum of <= 32x32 of them is exact in double: sliding
-    (OpenCV's RowSum / ColumnSum) and direct summation (oracle, kernels) give the same float32 -- the summation order is
-    not a parity risk."""
+    """cornerMinEigenVal's boxFilter keeps double sums of float32 products.  Where the derivatives are
+    integer * scale -- the MODEL this test draws -- every product lies in [2^-30, 2^-4] with a 24-bit mantissa, so any sum of
+    <= 32x32 of them is exact in double: sliding (OpenCV's RowSum / ColumnSum) and direct summation (oracle, kernels) give
+    the same float32.  That covers integer * scale values only.  Real dy = rdy[down] - rdy[up] is the difference of two row
+    smooths rounded three times each; where two pixel rows nearly cancel it is a rounding residue down to 2^-28, its products
+    fall far below 2^-30, and a box sum that holds one beside ordinary products rounds: outside this test.  Those frames,
+    the exact reference and the bound that takes the place of "the order cannot matter" are in tests/box_sum_frames.py,
+    tests/test_box_sums_host.py and tests/test_gpu_box_sums.py."""
     import math
     rng = np.random.RandomState(11)
     for bs in (3, 5, 7, 10, 16, 32):
