@@ -127,6 +127,9 @@ SIGNATURES = {
     "icelk_jpeg_crop_poll": (C.c_int, [handle_p, C.c_int, i32p]),
     "icelk_jpeg_crop_finish": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(JpegCropStats)]),
     "icelk_jpeg_crop_cancel": (C.c_int, [handle_p, C.c_int]),
+    "icelk_upload_jpeg_file_async_resave": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_jpeg_async_finish_file": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(JpegCropStats)]),
+    "icelk_jpeg_crop_fwd_device_coefficients": (C.c_int, [handle_p, vp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_uint64]),
     "icelk_plot_size": (C.c_int, [C.c_int, C.c_int, C.c_int, i32p, i32p]),
     "icelk_plot_glyph": (C.c_int, [C.c_int, u8p]),
     "icelk_plot_overlay_host": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_char_p, u8p, C.c_int]),

@@ -172,17 +172,26 @@ class Context:
             return
         self._ck_jpeg(self._lib.icelk_upload_jpeg_file(self._h, slot, data, len(data), variant, left, top, right, bottom))
 
-    def upload_jpeg_file_async(self, slot, data, variant=GRAY_CV4, crop=None):
+    def upload_jpeg_file_async(self, slot, data, variant=GRAY_CV4, crop=None, resave=None, crop_file=False):
         """`upload_jpeg_file` ahead of the frame: the host's share and the errors it can see now, every device phase
         enqueued on a decode stream beside the tracker, no wait (icelk_upload_jpeg_file_async).  `data` is copied by the
         library and free when the call returns.  The slot holds no usable frame before `jpeg_async_finish(slot)` has
-        returned -- or `jpeg_async_poll(slot)` says 1."""
+        returned -- or `jpeg_async_poll(slot)` says 1.  `resave`: as `upload_bgr`; the re-save is part of the enqueued
+        job (icelk_upload_jpeg_file_async_resave).  `crop_file` (needs `resave`): the job also codes the crop's file,
+        which `jpeg_async_finish_file(slot)` returns."""
         if isinstance(data, bytearray):
             buf = (C.c_char * len(data)).from_buffer(data)   # as it is: the library takes its own copy
         else:
             buf = data = bytes(data)
         left, top, right, bottom = _crop4(crop)
-        self._ck_jpeg(self._lib.icelk_upload_jpeg_file_async(self._h, slot, buf, len(data), variant, left, top, right, bottom))
+        quality = resave_quality(resave)
+        if quality is None:
+            if crop_file:
+                raise ValueError("crop_file needs resave=: the file is the re-saved crop's")
+            self._ck_jpeg(self._lib.icelk_upload_jpeg_file_async(self._h, slot, buf, len(data), variant, left, top, right, bottom))
+            return
+        self._ck_jpeg(self._lib.icelk_upload_jpeg_file_async_resave(self._h, slot, buf, len(data), variant, left, top, right, bottom,
+                                                                    quality, 1 if crop_file else 0))
 
     def jpeg_async_poll(self, slot):
         """0: the slot's file is in flight, 1: decoded, 2: the host decoder has to take it (`jpeg_async_finish` does).
@@ -198,6 +207,41 @@ class Context:
         st = _lib.JpegHuffStats()
         self._ck_jpeg(self._lib.icelk_jpeg_async_finish(self._h, slot, C.byref(st)))
         return _stats_dict(st)
+
+    def jpeg_async_finish_file(self, slot, comment=None):
+        """`jpeg_async_finish` for a file started with `resave=` and `crop_file=True`; returns (the bytes of the file
+        Pillow's `Image.open(f).crop(box).save(out)` writes, a dictionary as `jpeg_crop_finish` returns).  `comment`: the
+        source's comment (`jpeg.source_comment`) or None.  The job is gone afterwards, also when the call raises -- with one
+        exception: a file started without `crop_file=True` (IcelkError, ICELK_ESTATE) stays in flight, nothing of it has
+        been waited for, and `jpeg_async_finish(slot)` is still to be called."""
+        com, ncom = _comment_args(comment)
+        st = _lib.JpegCropStats()
+        try:
+            data = _encode_call(lambda out, cap, n: self._lib.icelk_jpeg_async_finish_file(self._h, slot, com, ncom, out, cap, n, C.byref(st)),
+                                self._crop_file_guess + ncom, "icelk_jpeg_async_finish_file", self._h)
+        except _lib.IcelkError as e:
+            if getattr(e, "code", None) == _lib.ECAP:     # the library keeps a job whose file did not fit: drop the file here
+                self._lib.icelk_jpeg_async_finish(self._h, slot, None)
+            raise
+        self._crop_file_guess = max(1 << 16, len(data) + len(data) // 4)
+        stats = _stats_dict(st.huff)
+        stats.update(route=_lib.JPEG_CROP_ROUTES[st.route], blocks=int(st.blocks), budget=int(st.budget), stream_len=int(st.stream_len))
+        return data, stats
+
+    def jpeg_crop_fwd_device_coefficients(self, data, crop=None, quality=75):
+        """The coefficients of the file Pillow's `Image.open(f).crop(box).save(out, quality=quality)` writes, as the fused
+        crop-and-forward kernel makes them from the decoded planes (icelk_jpeg_crop_fwd_device_coefficients), for tests."""
+        data = bytes(data)
+        left, top, right, bottom = _crop4(crop)
+        i = describe_jpeg(data)
+        w, h = i.width - left - right, i.height - top - bottom
+        if w < 1 or h < 1:
+            raise ValueError("crop box leaves no image")
+        count = 384 * ((w + 15) // 16) * ((h + 15) // 16)    # 4 luma and 2 chroma blocks per MCU
+        coef = np.empty(count, np.int16)
+        self._ck_jpeg(self._lib.icelk_jpeg_crop_fwd_device_coefficients(self._h, data, len(data), left, top, right, bottom, int(quality),
+                                                                        C.c_void_p(coef.ctypes.data), coef.size))
+        return coef
 
     # -- the crop step on its own: decode, crop, re-save and encode in one enqueued piece (csrc/abi_jpeg_crop.hip) --
     def jpeg_crop_config(self, stream_bytes_per_block=48):

@@ -11,7 +11,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "bgr2gray", "pyrdown", "lk", "lk_fb", "corner_candidates", "min_distance", "sort_emit",
     "project_tracks", "synth", "lk_fb_pair", "jpeg_idct", "jpeg_out", "jpeg_huff", "jpeg_fwd",
     "jpeg_enc_count", "jpeg_enc_scan", "jpeg_enc_pack", "jpeg_enc_ff", "jpeg_enc_stuff",
-    "jpeg_enc_pack_budget", "jpeg_enc_ff_budget", "jpeg_enc_stuff_budget", "jpeg_crop_rgb", "jpeg_crop_verdict",
+    "jpeg_enc_pack_budget", "jpeg_enc_ff_budget", "jpeg_enc_stuff_budget", "jpeg_crop_rgb", "jpeg_crop_verdict", "jpeg_crop_fwd",
     "plot_background", "plot_clear", "plot_scatter", "plot_resolve",
     "map_clear", "map_cells", "map_polyline", "map_arrows", "map_resolve",
 };

@@ -20,17 +20,31 @@
 // sanitizers).  What they leave in the job's buffers and in the slot is garbage that nobody may consume:
 // the slot counts as filled only after finish has returned ICELK_OK, and finish overwrites all of it.
 //
+// The re-save form (icelk_upload_jpeg_file_async_resave): the slot gets the frame the reference tracks on, the crop saved
+// again as a JPEG (quality, 4:2:0) and opened.  Behind the source's inverse DCT the chain goes on with the fused kernel
+// (k_jpeg_crop_fwd, k_jpeg_fwd.hip: the crop box of the planes -> the re-saved file's coefficients in d_rcoef, no R G B image
+// in between), the inverse DCT of THOSE into planes of the job's own (d_planes2), the output kernel from them into the
+// slot's level 0; with want_file the budgeted coder of a crop job (abi_jpeg_crop.hip) codes d_rcoef behind it, and the
+// verdict kernel is the crop job's, the coder's words "not asked" without a file.  poll answers by the decoder's verdict
+// alone: a scan over its budget concerns only the file.  On a file that does not settle the fused kernel reads the planes
+// at clamped coordinates inside them and stores whole blocks of the re-saved layout (its file header says why), the second
+// inverse DCT walks that layout, and the coder's stores are bounded by the budget for ANY contents of its control words
+// (the header of abi_jpeg_crop.hip): the same garbage-nobody-consumes as above.  finish runs everything behind the Huffman
+// phases again (a wanted file is dropped); finish_file does so too and returns the file by the crop job's three routes.
+//
 // Jobs.  Every file in flight owns one Ctx::JpegJob (device buffers as the synchronous calls' job, plus the pinned
 // staging area and the pinned verdict words) from start to finish; the ring grows when every job is in flight and is
 // never sized by the frame maximum.  A job's kernels are through when its verdict has arrived (the verdict kernel is
 // the last of the chain) or finish has synchronised its stream, so a freed job can go out on the other stream at once.
 #include "icelk_ctx.h"
+#include "jpeg_enc_host.h"
+#include "jpeg_resave_host.h"
 
 namespace icelk {
 
 static void free_job(Ctx::JpegJob* B)
 {
-    void* p[] = {B->d_coef, B->d_planes, B->d_file, B->d_seg, B->d_tabs, B->d_T, B->d_X, B->d_cnt, B->d_P, B->d_ctl, B->d_dc, B->d_rgb, B->d_rcoef};
+    void* p[] = {B->d_coef, B->d_planes, B->d_file, B->d_seg, B->d_tabs, B->d_T, B->d_X, B->d_cnt, B->d_P, B->d_ctl, B->d_dc, B->d_rgb, B->d_rcoef, B->d_planes2};
     for (void* q : p)
         if (q) hipFree(q);
     jpeg_enc_free(B->enc);
@@ -108,7 +122,10 @@ int jpeg_decode_stream(Ctx* c, hipStream_t* out)
 static int transform_into_slot(Ctx* c, Ctx::JpegJob& B)
 {
     if (int rc = jpeg_idct_on(c, B.st, B.idct)) return rc;
-    return jpeg_gray_on(c, B.st, B.out, c->slots[B.slot], B.variant);
+    if (!B.resave) return jpeg_gray_on(c, B.st, B.out, c->slots[B.slot], B.variant);
+    if (int rc = jpeg_crop_fwd_on(c, B.st, B.out, B.d_rcoef, B.rinfo)) return rc;
+    if (int rc = jpeg_idct_on(c, B.st, B.ridct)) return rc;
+    return jpeg_gray_on(c, B.st, B.rout, c->slots[B.slot], B.variant);
 }
 
 // the job leaves its slot; `state`: what icelk_jpeg_async_poll keeps answering for the slot
@@ -117,6 +134,7 @@ static void release_job(Ctx* c, Ctx::JpegJob& B, int state)
     c->jpeg.slot_state[B.slot] = state;
     c->jpeg.slot_job[B.slot] = -1;
     B.slot = -1;
+    B.resave = B.want_file = B.have_scan = false;
 }
 
 // The job's pinned staging area: tables | segment table | file.  The copies of a start read it when the stream gets there,
@@ -143,7 +161,7 @@ int jpeg_stage_file(Ctx* c, Ctx::JpegJob& B, const JpegIndex& X, size_t seg_byte
 }
 
 static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uint64_t len, JpegIndex& X, int left, int top, int right,
-                     int bottom)
+                     int bottom, const enc::Layout* L = nullptr)
 {
     Ctx::Jpeg& J = c->jpeg;
     const bool host_only = B.host_only;
@@ -158,6 +176,15 @@ static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uin
         seg_bytes = X.seg.size() * sizeof(lanes::Seg);
     }
     if (int rc = jpeg_stage_file(c, B, X, seg_bytes, data, len)) return rc;
+    if (B.resave) {
+        if (int rc = grow(c, &B.d_rcoef, &B.rcoef_cap, (size_t)B.rinfo.coef_count)) return rc;
+        if (int rc = grow(c, &B.d_planes2, &B.planes2_cap, jpeg_plane_bytes(B.rinfo))) return rc;
+        jpeg_plane_layout(B.rinfo, 0, 0, 0, 0, B.d_rcoef, B.d_planes2, &B.ridct, &B.rout);
+        if (B.want_file) {
+            B.budget = enc::budget_cap(L->blocks, J.crop_bytes_per_block);
+            if (int rc = jpeg_budget_buffers(c, B, *L)) return rc;
+        }
+    }
     if (int rc = jpeg_decode_stream(c, &B.st)) return rc;
     // from here on the slot is taken: whatever fails below leaves it without a frame
     if (int rc = begin_frame(c, slot, B.out.ow, B.out.oh)) return rc;
@@ -179,9 +206,16 @@ static int start_job(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uin
     }
     if (int rc = check_launch(c, "jpeg_huff")) return rc;
     if (int rc = transform_into_slot(c, B)) return rc;
+    if (B.want_file)
+        if (int rc = jpeg_encode_budgeted(c, B, *L)) return rc;
     B.seq = (B.seq + 1) & 0x3fffffffu;
-    launch_jpeg_huff_verdict(st, B.d_ctl, J.max_rounds, B.h_verdict, B.seq);
-    if (int rc = check_launch(c, "jpeg_huff_verdict")) return rc;
+    if (B.resave) {
+        ProfScope p(c, K_JPEG_CROP_VERDICT, st);
+        launch_jpeg_crop_verdict(st, B.d_ctl, J.max_rounds, B.want_file ? B.enc.d_ctl : nullptr, B.budget, B.h_verdict, B.seq);
+    } else {
+        launch_jpeg_huff_verdict(st, B.d_ctl, J.max_rounds, B.h_verdict, B.seq);
+    }
+    if (int rc = check_launch(c, B.resave ? "jpeg_crop_verdict" : "jpeg_huff_verdict")) return rc;
     HIPCHK(c, hipEventRecord(B.done, st));
     return foreign_write_end(c, s, st);
 }
@@ -235,6 +269,40 @@ static int host_takes_job(Ctx* c, Ctx::JpegJob& B)
     return ICELK_OK;
 }
 
+// What icelk_jpeg_async_finish_file waits for and redoes, by the three routes of a crop job's settle (abi_jpeg_crop.hip):
+// afterwards the slot holds its frame, the job's pinned area the scan, and cstats says how both got there.
+static int settle_file(Ctx* c, Ctx::JpegJob& B)
+{
+    icelk_jpeg_crop_stats_t& S = B.cstats;
+    memset(&S, 0, sizeof(S));
+    enc::Layout L;
+    if (int rc = jpeg_enc_rc(c, enc::layout_of(&B.rinfo, &L))) return rc;
+    S.blocks = L.blocks;
+    S.budget = B.budget;
+    uint32_t why = ICELK_JPEG_FALLBACK_SIZE, coder = enc::kOverBudget;
+    if (!B.host_only) {
+        if (int rc = jpeg_await_verdict(c, B)) return rc;
+        const uint32_t* v = B.h_verdict;
+        jpeg_huff_stats_of(B, &S.huff);
+        why = v[JV_VERDICT] == JV_DECODED ? ICELK_JPEG_FALLBACK_NONE : v[JV_VERDICT];
+        coder = v[JV_ENC_VERDICT];
+    }
+    S.huff.fallback = why;
+    if (why != ICELK_JPEG_FALLBACK_NONE) {
+        S.route = ICELK_JPEG_CROP_HOST_HUFFMAN;
+        if (int rc = host_takes_job(c, B)) return rc;   // the slot's frame again, from the host decoder's coefficients
+        if (int rc = jpeg_encode_on(c, B.enc, B.st, L, B.d_rcoef)) return rc;
+        return jpeg_fetch_scan(c, B, B.enc.stream_len, true);
+    }
+    if (coder != enc::kCoded) {
+        S.route = ICELK_JPEG_CROP_OVER_BUDGET;   // or a coefficient without a code, which the coder below reports
+        if (int rc = jpeg_encode_on(c, B.enc, B.st, L, B.d_rcoef)) return rc;
+        return jpeg_fetch_scan(c, B, B.enc.stream_len, true);
+    }
+    S.route = ICELK_JPEG_CROP_DEVICE;
+    return jpeg_fetch_scan(c, B, B.h_verdict[JV_ENC_LEN], false);
+}
+
 static int job_of(Ctx* c, int slot, Ctx::JpegJob** B)
 {
     *B = nullptr;
@@ -250,8 +318,9 @@ using namespace icelk;
 
 extern "C" {
 
-int icelk_upload_jpeg_file_async(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left,
-                                 int crop_top, int crop_right, int crop_bottom)
+// the start of both forms.  resave: the re-save form at `quality`; want_file: the job codes the crop's file as well
+static int upload_async(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left, int crop_top,
+                        int crop_right, int crop_bottom, bool resave, int quality, bool want_file)
 {
     if (!h) return ICELK_EARG;
     Ctx* c = C(h);
@@ -274,6 +343,16 @@ int icelk_upload_jpeg_file_async(icelk_t* h, int slot, const uint8_t* data, uint
     int rc = jpeg_open(c, data, len, *X, &info, &host_only);
     if (rc) return rc;
     if (info.ncomp != 3) FAIL(c, ICELK_EARG, "expected a 3-component JPEG file");
+    icelk_jpeg_info_t rinfo{};
+    enc::Layout L{};
+    if (resave) {
+        if (!jpeg_info_ok(info)) FAIL(c, ICELK_EARG, "JPEG descriptor does not describe a supported file");
+        int w = 0, h_ = 0;
+        if ((rc = check_crop_box(c, info, crop_left, crop_top, crop_right, crop_bottom, &w, &h_))) return rc;
+        if ((rc = jpeg_resave_check(c, w, h_, quality))) return rc;
+        resave::resave_info(w, h_, quality, &rinfo);
+        if (want_file && (rc = jpeg_enc_rc(c, enc::layout_of(&rinfo, &L)))) return rc;   // blocks * 1660 < 2^32 among it
+    }
     if (J.slot_job.empty()) {
         if (const char* e = getenv("ICELK_JPEG_ASYNC_STREAMS")) J.dec_streams = atoi(e) == 1 ? 1 : 2;
         if (const char* e = getenv("ICELK_JPEG_ASYNC_PRIO")) J.dec_high = !strcmp(e, "high");
@@ -292,16 +371,33 @@ int icelk_upload_jpeg_file_async(icelk_t* h, int slot, const uint8_t* data, uint
     B.variant = gray_variant;
     B.host_only = host_only;
     B.slot = -1;
-    rc = start_job(c, B, slot, data, len, *X, crop_left, crop_top, crop_right, crop_bottom);
+    B.resave = resave;
+    B.want_file = resave && want_file;
+    B.have_scan = false;
+    B.rinfo = rinfo;
+    rc = start_job(c, B, slot, data, len, *X, crop_left, crop_top, crop_right, crop_bottom, &L);
     if (rc) {
         // what went out before the failure may still use the job's buffers
         if (B.slot >= 0) hipStreamSynchronize(B.st);
         B.slot = -1;
+        B.resave = B.want_file = false;
         return rc;
     }
     J.slot_job[slot] = idx;
     J.slot_state[slot] = 0;
     return ICELK_OK;
+}
+
+int icelk_upload_jpeg_file_async(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left,
+                                 int crop_top, int crop_right, int crop_bottom)
+{
+    return upload_async(h, slot, data, len, gray_variant, crop_left, crop_top, crop_right, crop_bottom, false, 0, false);
+}
+
+int icelk_upload_jpeg_file_async_resave(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left,
+                                        int crop_top, int crop_right, int crop_bottom, int quality, int want_file)
+{
+    return upload_async(h, slot, data, len, gray_variant, crop_left, crop_top, crop_right, crop_bottom, true, quality, want_file != 0);
 }
 
 int icelk_jpeg_async_poll(icelk_t* h, int slot, int* state)
@@ -316,7 +412,8 @@ int icelk_jpeg_async_poll(icelk_t* h, int slot, int* state)
         *state = c->jpeg.slot_state[slot];
         return ICELK_OK;
     }
-    if (B->host_only) *state = 2;
+    if (B->have_scan) *state = B->cstats.huff.fallback == ICELK_JPEG_FALLBACK_NONE ? 1 : 2;   // finish_file ran out of room
+    else if (B->host_only) *state = 2;
     else if (!jpeg_verdict_here(*B)) *state = 0;
     else *state = B->h_verdict[JV_VERDICT] == JV_DECODED ? 1 : 2;
     return ICELK_OK;
@@ -332,6 +429,13 @@ int icelk_jpeg_async_finish(icelk_t* h, int slot, icelk_jpeg_huff_stats_t* stats
     if (int rc = job_of(c, slot, &Bp)) return rc;
     if (!Bp) FAIL(c, ICELK_ESTATE, "no JPEG file in flight in this slot");
     Ctx::JpegJob& B = *Bp;
+    if (B.have_scan) {
+        // icelk_jpeg_async_finish_file has done all of it and ran out of room: the file is dropped
+        const icelk_jpeg_huff_stats_t done = B.cstats.huff;
+        release_job(c, B, done.fallback == ICELK_JPEG_FALLBACK_NONE ? 1 : 2);
+        if (stats) *stats = done;
+        return ICELK_OK;
+    }
     icelk_jpeg_huff_stats_t st;
     memset(&st, 0, sizeof(st));
     uint32_t why = ICELK_JPEG_FALLBACK_SIZE;
@@ -358,6 +462,43 @@ int icelk_jpeg_async_finish(icelk_t* h, int slot, icelk_jpeg_huff_stats_t* stats
     release_job(c, B, why == ICELK_JPEG_FALLBACK_NONE ? 1 : 2);
     if (!rc && stats) *stats = st;
     return rc;
+}
+
+int icelk_jpeg_async_finish_file(icelk_t* h, int slot, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity,
+                                 uint64_t* len, icelk_jpeg_crop_stats_t* stats)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    Range rg("icelk jpeg_async_finish_file");
+    if (!len || !enc::comment_ok(comment, comment_len)) FAIL(c, ICELK_EARG, "null length, or a comment no segment holds");
+    HIPCHK(c, hipSetDevice(c->device));
+    Ctx::JpegJob* Bp = nullptr;
+    if (int rc = job_of(c, slot, &Bp)) return rc;
+    if (!Bp) FAIL(c, ICELK_ESTATE, "no JPEG file in flight in this slot");
+    Ctx::JpegJob& B = *Bp;
+    if (!B.want_file) FAIL(c, ICELK_ESTATE, "the slot's JPEG file was started without a file to write");
+    if (!B.have_scan) {
+        if (int rc = settle_file(c, B)) {
+            // a failed launch or a damaged file: nothing of the slot or the job can be relied on
+            hipStreamSynchronize(B.st);
+            c->slots[slot].levels_built = 0;
+            release_job(c, B, 2);
+            return rc;
+        }
+        B.cstats.stream_len = B.scan_len;
+    }
+    enc::Bytes H(nullptr, 0);
+    enc::header_bytes(B.rinfo, comment, comment_len, H);
+    *len = H.n + B.scan_len + 2;
+    if (!out || capacity < *len) FAIL(c, ICELK_ECAP, "the file does not fit the buffer (len says what it takes)");
+    enc::Bytes F(out, capacity);
+    enc::header_bytes(B.rinfo, comment, comment_len, F);
+    memcpy(out + F.n, B.h_out, (size_t)B.scan_len);
+    out[F.n + B.scan_len] = 0xFF;
+    out[F.n + B.scan_len + 1] = 0xD9;
+    if (stats) *stats = B.cstats;
+    release_job(c, B, B.cstats.huff.fallback == ICELK_JPEG_FALLBACK_NONE ? 1 : 2);
+    return ICELK_OK;
 }
 
 }  // extern "C"

@@ -39,39 +39,9 @@
 
 namespace icelk {
 
-namespace {
-
-Ctx::JpegJob* job_of_ticket(Ctx* c, int ticket)
-{
-    if (ticket < 1) return nullptr;
-    for (Ctx::JpegJob* B : c->jpeg.ring)
-        if (B->ticket == ticket) return B;
-    return nullptr;
-}
-
-// the crop box of the job's planes as R G B into d_rgb, on the job's stream
-int crop_rgb(Ctx* c, Ctx::JpegJob& B)
-{
-    JpegOutArgs O = B.out;
-    O.dst = B.d_rgb;
-    O.dst_pitch = 3 * O.ow;
-    {
-        ProfScope p(c, K_JPEG_CROP_RGB, B.st);
-        launch_jpeg_rgb(B.st, O);
-    }
-    return check_launch(c, "jpeg_crop_rgb");
-}
-
-// inverse DCT of the job's coefficients, the crop box, the forward kernel: d_coef -> d_rcoef
-int transform_and_resave(Ctx* c, Ctx::JpegJob& B)
-{
-    if (int rc = jpeg_idct_on(c, B.st, B.idct)) return rc;
-    if (int rc = crop_rgb(c, B)) return rc;
-    return jpeg_fwd_on(c, B.st, B.d_rgb, B.d_rcoef, B.out.ow, B.out.oh, B.rinfo);
-}
-
+// ---- shared with the slot-bound re-save job (abi_jpeg_async.hip)
 // the coder's buffers at the job's budget: nothing of them is sized by what a file measures
-int budget_buffers(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L)
+int jpeg_budget_buffers(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L)
 {
     Ctx::JpegEnc& E = B.enc;
     const uint32_t cap = B.budget, chunks = enc::chunks_of(cap);
@@ -84,7 +54,7 @@ int budget_buffers(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L)
 }
 
 // count, scan, pack, ff, scan, stuff on the job's stream with no look at the sizes
-int encode_budgeted(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L)
+int jpeg_encode_budgeted(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L)
 {
     Ctx::JpegEnc& E = B.enc;
     const hipStream_t st = B.st;
@@ -126,55 +96,11 @@ int encode_budgeted(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L)
     return check_launch(c, "jpeg_enc (budgeted)");
 }
 
-int start_job(Ctx* c, Ctx::JpegJob& B, const uint8_t* data, uint64_t len, JpegIndex& X, int left, int top, int right, int bottom,
-              const enc::Layout& L)
-{
-    Ctx::Jpeg& J = c->jpeg;
-    if (int rc = jpeg_plane_args(c, B, &B.info, left, top, right, bottom, &B.idct, &B.out)) return rc;
-    JpegHuffArgs H{};
-    size_t seg_bytes = 0;
-    if (!B.host_only) {
-        jpeg_index_lanes(X, (uint32_t)J.subseq_bits, J.max_hops);
-        if (int rc = jpeg_huff_setup(c, B, X, len, &H, true)) return rc;
-        seg_bytes = X.seg.size() * sizeof(lanes::Seg);
-    }
-    if (int rc = jpeg_stage_file(c, B, X, seg_bytes, data, len)) return rc;
-    if (int rc = grow(c, &B.d_rgb, &B.rgb_cap, (size_t)3 * B.out.ow * B.out.oh)) return rc;
-    if (int rc = grow(c, &B.d_rcoef, &B.rcoef_cap, (size_t)B.rinfo.coef_count)) return rc;
-    B.budget = enc::budget_cap(L.blocks, J.crop_bytes_per_block);
-    if (int rc = budget_buffers(c, B, L)) return rc;
-    if (int rc = jpeg_decode_stream(c, &B.st)) return rc;
-    if (B.host_only) return ICELK_OK;   // nothing goes out before finish, which has the host decoder take the file
-    const hipStream_t st = B.st;
-    memcpy(B.h_stage, X.tabs, sizeof(X.tabs));
-    memcpy(B.h_stage + sizeof(X.tabs), X.seg.data(), seg_bytes);
-    B.segments = X.scan.nseg;
-    B.subsequences = X.scan.nlanes;
-    B.ticket = 0;   // from here on something of the job is in flight: a failure has to wait for the stream
-    if (int rc = jpeg_huff_stage(c, B, X, B.h_stage + B.file_off, B.h_stage + sizeof(X.tabs), B.h_stage, len, st)) return rc;
-    {
-        ProfScope p(c, K_JPEG_HUFF, st);
-        for (int q = 0; q <= J.max_rounds; q++) launch_jpeg_huff_sync(st, H, q);
-        jpeg_huff_finish_phases(st, H);
-    }
-    if (int rc = check_launch(c, "jpeg_huff")) return rc;
-    if (int rc = transform_and_resave(c, B)) return rc;
-    if (int rc = encode_budgeted(c, B, L)) return rc;
-    B.seq = (B.seq + 1) & 0x3fffffffu;
-    {
-        ProfScope p(c, K_JPEG_CROP_VERDICT, st);
-        launch_jpeg_crop_verdict(st, B.d_ctl, J.max_rounds, B.enc.d_ctl, B.budget, B.h_verdict, B.seq);
-    }
-    if (int rc = check_launch(c, "jpeg_crop_verdict")) return rc;
-    HIPCHK(c, hipEventRecord(B.done, st));
-    return ICELK_OK;
-}
-
 // The scan at E.d_out (n bytes) into the job's pinned area.  The copy goes out on the handle's fetch stream behind the
 // job's event, not on the job's decode stream: newer jobs are queued there already (two streams in turn, several tickets
 // in flight), and the oldest ticket's finish must not wait for their chains.  again: the coder ran again on the job's
 // stream behind the verdict, so the event is recorded once more behind it.
-int fetch_scan(Ctx* c, Ctx::JpegJob& B, uint64_t n, bool again)
+int jpeg_fetch_scan(Ctx* c, Ctx::JpegJob& B, uint64_t n, bool again)
 {
     Ctx::Jpeg& J = c->jpeg;
     if (!J.fetch) HIPCHK(c, hipStreamCreateWithFlags(&J.fetch, hipStreamNonBlocking));
@@ -195,6 +121,81 @@ int fetch_scan(Ctx* c, Ctx::JpegJob& B, uint64_t n, bool again)
     HIPCHK(c, hipStreamSynchronize(J.fetch));
     B.scan_len = n;
     B.have_scan = true;
+    return ICELK_OK;
+}
+
+namespace {
+
+Ctx::JpegJob* job_of_ticket(Ctx* c, int ticket)
+{
+    if (ticket < 1) return nullptr;
+    for (Ctx::JpegJob* B : c->jpeg.ring)
+        if (B->ticket == ticket) return B;
+    return nullptr;
+}
+
+// the crop box of the job's planes as R G B into d_rgb, on the job's stream
+int crop_rgb(Ctx* c, Ctx::JpegJob& B)
+{
+    JpegOutArgs O = B.out;
+    O.dst = B.d_rgb;
+    O.dst_pitch = 3 * O.ow;
+    {
+        ProfScope p(c, K_JPEG_CROP_RGB, B.st);
+        launch_jpeg_rgb(B.st, O);
+    }
+    return check_launch(c, "jpeg_crop_rgb");
+}
+
+// inverse DCT of the job's coefficients, the crop box, the forward kernel: d_coef -> d_rcoef
+int transform_and_resave(Ctx* c, Ctx::JpegJob& B)
+{
+    if (int rc = jpeg_idct_on(c, B.st, B.idct)) return rc;
+    if (int rc = crop_rgb(c, B)) return rc;
+    return jpeg_fwd_on(c, B.st, B.d_rgb, B.d_rcoef, B.out.ow, B.out.oh, B.rinfo);
+}
+
+int start_job(Ctx* c, Ctx::JpegJob& B, const uint8_t* data, uint64_t len, JpegIndex& X, int left, int top, int right, int bottom,
+              const enc::Layout& L)
+{
+    Ctx::Jpeg& J = c->jpeg;
+    if (int rc = jpeg_plane_args(c, B, &B.info, left, top, right, bottom, &B.idct, &B.out)) return rc;
+    JpegHuffArgs H{};
+    size_t seg_bytes = 0;
+    if (!B.host_only) {
+        jpeg_index_lanes(X, (uint32_t)J.subseq_bits, J.max_hops);
+        if (int rc = jpeg_huff_setup(c, B, X, len, &H, true)) return rc;
+        seg_bytes = X.seg.size() * sizeof(lanes::Seg);
+    }
+    if (int rc = jpeg_stage_file(c, B, X, seg_bytes, data, len)) return rc;
+    if (int rc = grow(c, &B.d_rgb, &B.rgb_cap, (size_t)3 * B.out.ow * B.out.oh)) return rc;
+    if (int rc = grow(c, &B.d_rcoef, &B.rcoef_cap, (size_t)B.rinfo.coef_count)) return rc;
+    B.budget = enc::budget_cap(L.blocks, J.crop_bytes_per_block);
+    if (int rc = jpeg_budget_buffers(c, B, L)) return rc;
+    if (int rc = jpeg_decode_stream(c, &B.st)) return rc;
+    if (B.host_only) return ICELK_OK;   // nothing goes out before finish, which has the host decoder take the file
+    const hipStream_t st = B.st;
+    memcpy(B.h_stage, X.tabs, sizeof(X.tabs));
+    memcpy(B.h_stage + sizeof(X.tabs), X.seg.data(), seg_bytes);
+    B.segments = X.scan.nseg;
+    B.subsequences = X.scan.nlanes;
+    B.ticket = 0;   // from here on something of the job is in flight: a failure has to wait for the stream
+    if (int rc = jpeg_huff_stage(c, B, X, B.h_stage + B.file_off, B.h_stage + sizeof(X.tabs), B.h_stage, len, st)) return rc;
+    {
+        ProfScope p(c, K_JPEG_HUFF, st);
+        for (int q = 0; q <= J.max_rounds; q++) launch_jpeg_huff_sync(st, H, q);
+        jpeg_huff_finish_phases(st, H);
+    }
+    if (int rc = check_launch(c, "jpeg_huff")) return rc;
+    if (int rc = transform_and_resave(c, B)) return rc;
+    if (int rc = jpeg_encode_budgeted(c, B, L)) return rc;
+    B.seq = (B.seq + 1) & 0x3fffffffu;
+    {
+        ProfScope p(c, K_JPEG_CROP_VERDICT, st);
+        launch_jpeg_crop_verdict(st, B.d_ctl, J.max_rounds, B.enc.d_ctl, B.budget, B.h_verdict, B.seq);
+    }
+    if (int rc = check_launch(c, "jpeg_crop_verdict")) return rc;
+    HIPCHK(c, hipEventRecord(B.done, st));
     return ICELK_OK;
 }
 
@@ -227,15 +228,15 @@ int settle(Ctx* c, Ctx::JpegJob& B)
             hipStreamSynchronize(B.st);   // the copy of `host` may still be on its way
             return rc;
         }
-        return fetch_scan(c, B, B.enc.stream_len, true);
+        return jpeg_fetch_scan(c, B, B.enc.stream_len, true);
     }
     if (coder != enc::kCoded) {
         S.route = ICELK_JPEG_CROP_OVER_BUDGET;   // or a coefficient without a code, which the coder below reports
         if (int rc = jpeg_encode_on(c, B.enc, B.st, L, B.d_rcoef)) return rc;
-        return fetch_scan(c, B, B.enc.stream_len, true);
+        return jpeg_fetch_scan(c, B, B.enc.stream_len, true);
     }
     S.route = ICELK_JPEG_CROP_DEVICE;
-    return fetch_scan(c, B, B.h_verdict[JV_ENC_LEN], false);
+    return jpeg_fetch_scan(c, B, B.h_verdict[JV_ENC_LEN], false);
 }
 
 // the ticket is gone; what the job enqueued is through (the verdict has arrived or its stream was synchronised)

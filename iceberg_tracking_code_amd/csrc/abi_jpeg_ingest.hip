@@ -33,6 +33,27 @@ int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int lef
     if (!I) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
     if (!jpeg_info_ok(*I)) FAIL(c, ICELK_EARG, "JPEG descriptor does not describe a supported file");
     if (int rc = check_crop_box(c, *I, left, top, right, bottom, &out->ow, &out->oh)) return rc;
+    if (int rc = grow(c, &B.d_coef, &B.coef_cap, (size_t)I->coef_count)) return rc;
+    if (int rc = grow(c, &B.d_planes, &B.planes_cap, jpeg_plane_bytes(*I))) return rc;
+    jpeg_plane_layout(*I, left, top, right, bottom, B.d_coef, B.d_planes, Ap, out);
+    return ICELK_OK;
+}
+
+size_t jpeg_plane_bytes(const icelk_jpeg_info_t& I)
+{
+    size_t n = 0;
+    for (int k = 0; k < I.ncomp; k++) n += (size_t)I.blocks_x[k] * 8 * I.blocks_y[k] * 8;
+    return n;
+}
+
+// jpeg_plane_args without its checks and allocations: descriptor and box are known to be good, d_coef holds I.coef_count
+// values and d_planes jpeg_plane_bytes(I) bytes (the second plane buffer of a slot-bound re-save job, abi_jpeg_async.hip)
+void jpeg_plane_layout(const icelk_jpeg_info_t& Iref, int left, int top, int right, int bottom, int16_t* d_coef, uint8_t* d_planes,
+                       JpegIdctArgs* Ap, JpegOutArgs* out)
+{
+    const icelk_jpeg_info_t* I = &Iref;
+    out->ow = I->width - left - right;
+    out->oh = I->height - top - bottom;
     const int nc = I->ncomp;
     const bool sub_x = nc == 3 && I->hmax == 2, sub_y = nc == 3 && I->vmax == 2;
     // libjpeg filters only planes wider than 2 samples, narrower ones are replicated
@@ -42,8 +63,6 @@ int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int lef
         plane_off[k] = plane_bytes;
         plane_bytes += (size_t)I->blocks_x[k] * 8 * I->blocks_y[k] * 8;
     }
-    if (int rc = grow(c, &B.d_coef, &B.coef_cap, (size_t)I->coef_count)) return rc;
-    if (int rc = grow(c, &B.d_planes, &B.planes_cap, plane_bytes)) return rc;
     JpegIdctArgs& A = *Ap;
     A = JpegIdctArgs{};
     const int x0 = left, x1 = I->width - right - 1, y0 = top, y1 = I->height - bottom - 1;   // first / last pixel kept
@@ -64,8 +83,8 @@ int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int lef
         A.first[k + 1] = A.first[k] + A.nbx[k] * nby;
         A.blocks_x[k] = I->blocks_x[k];
         A.pitch[k] = I->blocks_x[k] * 8;
-        A.coef[k] = B.d_coef + I->coef_offset[k];
-        A.plane[k] = B.d_planes + plane_off[k];
+        A.coef[k] = d_coef + I->coef_offset[k];
+        A.plane[k] = d_planes + plane_off[k];
         memcpy(A.quant[k], I->quant[k], sizeof(A.quant[k]));
         out->plane[k] = A.plane[k];
         out->pitch[k] = A.pitch[k];
@@ -76,7 +95,6 @@ int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int lef
     out->mode = !sub_x ? 0 : (sub_y ? (fancy ? 2 : 4) : (fancy ? 1 : 3));
     out->left = left;
     out->top = top;
-    return ICELK_OK;
 }
 
 int jpeg_idct_on(Ctx* c, hipStream_t st, const JpegIdctArgs& A)

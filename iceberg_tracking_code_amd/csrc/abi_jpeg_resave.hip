@@ -42,7 +42,7 @@ int jpeg_resave_check(Ctx* c, int w, int h, int quality)
 // The forward kernel on stream st: the w x h image at d_src (rows 3 w bytes apart) -> the coefficients of the re-saved
 // file that I describes (resave_info) at d_coef.  The synchronous calls run it on the handle's re-save job, a crop job
 // (abi_jpeg_crop.hip) on its own buffers.
-int jpeg_fwd_on(Ctx* c, hipStream_t st, const uint8_t* d_src, int16_t* d_coef, int w, int h, const icelk_jpeg_info_t& I)
+static JpegFwdArgs fwd_args(const uint8_t* d_src, int16_t* d_coef, int w, int h, const icelk_jpeg_info_t& I)
 {
     JpegFwdArgs F{};
     F.rgb = d_src;
@@ -59,11 +59,29 @@ int jpeg_fwd_on(Ctx* c, hipStream_t st, const uint8_t* d_src, int16_t* d_coef, i
             F.quant[t][i] = I.quant[t][i];
             F.recip[t][i] = fwd::reciprocal((uint32_t)I.quant[t][i] << 3);
         }
+    return F;
+}
+
+int jpeg_fwd_on(Ctx* c, hipStream_t st, const uint8_t* d_src, int16_t* d_coef, int w, int h, const icelk_jpeg_info_t& I)
+{
+    const JpegFwdArgs F = fwd_args(d_src, d_coef, w, h, I);
     {
         ProfScope p(c, K_JPEG_FWD, st);
         launch_jpeg_fwd(st, F);
     }
     return check_launch(c, "jpeg_fwd");
+}
+
+// The fused form on stream st: the crop box of the decoded planes `O` describes (O.ow x O.oh at O.left, O.top) -> the
+// coefficients of the re-saved file that I describes at d_coef, with no R G B image in between.
+int jpeg_crop_fwd_on(Ctx* c, hipStream_t st, const JpegOutArgs& O, int16_t* d_coef, const icelk_jpeg_info_t& I)
+{
+    const JpegFwdArgs F = fwd_args(nullptr, d_coef, O.ow, O.oh, I);
+    {
+        ProfScope p(c, K_JPEG_CROP_FWD, st);
+        launch_jpeg_crop_fwd(st, O, F);
+    }
+    return check_launch(c, "jpeg_crop_fwd");
 }
 
 namespace {
@@ -191,6 +209,34 @@ int icelk_jpeg_resave_device_coefficients(icelk_t* h, const uint8_t* rgb, int w,
     JpegOutArgs O{};
     if (int rc = resave_forward(c, w, h_, quality, &I, &O, false)) return rc;
     HIPCHK(c, hipMemcpyAsync(coef, c->jpeg.resave.d_coef, (size_t)I.coef_count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ICELK_OK;
+}
+
+int icelk_jpeg_crop_fwd_device_coefficients(icelk_t* h, const uint8_t* data, uint64_t len, int crop_left, int crop_top, int crop_right,
+                                            int crop_bottom, int quality, int16_t* coef, uint64_t capacity)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!data || !coef) FAIL(c, ICELK_EARG, "null JPEG file or coefficient buffer");
+    icelk_jpeg_info_t I, R;
+    if (int rc = icelk_jpeg_describe(data, len, &I)) FAIL(c, rc, jpeg_open_error(rc));
+    int w = 0, h_ = 0;
+    if (int rc = cropped_size(c, &I, crop_left, crop_top, crop_right, crop_bottom, &w, &h_)) return rc;
+    if (int rc = jpeg_resave_check(c, w, h_, quality)) return rc;
+    resave_info(w, h_, quality, &R);
+    if (capacity < R.coef_count) FAIL(c, ICELK_ECAP, "coefficient buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = jpeg_huff_device(c, data, len, &I)) return rc;
+    JpegOutArgs O{};
+    if (int rc = jpeg_planes(c, &I, nullptr, crop_left, crop_top, crop_right, crop_bottom, &O, true)) return rc;
+    Ctx::JpegJob& B = c->jpeg.resave;
+    if (int rc = grow(c, &B.d_coef, &B.coef_cap, (size_t)R.coef_count)) return rc;
+    if (int rc = jpeg_crop_fwd_on(c, c->stream, O, B.d_coef, R)) return rc;
+    c->jpeg.enc.resaved = true;   // as resave_forward: these are the handle's most recent re-saved coefficients
+    c->jpeg.enc.stream_ok = false;
+    c->jpeg.enc.info = R;
+    HIPCHK(c, hipMemcpyAsync(coef, B.d_coef, (size_t)R.coef_count * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ICELK_OK;
 }

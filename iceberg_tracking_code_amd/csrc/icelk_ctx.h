@@ -135,6 +135,13 @@ struct Ctx {
         bool have_scan = false;          // h_out holds the scan (scan_len bytes): finish has done its waiting
         uint64_t scan_len = 0;
         icelk_jpeg_crop_stats_t cstats{};
+        // ---- slot-bound re-save jobs only (icelk_upload_jpeg_file_async_resave): the crop box of d_planes goes through the
+        // fused kernel into d_rcoef, whose inverse DCT needs planes of its own before the gray of the slot is made of them
+        bool resave = false, want_file = false;
+        uint8_t* d_planes2 = nullptr;
+        size_t planes2_cap = 0;
+        JpegIdctArgs ridct{};            // of the re-saved file, whole
+        JpegOutArgs rout{};
     };
     struct Jpeg {
         JpegJob sync;                                          // the working set of every synchronous call
@@ -537,6 +544,9 @@ int jpeg_host_decode(const uint8_t* data, size_t len, int16_t* coef, uint64_t ca
 int check_crop_box(Ctx* c, const icelk_jpeg_info_t& I, int left, int top, int right, int bottom, int* w, int* h);
 int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* A,
                     JpegOutArgs* out);
+size_t jpeg_plane_bytes(const icelk_jpeg_info_t& I);
+void jpeg_plane_layout(const icelk_jpeg_info_t& I, int left, int top, int right, int bottom, int16_t* d_coef, uint8_t* d_planes,
+                       JpegIdctArgs* A, JpegOutArgs* out);
 int jpeg_idct_on(Ctx* c, hipStream_t st, const JpegIdctArgs& A);
 int jpeg_gray_on(Ctx* c, hipStream_t st, JpegOutArgs O, const Slot& s, int gray_variant);
 int planes_to_gray_slot(Ctx* c, int slot, const JpegOutArgs& O, int gray_variant);
@@ -556,6 +566,7 @@ int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_
 void jpeg_resave_destroy(Ctx* c);
 int jpeg_resave_check(Ctx* c, int w, int h, int quality);
 int jpeg_fwd_on(Ctx* c, hipStream_t st, const uint8_t* d_src, int16_t* d_coef, int w, int h, const icelk_jpeg_info_t& I);
+int jpeg_crop_fwd_on(Ctx* c, hipStream_t st, const JpegOutArgs& O, int16_t* d_coef, const icelk_jpeg_info_t& I);
 // abi_jpeg_enc.hip
 void jpeg_enc_destroy(Ctx* c);
 void jpeg_enc_free(Ctx::JpegEnc& E);
@@ -571,6 +582,10 @@ int jpeg_stage_file(Ctx* c, Ctx::JpegJob& B, const JpegIndex& X, size_t seg_byte
 bool jpeg_verdict_here(const Ctx::JpegJob& B);
 int jpeg_await_verdict(Ctx* c, Ctx::JpegJob& B);
 void jpeg_huff_stats_of(const Ctx::JpegJob& B, icelk_jpeg_huff_stats_t* st);
+// abi_jpeg_crop.hip
+int jpeg_budget_buffers(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L);
+int jpeg_encode_budgeted(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L);
+int jpeg_fetch_scan(Ctx* c, Ctx::JpegJob& B, uint64_t n, bool again);
 // abi_plot.hip
 void plot_destroy(Ctx* c);
 // abi_map.hip

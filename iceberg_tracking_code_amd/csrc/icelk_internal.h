@@ -73,6 +73,7 @@ enum KernelId {
     K_JPEG_ENC_STUFF_BUDGET,
     K_JPEG_CROP_RGB,           // the crop box of the decoded planes as R G B into the job
     K_JPEG_CROP_VERDICT,
+    K_JPEG_CROP_FWD,           // the crop box of the decoded planes straight to the re-save's coefficients (k_jpeg_fwd.hip)
     K_PLOT_BACKGROUND,         // the segment picture (k_plot.hip): area-averaged gray plane
     K_PLOT_CLEAR,              // ... the count planes zeroed
     K_PLOT_SCATTER,            // ... lines and dots counted
@@ -155,6 +156,9 @@ struct JpegFwdArgs {
     uint32_t recip[2][64];    // fwd::reciprocal(8 * quant)
 };
 void launch_jpeg_fwd(hipStream_t s, const JpegFwdArgs& A);
+// The same from the crop box of a decoded file's planes (O: planes, chroma mode, left, top; O.dst is not used), fused: the
+// crop is A.w x A.h, A.rgb is not read.  The pixels are k_jpeg_out's (jpeg_rgb.h).
+void launch_jpeg_crop_fwd(hipStream_t s, const JpegOutArgs& O, const JpegFwdArgs& A);
 
 // The JPEG writer's entropy coder (k_jpeg_enc.hip; the arithmetic is jpeg_enc.h).  All pointers are device memory.
 constexpr int kJpegEncGroup = 64;        // blocks (lanes) per workgroup of count and pack: one wave
@@ -181,7 +185,8 @@ void launch_jpeg_enc_stuff(hipStream_t s, const uint32_t* packed, uint32_t nbyte
 void launch_jpeg_enc_pack_budget(hipStream_t s, const JpegEncArgs& A, uint32_t cap);
 void launch_jpeg_enc_ff_budget(hipStream_t s, const uint32_t* packed, const uint32_t* ctl, uint32_t cap, uint32_t* wg_ff);
 void launch_jpeg_enc_stuff_budget(hipStream_t s, const uint32_t* packed, const uint32_t* ctl, uint32_t cap, const uint32_t* wg_off, uint8_t* out);
-// last in a crop job's chain: the words of JpegVerdictWord (below) to the job's pinned words, the sequence word last
+// last in a crop job's chain: the words of JpegVerdictWord (below) to the job's pinned words, the sequence word last.
+// enc_ctl NULL: no file was asked for (a slot-bound re-save job without one), the coder's words say enc::kNotAsked
 void launch_jpeg_crop_verdict(hipStream_t s, const uint32_t* huff_ctl, int max_rounds, const uint32_t* enc_ctl, uint32_t cap, uint32_t* host_words,
                               uint32_t seq);
 

@@ -193,7 +193,7 @@ constexpr int kChunkBytes = 64;          // bytes of the packed stream one lane 
 constexpr int kChunksPerGroup = 256;     // lanes of a workgroup of ff / stuff: 16 KiB of the packed stream
 constexpr int kMinBytesPerBlock = 1, kMaxBytesPerBlock = 2 * ((kMaxBlockBits + 7) / 8);   // 416: every byte of a block stuffed
 constexpr int kDefaultBytesPerBlock = 48;
-enum Verdict : uint32_t { kCoded = 1, kOverBudget = 2, kInvalid = 3 };
+enum Verdict : uint32_t { kNotAsked = 0, kCoded = 1, kOverBudget = 2, kInvalid = 3 };
 
 // blocks * kMaxBlockBits < 2^32 (layout_of) and bytes_per_block <= 416: below 2^31
 ICELK_ENC_FN uint32_t budget_cap(uint32_t blocks, int bytes_per_block) { return blocks * (uint32_t)bytes_per_block; }

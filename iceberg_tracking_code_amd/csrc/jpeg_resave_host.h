@@ -76,11 +76,17 @@ inline void block_host(const uint8_t* s, size_t pitch, const uint16_t* q, int16_
     }
 }
 
-// the coefficients of the file Pillow would write for the w x h image at rgb, and its descriptor: icelk.h says the rest
-inline int coefficients_host(const uint8_t* rgb, int w, int h, int stride, int quality, icelk_jpeg_info_t* info, int16_t* coef,
-                             uint64_t capacity)
+struct Pixel {
+    int r, g, b;
+};
+
+// The coefficients of the file Pillow would write for a w x h image, and its descriptor.  px(y, x): the 8-bit R G B of image
+// pixel (x, y), 0 <= x < w and 0 <= y < h -- interleaved bytes (coefficients_host below) or the crop box of a decoded file's
+// planes (jpeg_crop_fwd_host.h); the padding of jpeg_fwd.h is a clamped coordinate here, as in the kernels.
+template <typename Px>
+inline int coefficients_from(Px px_of, int w, int h, int quality, icelk_jpeg_info_t* info, int16_t* coef, uint64_t capacity)
 {
-    if (!rgb || !info || !size_ok(w, h, quality) || stride < 3 * w) return ICELK_EARG;
+    if (!info || !size_ok(w, h, quality)) return ICELK_EARG;
     resave_info(w, h, quality, info);
     if (!coef) return ICELK_OK;   // the descriptor only
     if (capacity < info->coef_count) return ICELK_ECAP;
@@ -96,21 +102,21 @@ inline int coefficients_host(const uint8_t* rgb, int w, int h, int stride, int q
     } catch (...) {
         return ICELK_ENOMEM;
     }
-    auto px = [&](int y, int x) { return rgb + (size_t)y * stride + 3 * (size_t)(x < w ? x : w - 1); };
+    auto px = [&](int y, int x) { return px_of(y, x < w ? x : w - 1); };
     for (int qy = 0; qy < I.mcus_y * 8; qy++) {
         const fwd::QuadRows R = fwd::quad_rows(qy, h);
         for (int qx = 0; qx < I.mcus_x * 8; qx++) {
             for (int k = 0; k < 4; k++) {
                 const int ly = 2 * qy + (k >> 1), lx = 2 * qx + (k & 1);
                 if (ly >= rby * 8 || lx >= rbx * 8) continue;
-                const uint8_t* p = px((k >> 1) ? R.y1 : R.y0, lx);
-                Y[ly * lp + lx] = (uint8_t)fwd::luma(p[0], p[1], p[2]);
+                const Pixel p = px((k >> 1) ? R.y1 : R.y0, lx);
+                Y[ly * lp + lx] = (uint8_t)fwd::luma(p.r, p.g, p.b);
             }
-            const uint8_t *a = px(R.c0, 2 * qx), *b = px(R.c0, 2 * qx + 1), *d = px(R.c1, 2 * qx), *e = px(R.c1, 2 * qx + 1);
-            Cb[qy * cp + qx] = (uint8_t)fwd::downsample(fwd::chroma_b(a[0], a[1], a[2]), fwd::chroma_b(b[0], b[1], b[2]),
-                                                        fwd::chroma_b(d[0], d[1], d[2]), fwd::chroma_b(e[0], e[1], e[2]), qx);
-            Cr[qy * cp + qx] = (uint8_t)fwd::downsample(fwd::chroma_r(a[0], a[1], a[2]), fwd::chroma_r(b[0], b[1], b[2]),
-                                                        fwd::chroma_r(d[0], d[1], d[2]), fwd::chroma_r(e[0], e[1], e[2]), qx);
+            const Pixel a = px(R.c0, 2 * qx), b = px(R.c0, 2 * qx + 1), d = px(R.c1, 2 * qx), e = px(R.c1, 2 * qx + 1);
+            Cb[qy * cp + qx] = (uint8_t)fwd::downsample(fwd::chroma_b(a.r, a.g, a.b), fwd::chroma_b(b.r, b.g, b.b),
+                                                        fwd::chroma_b(d.r, d.g, d.b), fwd::chroma_b(e.r, e.g, e.b), qx);
+            Cr[qy * cp + qx] = (uint8_t)fwd::downsample(fwd::chroma_r(a.r, a.g, a.b), fwd::chroma_r(b.r, b.g, b.b),
+                                                        fwd::chroma_r(d.r, d.g, d.b), fwd::chroma_r(e.r, e.g, e.b), qx);
         }
     }
     int16_t* L = coef + I.coef_offset[0];
@@ -136,6 +142,19 @@ inline int coefficients_host(const uint8_t* rgb, int w, int h, int stride, int q
                     dst[0] = L[((2 * my + (from >> 1)) * lbx + 2 * mx + (from & 1)) * 64];
                 }
     return ICELK_OK;
+}
+
+// the coefficients of the file Pillow would write for the w x h image at rgb, and its descriptor: icelk.h says the rest
+inline int coefficients_host(const uint8_t* rgb, int w, int h, int stride, int quality, icelk_jpeg_info_t* info, int16_t* coef,
+                             uint64_t capacity)
+{
+    if (!rgb || stride < 3 * w) return ICELK_EARG;
+    return coefficients_from(
+        [&](int y, int x) {
+            const uint8_t* p = rgb + (size_t)y * stride + 3 * (size_t)x;
+            return Pixel{p[0], p[1], p[2]};
+        },
+        w, h, quality, info, coef, capacity);
 }
 
 }  // namespace resave

@@ -11,6 +11,7 @@
 //
 // The planes go through HBM between the two kernels (18 MB at 12 MP 4:2:0); each is one pass over its data.
 #include "icelk_internal.h"
+#include "jpeg_rgb.h"
 
 namespace icelk {
 
@@ -57,7 +58,7 @@ __device__ __forceinline__ void idct8(int (&xs)[8])
     xs[4] = (int)(a3 - o0 + half) >> shift;
 }
 
-__device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+using rgbpx::clamp255;
 
 // ------------------------------------------------------------------------------------------------
 // Inverse DCT.  8 lanes per block, 32 blocks per 256-thread workgroup.  Lane r of a block loads row r of the
@@ -124,77 +125,13 @@ void launch_jpeg_idct(hipStream_t s, const JpegIdctArgs& A)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Upsampling + colour + crop (+ gray).  The chroma sample at image position (X, Y), from a plane of cw x ch samples:
-//   mode 0  no subsampling
-//   mode 1  2x1 "fancy":  (3 near + neighbour + 1) >> 2 at even X (neighbour on the left), + 2 at odd X (on the right)
-//   mode 2  2x2 "fancy":  column sums 3 near row + far row (above at even Y, below at odd Y), then
-//           (3 s[j] + s[j-1] + 8) >> 4 at even X, (3 s[j] + s[j+1] + 7) >> 4 at odd X
-//   mode 3 / 4  2x1 / 2x2 by plain replication: what libjpeg does for planes of 2 samples' width or less
-// Neighbours beyond the plane's edge are the edge sample.
-//
-// A lane makes 4 neighbouring output pixels.  They need 4 luma samples and, in every mode, at most 4 neighbouring
-// chroma samples per row: each group of 4 is ONE dword load at whatever byte address the crop puts it (gfx950 under HSA
-// takes unaligned vector loads).  Loaded byte by byte -- 36 loads per lane at 4:2:0 instead of 5 -- the kernel is bound
-// by the address unit: 53.8 against 26.8 us per 12 MP frame.  Groups that reach over an edge of the plane are loaded
-// byte by byte with the column clamped.
+// Upsampling + colour + crop (+ gray).  The pixels are jpeg_rgb.h's (chroma modes, edge rules and the colour matrix are
+// stated there, and the fused crop-and-forward kernel of k_jpeg_fwd.hip runs the same functions): a lane makes 4 neighbouring
+// output pixels from 4 luma samples and at most 4 neighbouring chroma samples per row, each group ONE dword load.
 // ------------------------------------------------------------------------------------------------
-typedef uint32_t u32_a1 __attribute__((aligned(1)));
-
-// v[k] = row[clamp(c + k, 0, n - 1)], k = 0..3
-__device__ __forceinline__ void load4(const uint8_t* __restrict__ row, int c, int n, int (&v)[4])
-{
-    if (c >= 0 && c + 3 < n) {
-        const uint32_t w = *reinterpret_cast<const u32_a1*>(row + c);
-        v[0] = w & 255;
-        v[1] = (w >> 8) & 255;
-        v[2] = (w >> 16) & 255;
-        v[3] = w >> 24;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = row[min(max(c + k, 0), n - 1)];
-    }
-}
-
-// the chroma samples of image pixels X0 .. X0+3 in row Y
-template <int mode>
-__device__ __forceinline__ void chroma4(const uint8_t* __restrict__ p, int pitch, int cw, int ch, int X0, int Y, int (&out)[4])
-{
-    if (mode == 0) {
-        load4(p + (size_t)Y * pitch, X0, cw, out);
-        return;
-    }
-    const int odd = X0 & 1;
-    if (mode == 3 || mode == 4) {
-        int t[4];
-        load4(p + (size_t)(mode == 4 ? Y >> 1 : Y) * pitch, X0 >> 1, cw, t);
-#pragma unroll
-        for (int i = 0; i < 4; i++) out[i] = odd ? t[(i + 1) >> 1] : t[i >> 1];
-        return;
-    }
-    // the window of 4 samples from one left of pixel X0's own: every pixel's sample and neighbour lie inside
-    const int c0 = (X0 >> 1) - 1;
-    int t[4];
-    if (mode == 1) {
-        load4(p + (size_t)Y * pitch, c0, cw, t);
-    } else {
-        const int i = Y >> 1;
-        const int fi = (Y & 1) ? min(i + 1, ch - 1) : max(i - 1, 0);
-        int f[4];
-        load4(p + (size_t)i * pitch, c0, cw, t);
-        load4(p + (size_t)fi * pitch, c0, cw, f);
-#pragma unroll
-        for (int k = 0; k < 4; k++) t[k] = 3 * t[k] + f[k];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        // window index of the pixel's own sample and of its neighbour, for even and for odd X0
-        const int je = 1 + (i >> 1), jo = 1 + ((i + 1) >> 1);
-        const int ne = (i & 1) ? je + 1 : je - 1, no = ((i + 1) & 1) ? jo + 1 : jo - 1;
-        const int own = odd ? t[jo] : t[je], nb = odd ? t[no] : t[ne];
-        const int xodd = (i + odd) & 1;
-        out[i] = mode == 1 ? (3 * own + nb + 1 + xodd) >> 2 : (3 * own + nb + 8 - xodd) >> 4;
-    }
-}
+using rgbpx::chroma4;
+using rgbpx::load4;
+typedef rgbpx::u32_a1 u32_a1;
 
 // gray: one dword stored per lane (256 B per wave and row); rgb: 12 bytes
 template <int mode, bool rgb>
@@ -213,10 +150,8 @@ __global__ __launch_bounds__(256) void k_jpeg_out(JpegOutArgs A)
     uint32_t px[4];   // gray: px[0] holds the 4 pixels; rgb: R | G << 8 | B << 16 each
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        const int u = cb[i] - 128, v = cr[i] - 128;
-        const int R = clamp255(lum[i] + ((91881 * v + 32768) >> 16));
-        const int G = clamp255(lum[i] + ((-22554 * u - 46802 * v + 32768) >> 16));
-        const int B = clamp255(lum[i] + ((116130 * u + 32768) >> 16));
+        const rgbpx::Rgb c = rgbpx::colour(lum[i], cb[i], cr[i]);
+        const int R = c.r, G = c.g, B = c.b;
         // gray: channel 0 (R) takes the "B" weight, as k_bgr2gray gives it to the first byte of PIL's RGB pixels
         if (rgb) px[i] = (uint32_t)R | (uint32_t)G << 8 | (uint32_t)B << 16;
         else px[i] = (uint32_t)((R * A.k0 + G * A.k1 + B * A.k2 + half) >> A.shift);

@@ -325,10 +325,14 @@ __global__ __launch_bounds__(64) void k_jpeg_crop_verdict(const uint32_t* __rest
 {
     jpeg_huff_verdict_words(huff_ctl, max_rounds, out);
     if (threadIdx.x != 0) return;
-    const uint32_t bits = enc_ctl[JE_TOTAL_BITS], invalid = enc_ctl[JE_INVALID], ff = enc_ctl[JE_FF_TOTAL];
-    const uint32_t verdict = enc::budget_verdict(bits, invalid, ff, cap);
+    uint32_t verdict = enc::kNotAsked, len = 0;
+    if (enc_ctl) {   // uniform: a kernel argument
+        const uint32_t bits = enc_ctl[JE_TOTAL_BITS], invalid = enc_ctl[JE_INVALID], ff = enc_ctl[JE_FF_TOTAL];
+        verdict = enc::budget_verdict(bits, invalid, ff, cap);
+        if (verdict == enc::kCoded) len = enc::packed_bytes(bits) + ff;
+    }
     out[JV_ENC_VERDICT] = verdict;
-    out[JV_ENC_LEN] = verdict == enc::kCoded ? enc::packed_bytes(bits) + ff : 0u;
+    out[JV_ENC_LEN] = len;
     __threadfence_system();
     __hip_atomic_store(out + JV_SEQ, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }

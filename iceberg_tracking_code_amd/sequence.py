@@ -15,7 +15,8 @@ the pool only reads the files and the device Huffman-decodes them as well (`Cont
 `pipeline=True` on top of that the files are decoded ahead of their frame, beside the tracker steps of the frames in
 front of them (`SegmentTracker.prefetch_jpeg`).  Either way
 pixel values are those of the original photo unless `resave` asks for the reference's lossy re-save of the crop, which
-then runs on the device between crop and gray conversion (csrc/k_jpeg_fwd.hip; not with `pipeline=True`); gray conversion, detection,
+then runs on the device between crop and gray conversion (csrc/k_jpeg_fwd.hip; with `pipeline=True` as part of the job
+that decodes the file ahead, `resave_ahead=True`); gray conversion, detection,
 tracking, filtering and the track table are the device-resident loop of `SegmentTracker`; the mask is rasterised on
 the device from the polygon (`icelk_set_mask_polygon`) or uploaded.  Output files carry the reference's names and
 arrays.
@@ -72,7 +73,7 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                          mask_polygon=None, feature_params=None, lk_params=None, decode_threads=4, decode_ahead=6,
                          gray_variant=4, device=0, on_segment=None, save=True, decoder="pil", huffman="host", pipeline=False,
                          n_slots=PIPELINE_SLOTS, resave=None, save_crops=None, plots=None, plot_width=PLOT_WIDTH,
-                         plot_quality=PLOT_QUALITY):
+                         plot_quality=PLOT_QUALITY, resave_ahead=False):
     """Track one day's photos.  Returns [(npz path, tracks (n, T+1, 2) f32, trackquality (n, T) f32)] of the
     segments that pass the time-gap rule, in order.
 
@@ -91,7 +92,8 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
     n_slots        frame slots of the pipelined driver, at least 5
     resave         None: pixel values are those of the photos.  "reference": the tracker sees what the reference's tracker
                    sees, the crop saved by Pillow as a new JPEG (quality 75, s1:272) and opened again -- reproduced on the
-                   device, no file is written; an int: that quality.  Not with pipeline=True.  A file the device decoder
+                   device, no file is written; an int: that quality.  With pipeline=True only together with resave_ahead=True.
+                   A file the device decoder
                    does not take goes through PIL, that file only, and is re-saved on the device all the same.  The
                    two-pass route gets the same tracks with pipeline=True: `crop.crop_image_sequence` writes the re-saved
                    crops first, and this function then runs on those files with no crop and no resave
@@ -99,7 +101,12 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                    reference's crop step writes into its target folder (`Image.open(p).crop(box).save(out)`, the source's
                    comment carried over), entropy-coded on the device (csrc/k_jpeg_enc.hip) right after the upload and
                    written on the calling thread once the photo's step is enqueued; once per photo, however many entries
-                   of startlist visit it.  Not with pipeline=True.  The tracks do not change
+                   of startlist visit it.  With pipeline=True only together with resave_ahead=True.  The tracks do not
+                   change
+    resave_ahead   with pipeline=True and resave: the re-save -- and with save_crops the coding of the crop's file -- is part
+                   of the job that decodes a photo ahead of its frame (`SegmentTracker.prefetch_jpeg(resave=...)`,
+                   icelk_upload_jpeg_file_async_resave): one pass over the photos gives the reference's tracks and its crop
+                   folder.  Same outputs as pipeline=False with the same options
     plots          a directory (created) that receives, for every segment that passes the time-gap rule, the picture the
                    reference draws of it (s1:397-434): the segment's last frame `plot_width` pixels wide, its tracks as red
                    lines, their ends as red dots, '<last photo> <track_len * track_len_sec>/<track_len_sec>' in a corner --
@@ -119,12 +126,14 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
         raise ValueError('pipeline=True needs decoder="device" and huffman="device"')
     from .jpeg import resave_quality
     resave = resave_quality(resave)
-    if pipeline and resave is not None:
-        raise ValueError("resave is not available with pipeline=True")
+    if resave_ahead and not (pipeline and resave is not None):
+        raise ValueError("resave_ahead=True needs pipeline=True and resave")
+    if pipeline and resave is not None and not resave_ahead:
+        raise ValueError("resave is not available with pipeline=True (unless resave_ahead=True)")
     if save_crops is not None and resave is None:
         raise ValueError("save_crops needs resave: the files written are the re-saved crops")
-    if save_crops is not None and pipeline:
-        raise ValueError("save_crops is not available with pipeline=True")
+    if save_crops is not None and pipeline and not resave_ahead:
+        raise ValueError("save_crops is not available with pipeline=True (unless resave_ahead=True)")
     if pipeline and int(n_slots) < 5:
         raise ValueError("n_slots must be at least 5")
     imagelist = [str(p) for p in imagelist]
@@ -159,6 +168,7 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                                      mask_polygon=mask_polygon, device=device, n_slots=int(n_slots) if pipeline else 3)
                 pending = [pool.submit(load, p) for p in names[:decode_ahead]]
                 fed = 0                                   # pipeline=True: frames handed to the tracker's prefetch queue
+                ahead_kw = {}                             # ... and the options each of those in flight was handed with
                 for counter in range(len(names)):
                     if pipeline:
                         # previous and current frame stay resident, every other slot holds a frame on its way
@@ -166,19 +176,29 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                             frame = pending.pop(0).result()
                             if fed + decode_ahead < len(names):
                                 pending.append(pool.submit(load, names[fed + decode_ahead]))
+                            kw = dict(variant=gray_variant, crop=crop)
+                            if resave_ahead:
+                                kw.update(resave=resave)
+                            if save_crops is not None:
+                                frame, comment = frame
+                                if names[fed] not in written:
+                                    kw.update(crop_file=os.path.join(save_crops, os.path.basename(names[fed])), comment=comment)
+                                    written.add(names[fed])
+                            ahead_kw[fed] = kw
                             if isinstance(frame, bytes):
                                 try:
-                                    trk.prefetch_jpeg(frame, variant=gray_variant, crop=crop)
+                                    trk.prefetch_jpeg(frame, **kw)
                                 except ValueError:        # what the host sees of an unsupported or damaged file ...
-                                    trk.prefetch_bgr(_load(names[fed], "pixels", False), variant=gray_variant, crop=crop)
+                                    trk.prefetch_bgr(_load(names[fed], "pixels", False), **kw)
                             else:
-                                trk.prefetch_bgr(frame, variant=gray_variant, crop=crop)
+                                trk.prefetch_bgr(frame, **kw)
                             fed += 1
                         try:
                             seg = trk.push_prefetched()
                         except ValueError:                # ... and what only the decoder sees: PIL has the word
-                            trk.replace_prefetched_bgr(_load(names[counter], "pixels", False), variant=gray_variant, crop=crop)
+                            trk.replace_prefetched_bgr(_load(names[counter], "pixels", False), **ahead_kw[counter])
                             seg = trk.push_prefetched()
+                        del ahead_kw[counter]
                     else:
                         frame = pending.pop(0).result()
                         if counter + decode_ahead < len(names):

@@ -78,6 +78,7 @@ class SegmentTracker:
         self.n_detected = 0
         self._prefetched = []     # slots holding frames whose upload was started ahead of time
         self._jpeg_jobs = set()   # ... those of them whose JPEG file is still to be finished (`prefetch_jpeg`)
+        self._crop_files = {}     # prefetch slot -> (path, comment, the crop file's bytes or None while its job is in flight)
         self.lookahead = bool(lookahead)
         self.pair_launch = bool(pair_launch) and self.lookahead   # see `_step`: joint launch across a segment change
         self._pyr_ahead = set()   # slots whose pyramid was enqueued ahead of their step
@@ -179,32 +180,48 @@ class SegmentTracker:
         last = self._prefetched[-1] if self._prefetched else self.cur
         return (last + 1) % self.n_slots
 
-    def prefetch_jpeg(self, data, variant=4, crop=None):
+    def prefetch_jpeg(self, data, variant=4, crop=None, resave=None, crop_file=None, comment=None):
         """Start the decoding of a FUTURE frame from the bytes of its JPEG file (`Context.upload_jpeg_file_async`): it
         runs on the device beside the steps of the frames in front of it.  Slots, order and the n_slots - 2 limit are
         `prefetch_pinned`'s.  What the host can see of a bad file raises here (ValueError), and no slot is taken; the
-        rest comes out of `push_prefetched`."""
+        rest comes out of `push_prefetched`.  `resave`, `crop_file`, `comment`: as `push_bgr` -- the re-save and, with
+        `crop_file`, the coding of the crop's file are part of the enqueued job; `push_prefetched` writes the file."""
+        if crop_file is not None and resave is None:
+            raise ValueError("crop_file needs resave: the file written is the re-saved crop")
         s = self._next_prefetch_slot()
-        self.ctx.upload_jpeg_file_async(s, data, variant, crop)
+        self.ctx.upload_jpeg_file_async(s, data, variant, crop, resave, crop_file is not None)
         self._prefetched.append(s)
         self._jpeg_jobs.add(s)
+        if crop_file is not None:
+            self._crop_files[s] = (crop_file, comment, None)
 
-    def prefetch_bgr(self, frame, variant=4, crop=None):
+    def _upload_bgr_ahead(self, s, frame, variant, crop, resave, crop_file, comment):
+        """The synchronous `upload_bgr(resave=)` into prefetch slot s.  The crop's file is taken at once -- the handle's "most
+        recent re-save" is overwritten by the next one -- and its bytes are held until the frame is pushed."""
+        if crop_file is not None and resave is None:
+            raise ValueError("crop_file needs resave: the file written is the re-saved crop")
+        self._crop_files.pop(s, None)
+        self.ctx.upload_bgr(s, frame, variant, crop, resave)
+        if crop_file is not None:
+            self._crop_files[s] = (crop_file, comment, self.ctx.jpeg_resave_file(comment))
+
+    def prefetch_bgr(self, frame, variant=4, crop=None, resave=None, crop_file=None, comment=None):
         """A host-decoded frame into the next prefetch slot (a plain `upload_bgr`): the file of a folder that the device
-        decoder does not take, between files that it does."""
+        decoder does not take, between files that it does.  `resave`, `crop_file`, `comment`: as `push_bgr`."""
         s = self._next_prefetch_slot()
-        self.ctx.upload_bgr(s, frame, variant, crop)
+        self._upload_bgr_ahead(s, frame, variant, crop, resave, crop_file, comment)
         self._prefetched.append(s)
 
-    def replace_prefetched_bgr(self, frame, variant=4, crop=None):
+    def replace_prefetched_bgr(self, frame, variant=4, crop=None, resave=None, crop_file=None, comment=None):
         """After `push_prefetched` has raised for the JPEG file at the head of the queue: fill its slot from the
-        host-decoded frame instead; `push_prefetched` may then be called again."""
+        host-decoded frame instead; `push_prefetched` may then be called again.  `resave`, `crop_file`, `comment`: as
+        `push_bgr`."""
         if not self._prefetched:
             raise RuntimeError("no prefetched frame")
         s = self._prefetched[0]
         if s in self._jpeg_jobs:
             raise RuntimeError("the frame at the head of the queue has not failed")
-        self.ctx.upload_bgr(s, frame, variant, crop)
+        self._upload_bgr_ahead(s, frame, variant, crop, resave, crop_file, comment)
 
     def push_prefetched(self, wait=True):
         if not self._prefetched:
@@ -214,7 +231,12 @@ class SegmentTracker:
             # the verdict on the file, the host decoder if it is asked for.  A file that raises leaves the queue as it is
             # and its slot empty (`replace_prefetched_bgr`)
             self._jpeg_jobs.discard(s)
-            self.ctx.jpeg_async_finish(s)
+            crop_file, comment, _ = self._crop_files.pop(s, (None, None, None))
+            if crop_file is None:
+                self.ctx.jpeg_async_finish(s)
+            else:
+                self._crop_files[s] = (crop_file, comment, self.ctx.jpeg_async_finish_file(s, comment)[0])
+        crop_file, _, data = self._crop_files.pop(s, (None, None, None))
         self._prefetched.pop(0)
         q = self._prefetched
         # nothing is built or detected ahead on a frame whose verdict is still out: the list ends in front of it
@@ -223,7 +245,9 @@ class SegmentTracker:
             if s_k in self._jpeg_jobs and self.ctx.jpeg_async_poll(s_k) != 1:
                 break
             ahead.append(s_k)
-        return self._step(s, wait, *ahead)
+        seg = self._step(s, wait, *ahead)
+        self._write_crop(crop_file, data)      # once the step is enqueued, as `_push_upload`
+        return seg
 
     def push_slot(self, slot, wait=True, *ahead):
         """Use a frame that already sits in `slot` (level 0 resident in HBM); its pyramid is rebuilt.
@@ -417,6 +441,7 @@ class SegmentTracker:
             except ValueError:
                 pass
         self._jpeg_jobs = set()
+        self._crop_files = {}
         if self._advanced:
             # a joint launch has already tracked the pair into the frame announced for the next step (it sat in its slot):
             # that frame counts as consumed -- it is never a detection frame (track_len >= 2 wherever pairs are joined)

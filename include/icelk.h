@@ -532,7 +532,12 @@ int icelk_jpeg_resave_device_coefficients(icelk_t* h, const uint8_t* rgb, int w,
  * arguments are the parents' plus quality.  The cropped R G B is made on the device (or copied there), re-saved by the
  * forward kernel and decoded by the kernels of the section above with the re-save's tables.  Checked before anything is
  * enqueued: quality 1 .. 100, cropped width >= 3, the sizes as in the parents.  Scratch buffers are allocated at first
- * use and freed with the handle.  There is no _resave form of icelk_upload_jpeg_file_async. */
+ * use and freed with the handle.  The look-ahead form is icelk_upload_jpeg_file_async_resave, below the crop job. */
+/* The coefficients as the fused crop-and-forward kernel makes them from a file's decoded planes, copied back (for tests):
+ * the file is decoded on the device as by icelk_upload_jpeg_file, its crop box goes through k_jpeg_crop_fwd, and coef gets
+ * the re-saved file's coefficients in the layout of icelk_jpeg_resave_coefficients_host for the cropped size.  No slot. */
+int icelk_jpeg_crop_fwd_device_coefficients(icelk_t* h, const uint8_t* data, uint64_t len, int crop_left, int crop_top, int crop_right,
+                                            int crop_bottom, int quality, int16_t* coef, uint64_t capacity);
 int icelk_upload_bgr_resave(icelk_t* h, int slot, const uint8_t* host, int w, int h_, int stride, int gray_variant, int quality);
 int icelk_upload_jpeg_resave(icelk_t* h, int slot, const icelk_jpeg_info_t* info, const int16_t* coef, int gray_variant,
                              int crop_left, int crop_top, int crop_right, int crop_bottom, int quality);
@@ -627,6 +632,30 @@ int icelk_jpeg_crop_finish(icelk_t* h, int ticket, const uint8_t* comment, uint6
                            uint64_t* len, icelk_jpeg_crop_stats_t* stats);
 /* Waits for what the job has enqueued and drops the ticket. */
 int icelk_jpeg_crop_cancel(icelk_t* h, int ticket);
+
+/* ---- the re-save ahead of the frame: icelk_upload_jpeg_file_async with the re-save, optionally with the file (opt-in) ----
+ * One enqueued job per photo gives the slot the frame the reference tracks on and, with want_file, the crop file it would
+ * have written: the host's share and checks are those of icelk_upload_jpeg_file_async plus those of
+ * icelk_upload_jpeg_file_resave (and, with want_file, of icelk_jpeg_crop_start), all before the slot is taken; then H2D
+ * copies, Huffman rounds and phases, the source's inverse DCT, the fused crop-and-forward kernel (the crop box of the planes
+ * straight to the re-saved file's coefficients), their inverse DCT into planes of the job's own, the gray into the slot's
+ * level 0, with want_file the budgeted coder under icelk_jpeg_crop_config, a verdict and the slot's events go out on a
+ * decode stream in one piece.  Memory per job in flight at 12 MP: the plain job's ~56 MB, plus 36 MB for the re-saved
+ * coefficients and 18 MB for the second planes -- no cropped R G B image (36 MB in a crop job) -- plus 27 MB for the coder
+ * with want_file.
+ * icelk_jpeg_async_poll is unchanged in meaning: 1 = the slot's frame is usable, decided by the decoder's verdict alone (a
+ * scan over its budget concerns only the file).  icelk_jpeg_async_finish works on such a job: on the decoder's fallback
+ * everything behind the Huffman phases runs again into the slot; a wanted file is dropped.  Errors, icelk_sync,
+ * icelk_destroy with jobs in flight and a busy slot (ICELK_ESTATE) are as in the plain form. */
+int icelk_upload_jpeg_file_async_resave(icelk_t* h, int slot, const uint8_t* data, uint64_t len, int gray_variant, int crop_left,
+                                        int crop_top, int crop_right, int crop_bottom, int quality, int want_file);
+/* icelk_jpeg_async_finish for a job started with want_file, and the file as icelk_jpeg_crop_finish returns it, by the same
+ * three routes (stats->route; the copy goes over the fetch stream).  ICELK_ECAP: out is too small (or NULL), *len says what
+ * the file takes, the slot's frame is final and the job stays with its slot: the call can be repeated (or
+ * icelk_jpeg_async_finish drops the file).  After ICELK_OK the job is released.  ICELK_ESTATE: no job in flight in the
+ * slot, or one started without want_file. */
+int icelk_jpeg_async_finish_file(icelk_t* h, int slot, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity,
+                                 uint64_t* len, icelk_jpeg_crop_stats_t* stats);
 
 /* ---- the picture of a segment (opt-in) -----------------------------------------------------------
  * At every segment it saves the reference draws a picture (s1:397-434, plot_switch = 1): the segment's last gray frame,

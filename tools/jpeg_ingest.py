@@ -13,6 +13,8 @@
     python tools/jpeg_ingest.py resave-file [--frames 24] [--out profiles/jpeg_resave_file.txt]  MI355X: ... written as files
     python tools/jpeg_ingest.py crop-folder [--frames 96] [--out profiles/jpeg_crop_folder.txt]  MI355X: the crop step on its own
     python tools/jpeg_ingest.py crop-folder-loop [--frames 24]                    MI355X: the calls for a kernel trace
+    python tools/jpeg_ingest.py resave-fused [--out profiles/jpeg_resave_pipeline.txt]      MI355X: the fused kernel against the pair
+    python tools/jpeg_ingest.py resave-pipeline [--frames 96] [--out ...]         MI355X: one pass against two (appends to the file)
 
 host    one thread, best of 5: `read_jpeg` (Huffman decoding into coefficients) against `np.array(Image.open(...))` (what
         the "pil" decoder does per photo), and Pillow's own 1/8-scale draft decode -- entropy decoding plus a DC-only
@@ -47,6 +49,14 @@ crop-folder    the crop step on its own (`crop_image_sequence`, csrc/abi_jpeg_cr
         `jpeg_resave_file()` and the write, photo by photo on the calling thread -- and (b) `crop_image_sequence`; every
         file of (b) is compared with Pillow's before a rate counts; then where a photo's time goes in (b), one job at a time.
 crop-folder-loop   two runs of `crop_image_sequence` and nothing else, for `rocprofv3 --kernel-trace --stats --`.
+resave-fused   k_jpeg_crop_fwd (the crop box of the planes straight to the re-saved coefficients) against k_jpeg_out in its
+        R G B form followed by k_jpeg_fwd, summed, on the same 4000x3000 crop: HIP events around each kernel, 20 launches
+        each per run, the two alternating, three runs behind an untimed one.  The pair is a crop job's (its kernel ids
+        are its own), the fused kernel goes through its test entry.
+resave-pipeline    the folder of crop-folder, photos per second of (a) one pass, `pipeline=True, resave_ahead=True`, without
+        and with save_crops, (b) the two-pass route -- `crop_image_sequence`, then a pipelined run on its files, both
+        timed -- and (c) `pipeline=False, resave=`; alternating, three runs each behind untimed ones; tracks and crop
+        files are checked equal (the files against Pillow's) before a rate counts.
 pipeline-loop  one plain and two pipelined runs of the same folder and nothing else, for `rocprofv3 --kernel-trace --stats --`.
 """
 import argparse
@@ -660,6 +670,111 @@ def crop_folder(out, n):
         _remove_tree(tmp, dirs, names)
 
 
+def resave_fused(out):
+    from iceberg_tracking_code_amd import Context
+    data = encode(photo(), 90)
+    reps = 20
+    ctx = Context(W, H, n_slots=2, max_pts=64)
+    try:
+        def pair():
+            for _ in range(reps):
+                ctx.jpeg_crop_finish(ctx.jpeg_crop_start(data, None, 75))
+
+        def fused():
+            for _ in range(reps):
+                ctx.jpeg_crop_fwd_device_coefficients(data)
+
+        def timed(f, keys):
+            ctx.prof_reset()
+            ctx.prof_enable(True)
+            f()
+            ctx.prof_enable(False)
+            tab = ctx.prof_table()
+            assert all(tab[k]["launches"] == reps for k in keys), tab
+            return [tab[k]["avg_us"] for k in keys]
+        pair()
+        fused()                                                  # untimed
+        rows = []
+        for _ in range(3):
+            rgb, fwd = timed(pair, ("jpeg_crop_rgb", "jpeg_fwd"))
+            (one,) = timed(fused, ("jpeg_crop_fwd",))
+            rows.append((rgb, fwd, one))
+    finally:
+        ctx.close()
+    print("the fused crop-and-forward kernel against the pair it replaces, %dx%d crop of a 4:2:0 photo, quality 75, HIP events, "
+          "%d launches per run, us per launch (runs in order)" % (W, H, reps), file=out)
+    print("run  k_jpeg_out<rgb>  k_jpeg_fwd    pair  k_jpeg_crop_fwd  fused / pair", file=out)
+    for k, (rgb, fwd, one) in enumerate(rows):
+        print("%3d  %15.1f  %10.1f  %6.1f  %15.1f  %12.2f" % (k, rgb, fwd, rgb + fwd, one, one / (rgb + fwd)), file=out)
+    pairs, ones = [r[0] + r[1] for r in rows], [r[2] for r in rows]
+    spread = max(max(pairs) - min(pairs), max(ones) - min(ones))
+    diff = _median(ones) - _median(pairs)
+    print("medians: pair %.1f us, fused %.1f us; spread between runs %.1f us; fused - pair %+.1f us: %s" %
+          (_median(pairs), _median(ones), spread, diff,
+           "SLOWER than the pair by more than the spread" if diff > spread else "not slower than the pair by more than the spread"), file=out)
+    print("derived, not timed: the pair writes and reads %.1f MB of R G B per photo (%.1f MB of traffic) in a buffer of %.1f MB per "
+          "job in flight; the fused kernel has neither" % (3 * W * H / 1e6, 6 * W * H / 1e6, 3 * W * H / 1e6), file=out)
+
+
+def resave_pipeline(out, n, threads):
+    from iceberg_tracking_code_amd import crop_image_sequence
+    tmp, names = folder(n)
+    dirs = [os.path.join(tmp, d) for d in ("crops_pillow", "crops_one_pass", "crops_two_pass")]
+    for d in dirs:
+        os.makedirs(d)
+    pillow_dir, one_dir, two_dir = dirs
+    try:
+        for p in names:
+            _reference_step((p, os.path.join(pillow_dir, os.path.basename(p))))
+
+        def check_files(d):
+            for p in names:
+                with open(os.path.join(d, os.path.basename(p)), "rb") as f, open(os.path.join(pillow_dir, os.path.basename(p)), "rb") as g:
+                    if f.read() != g.read():
+                        raise SystemExit("%s: %s differs from Pillow's file" % (d, os.path.basename(p)))
+
+        def one_pass(save):
+            rate, got = run_folder(names, tmp, threads, pipeline=True, resave_ahead=True, resave="reference", save_crops=one_dir if save else None)
+            if save:
+                check_files(one_dir)
+            return rate, got
+
+        def two_pass():
+            t = time.perf_counter()
+            done = crop_image_sequence(names, two_dir)
+            got = run_folder([p for p, _, _ in done], tmp, threads, pipeline=True)[1]
+            rate = n / (time.perf_counter() - t)
+            check_files(two_dir)
+            return rate, got
+
+        def serial():
+            return run_folder(names, tmp, threads, resave="reference")
+        routes = (("(a) one pass, resave_ahead=True", lambda: one_pass(False)), ("(a) ... with save_crops", lambda: one_pass(True)),
+                  ("(b) two passes, crop pass included", two_pass), ("(c) pipeline=False, resave=", serial))
+        ref = None
+        for label, f in routes:                                  # untimed: cold files, code objects, clocks, the jobs' buffers
+            got = f()[1]
+            ref = got if ref is None else ref
+            if not same_tracks(got, ref):
+                raise SystemExit("%s: tracks differ from the first route's" % label)
+        res = {label: [] for label, _ in routes}
+        for _ in range(3):
+            for label, f in routes:
+                rate, got = f()
+                if not same_tracks(got, ref):
+                    raise SystemExit("%s: tracks differ" % label)
+                res[label].append(rate)
+        print("", file=out)
+        print("the reference's tracks from a folder of %d photos of %dx%d 4:2:0 quality 90, decode_threads %d, %d usable cores; photos/s "
+              "(runs in order), tracks equal on every route, crop files equal Pillow's" % (n, W, H, threads, len(os.sched_getaffinity(0))), file=out)
+        for label, _ in routes:
+            print("  %-36s %s   median %.1f" % (label, ", ".join("%.1f" % v for v in res[label]), _median(res[label])), file=out)
+        a, a_save, b, c = (_median(res[label]) for label, _ in routes)
+        print("(a) / (b): %.2f, with save_crops %.2f; (a) / (c): %.2f" % (a / b, a_save / b, a / c), file=out)
+    finally:
+        _remove_tree(tmp, dirs, names)
+
+
 def crop_folder_loop(n):
     from iceberg_tracking_code_amd import crop_image_sequence
     tmp, names = folder(n)
@@ -695,25 +810,30 @@ def pipeline_loop(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("mode", choices=("host", "device", "e2e", "huffman", "huffman-loop", "e2e-huffman", "e2e-pipeline",
-                                         "pipeline-loop", "resave", "resave-file", "crop-folder", "crop-folder-loop"))
+                                         "pipeline-loop", "resave", "resave-file", "crop-folder", "crop-folder-loop", "resave-fused",
+                                         "resave-pipeline"))
     ap.add_argument("--out", default=None)
     ap.add_argument("--frames", type=int, default=None)
     ap.add_argument("--threads", type=int, default=16)
     a = ap.parse_args()
     if a.frames is None:
-        a.frames = 96 if a.mode == "crop-folder" else 24
+        a.frames = 96 if a.mode in ("crop-folder", "resave-pipeline") else 24
     if a.mode == "huffman-loop":
         return huffman_loop()
     if a.mode == "pipeline-loop":
         return pipeline_loop(a.frames)
     if a.mode == "crop-folder-loop":
         return crop_folder_loop(a.frames)
-    name = {"resave": "jpeg_resave", "resave-file": "jpeg_resave_file", "crop-folder": "jpeg_crop_folder", "huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e", "e2e-pipeline": "jpeg_pipeline_e2e"}.get(
+    name = {"resave-fused": "jpeg_resave_pipeline", "resave-pipeline": "jpeg_resave_pipeline", "resave": "jpeg_resave", "resave-file": "jpeg_resave_file", "crop-folder": "jpeg_crop_folder", "huffman": "jpeg_huffman_device", "e2e-huffman": "jpeg_huffman_e2e", "e2e-pipeline": "jpeg_pipeline_e2e"}.get(
         a.mode, "jpeg_ingest_%s" % a.mode)
     path = a.out or os.path.join(ROOT, "profiles", name + ".txt")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as out:
-        if a.mode == "host":
+    with open(path, "a" if a.mode == "resave-pipeline" else "w") as out:
+        if a.mode == "resave-fused":
+            resave_fused(out)
+        elif a.mode == "resave-pipeline":
+            resave_pipeline(out, a.frames, min(a.threads, 16))
+        elif a.mode == "host":
             host(out)
         elif a.mode == "device":
             device(out)
