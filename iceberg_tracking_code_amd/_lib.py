@@ -174,6 +174,7 @@ SIGNATURES = {
     "icelk_set_variant": (C.c_int, [handle_p, C.c_char_p, C.c_int]),
     "icelk_seg_detect_stage_try": (C.c_int, [handle_p, C.c_int, i32p, i32p]),
     "icelk_detect_fast_stats": (C.c_int, [handle_p, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "icelk_detect_max_key": (C.c_int, [handle_p, C.POINTER(C.c_uint)]),
     "icelk_seg_detect_stage": (C.c_int, [handle_p, C.c_int, i32p]),
     "icelk_seg_switch": (C.c_int, [handle_p]),
     "icelk_seg_track": (C.c_int, [handle_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

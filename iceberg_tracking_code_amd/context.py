@@ -501,6 +501,12 @@ class Context:
         return dict(tiles=out[0], listed=out[1], whole_tiles=out[2], ties=out[3], max_listed=out[4], max_overflow_tiles=out[5],
                     longest_list=out[6], evaluated=out[7])
 
+    def detect_max_key(self):
+        """The masked maximum of the eigenvalue map as the latest detection published it: its order-preserving key."""
+        k = C.c_uint(0)
+        self._ck(self._lib.icelk_detect_max_key(self._h, C.byref(k)))
+        return k.value
+
     def detect_stats(self):
         a, b = C.c_int(0), C.c_int(0)
         self._ck(self._lib.icelk_detect_stats(self._h, C.byref(a), C.byref(b)))

@@ -710,4 +710,15 @@ int icelk_detect_fast_stats(icelk_t* h, int slot_w, int slot_h, long long* out)
     return ICELK_OK;
 }
 
+int icelk_detect_max_key(icelk_t* h, unsigned* out_key)
+{
+    if (!h || !out_key) return ICELK_EARG;
+    Ctx* c = C(h);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    const Ctx::EigOut& e = c->eo[c->dset[c->dset_last].eo_active];
+    HIPCHK(c, hipMemcpy(out_key, e.max_key, sizeof(unsigned), hipMemcpyDeviceToHost));
+    return ICELK_OK;
+}
+
 }  // extern "C"

@@ -30,9 +30,11 @@
 // The whole detection is enqueued without host round trips; the host synchronises once, to learn the
 // number of accepted corners.
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 
 #include "icelk_internal.h"
+#include "strip_sqrt.h"
 
 namespace icelk {
 
@@ -191,6 +193,9 @@ struct CandSrc {
 //     then the 3x3 non-max test, one thread per column, for the 4 rows whose lower neighbour now exists.
 // Strips that touch the top or bottom of the image (FRESH) reflect rows: the covariance row at a reflected position is
 // the one AT that position with its own neighbours, so the roll does not apply there and each row loads its 3x3 afresh.
+// Round 8 took out per-pixel work the results do not need: pixels are read through a buffer descriptor (no vector
+// address arithmetic), the square root is taken at the range the radicand has (strip_sqrt.h), and a strip that lies inside the
+// frame, unmasked, with no map asked for, runs a row phase that tests nothing per pixel (FAST).  Results are bit for bit as before.
 // Halo: 1.045 in x, 69 covariance rows for 58 output rows.  Regions: 4 per workgroup (16 output rows each).
 // Measured and dropped: a form that stays within the 72 VGPRs the tracker's five waves leave free on a SIMD (ring in
 // LDS, the running sums and the roll parked in LDS during the row-sum phase, s_setprio 3), so that its workgroups are
@@ -227,6 +232,19 @@ struct StripCfg {
     static_assert((VP * 8) % 16 == 0, "16-byte reads of the column sums");
 };
 
+// a frame's pixels behind a raw buffer descriptor (no stride, pitch * h bytes, the 32-bit data format word of gfx9); a row is
+// the descriptor and a scalar byte offset, a pixel of it one buffer_load_ubyte at a lane offset
+struct PixelRow {
+    __amdgpu_buffer_rsrc_t rsrc;
+    unsigned at;
+    __device__ __forceinline__ unsigned operator[](unsigned x) const { return __builtin_amdgcn_raw_buffer_load_b8(rsrc, x, at, 0); }
+};
+struct PixelRows {
+    __amdgpu_buffer_rsrc_t rsrc;
+    unsigned pitch;
+    __device__ __forceinline__ PixelRow row(int y) const { return PixelRow{rsrc, (unsigned)y * pitch}; }
+};
+
 struct SobelRoll {
     float d1, d2, t1, t2;   // row difference / row smooth of pixel rows yc (1) and yc - 1 (2)
 };
@@ -236,7 +254,43 @@ __device__ __forceinline__ float smooth3(float a, float b, float c, float k0, fl
     return __fadd_rn(__fadd_rn(__fmul_rn(k1, a), __fmul_rn(k0, b)), __fmul_rn(k1, c));
 }
 
-template <int BS, bool FRESH>
+// min_eig_of for the N outputs of a row task, with the square root taken at the range this kernel has.  sqrtf, as the
+// compiler expands it, scales the radicand into range, corrects the hardware's root by the two-sided residual test, scales
+// back and tests for 0 and infinity: about 16 instructions.  The radicand here, (a - c)^2 + b^2 of box sums that are at
+// most 1, lies between ~1e-20 and 1.25 wherever the ground has texture, so only the residual test does anything
+// (strip_sqrt.h: the band and why the result is sqrtf's bit for bit).  One wave-uniform test guards it: if any radicand of
+// the wave is outside the band -- 0 over flat ground, above all -- the whole wave takes sqrtf.  A real branch.  BAND = false:
+// min_eig_of as it is, for the block size that is faster with it.
+template <int N, bool BAND>
+__device__ __forceinline__ void min_eig_strip(const double (&Sm)[3][N], float (&e)[N])
+{
+    if constexpr (!BAND) {
+#pragma unroll
+        for (int k = 0; k < N; k++) e[k] = min_eig_of(Sm[0][k], Sm[1][k], Sm[2][k]);
+        return;
+    }
+    float tr[N], r[N];
+    unsigned lo = 0xffffffffu, hi = 0u;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const float a = __fmul_rn((float)Sm[0][k], 0.5f), b = (float)Sm[1][k], c = __fmul_rn((float)Sm[2][k], 0.5f);
+        const float d = __fsub_rn(a, c);
+        r[k] = __fadd_rn(__fmul_rn(d, d), __fmul_rn(b, b));
+        tr[k] = __fadd_rn(a, c);
+        const unsigned rb = __float_as_uint(r[k]);   // non-negative floats order like their bits; -0, negatives and NaN lie above
+        lo = rb < lo ? rb : lo;
+        hi = rb > hi ? rb : hi;
+    }
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(lo < SQRT_BAND_LO || hi > SQRT_BAND_HI) == 0, 1)) {
+#pragma unroll
+        for (int k = 0; k < N; k++) e[k] = __fsub_rn(tr[k], sqrt_in_band(r[k]));
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) e[k] = __fsub_rn(tr[k], sqrtf(r[k]));
+    }
+}
+
+template <int BS, bool FRESH, bool FAST>
 __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int w, int h, int pitch, float k0, float k1,
                                            const uint8_t* __restrict__ mask, int mask_pitch, unsigned* __restrict__ max_key,
                                            unsigned long long* __restrict__ raw, int* __restrict__ blk_count,
@@ -249,9 +303,19 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
     const int x0 = blockIdx.x * C::TW, y0 = blockIdx.y * C::SH;
     const int xs = x0 - 1 - C::AN, ys = y0 - 1 - C::AN;           // image position of covariance column / row 0
     const int rx = reflect101(xs + tid, w);
-    const int xm = reflect101(rx - 1, w), xp = reflect101(rx + 1, w);
+    // Pixels are read through a buffer descriptor of the frame: a load is then (descriptor, 32-bit lane offset, scalar row
+    // offset), and a row costs no vector address arithmetic at all -- a pointer plus a lane index is a 64-bit vector add per
+    // load.  The three column offsets of a thread are fixed; only the scalar row offset moves.  (The descriptor is no
+    // safety net: the hardware compares only the lane offset with pitch * h, not the scalar row offset.  Every read is inside
+    // the frame because rows and columns are reflected or clamped into it, as before.)
+    const unsigned xm = (unsigned)reflect101(rx - 1, w), xc = (unsigned)rx, xp = (unsigned)reflect101(rx + 1, w);
+    const PixelRows px{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(img), 0, pitch * h, 0x00020000), (unsigned)pitch};
     const int bid = blockIdx.y * gridDim.x + blockIdx.x;
     if (tid < C::NSUB) s_cnt[tid] = 0;
+    // the two doubles per row of column sums that the last row task reads beyond the NT columns: no thread writes them and no
+    // output uses them, but their radicands take part in the wave's test of the square root's band.  Zero, they give ordinary
+    // values; left as the LDS was found, a NaN or an infinity there would send every wave to sqrtf.
+    if (tid < C::R * 3 * (C::VP - C::NT)) Vb[(tid / (C::VP - C::NT)) * C::VP + C::NT + tid % (C::VP - C::NT)] = 0.0;
 
     float ring[3][BS];
 #pragma unroll
@@ -260,34 +324,34 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
     SobelRoll S{};
     unsigned pa = 0, pb = 0, pc = 0;   // the pixel row one ahead of the roll
     if (!FRESH) {
-        const uint8_t* r2 = img + (size_t)(ys - 1) * pitch;
-        const uint8_t* r1 = r2 + pitch;
-        const uint8_t* r0 = r1 + pitch;
-        const float a2 = (float)r2[xm], b2 = (float)r2[rx], c2 = (float)r2[xp];
-        const float a1 = (float)r1[xm], b1 = (float)r1[rx], c1 = (float)r1[xp];
+        const PixelRow r2 = px.row(ys - 1), r1 = px.row(ys), r0 = px.row(ys + 1);
+        const float a2 = (float)r2[xm], b2 = (float)r2[xc], c2 = (float)r2[xp];
+        const float a1 = (float)r1[xm], b1 = (float)r1[xc], c1 = (float)r1[xp];
         S.d2 = __fsub_rn(c2, a2); S.t2 = smooth3(a2, b2, c2, k0, k1);
         S.d1 = __fsub_rn(c1, a1); S.t1 = smooth3(a1, b1, c1, k0, k1);
-        pa = r0[xm]; pb = r0[rx]; pc = r0[xp];
+        pa = r0[xm]; pb = r0[xc]; pc = r0[xp];
     }
     // products of covariance row r (image row ys + r)
     auto cov_row = [&](int r, float& xx, float& xy, float& yy) {
         float dtop, dmid, dbot, ttop, tbot;
         if (FRESH) {
             const int ry = reflect101(ys + r, h);
-            const uint8_t* q0 = img + (size_t)reflect101(ry - 1, h) * pitch;
-            const uint8_t* q1 = img + (size_t)ry * pitch;
-            const uint8_t* q2 = img + (size_t)reflect101(ry + 1, h) * pitch;
-            const float a0 = (float)q0[xm], b0 = (float)q0[rx], c0 = (float)q0[xp];
+            const PixelRow q0 = px.row(reflect101(ry - 1, h)), q1 = px.row(ry), q2 = px.row(reflect101(ry + 1, h));
+            const float a0 = (float)q0[xm], b0 = (float)q0[xc], c0 = (float)q0[xp];
             const float a1 = (float)q1[xm], c1 = (float)q1[xp];
-            const float a2 = (float)q2[xm], b2 = (float)q2[rx], c2 = (float)q2[xp];
+            const float a2 = (float)q2[xm], b2 = (float)q2[xc], c2 = (float)q2[xp];
             dtop = __fsub_rn(c0, a0); dmid = __fsub_rn(c1, a1); dbot = __fsub_rn(c2, a2);
             ttop = smooth3(a0, b0, c0, k0, k1); tbot = smooth3(a2, b2, c2, k0, k1);
         } else {
-            const float a = (float)pa, b = (float)pb, c = (float)pc;
+            float a = (float)pa, b = (float)pb, c = (float)pc;
+            // a and c are needed as floats for the smooth anyway: kept opaque here, c - a is one subtraction of them and not an
+            // integer subtraction of the bytes plus a conversion of its own (the same value either way: both are exact).  This
+            // steers one compiler's choice; with another the asm costs nothing and the kernel computes the same
+            asm("" : "+v"(a), "+v"(c));
             int nr = ys + r + 2;                  // next pixel row; past the last row needed it is only kept inside the image
             nr = nr < h ? nr : h - 1;
-            const uint8_t* q = img + (size_t)nr * pitch;
-            pa = q[xm]; pb = q[rx]; pc = q[xp];
+            const PixelRow q = px.row(nr);
+            pa = q[xm]; pb = q[xc]; pc = q[xp];
             dtop = S.d2; dmid = S.d1; dbot = __fsub_rn(c, a);
             ttop = S.t2; tbot = smooth3(a, b, c, k0, k1);
             S.d2 = S.d1; S.d1 = dbot; S.t2 = S.t1; S.t1 = tbot;
@@ -307,8 +371,20 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
     }
 
     unsigned best = 0;
+    // FAST: the masked maximum without a key per pixel.  Of the RX outputs of a task, output 0 lies outside the strip for the
+    // first task of a row and outputs KL + 1 .. RX - 1 for the last; nothing else is ever left out.  So three classes of
+    // outputs (0 | 1 .. KL | KL + 1 .. RX - 1) each keep what they have seen down the strip, and which classes count is
+    // decided once per thread after the loop.  Kept per class: the largest and the smallest of the values' bits as SIGNED
+    // integers.  If any value is >= +0 the largest is the maximum (such floats order like their bits, and every float with the
+    // sign set, -0 included, is a negative integer); if none is, the values order against their bits and the smallest is the
+    // maximum.  That is the order of ordered_key, -0 below +0 included, with no assumption about the values.
+    constexpr int KL = C::TW - C::RX * (C::NG - 1);
+    static_assert(KL >= 0 && KL < C::RX && C::RX * C::NG - 1 >= C::TW, "the last row task holds the strip's last output column");
+    int top_hi[3], top_lo[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { top_hi[k] = INT_MIN; top_lo[k] = INT_MAX; }
     // row-sum phase: which row of the batch (= wave) / which group of RX outputs this thread takes
-    const int wr = tid >> 6, g = tid & 63;
+    const int wr = __builtin_amdgcn_readfirstlane(tid >> 6), g = tid & 63;   // wr is the wave: row tests on it are scalar
     for (int base = 0; base < C::EH; base += C::UNROLL) {
 #pragma unroll
         for (int j = 0; j < C::UNROLL; j++) {
@@ -339,11 +415,25 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
                 }
                 const int er = eb * C::R + wr;
                 float e[C::RX];
-#pragma unroll
-                for (int k = 0; k < C::RX; k++) e[k] = min_eig_of(Sm[0][k], Sm[1][k], Sm[2][k]);
+                // blockSize 3 keeps sqrtf: measured alone, its kernel is 69-71 us with sqrtf and 75-77 with the band form (the
+                // parent: 75-76), though the band form issues fewer instructions -- its row phase is the short one (two additions
+                // per output and plane) and the wave-wide test and branch sit in the middle of it
+                min_eig_strip<C::RX, BS != 3>(Sm, e);
                 *reinterpret_cast<float4*>(Er + (er & 7) * C::NT + C::RX * g) = make_float4(e[0], e[1], e[2], e[3]);
                 const int y = y0 - 1 + er;
-                if (er >= 1 && er <= C::SH && y < h) {
+                if constexpr (FAST) {
+                    // every output of the strip is inside the frame, unmasked, and no map is asked for: nothing to test per
+                    // pixel.  The first and last eigenvalue row are left out here (per wave), the first and last column
+                    // after the loop (per thread).
+                    if (er >= 1 && er <= C::SH) {
+#pragma unroll
+                        for (int k = 0; k < C::RX; k++) {
+                            const int cls = k == 0 ? 0 : (k <= KL ? 1 : 2), bits = __float_as_int(e[k]);
+                            top_hi[cls] = max(top_hi[cls], bits);
+                            top_lo[cls] = min(top_lo[cls], bits);
+                        }
+                    }
+                } else if (er >= 1 && er <= C::SH && y < h) {
 #pragma unroll
                     for (int k = 0; k < C::RX; k++) {
                         const int ce = C::RX * g + k, x = x0 - 1 + ce;
@@ -389,6 +479,15 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
             }
         }
     }
+    if constexpr (FAST) {
+        // one key per thread: class 0 counts unless this is the first task of a row, class 2 unless it is the last
+        const bool counts[3] = {g >= 1 && g < C::NG, g < C::NG, g < C::NG - 1};
+        int hi = INT_MIN, lo = INT_MAX;
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            if (counts[k]) { hi = max(hi, top_hi[k]); lo = min(lo, top_lo[k]); }
+        if (lo <= hi) best = ordered_key(__int_as_float(hi >= 0 ? hi : lo));   // lo > hi: the thread has seen no output
+    }
     publish_max(max_key, best, tid);
     __syncthreads();
     if (tid < C::NSUB) blk_count[bid * C::NSUB + tid] = s_cnt[tid];
@@ -399,6 +498,9 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
 // faster ALONE (81 against 98 us) and slower where it counts: beside a tracker launch the tracker decides how many of its
 // waves fit, and without scratch C2 runs at 6 900-6 940 pairs/s instead of 6 620-6 650 (same-box A/B,
 // profiles/r04_ab_corner_kernel_registers.txt; REF equal, C5 +1 %).  blockSize 3 / 5 / 7 need 87 / 110 / 124 and keep four waves.
+// Round 8 (profiles/r08_corner_resources.json): 148 at blockSize 10, three waves, no scratch; blockSize 7 now needs exactly the 128
+// of a fourth wave, so a change of compiler or of this body can cost blockSize 7 that wave -- look at the resource remarks
+// (-Rpass-analysis=kernel-resource-usage) after either.
 template <int BS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_eig_strip(const uint8_t* __restrict__ img, int w, int h, int pitch, float k0,
                                                     float k1, const uint8_t* __restrict__ mask, int mask_pitch,
@@ -410,11 +512,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ int s_cnt[C::NSUB];
     const int ys = (int)blockIdx.y * C::SH - 1 - C::AN;
-    // pixel rows ys - 1 .. ys + NROWS are read by the rolling form
-    if (ys - 1 >= 0 && ys + C::NROWS <= h - 1)
-        strip_body<BS, false>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
+    // pixel rows ys - 1 .. ys + NROWS are read by the rolling form: such a strip has all its output rows inside the frame
+    const bool rolling = ys - 1 >= 0 && ys + C::NROWS <= h - 1;
+    // all TW output columns of the strip are inside the frame (every strip but a narrower last one)
+    const bool inside_x = ((int)blockIdx.x + 1) * C::TW <= w;
+    if (rolling && inside_x && !mask && !eig_out)
+        strip_body<BS, false, true>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
+    else if (rolling)
+        strip_body<BS, false, false>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
     else
-        strip_body<BS, true>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
+        strip_body<BS, true, false>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
 }
 
 // workgroup-aggregated append: every thread offers at most one key per call; one global atomic per call

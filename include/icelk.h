@@ -180,6 +180,10 @@ int icelk_detect_stats(icelk_t* h, int* n_candidates, int* n_accepted);
  * handed to the 3x3 tie pass, [4] pixels listed as possible carriers of the maximum, [5] tiles whose such list overflowed,
  * [6] longest tile list, [7] listed pixels that got their exact value in the one-pixel pass (certain, above the cut). */
 int icelk_detect_fast_stats(icelk_t* h, int frame_w, int frame_h, long long* out);
+/* The masked maximum of the eigenvalue map as the candidate stage of the latest detection (or icelk_min_eig_map) on this
+ * handle published it: the order-preserving key of the float (sign set: ~bits, else bits | 0x80000000), 0 if no pixel
+ * counted (diagnostics and tests; waits for the device). */
+int icelk_detect_max_key(icelk_t* h, unsigned* out_key);
 
 /* ---- device-resident segment state: the `tracks` / `trackquality` lists of s1:299-300,335-359 --
  * A segment starts at a detection frame (counter % track_len == 0, s1:362,437-448) and is extended
