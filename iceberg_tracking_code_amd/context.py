@@ -243,7 +243,7 @@ class Context:
                                                                         C.c_void_p(coef.ctypes.data), coef.size))
         return coef
 
-    # -- the crop step on its own: decode, crop, re-save and encode in one enqueued piece (csrc/abi_jpeg_crop.hip) --
+    # -- the crop step on its own: decode, crop, re-save and encode in one enqueued piece (csrc/abi_jpeg_crop.hip on csrc/abi_jpeg_job.hip) --
     def jpeg_crop_config(self, stream_bytes_per_block=48):
         """Bytes of stuffed scan per block (1 .. 416) that a crop job started from now on may take on the device; a scan
         that takes more is coded again at `jpeg_crop_finish` with host-read sizes (route "over-budget"), same bytes."""

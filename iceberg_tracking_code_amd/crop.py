@@ -1,7 +1,7 @@
 """The reference's crop step on its own: `cam.crop_image_parallel(imagelist, targetworkspace)` (camtools.py:64-104,
 237-258, called at s1:272) opens every photo, crops it and saves it again as a JPEG into the day's target folder, which
 the tracker, s3's plots and the movies then read.  `crop_image_sequence` writes that folder, byte for byte, with the
-work on the device: a photo is one crop job (`Context.jpeg_crop_start` / `jpeg_crop_finish`, csrc/abi_jpeg_crop.hip) --
+work on the device: a photo is one crop job (`Context.jpeg_crop_start` / `jpeg_crop_finish`, csrc/abi_jpeg_crop.hip on csrc/abi_jpeg_job.hip) --
 Huffman decoding, inverse DCT, the crop box, the lossy re-save and the entropy coder enqueued in one piece, the coder's
 sizes left on the device -- and only the finished file comes back.
 

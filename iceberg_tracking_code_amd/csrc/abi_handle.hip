@@ -216,10 +216,7 @@ static void destroy_ctx(Ctx* c)
                     c->d_st_f, c->d_st_b, c->d_valid, c->dset[0].D.eig, c->d_tracked,
                     c->d_out_tracks, c->d_out_quality, c->post.d_proj, c->post.d_keep, c->post.d_cube_u, c->post.d_cube_v,
                     c->post.d_cube_count, c->calib.d_shore, c->calib.d_water, c->jpeg.d_rgb};
-    const Ctx::JpegJob& jb = c->jpeg.sync;
-    void* jp[] = {jb.d_coef, jb.d_planes, jb.d_file, jb.d_seg, jb.d_tabs, jb.d_T, jb.d_X, jb.d_cnt, jb.d_P, jb.d_ctl, jb.d_dc};
-    for (void* p : jp)
-        if (p) hipFree(p);
+    jpeg_dec_free(c->jpeg.sync);
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto& S : c->sb) {

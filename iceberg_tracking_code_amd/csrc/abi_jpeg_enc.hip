@@ -30,6 +30,14 @@ void jpeg_enc_free(Ctx::JpegEnc& E)
 
 void jpeg_enc_destroy(Ctx* c) { jpeg_enc_free(c->jpeg.enc); }
 
+void jpeg_resave_free(Ctx::JpegResave& R)
+{
+    if (R.d_rgb) hipFree(R.d_rgb);
+    if (R.d_rcoef) hipFree(R.d_rcoef);
+    jpeg_enc_free(R.enc);
+    R = Ctx::JpegResave{};
+}
+
 int jpeg_enc_rc(Ctx* c, int rc)
 {
     switch (rc) {
@@ -61,7 +69,7 @@ int jpeg_enc_prepare(Ctx* c, Ctx::JpegEnc& E)
 
 // The scan of the coefficients at d_coef (laid out as L says) -> E.d_out, E.stream_len, on stream st with the host reading
 // the two sizes in between.  The synchronous calls run it on the handle's coder and compute stream, a crop job
-// (abi_jpeg_crop.hip) on its own where its budget did not hold the scan.
+// (abi_jpeg_job.hip) on its own where its budget did not hold the scan.
 int jpeg_encode_on(Ctx* c, Ctx::JpegEnc& E, hipStream_t st, const enc::Layout& L, const int16_t* d_coef)
 {
     E.stream_ok = false;
@@ -124,25 +132,28 @@ int jpeg_encode_on(Ctx* c, Ctx::JpegEnc& E, hipStream_t st, const enc::Layout& L
     return ICELK_OK;
 }
 
+// Header, E.d_out (E.stream_len bytes, copied on stream st, which is synchronised) and EOI into the caller's buffer.
+// pending: st holds a copy into another buffer of the caller's, which a refusal has to wait for
+int jpeg_deliver_file(Ctx* c, const Ctx::JpegEnc& E, hipStream_t st, bool pending, const icelk_jpeg_info_t& I, const uint8_t* comment,
+                      uint64_t comment_len, uint8_t* out, uint64_t capacity, uint64_t* len)
+{
+    uint8_t* at = nullptr;
+    if (enc::file_frame(I, comment, comment_len, E.stream_len, out, capacity, len, &at)) {
+        if (pending) HIPCHK(c, hipStreamSynchronize(st));
+        FAIL(c, ICELK_ECAP, "the file does not fit the buffer (len says what it takes)");
+    }
+    HIPCHK(c, hipMemcpyAsync(at, E.d_out, (size_t)E.stream_len, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return ICELK_OK;
+}
+
 namespace {
 
 int encode_device(Ctx* c, const enc::Layout& L, const int16_t* d_coef) { return jpeg_encode_on(c, c->jpeg.enc, c->stream, L, d_coef); }
 
-// header, E.d_out and EOI into the caller's buffer
 int deliver(Ctx* c, const icelk_jpeg_info_t& I, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity, uint64_t* len)
 {
-    Ctx::Jpeg::Enc& E = c->jpeg.enc;
-    enc::Bytes H(nullptr, 0);
-    enc::header_bytes(I, comment, comment_len, H);
-    *len = H.n + E.stream_len + 2;
-    if (!out || capacity < *len) FAIL(c, ICELK_ECAP, "the file does not fit the buffer (len says what it takes)");
-    enc::Bytes B(out, capacity);
-    enc::header_bytes(I, comment, comment_len, B);
-    HIPCHK(c, hipMemcpyAsync(out + B.n, E.d_out, (size_t)E.stream_len, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    out[B.n + E.stream_len] = 0xFF;
-    out[B.n + E.stream_len + 1] = 0xD9;
-    return ICELK_OK;
+    return jpeg_deliver_file(c, c->jpeg.enc, c->stream, false, I, comment, comment_len, out, capacity, len);
 }
 
 }  // namespace

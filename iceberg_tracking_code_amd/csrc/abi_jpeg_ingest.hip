@@ -8,11 +8,19 @@
 //   jpeg_plane_args         what the box needs of a described file, checked: arguments of the two pixel kernels
 //   jpeg_idct_on / jpeg_gray_on   the two pixel kernels on a stream; planes_to_gray_slot: the end of a synchronous upload
 //
-// The re-save (abi_jpeg_resave.hip) puts its forward kernel between jpeg_planes and planes_to_gray_slot, the look-ahead
-// decoder (abi_jpeg_async.hip) runs the same steps on a decode stream between foreign_write_begin / _end (abi_frames.hip).
+// The re-save (abi_jpeg_resave.hip) puts its forward kernel between jpeg_planes and planes_to_gray_slot, the job
+// driver (abi_jpeg_job.hip) runs the same steps on a decode stream between foreign_write_begin / _end (abi_frames.hip).
 #include "icelk_ctx.h"
 
 namespace icelk {
+
+void jpeg_dec_free(Ctx::JpegDec& D)
+{
+    void* p[] = {D.d_coef, D.d_planes, D.d_file, D.d_seg, D.d_tabs, D.d_T, D.d_X, D.d_cnt, D.d_P, D.d_ctl, D.d_dc};
+    for (void* q : p)
+        if (q) hipFree(q);
+    D = Ctx::JpegDec{};
+}
 
 int check_crop_box(Ctx* c, const icelk_jpeg_info_t& I, int left, int top, int right, int bottom, int* w, int* h)
 {
@@ -27,7 +35,7 @@ int check_crop_box(Ctx* c, const icelk_jpeg_info_t& I, int left, int top, int ri
 // The block rows the pixel box [left, W - right) x [top, H - bottom) needs and the blocks to transform: fills `A` and `out`
 // (planes, chroma mode, box) for the transform and the output kernel, and grows job B's coefficient and plane buffers.
 // The descriptor comes from the caller: nothing in it is trusted beyond what jpeg_info_ok has checked against the image size.
-int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* Ap,
+int jpeg_plane_args(Ctx* c, Ctx::JpegDec& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* Ap,
                     JpegOutArgs* out)
 {
     if (!I) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
@@ -47,7 +55,7 @@ size_t jpeg_plane_bytes(const icelk_jpeg_info_t& I)
 }
 
 // jpeg_plane_args without its checks and allocations: descriptor and box are known to be good, d_coef holds I.coef_count
-// values and d_planes jpeg_plane_bytes(I) bytes (the second plane buffer of a slot-bound re-save job, abi_jpeg_async.hip)
+// values and d_planes jpeg_plane_bytes(I) bytes (the second plane buffer of a slot-bound re-save job, abi_jpeg_job.hip)
 void jpeg_plane_layout(const icelk_jpeg_info_t& Iref, int left, int top, int right, int bottom, int16_t* d_coef, uint8_t* d_planes,
                        JpegIdctArgs* Ap, JpegOutArgs* out)
 {
@@ -136,7 +144,7 @@ int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int lef
                 bool on_device)
 {
     if (!I || (!coef && !on_device)) FAIL(c, ICELK_EARG, "null JPEG descriptor or coefficients");
-    Ctx::JpegJob& B = c->jpeg.sync;
+    Ctx::JpegDec& B = c->jpeg.sync;
     JpegIdctArgs A;
     if (int rc = jpeg_plane_args(c, B, I, left, top, right, bottom, &A, out)) return rc;
     for (int k = 0; k < I->ncomp && !on_device; k++) {
@@ -188,7 +196,7 @@ int jpeg_open(Ctx* c, const uint8_t* data, uint64_t len, JpegIndex& X, icelk_jpe
 }
 
 // The serial decoder takes the file: its coefficients, kept in `keep` until stream st is through, go into job J.
-int jpeg_host_into_job(Ctx* c, Ctx::JpegJob& J, const uint8_t* data, uint64_t len, const icelk_jpeg_info_t& I, hipStream_t st,
+int jpeg_host_into_job(Ctx* c, Ctx::JpegDec& J, const uint8_t* data, uint64_t len, const icelk_jpeg_info_t& I, hipStream_t st,
                        std::vector<int16_t>& keep)
 {
     try {
@@ -214,7 +222,7 @@ static int jpeg_huff_fallback(Ctx* c, const uint8_t* data, uint64_t len, const i
 // The buffers of job J for a file of `len` bytes indexed as X (jpeg_index, jpeg_index_lanes), and the kernels' arguments.
 // headroom: what grows with the file's length is taken a quarter larger than this file needs -- growing a buffer frees
 // it, which waits for the whole device, and the photos of a folder all differ a little in length (asynchronous jobs).
-int jpeg_huff_setup(Ctx* c, Ctx::JpegJob& J, const JpegIndex& X, uint64_t len, JpegHuffArgs* Hp, bool headroom)
+int jpeg_huff_setup(Ctx* c, Ctx::JpegDec& J, const JpegIndex& X, uint64_t len, JpegHuffArgs* Hp, bool headroom)
 {
     const lanes::Scan& A = X.scan;
     auto pad = [&](size_t n) { return headroom ? n + n / 4 : n; };
@@ -256,7 +264,7 @@ int jpeg_huff_setup(Ctx* c, Ctx::JpegJob& J, const JpegIndex& X, uint64_t len, J
 
 // The file's `len` bytes, X's segment table and X's tables, each from where the caller keeps them (its own memory, or the
 // job's pinned staging area), into job J on stream st; the control words and the coefficients cleared behind them.
-int jpeg_huff_stage(Ctx* c, Ctx::JpegJob& J, const JpegIndex& X, const uint8_t* file, const void* seg, const void* tabs, uint64_t len,
+int jpeg_huff_stage(Ctx* c, Ctx::JpegDec& J, const JpegIndex& X, const uint8_t* file, const void* seg, const void* tabs, uint64_t len,
                     hipStream_t st)
 {
     HIPCHK(c, hipMemcpyAsync(J.d_file, file, (size_t)len, hipMemcpyHostToDevice, st));
@@ -280,7 +288,7 @@ int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_
 {
     if (!data || !info) FAIL(c, ICELK_EARG, "null JPEG file");
     Ctx::Jpeg& J = c->jpeg;
-    Ctx::JpegJob& B = J.sync;
+    Ctx::JpegDec& B = J.sync;
     memset(&J.stats, 0, sizeof(J.stats));
     JpegIndex X;
     bool host_only = false;

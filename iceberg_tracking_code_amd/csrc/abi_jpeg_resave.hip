@@ -22,12 +22,10 @@ using resave::resave_info;
 void jpeg_resave_destroy(Ctx* c)
 {
     Ctx::Jpeg& J = c->jpeg;
-    void* p[] = {J.resave.d_coef, J.resave.d_planes, J.d_src};
-    for (void* q : p)
-        if (q) hipFree(q);
-    J.resave.d_coef = nullptr;
-    J.resave.d_planes = nullptr;
+    jpeg_dec_free(J.resave);
+    if (J.d_src) hipFree(J.d_src);
     J.d_src = nullptr;
+    J.src_cap = 0;
 }
 
 // what the device entry points accept, checked before anything is enqueued
@@ -40,8 +38,8 @@ int jpeg_resave_check(Ctx* c, int w, int h, int quality)
 }
 
 // The forward kernel on stream st: the w x h image at d_src (rows 3 w bytes apart) -> the coefficients of the re-saved
-// file that I describes (resave_info) at d_coef.  The synchronous calls run it on the handle's re-save job, a crop job
-// (abi_jpeg_crop.hip) on its own buffers.
+// file that I describes (resave_info) at d_coef.  The synchronous calls run it on the handle's re-save job, a job in flight
+// (abi_jpeg_job.hip) on its own buffers.
 static JpegFwdArgs fwd_args(const uint8_t* d_src, int16_t* d_coef, int w, int h, const icelk_jpeg_info_t& I)
 {
     JpegFwdArgs F{};
@@ -109,7 +107,7 @@ int rgb_to_src(Ctx* c, const uint8_t* rgb, int w, int h, int stride)
 // its component planes, `O` ready for k_jpeg_out
 int resave_forward(Ctx* c, int w, int h, int quality, icelk_jpeg_info_t* I, JpegOutArgs* O, bool with_planes = true)
 {
-    Ctx::JpegJob& B = c->jpeg.resave;
+    Ctx::JpegDec& B = c->jpeg.resave;
     resave_info(w, h, quality, I);
     JpegIdctArgs D;
     if (int rc = jpeg_plane_args(c, B, I, 0, 0, 0, 0, &D, O)) return rc;   // grows d_coef and d_planes
@@ -230,7 +228,7 @@ int icelk_jpeg_crop_fwd_device_coefficients(icelk_t* h, const uint8_t* data, uin
     if (int rc = jpeg_huff_device(c, data, len, &I)) return rc;
     JpegOutArgs O{};
     if (int rc = jpeg_planes(c, &I, nullptr, crop_left, crop_top, crop_right, crop_bottom, &O, true)) return rc;
-    Ctx::JpegJob& B = c->jpeg.resave;
+    Ctx::JpegDec& B = c->jpeg.resave;
     if (int rc = grow(c, &B.d_coef, &B.coef_cap, (size_t)R.coef_count)) return rc;
     if (int rc = jpeg_crop_fwd_on(c, c->stream, O, B.d_coef, R)) return rc;
     c->jpeg.enc.resaved = true;   // as resave_forward: these are the handle's most recent re-saved coefficients

@@ -38,11 +38,11 @@ namespace icelk {
 void map_destroy(Ctx* c)
 {
     Ctx::Map& M = c->map;
-    void* p[] = {M.job.d_rgb, M.job.d_rcoef, M.d_planes, M.d_items, M.d_measured, M.d_scene, M.d_arrows, M.d_group};
+    void* p[] = {M.d_planes, M.d_items, M.d_measured, M.d_scene, M.d_arrows, M.d_group};
     for (void* q : p)
         if (q) hipFree(q);
     delete M.h_scene;
-    jpeg_enc_free(M.job.enc);
+    jpeg_resave_free(M.rs);
     M = Ctx::Map{};
 }
 
@@ -205,8 +205,8 @@ int grow_picture(Ctx* c, const icelk_map_desc_t* d, const Picture& Q)
     if (int rc = grow(c, &M.d_planes, &M.planes_cap, 3 * px)) return rc;
     if (int rc = grow(c, &M.d_items, &M.items_cap, Q.items)) return rc;
     if (int rc = grow(c, &M.d_measured, &M.measured_cap, Q.measured)) return rc;
-    if (int rc = grow(c, &M.job.d_rgb, &M.job.rgb_cap, 3 * px)) return rc;
-    return grow(c, &M.job.d_rcoef, &M.job.rcoef_cap, (size_t)Q.info.coef_count);
+    if (int rc = grow(c, &M.rs.d_rgb, &M.rs.rgb_cap, 3 * px)) return rc;
+    return grow(c, &M.rs.d_rcoef, &M.rs.rcoef_cap, (size_t)Q.info.coef_count);
 }
 
 int draw_and_encode(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked, const Picture& Q, uint8_t* rgb, int rgb_stride, uint8_t* file,
@@ -270,27 +270,13 @@ int draw_and_encode(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked
     HIPCHK(c, hipMemcpyAsync(M.d_scene, &S, sizeof(S), hipMemcpyHostToDevice, st));
     {
         ProfScope p(c, K_MAP_RESOLVE);
-        launch_map_resolve(st, M.d_scene, Wo, Ho, base, top, count, M.job.d_rgb);
+        launch_map_resolve(st, M.d_scene, Wo, Ho, base, top, count, M.rs.d_rgb);
     }
     if (int rc = check_launch(c, "map_resolve")) return rc;
-    if (int rc = jpeg_fwd_on(c, st, M.job.d_rgb, M.job.d_rcoef, Wo, Ho, Q.info)) return rc;
-    if (int rc = jpeg_encode_on(c, M.job.enc, st, Q.L, M.job.d_rcoef)) return rc;   // synchronises
-    Ctx::JpegEnc& E = M.job.enc;
-    if (rgb) HIPCHK(c, hipMemcpy2DAsync(rgb, rgb_stride, M.job.d_rgb, 3 * (size_t)Wo, 3 * (size_t)Wo, Ho, hipMemcpyDeviceToHost, st));
-    enc::Bytes H(nullptr, 0);
-    enc::header_bytes(Q.info, nullptr, 0, H);
-    *len = H.n + E.stream_len + 2;
-    if (!file || capacity < *len) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        FAIL(c, ICELK_ECAP, "the file does not fit the buffer (len says what it takes)");
-    }
-    enc::Bytes B(file, capacity);
-    enc::header_bytes(Q.info, nullptr, 0, B);
-    HIPCHK(c, hipMemcpyAsync(file + B.n, E.d_out, (size_t)E.stream_len, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    file[B.n + E.stream_len] = 0xFF;
-    file[B.n + E.stream_len + 1] = 0xD9;
-    return ICELK_OK;
+    if (int rc = jpeg_fwd_on(c, st, M.rs.d_rgb, M.rs.d_rcoef, Wo, Ho, Q.info)) return rc;
+    if (int rc = jpeg_encode_on(c, M.rs.enc, st, Q.L, M.rs.d_rcoef)) return rc;   // synchronises
+    if (rgb) HIPCHK(c, hipMemcpy2DAsync(rgb, rgb_stride, M.rs.d_rgb, 3 * (size_t)Wo, 3 * (size_t)Wo, Ho, hipMemcpyDeviceToHost, st));
+    return jpeg_deliver_file(c, M.rs.enc, st, rgb != nullptr, Q.info, nullptr, 0, file, capacity, len);
 }
 
 void release_arrows(Ctx* c)

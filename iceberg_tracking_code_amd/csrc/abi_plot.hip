@@ -27,10 +27,10 @@ namespace icelk {
 void plot_destroy(Ctx* c)
 {
     Ctx::Plot& P = c->plot;
-    void* p[] = {P.job.d_rgb, P.job.d_rcoef, P.d_bg, P.d_counts, P.d_tables, P.d_tracks};
+    void* p[] = {P.d_bg, P.d_counts, P.d_tables, P.d_tracks};
     for (void* q : p)
         if (q) hipFree(q);
-    jpeg_enc_free(P.job.enc);
+    jpeg_resave_free(P.rs);
     P = Ctx::Plot{};
 }
 
@@ -147,8 +147,8 @@ int grow_picture(Ctx* c, const Picture& Q)
     }
     if (int rc = grow(c, &P.d_bg, &P.bg_cap, px)) return rc;
     if (int rc = grow(c, &P.d_counts, &P.counts_cap, 2 * px)) return rc;
-    if (int rc = grow(c, &P.job.d_rgb, &P.job.rgb_cap, 3 * px)) return rc;
-    return grow(c, &P.job.d_rcoef, &P.job.rcoef_cap, (size_t)Q.info.coef_count);
+    if (int rc = grow(c, &P.rs.d_rgb, &P.rs.rgb_cap, 3 * px)) return rc;
+    return grow(c, &P.rs.d_rcoef, &P.rs.rcoef_cap, (size_t)Q.info.coef_count);
 }
 
 // d_tracks: (n, nv, 2) on the device, ordered on the compute stream.  The four kernels, the forward kernel, the coder;
@@ -181,28 +181,14 @@ int draw_and_encode(Ctx* c, const Picture& Q, const float* d_tracks, int n, int 
     if (int rc = check_launch(c, "plot_scatter")) return rc;
     {
         ProfScope p(c, K_PLOT_RESOLVE);
-        launch_plot_resolve(st, P.d_bg, lines, dots, P.d_tables, Q.stamp, Q.Wo, Q.Ho, P.job.d_rgb);
+        launch_plot_resolve(st, P.d_bg, lines, dots, P.d_tables, Q.stamp, Q.Wo, Q.Ho, P.rs.d_rgb);
     }
     if (int rc = check_launch(c, "plot_resolve")) return rc;
-    if (int rc = jpeg_fwd_on(c, st, P.job.d_rgb, P.job.d_rcoef, Q.Wo, Q.Ho, Q.info)) return rc;
-    if (int rc = jpeg_encode_on(c, P.job.enc, st, Q.L, P.job.d_rcoef)) return rc;   // synchronises
-    Ctx::JpegEnc& E = P.job.enc;
+    if (int rc = jpeg_fwd_on(c, st, P.rs.d_rgb, P.rs.d_rcoef, Q.Wo, Q.Ho, Q.info)) return rc;
+    if (int rc = jpeg_encode_on(c, P.rs.enc, st, Q.L, P.rs.d_rcoef)) return rc;   // synchronises
     if (rgb)
-        HIPCHK(c, hipMemcpy2DAsync(rgb, rgb_stride, P.job.d_rgb, 3 * (size_t)Q.Wo, 3 * (size_t)Q.Wo, Q.Ho, hipMemcpyDeviceToHost, st));
-    enc::Bytes H(nullptr, 0);
-    enc::header_bytes(Q.info, nullptr, 0, H);
-    *len = H.n + E.stream_len + 2;
-    if (!file || capacity < *len) {
-        HIPCHK(c, hipStreamSynchronize(st));
-        FAIL(c, ICELK_ECAP, "the file does not fit the buffer (len says what it takes)");
-    }
-    enc::Bytes B(file, capacity);
-    enc::header_bytes(Q.info, nullptr, 0, B);
-    HIPCHK(c, hipMemcpyAsync(file + B.n, E.d_out, (size_t)E.stream_len, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    file[B.n + E.stream_len] = 0xFF;
-    file[B.n + E.stream_len + 1] = 0xD9;
-    return ICELK_OK;
+        HIPCHK(c, hipMemcpy2DAsync(rgb, rgb_stride, P.rs.d_rgb, 3 * (size_t)Q.Wo, 3 * (size_t)Q.Wo, Q.Ho, hipMemcpyDeviceToHost, st));
+    return jpeg_deliver_file(c, P.rs.enc, st, rgb != nullptr, Q.info, nullptr, 0, file, capacity, len);
 }
 
 }  // namespace

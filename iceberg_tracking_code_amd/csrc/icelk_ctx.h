@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <mutex>
 
 #include "icelk_internal.h"
@@ -79,7 +80,7 @@ struct Ctx {
     // JPEG ingest.  What ONE file owns while it is decoded: coefficients, component planes, and for the Huffman decoding
     // on the device (icelk_upload_jpeg_file ...) the file, its segments and tables and the lanes' arrays; grown on demand,
     // because the file may be larger than max_w x max_h (the crop is what has to fit).  The synchronous calls share one
-    // job; every file of icelk_upload_jpeg_file_async has its own until icelk_jpeg_async_finish (abi_jpeg_async.hip).
+    // job; every file of icelk_upload_jpeg_file_async has its own until icelk_jpeg_async_finish (abi_jpeg_job.hip).
     // The JPEG writer (abi_jpeg_enc.hip), allocated at first use: the tables, the blocks' bit lengths, the groups' offsets,
     // the packed and the stuffed stream -- grown to what a file measures by the synchronous calls, which share one
     // (Jpeg::enc), allocated to the job's budget by a crop job, which has its own.  `resaved` / `info`: the handle has run
@@ -96,7 +97,10 @@ struct Ctx {
         icelk_jpeg_info_t info{};
         uint64_t stream_len = 0;
     };
-    struct JpegJob {
+    // One file's working set is split by owner, and every part has ONE free function (which nulls what it frees): a field
+    // added to a part is freed wherever the part is embedded.
+    // The decoder's part (jpeg_dec_free, abi_jpeg_ingest.hip): coefficients, planes and the Huffman decoder's arrays
+    struct JpegDec {
         int16_t* d_coef = nullptr;
         uint8_t* d_planes = nullptr;
         size_t coef_cap = 0, planes_cap = 0;   // elements / bytes
@@ -107,14 +111,36 @@ struct Ctx {
         uint32_t *d_cnt = nullptr, *d_P = nullptr, *d_ctl = nullptr;
         int32_t* d_dc = nullptr;
         size_t file_cap = 0, seg_cap = 0, lane_cap = 0, group_cap = 0, dc_cap = 0;
-        // ---- asynchronous jobs only
+    };
+    // The re-save's part (jpeg_resave_free, abi_jpeg_enc.hip): what the forward kernel reads and writes, and the coder
+    // behind it.  A crop job, a slot-bound re-save job, the segment picture and the velocity map have one each
+    struct JpegResave {
+        uint8_t* d_rgb = nullptr;        // the R G B image, rows 3 * width bytes apart
+        int16_t* d_rcoef = nullptr;      // the re-save's coefficients (described by rinfo)
+        size_t rgb_cap = 0, rcoef_cap = 0;
+        JpegEnc enc;                     // the coder's buffers: at the job's budget, or grown to what a picture measures
+        icelk_jpeg_info_t rinfo{};       // of the re-saved file (jobs only)
+    };
+    // A file in flight (abi_jpeg_job.hip; freed by free_job there): the two parts above and what start, poll and finish keep.
+    // kind: a slot's frame as decoded / a slot's frame re-saved (icelk_upload_jpeg_file_async_resave: the crop box of
+    // dec.d_planes goes through the fused kernel into rs.d_rcoef, whose inverse DCT needs planes of its own before the
+    // gray of the slot is made of them) / a crop job (abi_jpeg_crop.hip: decode -> crop -> re-save -> encode, owned by a
+    // ticket instead of a slot)
+    enum JpegJobKind { JOB_SLOT, JOB_SLOT_RESAVE, JOB_CROP };
+    struct JpegJob {
+        JpegDec dec;
+        JpegResave rs;
+        JpegJobKind kind = JOB_SLOT;
+        bool want_file = false;          // the chain codes rs.d_rcoef as well (always, for a crop job)
         uint8_t* h_stage = nullptr;      // pinned: tables | segment table | the file's bytes (what the host decoder reads)
         size_t stage_cap = 0, file_off = 0;
         uint32_t* h_verdict = nullptr;   // pinned, device-visible: JpegVerdictWord
         uint32_t seq = 0;                // h_verdict[JV_SEQ] == seq: the verdict of the file in flight has arrived
         hipEvent_t done = nullptr;       // behind the verdict kernel
         hipStream_t st = nullptr;        // the decode stream the file went out on
-        int slot = -1;                   // the slot that owns the job, -1: free
+        int slot = -1;                   // the slot that owns the job, -1: none
+        int ticket = -1;                 // the ticket that owns the job, -1: none
+        bool enqueued = false;           // something of the job may be on its stream: a failing start waits for it
         bool host_only = false;          // nothing was enqueued (a file of 256 MiB or more): the host decoder takes it
         uint64_t len = 0;
         int variant = 0;
@@ -122,32 +148,22 @@ struct Ctx {
         icelk_jpeg_info_t info{};
         JpegIdctArgs idct{};             // of the file and its crop: what a second transform after the host decoder runs on
         JpegOutArgs out{};
-        // ---- crop jobs only (abi_jpeg_crop.hip): decode -> crop -> re-save -> encode, owned by a ticket instead of a slot
-        int ticket = -1;                 // the ticket that owns the job, -1: none
-        uint8_t* d_rgb = nullptr;        // the cropped R G B, rows 3 * width bytes apart
-        int16_t* d_rcoef = nullptr;      // the re-save's coefficients (described by rinfo)
-        size_t rgb_cap = 0, rcoef_cap = 0;
-        JpegEnc enc;                     // the coder's buffers, at the job's budget
-        uint8_t* h_out = nullptr;        // pinned: the finished scan
-        size_t hout_cap = 0;
-        uint32_t budget = 0;             // bytes the stuffed scan may take on the device
-        icelk_jpeg_info_t rinfo{};       // of the re-saved file
-        bool have_scan = false;          // h_out holds the scan (scan_len bytes): finish has done its waiting
-        uint64_t scan_len = 0;
-        icelk_jpeg_crop_stats_t cstats{};
-        // ---- slot-bound re-save jobs only (icelk_upload_jpeg_file_async_resave): the crop box of d_planes goes through the
-        // fused kernel into d_rcoef, whose inverse DCT needs planes of its own before the gray of the slot is made of them
-        bool resave = false, want_file = false;
-        uint8_t* d_planes2 = nullptr;
+        uint8_t* d_planes2 = nullptr;    // JOB_SLOT_RESAVE: the planes of the re-saved file
         size_t planes2_cap = 0;
         JpegIdctArgs ridct{};            // of the re-saved file, whole
         JpegOutArgs rout{};
+        uint8_t* h_out = nullptr;        // pinned: the finished scan
+        size_t hout_cap = 0;
+        uint32_t budget = 0;             // bytes the stuffed scan may take on the device
+        bool have_scan = false;          // h_out holds the scan (scan_len bytes): finish has done its waiting
+        uint64_t scan_len = 0;
+        icelk_jpeg_crop_stats_t cstats{};
     };
     struct Jpeg {
-        JpegJob sync;                                          // the working set of every synchronous call
+        JpegDec sync;                                          // the working set of every synchronous call
         // the re-save (abi_jpeg_resave.hip), allocated at first use: the cropped R G B image the forward kernel reads
-        // (rows 3 * width bytes apart), and the coefficients and planes of the re-saved file
-        JpegJob resave;
+        // (rows 3 * width bytes apart), and the coefficients and planes of the re-saved file (of `resave` only those two)
+        JpegDec resave;
         uint8_t* d_src = nullptr;
         size_t src_cap = 0;
         // the JPEG writer of the synchronous calls (JpegEnc above)
@@ -167,14 +183,14 @@ struct Ctx {
         bool dec_high = false;                                 // ICELK_JPEG_ASYNC_PRIO=high|normal
         int crop_bytes_per_block = enc::kDefaultBytesPerBlock;   // icelk_jpeg_crop_config
         int crop_next_ticket = 1;
-        hipStream_t fetch = nullptr;                           // D2H copies of finished scans (abi_jpeg_crop.hip: fetch_scan)
+        hipStream_t fetch = nullptr;                           // D2H copies of finished scans (abi_jpeg_job.hip: jpeg_fetch_scan)
     } jpeg;
 
     // ---- abi_plot.hip: the segment picture, allocated at first use.  A working set that belongs to plotting alone: the
-    // re-save's and the crop jobs' buffers are never touched, so crops and pictures can be asked for together.  Of `job`
-    // only d_rgb (what k_plot_resolve writes and the forward kernel reads), d_rcoef and enc are used
+    // re-save's and the crop jobs' buffers are never touched, so crops and pictures can be asked for together.
+    // rs.d_rgb is what k_plot_resolve writes and the forward kernel reads
     struct Plot {
-        JpegJob job;
+        JpegResave rs;
         uint8_t* d_bg = nullptr;        // Wo x Ho gray plane, padded to four pixels
         uint32_t* d_counts = nullptr;   // lines | dots, each padded to four pixels
         uint32_t* d_tables = nullptr;   // TL | TD
@@ -182,11 +198,11 @@ struct Ctx {
         size_t bg_cap = 0, counts_cap = 0, tracks_cap = 0;
     } plot;
 
-    // ---- abi_map.hip: the velocity map, allocated at first use.  A working set of its own, as the segment picture's: of
-    // `job` only d_rgb (what k_map_resolve writes and the forward kernel reads), d_rcoef and enc are used.  The day's arrows
+    // ---- abi_map.hip: the velocity map, allocated at first use.  A working set of its own, as the segment picture's:
+    // rs.d_rgb is what k_map_resolve writes and the forward kernel reads.  The day's arrows
     // of icelk_map_arrows_set stay resident until release / destroy
     struct Map {
-        JpegJob job;
+        JpegResave rs;
         uint32_t* d_planes = nullptr;   // base | top | count, each padded to four pixels
         double* d_items = nullptr;      // per call: cells, outline and the caller's arrows of every panel
         uint8_t* d_measured = nullptr;
@@ -542,7 +558,7 @@ bool jpeg_huff_config_ok(int subseq_bits, int max_hops, int max_rounds);
 int jpeg_host_decode(const uint8_t* data, size_t len, int16_t* coef, uint64_t capacity);
 // abi_jpeg_ingest.hip: the ingest steps (listed at the head of that file)
 int check_crop_box(Ctx* c, const icelk_jpeg_info_t& I, int left, int top, int right, int bottom, int* w, int* h);
-int jpeg_plane_args(Ctx* c, Ctx::JpegJob& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* A,
+int jpeg_plane_args(Ctx* c, Ctx::JpegDec& B, const icelk_jpeg_info_t* I, int left, int top, int right, int bottom, JpegIdctArgs* A,
                     JpegOutArgs* out);
 size_t jpeg_plane_bytes(const icelk_jpeg_info_t& I);
 void jpeg_plane_layout(const icelk_jpeg_info_t& I, int left, int top, int right, int bottom, int16_t* d_coef, uint8_t* d_planes,
@@ -555,13 +571,14 @@ int jpeg_planes(Ctx* c, const icelk_jpeg_info_t* I, const int16_t* coef, int lef
 int jpeg_rgb_out(Ctx* c, const icelk_jpeg_info_t& I, JpegOutArgs& O, uint8_t* out, int stride);
 const char* jpeg_open_error(int rc);
 int jpeg_open(Ctx* c, const uint8_t* data, uint64_t len, JpegIndex& X, icelk_jpeg_info_t* info, bool* host_only);
-int jpeg_host_into_job(Ctx* c, Ctx::JpegJob& J, const uint8_t* data, uint64_t len, const icelk_jpeg_info_t& I, hipStream_t st,
+int jpeg_host_into_job(Ctx* c, Ctx::JpegDec& J, const uint8_t* data, uint64_t len, const icelk_jpeg_info_t& I, hipStream_t st,
                        std::vector<int16_t>& keep);
-int jpeg_huff_setup(Ctx* c, Ctx::JpegJob& B, const JpegIndex& X, uint64_t len, JpegHuffArgs* H, bool headroom);
-int jpeg_huff_stage(Ctx* c, Ctx::JpegJob& J, const JpegIndex& X, const uint8_t* file, const void* seg, const void* tabs, uint64_t len,
+int jpeg_huff_setup(Ctx* c, Ctx::JpegDec& B, const JpegIndex& X, uint64_t len, JpegHuffArgs* H, bool headroom);
+int jpeg_huff_stage(Ctx* c, Ctx::JpegDec& J, const JpegIndex& X, const uint8_t* file, const void* seg, const void* tabs, uint64_t len,
                     hipStream_t st);
 void jpeg_huff_finish_phases(hipStream_t st, const JpegHuffArgs& H);
 int jpeg_huff_device(Ctx* c, const uint8_t* data, uint64_t len, icelk_jpeg_info_t* info);
+void jpeg_dec_free(Ctx::JpegDec& D);
 // abi_jpeg_resave.hip
 void jpeg_resave_destroy(Ctx* c);
 int jpeg_resave_check(Ctx* c, int w, int h, int quality);
@@ -570,10 +587,13 @@ int jpeg_crop_fwd_on(Ctx* c, hipStream_t st, const JpegOutArgs& O, int16_t* d_co
 // abi_jpeg_enc.hip
 void jpeg_enc_destroy(Ctx* c);
 void jpeg_enc_free(Ctx::JpegEnc& E);
+void jpeg_resave_free(Ctx::JpegResave& R);
 int jpeg_enc_rc(Ctx* c, int rc);
 int jpeg_enc_prepare(Ctx* c, Ctx::JpegEnc& E);
 int jpeg_encode_on(Ctx* c, Ctx::JpegEnc& E, hipStream_t st, const enc::Layout& L, const int16_t* d_coef);
-// abi_jpeg_async.hip
+int jpeg_deliver_file(Ctx* c, const Ctx::JpegEnc& E, hipStream_t st, bool pending, const icelk_jpeg_info_t& I, const uint8_t* comment,
+                      uint64_t comment_len, uint8_t* out, uint64_t capacity, uint64_t* len);
+// abi_jpeg_job.hip: the driver of a file in flight (its steps are listed at the head of that file)
 void jpeg_async_destroy(Ctx* c);
 int jpeg_async_sync(Ctx* c);
 int jpeg_take_job(Ctx* c, int* idx);
@@ -582,10 +602,23 @@ int jpeg_stage_file(Ctx* c, Ctx::JpegJob& B, const JpegIndex& X, size_t seg_byte
 bool jpeg_verdict_here(const Ctx::JpegJob& B);
 int jpeg_await_verdict(Ctx* c, Ctx::JpegJob& B);
 void jpeg_huff_stats_of(const Ctx::JpegJob& B, icelk_jpeg_huff_stats_t* st);
-// abi_jpeg_crop.hip
 int jpeg_budget_buffers(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L);
 int jpeg_encode_budgeted(Ctx* c, Ctx::JpegJob& B, const enc::Layout& L);
 int jpeg_fetch_scan(Ctx* c, Ctx::JpegJob& B, uint64_t n, bool again);
+struct JpegBox {
+    int left, top, right, bottom;
+};
+int jpeg_job_open(Ctx* c, Ctx::JpegJobKind kind, bool want_file, const uint8_t* data, uint64_t len, const JpegBox& box, int quality,
+                  std::unique_ptr<JpegIndex>* X, int* idx, enc::Layout* L);
+int jpeg_job_start(Ctx* c, Ctx::JpegJob& B, int slot, const uint8_t* data, uint64_t len, JpegIndex& X, const JpegBox& box,
+                   const enc::Layout& L);
+void jpeg_job_abandon(Ctx::JpegJob& B);
+int jpeg_job_verdict(Ctx* c, Ctx::JpegJob& B, icelk_jpeg_huff_stats_t* huff, uint32_t* coder);
+int jpeg_job_redo_on_host(Ctx* c, Ctx::JpegJob& B, const enc::Layout* L);
+int jpeg_job_settle(Ctx* c, Ctx::JpegJob& B);
+int jpeg_job_state(const Ctx::JpegJob& B, bool with_coder);
+int jpeg_job_file(Ctx* c, const Ctx::JpegJob& B, const uint8_t* comment, uint64_t comment_len, uint8_t* out, uint64_t capacity,
+                  uint64_t* len);
 // abi_plot.hip
 void plot_destroy(Ctx* c);
 // abi_map.hip

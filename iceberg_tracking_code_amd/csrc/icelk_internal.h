@@ -68,7 +68,7 @@ enum KernelId {
     K_JPEG_ENC_PACK,    // ... the blocks' bits at their offsets
     K_JPEG_ENC_FF,      // ... FF bytes of the packed stream
     K_JPEG_ENC_STUFF,   // ... the stream with a 00 behind every FF
-    K_JPEG_ENC_PACK_BUDGET,    // the device-sized forms of a crop job (abi_jpeg_crop.hip)
+    K_JPEG_ENC_PACK_BUDGET,    // the device-sized forms of a job with a file (abi_jpeg_job.hip)
     K_JPEG_ENC_FF_BUDGET,
     K_JPEG_ENC_STUFF_BUDGET,
     K_JPEG_CROP_RGB,           // the crop box of the decoded planes as R G B into the job
@@ -179,7 +179,7 @@ void launch_jpeg_enc_scan(hipStream_t s, uint32_t* v, uint32_t n, uint32_t* tota
 void launch_jpeg_enc_pack(hipStream_t s, const JpegEncArgs& A);
 void launch_jpeg_enc_ff(hipStream_t s, const uint32_t* packed, uint32_t nchunks, uint32_t* wg_ff);
 void launch_jpeg_enc_stuff(hipStream_t s, const uint32_t* packed, uint32_t nbytes, uint32_t nchunks, const uint32_t* wg_off, uint8_t* out);
-// The device-sized forms of a crop job (abi_jpeg_crop.hip): `cap` bytes are allocated for the stuffed scan, packed (whole
+// The device-sized forms of a job with a file (abi_jpeg_job.hip): `cap` bytes are allocated for the stuffed scan, packed (whole
 // chunks of it, zeroed) and out; the sizes come from ctl, where count and the scans left them.  wg_ff has
 // enc::groups_of(enc::chunks_of(cap)) entries, which the second scan runs over.
 void launch_jpeg_enc_pack_budget(hipStream_t s, const JpegEncArgs& A, uint32_t cap);

@@ -184,7 +184,7 @@ ICELK_ENC_FN bool encode_block(Get get, int pred, const uint32_t* dc, const uint
     return ok;
 }
 
-// ---- the budget of a scan whose sizes stay on the device (the crop jobs: abi_jpeg_crop.hip) ----------------------------
+// ---- the budget of a scan whose sizes stay on the device (jobs with a file: abi_jpeg_job.hip) ----------------------------
 // Such a job may take `cap` = bytes per block x blocks bytes for the stuffed scan; the packed and the stuffed stream are
 // allocated to that before anything is enqueued, and the kernels read the sizes the count and the scans left in the
 // control words.  Every decision they take on those words is one of the functions below, which the host walk

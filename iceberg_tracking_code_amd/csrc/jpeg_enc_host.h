@@ -156,6 +156,41 @@ inline int header_host(const icelk_jpeg_info_t* info, const uint8_t* comment, ui
     return out && B.n <= capacity ? ICELK_OK : ICELK_ECAP;
 }
 
+// ---- the file around a scan: header | scan | EOI ------------------------------------------------------------------------------
+// the file's length
+inline uint64_t file_len(const icelk_jpeg_info_t& I, const uint8_t* comment, uint64_t comment_len, uint64_t scan_len)
+{
+    Bytes H(nullptr, 0);
+    header_bytes(I, comment, comment_len, H);
+    return H.n + scan_len + 2;
+}
+
+// Header and EOI of a file whose scan takes scan_len bytes into `out`; *scan_at: where the scan goes, which the caller
+// fills (from host memory: file_into; from the device: jpeg_deliver_file, abi_jpeg_enc.hip; as it is coded: encode_host).
+// ICELK_ECAP with nothing written: out is too small (or NULL); *len says what the file takes in either case
+inline int file_frame(const icelk_jpeg_info_t& I, const uint8_t* comment, uint64_t comment_len, uint64_t scan_len, uint8_t* out,
+                      uint64_t capacity, uint64_t* len, uint8_t** scan_at)
+{
+    *len = file_len(I, comment, comment_len, scan_len);
+    if (!out || capacity < *len) return ICELK_ECAP;
+    Bytes B(out, capacity);
+    header_bytes(I, comment, comment_len, B);
+    *scan_at = out + B.n;
+    out[B.n + scan_len] = 0xFF;
+    out[B.n + scan_len + 1] = 0xD9;
+    return ICELK_OK;
+}
+
+// the whole file around a scan in host memory
+inline int file_into(const icelk_jpeg_info_t& I, const uint8_t* comment, uint64_t comment_len, const uint8_t* scan, uint64_t scan_len,
+                     uint8_t* out, uint64_t capacity, uint64_t* len)
+{
+    uint8_t* at = nullptr;
+    if (int rc = file_frame(I, comment, comment_len, scan_len, out, capacity, len, &at)) return rc;
+    if (scan_len) memcpy(at, scan, (size_t)scan_len);
+    return ICELK_OK;
+}
+
 // bits -> bytes, most significant first, a 00 behind every FF
 struct ByteSink {
     Bytes& B;
@@ -186,7 +221,7 @@ struct HostBlock {
 };
 
 // the whole file.  ICELK_ECAP: out is too small (or NULL), *len says what it takes; ICELK_EARG: a coefficient without a
-// code -- found by a counting pass before anything is written
+// code -- found by the measuring pass before anything is written
 inline int encode_host(const icelk_jpeg_info_t* info, const int16_t* coef, const uint8_t* comment, uint64_t comment_len, uint8_t* out,
                        uint64_t capacity, uint64_t* len)
 {
@@ -194,25 +229,26 @@ inline int encode_host(const icelk_jpeg_info_t* info, const int16_t* coef, const
     if (!len || !coef || !comment_ok(comment, comment_len)) return ICELK_EARG;
     if (int rc = layout_of(info, &L)) return rc;
     const Codes& C = codes();
-    for (uint32_t s = 0; s < L.blocks; s++) {
-        const Place P = place(L, s);
-        CountSink n;
-        if (!encode_block(HostBlock{coef + P.at}, P.pred == kNoPred ? 0 : coef[P.pred], C.dc[P.table], C.ac[P.table], n)) return ICELK_EARG;
-    }
-    Bytes B(out, capacity);
-    header_bytes(*info, comment, comment_len, B);
-    ByteSink S(B);
-    for (uint32_t s = 0; s < L.blocks; s++) {
-        const Place P = place(L, s);
-        encode_block(HostBlock{coef + P.at}, P.pred == kNoPred ? 0 : coef[P.pred], C.dc[P.table], C.ac[P.table], S);
-    }
-    S.pad();
-    B.put16(0xFFD9);
-    *len = B.n;
-    return out && B.n <= capacity ? ICELK_OK : ICELK_ECAP;
+    // the scan twice: measured (into no buffer), then written where file_frame says
+    auto scan_into = [&](Bytes& B) {
+        ByteSink S(B);
+        for (uint32_t s = 0; s < L.blocks; s++) {
+            const Place P = place(L, s);
+            if (!encode_block(HostBlock{coef + P.at}, P.pred == kNoPred ? 0 : coef[P.pred], C.dc[P.table], C.ac[P.table], S)) return false;
+        }
+        S.pad();
+        return true;
+    };
+    Bytes N(nullptr, 0);
+    if (!scan_into(N)) return ICELK_EARG;
+    uint8_t* at = nullptr;
+    if (int rc = file_frame(*info, comment, comment_len, N.n, out, capacity, len, &at)) return rc;
+    Bytes B(at, N.n);
+    scan_into(B);
+    return ICELK_OK;
 }
 
-// ---- the budgeted chain of a crop job (abi_jpeg_crop.hip), in the kernels' order --------------------------------------------
+// ---- the budgeted chain of a job with a file (abi_jpeg_job.hip), in the kernels' order --------------------------------------------
 // count, scan, pack, ff, scan, stuff and the verdict as k_jpeg_enc.hip runs them when the sizes stay on the device, with
 // the decisions of jpeg_enc.h: `packed` and `out` hold exactly cap = bytes_per_block x blocks bytes and nothing is read
 // or written outside them, whatever the control words say.  force / force_mask: words of ctl (bit JE_* of the mask) that

@@ -25,7 +25,7 @@
 // Lanes diverge per coefficient in count and pack (zero or not, ZRL or not), as the decoder's lanes do per symbol; the
 // loop counter, the table addresses and everything between the walks are uniform.  No scratch in any kernel.
 //
-// The device-sized forms (k_jpeg_enc_pack_budget, _ff_budget, _stuff_budget; the crop jobs of abi_jpeg_crop.hip) run the
+// The device-sized forms (k_jpeg_enc_pack_budget, _ff_budget, _stuff_budget; the jobs with a file of abi_jpeg_job.hip) run the
 // same bodies with the sizes read from the control words instead of from the host: packed and stuffed stream are
 // allocated to a capacity of `cap` bytes beforehand, and each of the three leaves the whole grid -- a uniform branch on
 // two loaded words -- when the stream does not fit it (jpeg_enc.h: packed_fits, live_bytes, stuffed_fits).  Behind them

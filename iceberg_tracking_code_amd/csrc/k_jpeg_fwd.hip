@@ -32,7 +32,7 @@
 // may lie in blocks the source's inverse DCT did not transform (it transforms the box's blocks and the filter's
 // neighbours): they hold whatever the buffer held, are computed with, and are never picked.  Stores are blocks of the
 // re-saved file's layout only, walked by the grid, not by the data.  So the kernel is safe on whatever a decode that did
-// not settle left in the planes (abi_jpeg_async.hip): it turns garbage samples into bounded coefficients.
+// not settle left in the planes (abi_jpeg_job.hip): it turns garbage samples into bounded coefficients.
 #include "icelk_internal.h"
 #include "jpeg_fwd.h"
 #include "jpeg_rgb.h"

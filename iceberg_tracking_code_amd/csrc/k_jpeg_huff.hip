@@ -13,7 +13,7 @@
 //                       non-zero coefficients as 2-byte stores, DC as the difference.
 //   k_jpeg_dc_*         the DC differences summed up in scan order inside every restart interval: per-chunk sums, a
 //                       prefix sum of the chunk sums, and the pass that writes the values.
-//   k_jpeg_huff_verdict the asynchronous ingest only (abi_jpeg_async.hip): what the host reads from ctl[] between the
+//   k_jpeg_huff_verdict the asynchronous ingest only (abi_jpeg_job.hip): what the host reads from ctl[] between the
 //                       phases of a synchronous file, worked out at the end of the chain and published to pinned words.
 //
 // Divergence.  Lanes of a wave decode different bits, so they diverge at every symbol by nature; what is kept uniform

@@ -9,7 +9,9 @@
 // report, so a read or a store outside them is AddressSanitizer's to find; the file goes to BLOB.jpg with the comment
 // "blob" (the test compares it with the library's and with Pillow's).  Then the longest blocks the tables can code -- all
 // AC coefficients at +-1023, DC differences of +-2047 -- are written into a buffer of exactly their size, and a
-// coefficient without a code is refused.
+// coefficient without a code is refused.  Every file is also put together again by the assembler the library's finish calls
+// use (enc::file_into: header, a scan from host memory, EOI), from a scan of exactly its size into a buffer of exactly the
+// file's length, and into one a byte short of it, which must be refused with the length.
 #define __host__
 #define __device__
 #define __forceinline__ inline
@@ -30,6 +32,30 @@ namespace {
 
 const uint8_t kComment[] = {'b', 'l', 'o', 'b'};
 
+int assembled = 0;
+
+// `file` (its header takes hlen bytes) once more, from its scan alone
+void assemble_again(const icelk_jpeg_info_t& info, const std::vector<uint8_t>& file, uint64_t hlen, const char* what)
+{
+    const std::vector<uint8_t> scan(file.begin() + (size_t)hlen, file.end() - 2);
+    if (icelk::enc::file_len(info, kComment, sizeof(kComment), scan.size()) != file.size()) die("assembler: length", what);
+    uint64_t len = 0;
+    std::vector<uint8_t> shorter(file.size() - 1, 0xAA), exact(file.size());
+    if (icelk::enc::file_into(info, kComment, sizeof(kComment), scan.data(), scan.size(), shorter.data(), shorter.size(), &len) != ICELK_ECAP ||
+        len != file.size())
+        die("assembler: capacity not checked", what);
+    for (uint8_t b : shorter)
+        if (b != 0xAA) die("assembler: wrote into a buffer it refused", what);
+    len = 0;
+    if (icelk::enc::file_into(info, kComment, sizeof(kComment), scan.data(), scan.size(), nullptr, file.size(), &len) != ICELK_ECAP || len != file.size())
+        die("assembler: null buffer taken", what);
+    len = 0;
+    if (icelk::enc::file_into(info, kComment, sizeof(kComment), scan.data(), scan.size(), exact.data(), exact.size(), &len) != ICELK_OK ||
+        len != file.size() || exact != file)
+        die("assembler: file", what);
+    assembled++;
+}
+
 // the file of (info, coef) in a buffer of exactly its size; every smaller capacity is refused with the size
 std::vector<uint8_t> file_of(const icelk_jpeg_info_t& info, const std::vector<int16_t>& coef, const char* what)
 {
@@ -45,6 +71,7 @@ std::vector<uint8_t> file_of(const icelk_jpeg_info_t& info, const std::vector<in
     std::vector<uint8_t> head((size_t)hlen);
     if (icelk::enc::header_host(&info, kComment, sizeof(kComment), head.data(), hlen, &again) != ICELK_OK || again != hlen) die("header", what);
     if (memcmp(head.data(), out.data(), (size_t)hlen)) die("header differs from the file's", what);
+    assemble_again(info, out, hlen, what);
     return out;
 }
 
@@ -102,6 +129,7 @@ int main(int argc, char** argv)
 {
     for (int i = 1; i < argc; i++) run(argv[i]);
     extremes();
+    printf("assembled: %d of %d\n", assembled, argc);
     printf("done\n");
     return 0;
 }

@@ -1,6 +1,6 @@
 // jpeg_lanes_states.cpp -- the functions of csrc/jpeg_lanes.h called from states that are not the true ones, as plain C++
 // under the host's sanitizers (test_jpeg_lanes_states_host.py builds and runs this program; nothing of the library is
-// linked).  The asynchronous JPEG ingest (csrc/abi_jpeg_async.hip) cannot stop its chain of kernels when a file hits the
+// linked).  The asynchronous JPEG ingest (csrc/abi_jpeg_job.hip) cannot stop its chain of kernels when a file hits the
 // work bound or does not settle: scan, write and DC pass then run on whatever phase 1 left.  That this stores nothing
 // outside the coefficient buffer, reads nothing outside the file and ends is a property of jpeg_lanes.h alone, so it is
 // shown here, where an overrun lands in a redzone, and never on a device.

@@ -1,4 +1,4 @@
-"""GPU: JPEG files decoded ahead of their frame (csrc/abi_jpeg_async.hip, k_jpeg_huff_verdict) against the synchronous
+"""GPU: JPEG files decoded ahead of their frame (csrc/abi_jpeg_async.hip on csrc/abi_jpeg_job.hip, k_jpeg_huff_verdict) against the synchronous
 call on the same bytes under the same `jpeg_huff_config`: one file, several in flight and their working sets reused,
 the caller's buffer, damaged and unsupported files, the tracker fed by `prefetch_jpeg`, the pipelined folder driver;
 the verdict kernel on the edges of its bounds (the round a file settles in, more than 64 rounds, the longest chain)

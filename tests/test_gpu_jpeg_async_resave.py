@@ -1,4 +1,4 @@
-"""GPU: the slot-bound re-save job (csrc/abi_jpeg_async.hip: icelk_upload_jpeg_file_async_resave, icelk_jpeg_async_finish,
+"""GPU: the slot-bound re-save job (csrc/abi_jpeg_async.hip on csrc/abi_jpeg_job.hip: icelk_upload_jpeg_file_async_resave, icelk_jpeg_async_finish,
 icelk_jpeg_async_finish_file) -- one enqueued job per photo that leaves the slot the frame the reference tracks on and,
 when asked, the crop file it would have written.  The slot is compared with the synchronous `upload_jpeg_file(resave=)`
 and with `upload_bgr` of Pillow's reopened crop, the file with the bytes of Pillow's `Image.open(f).crop(box).save(out)`.

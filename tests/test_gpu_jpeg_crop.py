@@ -1,4 +1,4 @@
-"""GPU: the crop stage on its own (csrc/abi_jpeg_crop.hip, the device-sized kernels of csrc/k_jpeg_enc.hip,
+"""GPU: the crop stage on its own (csrc/abi_jpeg_crop.hip on csrc/abi_jpeg_job.hip, the device-sized kernels of csrc/k_jpeg_enc.hip,
 iceberg_tracking_code_amd/crop.py) against the file the reference's crop step writes (camtools.py:64-104, Pillow's
 `Image.open(p).crop(box).save(out)`), against the synchronous calls on the same bytes, and -- the two-pass route --
 against the one-pass folder driver.  Every comparison is equality of bytes or arrays.

@@ -41,6 +41,8 @@ def test_host_writer_under_sanitizers(tmp_path):
     run = subprocess.run([exe] + blobs, capture_output=True, text=True, timeout=120)
     assert run.returncode == 0, run.stdout + run.stderr
     assert "extremes:" in run.stdout and run.stdout.rstrip().endswith("done")
+    n = len(CASES) + 1     # every case's file and the extremes', through the file assembler at exactly and one short of its length
+    assert "assembled: %d of %d" % (n, n) in run.stdout
     for path, (rgb, q) in zip(blobs, images):
         with open(path + ".jpg", "rb") as f:
             got = f.read()

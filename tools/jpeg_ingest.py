@@ -43,7 +43,7 @@ resave-file    the re-saved crop as a file (`Context.jpeg_resave_file`, csrc/k_j
         kernel against the bytes it moves, the whole call by the host clock split into kernels, the rest (two
         synchronisations, the copy to the host, the header) and the file write; then photos per second of the folder
         driver with resave="reference", without and with save_crops, alternating, three runs each.
-crop-folder    the crop step on its own (`crop_image_sequence`, csrc/abi_jpeg_crop.hip) on the folder of resave-file: the same
+crop-folder    the crop step on its own (`crop_image_sequence`, csrc/abi_jpeg_crop.hip on csrc/abi_jpeg_job.hip) on the folder of resave-file: the same
         yardstick first (one thread, a pool of 16 processes forked before the GPU is touched); then, alternating behind
         untimed runs, three runs each of (a) the synchronous way to the same folder -- `upload_jpeg_file(resave=)`,
         `jpeg_resave_file()` and the write, photo by photo on the calling thread -- and (b) `crop_image_sequence`; every
