@@ -10,6 +10,8 @@ Also here: the `.npz` wire format consumed by s2_cam_to_utm.py:177,197-198,233-2
 """
 import datetime as dt
 import os
+from contextlib import suppress
+from itertools import takewhile
 
 import numpy as np
 
@@ -41,6 +43,15 @@ def segment_time_ok(names, track_len_sec):
 def save_tracks(npzname, tracks, trackquality):
     """np.savez(npzname, tracks=tracks, trackquality=trackquality) (s1:395)."""
     np.savez(npzname, tracks=tracks, trackquality=trackquality)
+
+
+class _Ahead:
+    """A frame whose upload was started ahead of its push: its slot, whether its JPEG file is still to be finished, and the
+    crop file asked for -- path, comment and, once they are there, its bytes: without them (`abort()`) nothing is written."""
+    __slots__ = ("slot", "in_flight", "crop_file", "comment", "data")
+
+    def __init__(self, slot, in_flight=False, crop_file=None, comment=None):
+        self.slot, self.in_flight, self.crop_file, self.comment, self.data = slot, in_flight, crop_file, comment, None
 
 
 class SegmentTracker:
@@ -76,12 +87,9 @@ class SegmentTracker:
         self.seg_first = 0
         self.active = False
         self.n_detected = 0
-        self._prefetched = []     # slots holding frames whose upload was started ahead of time
-        self._jpeg_jobs = set()   # ... those of them whose JPEG file is still to be finished (`prefetch_jpeg`)
-        self._crop_files = {}     # prefetch slot -> (path, comment, the crop file's bytes or None while its job is in flight)
+        self._queue = []          # frames whose upload was started ahead of time, in the order they will be pushed
         self.lookahead = bool(lookahead)
         self.pair_launch = bool(pair_launch) and self.lookahead   # see `_step`: joint launch across a segment change
-        self._pyr_ahead = set()   # slots whose pyramid was enqueued ahead of their step
         # how many steps ahead of a detection frame its min-distance stage / its corner candidates may start (`_step`)
         self.begin_ahead, self.prepare_ahead, self.stage_lag = 4, 6, 2
         self.stage_nowait = True  # the host round trip of a detection is taken without waiting (icelk_seg_detect_stage_try)
@@ -95,20 +103,22 @@ class SegmentTracker:
         # ctx.seg_archive(..., closed=closed).  closed=False: the segment is still the current one (the switch follows);
         # closed=True: the switch has happened (its last pair went out in a joint launch, see `_step`)
         self.on_close = None
-        self._advanced = False    # the pair (cur, next) has gone out already, with the joint launch of this step
-        self._advanced_slot = None   # ... and `next` was announced to sit in this slot
-        self._det_queue = []      # detections in flight, oldest first: (frame counter, step at which it was begun)
-        self._begun_upto = -1     # latest frame whose detection has been begun
-        self._prep_upto = -1      # latest frame whose corner candidates have been prepared ahead
-        self._staged = False      # a new segment waits in the spare set for the switch
-        self._staged_for = None   # ... the detection frame it belongs to
-        self._staged_n = 0
+        self._advanced = None     # the slot announced for the next frame, when the joint launch of this step took its pair
+        self._reset_ahead()
         self.pairs_launched = 0   # frame pairs handed to the tracker kernels so far (a joint launch carries two)
         self._closed_now = False  # the latest step closed a segment: `plot_closed` may draw it on that step's frame
 
+    def _reset_ahead(self):
+        """Nothing is under way for the frames after `counter - 1`."""
+        self._det_queue = []      # detections in flight, oldest first: (frame counter, step at which it was begun)
+        # latest frame whose detection has been begun / whose corner candidates have been prepared ahead
+        self._begun_upto = self._prep_upto = self.counter - 1
+        self._staged = None       # (detection frame, corners): a new segment waits in the spare set for the switch
+        self._pyr_ahead = set()   # slots whose pyramid was enqueued ahead of their step
+
     # -- frame sources --------------------------------------------------------------------------
     def _next_slot(self):
-        if self._prefetched:
+        if self._queue:
             raise RuntimeError("prefetched frames are pending; consume them with push_prefetched()")
         return (self.cur + 1) % self.n_slots
 
@@ -117,25 +127,25 @@ class SegmentTracker:
         self.ctx.upload_gray(s, frame_gray)
         return self._step(s, wait)
 
-    def _crop_bytes(self, crop_file, comment):
-        """The file of the re-save the upload just ran (`Context.jpeg_resave_file`), or None when none is asked for.  Taken
-        before the step is enqueued, so that the call's synchronisations wait for the upload alone."""
-        return None if crop_file is None else self.ctx.jpeg_resave_file(comment)
+    @staticmethod
+    def _check_crop(crop_file, resave):
+        if crop_file is not None and resave is None:
+            raise ValueError("crop_file needs resave: the file written is the re-saved crop")
 
     @staticmethod
     def _write_crop(crop_file, data):
-        """Written on the calling thread once the step is enqueued: the device tracks meanwhile."""
-        if crop_file is not None:
+        """Written on the calling thread once the step is enqueued: the device tracks meanwhile.  No bytes, no file."""
+        if data is not None:
             with open(crop_file, "wb") as f:
                 f.write(data)
 
     def _push_upload(self, upload, frame, wait, variant, crop, resave, crop_file, comment):
         """The body of `push_bgr` and `push_jpeg`: `upload` is the Context method that fills the slot."""
-        if crop_file is not None and resave is None:
-            raise ValueError("crop_file needs resave: the file written is the re-saved crop")
+        self._check_crop(crop_file, resave)
         s = self._next_slot()
         upload(s, frame, variant, crop, resave)
-        data = self._crop_bytes(crop_file, comment)
+        # the re-saved crop's file, taken before the step is enqueued: the call's synchronisations wait for the upload alone
+        data = None if crop_file is None else self.ctx.jpeg_resave_file(comment)
         seg = self._step(s, wait)
         self._write_crop(crop_file, data)
         return seg
@@ -172,12 +182,17 @@ class SegmentTracker:
         most n_slots - 2 uploads may be in flight (previous and current frame stay resident)."""
         s = self._next_prefetch_slot()
         self.ctx.upload_gray_async(s, pinned_ptr, self.w, self.h, stride)
-        self._prefetched.append(s)
+        self._queue.append(_Ahead(s))
+
+    @property
+    def prefetched(self):
+        """The slots of the frames prefetched and not yet pushed, in their order."""
+        return [q.slot for q in self._queue]
 
     def _next_prefetch_slot(self):
-        if len(self._prefetched) >= self.n_slots - 2:
+        if len(self._queue) >= self.n_slots - 2:
             raise RuntimeError("too many frames in flight for %d slots" % self.n_slots)
-        last = self._prefetched[-1] if self._prefetched else self.cur
+        last = self._queue[-1].slot if self._queue else self.cur
         return (last + 1) % self.n_slots
 
     def prefetch_jpeg(self, data, variant=4, crop=None, resave=None, crop_file=None, comment=None):
@@ -186,67 +201,54 @@ class SegmentTracker:
         `prefetch_pinned`'s.  What the host can see of a bad file raises here (ValueError), and no slot is taken; the
         rest comes out of `push_prefetched`.  `resave`, `crop_file`, `comment`: as `push_bgr` -- the re-save and, with
         `crop_file`, the coding of the crop's file are part of the enqueued job; `push_prefetched` writes the file."""
-        if crop_file is not None and resave is None:
-            raise ValueError("crop_file needs resave: the file written is the re-saved crop")
+        self._check_crop(crop_file, resave)
         s = self._next_prefetch_slot()
         self.ctx.upload_jpeg_file_async(s, data, variant, crop, resave, crop_file is not None)
-        self._prefetched.append(s)
-        self._jpeg_jobs.add(s)
-        if crop_file is not None:
-            self._crop_files[s] = (crop_file, comment, None)
+        self._queue.append(_Ahead(s, True, crop_file, comment))
 
-    def _upload_bgr_ahead(self, s, frame, variant, crop, resave, crop_file, comment):
-        """The synchronous `upload_bgr(resave=)` into prefetch slot s.  The crop's file is taken at once -- the handle's "most
+    def _upload_bgr_ahead(self, q, frame, variant, crop, resave, crop_file, comment):
+        """The synchronous `upload_bgr(resave=)` into the slot of q.  The crop's file is taken at once -- the handle's "most
         recent re-save" is overwritten by the next one -- and its bytes are held until the frame is pushed."""
-        if crop_file is not None and resave is None:
-            raise ValueError("crop_file needs resave: the file written is the re-saved crop")
-        self._crop_files.pop(s, None)
-        self.ctx.upload_bgr(s, frame, variant, crop, resave)
+        self._check_crop(crop_file, resave)
+        q.data = None
+        self.ctx.upload_bgr(q.slot, frame, variant, crop, resave)
         if crop_file is not None:
-            self._crop_files[s] = (crop_file, comment, self.ctx.jpeg_resave_file(comment))
+            q.crop_file, q.comment, q.data = crop_file, comment, self.ctx.jpeg_resave_file(comment)
 
     def prefetch_bgr(self, frame, variant=4, crop=None, resave=None, crop_file=None, comment=None):
         """A host-decoded frame into the next prefetch slot (a plain `upload_bgr`): the file of a folder that the device
         decoder does not take, between files that it does.  `resave`, `crop_file`, `comment`: as `push_bgr`."""
-        s = self._next_prefetch_slot()
-        self._upload_bgr_ahead(s, frame, variant, crop, resave, crop_file, comment)
-        self._prefetched.append(s)
+        q = _Ahead(self._next_prefetch_slot())
+        self._upload_bgr_ahead(q, frame, variant, crop, resave, crop_file, comment)
+        self._queue.append(q)
 
     def replace_prefetched_bgr(self, frame, variant=4, crop=None, resave=None, crop_file=None, comment=None):
         """After `push_prefetched` has raised for the JPEG file at the head of the queue: fill its slot from the
         host-decoded frame instead; `push_prefetched` may then be called again.  `resave`, `crop_file`, `comment`: as
         `push_bgr`."""
-        if not self._prefetched:
+        if not self._queue:
             raise RuntimeError("no prefetched frame")
-        s = self._prefetched[0]
-        if s in self._jpeg_jobs:
+        if self._queue[0].in_flight:
             raise RuntimeError("the frame at the head of the queue has not failed")
-        self._upload_bgr_ahead(s, frame, variant, crop, resave, crop_file, comment)
+        self._upload_bgr_ahead(self._queue[0], frame, variant, crop, resave, crop_file, comment)
 
     def push_prefetched(self, wait=True):
-        if not self._prefetched:
+        if not self._queue:
             raise RuntimeError("no prefetched frame")
-        s = self._prefetched[0]
-        if s in self._jpeg_jobs:
+        q = self._queue[0]
+        if q.in_flight:
             # the verdict on the file, the host decoder if it is asked for.  A file that raises leaves the queue as it is
-            # and its slot empty (`replace_prefetched_bgr`)
-            self._jpeg_jobs.discard(s)
-            crop_file, comment, _ = self._crop_files.pop(s, (None, None, None))
-            if crop_file is None:
-                self.ctx.jpeg_async_finish(s)
+            # and its slot empty, with no bytes for a crop file (`replace_prefetched_bgr`)
+            q.in_flight = False
+            if q.crop_file is None:
+                self.ctx.jpeg_async_finish(q.slot)
             else:
-                self._crop_files[s] = (crop_file, comment, self.ctx.jpeg_async_finish_file(s, comment)[0])
-        crop_file, _, data = self._crop_files.pop(s, (None, None, None))
-        self._prefetched.pop(0)
-        q = self._prefetched
+                q.data = self.ctx.jpeg_async_finish_file(q.slot, q.comment)[0]
+        self._queue.pop(0)
         # nothing is built or detected ahead on a frame whose verdict is still out: the list ends in front of it
-        ahead = []
-        for s_k in q[:self.MAX_AHEAD]:
-            if s_k in self._jpeg_jobs and self.ctx.jpeg_async_poll(s_k) != 1:
-                break
-            ahead.append(s_k)
-        seg = self._step(s, wait, *ahead)
-        self._write_crop(crop_file, data)      # once the step is enqueued, as `_push_upload`
+        ahead = takewhile(lambda a: not a.in_flight or self.ctx.jpeg_async_poll(a.slot) == 1, self._queue[:self.MAX_AHEAD])
+        seg = self._step(q.slot, wait, *[a.slot for a in ahead])
+        self._write_crop(q.crop_file, q.data)  # once the step is enqueued, as `_push_upload`
         return seg
 
     def push_slot(self, slot, wait=True, *ahead):
@@ -293,122 +295,125 @@ class SegmentTracker:
         holds the first back (`seg_track_defer`), switches, and tracks (d, d+1) at once: both pairs go to the device as
         ONE tracker launch and step d+1 has no pair left to launch.  Results are those of the serial order in every
         case."""
-        out = None
         self._closed_now = False
-        prev = self.cur
-        T = self.track_len
         c = self.counter
-        detect = c % T == 0
-        ahead = self.lookahead and T >= 2
-        bs = self.fp.get("blockSize", 3)
-        lk_tail = (self.lk["winSize"], self.lk["maxLevel"], self.lk["criteria"], self.lk.get("minEigThreshold", 1e-4),
-                   self.fb_threshold)
-        slot_of = {0: slot}
-        for k, s_k in enumerate(ahead_slots[:self.MAX_AHEAD]):
-            if s_k is None:
-                break
-            slot_of[k + 1] = s_k
-        next_slot, next2_slot = slot_of.get(1), slot_of.get(2)
+        detect = c % self.track_len == 0
+        ahead = self.lookahead and self.track_len >= 2
+        known = ahead_slots[:self.MAX_AHEAD] + (None,)                   # None ends the list
+        slot_of = dict(enumerate((slot,) + known[:known.index(None)]))   # frame c + k sits in slot_of[k]
         self._pyr_ahead.discard(slot)
-        staged_now = self._staged and self._staged_for == c
-        if detect and ahead and not staged_now and not self._staged and self._det_queue and self._det_queue[0][0] == c \
-                and self._det_queue[0][1] < c:
-            # the detection of this frame was begun steps ago and its tail has run on the device: adopt it now (waits only if
-            # the device is behind)
-            self._staged_n = self.ctx.seg_detect_stage(self.fp["maxCorners"])
-            self._staged, self._staged_for = True, c
-            self._det_queue.pop(0)
-            staged_now = True
-        if detect and not staged_now and not (self._det_queue and self._det_queue[0][0] == c):
-            # nothing was started ahead for this detection frame: start it now, on its own stream, so that it runs
-            # beside the tracker launch below (the reference does them back to back, s1:323-326 then s1:437)
+        staged_now = detect and self._adopt_staged(c, ahead)
+        if detect and not staged_now:
+            self._begin_unstarted(c, slot)
+        joint = self._launch_pair(c, slot, slot_of.get(1), detect and staged_now and not wait)
+        if self.lookahead:
+            self._pyramids_ahead(slot, slot_of.get(1), slot_of.get(2) if self.pair_launch else None)
+        out = self._change_segment(c, wait, staged_now) if detect and not joint else None
+        if ahead:
+            self._work_ahead(c, slot_of)
+        self._closed_now = detect and c > 0
+        self.cur, self.counter = slot, c + 1
+        return out
+
+    def _adopt_staged(self, c, ahead):
+        """Phase 1, at a detection frame c.  If its detection was begun steps ago and its tail has run on the device, adopt it
+        now (waits only if the device is behind).  Returns whether the segment of frame c waits in the spare set."""
+        q = self._det_queue
+        if self._staged is None and ahead and q and q[0][0] == c and q[0][1] < c:
+            self._staged = (c, self.ctx.seg_detect_stage(self.fp["maxCorners"]))
+            q.pop(0)
+        return self._staged is not None and self._staged[0] == c
+
+    def _begin_unstarted(self, c, slot):
+        """Phase 2, at a detection frame c with nothing staged.  If nothing was started ahead for it, start it now, on its own
+        stream, beside the tracker launch of phase 3 (the reference does them back to back, s1:323-326 then s1:437)."""
+        if not (self._det_queue and self._det_queue[0][0] == c):
             self._detect_begin(slot)
             self._det_queue.append((c, c))
             self._begun_upto = c
-        joint = False
-        if self._advanced:
-            # the pair (prev, slot) went out with the launch of the previous step -- on the strength of the slot that was
-            # announced for this frame then
-            if slot != self._advanced_slot:
+
+    def _enter_segment(self, c, n_detected):
+        """The segment that starts at frame c is the current one: the bookkeeping of a joint and of a plain change."""
+        self.n_detected, self._staged, self.seg_first, self.active = n_detected, None, c, True
+
+    def _launch_pair(self, c, slot, next_slot, may_join):
+        """Phase 3: the pair (previous frame, this frame) goes to the tracker, unless it went out with the launch of the step
+        before -- on the strength of the slot that was announced for this frame then.  Where a staged segment starts here and
+        nothing is read (`may_join`) and the next frame's slot is known: the joint launch of `_step`, and True."""
+        if self._advanced is not None:
+            if slot != self._advanced:
                 raise RuntimeError("frame pushed in slot %d, but slot %d was announced for it one step ago (its pair has "
-                                   "been launched already)" % (slot, self._advanced_slot))
-            self._advanced = False
+                                   "been launched already)" % (slot, self._advanced))
+            self._advanced = None
         elif self.active:
-            joint = detect and self.pair_launch and not wait and staged_now and next_slot is not None and c > 0
-            if joint:
-                self.ctx.seg_track_defer(prev, slot, *lk_tail)
+            lk_tail = (self.lk["winSize"], self.lk["maxLevel"], self.lk["criteria"], self.lk.get("minEigThreshold", 1e-4),
+                       self.fb_threshold)
+            if may_join and self.pair_launch and next_slot is not None and c > 0:
+                self.ctx.seg_track_defer(self.cur, slot, *lk_tail)
                 self.ctx.seg_switch()
                 self.ctx.seg_track(slot, next_slot, *lk_tail, wait=False)
                 self.pairs_launched += 2
-                self._advanced, self._advanced_slot = True, next_slot
+                self._advanced = next_slot
                 if self.on_close is not None:
                     self.on_close(self.seg_first, True)
-                self.n_detected = self._staged_n
-                self._staged = False
-                self.seg_first = c
-            else:
-                self.ctx.seg_track(prev, slot, *lk_tail, wait=False)
-                self.pairs_launched += 1
-        if self.lookahead:
-            # pyramids of the following frames, on the copy stream, in the shadow of the tracker launch above (two ahead
-            # when a joint launch may need frame c+2 at step c+1)
-            for s_k in (next_slot, next2_slot if self.pair_launch else None):
-                if s_k is None or s_k in self._pyr_ahead or s_k in (slot, prev) or (s_k == next_slot and self._advanced):
-                    continue
-                if self._resident:
-                    self.ctx.drop_pyramid(s_k)   # a resident ring is rebuilt on every visit
-                self.ctx.build_pyramid_ahead(s_k, self.lk["winSize"], self.lk["maxLevel"])
-                self._pyr_ahead.add(s_k)
-        if detect and not joint:
-            if c > 0 and self.on_close is not None:
-                self.on_close(self.seg_first, False)
-            if c > 0 and wait:
-                tracks, quality = self.ctx.seg_read()
-                out = (self.seg_first, tracks, quality)
-            if staged_now:
-                self.ctx.seg_switch()
-                self.n_detected = self._staged_n
-                self._staged = False
-            else:
-                self.n_detected = self.ctx.seg_detect_finish(self.fp["maxCorners"])   # the oldest in flight: frame c's
-                self._det_queue.pop(0)
-            self.active = True
-            self.seg_first = c
-        if ahead:
-            # the oldest detection in flight: its host round trip, and the new segment into the spare set (behind this
-            # step's switch, if there was one: the spare set is the one after the current) -- once its kernels have had
-            # `stage_lag` steps, or when its frame is next
-            if self._det_queue and not self._staged:
-                d, begun = self._det_queue[0]
-                if d > c and begun < c and (c - begun >= self.stage_lag or d - c <= 1):
-                    # without waiting while there is a later step to do it at; the segment is needed at step d
-                    # (waiting only at d itself was measured too: the tail of the detection -- sort, corner list, the new
-                    # segment's tables -- then starts when the tracker launch already needs it: C3 3 820 -> 3 290 pairs/s)
-                    if d - c <= self.stage_block_at or not self.stage_nowait:
-                        n_new = self.ctx.seg_detect_stage(self.fp["maxCorners"])
-                    else:
-                        n_new = self.ctx.seg_detect_stage_try(self.fp["maxCorners"])
-                    if n_new is not None:
-                        self._staged_n = n_new
-                        self._staged, self._staged_for = True, d
-                        self._det_queue.pop(0)
-            # min-distance stage of the next detection frame not begun yet: up to `begin_ahead` steps ahead, two
-            # detections in flight at most
-            d = max(self._begun_upto, c) // T * T + T
-            if len(self._det_queue) < 2 and 1 <= d - c <= self.begin_ahead and slot_of.get(d - c) is not None:
-                self._detect_begin(slot_of[d - c])
-                self._det_queue.append((d, c))
-                self._begun_upto = d
-            # corner candidates of the detection frame after the one begun last, once the frame's slot is known (six steps
-            # ahead at most) and the candidates prepared before have been adopted by their seg_detect_begin
-            d = max(self._begun_upto, self._prep_upto, c) // T * T + T
-            if self._prep_upto <= self._begun_upto and 1 <= d - c <= self.prepare_ahead and slot_of.get(d - c) is not None:
-                self.ctx.seg_detect_prepare(slot_of[d - c], self.use_mask, bs)
-                self._prep_upto = d
-        self._closed_now = detect and c > 0
-        self.cur = slot
-        self.counter += 1
+                self._enter_segment(c, self._staged[1])
+                return True
+            self.ctx.seg_track(self.cur, slot, *lk_tail, wait=False)
+            self.pairs_launched += 1
+        return False
+
+    def _pyramids_ahead(self, slot, next_slot, next2_slot):
+        """Phase 4: pyramids of the following frames, on the copy stream, in the shadow of the tracker launch of phase 3
+        (two ahead when a joint launch may need frame c+2 at step c+1; not the frame that launch has just tracked into)."""
+        for s_k in (next_slot, next2_slot):
+            if s_k is None or s_k in self._pyr_ahead or s_k in (slot, self.cur, self._advanced):
+                continue
+            if self._resident:
+                self.ctx.drop_pyramid(s_k)   # a resident ring is rebuilt on every visit
+            self.ctx.build_pyramid_ahead(s_k, self.lk["winSize"], self.lk["maxLevel"])
+            self._pyr_ahead.add(s_k)
+
+    def _change_segment(self, c, wait, staged_now):
+        """Phase 5, at a detection frame c whose pair went out plain.  The finished segment is handed over (`on_close`; read
+        for the push to return if the caller waits); then the switch, or else the end of frame c's detection, the oldest."""
+        if c > 0 and self.on_close is not None:
+            self.on_close(self.seg_first, False)
+        out = (self.seg_first, *self.ctx.seg_read()) if c > 0 and wait else None
+        if staged_now:
+            self.ctx.seg_switch()
+            self._enter_segment(c, self._staged[1])
+        else:
+            self._enter_segment(c, self.ctx.seg_detect_finish(self.fp["maxCorners"]))
+            self._det_queue.pop(0)
         return out
+
+    def _work_ahead(self, c, slot_of):
+        """Phase 6, in this order.  Stage: the host round trip of the oldest detection in flight, and the new segment into
+        the spare set (behind this step's switch, if there was one: the spare set is the one after the current) -- once its
+        kernels have had `stage_lag` steps, or when its frame is next; without waiting while there is a later step to do
+        it at, the segment is needed at step d.  (Waiting only at d itself was measured too: the tail of the detection --
+        sort, corner list, the new segment's tables -- then starts when the tracker launch already needs it: C3 3 820 ->
+        3 290 pairs/s.)  Begin: the next detection frame not begun yet, up to `begin_ahead` steps ahead, two in flight at
+        most.  Prepare: the detection frame after the one begun last, once its slot is known (six steps ahead at most) and
+        the candidates prepared before have been adopted by their seg_detect_begin."""
+        T = self.track_len
+        if self._det_queue and self._staged is None:
+            d, begun = self._det_queue[0]
+            if d > c and begun < c and (c - begun >= self.stage_lag or d - c <= 1):
+                wait = d - c <= self.stage_block_at or not self.stage_nowait
+                n_new = (self.ctx.seg_detect_stage if wait else self.ctx.seg_detect_stage_try)(self.fp["maxCorners"])
+                if n_new is not None:
+                    self._staged = (d, n_new)
+                    self._det_queue.pop(0)
+        d = max(self._begun_upto, c) // T * T + T
+        if len(self._det_queue) < 2 and 1 <= d - c <= self.begin_ahead and slot_of.get(d - c) is not None:
+            self._detect_begin(slot_of[d - c])
+            self._det_queue.append((d, c))
+            self._begun_upto = d
+        d = max(self._begun_upto, self._prep_upto, c) // T * T + T
+        if self._prep_upto <= self._begun_upto and 1 <= d - c <= self.prepare_ahead and slot_of.get(d - c) is not None:
+            self.ctx.seg_detect_prepare(slot_of[d - c], self.use_mask, self.fp.get("blockSize", 3))
+            self._prep_upto = d
 
     def plot_closed(self, width=PLOT_WIDTH, stamp="", quality=PLOT_QUALITY):
         """The picture of the segment the latest push closed (the one it returned), drawn on the frame of that push -- the
@@ -434,22 +439,16 @@ class SegmentTracker:
         number of frames consumed so far."""
         self.ctx.seg_flush()
         self.ctx.seg_detect_cancel()
-        for s in sorted(self._jpeg_jobs):
-            # JPEG files in flight are dropped: finished for their working set's sake, whatever they end as
-            try:
-                self.ctx.jpeg_async_finish(s)
-            except ValueError:
-                pass
-        self._jpeg_jobs = set()
-        self._crop_files = {}
-        if self._advanced:
+        for s in sorted(q.slot for q in self._queue if q.in_flight):
+            with suppress(ValueError):    # JPEG files in flight are dropped: finished for their working set's sake,
+                self.ctx.jpeg_async_finish(s)   # whatever they end as
+        for q in self._queue:     # the frames stay queued in their slots; no crop file of theirs is written
+            q.in_flight, q.data = False, None
+        if self._advanced is not None:
             # a joint launch has already tracked the pair into the frame announced for the next step (it sat in its slot):
             # that frame counts as consumed -- it is never a detection frame (track_len >= 2 wherever pairs are joined)
-            self.cur, self.counter, self._advanced = self._advanced_slot, self.counter + 1, False
-        self._det_queue = []
-        self._staged, self._staged_for, self._staged_n = False, None, 0
-        self._begun_upto = self._prep_upto = self.counter - 1
-        self._pyr_ahead = set()
+            self.cur, self.counter, self._advanced = self._advanced, self.counter + 1, None
+        self._reset_ahead()
         return self.counter
 
     def close(self):

@@ -292,7 +292,7 @@ def test_failed_file_is_replaced_and_abort_drops_jobs(tracker_case):
     trk.prefetch_jpeg(files[4])
     trk.prefetch_jpeg(files[5])
     assert trk.abort() == 4
-    for s in (trk._prefetched[0], trk._prefetched[1]):
+    for s in (trk.prefetched[0], trk.prefetched[1]):
         trk.ctx.upload_bgr(s, np.zeros((240, 320, 3), np.uint8))     # the slots are nobody's any more
     trk.close()
 

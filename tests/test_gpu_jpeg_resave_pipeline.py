@@ -201,7 +201,7 @@ def test_p3_failed_file_is_replaced_and_abort_drops_jobs(folder, tmp_path):
         assert trk.abort() == 4
         assert sorted(os.listdir(str(out_dir))) == sorted(names[:4])
         # the slots are nobody's any more: each takes a new job, whose file is right
-        for n, s in zip((4, 5, 6), list(trk._prefetched)):
+        for n, s in zip((4, 5, 6), list(trk.prefetched)):
             trk.ctx.upload_jpeg_file_async(s, files[usable[n]], 4, FOLDER_CROP, resave="reference", crop_file=True)
             assert trk.ctx.jpeg_async_finish_file(s, None)[0] == folder["cropped"][names[n]], names[n]
         for n in (4, 5, 6):                                         # their frames are in the slots: pushing continues
