@@ -16,15 +16,16 @@ from .utm import CameraModel, REF_UTM_FILTER, cam_to_utm, project_segment, proje
 from .sequence import track_image_sequence  # noqa: F401
 from .crop import crop_image_sequence  # noqa: F401
 from .gridding import bin_velocities, create_grid_across_fjord, points_in_polygon  # noqa: F401
-from .day_grid import utm_to_gridded_utm, utm_to_gridded_utm_days  # noqa: F401
+from .day_grid import closest_image, utm_to_gridded_utm, utm_to_gridded_utm_days  # noqa: F401
 from .postprocess import (VelocityCube, average_periods, average_spatially_temporally, combine_npzs,  # noqa: F401
                           daily_averages, npz_to_csv, npz_to_mat, save_csv, velocities_to_regular_grid)
 from .calibration import CalibrationResult, ShorelineScene, calibrate, run_calibration  # noqa: F401
 from .jpeg import (JpegCoefficients, UnsupportedJpeg, decode_jpeg, read_jpeg, read_jpeg_lanes, resave_coefficients,  # noqa: F401
-                   resave_rgb, resave_tables, encode_jpeg, resave_bytes, source_comment)
+                   resave_rgb, resave_tables, encode_jpeg, resave_bytes, source_comment, thumbnail, thumbnail_host,
+                   thumbnail_size)
 from .plot import plot_glyph, plot_name, plot_overlay_host, plot_size, plot_stamp  # noqa: F401
-from .velocity_map import (gist_rainbow_table, map_descriptor, map_glyph, map_layout, map_name, map_overlay_host, map_picture,  # noqa: F401
-                           map_strings, map_texts, map_view, scaled_arrows)
+from .velocity_map import (gist_rainbow_table, map_descriptor, map_glyph, map_inset_array, map_layout, map_name, map_overlay_host, map_picture,  # noqa: F401
+                           map_insets, map_strings, map_texts, map_view, scaled_arrows)
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

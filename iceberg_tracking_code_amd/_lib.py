@@ -74,6 +74,21 @@ class MapDesc(C.Structure):
 
 map_desc_p = C.POINTER(MapDesc)
 
+
+class MapInset(C.Structure):
+    """icelk_map_inset_t"""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("index", C.c_int32), ("label_px", C.c_int32), ("label_py", C.c_int32),
+                ("reserved", C.c_int32), ("label", C.c_char * 56)]
+
+
+class MapInsetPixels(C.Structure):
+    """icelk_map_inset_pixels_t"""
+    _fields_ = [("rgb", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("stride", C.c_int32), ("reserved", C.c_int32)]
+
+
+map_inset_p = C.POINTER(MapInset)
+MAP_INSETS_MAX = 8
+
 JPEG_CROP_ROUTES = ("device", "host-huffman", "over-budget")   # ICELK_JPEG_CROP_*
 JPEG_TABLE_BYTES = 11328
 JPEG_FALLBACK_NONE, JPEG_FALLBACK_BOUND, JPEG_FALLBACK_STREAM, JPEG_FALLBACK_SIZE = 0, 1, 2, 3
@@ -142,6 +157,14 @@ SIGNATURES = {
     "icelk_map_arrows_set": (C.c_int, [handle_p, f64p, i32p, C.c_int]),
     "icelk_map_arrows_release": (C.c_int, [handle_p]),
     "icelk_map_draw": (C.c_int, [handle_p, map_desc_p, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_thumb_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, i32p, i32p]),
+    "icelk_thumb_host": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
+    "icelk_map_overlay_insets_host": (C.c_int, [map_desc_p, f64p, i32p, C.c_int, map_inset_p, C.c_int, C.POINTER(MapInsetPixels), u8p, C.c_int]),
+    "icelk_jpeg_thumb_file": (C.c_int, [handle_p, vp, C.c_uint64, C.c_int, C.c_int, u8p, C.c_int]),
+    "icelk_map_inset_set_file": (C.c_int, [handle_p, C.c_int, vp, C.c_uint64, C.c_int, C.c_int]),
+    "icelk_map_inset_set_pixels": (C.c_int, [handle_p, C.c_int, u8p, C.c_int, C.c_int, C.c_int]),
+    "icelk_map_inset_release": (C.c_int, [handle_p]),
+    "icelk_map_draw_insets": (C.c_int, [handle_p, map_desc_p, map_inset_p, C.c_int, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

@@ -10,9 +10,9 @@ import numpy as np
 from . import _lib
 from ._lib import check, f32p, u8p
 from .plot import PLOT_QUALITY, PLOT_WIDTH, _stamp_arg, _tracks3, plot_size
-from .velocity_map import _resident_args, map_descriptor
+from .velocity_map import _resident_args, map_descriptor, map_inset_array
 from .jpeg import (UnsupportedJpeg, _comment_args, _encode_call, _rgb3, _stats_dict, describe_jpeg, resave_coefficients,
-                   resave_quality)
+                   resave_quality, thumbnail_host, thumbnail_size)
 
 TERM_CRITERIA_COUNT = 1
 TERM_CRITERIA_MAX_ITER = 1
@@ -302,6 +302,17 @@ class Context:
         i = describe_jpeg(data)
         out = np.empty((i.height, i.width, 3) if i.ncomp == 3 else (i.height, i.width), np.uint8)
         self._ck_jpeg(self._lib.icelk_jpeg_decode_rgb_file(self._h, data, len(data), _u8(out), out.strides[0]))
+        return out
+
+    def jpeg_thumb_file(self, data, size):
+        """The (th, tw, 3) thumbnail of size = (tw, th) of a JPEG file given as bytes: decoded on the device as
+        `jpeg_decode_rgb_file` decodes it and reduced there from the component planes, every channel the exact area average
+        (icelk_jpeg_thumb_file; `jpeg.thumbnail_size` gives the size of a box).  Equal to `jpeg.thumbnail_host` of Pillow's
+        pixels."""
+        data = bytes(data)
+        tw, th = (int(v) for v in size)
+        out = np.empty((max(th, 1), max(tw, 1), 3), np.uint8)
+        self._ck_jpeg(self._lib.icelk_jpeg_thumb_file(self._h, data, len(data), tw, th, _u8(out), out.strides[0]))
         return out
 
     def jpeg_resave_rgb(self, rgb, quality=75):
@@ -669,9 +680,40 @@ class Context:
     def map_arrows_release(self):
         self._ck(self._lib.icelk_map_arrows_release(self._h))
 
+    def map_inset_set(self, index, source, box=None):
+        """Resident inset `index` (0 .. 7) of the maps' pictures, until the next set of that index, `map_inset_release` or
+        `close`; returns its (tw, th).  `source`: the bytes of a JPEG file -- decoded and reduced on the device to fit
+        box = (box_w, box_h) (icelk_map_inset_set_file); a file the device decoder does not take is opened with Pillow and
+        reduced with `jpeg.thumbnail_host` -- or an H x W (x 3) uint8 array, reduced on the host to fit `box` (None: taken as
+        it is) and uploaded (icelk_map_inset_set_pixels)."""
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            data = bytes(source)
+            if box is None:
+                raise ValueError("a JPEG file needs a box to be fitted into")
+            try:
+                info = describe_jpeg(data)
+                size = thumbnail_size(info.width, info.height, box)
+                self._ck_jpeg(self._lib.icelk_map_inset_set_file(self._h, int(index), data, len(data), size[0], size[1]))
+                return size
+            except UnsupportedJpeg:
+                import io
+                from PIL import Image
+                source = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+        a = np.asarray(source)
+        if box is not None:
+            a = thumbnail_host(a, thumbnail_size(a.shape[1], a.shape[0], box))
+        a = _rgb3(a if a.ndim == 3 else np.repeat(a[..., None], 3, axis=2))
+        self._ck(self._lib.icelk_map_inset_set_pixels(self._h, int(index), _u8(a), a.shape[1], a.shape[0], a.strides[0]))
+        return a.shape[1], a.shape[0]
+
+    def map_inset_release(self):
+        self._ck(self._lib.icelk_map_inset_release(self._h))
+
     def map_draw(self, picture, want_rgb=False):
         """The picture a dict of velocity_map describes (`velocity_map.map_picture` makes one of a window), as the bytes of a
-        JPEG file (icelk_map_draw; the rules are DESIGN.md 7.7).  Rasterised and coded on the device; the file is what
+        JPEG file (icelk_map_draw; the rules are DESIGN.md 7.7).  With picture["insets"] = [dict(index=, at=(x0, y0),
+        label=(px, py, text) | None)] the resident thumbnails of `map_inset_set` are pasted in, each with its label
+        (icelk_map_draw_insets); without the key, or with an empty list, the call is icelk_map_draw's.  Rasterised and coded on the device; the file is what
         `Image.fromarray(rgb).save(f, "JPEG", quality=quality)` writes for the picture's R G B.  want_rgb: (bytes, that
         R G B (height, width, 3) uint8), for tests.  IcelkError (code ICELK_ESTATE) when a panel draws the resident arrows
         and none are set."""
@@ -681,8 +723,13 @@ class Context:
             rgb = np.empty((max(d.height, 1), max(d.width, 1), 3), np.uint8)
             rgb_ptr, stride = _u8(rgb), rgb.strides[0]
         guess = getattr(self, "_map_file_guess", 1 << 18)
-        data = _encode_call(lambda out, cap, n: self._lib.icelk_map_draw(self._h, C.byref(d), rgb_ptr, stride, out, cap, n), guess,
-                            "icelk_map_draw", self._h)
+        if picture.get("insets"):
+            insets, n_insets = map_inset_array(picture["insets"])
+            data = _encode_call(lambda out, cap, n: self._lib.icelk_map_draw_insets(self._h, C.byref(d), insets, n_insets, rgb_ptr, stride, out, cap, n),
+                                guess, "icelk_map_draw_insets", self._h)
+        else:
+            data = _encode_call(lambda out, cap, n: self._lib.icelk_map_draw(self._h, C.byref(d), rgb_ptr, stride, out, cap, n), guess,
+                                "icelk_map_draw", self._h)
         self._map_file_guess = max(1 << 16, len(data) + len(data) // 4)   # the next window's picture is about as large
         del keep
         return (data, rgb) if want_rgb else data

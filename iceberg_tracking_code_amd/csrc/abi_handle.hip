@@ -14,6 +14,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "jpeg_enc_pack_budget", "jpeg_enc_ff_budget", "jpeg_enc_stuff_budget", "jpeg_crop_rgb", "jpeg_crop_verdict", "jpeg_crop_fwd",
     "plot_background", "plot_clear", "plot_scatter", "plot_resolve",
     "map_clear", "map_cells", "map_polyline", "map_arrows", "map_resolve",
+    "jpeg_thumb", "map_inset",
 };
 
 std::string g_create_err;

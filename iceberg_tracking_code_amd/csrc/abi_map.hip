@@ -2,13 +2,16 @@
 // per measured cell coloured by speed, with switch 2 every velocity vector of the window in a second panel, the outline, the
 // cameras, four strings and a colour bar -- rasterised on the device and handed to the JPEG writer that is there as well.
 //
-//   host    icelk_map_glyph, icelk_map_overlay_host: map_raster.h on the CPU; no handle, re-entrant
+//   host    icelk_map_glyph, icelk_map_overlay_host: map_raster.h on the CPU; no handle, re-entrant.
+//           icelk_map_overlay_insets_host: the same, then thumb_raster.h's paste
 //   device  icelk_map_arrows_set / _release (a day's vectors, resident like the s4 cube) and icelk_map_draw.  On the handle's
 //           compute stream: k_map_clear, then per panel k_map_cells, k_map_polyline, k_map_arrows, then k_map_resolve
 //           (k_map.hip) into the R G B buffer of a working set of the map's own (Ctx::Map), then the re-save's forward
 //           kernel (jpeg_fwd_on) at the caller's quality and the entropy coder (jpeg_encode_on) on that set, then header,
 //           scan and EOI into the caller's buffer.  The call waits for the device.  After ICELK_ECAP the call is simply
 //           repeated: the picture is a function of its arguments.
+//           icelk_map_draw_insets: the same with one k_map_inset (k_thumb.hip) per inset between k_map_resolve and the
+//           forward kernel, from the resident thumbnails of abi_thumb.hip, whose header states that kernel's bounds
 //
 // Bounds, store by store.  Everything is sized from the picture (Wo x Ho, px = Wo Ho padded to four pixels) and the
 // descriptor's counts before anything is enqueued, and check_desc has refused every view that is not inside the picture.
@@ -43,6 +46,7 @@ void map_destroy(Ctx* c)
         if (q) hipFree(q);
     delete M.h_scene;
     jpeg_resave_free(M.rs);
+    map_insets_free(c);
     M = Ctx::Map{};
 }
 
@@ -167,6 +171,36 @@ int overlay_host(const icelk_map_desc_t* d, map::Scene& S, const double* residen
     return ICELK_OK;
 }
 
+// The insets of a picture against the thumbnails `have` (kMaxInsets entries, host or device memory): what is refused, and
+// the paste's arguments.  The descriptor has passed check_desc
+int check_insets(const icelk_map_desc_t* d, const icelk_map_inset_t* in, int n, const icelk_map_inset_pixels_t* have, thumb::Inset* out,
+                 const char** why)
+{
+    *why = "insets: a count outside 0 .. 8 or a null array";
+    if (n < 0 || n > thumb::kMaxInsets || (n > 0 && (!in || !have))) return ICELK_EARG;
+    for (int k = 0; k < n; k++) {
+        const icelk_map_inset_t& I = in[k];
+        *why = "an inset index outside 0 .. 7";
+        if (I.index < 0 || I.index >= thumb::kMaxInsets) return ICELK_EARG;
+        const icelk_map_inset_pixels_t& T = have[I.index];
+        *why = "an inset's index holds no thumbnail (icelk_map_inset_set_file, icelk_map_inset_set_pixels)";
+        if (!T.rgb) return ICELK_ESTATE;
+        *why = "a thumbnail that is not wholly inside the picture";
+        if (T.w < 1 || T.h < 1 || T.stride < 3 * T.w || I.x0 < 0 || I.y0 < 0 || I.x0 > d->width - T.w || I.y0 > d->height - T.h) return ICELK_EARG;
+        *why = "a label position beyond 2^20";
+        if (I.label_px < -thumb::kLabelLimit || I.label_px > thumb::kLabelLimit || I.label_py < -thumb::kLabelLimit || I.label_py > thumb::kLabelLimit)
+            return ICELK_EARG;
+        out[k].x0 = I.x0, out[k].y0 = I.y0, out[k].w = T.w, out[k].h = T.h, out[k].px = T.rgb, out[k].pitch = T.stride;
+        *why = "a label of more than 48 characters, or a character outside 0-9 - : . / space A-Z a-z , ( )";
+        char text[sizeof(I.label) + 1];
+        memcpy(text, I.label, sizeof(I.label));
+        text[sizeof(I.label)] = 0;
+        if (!map::make_text(text, I.label_px, I.label_py, &out[k].label)) return ICELK_EARG;
+    }
+    *why = nullptr;
+    return ICELK_OK;
+}
+
 struct Picture {
     icelk_jpeg_info_t info;   // of the file
     enc::Layout L;
@@ -210,7 +244,7 @@ int grow_picture(Ctx* c, const icelk_map_desc_t* d, const Picture& Q)
 }
 
 int draw_and_encode(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked, const Picture& Q, uint8_t* rgb, int rgb_stride, uint8_t* file,
-                    uint64_t capacity, uint64_t* len)
+                    uint64_t capacity, uint64_t* len, const thumb::Inset* insets = nullptr, int n_insets = 0)
 {
     Ctx::Map& M = c->map;
     const hipStream_t st = c->stream;
@@ -273,6 +307,13 @@ int draw_and_encode(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked
         launch_map_resolve(st, M.d_scene, Wo, Ho, base, top, count, M.rs.d_rgb);
     }
     if (int rc = check_launch(c, "map_resolve")) return rc;
+    for (int k = 0; k < n_insets; k++) {
+        {
+            ProfScope p(c, K_MAP_INSET);
+            launch_map_inset(st, insets[k], Wo, Ho, M.rs.d_rgb);
+        }
+        if (int rc = check_launch(c, "map_inset")) return rc;
+    }
     if (int rc = jpeg_fwd_on(c, st, M.rs.d_rgb, M.rs.d_rcoef, Wo, Ho, Q.info)) return rc;
     if (int rc = jpeg_encode_on(c, M.rs.enc, st, Q.L, M.rs.d_rcoef)) return rc;   // synchronises
     if (rgb) HIPCHK(c, hipMemcpy2DAsync(rgb, rgb_stride, M.rs.d_rgb, 3 * (size_t)Wo, 3 * (size_t)Wo, Ho, hipMemcpyDeviceToHost, st));
@@ -322,6 +363,23 @@ int icelk_map_overlay_host(const icelk_map_desc_t* d, const double* resident, co
     return rc;
 }
 
+int icelk_map_overlay_insets_host(const icelk_map_desc_t* d, const double* resident, const int32_t* group, int n_resident,
+                                  const icelk_map_inset_t* insets, int n_insets, const icelk_map_inset_pixels_t* resident_insets,
+                                  uint8_t* rgb, int rgb_stride)
+{
+    map::Scene* S = new (std::nothrow) map::Scene;
+    if (!S) return ICELK_ENOMEM;
+    const bool desc_ok = !check_desc(d, S);
+    delete S;
+    if (!rgb || !desc_ok) return ICELK_EARG;
+    thumb::Inset I[thumb::kMaxInsets];
+    const char* why;
+    if (int rc = check_insets(d, insets, n_insets, resident_insets, I, &why)) return rc;
+    if (int rc = icelk_map_overlay_host(d, resident, group, n_resident, rgb, rgb_stride)) return rc;
+    thumb::paste_host(I, n_insets, d->width, d->height, rgb, (size_t)rgb_stride);
+    return ICELK_OK;
+}
+
 int icelk_map_arrows_set(icelk_t* h, const double* arrows, const int32_t* group_or_null, int n)
 {
     if (!h) return ICELK_EARG;
@@ -358,16 +416,26 @@ int icelk_map_arrows_release(icelk_t* h)
     return ICELK_OK;
 }
 
-int icelk_map_draw(icelk_t* h, const icelk_map_desc_t* d, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
-                   uint64_t* len)
+// icelk_map_draw (no insets: nothing below touches them) and icelk_map_draw_insets
+static int map_draw_call(icelk_t* h, const char* range, const icelk_map_desc_t* d, const icelk_map_inset_t* insets, int n_insets,
+                         uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len)
 {
     if (!h) return ICELK_EARG;
     Ctx* c = C(h);
-    Range rg("icelk map_draw");
+    Range rg(range);
     map::Scene* S = new (std::nothrow) map::Scene;
     if (!S) FAIL(c, ICELK_ENOMEM, "the map's scene");
     Picture Q;
     int rc = check_device_call(c, d, S, rgb_or_null, rgb_stride, len, &Q);
+    thumb::Inset I[thumb::kMaxInsets];
+    if (rc == ICELK_OK && (insets || n_insets)) {
+        icelk_map_inset_pixels_t have[thumb::kMaxInsets];
+        for (int k = 0; k < thumb::kMaxInsets; k++)
+            have[k] = icelk_map_inset_pixels_t{c->map.d_inset[k], c->map.inset_w[k], c->map.inset_h[k], 3 * c->map.inset_w[k], 0};
+        const char* why;
+        rc = check_insets(d, insets, n_insets, have, I, &why);
+        if (rc) c->err = why;
+    }
     if (rc == ICELK_OK) {
         for (int k = 0; k < d->n_panels; k++)
             if (d->panel[k].resident && d->panel[k].group >= 0 && !c->map.d_group) {
@@ -383,9 +451,21 @@ int icelk_map_draw(icelk_t* h, const icelk_map_desc_t* d, uint8_t* rgb_or_null, 
         }
     }
     if (rc == ICELK_OK) rc = grow_picture(c, d, Q);
-    if (rc == ICELK_OK) rc = draw_and_encode(c, d, *S, Q, rgb_or_null, rgb_stride, file, capacity, len);
+    if (rc == ICELK_OK) rc = draw_and_encode(c, d, *S, Q, rgb_or_null, rgb_stride, file, capacity, len, I, n_insets);
     delete S;
     return rc;
+}
+
+int icelk_map_draw(icelk_t* h, const icelk_map_desc_t* d, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
+                   uint64_t* len)
+{
+    return map_draw_call(h, "icelk map_draw", d, nullptr, 0, rgb_or_null, rgb_stride, file, capacity, len);
+}
+
+int icelk_map_draw_insets(icelk_t* h, const icelk_map_desc_t* d, const icelk_map_inset_t* insets, int n_insets, uint8_t* rgb_or_null,
+                          int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len)
+{
+    return map_draw_call(h, "icelk map_draw_insets", d, insets, n_insets, rgb_or_null, rgb_stride, file, capacity, len);
 }
 
 }  // extern "C"

@@ -200,7 +200,7 @@ struct Ctx {
 
     // ---- abi_map.hip: the velocity map, allocated at first use.  A working set of its own, as the segment picture's:
     // rs.d_rgb is what k_map_resolve writes and the forward kernel reads.  The day's arrows
-    // of icelk_map_arrows_set stay resident until release / destroy
+    // of icelk_map_arrows_set and the inset thumbnails of icelk_map_inset_set_* stay resident until release / destroy
     struct Map {
         JpegResave rs;
         uint32_t* d_planes = nullptr;   // base | top | count, each padded to four pixels
@@ -213,6 +213,9 @@ struct Ctx {
         int32_t* d_group = nullptr;     // resident: NULL or n
         int n_arrows = 0;
         bool have_arrows = false;
+        // resident: the thumbnails of icelk_map_inset_set_file / _pixels, R G B rows 3 inset_w bytes apart; NULL: not set
+        uint8_t* d_inset[thumb::kMaxInsets] = {};
+        int inset_w[thumb::kMaxInsets] = {}, inset_h[thumb::kMaxInsets] = {};
     } map;
 
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
@@ -623,6 +626,8 @@ int jpeg_job_file(Ctx* c, const Ctx::JpegJob& B, const uint8_t* comment, uint64_
 void plot_destroy(Ctx* c);
 // abi_map.hip
 void map_destroy(Ctx* c);
+// abi_thumb.hip
+void map_insets_free(Ctx* c);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

@@ -10,6 +10,7 @@
 #include "jpeg_lanes.h"
 #include "plot_raster.h"
 #include "map_raster.h"
+#include "thumb_raster.h"
 
 namespace icelk {
 
@@ -83,6 +84,8 @@ enum KernelId {
     K_MAP_POLYLINE,            // ... the outline
     K_MAP_ARROWS,              // ... shafts and heads: top index and hit count
     K_MAP_RESOLVE,             // ... planes, cameras, bars and texts -> R G B
+    K_JPEG_THUMB,              // the inset photographs (k_thumb.hip): decoded planes -> area-averaged R G B thumbnail
+    K_MAP_INSET,               // ... a thumbnail and its label into the map's R G B
     K_COUNT_
 };
 
@@ -279,6 +282,11 @@ void launch_map_arrows(hipStream_t s, const map::View& V, int w, bool pivot_mid,
                        int Wo, uint32_t* top, uint32_t* count);
 void launch_map_resolve(hipStream_t s, const map::Scene* d_scene, int Wo, int Ho, const uint32_t* base, const uint32_t* top,
                         const uint32_t* count, uint8_t* rgb);
+
+// k_thumb.hip: the inset photographs.  A: the planes of a whole decoded file (left = top = 0, ow x oh the image), dst the
+// Wt x Ht thumbnail (R G B, dst_pitch bytes per row); ncomp 1 or 3.  I.px: device memory; rgb: the map's R G B, 3 Wo bytes per row
+void launch_jpeg_thumb(hipStream_t s, const JpegOutArgs& A, int ncomp, int Wt, int Ht);
+void launch_map_inset(hipStream_t s, const thumb::Inset& I, int Wo, int Ho, uint8_t* rgb);
 
 // LK.  p_in/p_out etc. are device pointers.  fb = fused forward+backward.
 struct LKBuffers {

@@ -25,8 +25,10 @@ What the reference does, and this module reproduces:
 Times are taken as float64: s2 writes int64 epoch seconds, which float64 holds exactly.
 With `plots=directory` every window that writes an `.npz` also writes its map (plot_switch 1 and 2, s3:449-465), drawn on
 the device as a JPEG file (velocity_map.py); with plot_switch 2 the day's selected vectors are uploaded once
-and each window's picture draws its group of them.
-Not built: the inset photographs and the movie of the plots, the xlsx readers (pass the rows pd.read_excel gives),
+and each window's picture draws its group of them.  With `photos=directory` as well, the picture carries the cameras'
+photographs from the middle of the window (s3:593-626, s3:788-829): `closest_image` picks the file, the device decodes it
+and reduces it to a thumbnail that is pasted into the map with the camera's name.
+Not built: the movie of the plots, the xlsx readers (pass the rows pd.read_excel gives),
 s3:main's process pool.
 """
 import ctypes as C
@@ -40,7 +42,8 @@ import numpy as np
 from . import _lib
 from .context import Context
 from .gridding import cell_table, create_grid_across_fjord, pack_cells
-from .velocity_map import MAP_QUALITY, MAP_WIDTH, map_name, map_picture, map_strings
+from .jpeg import UnsupportedJpeg, describe_jpeg
+from .velocity_map import MAP_QUALITY, MAP_WIDTH, map_insets, map_layout, map_name, map_picture, map_strings, map_text, map_view
 
 EPOCH = dt.datetime(1970, 1, 1)
 HOUR_KEYS = ("x", "y", "u", "v", "speed", "time")
@@ -231,6 +234,77 @@ def camera_positions(camnames, cameras, day):
     return out, label
 
 
+def closest_image(workspace, target_time, max_timediff=300):
+    """trm.return_closest_image (imports/tracking_misc.py:295-315): the photo of `workspace` nearest in time to
+    `target_time` (UTC), or None.  The folder is (target_time - 8 h).strftime('%Y%m%d') -- the cameras' folders are named in
+    Alaska time --, the files are '%Y%m%d-%H%M%S.jpg', and the nearest one counts only if it is less than `max_timediff`
+    seconds away, strictly.  Where the reference raises or leaves it to chance: a missing or empty folder gives None, names
+    that do not parse are skipped, a tie goes to the earlier photo."""
+    folder = os.path.join(str(workspace), (target_time - dt.timedelta(hours=8)).strftime("%Y%m%d"))
+    times = []
+    for path in sorted(glob.glob(os.path.join(folder, "*.jpg"))):
+        try:
+            times.append((dt.datetime.strptime(os.path.basename(path), "%Y%m%d-%H%M%S.jpg"), path))
+        except ValueError:
+            continue
+    if not times:
+        return None
+    when, path = min(sorted(times), key=lambda tp: abs(tp[0] - target_time))
+    return path if abs((target_time - when).total_seconds()) < max_timediff else None
+
+
+def photo_time(plan, w, plot_switch, min_time=None, max_time=None):
+    """The time whose photographs a window's picture shows.  One map (s3:600-603): the last scheduled camera's corrected
+    window start plus half the window -- the reference's variable is left over from its loop over the cameras (s3:304-314),
+    so it is that camera's whether or not it has files --, for the full day min_time + (max_time - min_time) / 2.  Two
+    maps (s3:807): always the corrected start plus half the window."""
+    if plot_switch != 2 and plan.time_window == 24.0:
+        return min_time + (max_time - min_time) / 2
+    start = plan.windows[w][0] - dt.timedelta(seconds=plan.cameras[-1]["correction"])
+    return start + dt.timedelta(hours=plan.time_window / 2.0)
+
+
+def _photo_size(data):
+    """(width, height) of a photo's file: from its header, by Pillow for a file the device decoder does not take"""
+    try:
+        info = describe_jpeg(data)
+        return info.width, info.height
+    except UnsupportedJpeg:
+        import io
+        from PIL import Image
+        return Image.open(io.BytesIO(data)).size
+
+
+def window_insets(ctx, photos, names, when, plot_switch, fjord, out_width):
+    """The insets of one window's picture: for each camera with tracks the photo of <photos>/<camera>/ closest to `when`,
+    made resident on `ctx` (`Context.map_inset_set`) and placed by `velocity_map.map_insets`.  One map: the reference stacks
+    every camera's photo in the one box; only the last camera that has one is drawn (inset 0).  Two maps: camera k goes to
+    box k, a camera without a photo leaves its box empty."""
+    paths = [closest_image(os.path.join(photos, name), when) for name in names]
+    if plot_switch == 2 and len(names) > 4:
+        raise ValueError("the two-map figure has room for four cameras' photographs")
+    if plot_switch != 2:
+        last = [k for k, p in enumerate(paths) if p is not None][-1:]
+        names, paths = [names[k] for k in last], [paths[k] for k in last]
+    files = []
+    for path in paths:
+        if path is None:
+            files.append(None)
+            continue
+        with open(path, "rb") as f:
+            files.append(f.read())
+    layout = map_layout(map_view(fjord, plot_switch), out_width, 2 if plot_switch == 2 else 1)
+    places = map_insets(layout, plot_switch, [None if d is None else _photo_size(d) for d in files])
+    out = []
+    for k, (name, data, place) in enumerate(zip(names, files, places)):
+        if place is None:
+            continue
+        size = ctx.map_inset_set(k, data, place["box"])
+        assert tuple(size) == tuple(place["size"])
+        out.append(dict(index=k, at=place["at"], label=(place["label_at"][0], place["label_at"][1], map_text(name))))
+    return out
+
+
 def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, maps=None):
     """Loads the plan's files, runs the device pass, and packs every window that selected a point.  `timing`: a dict
     that receives the seconds of each stage and the kernels' milliseconds (tools/grid_day_bench.py).  `maps`: None, or
@@ -302,9 +376,15 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
         picture = map_picture(fjord, grid_size, r["measured"], r["not_measured"], r["x"], r["y"], r["u"], r["v"], r["speed"], strings,
                               cameras=positions, label=label, n_camnames=len(names), plot_switch=maps["plot_switch"], group=w,
                               speedthreshold_cbar=maps["speedthreshold_cbar"], out_width=maps["out_width"], quality=maps["quality"])
+        if maps.get("photos") is not None:
+            at = photo_time(plan, w, maps["plot_switch"], when["min_time"], when["max_time"])
+            picture["insets"] = window_insets(ctx, maps["photos"], [nm for nm, k in zip(names, sel[w]) if k], at, maps["plot_switch"], fjord,
+                                              maps["out_width"])
         written.append((name, arrays, map_name(maps["dir"], start, end, **when), ctx.map_draw(picture)))
     if vectors:
         ctx.map_arrows_release()
+    if maps is not None and maps.get("photos") is not None:
+        ctx.map_inset_release()
     if timing is not None:
         timing.update(points=n, load_s=t1 - t0, device_call_s=t2 - t1, kernels_ms=device_ms.value,
                       pack_s=clock() - t2)
@@ -313,7 +393,7 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
 
 def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts, fjord, day,
                        time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None, plot_switch=1,
-                       speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY):
+                       speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None):
     """One day of hourly velocity files -> one gridded .npz per time window, as s3_utm_to_gridded_utm.utm_to_gridded_utm
     (s3:222-446) with plot_switch 0.
 
@@ -326,11 +406,19 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
     `plots`: a directory; every window that writes an .npz also gets its map there (s3:449-465), '%Y%m%d_%H%M-%H%M.jpg',
     drawn and coded on the device.  plot_switch 1: the gridded map; 2: the all-vectors panel beside it.
     `cameras`: the parameter workbook's rows with camera, start_day, end_day, easting, northing (None: `schedule`, whose
-    rows may carry them); `speedthreshold_cbar`: the speed at the colour bar's end.  plots=None calls nothing of this."""
+    rows may carry them); `speedthreshold_cbar`: the speed at the colour bar's end.  plots=None calls nothing of this.
+
+    `photos`: the reference's source_path_photos, a directory with <camera>/<%Y%m%d>/<%Y%m%d-%H%M%S>.jpg; every picture then
+    carries, for each camera with tracks in its window, the photograph closest to the middle of the window (less than
+    300 s away, `closest_image`), reduced on the device and labelled with the camera's name.  It needs
+    `plots`; photos=None calls nothing of this."""
     if plots is not None and plot_switch not in (1, 2):
         raise ValueError("plot_switch must be 1 or 2")
+    if photos is not None and plots is None:
+        raise ValueError("photos needs plots: the photographs go into the windows' pictures")
     maps = None if plots is None else dict(dir=str(plots), plot_switch=plot_switch, speedthreshold_cbar=speedthreshold_cbar,
-                                           cameras=schedule if cameras is None else cameras, out_width=out_width, quality=quality)
+                                           cameras=schedule if cameras is None else cameras, out_width=out_width, quality=quality,
+                                           photos=None if photos is None else str(photos))
     plan = plan_day(camnames, source_path_head, source_path_tail, schedule, clock_drifts, day, time_window, grid_size)
     if not plan.files:
         return []
@@ -356,7 +444,7 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
 
 def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts,
                             fjord, time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None,
-                            plot_switch=1, speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY):
+                            plot_switch=1, speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None):
     """s3:main's loop over days (without its process pool), on one context: the files of every day, in order.  The plot
     keywords are utm_to_gridded_utm's."""
     own = ctx is None
@@ -369,7 +457,7 @@ def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, 
                                       clock_drifts, fjord, day, time_window, grid_size, observation_threshold,
                                       ctx=ctx, save=save, plots=plots, plot_switch=plot_switch,
                                       speedthreshold_cbar=speedthreshold_cbar, cameras=cameras, out_width=out_width,
-                                      quality=quality)
+                                      quality=quality, photos=photos)
         return out
     finally:
         if own:

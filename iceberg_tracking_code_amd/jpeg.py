@@ -143,6 +143,58 @@ def decode_jpeg(data, ctx=None, huffman="host"):
     return ctx.jpeg_decode_rgb(j)
 
 
+# ---- thumbnails: the inset photographs of the velocity map (csrc/thumb_raster.h) --------------------------
+def _box2(box):
+    bw, bh = (int(v) for v in box)
+    return bw, bh
+
+
+def thumbnail_size(width, height, box):
+    """(tw, th): a width x height image fitted into box = (box_w, box_h), proportions kept, never enlarged
+    (icelk_thumb_size)."""
+    bw, bh = _box2(box)
+    tw, th = C.c_int(0), C.c_int(0)
+    if _lib.load().icelk_thumb_size(int(width), int(height), bw, bh, C.byref(tw), C.byref(th)) != _lib.OK:
+        raise ValueError("an image outside 1 .. 65535 or a box outside 1 .. 16384 pixels a side")
+    return tw.value, th.value
+
+
+def thumbnail_host(image, size):
+    """H x W or H x W x 3 uint8 -> its (th, tw, 3) thumbnail of size = (tw, th), every channel the exact area average, by the
+    code the device runs, on the CPU (icelk_thumb_host).  No GPU is needed."""
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("expected an HxW or HxWx3 uint8 image")
+    channels = 1 if a.ndim == 2 else a.shape[2]
+    if a.strides[-1] != 1 or (a.ndim == 3 and a.strides[1] != channels) or a.strides[0] < channels * a.shape[1]:
+        a = np.ascontiguousarray(a)
+    tw, th = (int(v) for v in size)
+    out = np.empty((max(th, 1), max(tw, 1), 3), np.uint8)
+    rc = _lib.load().icelk_thumb_host(a.ctypes.data_as(_lib.u8p), a.shape[1], a.shape[0], channels, a.strides[0], tw, th,
+                                      out.ctypes.data_as(_lib.u8p), out.strides[0])
+    if rc == _lib.ENOMEM:
+        raise MemoryError("icelk_thumb_host")
+    if rc != _lib.OK:
+        raise ValueError("icelk_thumb_host: a thumbnail larger than the image or smaller than one pixel")
+    return out
+
+
+def thumbnail(data_or_path, box, ctx=None):
+    """A path or the bytes of a JPEG file -> its (th, tw, 3) uint8 thumbnail fitted into box = (box_w, box_h): decoded and
+    reduced on the device (icelk_jpeg_thumb_file), equal to `thumbnail_host(np.asarray(Image.open(f).convert("RGB")),
+    thumbnail_size(...))`.  `ctx`: as `decode_jpeg`.  Files the device decoder does not take raise `UnsupportedJpeg`."""
+    if not isinstance(data_or_path, (bytes, bytearray, memoryview)):
+        with open(data_or_path, "rb") as f:
+            data_or_path = f.read()
+    data = bytes(data_or_path)
+    info = describe_jpeg(data)
+    size = thumbnail_size(info.width, info.height, box)
+    if ctx is None:
+        from .api import default_context
+        ctx = default_context(info.width, info.height)
+    return ctx.jpeg_thumb_file(data, size)
+
+
 # ---- the reference's re-save of the crop -----------------------------------------------------------------------------
 REFERENCE_RESAVE_QUALITY = 75   # Pillow's default: `img_crop.save(outpath)` names none (camtools.py:64-104)
 

@@ -11,6 +11,9 @@ A picture is described by a dict:
     panels [dict(view=(x0, y0, w, h), bar=(bar_x0, bar_w), limits=(xmin, xmax, ymin, ymax), cells (n, 3) left top size,
                  measured (n,), outline (n, 2), arrows (n, 5) x y dx dy speed | resident=True with group=int or -1,
                  pivot 'tail' | 'mid', width, alpha, vmax, cameras (n, 2))]
+and, for the cameras' inset photographs (`map_insets` places them),
+    insets [dict(index = which resident thumbnail of `Context.map_inset_set`, at=(x0, y0), label=(px, py, text) | None;
+                 for `map_overlay_host`: pixels = the thumbnail (h, w, 3) uint8)]
 """
 import ctypes as C
 import os
@@ -187,6 +190,50 @@ def map_picture(fjord, grid_size, polygons_measured, polygons_not_measured, x, y
                                 speedthreshold_cbar, plot_switch), panels=out)
 
 
+def map_insets(layout, plot_switch, sizes):
+    """Where the cameras' photographs go in a picture of `layout`, in integers from the reference's figure fractions
+    (s3:614 one map: one box [0.06, 0.06, 0.2, 0.2]; s3:791-796 two maps: four boxes [0.03, 0.06 + 0.2 k, 0.18, 0.18]; left,
+    bottom, width, height with the origin at the figure's bottom-left).  `sizes`: per inset the photo's (width, height), or
+    None for none.  Returns per inset None or dict(box=(bw, bh), size=(tw, th) the thumbnail's by icelk_thumb_size,
+    at=(x0, y0) its top-left corner -- it sits in the bottom-left corner of its box (anchor='SW') --, label_at=(px, py) the
+    top-left corner of the camera's name, whose bottom-left corner is 5 % of the thumbnail's width from its left edge and
+    15 % of its height below its top (annotatefun(axins, [name], 0.05, 0.85)).  One map: every inset has the one box; two
+    maps: inset k has box k, more than four raise ValueError where the reference asserts."""
+    from .jpeg import thumbnail_size
+    W, H, k = layout["width"], layout["height"], layout["scale"]
+    sizes = list(sizes)
+    if plot_switch == 2 and len(sizes) > 4:
+        raise ValueError("the two-map figure has room for four cameras' photographs")
+    out = []
+    for n, size in enumerate(sizes):
+        if size is None:
+            out.append(None)
+            continue
+        if plot_switch == 2:
+            x, bw, bh, bottom = (3 * W) // 100, (18 * W) // 100, (18 * H) // 100, H - ((6 + 20 * n) * H) // 100
+        else:
+            x, bw, bh, bottom = (6 * W) // 100, (20 * W) // 100, (20 * H) // 100, H - (6 * H) // 100
+        tw, th = thumbnail_size(size[0], size[1], (max(bw, 1), max(bh, 1)))
+        y0 = bottom - th
+        out.append(dict(box=(max(bw, 1), max(bh, 1)), size=(tw, th), at=(x, y0), label_at=(x + (5 * tw) // 100, y0 + (15 * th) // 100 - 7 * k)))
+    return out
+
+
+def map_inset_array(insets):
+    """(array of icelk_map_inset_t, its length) of a picture's insets"""
+    insets = list(insets)
+    if len(insets) > _lib.MAP_INSETS_MAX:
+        raise ValueError("more than 8 insets")
+    a = (_lib.MapInset * max(len(insets), 1))()
+    for t, q in zip(a, insets):
+        t.x0, t.y0 = (int(v) for v in q["at"])
+        t.index = int(q["index"])
+        if q.get("label") is not None:
+            px, py, s = q["label"]
+            t.label_px, t.label_py, t.label = int(px), int(py), _text_bytes(s)
+    return a, len(insets)
+
+
 def _text_bytes(s):
     if isinstance(s, str):
         try:
@@ -262,15 +309,29 @@ def map_glyph(ch):
 def map_overlay_host(picture, resident=None, group=None):
     """The picture's R G B (height, width, 3) uint8 by the host statement of the rasteriser (icelk_map_overlay_host): what
     `Context.map_draw(picture, want_rgb=True)` returns, byte for byte.  `resident`, `group`: what `Context.map_arrows_set`
-    was given, for panels that draw the resident arrows.  No GPU is needed."""
+    was given, for panels that draw the resident arrows.  picture["insets"]: each with pixels= the thumbnail its index
+    stands for (icelk_map_overlay_insets_host); an index given pixels twice keeps the last.  No GPU is needed."""
     d, keep = map_descriptor(picture)
     a, g, _, n = _resident_args(resident, group)
     rgb = np.empty((max(d.height, 1), max(d.width, 1), 3), np.uint8)
-    rc = _lib.load().icelk_map_overlay_host(C.byref(d), None if a is None else a.ctypes.data_as(_lib.f64p),
-                                            None if g is None else g.ctypes.data_as(_lib.i32p), n, rgb.ctypes.data_as(_lib.u8p), rgb.strides[0])
+    args = (C.byref(d), None if a is None else a.ctypes.data_as(_lib.f64p), None if g is None else g.ctypes.data_as(_lib.i32p), n)
+    if picture.get("insets"):
+        insets, n_insets = map_inset_array(picture["insets"])
+        have = (_lib.MapInsetPixels * _lib.MAP_INSETS_MAX)()
+        for q in picture["insets"]:
+            if q.get("pixels") is not None and 0 <= int(q["index"]) < _lib.MAP_INSETS_MAX:
+                px = np.ascontiguousarray(q["pixels"], dtype=np.uint8)
+                if px.ndim != 3 or px.shape[2] != 3:
+                    raise ValueError("an inset's pixels must be (h, w, 3) uint8")
+                keep.append(px)
+                t = have[int(q["index"])]
+                t.rgb, t.w, t.h, t.stride = px.ctypes.data, px.shape[1], px.shape[0], px.strides[0]
+        rc = _lib.load().icelk_map_overlay_insets_host(*args, insets, n_insets, have, rgb.ctypes.data_as(_lib.u8p), rgb.strides[0])
+    else:
+        rc = _lib.load().icelk_map_overlay_host(*args, rgb.ctypes.data_as(_lib.u8p), rgb.strides[0])
     if rc == _lib.EARG:
         raise ValueError("icelk_map_overlay_host: a bad argument (include/icelk.h lists what a picture may hold)")
     if rc == _lib.ESTATE:
-        raise _lib.IcelkError("icelk_map_overlay_host: a panel draws the resident arrows and none were given")
+        raise _lib.IcelkError("icelk_map_overlay_host: a panel draws the resident arrows, or an inset a thumbnail, and none were given")
     _lib.check(rc)
     return rgb

@@ -776,6 +776,65 @@ int icelk_map_arrows_release(icelk_t* h);
 int icelk_map_draw(icelk_t* h, const icelk_map_desc_t* d, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
                    uint64_t* len);
 
+/* ---- the inset photographs of the velocity map (opt-in) ------------------------------------------
+ * The reference's maps carry, in a corner, the photograph each camera took in the middle of the window with the camera's
+ * name on it (s3:593-626 for one map, s3:788-829 for two).  Here a photo is decoded on the device as
+ * icelk_jpeg_decode_rgb_file decodes it, reduced to a thumbnail there without its full-size R G B ever being stored
+ * (k_jpeg_thumb, csrc/k_thumb.hip), kept resident, and pasted into the map's R G B behind k_map_resolve (k_map_inset).
+ * The rules are csrc/thumb_raster.h, which the device, the host statements below and
+ * tests/thumb_restatement.py compute byte for byte alike:
+ *   size     a w x h image is fitted into a box box_w x box_h, proportions kept, never enlarged: tw = min(box_w, w),
+ *            th = max(1, (2 tw h + w) / (2 w)) (icelk_plot_size's rule); if th > box_h then th = min(box_h, h),
+ *            tw = min(box_w, max(1, (2 th w + h) / (2 h))).  w, h in 1 .. 65535, box_w, box_h in 1 .. 16384, else ICELK_EARG
+ *   pixels   every channel the exact area average: v = (sum wx wy s + w h / 2) / (w h) with the integer overlap weights of
+ *            the segment picture's background; a one-channel image gives R = G = B.  The source samples of a file are
+ *            the decoded R G B icelk_jpeg_decode_rgb_file returns, that is Pillow's
+ *   paste    a thumbnail opaque with its top-left corner at (x0, y0), wholly inside the picture, then its label: at most
+ *            48 characters of a map text's character set in its glyphs and at the picture's text scale, opaque black,
+ *            (label_px, label_py) its top-left corner, clipped to the picture; an empty label draws nothing.  Insets are
+ *            drawn in array order, behind everything icelk_map_draw draws: a later inset covers an earlier one */
+typedef struct {
+    int32_t x0, y0;                /* the thumbnail's top-left corner in the picture */
+    int32_t index;                 /* which resident thumbnail, 0 .. 7 */
+    int32_t label_px, label_py;    /* |label_px|, |label_py| <= 2^20 */
+    int32_t reserved;
+    char label[56];                /* NUL-terminated */
+} icelk_map_inset_t;
+typedef struct {
+    const uint8_t* rgb;            /* interleaved R G B, stride bytes per row; NULL: this index holds no thumbnail */
+    int32_t w, h, stride, reserved;
+} icelk_map_inset_pixels_t;
+/* Host only, no handle, re-entrant: the size of the thumbnail of a w x h image in a box. */
+int icelk_thumb_size(int w, int h_, int box_w, int box_h, int* tw, int* th);
+/* Host only, no handle, re-entrant: the tw x th thumbnail (R G B, out_stride bytes per row) of an interleaved image of 1 or
+ * 3 channels (stride bytes per row), by the code the device runs, on the CPU.  1 <= tw <= w, 1 <= th <= h. */
+int icelk_thumb_host(const uint8_t* img, int w, int h_, int channels, int stride, int tw, int th, uint8_t* out_rgb, int out_stride);
+/* Host only: icelk_map_overlay_host, then the insets.  resident_insets[8] stands for what icelk_map_inset_set_* hold: an
+ * inset whose index has rgb == NULL there is ICELK_ESTATE.  n_insets 0 .. 8; the other refusals are icelk_map_draw_insets'. */
+int icelk_map_overlay_insets_host(const icelk_map_desc_t* d, const double* resident, const int32_t* group, int n_resident,
+                                  const icelk_map_inset_t* insets, int n_insets, const icelk_map_inset_pixels_t* resident_insets,
+                                  uint8_t* rgb, int rgb_stride);
+/* The tw x th thumbnail of a JPEG file given as bytes: decoded on the device as icelk_jpeg_decode_rgb_file does (the same
+ * files, the same error codes, the host's Huffman decoder inside the call where the lanes give up), reduced by k_jpeg_thumb
+ * from the component planes and copied to out_rgb (stride >= 3 tw bytes per row).  1 <= tw <= width, 1 <= th <= height,
+ * else ICELK_EARG.  The call waits for the device. */
+int icelk_jpeg_thumb_file(icelk_t* h, const uint8_t* data, uint64_t len, int tw, int th, uint8_t* out_rgb, int stride);
+/* The same, but the thumbnail stays on the device as resident inset `index` (0 .. 7) until the next set of that index,
+ * icelk_map_inset_release or icelk_destroy.  After an error the index holds what it held. */
+int icelk_map_inset_set_file(icelk_t* h, int index, const uint8_t* data, uint64_t len, int tw, int th);
+/* A ready thumbnail (R G B, stride >= 3 tw bytes per row, tw and th in 1 .. 16384) as resident inset `index`: for files
+ * the device decoder refuses, reduced on the host with icelk_thumb_host, and for tests. */
+int icelk_map_inset_set_pixels(icelk_t* h, int index, const uint8_t* rgb, int tw, int th, int stride);
+int icelk_map_inset_release(icelk_t* h);
+/* icelk_map_draw with insets: everything icelk_map_draw draws, texts included, then per inset, in array order, k_map_inset
+ * (csrc/k_thumb.hip) on the map's R G B.  n_insets 0 .. 8; with 0 the file is icelk_map_draw's.  Refused before anything
+ * is enqueued or allocated, besides what icelk_map_draw refuses: an index outside 0 .. 7, a thumbnail's rectangle that is
+ * not wholly inside the picture, a label of more than 48 characters or with a character outside a map text's, a label
+ * position beyond 2^20 (ICELK_EARG); an index that holds no thumbnail (ICELK_ESTATE).  ICELK_ECAP and the repeat are
+ * icelk_map_draw's. */
+int icelk_map_draw_insets(icelk_t* h, const icelk_map_desc_t* d, const icelk_map_inset_t* insets, int n_insets, uint8_t* rgb_or_null,
+                          int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
