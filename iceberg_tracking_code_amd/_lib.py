@@ -165,6 +165,11 @@ SIGNATURES = {
     "icelk_map_inset_set_pixels": (C.c_int, [handle_p, C.c_int, u8p, C.c_int, C.c_int, C.c_int]),
     "icelk_map_inset_release": (C.c_int, [handle_p]),
     "icelk_map_draw_insets": (C.c_int, [handle_p, map_desc_p, map_inset_p, C.c_int, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_png_bound": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "icelk_png_filter_host": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, u8p]),
+    "icelk_png_encode_host": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_png_encode_rgb": (C.c_int, [handle_p, u8p, C.c_int, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_map_draw_png": (C.c_int, [handle_p, map_desc_p, map_inset_p, C.c_int, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

@@ -709,19 +709,38 @@ class Context:
     def map_inset_release(self):
         self._ck(self._lib.icelk_map_inset_release(self._h))
 
-    def map_draw(self, picture, want_rgb=False):
+    def png_encode(self, rgb):
+        """H x W x 3 uint8 -> the bytes of the PNG file `png.encode_png_host(rgb)` returns, with the row filters, the deflate
+        block and the Adler-32 made on the device (icelk_png_encode_rgb): pixels up, file down."""
+        a = _rgb3(rgb)
+        args = (_u8(a), a.shape[1], a.shape[0], a.strides[0])
+        from .png import png_bound
+        return _encode_call(lambda out, cap, n: self._lib.icelk_png_encode_rgb(self._h, *args, out, cap, n), png_bound(a.shape[1], a.shape[0]),
+                            "icelk_png_encode_rgb", self._h)
+
+    def map_draw(self, picture, want_rgb=False, format="jpeg"):
         """The picture a dict of velocity_map describes (`velocity_map.map_picture` makes one of a window), as the bytes of a
-        JPEG file (icelk_map_draw; the rules are DESIGN.md 7.7).  With picture["insets"] = [dict(index=, at=(x0, y0),
+        JPEG file (icelk_map_draw; the rules are DESIGN.md 7.7) or, with format="png", of a PNG file that decodes to exactly
+        the picture's R G B (icelk_map_draw_png, DESIGN.md 7.9: the quality is ignored, everything else below holds).  With picture["insets"] = [dict(index=, at=(x0, y0),
         label=(px, py, text) | None)] the resident thumbnails of `map_inset_set` are pasted in, each with its label
         (icelk_map_draw_insets); without the key, or with an empty list, the call is icelk_map_draw's.  Rasterised and coded on the device; the file is what
         `Image.fromarray(rgb).save(f, "JPEG", quality=quality)` writes for the picture's R G B.  want_rgb: (bytes, that
         R G B (height, width, 3) uint8), for tests.  IcelkError (code ICELK_ESTATE) when a panel draws the resident arrows
         and none are set."""
+        if format not in ("jpeg", "png"):
+            raise ValueError("format is 'jpeg' or 'png'")
         d, keep = map_descriptor(picture)
         rgb, rgb_ptr, stride = None, None, 0
         if want_rgb:
             rgb = np.empty((max(d.height, 1), max(d.width, 1), 3), np.uint8)
             rgb_ptr, stride = _u8(rgb), rgb.strides[0]
+        if format == "png":
+            insets, n_insets = map_inset_array(picture["insets"]) if picture.get("insets") else (None, 0)
+            data = _encode_call(lambda out, cap, n: self._lib.icelk_map_draw_png(self._h, C.byref(d), insets, n_insets, rgb_ptr, stride, out, cap, n),
+                                getattr(self, "_map_png_guess", 1 << 18), "icelk_map_draw_png", self._h)
+            self._map_png_guess = max(1 << 16, len(data) + len(data) // 4)
+            del keep
+            return (data, rgb) if want_rgb else data
         guess = getattr(self, "_map_file_guess", 1 << 18)
         if picture.get("insets"):
             insets, n_insets = map_inset_array(picture["insets"])

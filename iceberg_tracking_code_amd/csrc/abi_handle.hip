@@ -15,6 +15,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "plot_background", "plot_clear", "plot_scatter", "plot_resolve",
     "map_clear", "map_cells", "map_polyline", "map_arrows", "map_resolve",
     "jpeg_thumb", "map_inset",
+    "png_filter", "png_parse", "png_scan", "png_pack", "png_adler",
 };
 
 std::string g_create_err;
@@ -172,6 +173,7 @@ static void destroy_ctx(Ctx* c)
     jpeg_enc_destroy(c);
     plot_destroy(c);
     map_destroy(c);
+    png_destroy(c);
     prof_drain(c);
     for (auto& e : c->evt_pool) {
         hipEventDestroy(e.a);

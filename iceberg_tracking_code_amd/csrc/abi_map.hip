@@ -12,6 +12,8 @@
 //           repeated: the picture is a function of its arguments.
 //           icelk_map_draw_insets: the same with one k_map_inset (k_thumb.hip) per inset between k_map_resolve and the
 //           forward kernel, from the resident thumbnails of abi_thumb.hip, whose header states that kernel's bounds
+//           icelk_map_draw_png: the same drawing (draw_picture) with or without insets, then the PNG writer of
+//           abi_png.hip on the resident R G B instead of the forward kernel and the JPEG coder; the quality is ignored
 //
 // Bounds, store by store.  Everything is sized from the picture (Wo x Ho, px = Wo Ho padded to four pixels) and the
 // descriptor's counts before anything is enqueued, and check_desc has refused every view that is not inside the picture.
@@ -209,11 +211,13 @@ struct Picture {
 };
 
 // Everything that can be refused is refused here, before anything is enqueued or allocated
-int check_device_call(Ctx* c, const icelk_map_desc_t* d, map::Scene* S, const uint8_t* rgb, int rgb_stride, const uint64_t* len, Picture* Q)
+// as_png: the file is a PNG (abi_png.hip): the quality is not looked at and the picture has no JPEG layout
+int check_device_call(Ctx* c, const icelk_map_desc_t* d, map::Scene* S, const uint8_t* rgb, int rgb_stride, const uint64_t* len, bool as_png,
+                      Picture* Q)
 {
     if (!len) FAIL(c, ICELK_EARG, "null length");
     if (const char* why = check_desc(d, S)) FAIL(c, ICELK_EARG, why);
-    if (int rc = jpeg_resave_check(c, d->width, d->height, d->quality)) return rc;
+    if (int rc = as_png ? png_check(c, d->width, d->height) : jpeg_resave_check(c, d->width, d->height, d->quality)) return rc;
     if (rgb && rgb_stride < 3 * d->width) FAIL(c, ICELK_EARG, "rgb stride smaller than 3 x the picture's width");
     Q->items = Q->measured = 0;
     for (int k = 0; k < d->n_panels; k++) {
@@ -222,6 +226,9 @@ int check_device_call(Ctx* c, const icelk_map_desc_t* d, map::Scene* S, const ui
         Q->items += 3 * (size_t)p.n_cells + 2 * (size_t)p.n_outline + (p.resident ? 0 : 5 * (size_t)p.n_arrows);
         Q->measured += (size_t)p.n_cells;
     }
+    Q->info = icelk_jpeg_info_t{};
+    Q->L = enc::Layout{};
+    if (as_png) return ICELK_OK;
     resave::resave_info(d->width, d->height, d->quality, &Q->info);
     return jpeg_enc_rc(c, enc::layout_of(&Q->info, &Q->L));
 }
@@ -243,8 +250,8 @@ int grow_picture(Ctx* c, const icelk_map_desc_t* d, const Picture& Q)
     return grow(c, &M.rs.d_rcoef, &M.rs.rcoef_cap, (size_t)Q.info.coef_count);
 }
 
-int draw_and_encode(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked, const Picture& Q, uint8_t* rgb, int rgb_stride, uint8_t* file,
-                    uint64_t capacity, uint64_t* len, const thumb::Inset* insets = nullptr, int n_insets = 0)
+// the picture into M.rs.d_rgb, enqueued on the handle's compute stream: what every file format starts from
+int draw_picture(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked, const thumb::Inset* insets, int n_insets)
 {
     Ctx::Map& M = c->map;
     const hipStream_t st = c->stream;
@@ -313,6 +320,22 @@ int draw_and_encode(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked
             launch_map_inset(st, insets[k], Wo, Ho, M.rs.d_rgb);
         }
         if (int rc = check_launch(c, "map_inset")) return rc;
+    }
+    return ICELK_OK;
+}
+
+int draw_and_encode(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked, const Picture& Q, bool as_png, uint8_t* rgb, int rgb_stride,
+                    uint8_t* file, uint64_t capacity, uint64_t* len, const thumb::Inset* insets = nullptr, int n_insets = 0)
+{
+    Ctx::Map& M = c->map;
+    const hipStream_t st = c->stream;
+    const int Wo = d->width, Ho = d->height;
+    if (int rc = draw_picture(c, d, checked, insets, n_insets)) return rc;
+    if (as_png) {
+        uint32_t nbytes = 0;
+        if (int rc = png_encode_on(c, st, M.rs.d_rgb, 3u * (uint32_t)Wo, Wo, Ho, &nbytes)) return rc;   // synchronises
+        if (rgb) HIPCHK(c, hipMemcpy2DAsync(rgb, rgb_stride, M.rs.d_rgb, 3 * (size_t)Wo, 3 * (size_t)Wo, Ho, hipMemcpyDeviceToHost, st));
+        return png_deliver_file(c, st, rgb != nullptr, Wo, Ho, nbytes, file, capacity, len);
     }
     if (int rc = jpeg_fwd_on(c, st, M.rs.d_rgb, M.rs.d_rcoef, Wo, Ho, Q.info)) return rc;
     if (int rc = jpeg_encode_on(c, M.rs.enc, st, Q.L, M.rs.d_rcoef)) return rc;   // synchronises
@@ -417,7 +440,7 @@ int icelk_map_arrows_release(icelk_t* h)
 }
 
 // icelk_map_draw (no insets: nothing below touches them) and icelk_map_draw_insets
-static int map_draw_call(icelk_t* h, const char* range, const icelk_map_desc_t* d, const icelk_map_inset_t* insets, int n_insets,
+static int map_draw_call(icelk_t* h, const char* range, bool as_png, const icelk_map_desc_t* d, const icelk_map_inset_t* insets, int n_insets,
                          uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len)
 {
     if (!h) return ICELK_EARG;
@@ -426,7 +449,7 @@ static int map_draw_call(icelk_t* h, const char* range, const icelk_map_desc_t* 
     map::Scene* S = new (std::nothrow) map::Scene;
     if (!S) FAIL(c, ICELK_ENOMEM, "the map's scene");
     Picture Q;
-    int rc = check_device_call(c, d, S, rgb_or_null, rgb_stride, len, &Q);
+    int rc = check_device_call(c, d, S, rgb_or_null, rgb_stride, len, as_png, &Q);
     thumb::Inset I[thumb::kMaxInsets];
     if (rc == ICELK_OK && (insets || n_insets)) {
         icelk_map_inset_pixels_t have[thumb::kMaxInsets];
@@ -451,7 +474,8 @@ static int map_draw_call(icelk_t* h, const char* range, const icelk_map_desc_t* 
         }
     }
     if (rc == ICELK_OK) rc = grow_picture(c, d, Q);
-    if (rc == ICELK_OK) rc = draw_and_encode(c, d, *S, Q, rgb_or_null, rgb_stride, file, capacity, len, I, n_insets);
+    if (rc == ICELK_OK && as_png) rc = png_grow(c, d->width, d->height);
+    if (rc == ICELK_OK) rc = draw_and_encode(c, d, *S, Q, as_png, rgb_or_null, rgb_stride, file, capacity, len, I, n_insets);
     delete S;
     return rc;
 }
@@ -459,13 +483,19 @@ static int map_draw_call(icelk_t* h, const char* range, const icelk_map_desc_t* 
 int icelk_map_draw(icelk_t* h, const icelk_map_desc_t* d, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
                    uint64_t* len)
 {
-    return map_draw_call(h, "icelk map_draw", d, nullptr, 0, rgb_or_null, rgb_stride, file, capacity, len);
+    return map_draw_call(h, "icelk map_draw", false, d, nullptr, 0, rgb_or_null, rgb_stride, file, capacity, len);
 }
 
 int icelk_map_draw_insets(icelk_t* h, const icelk_map_desc_t* d, const icelk_map_inset_t* insets, int n_insets, uint8_t* rgb_or_null,
                           int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len)
 {
-    return map_draw_call(h, "icelk map_draw_insets", d, insets, n_insets, rgb_or_null, rgb_stride, file, capacity, len);
+    return map_draw_call(h, "icelk map_draw_insets", false, d, insets, n_insets, rgb_or_null, rgb_stride, file, capacity, len);
+}
+
+int icelk_map_draw_png(icelk_t* h, const icelk_map_desc_t* d, const icelk_map_inset_t* insets_or_null, int n_insets, uint8_t* rgb_or_null,
+                       int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len)
+{
+    return map_draw_call(h, "icelk map_draw_png", true, d, insets_or_null, n_insets, rgb_or_null, rgb_stride, file, capacity, len);
 }
 
 }  // extern "C"

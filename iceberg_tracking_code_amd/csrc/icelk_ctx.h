@@ -218,6 +218,17 @@ struct Ctx {
         int inset_w[thumb::kMaxInsets] = {}, inset_h[thumb::kMaxInsets] = {};
     } map;
 
+    // ---- abi_png.hip: the PNG writer, allocated at first use and grown to what a picture takes.  A working set of its own:
+    // the map's PNG (icelk_map_draw_png) reads the map's R G B and writes here, icelk_png_encode_rgb uploads into d_src
+    struct Png {
+        uint8_t* d_src = nullptr;       // the caller's picture (icelk_png_encode_rgb only), rows 3 * width bytes apart
+        uint8_t* d_F = nullptr;         // the filtered stream, whole segments
+        uint16_t* d_tok = nullptr;      // the tokens, whole segments
+        uint32_t *d_seg = nullptr, *d_adler = nullptr, *d_stream = nullptr, *d_ctl = nullptr;
+        uint32_t* h_ctl = nullptr;      // pinned
+        size_t src_cap = 0, F_cap = 0, tok_cap = 0, seg_cap = 0, adler_cap = 0, stream_cap = 0;   // elements
+    } png;
+
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
     float *d_p0 = nullptr, *d_p1 = nullptr, *d_p0r = nullptr, *d_err_f = nullptr, *d_err_b = nullptr, *d_dist = nullptr;
     uint8_t *d_st_f = nullptr, *d_st_b = nullptr, *d_valid = nullptr;
@@ -628,6 +639,12 @@ void plot_destroy(Ctx* c);
 void map_destroy(Ctx* c);
 // abi_thumb.hip
 void map_insets_free(Ctx* c);
+// abi_png.hip
+void png_destroy(Ctx* c);
+int png_check(Ctx* c, int w, int h);
+int png_grow(Ctx* c, int w, int h);
+int png_encode_on(Ctx* c, hipStream_t st, const uint8_t* d_rgb, uint32_t stride, int w, int h, uint32_t* nbytes);
+int png_deliver_file(Ctx* c, hipStream_t st, bool pending, int w, int h, uint32_t nbytes, uint8_t* out, uint64_t capacity, uint64_t* len);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

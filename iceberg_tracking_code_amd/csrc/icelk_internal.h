@@ -9,6 +9,7 @@
 #include "jpeg_enc.h"
 #include "jpeg_lanes.h"
 #include "plot_raster.h"
+#include "png_enc.h"
 #include "map_raster.h"
 #include "thumb_raster.h"
 
@@ -86,6 +87,11 @@ enum KernelId {
     K_MAP_RESOLVE,             // ... planes, cameras, bars and texts -> R G B
     K_JPEG_THUMB,              // the inset photographs (k_thumb.hip): decoded planes -> area-averaged R G B thumbnail
     K_MAP_INSET,               // ... a thumbnail and its label into the map's R G B
+    K_PNG_FILTER,              // the PNG writer (k_png.hip): the five row filters, the smallest kept -> the filtered stream
+    K_PNG_PARSE,               // ... a segment's tokens, their bit count, its Adler piece
+    K_PNG_SCAN,                // ... bit offset of every segment (k_jpeg_enc_scan)
+    K_PNG_PACK,                // ... the deflate bits
+    K_PNG_ADLER,               // ... the pieces joined
     K_COUNT_
 };
 
@@ -287,6 +293,28 @@ void launch_map_resolve(hipStream_t s, const map::Scene* d_scene, int Wo, int Ho
 // Wt x Ht thumbnail (R G B, dst_pitch bytes per row); ncomp 1 or 3.  I.px: device memory; rgb: the map's R G B, 3 Wo bytes per row
 void launch_jpeg_thumb(hipStream_t s, const JpegOutArgs& A, int ncomp, int Wt, int Ht);
 void launch_map_inset(hipStream_t s, const thumb::Inset& I, int Wo, int Ho, uint8_t* rgb);
+
+// k_png.hip: the PNG writer (the arithmetic is png_enc.h).  All pointers are device memory; F and tok are allocated in
+// whole segments (png::segments_of(n) * png::kSegment elements), stream is zero before pack and holds
+// png::deflate_bytes(9 n) bytes rounded up to dwords, plus one
+constexpr int kPngLanes = 256;   // lanes per workgroup of every kernel; parse and pack take png::kSegment / 256 positions per lane
+enum PngCtl { PNG_TOTAL_BITS = 0, PNG_ADLER, PNG_WORDS = 4 };   // words of PngArgs::ctl
+struct PngArgs {
+    const uint8_t* rgb;   // the picture, rows `stride` bytes apart
+    uint32_t stride;
+    int w, h;
+    uint32_t n, pitch;    // bytes of the filtered stream, of one of its rows (1 + 3 w)
+    uint8_t* F;           // the filtered stream
+    uint16_t* tok;        // per position of F: the token that begins there, or 0
+    uint32_t* seg;        // per segment: the bits of its tokens, after the scan the sum of those before it
+    uint32_t* adler;      // per segment: A, B, n of png::Adler
+    uint32_t* stream;     // the deflate block
+    uint32_t* ctl;        // PngCtl
+};
+void launch_png_filter(hipStream_t s, const PngArgs& A);
+void launch_png_parse(hipStream_t s, const PngArgs& A);
+void launch_png_pack(hipStream_t s, const PngArgs& A);
+void launch_png_adler(hipStream_t s, const uint32_t* pieces, uint32_t n, uint32_t* value);
 
 // LK.  p_in/p_out etc. are device pointers.  fb = fused forward+backward.
 struct LKBuffers {

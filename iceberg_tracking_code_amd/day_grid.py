@@ -24,11 +24,12 @@ What the reference does, and this module reproduces:
   the first / last selected time (+ drift) rounded to 30 minutes (trm.round_time).
 Times are taken as float64: s2 writes int64 epoch seconds, which float64 holds exactly.
 With `plots=directory` every window that writes an `.npz` also writes its map (plot_switch 1 and 2, s3:449-465), drawn on
-the device as a JPEG file (velocity_map.py); with plot_switch 2 the day's selected vectors are uploaded once
+the device as a JPEG file (velocity_map.py) or, with plot_format="png", as the PNG file the reference
+writes, with its name and exactly the rasterised pixels; with plot_switch 2 the day's selected vectors are uploaded once
 and each window's picture draws its group of them.  With `photos=directory` as well, the picture carries the cameras'
 photographs from the middle of the window (s3:593-626, s3:788-829): `closest_image` picks the file, the device decodes it
 and reduces it to a thumbnail that is pasted into the map with the camera's name.
-Not built: the movie of the plots, the xlsx readers (pass the rows pd.read_excel gives),
+Not built: the movie of the plots, PNG files with dynamic Huffman codes (the PNG is one fixed-Huffman block), the xlsx readers (pass the rows pd.read_excel gives),
 s3:main's process pool.
 """
 import ctypes as C
@@ -380,7 +381,9 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
             at = photo_time(plan, w, maps["plot_switch"], when["min_time"], when["max_time"])
             picture["insets"] = window_insets(ctx, maps["photos"], [nm for nm, k in zip(names, sel[w]) if k], at, maps["plot_switch"], fjord,
                                               maps["out_width"])
-        written.append((name, arrays, map_name(maps["dir"], start, end, **when), ctx.map_draw(picture)))
+        as_png = maps.get("format", "jpeg") == "png"
+        written.append((name, arrays, map_name(maps["dir"], start, end, ext=".png" if as_png else ".jpg", **when),
+                        ctx.map_draw(picture, format="png" if as_png else "jpeg")))
     if vectors:
         ctx.map_arrows_release()
     if maps is not None and maps.get("photos") is not None:
@@ -393,7 +396,7 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
 
 def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts, fjord, day,
                        time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None, plot_switch=1,
-                       speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None):
+                       speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None, plot_format="jpeg"):
     """One day of hourly velocity files -> one gridded .npz per time window, as s3_utm_to_gridded_utm.utm_to_gridded_utm
     (s3:222-446) with plot_switch 0.
 
@@ -407,6 +410,8 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
     drawn and coded on the device.  plot_switch 1: the gridded map; 2: the all-vectors panel beside it.
     `cameras`: the parameter workbook's rows with camera, start_day, end_day, easting, northing (None: `schedule`, whose
     rows may carry them); `speedthreshold_cbar`: the speed at the colour bar's end.  plots=None calls nothing of this.
+    `plot_format`: "jpeg", or "png" for '%Y%m%d_%H%M-%H%M.png', the reference's name, a file that decodes to exactly the
+    rasterised pixels (`quality` plays no part then).
 
     `photos`: the reference's source_path_photos, a directory with <camera>/<%Y%m%d>/<%Y%m%d-%H%M%S>.jpg; every picture then
     carries, for each camera with tracks in its window, the photograph closest to the middle of the window (less than
@@ -414,11 +419,13 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
     `plots`; photos=None calls nothing of this."""
     if plots is not None and plot_switch not in (1, 2):
         raise ValueError("plot_switch must be 1 or 2")
+    if plot_format not in ("jpeg", "png"):
+        raise ValueError("plot_format is 'jpeg' or 'png'")
     if photos is not None and plots is None:
         raise ValueError("photos needs plots: the photographs go into the windows' pictures")
     maps = None if plots is None else dict(dir=str(plots), plot_switch=plot_switch, speedthreshold_cbar=speedthreshold_cbar,
                                            cameras=schedule if cameras is None else cameras, out_width=out_width, quality=quality,
-                                           photos=None if photos is None else str(photos))
+                                           photos=None if photos is None else str(photos), format=plot_format)
     plan = plan_day(camnames, source_path_head, source_path_tail, schedule, clock_drifts, day, time_window, grid_size)
     if not plan.files:
         return []
@@ -444,7 +451,8 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
 
 def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts,
                             fjord, time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None,
-                            plot_switch=1, speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None):
+                            plot_switch=1, speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None,
+                            plot_format="jpeg"):
     """s3:main's loop over days (without its process pool), on one context: the files of every day, in order.  The plot
     keywords are utm_to_gridded_utm's."""
     own = ctx is None
@@ -457,7 +465,7 @@ def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, 
                                       clock_drifts, fjord, day, time_window, grid_size, observation_threshold,
                                       ctx=ctx, save=save, plots=plots, plot_switch=plot_switch,
                                       speedthreshold_cbar=speedthreshold_cbar, cameras=cameras, out_width=out_width,
-                                      quality=quality, photos=photos)
+                                      quality=quality, photos=photos, plot_format=plot_format)
         return out
     finally:
         if own:

@@ -2,7 +2,7 @@
 plot_velocities_one_map, s3:471-641; plot_switch 2: plot_velocities_two_maps, s3:644-844): the grid with its unmeasured
 cells filled, one arrow per measured cell coloured by speed, with switch 2 a second panel with every velocity vector of the
 window, the fjord's outline, the cameras, four strings and a colour bar.  The device rasterises it and writes it as a JPEG
-file (`Context.map_draw`, `utm_to_gridded_utm(plots=...)`); here are the host-only parts: the reference's limits, the
+file or, with format="png", as a PNG file with exactly the rasterised pixels (`Context.map_draw`, `utm_to_gridded_utm(plots=...)`); here are the host-only parts: the reference's limits, the
 layout of the picture in integers, the colour table, the arrow scaling, the strings, the file name, and the host statement
 of the rasteriser (csrc/map_raster.h on the CPU).  DESIGN.md 7.7 has the rules and what differs from the reference's PNG.
 
@@ -96,11 +96,11 @@ def map_strings(day, start, end, cam_with_tracks, grid_size, time_window=None, m
             ("Camera: {}" if len(cam_with_tracks) == 1 else "Cameras: {}").format(cams), "Grid spacing: {} m".format(grid_size)]
 
 
-def map_name(plot_dir, start, end, time_window=None, min_time=None, max_time=None):
-    """'<plots>/%Y%m%d_%H%M-%H%M.jpg' of the window (s3:630-637, .jpg for .png); the full day (time_window 24.0) from the
-    rounded first and last selected times."""
+def map_name(plot_dir, start, end, time_window=None, min_time=None, max_time=None, ext=".jpg"):
+    """'<plots>/%Y%m%d_%H%M-%H%M.jpg' of the window (s3:630-637, .jpg for .png; ext=".png" gives the reference's name); the
+    full day (time_window 24.0) from the rounded first and last selected times."""
     a, b = (min_time, max_time) if time_window == 24.0 else (start, end)
-    return os.path.join(str(plot_dir), "{}-{}.jpg".format(a.strftime("%Y%m%d_%H%M"), b.strftime("%H%M")))
+    return os.path.join(str(plot_dir), "{}-{}{}".format(a.strftime("%Y%m%d_%H%M"), b.strftime("%H%M"), ext))
 
 
 def map_corner_right(xcord, ycord, limits):

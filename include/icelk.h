@@ -835,6 +835,29 @@ int icelk_map_inset_release(icelk_t* h);
 int icelk_map_draw_insets(icelk_t* h, const icelk_map_desc_t* d, const icelk_map_inset_t* insets, int n_insets, uint8_t* rgb_or_null,
                           int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len);
 
+/* ---- the PNG writer ------------------------------------------------------------ */
+/* An 8-bit R G B picture as a PNG file with the pixels exact: signature, IHDR (8 bits, colour type 2, no interlace), one
+ * IDAT, IEND.  IDAT is a zlib stream (78 01) of ONE fixed-Huffman deflate block over the filtered rows -- per row the
+ * filter type (of None, Sub, Up, Average, Paeth the one with the smallest sum of absolute values as signed bytes, ties to
+ * the lowest type) and the filtered bytes -- parsed greedily in segments of 4096 bytes with the match distances 1, 3 and
+ * 1 + 3 w (csrc/png_enc.h).  1 <= w, h <= 16384 and h (1 + 3 w) <= 2^28, stride >= 3 w, else ICELK_EARG.
+ * icelk_png_bound: the largest file the coder writes for a w x h picture (9 bits per filtered byte and the fixed parts).
+ * icelk_png_filter_host: the filtered rows, h (1 + 3 w) bytes.
+ * icelk_png_encode_host: the file, on the host.  ICELK_ECAP when it does not fit `capacity` (out may be NULL then), with
+ * *len = what it takes; otherwise *len bytes are written.  None of the three takes a handle; they are re-entrant. */
+int icelk_png_bound(int w, int h, uint64_t* bytes);
+int icelk_png_filter_host(const uint8_t* rgb, int w, int h, int stride, uint8_t* out);
+int icelk_png_encode_host(const uint8_t* rgb, int w, int h, int stride, uint8_t* out, uint64_t capacity, uint64_t* len);
+/* The same file, byte for byte, with filters, deflate and Adler-32 on the device (csrc/k_png.hip): host pixels up, file
+ * down.  Synchronous.  Refusals come before anything is allocated or enqueued.  ICELK_ECAP as above; the call is then
+ * repeated with a larger buffer. */
+int icelk_png_encode_rgb(icelk_t* h, const uint8_t* rgb, int w, int h_, int stride, uint8_t* out, uint64_t capacity, uint64_t* len);
+/* icelk_map_draw (insets_or_null NULL, n_insets 0) or icelk_map_draw_insets up to and including k_map_resolve / k_map_inset,
+ * then the PNG writer on the R G B that is resident on the device: the file decodes to exactly the pixels rgb_or_null
+ * receives.  d->quality is ignored.  Refusals, ICELK_ECAP and the repeat are those calls'. */
+int icelk_map_draw_png(icelk_t* h, const icelk_map_desc_t* d, const icelk_map_inset_t* insets_or_null, int n_insets, uint8_t* rgb_or_null,
+                       int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
