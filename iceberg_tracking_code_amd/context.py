@@ -56,6 +56,26 @@ def _criteria(criteria):
     return int(t), int(cnt), float(eps)
 
 
+# bytes first offered for a file of each kind (`_file_call`); a map's PNG is about 1.6 x its JPEG (profiles/png_map.txt)
+FIRST_GUESSES = {"crop": 1 << 16, "resave": 1 << 16, "plot": 1 << 18, "map_jpeg": 1 << 18, "map_png": 1 << 18}
+
+
+def _file_call(guesses, key, call, what, handle=None, extra=0):
+    """A call that fills a file buffer: call(out, capacity, byref(len)) -> rc is offered guesses[key] + extra bytes, then what
+    it says it takes (`_encode_call`); the next file of its kind is about as large: a quarter more is remembered for it."""
+    data = _encode_call(call, guesses[key] + extra, what, handle)
+    guesses[key] = max(1 << 16, len(data) + len(data) // 4)
+    return data
+
+
+def _rgb_out(want, width, height):
+    """The optional R G B output of a picture call: (array or None, pointer or None, row stride)"""
+    if not want:
+        return None, None, 0
+    rgb = np.empty((height, width, 3), np.uint8)
+    return rgb, _u8(rgb), rgb.strides[0]
+
+
 class Context:
     """Owns the device memory of `n_slots` resident frames (+ pyramids) and all point buffers."""
 
@@ -64,7 +84,7 @@ class Context:
         self._h = C.c_void_p()
         self.max_w, self.max_h, self.n_slots, self.max_pts, self.device = max_w, max_h, n_slots, max_pts, device
         check(self._lib.icelk_create(device, max_w, max_h, n_slots, max_pts, C.byref(self._h)), None)
-        self._crop_file_guess = 1 << 16                   # bytes `jpeg_crop_finish` offers first: about the last file's
+        self._guesses = dict(FIRST_GUESSES)
 
     # -- lifetime -----------------------------------------------------------------------------
     def close(self):
@@ -214,16 +234,20 @@ class Context:
         source's comment (`jpeg.source_comment`) or None.  The job is gone afterwards, also when the call raises -- with one
         exception: a file started without `crop_file=True` (IcelkError, ICELK_ESTATE) stays in flight, nothing of it has
         been waited for, and `jpeg_async_finish(slot)` is still to be called."""
+        return self._finish_file(lambda *args: self._lib.icelk_jpeg_async_finish_file(self._h, slot, *args), "icelk_jpeg_async_finish_file",
+                                 comment, lambda: self._lib.icelk_jpeg_async_finish(self._h, slot, None))
+
+    def _finish_file(self, call, what, comment, drop):
+        """call(comment, its length, out, capacity, byref(len), byref(stats)) -> rc; (the file's bytes, the statistics).
+        drop(): the library keeps a job whose file did not fit (ICELK_ECAP); this ends it here"""
         com, ncom = _comment_args(comment)
         st = _lib.JpegCropStats()
         try:
-            data = _encode_call(lambda out, cap, n: self._lib.icelk_jpeg_async_finish_file(self._h, slot, com, ncom, out, cap, n, C.byref(st)),
-                                self._crop_file_guess + ncom, "icelk_jpeg_async_finish_file", self._h)
+            data = _file_call(self._guesses, "crop", lambda out, cap, n: call(com, ncom, out, cap, n, C.byref(st)), what, self._h, ncom)
         except _lib.IcelkError as e:
-            if getattr(e, "code", None) == _lib.ECAP:     # the library keeps a job whose file did not fit: drop the file here
-                self._lib.icelk_jpeg_async_finish(self._h, slot, None)
+            if getattr(e, "code", None) == _lib.ECAP:
+                drop()
             raise
-        self._crop_file_guess = max(1 << 16, len(data) + len(data) // 4)
         stats = _stats_dict(st.huff)
         stats.update(route=_lib.JPEG_CROP_ROUTES[st.route], blocks=int(st.blocks), budget=int(st.budget), stream_len=int(st.stream_len))
         return data, stats
@@ -278,19 +302,8 @@ class Context:
         dictionary: the keys of `jpeg_huff_stats` for the source file, "route" -- "device", "host-huffman" or
         "over-budget" --, "blocks", "budget" and "stream_len").  `comment`: the source's comment (`jpeg.source_comment`),
         which Pillow carries over, or None.  The ticket is gone afterwards, also when the call raises."""
-        com, ncom = _comment_args(comment)
-        st = _lib.JpegCropStats()
-        try:
-            data = _encode_call(lambda out, cap, n: self._lib.icelk_jpeg_crop_finish(self._h, int(ticket), com, ncom, out, cap, n, C.byref(st)),
-                                self._crop_file_guess + ncom, "icelk_jpeg_crop_finish", self._h)
-        except _lib.IcelkError as e:
-            if getattr(e, "code", None) == _lib.ECAP:     # the library keeps a ticket whose file did not fit: drop it here
-                self._lib.icelk_jpeg_crop_cancel(self._h, int(ticket))
-            raise
-        self._crop_file_guess = max(1 << 16, len(data) + len(data) // 4)   # the next photo of a folder is about as large
-        stats = _stats_dict(st.huff)
-        stats.update(route=_lib.JPEG_CROP_ROUTES[st.route], blocks=int(st.blocks), budget=int(st.budget), stream_len=int(st.stream_len))
-        return data, stats
+        return self._finish_file(lambda *args: self._lib.icelk_jpeg_crop_finish(self._h, int(ticket), *args), "icelk_jpeg_crop_finish",
+                                 comment, lambda: self._lib.icelk_jpeg_crop_cancel(self._h, int(ticket)))
 
     def jpeg_crop_cancel(self, ticket):
         """Waits for what the job has enqueued and drops the ticket."""
@@ -330,11 +343,8 @@ class Context:
         source's comment (`jpeg.source_comment`), which Pillow carries over, or None.  IcelkError (code ICELK_ESTATE) when
         the handle has never re-saved."""
         com, ncom = _comment_args(comment)
-        guess = getattr(self, "_resave_file_guess", 1 << 16) + ncom
-        data = _encode_call(lambda out, cap, n: self._lib.icelk_jpeg_resave_encode(self._h, com, ncom, out, cap, n), guess,
-                            "icelk_jpeg_resave_encode", self._h)
-        self._resave_file_guess = max(1 << 16, len(data) + len(data) // 4)   # the next photo of a folder is about as large
-        return data
+        return _file_call(self._guesses, "resave", lambda out, cap, n: self._lib.icelk_jpeg_resave_encode(self._h, com, ncom, out, cap, n),
+                          "icelk_jpeg_resave_encode", self._h, ncom)
 
     def jpeg_encode(self, info, coef_ptr, comment, comment_len, guess):
         """`jpeg.encode_jpeg` on the device (icelk_jpeg_encode_coefficients)."""
@@ -639,16 +649,11 @@ class Context:
     # -- the picture of a segment (s1:397-434) --------------------------------------------------
     def _plot_call(self, slot, width, want_rgb, call, what):
         """call(rgb pointer, rgb stride, out, capacity, byref(len)) -> rc; the file's bytes, with the R G B if asked for"""
-        rgb, rgb_ptr, stride = None, None, 0
+        w, h = C.c_int(0), C.c_int(0)
         if want_rgb:
-            w, h = C.c_int(0), C.c_int(0)
             self._ck(self._lib.icelk_download_level(self._h, int(slot), 0, None, 0, C.byref(w), C.byref(h)))
-            ow, oh = plot_size(w.value, h.value, width)
-            rgb = np.empty((oh, ow, 3), np.uint8)
-            rgb_ptr, stride = _u8(rgb), rgb.strides[0]
-        guess = getattr(self, "_plot_file_guess", 1 << 18)
-        data = _encode_call(lambda out, cap, n: call(rgb_ptr, stride, out, cap, n), guess, what, self._h)
-        self._plot_file_guess = max(1 << 16, len(data) + len(data) // 4)   # the next picture of a day is about as large
+        rgb, rgb_ptr, stride = _rgb_out(want_rgb, *(plot_size(w.value, h.value, width) if want_rgb else (0, 0)))
+        data = _file_call(self._guesses, "plot", lambda out, cap, n: call(rgb_ptr, stride, out, cap, n), what, self._h)
         return (data, rgb) if want_rgb else data
 
     def plot_tracks(self, slot, tracks, width=PLOT_WIDTH, stamp="", quality=PLOT_QUALITY, want_rgb=False):
@@ -730,27 +735,17 @@ class Context:
         if format not in ("jpeg", "png"):
             raise ValueError("format is 'jpeg' or 'png'")
         d, keep = map_descriptor(picture)
-        rgb, rgb_ptr, stride = None, None, 0
-        if want_rgb:
-            rgb = np.empty((max(d.height, 1), max(d.width, 1), 3), np.uint8)
-            rgb_ptr, stride = _u8(rgb), rgb.strides[0]
+        rgb, rgb_ptr, stride = _rgb_out(want_rgb, max(d.width, 1), max(d.height, 1))
+        insets, n_insets = map_inset_array(picture["insets"]) if picture.get("insets") else (None, 0)
         if format == "png":
-            insets, n_insets = map_inset_array(picture["insets"]) if picture.get("insets") else (None, 0)
-            data = _encode_call(lambda out, cap, n: self._lib.icelk_map_draw_png(self._h, C.byref(d), insets, n_insets, rgb_ptr, stride, out, cap, n),
-                                getattr(self, "_map_png_guess", 1 << 18), "icelk_map_draw_png", self._h)
-            self._map_png_guess = max(1 << 16, len(data) + len(data) // 4)
-            del keep
-            return (data, rgb) if want_rgb else data
-        guess = getattr(self, "_map_file_guess", 1 << 18)
-        if picture.get("insets"):
-            insets, n_insets = map_inset_array(picture["insets"])
-            data = _encode_call(lambda out, cap, n: self._lib.icelk_map_draw_insets(self._h, C.byref(d), insets, n_insets, rgb_ptr, stride, out, cap, n),
-                                guess, "icelk_map_draw_insets", self._h)
+            fn, what, head = self._lib.icelk_map_draw_png, "icelk_map_draw_png", (insets, n_insets)
+        elif n_insets:
+            fn, what, head = self._lib.icelk_map_draw_insets, "icelk_map_draw_insets", (insets, n_insets)
         else:
-            data = _encode_call(lambda out, cap, n: self._lib.icelk_map_draw(self._h, C.byref(d), rgb_ptr, stride, out, cap, n), guess,
-                                "icelk_map_draw", self._h)
-        self._map_file_guess = max(1 << 16, len(data) + len(data) // 4)   # the next window's picture is about as large
-        del keep
+            fn, what, head = self._lib.icelk_map_draw, "icelk_map_draw", ()
+        data = _file_call(self._guesses, "map_" + format, lambda out, cap, n: fn(self._h, C.byref(d), *head, rgb_ptr, stride, out, cap, n),
+                          what, self._h)
+        del keep   # what the descriptor points into: alive until the call has returned
         return (data, rgb) if want_rgb else data
 
     # -- measurement ----------------------------------------------------------------------------

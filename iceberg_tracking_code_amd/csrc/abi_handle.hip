@@ -173,6 +173,7 @@ static void destroy_ctx(Ctx* c)
     jpeg_enc_destroy(c);
     plot_destroy(c);
     map_destroy(c);
+    picture_destroy(c);
     png_destroy(c);
     prof_drain(c);
     for (auto& e : c->evt_pool) {

@@ -1,23 +1,22 @@
 // abi_map.hip -- the map the reference draws of every gridded window (s3:449-465, plot_switch 1 and 2): the grid, an arrow
 // per measured cell coloured by speed, with switch 2 every velocity vector of the window in a second panel, the outline, the
-// cameras, four strings and a colour bar -- rasterised on the device and handed to the JPEG writer that is there as well.
+// cameras, four strings and a colour bar -- rasterised on the device and handed to the picture writer that is there as well.
 //
 //   host    icelk_map_glyph, icelk_map_overlay_host: map_raster.h on the CPU; no handle, re-entrant.
 //           icelk_map_overlay_insets_host: the same, then thumb_raster.h's paste
 //   device  icelk_map_arrows_set / _release (a day's vectors, resident like the s4 cube) and icelk_map_draw.  On the handle's
-//           compute stream: k_map_clear, then per panel k_map_cells, k_map_polyline, k_map_arrows, then k_map_resolve
-//           (k_map.hip) into the R G B buffer of a working set of the map's own (Ctx::Map), then the re-save's forward
-//           kernel (jpeg_fwd_on) at the caller's quality and the entropy coder (jpeg_encode_on) on that set, then header,
-//           scan and EOI into the caller's buffer.  The call waits for the device.  After ICELK_ECAP the call is simply
-//           repeated: the picture is a function of its arguments.
-//           icelk_map_draw_insets: the same with one k_map_inset (k_thumb.hip) per inset between k_map_resolve and the
-//           forward kernel, from the resident thumbnails of abi_thumb.hip, whose header states that kernel's bounds
-//           icelk_map_draw_png: the same drawing (draw_picture) with or without insets, then the PNG writer of
-//           abi_png.hip on the resident R G B instead of the forward kernel and the JPEG coder; the quality is ignored
+//           compute stream (draw_picture): k_picture_clear, then per panel k_map_cells, k_map_polyline, k_map_arrows, then
+//           k_map_resolve (k_map.hip), from planes of the map's own (Ctx::Map) into the picture writer's R G B; the file,
+//           the optional R G B output, the wait for the device and ICELK_ECAP are the writer's (abi_picture.hip:
+//           picture_check, picture_grow, picture_write)
+//           icelk_map_draw_insets: the same with one k_map_inset (k_thumb.hip) per inset behind k_map_resolve, from the
+//           resident thumbnails of abi_thumb.hip, whose header states that kernel's bounds
+//           icelk_map_draw_png: the same drawing with or without insets, and the writer is asked for a PNG: the quality
+//           is ignored
 //
 // Bounds, store by store.  Everything is sized from the picture (Wo x Ho, px = Wo Ho padded to four pixels) and the
 // descriptor's counts before anything is enqueued, and check_desc has refused every view that is not inside the picture.
-//   k_map_clear     16-byte stores k < 3 px / 4 into the 3 px words of d_planes
+//   k_picture_clear 16-byte stores k < 3 px / 4 into the 3 px words of d_planes
 //   k_map_cells     atomicMax into base = d_planes[0 .. px): walk_cell clips the fill's rectangle to [0, vw) x [0, vh) and
 //   k_map_polyline  walk_pair clips the range it walks to the view and tests the other coordinate of every hit, whatever the
 //                   numbers hold (items with a coordinate that is not finite or beyond 2^20 pixels never get that far); the
@@ -31,12 +30,11 @@
 //   k_map_resolve   reads the three planes at 4-pixel steps below px (padded), the scene, and arrows[5 (top - 1) + 4] with
 //                   top <= the panel's n (only k_map_arrows of that panel wrote top inside its view, and the views of two
 //                   panels do not overlap: check_desc); stores 12 bytes per four pixels below 3 Wo Ho, the tail byte by byte
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "icelk_ctx.h"
-#include "jpeg_enc_host.h"
-#include "jpeg_resave_host.h"
 
 namespace icelk {
 
@@ -47,7 +45,6 @@ void map_destroy(Ctx* c)
     for (void* q : p)
         if (q) hipFree(q);
     delete M.h_scene;
-    jpeg_resave_free(M.rs);
     map_insets_free(c);
     M = Ctx::Map{};
 }
@@ -56,8 +53,6 @@ namespace {
 
 constexpr int kMaxArrows = 1 << 27;
 constexpr int kMaxItems = 1 << 24;   // cells, outline vertices
-
-size_t pad4(size_t v) { return (v + 3) & ~(size_t)3; }
 
 bool finite(double v) { return v > -HUGE_VAL && v < HUGE_VAL; }
 
@@ -174,96 +169,104 @@ int overlay_host(const icelk_map_desc_t* d, map::Scene& S, const double* residen
 }
 
 // The insets of a picture against the thumbnails `have` (kMaxInsets entries, host or device memory): what is refused, and
-// the paste's arguments.  The descriptor has passed check_desc
-int check_insets(const icelk_map_desc_t* d, const icelk_map_inset_t* in, int n, const icelk_map_inset_pixels_t* have, thumb::Inset* out,
-                 const char** why)
+// the paste's arguments.  The descriptor has passed check_desc.  c: a handle, or whatever has an `err` to take the reason
+template <typename Handle>
+int check_insets(Handle* c, const icelk_map_desc_t* d, const icelk_map_inset_t* in, int n, const icelk_map_inset_pixels_t* have, thumb::Inset* out)
 {
-    *why = "insets: a count outside 0 .. 8 or a null array";
-    if (n < 0 || n > thumb::kMaxInsets || (n > 0 && (!in || !have))) return ICELK_EARG;
+    if (n < 0 || n > thumb::kMaxInsets || (n > 0 && (!in || !have))) FAIL(c, ICELK_EARG, "insets: a count outside 0 .. 8 or a null array");
     for (int k = 0; k < n; k++) {
         const icelk_map_inset_t& I = in[k];
-        *why = "an inset index outside 0 .. 7";
-        if (I.index < 0 || I.index >= thumb::kMaxInsets) return ICELK_EARG;
+        if (I.index < 0 || I.index >= thumb::kMaxInsets) FAIL(c, ICELK_EARG, "an inset index outside 0 .. 7");
         const icelk_map_inset_pixels_t& T = have[I.index];
-        *why = "an inset's index holds no thumbnail (icelk_map_inset_set_file, icelk_map_inset_set_pixels)";
-        if (!T.rgb) return ICELK_ESTATE;
-        *why = "a thumbnail that is not wholly inside the picture";
-        if (T.w < 1 || T.h < 1 || T.stride < 3 * T.w || I.x0 < 0 || I.y0 < 0 || I.x0 > d->width - T.w || I.y0 > d->height - T.h) return ICELK_EARG;
-        *why = "a label position beyond 2^20";
+        if (!T.rgb) FAIL(c, ICELK_ESTATE, "an inset's index holds no thumbnail (icelk_map_inset_set_file, icelk_map_inset_set_pixels)");
+        if (T.w < 1 || T.h < 1 || T.stride < 3 * T.w || I.x0 < 0 || I.y0 < 0 || I.x0 > d->width - T.w || I.y0 > d->height - T.h)
+            FAIL(c, ICELK_EARG, "a thumbnail that is not wholly inside the picture");
         if (I.label_px < -thumb::kLabelLimit || I.label_px > thumb::kLabelLimit || I.label_py < -thumb::kLabelLimit || I.label_py > thumb::kLabelLimit)
-            return ICELK_EARG;
+            FAIL(c, ICELK_EARG, "a label position beyond 2^20");
         out[k].x0 = I.x0, out[k].y0 = I.y0, out[k].w = T.w, out[k].h = T.h, out[k].px = T.rgb, out[k].pitch = T.stride;
-        *why = "a label of more than 48 characters, or a character outside 0-9 - : . / space A-Z a-z , ( )";
         char text[sizeof(I.label) + 1];
         memcpy(text, I.label, sizeof(I.label));
         text[sizeof(I.label)] = 0;
-        if (!map::make_text(text, I.label_px, I.label_py, &out[k].label)) return ICELK_EARG;
+        if (!map::make_text(text, I.label_px, I.label_py, &out[k].label))
+            FAIL(c, ICELK_EARG, "a label of more than 48 characters, or a character outside 0-9 - : . / space A-Z a-z , ( )");
     }
-    *why = nullptr;
+    return ICELK_OK;
+}
+
+// icelk_map_overlay_host and, with insets, icelk_map_overlay_insets_host
+int overlay_call(const icelk_map_desc_t* d, const double* resident, const int32_t* group, int n_resident, const icelk_map_inset_t* insets,
+                 int n_insets, const icelk_map_inset_pixels_t* have, uint8_t* rgb, int rgb_stride)
+{
+    std::unique_ptr<map::Scene> S(new (std::nothrow) map::Scene);
+    if (!S) return ICELK_ENOMEM;
+    if (!rgb || check_desc(d, S.get())) return ICELK_EARG;
+    thumb::Inset I[thumb::kMaxInsets];
+    struct { std::string err; } nobody;   // no handle: the reason goes nowhere
+    if (int rc = check_insets(&nobody, d, insets, n_insets, have, I)) return rc;
+    if (rgb_stride < 3 * d->width || n_resident < 0 || n_resident > kMaxArrows) return ICELK_EARG;
+    for (int k = 0; k < d->n_panels; k++)
+        if (d->panel[k].resident && (!resident || (d->panel[k].group >= 0 && !group))) return ICELK_ESTATE;
+    fill_scene(d, S.get());
+    if (int rc = overlay_host(d, *S, resident, group, n_resident, rgb, rgb_stride)) return rc;
+    thumb::paste_host(I, n_insets, d->width, d->height, rgb, (size_t)rgb_stride);
     return ICELK_OK;
 }
 
 struct Picture {
-    icelk_jpeg_info_t info;   // of the file
-    enc::Layout L;
-    size_t items;             // doubles of the call's cells, outlines and arrows
-    size_t measured;          // bytes
+    PictureFile file;
+    size_t items;      // doubles of the call's cells, outlines and arrows
+    size_t measured;   // bytes
 };
 
-// Everything that can be refused is refused here, before anything is enqueued or allocated
-// as_png: the file is a PNG (abi_png.hip): the quality is not looked at and the picture has no JPEG layout
-int check_device_call(Ctx* c, const icelk_map_desc_t* d, map::Scene* S, const uint8_t* rgb, int rgb_stride, const uint64_t* len, bool as_png,
-                      Picture* Q)
+// Everything that can be refused is refused here, before anything is enqueued or allocated.  The scene's texts are made
+// on the way (check_desc), the insets' paste arguments too (I: kMaxInsets entries)
+int check_device_call(Ctx* c, const icelk_map_desc_t* d, PictureFormat format, const icelk_map_inset_t* insets, int n_insets, const uint8_t* rgb,
+                      int rgb_stride, const uint64_t* len, map::Scene* S, thumb::Inset* I, Picture* Q)
 {
-    if (!len) FAIL(c, ICELK_EARG, "null length");
+    const Ctx::Map& M = c->map;
     if (const char* why = check_desc(d, S)) FAIL(c, ICELK_EARG, why);
-    if (int rc = as_png ? png_check(c, d->width, d->height) : jpeg_resave_check(c, d->width, d->height, d->quality)) return rc;
-    if (rgb && rgb_stride < 3 * d->width) FAIL(c, ICELK_EARG, "rgb stride smaller than 3 x the picture's width");
+    if (int rc = picture_check(c, d->width, d->height, format, d->quality, rgb, rgb_stride, len, &Q->file)) return rc;
     Q->items = Q->measured = 0;
     for (int k = 0; k < d->n_panels; k++) {
         const icelk_map_panel_t& p = d->panel[k];
-        if (p.resident && !c->map.have_arrows) FAIL(c, ICELK_ESTATE, "a panel draws the resident arrows and none are set (icelk_map_arrows_set)");
+        if (p.resident && !M.have_arrows) FAIL(c, ICELK_ESTATE, "a panel draws the resident arrows and none are set (icelk_map_arrows_set)");
         Q->items += 3 * (size_t)p.n_cells + 2 * (size_t)p.n_outline + (p.resident ? 0 : 5 * (size_t)p.n_arrows);
         Q->measured += (size_t)p.n_cells;
     }
-    Q->info = icelk_jpeg_info_t{};
-    Q->L = enc::Layout{};
-    if (as_png) return ICELK_OK;
-    resave::resave_info(d->width, d->height, d->quality, &Q->info);
-    return jpeg_enc_rc(c, enc::layout_of(&Q->info, &Q->L));
+    icelk_map_inset_pixels_t have[thumb::kMaxInsets];
+    for (int k = 0; k < thumb::kMaxInsets; k++) have[k] = icelk_map_inset_pixels_t{M.d_inset[k], M.inset_w[k], M.inset_h[k], 3 * M.inset_w[k], 0};
+    if (int rc = check_insets(c, d, insets, n_insets, have, I)) return rc;
+    for (int k = 0; k < d->n_panels; k++)
+        if (d->panel[k].resident && d->panel[k].group >= 0 && !M.d_group)
+            FAIL(c, ICELK_ESTATE, "a panel asks for one group and the resident arrows have none");
+    return ICELK_OK;
 }
 
-int grow_picture(Ctx* c, const icelk_map_desc_t* d, const Picture& Q)
+int grow_planes(Ctx* c, const Picture& Q)
 {
     Ctx::Map& M = c->map;
-    const size_t px = pad4((size_t)d->width * d->height);
-    if (!M.h_scene) {
-        M.h_scene = new (std::nothrow) map::Scene;
-        if (!M.h_scene) FAIL(c, ICELK_ENOMEM, "the map's scene");
-    }
     if (!M.d_scene)
         if (int rc = dmalloc(c, &M.d_scene, 1)) return rc;
-    if (int rc = grow(c, &M.d_planes, &M.planes_cap, 3 * px)) return rc;
+    if (int rc = grow(c, &M.d_planes, &M.planes_cap, 3 * Q.file.px)) return rc;
     if (int rc = grow(c, &M.d_items, &M.items_cap, Q.items)) return rc;
     if (int rc = grow(c, &M.d_measured, &M.measured_cap, Q.measured)) return rc;
-    if (int rc = grow(c, &M.rs.d_rgb, &M.rs.rgb_cap, 3 * px)) return rc;
-    return grow(c, &M.rs.d_rcoef, &M.rs.rcoef_cap, (size_t)Q.info.coef_count);
+    return picture_grow(c, Q.file);
 }
 
-// the picture into M.rs.d_rgb, enqueued on the handle's compute stream: what every file format starts from
-int draw_picture(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked, const thumb::Inset* insets, int n_insets)
+// the picture into the writer's R G B, enqueued on the handle's compute stream: what every file format starts from.
+// M.h_scene holds the checked scene
+int draw_picture(Ctx* c, const icelk_map_desc_t* d, size_t px, const thumb::Inset* insets, int n_insets)
 {
     Ctx::Map& M = c->map;
     const hipStream_t st = c->stream;
     const int Wo = d->width, Ho = d->height;
-    const size_t px = pad4((size_t)Wo * Ho);
+    uint8_t* rgb = c->picture.d_rgb;
     uint32_t *base = M.d_planes, *top = M.d_planes + px, *count = M.d_planes + 2 * px;
     map::Scene& S = *M.h_scene;
-    S = checked;
     fill_scene(d, &S);
     {
         ProfScope p(c, K_MAP_CLEAR);
-        launch_map_clear(st, M.d_planes, 3 * px);
+        launch_picture_clear(st, M.d_planes, 3 * px);
     }
     if (int rc = check_launch(c, "map_clear")) return rc;
     size_t at = 0, at_m = 0;   // doubles / bytes of d_items / d_measured handed out
@@ -311,36 +314,17 @@ int draw_picture(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked, c
     HIPCHK(c, hipMemcpyAsync(M.d_scene, &S, sizeof(S), hipMemcpyHostToDevice, st));
     {
         ProfScope p(c, K_MAP_RESOLVE);
-        launch_map_resolve(st, M.d_scene, Wo, Ho, base, top, count, M.rs.d_rgb);
+        launch_map_resolve(st, M.d_scene, Wo, Ho, base, top, count, rgb);
     }
     if (int rc = check_launch(c, "map_resolve")) return rc;
     for (int k = 0; k < n_insets; k++) {
         {
             ProfScope p(c, K_MAP_INSET);
-            launch_map_inset(st, insets[k], Wo, Ho, M.rs.d_rgb);
+            launch_map_inset(st, insets[k], Wo, Ho, rgb);
         }
         if (int rc = check_launch(c, "map_inset")) return rc;
     }
     return ICELK_OK;
-}
-
-int draw_and_encode(Ctx* c, const icelk_map_desc_t* d, const map::Scene& checked, const Picture& Q, bool as_png, uint8_t* rgb, int rgb_stride,
-                    uint8_t* file, uint64_t capacity, uint64_t* len, const thumb::Inset* insets = nullptr, int n_insets = 0)
-{
-    Ctx::Map& M = c->map;
-    const hipStream_t st = c->stream;
-    const int Wo = d->width, Ho = d->height;
-    if (int rc = draw_picture(c, d, checked, insets, n_insets)) return rc;
-    if (as_png) {
-        uint32_t nbytes = 0;
-        if (int rc = png_encode_on(c, st, M.rs.d_rgb, 3u * (uint32_t)Wo, Wo, Ho, &nbytes)) return rc;   // synchronises
-        if (rgb) HIPCHK(c, hipMemcpy2DAsync(rgb, rgb_stride, M.rs.d_rgb, 3 * (size_t)Wo, 3 * (size_t)Wo, Ho, hipMemcpyDeviceToHost, st));
-        return png_deliver_file(c, st, rgb != nullptr, Wo, Ho, nbytes, file, capacity, len);
-    }
-    if (int rc = jpeg_fwd_on(c, st, M.rs.d_rgb, M.rs.d_rcoef, Wo, Ho, Q.info)) return rc;
-    if (int rc = jpeg_encode_on(c, M.rs.enc, st, Q.L, M.rs.d_rcoef)) return rc;   // synchronises
-    if (rgb) HIPCHK(c, hipMemcpy2DAsync(rgb, rgb_stride, M.rs.d_rgb, 3 * (size_t)Wo, 3 * (size_t)Wo, Ho, hipMemcpyDeviceToHost, st));
-    return jpeg_deliver_file(c, M.rs.enc, st, rgb != nullptr, Q.info, nullptr, 0, file, capacity, len);
 }
 
 void release_arrows(Ctx* c)
@@ -370,37 +354,14 @@ int icelk_map_glyph(int ch, uint8_t* rows)
 int icelk_map_overlay_host(const icelk_map_desc_t* d, const double* resident, const int32_t* group, int n_resident, uint8_t* rgb,
                            int rgb_stride)
 {
-    map::Scene* S = new (std::nothrow) map::Scene;
-    if (!S) return ICELK_ENOMEM;
-    int rc = ICELK_EARG;
-    if (rgb && !check_desc(d, S) && rgb_stride >= 3 * d->width && n_resident >= 0 && n_resident <= kMaxArrows) {
-        rc = ICELK_OK;
-        for (int k = 0; k < d->n_panels; k++)
-            if (d->panel[k].resident && (!resident || (d->panel[k].group >= 0 && !group))) rc = ICELK_ESTATE;
-        if (rc == ICELK_OK) {
-            fill_scene(d, S);
-            rc = overlay_host(d, *S, resident, group, n_resident, rgb, rgb_stride);
-        }
-    }
-    delete S;
-    return rc;
+    return overlay_call(d, resident, group, n_resident, nullptr, 0, nullptr, rgb, rgb_stride);
 }
 
 int icelk_map_overlay_insets_host(const icelk_map_desc_t* d, const double* resident, const int32_t* group, int n_resident,
                                   const icelk_map_inset_t* insets, int n_insets, const icelk_map_inset_pixels_t* resident_insets,
                                   uint8_t* rgb, int rgb_stride)
 {
-    map::Scene* S = new (std::nothrow) map::Scene;
-    if (!S) return ICELK_ENOMEM;
-    const bool desc_ok = !check_desc(d, S);
-    delete S;
-    if (!rgb || !desc_ok) return ICELK_EARG;
-    thumb::Inset I[thumb::kMaxInsets];
-    const char* why;
-    if (int rc = check_insets(d, insets, n_insets, resident_insets, I, &why)) return rc;
-    if (int rc = icelk_map_overlay_host(d, resident, group, n_resident, rgb, rgb_stride)) return rc;
-    thumb::paste_host(I, n_insets, d->width, d->height, rgb, (size_t)rgb_stride);
-    return ICELK_OK;
+    return overlay_call(d, resident, group, n_resident, insets, n_insets, resident_insets, rgb, rgb_stride);
 }
 
 int icelk_map_arrows_set(icelk_t* h, const double* arrows, const int32_t* group_or_null, int n)
@@ -439,63 +400,41 @@ int icelk_map_arrows_release(icelk_t* h)
     return ICELK_OK;
 }
 
-// icelk_map_draw (no insets: nothing below touches them) and icelk_map_draw_insets
-static int map_draw_call(icelk_t* h, const char* range, bool as_png, const icelk_map_desc_t* d, const icelk_map_inset_t* insets, int n_insets,
-                         uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len)
+// the three entry points: icelk_map_draw has no insets
+static int map_draw_call(icelk_t* h, const char* range, PictureFormat format, const icelk_map_desc_t* d, const icelk_map_inset_t* insets,
+                         int n_insets, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len)
 {
     if (!h) return ICELK_EARG;
     Ctx* c = C(h);
     Range rg(range);
-    map::Scene* S = new (std::nothrow) map::Scene;
-    if (!S) FAIL(c, ICELK_ENOMEM, "the map's scene");
+    Ctx::Map& M = c->map;
+    if (!M.h_scene) M.h_scene = new (std::nothrow) map::Scene;
+    if (!M.h_scene) FAIL(c, ICELK_ENOMEM, "the map's scene");
     Picture Q;
-    int rc = check_device_call(c, d, S, rgb_or_null, rgb_stride, len, as_png, &Q);
     thumb::Inset I[thumb::kMaxInsets];
-    if (rc == ICELK_OK && (insets || n_insets)) {
-        icelk_map_inset_pixels_t have[thumb::kMaxInsets];
-        for (int k = 0; k < thumb::kMaxInsets; k++)
-            have[k] = icelk_map_inset_pixels_t{c->map.d_inset[k], c->map.inset_w[k], c->map.inset_h[k], 3 * c->map.inset_w[k], 0};
-        const char* why;
-        rc = check_insets(d, insets, n_insets, have, I, &why);
-        if (rc) c->err = why;
-    }
-    if (rc == ICELK_OK) {
-        for (int k = 0; k < d->n_panels; k++)
-            if (d->panel[k].resident && d->panel[k].group >= 0 && !c->map.d_group) {
-                c->err = "a panel asks for one group and the resident arrows have none";
-                rc = ICELK_ESTATE;
-            }
-    }
-    if (rc == ICELK_OK) {
-        hipError_t e = hipSetDevice(c->device);
-        if (e != hipSuccess) {
-            c->err = std::string("hipSetDevice: ") + hipGetErrorString(e);
-            rc = ICELK_EHIP;
-        }
-    }
-    if (rc == ICELK_OK) rc = grow_picture(c, d, Q);
-    if (rc == ICELK_OK && as_png) rc = png_grow(c, d->width, d->height);
-    if (rc == ICELK_OK) rc = draw_and_encode(c, d, *S, Q, as_png, rgb_or_null, rgb_stride, file, capacity, len, I, n_insets);
-    delete S;
-    return rc;
+    if (int rc = check_device_call(c, d, format, insets, n_insets, rgb_or_null, rgb_stride, len, M.h_scene, I, &Q)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = grow_planes(c, Q)) return rc;
+    if (int rc = draw_picture(c, d, Q.file.px, I, n_insets)) return rc;
+    return picture_write(c, c->stream, Q.file, rgb_or_null, rgb_stride, file, capacity, len);
 }
 
 int icelk_map_draw(icelk_t* h, const icelk_map_desc_t* d, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
                    uint64_t* len)
 {
-    return map_draw_call(h, "icelk map_draw", false, d, nullptr, 0, rgb_or_null, rgb_stride, file, capacity, len);
+    return map_draw_call(h, "icelk map_draw", PICTURE_JPEG, d, nullptr, 0, rgb_or_null, rgb_stride, file, capacity, len);
 }
 
 int icelk_map_draw_insets(icelk_t* h, const icelk_map_desc_t* d, const icelk_map_inset_t* insets, int n_insets, uint8_t* rgb_or_null,
                           int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len)
 {
-    return map_draw_call(h, "icelk map_draw_insets", false, d, insets, n_insets, rgb_or_null, rgb_stride, file, capacity, len);
+    return map_draw_call(h, "icelk map_draw_insets", PICTURE_JPEG, d, insets, n_insets, rgb_or_null, rgb_stride, file, capacity, len);
 }
 
 int icelk_map_draw_png(icelk_t* h, const icelk_map_desc_t* d, const icelk_map_inset_t* insets_or_null, int n_insets, uint8_t* rgb_or_null,
                        int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len)
 {
-    return map_draw_call(h, "icelk map_draw_png", true, d, insets_or_null, n_insets, rgb_or_null, rgb_stride, file, capacity, len);
+    return map_draw_call(h, "icelk map_draw_png", PICTURE_PNG, d, insets_or_null, n_insets, rgb_or_null, rgb_stride, file, capacity, len);
 }
 
 }  // extern "C"

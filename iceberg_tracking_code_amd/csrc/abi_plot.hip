@@ -1,14 +1,13 @@
 // abi_plot.hip -- the picture the reference draws of every saved segment (s1:397-434, plot_switch = 1): the segment's last
 // gray frame at out_width pixels, its surviving tracks as red lines, their end points as red dots, a stamp in a corner --
-// rasterised on the device, where frame and tracks already are, and handed to the JPEG writer that is there as well.
+// rasterised on the device, where frame and tracks already are, and handed to the picture writer that is there as well.
 //
 //   host    icelk_plot_size, icelk_plot_glyph, icelk_plot_overlay_host: plot_raster.h on the CPU; no handle, re-entrant
 //   device  icelk_plot_tracks (tracks from the host) and icelk_seg_plot (the surviving tracks of a segment, gathered on the
-//           device: no track data crosses PCIe).  On the handle's compute stream: k_plot_background, k_plot_clear,
-//           k_plot_scatter, k_plot_resolve (k_plot.hip) into the R G B buffer of a working set of plotting's own
-//           (Ctx::Plot), then the re-save's forward kernel (jpeg_fwd_on) at the caller's quality and the entropy coder
-//           (jpeg_encode_on) on that set, then header, scan and EOI into the caller's buffer.  The calls wait for the
-//           device.  After ICELK_ECAP the call is simply repeated: the picture is a function of its arguments.
+//           device: no track data crosses PCIe).  On the handle's compute stream: k_plot_background, k_picture_clear,
+//           k_plot_scatter, k_plot_resolve (k_plot.hip), from planes of plotting's own (Ctx::Plot) into the picture
+//           writer's R G B; the file, the optional R G B output, the wait for the device and ICELK_ECAP are the writer's
+//           (abi_picture.hip: picture_check, picture_grow, picture_write)
 //
 // Bounds.  Every store of the kernels is inside a buffer sized from Wo x Ho before anything is enqueued: the background
 // kernel writes pixel (i, j) with i < Wo, j < Ho and reads dwords inside the rows of the slot's level 0; the scatter
@@ -19,8 +18,6 @@
 #include <vector>
 
 #include "icelk_ctx.h"
-#include "jpeg_enc_host.h"
-#include "jpeg_resave_host.h"
 
 namespace icelk {
 
@@ -30,15 +27,12 @@ void plot_destroy(Ctx* c)
     void* p[] = {P.d_bg, P.d_counts, P.d_tables, P.d_tracks};
     for (void* q : p)
         if (q) hipFree(q);
-    jpeg_resave_free(P.rs);
     P = Ctx::Plot{};
 }
 
 namespace {
 
 constexpr int kMaxTracks = 1 << 24;
-
-size_t pad4(size_t v) { return (v + 3) & ~(size_t)3; }
 
 // what needs no handle: the frame's size, the width asked for, the stamp.  nullptr: fine
 const char* check_picture(int w, int h, int out_width, const char* stamp, plot::Stamp* S)
@@ -103,36 +97,28 @@ int overlay_host(const uint8_t* gray, int w, int h, int stride, const float* tra
 }
 
 struct Picture {
-    int slot, Wo, Ho, quality;
+    int slot;
     plot::Stamp stamp;
-    icelk_jpeg_info_t info;   // of the file
-    enc::Layout L;
+    PictureFile file;
 };
 
 // Everything that can be refused is refused here, before anything is enqueued or allocated
 int check_device_call(Ctx* c, int slot, int out_width, const char* stamp, int quality, const uint8_t* rgb, int rgb_stride, const uint64_t* len,
                       Picture* Q)
 {
-    if (!len) FAIL(c, ICELK_EARG, "null length");
     if (int rc = check_slot(c, slot, true)) return rc;
     if (!c->jpeg.slot_job.empty() && c->jpeg.slot_job[slot] >= 0)
         FAIL(c, ICELK_ESTATE, "the slot's JPEG file is still in flight (icelk_jpeg_async_finish ends it)");
     const Slot& s = c->slots[slot];
     if (const char* why = check_picture(s.w, s.h, out_width, stamp, &Q->stamp)) FAIL(c, ICELK_EARG, why);
     Q->slot = slot;
-    Q->Wo = plot::out_width_of(s.w, out_width);
-    Q->Ho = plot::out_height_of(s.w, s.h, Q->Wo);
-    Q->quality = quality;
-    if (int rc = jpeg_resave_check(c, Q->Wo, Q->Ho, quality)) return rc;
-    if (rgb && rgb_stride < 3 * Q->Wo) FAIL(c, ICELK_EARG, "rgb stride smaller than 3 x the picture's width");
-    resave::resave_info(Q->Wo, Q->Ho, quality, &Q->info);
-    return jpeg_enc_rc(c, enc::layout_of(&Q->info, &Q->L));
+    const int Wo = plot::out_width_of(s.w, out_width);
+    return picture_check(c, Wo, plot::out_height_of(s.w, s.h, Wo), PICTURE_JPEG, quality, rgb, rgb_stride, len, &Q->file);
 }
 
-int grow_picture(Ctx* c, const Picture& Q)
+int grow_planes(Ctx* c, const Picture& Q)
 {
     Ctx::Plot& P = c->plot;
-    const size_t px = pad4((size_t)Q.Wo * Q.Ho);
     if (!P.d_tables) {
         uint32_t T[2 * plot::kTable];
         plot::make_tables(T, T + plot::kTable);
@@ -145,50 +131,44 @@ int grow_picture(Ctx* c, const Picture& Q)
         }
         P.d_tables = d;
     }
-    if (int rc = grow(c, &P.d_bg, &P.bg_cap, px)) return rc;
-    if (int rc = grow(c, &P.d_counts, &P.counts_cap, 2 * px)) return rc;
-    if (int rc = grow(c, &P.rs.d_rgb, &P.rs.rgb_cap, 3 * px)) return rc;
-    return grow(c, &P.rs.d_rcoef, &P.rs.rcoef_cap, (size_t)Q.info.coef_count);
+    if (int rc = grow(c, &P.d_bg, &P.bg_cap, Q.file.px)) return rc;
+    if (int rc = grow(c, &P.d_counts, &P.counts_cap, 2 * Q.file.px)) return rc;
+    return picture_grow(c, Q.file);
 }
 
-// d_tracks: (n, nv, 2) on the device, ordered on the compute stream.  The four kernels, the forward kernel, the coder;
-// then the picture's R G B (if asked for) and the file go to the host
-int draw_and_encode(Ctx* c, const Picture& Q, const float* d_tracks, int n, int nv, uint8_t* rgb, int rgb_stride, uint8_t* file,
-                    uint64_t capacity, uint64_t* len)
+// d_tracks: (n, nv, 2) on the device, ordered on the compute stream.  The four kernels, then the writer
+int draw_and_write(Ctx* c, const Picture& Q, const float* d_tracks, int n, int nv, uint8_t* rgb, int rgb_stride, uint8_t* file,
+                   uint64_t capacity, uint64_t* len)
 {
     Ctx::Plot& P = c->plot;
     const hipStream_t st = c->stream;
     Slot& s = c->slots[Q.slot];
-    const size_t px = pad4((size_t)Q.Wo * Q.Ho);
-    uint32_t *lines = P.d_counts, *dots = P.d_counts + px;
+    const int Wo = Q.file.Wo, Ho = Q.file.Ho;
+    uint32_t *lines = P.d_counts, *dots = P.d_counts + Q.file.px;
     if (int rc = wait_slot(c, Q.slot)) return rc;
     {
         ProfScope p(c, K_PLOT_BACKGROUND);
-        launch_plot_background(st, s.lv[0], Q.Wo, Q.Ho, P.d_bg);
+        launch_plot_background(st, s.lv[0], Wo, Ho, P.d_bg);
     }
     if (int rc = check_launch(c, "plot_background")) return rc;
     HIPCHK(c, hipEventRecord(s.used_own, st));   // an upload into the slot waits for this reader
     s.used = s.used_own;
     {
         ProfScope p(c, K_PLOT_CLEAR);
-        launch_plot_clear(st, P.d_counts, 2 * px);
+        launch_picture_clear(st, P.d_counts, 2 * Q.file.px);
     }
     if (int rc = check_launch(c, "plot_clear")) return rc;
     {
         ProfScope p(c, K_PLOT_SCATTER);
-        launch_plot_scatter(st, d_tracks, n, nv, s.w, s.h, Q.Wo, Q.Ho, lines, dots);
+        launch_plot_scatter(st, d_tracks, n, nv, s.w, s.h, Wo, Ho, lines, dots);
     }
     if (int rc = check_launch(c, "plot_scatter")) return rc;
     {
         ProfScope p(c, K_PLOT_RESOLVE);
-        launch_plot_resolve(st, P.d_bg, lines, dots, P.d_tables, Q.stamp, Q.Wo, Q.Ho, P.rs.d_rgb);
+        launch_plot_resolve(st, P.d_bg, lines, dots, P.d_tables, Q.stamp, Wo, Ho, c->picture.d_rgb);
     }
     if (int rc = check_launch(c, "plot_resolve")) return rc;
-    if (int rc = jpeg_fwd_on(c, st, P.rs.d_rgb, P.rs.d_rcoef, Q.Wo, Q.Ho, Q.info)) return rc;
-    if (int rc = jpeg_encode_on(c, P.rs.enc, st, Q.L, P.rs.d_rcoef)) return rc;   // synchronises
-    if (rgb)
-        HIPCHK(c, hipMemcpy2DAsync(rgb, rgb_stride, P.rs.d_rgb, 3 * (size_t)Q.Wo, 3 * (size_t)Q.Wo, Q.Ho, hipMemcpyDeviceToHost, st));
-    return jpeg_deliver_file(c, P.rs.enc, st, rgb != nullptr, Q.info, nullptr, 0, file, capacity, len);
+    return picture_write(c, st, Q.file, rgb, rgb_stride, file, capacity, len);
 }
 
 }  // namespace
@@ -236,14 +216,14 @@ int icelk_plot_tracks(icelk_t* h, int slot, const float* tracks, int n, int vert
     Picture Q;
     if (int rc = check_device_call(c, slot, out_width, stamp, quality, rgb_or_null, rgb_stride, len, &Q)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = grow_picture(c, Q)) return rc;
+    if (int rc = grow_planes(c, Q)) return rc;
     Ctx::Plot& P = c->plot;
     if (n > 0) {
         const size_t floats = (size_t)n * vertices * 2;
         if (int rc = grow(c, &P.d_tracks, &P.tracks_cap, floats)) return rc;
         HIPCHK(c, hipMemcpyAsync(P.d_tracks, tracks, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
     }
-    return draw_and_encode(c, Q, P.d_tracks, n, n > 0 ? vertices : 1, rgb_or_null, rgb_stride, file, capacity, len);
+    return draw_and_write(c, Q, P.d_tracks, n, n > 0 ? vertices : 1, rgb_or_null, rgb_stride, file, capacity, len);
 }
 
 int icelk_seg_plot(icelk_t* h, int slot, int closed, int out_width, const char* stamp, int quality, uint8_t* rgb_or_null, int rgb_stride,
@@ -258,8 +238,8 @@ int icelk_seg_plot(icelk_t* h, int slot, int closed, int out_width, const char* 
     int n = 0, nv = 0;
     if (int rc = seg_gather_packed(c, closed != 0, &n, &nv)) return rc;
     if (out_n) *out_n = n;
-    if (int rc = grow_picture(c, Q)) return rc;
-    return draw_and_encode(c, Q, c->d_out_tracks, n, n > 0 ? nv : 1, rgb_or_null, rgb_stride, file, capacity, len);
+    if (int rc = grow_planes(c, Q)) return rc;
+    return draw_and_write(c, Q, c->d_out_tracks, n, n > 0 ? nv : 1, rgb_or_null, rgb_stride, file, capacity, len);
 }
 
 }  // extern "C"

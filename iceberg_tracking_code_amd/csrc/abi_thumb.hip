@@ -23,7 +23,7 @@
 //       stores     the byte(s) of pair (i, c) at dst + j pitch + 3 i + c, i <= i_last <= tw - 1, c < 3, j < th,
 //                  pitch >= 3 tw: inside the th pitch bytes of dst
 //   k_map_inset    threads t < bw bh over the rectangle inset_box clips to [0, Wo) x [0, Ho): three byte stores at
-//                  rgb + 3 (py Wo + px) < 3 Wo Ho, the size grow_picture gives M.rs.d_rgb.  Loads: the thumbnail at
+//                  rgb + 3 (py Wo + px) < 3 Wo Ho, the size picture_grow gives c->picture.d_rgb.  Loads: the thumbnail at
 //                  (dy, dx), 0 <= dx < w, 0 <= dy < h, of an allocation of h 3 w bytes; the label's glyph indices g[cell],
 //                  cell < n <= 48, in the kernel's own argument
 #include "icelk_ctx.h"

@@ -113,7 +113,7 @@ struct Ctx {
         size_t file_cap = 0, seg_cap = 0, lane_cap = 0, group_cap = 0, dc_cap = 0;
     };
     // The re-save's part (jpeg_resave_free, abi_jpeg_enc.hip): what the forward kernel reads and writes, and the coder
-    // behind it.  A crop job, a slot-bound re-save job, the segment picture and the velocity map have one each
+    // behind it.  A crop job and a slot-bound re-save job have one each, the picture writer has one for every picture
     struct JpegResave {
         uint8_t* d_rgb = nullptr;        // the R G B image, rows 3 * width bytes apart
         int16_t* d_rcoef = nullptr;      // the re-save's coefficients (described by rinfo)
@@ -186,11 +186,16 @@ struct Ctx {
         hipStream_t fetch = nullptr;                           // D2H copies of finished scans (abi_jpeg_job.hip: jpeg_fetch_scan)
     } jpeg;
 
-    // ---- abi_plot.hip: the segment picture, allocated at first use.  A working set that belongs to plotting alone: the
-    // re-save's and the crop jobs' buffers are never touched, so crops and pictures can be asked for together.
-    // rs.d_rgb is what k_plot_resolve writes and the forward kernel reads
+    // ---- abi_picture.hip: the picture writer's working set, allocated at first use: d_rgb is what k_plot_resolve and
+    // k_map_resolve (and k_map_inset) write and the forward kernel or the PNG coder reads.  It belongs to pictures alone
+    // -- the re-save's and the crop jobs' buffers are never touched, so crops and pictures can be asked for together --
+    // and ONE set serves the segment picture and the velocity map.  That is safe because every picture call runs on the
+    // handle's compute stream and has waited for the device when it returns: no two are ever in flight.  An asynchronous
+    // picture call would break it: the next call would draw over, or grow() would free, what the first still reads
+    JpegResave picture;
+
+    // ---- abi_plot.hip: the segment picture's own buffers, allocated at first use
     struct Plot {
-        JpegResave rs;
         uint8_t* d_bg = nullptr;        // Wo x Ho gray plane, padded to four pixels
         uint32_t* d_counts = nullptr;   // lines | dots, each padded to four pixels
         uint32_t* d_tables = nullptr;   // TL | TD
@@ -198,11 +203,9 @@ struct Ctx {
         size_t bg_cap = 0, counts_cap = 0, tracks_cap = 0;
     } plot;
 
-    // ---- abi_map.hip: the velocity map, allocated at first use.  A working set of its own, as the segment picture's:
-    // rs.d_rgb is what k_map_resolve writes and the forward kernel reads.  The day's arrows
+    // ---- abi_map.hip: the velocity map's own buffers, allocated at first use.  The day's arrows
     // of icelk_map_arrows_set and the inset thumbnails of icelk_map_inset_set_* stay resident until release / destroy
     struct Map {
-        JpegResave rs;
         uint32_t* d_planes = nullptr;   // base | top | count, each padded to four pixels
         double* d_items = nullptr;      // per call: cells, outline and the caller's arrows of every panel
         uint8_t* d_measured = nullptr;
@@ -219,7 +222,7 @@ struct Ctx {
     } map;
 
     // ---- abi_png.hip: the PNG writer, allocated at first use and grown to what a picture takes.  A working set of its own:
-    // the map's PNG (icelk_map_draw_png) reads the map's R G B and writes here, icelk_png_encode_rgb uploads into d_src
+    // a picture's PNG (picture_write) reads the writer's R G B and writes here, icelk_png_encode_rgb uploads into d_src
     struct Png {
         uint8_t* d_src = nullptr;       // the caller's picture (icelk_png_encode_rgb only), rows 3 * width bytes apart
         uint8_t* d_F = nullptr;         // the filtered stream, whole segments
@@ -645,6 +648,21 @@ int png_check(Ctx* c, int w, int h);
 int png_grow(Ctx* c, int w, int h);
 int png_encode_on(Ctx* c, hipStream_t st, const uint8_t* d_rgb, uint32_t stride, int w, int h, uint32_t* nbytes);
 int png_deliver_file(Ctx* c, hipStream_t st, bool pending, int w, int h, uint32_t nbytes, uint8_t* out, uint64_t capacity, uint64_t* len);
+// abi_picture.hip: the picture writer (its steps are listed at the head of that file)
+enum PictureFormat { PICTURE_JPEG, PICTURE_PNG };
+struct PictureFile {          // the file to write: what picture_check makes of the caller's arguments
+    PictureFormat format;
+    int Wo, Ho;
+    size_t px;                // Wo Ho padded to four pixels: what every plane of a picture is sized to
+    icelk_jpeg_info_t info;   // JPEG: of the file
+    enc::Layout L;
+};
+void picture_destroy(Ctx* c);
+int picture_check(Ctx* c, int Wo, int Ho, PictureFormat format, int quality, const uint8_t* rgb, int rgb_stride, const uint64_t* len,
+                  PictureFile* F);
+int picture_grow(Ctx* c, const PictureFile& F);
+int picture_write(Ctx* c, hipStream_t st, const PictureFile& F, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
+                  uint64_t* len);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

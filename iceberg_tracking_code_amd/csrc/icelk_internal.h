@@ -274,14 +274,13 @@ __device__ __forceinline__ void jpeg_huff_verdict_words(const uint32_t* __restri
 // two count planes (words) are padded to a multiple of four pixels; counts = lines | dots, `words` in all; tables = TL | TD,
 // plot::kTable words each; rgb: rows 3 Wo bytes apart.  tracks: (n, nv, 2) float32.
 void launch_plot_background(hipStream_t s, const Level& src, int Wo, int Ho, uint8_t* bg);
-void launch_plot_clear(hipStream_t s, uint32_t* counts, size_t words);
+void launch_picture_clear(hipStream_t s, uint32_t* planes, size_t words);   // the map's three planes as well
 void launch_plot_scatter(hipStream_t s, const float* tracks, int n, int nv, int W, int H, int Wo, int Ho, uint32_t* lines, uint32_t* dots);
 void launch_plot_resolve(hipStream_t s, const uint8_t* bg, const uint32_t* lines, const uint32_t* dots, const uint32_t* tables,
                          const plot::Stamp& stamp, int Wo, int Ho, uint8_t* rgb);
 
 // k_map.hip: the velocity map.  planes: base | top | count, each padded to four pixels; cells (n, 3), xy (n, 2), arrows
 // (n, 5) float64 on the device; group: NULL or one int32 per arrow; d_scene: a map::Scene in device memory
-void launch_map_clear(hipStream_t s, uint32_t* planes, size_t words);
 void launch_map_cells(hipStream_t s, const map::View& V, const double* cells, const uint8_t* measured, int n, int Wo, uint32_t* base);
 void launch_map_polyline(hipStream_t s, const map::View& V, const double* xy, int n, int Wo, uint32_t* base);
 void launch_map_arrows(hipStream_t s, const map::View& V, int w, bool pivot_mid, const double* arrows, const int32_t* group, int want, int n,

@@ -1,7 +1,6 @@
 // k_map.hip -- the velocity map of a gridded window on the device: the arithmetic is map_raster.h, which the host statement
 // (icelk_map_overlay_host) runs as well.
 //
-//   k_map_clear      zeroes the three planes (base | top | count)
 //   k_map_cells      one thread per cell: the interior of an unmeasured cell row by row over its rectangle clipped to the
 //                    view, the four sides through walk_pair; atomicMax of the code into `base`
 //   k_map_polyline   one thread per pair of consecutive outline vertices, atomicMax of code 3 into `base`
@@ -10,21 +9,17 @@
 //                    once: one resident upload of a day's vectors serves every window's picture.  The work of a thread is
 //                    bounded by 7 max(vw, vh) + 97^2 hits whatever the arrow's numbers
 //   k_map_resolve    planes + scene (views, cameras, tables, texts, colour table) -> interleaved R G B, rows 3 Wo bytes
-//                    apart (what the re-save's forward kernel reads); a thread makes four pixels and stores three dwords.
-//                    The arrow's speed is gathered through `top`
+//                    apart (what the picture writer reads); a thread makes four pixels and stores three dwords
+//                    (picture_raster.h).  The arrow's speed is gathered through `top`
+// The three planes (base | top | count) are zeroed by k_picture_clear (k_plot.hip).
 // Every atomic goes to plane[(y0 + q) Wo + x0 + p] with 0 <= p < vw, 0 <= q < vh -- map_raster.h hands out no other
 // pixel -- and the view lies inside the Wo x Ho picture (abi_map.hip checks it before anything is enqueued).
 #include "icelk_internal.h"
+#include "picture_raster.h"
 
 namespace icelk {
 
 namespace {
-
-__global__ __launch_bounds__(256) void k_map_clear(uint4* __restrict__ planes, size_t n16)
-{
-    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n16) planes[k] = make_uint4(0, 0, 0, 0);
-}
 
 struct BaseHit {
     uint32_t* base;
@@ -83,31 +78,10 @@ __global__ __launch_bounds__(256) void k_map_resolve(const map::Scene* __restric
     const uint4 b4 = *reinterpret_cast<const uint4*>(base + p0), t4 = *reinterpret_cast<const uint4*>(top + p0),
                 c4 = *reinterpret_cast<const uint4*>(count + p0);
     const uint32_t b[4] = {b4.x, b4.y, b4.z, b4.w}, t[4] = {t4.x, t4.y, t4.z, t4.w}, c[4] = {c4.x, c4.y, c4.z, c4.w};
-    uint8_t out[12] = {0};
-    int py = (int)(p0 / (size_t)Wo), px = (int)(p0 - (size_t)py * Wo);
-    const int live = total - p0 < 4 ? (int)(total - p0) : 4;
-    for (int k = 0; k < live; k++) {
-        map::resolve_pixel(S, b[k], t[k], c[k], px, py, out + 3 * k);
-        if (++px == Wo) px = 0, py++;
-    }
-    uint8_t* dst = rgb + 3 * p0;   // 12-byte steps from an allocation's start: dword aligned
-    if (live == 4) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(dst);
-        for (int k = 0; k < 3; k++)
-            q[k] = (uint32_t)out[4 * k] | (uint32_t)out[4 * k + 1] << 8 | (uint32_t)out[4 * k + 2] << 16 | (uint32_t)out[4 * k + 3] << 24;
-    } else {
-        for (int k = 0; k < 3 * live; k++) dst[k] = out[k];
-    }
+    picture::resolve_quad(p0, total, Wo, rgb, [&](int k, int px, int py, uint8_t* out) { map::resolve_pixel(S, b[k], t[k], c[k], px, py, out); });
 }
 
 }  // namespace
-
-void launch_map_clear(hipStream_t s, uint32_t* planes, size_t words)
-{
-    const size_t n16 = words / 4;
-    if (!n16) return;
-    hipLaunchKernelGGL(k_map_clear, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint4*>(planes), n16);
-}
 
 void launch_map_cells(hipStream_t s, const map::View& V, const double* cells, const uint8_t* measured, int n, int Wo, uint32_t* base)
 {

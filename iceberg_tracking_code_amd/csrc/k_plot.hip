@@ -8,13 +8,14 @@
 //                       once for all the output pixels above it -- into LDS, 1024 columns at a time; then every lane
 //                       adds up, with the horizontal weights, the few column sums of its own pixel.  Exact: the weights
 //                       are integers and the sums are products of sums.
-//   k_plot_clear        zeroes the two count planes
+//   k_picture_clear     zeroes the two count planes (and the three planes of the velocity map: abi_map.hip)
 //   k_plot_scatter      one thread per pair of consecutive vertices and one per track for the dot; the walk is bounded
 //                       by max(Wo, Ho) steps whatever the coordinates, hits are counted with integer atomics, so the
 //                       result does not depend on the order of arrival
 //   k_plot_resolve      counts + background + tables + stamp -> interleaved R G B, rows 3 Wo bytes apart (what the
-//                       re-save's forward kernel reads); a thread makes four pixels and stores three dwords
+//                       picture writer reads); a thread makes four pixels and stores three dwords (picture_raster.h)
 #include "icelk_internal.h"
+#include "picture_raster.h"
 
 namespace icelk {
 
@@ -62,10 +63,10 @@ __global__ __launch_bounds__(kBgThreads) void k_plot_background(Level src, int W
     if (i < Wo) bg[(size_t)j * Wo + i] = (uint8_t)plot::average(acc, W, H);
 }
 
-__global__ __launch_bounds__(256) void k_plot_clear(uint4* __restrict__ counts, size_t n16)
+__global__ __launch_bounds__(256) void k_picture_clear(uint4* __restrict__ planes, size_t n16)
 {
     const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n16) counts[k] = make_uint4(0, 0, 0, 0);
+    if (k < n16) planes[k] = make_uint4(0, 0, 0, 0);
 }
 
 struct CountHit {
@@ -114,21 +115,9 @@ __global__ __launch_bounds__(256) void k_plot_resolve(const uint8_t* __restrict_
     const uint32_t g4 = *reinterpret_cast<const uint32_t*>(bg + p0);
     const uint4 l4 = *reinterpret_cast<const uint4*>(lines + p0), d4 = *reinterpret_cast<const uint4*>(dots + p0);
     const uint32_t l[4] = {l4.x, l4.y, l4.z, l4.w}, d[4] = {d4.x, d4.y, d4.z, d4.w};
-    uint8_t out[12] = {0};
-    int py = (int)(p0 / (size_t)Wo), px = (int)(p0 - (size_t)py * Wo);
-    const int live = total - p0 < 4 ? (int)(total - p0) : 4;
-    for (int k = 0; k < live; k++) {
-        plot::resolve_pixel((int)((g4 >> (8 * k)) & 255u), l[k], d[k], T.TL, T.TD, stamp, px, py, Wo, Ho, out + 3 * k);
-        if (++px == Wo) px = 0, py++;
-    }
-    uint8_t* dst = rgb + 3 * p0;   // 12-byte steps from an allocation's start: dword aligned
-    if (live == 4) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(dst);
-        for (int k = 0; k < 3; k++)
-            q[k] = (uint32_t)out[4 * k] | (uint32_t)out[4 * k + 1] << 8 | (uint32_t)out[4 * k + 2] << 16 | (uint32_t)out[4 * k + 3] << 24;
-    } else {
-        for (int k = 0; k < 3 * live; k++) dst[k] = out[k];
-    }
+    picture::resolve_quad(p0, total, Wo, rgb, [&](int k, int px, int py, uint8_t* out) {
+        plot::resolve_pixel((int)((g4 >> (8 * k)) & 255u), l[k], d[k], T.TL, T.TD, stamp, px, py, Wo, Ho, out);
+    });
 }
 
 }  // namespace
@@ -138,11 +127,12 @@ void launch_plot_background(hipStream_t s, const Level& src, int Wo, int Ho, uin
     hipLaunchKernelGGL(k_plot_background, dim3((Wo + kBgThreads - 1) / kBgThreads, Ho), dim3(kBgThreads), 0, s, src, Wo, Ho, bg);
 }
 
-void launch_plot_clear(hipStream_t s, uint32_t* counts, size_t words)
+// words: a multiple of four, from an allocation's start
+void launch_picture_clear(hipStream_t s, uint32_t* planes, size_t words)
 {
     const size_t n16 = words / 4;
     if (!n16) return;
-    hipLaunchKernelGGL(k_plot_clear, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint4*>(counts), n16);
+    hipLaunchKernelGGL(k_picture_clear, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint4*>(planes), n16);
 }
 
 void launch_plot_scatter(hipStream_t s, const float* tracks, int n, int nv, int W, int H, int Wo, int Ho, uint32_t* lines, uint32_t* dots)

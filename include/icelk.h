@@ -686,8 +686,8 @@ int icelk_plot_overlay_host(const uint8_t* gray, int w, int h_, int stride, cons
                             const char* stamp, uint8_t* rgb, int rgb_stride);
 /* The picture of the frame `slot` holds (ICELK_ESTATE when it holds none) with the tracks at `tracks` (host), as a file.
  * Four kernels (csrc/k_plot.hip), the re-save's forward kernel and the entropy coder run on the handle's compute stream,
- * on a working set that belongs to plotting alone -- the "most recent re-save" of icelk_jpeg_resave_encode and the crop
- * jobs are untouched; it is allocated at first use (at 1200 x 800: 1 MB gray, 7.7 MB counts, 2.9 MB R G B, 2.9 MB
+ * on a working set that belongs to pictures alone (the velocity map's calls share its R G B, coefficients and coder) --
+ * the "most recent re-save" of icelk_jpeg_resave_encode and the crop jobs are untouched; it is allocated at first use (at 1200 x 800: 1 MB gray, 7.7 MB counts, 2.9 MB R G B, 2.9 MB
  * coefficients and the coder's buffers) and freed with the handle.  The call waits for the device.  Arguments are checked
  * before anything is enqueued; after an error nothing has been written.  ICELK_ECAP: `file` is too small (or NULL), *len
  * says what the file takes and the call can be repeated.  rgb_or_null: receives the R G B the writer was given (tests). */
@@ -765,10 +765,11 @@ int icelk_map_overlay_host(const icelk_map_desc_t* d, const double* resident, co
  * the next set, icelk_map_arrows_release or icelk_destroy: every picture of the day draws from the one upload.  n <= 2^27. */
 int icelk_map_arrows_set(icelk_t* h, const double* arrows, const int32_t* group_or_null, int n);
 int icelk_map_arrows_release(icelk_t* h);
-/* The picture d describes, as a file.  k_map_clear, k_map_cells, k_map_polyline, k_map_arrows and k_map_resolve
+/* The picture d describes, as a file.  k_picture_clear, k_map_cells, k_map_polyline, k_map_arrows and k_map_resolve
  * (csrc/k_map.hip), then the re-save's forward kernel and the entropy coder run on the handle's compute stream, on a
- * working set that belongs to the map alone -- the segment picture, the "most recent re-save" of icelk_jpeg_resave_encode
- * and the crop jobs are untouched; it is allocated at first use (at 1400 x 1000: 16.8 MB planes, 4.2 MB R G B, 4.2 MB
+ * working set that belongs to pictures alone (planes of the map's own; R G B, coefficients and coder shared with the
+ * segment picture's calls) -- the "most recent re-save" of icelk_jpeg_resave_encode and the crop jobs are untouched; it
+ * is allocated at first use (at 1400 x 1000: 16.8 MB planes, 4.2 MB R G B, 4.2 MB
  * coefficients, the call's items and the coder's buffers) and freed with the handle.  The call waits for the device.
  * Every argument is checked before anything is enqueued or allocated; after an error nothing has been written.
  * ICELK_ESTATE: a panel asks for resident arrows and none are set.  ICELK_ECAP: `file` is too small (or NULL), *len says
