@@ -8,17 +8,18 @@ namespace icelk {
 int alloc_eig_out(Ctx* c, Ctx::EigOut& e, int cand_cap)
 {
     const int w = c->max_w, h = c->max_h;
+    CandBuf& b = e.buf;
     int rc;
-    if ((rc = dmalloc(c, &e.max_key, 1)) || (rc = dmalloc(c, &e.raw, (size_t)cand_cap)) ||
-        (rc = dmalloc(c, &e.blk_count, candidate_blocks(w, h) * 4)))
+    if ((rc = dmalloc(c, &b.max_key, 1)) || (rc = dmalloc(c, &b.raw, (size_t)cand_cap)) ||
+        (rc = dmalloc(c, &b.blk_count, candidate_blocks(w, h) * 4)))
         return rc;
     // the two-pass detector's scratch (~20 MB per buffer at 12 MP) only on a handle created with its switch set: a
-    // handle without it runs the strip kernel whatever the switch says later (launch_candidates looks at D.acand)
+    // handle without it runs the strip kernel whatever the switch says later (launch_candidates looks at D.cb.acand)
     if (getenv("ICELK_TWO_PASS_CORNERS") &&
-        ((rc = dmalloc(c, &e.acand, fast_cand_entries(w, h))) || (rc = dmalloc(c, &e.acount, fast_tiles(w, h))) ||
-         (rc = dmalloc(c, &e.amaxc, fast_max_entries(w, h))) || (rc = dmalloc(c, &e.amaxn, fast_tiles(w, h))) ||
-         (rc = dmalloc(c, &e.aemax, fast_tiles(w, h))) || (rc = dmalloc(c, &e.fmax_key, 8)) ||
-         (rc = dmalloc(c, &e.aties, fast_cand_entries(w, h) + fast_tiles(w, h)))))
+        ((rc = dmalloc(c, &b.acand, fast_cand_entries(w, h))) || (rc = dmalloc(c, &b.acount, fast_tiles(w, h))) ||
+         (rc = dmalloc(c, &b.amaxc, fast_max_entries(w, h))) || (rc = dmalloc(c, &b.amaxn, fast_tiles(w, h))) ||
+         (rc = dmalloc(c, &b.aemax, fast_tiles(w, h))) || (rc = dmalloc(c, &b.fmax_key, 8)) ||
+         (rc = dmalloc(c, &b.aties, fast_cand_entries(w, h) + fast_tiles(w, h)))))
         return rc;
     if (hipEventCreateWithFlags(&e.done, hipEventDisableTiming) != hipSuccess) FAIL(c, ICELK_EHIP, "hipEventCreate failed");
     return ICELK_OK;
@@ -26,7 +27,8 @@ int alloc_eig_out(Ctx* c, Ctx::EigOut& e, int cand_cap)
 
 void free_eig_out(Ctx::EigOut& e)
 {
-    void* p[] = {e.raw, e.blk_count, e.max_key, e.acand, e.acount, e.amaxc, e.amaxn, e.aemax, e.fmax_key, e.aties};
+    const CandBuf& b = e.buf;
+    void* p[] = {b.raw, b.blk_count, b.max_key, b.acand, b.acount, b.amaxc, b.amaxn, b.aemax, b.fmax_key, b.aties};
     for (void* q : p)
         if (q) hipFree(q);
     if (e.done) hipEventDestroy(e.done);
@@ -53,11 +55,11 @@ int alloc_det_set(Ctx* c, Ctx::DetSet& S, int cand_cap)
         hipMemset(D.tail_ctl, 0, sizeof(int) * TC_WORDS_) != hipSuccess ||
         hipMemset(D.tail_bins, 0, sizeof(int) * (kTailOrderBins + 2)) != hipSuccess)
         FAIL(c, ICELK_EHIP, "hipMemset failed");
-    if (hipHostMalloc(reinterpret_cast<void**>(&S.h_counts), 64, hipHostMallocMapped) != hipSuccess ||
+    if (hipHostMalloc(reinterpret_cast<void**>(&S.h_counts), sizeof(int) * CW_WORDS_, hipHostMallocMapped) != hipSuccess ||
         hipEventCreateWithFlags(&S.counts_ev, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&S.tail_done, hipEventDisableTiming) != hipSuccess)
         FAIL(c, ICELK_EHIP, "hipHostMalloc failed");
-    memset(S.h_counts, 0, 64);
+    memset(S.h_counts, 0, sizeof(int) * CW_WORDS_);
     return ICELK_OK;
 }
 
@@ -75,21 +77,18 @@ void free_det_set(Ctx::DetSet& S)
 
 // ---- detector core shared by icelk_good_features and icelk_seg_detect --------------------------
 // detect_begin enqueues K6..K8 on the detection stream and returns at once; detect_finish waits for the
-// counts, sorts the accepted corners and leaves the first *n_out of them in c->d_corners (device), in
-// response order.
-constexpr int kCountsSeq = 8;   // word of the pinned counts that carries the sequence number of the publication
+// counts, sorts the accepted corners and leaves the first of them in c->d_corners (device), in response order.
 __global__ void k_publish_counts(const int* __restrict__ cand, const int* __restrict__ acc,
                                  const int* __restrict__ undecided, const unsigned* __restrict__ prune_key,
                                  int* __restrict__ host_out, int seq)
 {
-    host_out[0] = *cand;
-    host_out[1] = *acc;
-    host_out[2] = *undecided;
-    host_out[3] = (int)(*prune_key != 0u);
+    host_out[CW_CAND] = *cand;
+    host_out[CW_ACC] = *acc;
+    host_out[CW_UNDECIDED] = *undecided;
+    host_out[CW_PRUNED] = (int)(*prune_key != 0u);
     __threadfence_system();
-    // the host polls this word (fetch_counts): it learns of the counts when they land in its memory, not when the
-    // runtime has processed the completion signal of an event behind this kernel and woken the waiting thread
-    __hip_atomic_store(host_out + kCountsSeq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    // the word the host polls (await_pinned_seq)
+    __hip_atomic_store(host_out + CW_SEQ, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // the set of the oldest detection in flight, or -1
@@ -110,27 +109,16 @@ static int det_free(const Ctx* c)
 }
 
 // what a candidate buffer must hold to serve a detection of `slot` as it is now
-static Ctx::EigOut eo_want(const Ctx* c, int slot, int use_mask, int block_size)
+static Ctx::CandKey eo_want(const Ctx* c, int slot, int use_mask, int block_size)
 {
-    Ctx::EigOut want;
-    want.slot = slot;
-    want.gen = c->slots[slot].gen;
-    want.block_size = block_size;
-    want.use_mask = use_mask;
-    want.mask_gen = c->mask_gen;
-    return want;
+    return {slot, block_size, use_mask, c->slots[slot].gen, c->mask_gen};
 }
 
-// does e hold the prepared candidates `want` asks for (slot, frame generation, blockSize, mask, mask generation)?
-static bool eo_holds(const Ctx::EigOut& e, const Ctx::EigOut& want)
-{
-    return e.valid && e.slot == want.slot && e.gen == want.gen && e.block_size == want.block_size &&
-           e.use_mask == want.use_mask && e.mask_gen == want.mask_gen;
-}
+static bool eo_holds(const Ctx::EigOut& e, const Ctx::CandKey& want) { return e.valid && e.key == want; }
 
 // a candidate buffer no detection in flight reads: the one that holds what `want` asks for if there is one, else one
 // without valid content, else any
-static int eo_free(const Ctx* c, const Ctx::EigOut& want)
+static int eo_free(const Ctx* c, const Ctx::CandKey& want)
 {
     bool busy[3] = {false, false, false};
     for (const auto& S : c->dset)
@@ -145,67 +133,45 @@ static int eo_free(const Ctx* c, const Ctx::EigOut& want)
     return pick;
 }
 
-// point a detector scratch at candidate buffer e: the stages read (and the non-prepared corner kernel writes) e
-static void point_at_eig_out(DetectScratch& D, const Ctx::EigOut& e)
-{
-    D.raw = e.raw;
-    D.blk_count = e.blk_count;
-    D.max_key = e.max_key;
-    D.acand = e.acand;
-    D.acount = e.acount;
-    D.amaxc = e.amaxc;
-    D.amaxn = e.amaxn;
-    D.aemax = e.aemax;
-    D.fmax_key = e.fmax_key;
-    D.aties = e.aties;
-    D.src_nblk = e.nblk;
-    D.src_region = e.region;
-}
-
-// make eo[idx] the candidate buffer of set S
+// make eo[idx] the candidate buffer of set S: the stages read (and the non-prepared corner kernel writes) it
 void activate_eig_out(Ctx* c, Ctx::DetSet& S, int idx)
 {
     S.eo_active = idx;
-    point_at_eig_out(S.D, c->eo[idx]);
+    S.D.cb = c->eo[idx].buf;
 }
+
+// Does the strip kernel produce this handle's candidates at block_size (else: the any-blockSize kernels, which serve no
+// prepare launch and no fused map)?  The switch is read at every call: it is set and cleared on a live handle.
+static bool strip_kernel_serves(const Ctx* c, int block_size)
+{
+    return fused_block_size(block_size) && !getenv("ICELK_GENERIC_CORNERS") && !c->corner_variant;
+}
+
+static int next_counts_seq(Ctx::DetSet& S) { return S.counts_seq = (S.counts_seq + 1) & 0x3fffffff; }
 
 // The counts of set S's detection go to its pinned host words behind whatever is queued on the detection stream, and
 // an event of the set marks them.  detect_begin ends with this, so the host round trip of that detection waits for
 // ITS kernels only -- not for the min-distance stage of the next detection that may be queued behind them.
 static int publish_counts(Ctx* c, Ctx::DetSet& S)
 {
-    S.counts_seq = (S.counts_seq + 1) & 0x3fffffff;
     hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(1), 0, c->det_stream, S.job.cand_count_ptr, S.D.acc_count,
-                       S.D.undecided + suppress_launch_count() - 1, S.D.prune_key, S.h_counts, S.counts_seq);
+                       S.D.undecided + suppress_launch_count() - 1, S.D.prune_key, S.h_counts, next_counts_seq(S));
     HIPCHK(c, hipEventRecord(S.counts_ev, c->det_stream));
     return ICELK_OK;
 }
 
-// have the counts published last arrived?  (the sequence word, no runtime call)
-static inline bool counts_here(const int* h_counts, int seq)
-{
-    return __atomic_load_n(h_counts + kCountsSeq, __ATOMIC_ACQUIRE) == seq;
-}
+// the pinned counts (CountsWord) once their sequence word has been seen; n_out and status: of a device-driven tail only
+struct Counts {
+    int candidates, accepted, undecided, pruned, n_out, status;
+};
 
-// Waits for the counts by polling the pinned sequence word; the event is looked at now and then, so that a failed
-// kernel ends the wait with its error instead of hanging it.
-static int fetch_counts(Ctx* c, Ctx::DetSet& S, bool published = false)
+// the host round trip of a detection: publishes the counts unless the job's last launch did, and waits for them
+static int fetch_counts(Ctx* c, Ctx::DetSet& S, Counts* n, bool published = false)
 {
-    if (!published) {
-        int rc = publish_counts(c, S);
-        if (rc) return rc;
-    }
-    for (unsigned it = 1;; it++) {
-        if (counts_here(S.h_counts, S.counts_seq)) return ICELK_OK;
-        if ((it & 4095u) == 0) {
-            const hipError_t q = hipEventQuery(S.counts_ev);
-            if (q == hipSuccess) break;             // complete: the synchronize below returns at once
-            if (q != hipErrorNotReady) HIPCHK(c, q);
-            (void)hipGetLastError();
-        }
-        __builtin_ia32_pause();
-    }
-    HIPCHK(c, hipEventSynchronize(S.counts_ev));
+    int rc = published ? ICELK_OK : publish_counts(c, S);
+    if (rc || (rc = await_pinned_seq(c, S.h_counts + CW_SEQ, S.counts_seq, S.counts_ev))) return rc;
+    const int* w = S.h_counts;
+    *n = {w[CW_CAND], w[CW_ACC], w[CW_UNDECIDED], w[CW_PRUNED], w[CW_NOUT], w[CW_STATUS]};
     return ICELK_OK;
 }
 
@@ -220,7 +186,7 @@ static int pick_mask(Ctx* c, int use_mask, int w, int h, const uint8_t** mask)
     return ICELK_OK;
 }
 
-// Corner candidates of a frame ahead of its detection (fused kernel only; anything else is left to
+// Corner candidates of a frame ahead of its detection (strip kernel only; anything else is left to
 // detect_begin).  Runs on eig_stream into the spare buffer; detect_begin adopts it when slot, frame
 // generation, blockSize and mask still match.
 int detect_prepare(Ctx* c, int slot, int use_mask, int block_size)
@@ -228,19 +194,19 @@ int detect_prepare(Ctx* c, int slot, int use_mask, int block_size)
     Range rg("icelk detect_prepare (corner candidates ahead)");
     int rc = check_slot(c, slot, true);
     if (rc) return rc;
-    if (!fused_block_size(block_size) || getenv("ICELK_GENERIC_CORNERS") || c->corner_variant) return ICELK_OK;
+    if (!strip_kernel_serves(c, block_size)) return ICELK_OK;
     Slot& s = c->slots[slot];
     const uint8_t* mask = nullptr;
     if ((rc = pick_mask(c, use_mask, s.w, s.h, &mask))) return rc;
-    const Ctx::EigOut want = eo_want(c, slot, use_mask, block_size);
+    const Ctx::CandKey want = eo_want(c, slot, use_mask, block_size);
     Ctx::EigOut& e = c->eo[eo_free(c, want)];
     if (eo_holds(e, want)) return ICELK_OK;   // already there
     const hipStream_t es = c->eig_stream;
     // level 0 only: `ready` would also wait for a pyramid built ahead, which the detector never reads
     if (int rcw = wait_event(c, es, s.frame_ev)) return rcw;
-    HIPCHK(c, hipMemsetAsync(e.max_key, 0, sizeof(unsigned), es));
+    HIPCHK(c, hipMemsetAsync(e.buf.max_key, 0, sizeof(unsigned), es));
     DetectScratch T{};   // the corner kernel touches the candidate buffer only
-    point_at_eig_out(T, e);
+    T.cb = e.buf;
     // the quality level is not known yet: the one of the latest detection begun on this handle is taken (0 at first: every
     // local maximum gets its exact key); detect_begin adopts the result only if its own level is not lower
     const double prep_quality = c->prep_quality;
@@ -248,288 +214,304 @@ int detect_prepare(Ctx* c, int slot, int use_mask, int block_size)
         ProfScope p(c, K_EIG, es);
         launch_candidates(es, T, s.lv[0], block_size, mask, c->mask_pitch, prep_quality, false, nullptr);
     }
-    rc = check_launch(c, "corner candidates (prepared)");
-    if (rc) return rc;
+    if ((rc = check_launch(c, "corner candidates (prepared)"))) return rc;
     HIPCHK(c, hipEventRecord(e.done, es));
     HIPCHK(c, hipEventRecord(s.eig_used, es));
-    e.nblk = T.src_nblk;
-    e.region = T.src_region;
+    e.buf = T.cb;   // with the geometry of the regions written
     e.valid = true;
-    e.slot = slot;
-    e.gen = s.gen;
-    e.block_size = block_size;
-    e.use_mask = use_mask;
-    e.mask_gen = c->mask_gen;
+    e.key = want;
     e.quality = prep_quality;
     return ICELK_OK;
 }
 
-// for_segment: the corners start a segment (icelk_seg_detect_begin) -- the tail of the detection is then enqueued here, behind
-// the min-distance stage, driven by the device-side counts (k_tail.hip), and writes the segment's tables into the set it
-// reserves; otherwise (icelk_good_features) detect_finish runs the tail after the host round trip
+// ---- detect_begin, phase by phase ------------------------------------------------------------------------------------
+// Arguments and capacities: the set the detection takes (*k), the mask it reads, the cells of its min-distance grid
+static int begin_checks(Ctx* c, int slot, int use_mask, double quality, double min_distance, int block_size, int* k,
+                        const uint8_t** mask, size_t* ncell)
+{
+    if (int rc = check_slot(c, slot, true)) return rc;
+    if (!(quality > 0) || min_distance < 0 || block_size <= 0) FAIL(c, ICELK_EARG, "bad detector parameters");
+    if (min_eig_lds_bytes(block_size) > 150 * 1024) FAIL(c, ICELK_EARG, "blockSize too large");
+    *k = det_free(c);
+    if (*k < 0) FAIL(c, ICELK_ESTATE, "two detections are in flight already");
+    c->dset_last = *k;
+    const Slot& s = c->slots[slot];
+    if (int rc = pick_mask(c, use_mask, s.w, s.h, mask)) return rc;
+    if (min_distance >= 1) {
+        const int cell = (int)lrint(min_distance);
+        *ncell = (size_t)((s.w + cell - 1) / cell) * ((s.h + cell - 1) / cell);
+        if (*ncell + 1 > c->ncell_cap) FAIL(c, ICELK_ECAP, "cell grid larger than allocated");
+    }
+    return ICELK_OK;
+}
+
+// The job of a detection begun now.  Top-K pruning (k_corners.hip) is worthwhile when maxCorners is a real cap: only the
+// strongest candidates can be among the first maxCorners accepted ones; how many to keep follows the share that survived
+// the minDistance rule in the detection before (update_prune_factor), and relax_on_host verifies that maxCorners came out
+static DetectJob new_job(const Ctx* c, const Slot& s, int max_corners, double quality, double min_distance, size_t ncell)
+{
+    DetectJob J;
+    J.w = s.w;
+    J.h = s.h;
+    J.quality = quality;
+    J.min_distance = min_distance;
+    J.ncell = ncell;
+    J.max_corners = max_corners;
+    if (min_distance >= 1 && max_corners > 0 && max_corners <= (1 << 24) && !getenv("ICELK_NO_PRUNE"))
+        J.prune_want = (int)std::min(8.0 * max_corners, std::ceil(c->prune_factor * max_corners));
+    return J;
+}
+
+// Claims a candidate buffer no detection in flight reads for set S.  What detect_prepare left there for this very frame
+// is adopted; else the corner kernel fills it here, once a prepare launch that wrote it (for another frame) is through,
+// with its maximum starting from zero.  The frame must be in the slot, and the tail of this set's previous detection (it
+// sorted this set's accepted keys and reset its counters on the tail stream) through.  That reset normally leaves the
+// counters zeroed, off the critical path: they are reset here only the first time or when the cell grid grew.
+static int begin_candidates(Ctx* c, Ctx::DetSet& S, int slot, int use_mask, const uint8_t* mask, int block_size)
+{
+    const DetectJob& J = S.job;
+    Slot& s = c->slots[slot];
+    const hipStream_t ds = c->det_stream;
+    if (int rcw = wait_event(c, ds, s.frame_ev)) return rcw;   // level 0 only (see detect_prepare)
+    if (int rcw = wait_event(c, ds, S.tail_done)) return rcw;
+    const bool strip = strip_kernel_serves(c, block_size);
+    const bool need_reset = !S.counters_clean || J.ncell > S.reset_ncell;
+    const Ctx::CandKey want = eo_want(c, slot, use_mask, block_size);
+    const int spare_idx = eo_free(c, want);
+    Ctx::EigOut& spare = c->eo[spare_idx];
+    const bool prepared = eo_holds(spare, want) && strip && spare.quality <= J.quality;
+    c->prep_quality = J.quality;
+    spare.valid = false;   // adopted, or overwritten: either way it is not offered again
+    S.counters_clean = false;
+    activate_eig_out(c, S, spare_idx);
+    if (int rcw = wait_event(c, ds, spare.done)) return rcw;
+    if (prepared) {
+        if (need_reset) launch_detect_reset(ds, S.D, (int)J.ncell, 1);
+    } else {
+        ProfScope p(c, K_EIG, ds);
+        HIPCHK(c, hipMemsetAsync(spare.buf.max_key, 0, sizeof(unsigned), ds));
+        if (need_reset) launch_detect_reset(ds, S.D, (int)J.ncell, 1);
+        launch_candidates(ds, S.D, s.lv[0], block_size, mask, c->mask_pitch, J.quality, !strip, nullptr, c->corner_variant);
+        HIPCHK(c, hipEventRecord(s.det_used, ds));   // nothing after this launch reads the frame
+    }
+    return check_launch(c, "corner candidates");
+}
+
+// The min-distance stage (with the device-driven tail's gather behind it), or for minDistance < 1 the flat list
+static int begin_min_distance(Ctx* c, Ctx::DetSet& S, bool dev_tail)
+{
+    DetectJob& J = S.job;
+    DetectScratch& D = S.D;
+    const hipStream_t ds = c->det_stream;
+    if (J.min_distance >= 1) {
+        J.cand_count_ptr = D.cell_start + J.ncell;
+        ProfScope p(c, K_SUPPRESS, ds);
+        launch_min_distance(ds, D, J.w, J.h, J.min_distance, J.quality, J.prune_want, dev_tail);
+        const int last = suppress_launch_count() - 1;
+        if (dev_tail) launch_tail_gather(ds, D, (int)J.ncell, J.quality, last, J.max_corners, c->max_pts, c->tail_force_status);
+    } else {
+        J.cand_count_ptr = D.cand_count;
+        launch_flatten(ds, D, J.quality);
+    }
+    return check_launch(c, "min_distance");
+}
+
+// The segment set the detection begun now in dset[k] will start its segment in: behind the current one, the staged one
+// and the one the other detection in flight has reserved (segments are staged and switched to in the order of _begin)
+static int reserve_seg_set(const Ctx* c, int k)
+{
+    return (c->sb_cur + 1 + (c->seg_staged ? 1 : 0) + (c->dset[k ^ 1].job.active ? 1 : 0)) % kSegSets;
+}
+
+// The tail driven by the device-side counts (k_tail.hip), behind the min-distance stage: it writes the segment's tables
+// into the set reserved here, once launches that still touch it (a segment closed several switches ago) are through
+static int begin_device_tail(Ctx* c, Ctx::DetSet& S, int k)
+{
+    DetectJob& J = S.job;
+    const hipStream_t ds = c->det_stream;
+    const int target = reserve_seg_set(c, k);
+    Ctx::SegBuf& nb = c->sb[target];
+    if (int rcw = wait_event(c, ds, nb.used)) return rcw;
+    next_counts_seq(S);
+    {
+        ProfScope p(c, K_EMIT, ds);
+        launch_tail_device(ds, S.D, J.quality, nb.live, nb.alive, nb.tracks, kMaxVert, c->use_order ? nb.order : nullptr,
+                           nb.order_border, tail_order_geometry(J.w, J.h, c->border_px), tail_reset_of(S.D, (int)J.ncell),
+                           S.h_counts, S.counts_seq);
+    }
+    if (int rc = check_launch(c, "tail (device-driven)")) return rc;
+    HIPCHK(c, hipEventRecord(nb.ready, ds));
+    HIPCHK(c, hipEventRecord(S.counts_ev, ds));
+    J.dev_tail = true;
+    J.seg_set = target;
+    return ICELK_OK;
+}
+
+// for_segment: the corners start a segment (icelk_seg_detect_begin) -- the tail of the detection is then enqueued here,
+// driven by the device; otherwise (icelk_good_features) detect_finish runs the tail after the host round trip
 int detect_begin(Ctx* c, int slot, int use_mask, int max_corners, double quality, double min_distance, int block_size,
                  bool for_segment)
 {
     Range rg("icelk detect_begin (candidates + min-distance stage)");
-    int rc = check_slot(c, slot, true);
-    if (rc) return rc;
-    if (!(quality > 0) || min_distance < 0 || block_size <= 0) FAIL(c, ICELK_EARG, "bad detector parameters");
-    if (min_eig_lds_bytes(block_size) > 150 * 1024) FAIL(c, ICELK_EARG, "blockSize too large");
-    const int k = det_free(c);
-    if (k < 0) FAIL(c, ICELK_ESTATE, "two detections are in flight already");
-    c->dset_last = k;
-    Ctx::DetSet& S = c->dset[k];
-    Slot& s = c->slots[slot];
-    const hipStream_t ds = c->det_stream;
-    const int w = s.w, h = s.h;
+    int k = -1;
     const uint8_t* mask = nullptr;
-    if ((rc = pick_mask(c, use_mask, w, h, &mask))) return rc;
-    DetectScratch& D = S.D;
     size_t ncell = 0;
-    if (min_distance >= 1) {
-        const int cell = (int)lrint(min_distance);
-        ncell = (size_t)((w + cell - 1) / cell) * ((h + cell - 1) / cell);
-        if (ncell + 1 > c->ncell_cap) FAIL(c, ICELK_ECAP, "cell grid larger than allocated");
-    }
-    // the frame must be in the slot (ingest on the compute or the copy stream), and the tail of this set's previous detection (it sorted this set's accepted keys and
-    // reset its counters on the tail stream) must be through
-    if (int rcw = wait_event(c, ds, s.frame_ev)) return rcw;   // level 0 only (see detect_prepare)
-    if (int rcw = wait_event(c, ds, S.tail_done)) return rcw;
-    const bool generic = getenv("ICELK_GENERIC_CORNERS") != nullptr || c->corner_variant != 0;
-    // counters are normally left zeroed by the previous detection (the reset runs after its last kernel,
-    // off the critical path); reset here only the first time or when the cell grid grew
-    const bool need_reset = !S.counters_clean || ncell > S.reset_ncell;
-    const Ctx::EigOut want = eo_want(c, slot, use_mask, block_size);
-    const int spare_idx = eo_free(c, want);
-    Ctx::EigOut& spare = c->eo[spare_idx];
-    const bool prepared = eo_holds(spare, want) && !generic && spare.quality <= quality;
-    c->prep_quality = quality;
-    spare.valid = false;   // adopted below, or overwritten: either way it is not offered again
-    if (prepared) {
-        if (need_reset) launch_detect_reset(ds, D, (int)ncell, 1);
-        activate_eig_out(c, S, spare_idx);
-        if (int rcw = wait_event(c, ds, spare.done)) return rcw;
-    } else {
-        ProfScope p(c, K_EIG, ds);
-        // this detection's candidates go into a buffer no detection in flight reads; a prepare launch that wrote it
-        // (for another frame) must be through, and its maximum starts from zero
-        activate_eig_out(c, S, spare_idx);
-        if (int rcw = wait_event(c, ds, spare.done)) return rcw;
-        HIPCHK(c, hipMemsetAsync(spare.max_key, 0, sizeof(unsigned), ds));
-        if (need_reset) launch_detect_reset(ds, D, (int)ncell, 1);
-        launch_candidates(ds, D, s.lv[0], block_size, mask, c->mask_pitch, quality, generic, nullptr, c->corner_variant);
-        HIPCHK(c, hipEventRecord(s.det_used, ds));   // nothing after this launch reads the frame
-    }
-    S.counters_clean = false;
-    rc = check_launch(c, "corner candidates");
+    int rc = begin_checks(c, slot, use_mask, quality, min_distance, block_size, &k, &mask, &ncell);
     if (rc) return rc;
-    DetectJob& J = S.job;
-    J.w = w;
-    J.h = h;
-    J.quality = quality;
-    J.min_distance = min_distance;
-    J.ncell = ncell;
-    // top-K pruning (k_corners.hip): worthwhile when maxCorners is a real cap.  Only the strongest candidates can be among
-    // the first maxCorners accepted ones; how many to keep follows the share that survived the minDistance rule in the
-    // detection before (with half as many again; 8x to begin with and after a shortfall), and detect_finish verifies
-    // that maxCorners corners came out -- else the stage runs once more on all candidates
-    J.prune_want = 0;
-    if (min_distance >= 1 && max_corners > 0 && max_corners <= (1 << 24) && !getenv("ICELK_NO_PRUNE"))
-        J.prune_want = (int)std::min(8.0 * max_corners, std::ceil(c->prune_factor * max_corners));
-    J.dev_tail = false;
-    J.seg_set = -1;
-    J.max_corners = max_corners;
+    Ctx::DetSet& S = c->dset[k];
+    S.job = new_job(c, c->slots[slot], max_corners, quality, min_distance, ncell);
     const bool dev_tail = for_segment && !c->host_tail && min_distance >= 1;
-    if (min_distance >= 1) {
-        J.cand_count_ptr = D.cell_start + ncell;
-        ProfScope p(c, K_SUPPRESS, ds);
-        launch_min_distance(ds, D, w, h, min_distance, quality, J.prune_want, dev_tail);
-        if (dev_tail)
-            launch_tail_gather(ds, D, (int)ncell, quality, suppress_launch_count() - 1, max_corners, c->max_pts, c->tail_force_status);
-    } else {
-        J.cand_count_ptr = D.cand_count;
-        launch_flatten(ds, D, quality);
-    }
-    rc = check_launch(c, "min_distance");
-    if (rc) return rc;
-    if (dev_tail) {
-        // the set the new segment goes into: behind the current one, the staged one and the one the other detection in
-        // flight has reserved (segments are staged and switched to in the order their detections were begun)
-        const Ctx::DetSet& other = c->dset[k ^ 1];
-        const int ahead = (c->seg_staged ? 1 : 0) + (other.job.active ? 1 : 0);
-        const int target = (c->sb_cur + 1 + ahead) % kSegSets;
-        Ctx::SegBuf& nb = c->sb[target];
-        // launches that still touch that set (a segment closed several switches ago) must be through
-        if (int rcw = wait_event(c, ds, nb.used)) return rcw;
-        S.counts_seq = (S.counts_seq + 1) & 0x3fffffff;
-        {
-            ProfScope p(c, K_EMIT, ds);
-            launch_tail_device(ds, D, quality, nb.live, nb.alive, nb.tracks, kMaxVert, c->use_order ? nb.order : nullptr,
-                               nb.order_border, tail_order_geometry(w, h, c->border_px), tail_reset_of(D, (int)ncell),
-                               S.h_counts, kCountsSeq, S.counts_seq);
-        }
-        rc = check_launch(c, "tail (device-driven)");
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(nb.ready, ds));
-        HIPCHK(c, hipEventRecord(S.counts_ev, ds));
-        J.dev_tail = true;
-        J.seg_set = target;
-    } else {
-        rc = publish_counts(c, S);
-        if (rc) return rc;
-    }
-    J.active = true;
-    J.seq = ++c->job_seq;
+    if ((rc = begin_candidates(c, S, slot, use_mask, mask, block_size))) return rc;
+    if ((rc = begin_min_distance(c, S, dev_tail))) return rc;
+    if ((rc = dev_tail ? begin_device_tail(c, S, k) : publish_counts(c, S))) return rc;
+    S.job.active = true;
+    S.job.seq = ++c->job_seq;
     return ICELK_OK;
 }
 
-// seg != null (seg_stage): the corners start a segment in that set -- corner list, the segment's tables and the counter
-// reset go out as ONE launch (k_tail) instead of three; *seg_done tells seg_stage that the tables are written
-// *dev_done: the device-driven tail has written everything (tables AND launch order): nothing is left to enqueue
-// *finished: the job of the detection finished here (the oldest in flight)
-int detect_finish(Ctx* c, int max_corners, int cap, int* n_out, Ctx::SegBuf* seg, bool* seg_done, bool* dev_done,
-                  DetectJob* finished)
+// ---- detect_finish, phase by phase -----------------------------------------------------------------------------------
+static int over_capacity(Ctx* c) { FAIL(c, ICELK_ECAP, "more corners than the output capacity (raise max_pts)"); }
+
+// Next time: candidates per accepted corner as seen now, and half as many again; 8x to begin with, after a detection that
+// fell short (its stage was redone) and after one that was not pruned at all
+static void update_prune_factor(Ctx* c, const DetectJob& J, int max_corners, const Counts& n, bool fell_short)
+{
+    if (J.prune_want <= 0 || max_corners <= 0) return;
+    const bool start_over = fell_short || !n.pruned || n.accepted <= 0;
+    c->prune_factor = start_over ? 8.0 : std::min(8.0, std::max(2.0, 1.5 * (double)n.candidates / n.accepted));
+}
+
+static void record_stats(Ctx* c, int candidates, int accepted)
+{
+    c->last_candidates = candidates;
+    c->last_accepted = accepted;
+}
+
+// The tail ran on the device already and the host adopts its verdict: done (out->order_written), an error, or -- the
+// relaxation not converged, the pruned set short, the bins skewed -- the host's tail on the counts the device published
+static int adopt_device_verdict(Ctx* c, Ctx::DetSet& S, const Counts& n, int max_corners, int cap, const Ctx::SegBuf* seg,
+                                DetectResult* out)
+{
+    const DetectJob& J = S.job;
+    if (!seg || seg != &c->sb[J.seg_set] || max_corners != J.max_corners)
+        FAIL(c, ICELK_ESTATE, "the segment staged is not the one its detection was begun for (set / maxCorners differ)");
+    if (n.status == TAIL_OVERFLOW) return over_capacity(c);
+    if (n.status != TAIL_OK) return ICELK_OK;
+    if (n.n_out > cap) return over_capacity(c);
+    update_prune_factor(c, J, max_corners, n, false);
+    record_stats(c, n.candidates, n.accepted);
+    S.reset_ncell = J.ncell;
+    S.counters_clean = true;    // k_tail_order left them zeroed
+    c->tails_dev++;
+    out->n = n.n_out;
+    out->tables_written = out->order_written = true;
+    return ICELK_OK;
+}
+
+// The min-distance relaxation continued from the host until no candidate is undecided; when the pruned candidate set did
+// not yield maxCorners corners, the stage once more on all candidates.  *n: the counts behind all that
+static int relax_on_host(Ctx* c, Ctx::DetSet& S, int max_corners, Counts* n)
+{
+    const DetectJob& J = S.job;
+    const hipStream_t ds = c->det_stream;
+    auto converge = [&]() -> int {
+        for (int guard = 0; n->undecided != 0; guard++) {
+            if (guard > 100000) FAIL(c, ICELK_EHIP, "min-distance suppression did not converge");
+            continue_min_distance(ds, S.D, J.w, J.h, J.min_distance);
+            if (int r = fetch_counts(c, S, n)) return r;
+        }
+        return ICELK_OK;
+    };
+    if (int rc = converge()) return rc;
+    const bool fell_short = J.prune_want > 0 && n->pruned && (max_corners <= 0 || n->accepted < max_corners);
+    if (fell_short) {
+        launch_detect_reset(ds, S.D, (int)J.ncell, 0);
+        launch_min_distance(ds, S.D, J.w, J.h, J.min_distance, J.quality, 0);
+        int rc = check_launch(c, "min_distance (unpruned)");
+        if (rc || (rc = fetch_counts(c, S, n)) || (rc = converge())) return rc;
+    }
+    update_prune_factor(c, J, max_corners, *n, fell_short);
+    return ICELK_OK;
+}
+
+// The corners by response, on the tail stream: the accepted keys, or for minDistance < 1 every candidate.  *total: how
+// many there are (0: nothing was enqueued)
+static int sort_corners(Ctx* c, Ctx::DetSet& S, const Counts& n, const unsigned long long** sorted, int* total)
+{
+    DetectScratch& D = S.D;
+    const bool relaxed = S.job.min_distance >= 1;
+    *total = relaxed ? n.accepted : n.candidates;
+    record_stats(c, n.candidates, *total);
+    if (*total == 0) return ICELK_OK;
+    sort_keys_desc(c->tail_stream, D, relaxed ? D.acc : D.cand, relaxed ? D.acc_sorted : D.cell_cand, *total);
+    *sorted = relaxed ? D.acc_sorted : D.cell_cand;
+    return check_launch(c, "sort");
+}
+
+// The first n sorted keys become the corner list in c->d_corners.  seg != null: and the tables of the segment they start
+// in that set, with the reset of this set's counters, as ONE launch (k_tail), once launches that still touch the set are
+// through.  Otherwise the reset follows the list, for this set's next detection, which waits for tail_done
+static int tail_or_emit(Ctx* c, Ctx::DetSet& S, const unsigned long long* sorted, int n, Ctx::SegBuf* seg, DetectResult* out)
+{
+    const DetectJob& J = S.job;
+    const hipStream_t ts = c->tail_stream;
+    if (int rcw = seg ? wait_event(c, ts, seg->used) : ICELK_OK) return rcw;
+    {
+        ProfScope p(c, K_EMIT, ts);
+        if (seg) launch_tail_fused(ts, sorted, n, c->d_corners, seg->live, seg->alive, seg->tracks, kMaxVert, S.D, (int)J.ncell, 1);
+        else launch_emit_corners(ts, sorted, n, J.w, c->d_corners);
+    }
+    if (int rc = check_launch(c, seg ? "tail" : "emit")) return rc;
+    HIPCHK(c, hipEventRecord(c->det_done, ts));
+    if (!seg) launch_detect_reset(ts, S.D, (int)J.ncell, 1);
+    HIPCHK(c, hipEventRecord(S.tail_done, ts));
+    out->tables_written = seg != nullptr;
+    S.reset_ncell = J.ncell;
+    S.counters_clean = true;
+    out->n = n;
+    return ICELK_OK;
+}
+
+// Finishes the oldest detection in flight.  seg != null (seg_stage): its corners start a segment in that set.  Everything
+// behind the host round trip -- sort, corner list, counter reset, the segment's tables -- goes to the tail stream: the
+// detection stream may already hold the min-distance stage of the NEXT detection (the other set), and the two have
+// nothing in common but d_corners, which only tails touch.
+int detect_finish(Ctx* c, int max_corners, int cap, Ctx::SegBuf* seg, DetectResult* out)
 {
     Range rg("icelk detect_finish (host round trip, sort, corner list)");
-    if (seg_done) *seg_done = false;
-    if (dev_done) *dev_done = false;
+    *out = DetectResult{};
     const int k = det_oldest(c);
     if (k < 0) FAIL(c, ICELK_ESTATE, "no detection in flight");
     c->dset_last = k;
     Ctx::DetSet& S = c->dset[k];
-    DetectJob& J = S.job;
-    J.active = false;
-    if (finished) *finished = J;
-    *n_out = 0;
-    const hipStream_t ds = c->det_stream;
-    // Everything behind the host round trip -- sort, corner list, the reset of this set's counters, and in seg_stage the
-    // new segment's tables -- goes to the tail stream: the detection stream may already hold the min-distance stage of
-    // the NEXT detection (the other set), and the two have nothing in common but d_corners, which only tails touch.
-    const hipStream_t ts = c->tail_stream;
-    DetectScratch& D = S.D;
-    int rc = fetch_counts(c, S, true);   // the one host round trip of a detection: {candidates, accepted, undecided}
+    const DetectJob& J = S.job;
+    S.job.active = false;
+    out->w = J.w;
+    out->h = J.h;
+    Counts n{};
+    int rc = fetch_counts(c, S, &n, true);   // the one host round trip of a detection
     if (rc) return rc;
-    if (J.dev_tail) {
-        // the tail ran on the device already; the host adopts its verdict
-        const int status = S.h_counts[5];
-        if (!seg || seg != &c->sb[J.seg_set] || max_corners != J.max_corners)
-            FAIL(c, ICELK_ESTATE, "the segment staged is not the one its detection was begun for (set / maxCorners differ)");
-        if (status == TAIL_OVERFLOW) FAIL(c, ICELK_ECAP, "more corners than the output capacity (raise max_pts)");
-        if (status == TAIL_OK) {
-            const int total = S.h_counts[1], n = S.h_counts[4];
-            if (n > cap) FAIL(c, ICELK_ECAP, "more corners than the output capacity (raise max_pts)");
-            if (J.prune_want > 0 && max_corners > 0)
-                c->prune_factor = !S.h_counts[3] || total <= 0 ? 8.0 : std::min(8.0, std::max(2.0, 1.5 * (double)S.h_counts[0] / total));
-            c->last_candidates = S.h_counts[0];
-            c->last_accepted = total;
-            S.reset_ncell = J.ncell;
-            S.counters_clean = true;    // k_tail_order left them zeroed
-            c->tails_dev++;
-            *n_out = n;
-            if (seg_done) *seg_done = true;
-            if (dev_done) *dev_done = true;
-            return ICELK_OK;
-        }
-        // not converged / pruned set fell short: the host's tail below, on the counts the device published
-    }
+    if (J.dev_tail && ((rc = adopt_device_verdict(c, S, n, max_corners, cap, seg, out)) || out->order_written)) return rc;
     c->tails_host++;
+    if (J.min_distance >= 1 && (rc = relax_on_host(c, S, max_corners, &n))) return rc;
     const unsigned long long* sorted = nullptr;
     int total = 0;
-    if (J.min_distance >= 1) {
-        auto converge = [&]() -> int {
-            for (int guard = 0; S.h_counts[2] != 0; guard++) {
-                if (guard > 100000) FAIL(c, ICELK_EHIP, "min-distance suppression did not converge");
-                continue_min_distance(ds, D, J.w, J.h, J.min_distance);
-                int r = fetch_counts(c, S);
-                if (r) return r;
-            }
-            return ICELK_OK;
-        };
-        if ((rc = converge())) return rc;
-        bool redone = false;
-        if (J.prune_want > 0 && S.h_counts[3] && (max_corners <= 0 || S.h_counts[1] < max_corners)) {
-            // the pruned candidate set did not yield maxCorners corners: redo the stage on all candidates
-            redone = true;
-            launch_detect_reset(ds, D, (int)J.ncell, 0);
-            launch_min_distance(ds, D, J.w, J.h, J.min_distance, J.quality, 0);
-            if ((rc = check_launch(c, "min_distance (unpruned)"))) return rc;
-            if ((rc = fetch_counts(c, S))) return rc;
-            if ((rc = converge())) return rc;
-        }
-        total = S.h_counts[1];
-        if (J.prune_want > 0 && max_corners > 0) {
-            // next time: candidates per accepted corner as seen now, and half as many again; a detection that fell short
-            // (it was redone above) or was not pruned at all starts over at 8x
-            const bool fell_short = !S.h_counts[3] || redone;
-            c->prune_factor = fell_short || total <= 0 ? 8.0 : std::min(8.0, std::max(2.0, 1.5 * (double)S.h_counts[0] / total));
-        }
-        c->last_candidates = S.h_counts[0];
-        c->last_accepted = total;
-        if (total == 0) return ICELK_OK;
-        sort_keys_desc(ts, D, D.acc, D.acc_sorted, total);
-        sorted = D.acc_sorted;
-    } else {
-        total = S.h_counts[0];
-        c->last_candidates = total;
-        c->last_accepted = total;
-        if (total == 0) return ICELK_OK;
-        sort_keys_desc(ts, D, D.cand, D.cell_cand, total);
-        sorted = D.cell_cand;
-    }
-    rc = check_launch(c, "sort");
-    if (rc) return rc;
-    int n = total;
-    if (max_corners > 0 && n > max_corners) n = max_corners;
-    if (n > cap || n > c->max_pts) FAIL(c, ICELK_ECAP, "more corners than the output capacity (raise max_pts)");
-    if (seg) {
-        // launches that still touch the segment set (a segment closed two switches ago) must be through
-        if (int rcw = wait_event(c, ts, seg->used)) return rcw;
-        {
-            ProfScope p(c, K_EMIT, ts);
-            launch_tail_fused(ts, sorted, n, c->d_corners, seg->live, seg->alive, seg->tracks, kMaxVert, D, (int)J.ncell, 1);
-        }
-        rc = check_launch(c, "tail");
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(c->det_done, ts));
-        HIPCHK(c, hipEventRecord(S.tail_done, ts));
-        *seg_done = true;
-    } else {
-        {
-            ProfScope p(c, K_EMIT, ts);
-            launch_emit_corners(ts, sorted, n, J.w, c->d_corners);
-        }
-        rc = check_launch(c, "emit");
-        if (rc) return rc;
-        HIPCHK(c, hipEventRecord(c->det_done, ts));
-        launch_detect_reset(ts, D, (int)J.ncell, 1);   // for this set's next detection, which waits for tail_done
-        HIPCHK(c, hipEventRecord(S.tail_done, ts));
-    }
-    S.reset_ncell = J.ncell;
-    S.counters_clean = true;
-    *n_out = n;
-    return ICELK_OK;
-}
-
-static int detect_core(Ctx* c, int slot, int use_mask, int max_corners, double quality, double min_distance,
-                       int block_size, int cap, int* n_out)
-{
-    *n_out = 0;
-    // begin + finish in one go: the detection finished must be the one begun here
-    if (det_oldest(c) >= 0) FAIL(c, ICELK_ESTATE, "a detection is in flight (icelk_seg_detect_begin without _stage / _finish)");
-    int rc = detect_begin(c, slot, use_mask, max_corners, quality, min_distance, block_size, false);
-    if (rc) return rc;
-    return detect_finish(c, max_corners, cap, n_out);
+    if ((rc = sort_corners(c, S, n, &sorted, &total)) || total == 0) return rc;
+    const int n_out = max_corners > 0 && total > max_corners ? max_corners : total;
+    if (n_out > cap || n_out > c->max_pts) return over_capacity(c);
+    return tail_or_emit(c, S, sorted, n_out, seg, out);
 }
 
 // for icelk_seg_detect_stage_try: have the counts of the oldest detection in flight arrived?  They are published behind
-// its min-distance stage (publish_counts); no wait
+// its min-distance stage (publish_counts); no wait: a look at the sequence word, and if it is not there at the event
 int detect_counts_arrived(Ctx* c, bool* arrived)
 {
     *arrived = false;
     const int k = det_oldest(c);
     if (k < 0) FAIL(c, ICELK_ESTATE, "no detection in flight");
-    if (!counts_here(c->dset[k].h_counts, c->dset[k].counts_seq)) {
-        const hipError_t q = hipEventQuery(c->dset[k].counts_ev);
+    const Ctx::DetSet& S = c->dset[k];
+    if (__atomic_load_n(S.h_counts + CW_SEQ, __ATOMIC_ACQUIRE) != S.counts_seq) {
+        const hipError_t q = hipEventQuery(S.counts_ev);
         if (q == hipErrorNotReady) {
             (void)hipGetLastError();
             return ICELK_OK;
@@ -642,10 +624,10 @@ int icelk_min_eig_map(icelk_t* h, int slot, int block_size, float* host_out, int
         ProfScope p(c, K_EIG);
         launch_detect_reset(c->stream, S.D, 0, 3);
         S.counters_clean = false;
-        if (fused_block_size(block_size) && !getenv("ICELK_GENERIC_CORNERS") && !c->corner_variant) {
+        if (strip_kernel_serves(c, block_size)) {
             launch_candidates(c->stream, S.D, s.lv[0], block_size, nullptr, 0, 1.0, false, S.D.eig);
         } else {
-            launch_min_eig(c->stream, s.lv[0], block_size, S.D.eig, nullptr, 0, S.D.max_key, c->corner_variant);
+            launch_min_eig(c->stream, s.lv[0], block_size, S.D.eig, nullptr, 0, S.D.cb.max_key, c->corner_variant);
         }
     }
     rc = check_launch(c, "min_eig");
@@ -663,14 +645,16 @@ int icelk_good_features(icelk_t* h, int slot, int use_mask, int max_corners, dou
     Ctx* c = C(h);
     HIPCHK(c, hipSetDevice(c->device));
     if (!out_n || cap < 0 || (cap > 0 && !out_xy)) FAIL(c, ICELK_EARG, "bad output buffer");
-    int n = 0;
-    int rc = detect_core(c, slot, use_mask, max_corners, quality_level, min_distance, block_size, cap, &n);
-    if (rc) return rc;
-    if (n > 0) {
-        HIPCHK(c, hipMemcpyAsync(out_xy, c->d_corners, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, c->tail_stream));
+    // begin + finish in one go: the detection finished must be the one begun here
+    if (det_oldest(c) >= 0) FAIL(c, ICELK_ESTATE, "a detection is in flight (icelk_seg_detect_begin without _stage / _finish)");
+    DetectResult r;
+    int rc = detect_begin(c, slot, use_mask, max_corners, quality_level, min_distance, block_size, false);
+    if (rc || (rc = detect_finish(c, max_corners, cap, nullptr, &r))) return rc;
+    if (r.n > 0) {
+        HIPCHK(c, hipMemcpyAsync(out_xy, c->d_corners, sizeof(float) * 2 * r.n, hipMemcpyDeviceToHost, c->tail_stream));
         HIPCHK(c, hipStreamSynchronize(c->tail_stream));
     }
-    *out_n = n;
+    *out_n = r.n;
     return ICELK_OK;
 }
 
@@ -689,7 +673,7 @@ int icelk_detect_fast_stats(icelk_t* h, int slot_w, int slot_h, long long* out)
     Ctx* c = C(h);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    const Ctx::EigOut& e = c->eo[c->dset[c->dset_last].eo_active];
+    const CandBuf& e = c->eo[c->dset[c->dset_last].eo_active].buf;
     if (!e.acand) FAIL(c, ICELK_EARG, "the two-pass detector was not enabled when this handle was created (ICELK_TWO_PASS_CORNERS)");
     const size_t nt = fast_tiles(slot_w, slot_h);
     std::vector<int> cnt(nt), mx(nt);
@@ -716,7 +700,7 @@ int icelk_detect_max_key(icelk_t* h, unsigned* out_key)
     Ctx* c = C(h);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    const Ctx::EigOut& e = c->eo[c->dset[c->dset_last].eo_active];
+    const CandBuf& e = c->eo[c->dset[c->dset_last].eo_active].buf;
     HIPCHK(c, hipMemcpy(out_key, e.max_key, sizeof(unsigned), hipMemcpyDeviceToHost));
     return ICELK_OK;
 }

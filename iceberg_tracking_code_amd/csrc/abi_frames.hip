@@ -76,6 +76,25 @@ int wait_event(Ctx* c, hipStream_t s, hipEvent_t e)
     return ICELK_OK;
 }
 
+// Waits until the pinned word holds seq (a kernel's system-scope release store) by polling it: the host learns of it when
+// it lands in its memory, not when the runtime has processed an event's completion signal and woken the thread.  The
+// event behind that kernel is looked at now and then, so that a failed launch ends the wait with its error, not a hang
+int await_pinned_seq(Ctx* c, const int* word, int seq, hipEvent_t ev)
+{
+    for (unsigned it = 1;; it++) {
+        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return ICELK_OK;
+        if ((it & 4095u) == 0) {
+            const hipError_t q = hipEventQuery(ev);
+            if (q == hipSuccess) break;             // complete: the synchronize below returns at once
+            if (q != hipErrorNotReady) HIPCHK(c, q);
+            (void)hipGetLastError();
+        }
+        __builtin_ia32_pause();
+    }
+    HIPCHK(c, hipEventSynchronize(ev));
+    return ICELK_OK;
+}
+
 int wait_slot(Ctx* c, int slot)
 {
     Slot& s = c->slots[slot];

@@ -399,21 +399,10 @@ bool jpeg_verdict_here(const Ctx::JpegJob& B)
     return __atomic_load_n(B.h_verdict + JV_SEQ, __ATOMIC_ACQUIRE) == B.seq;
 }
 
-// Waits for the verdict by polling the pinned sequence word, as fetch_counts (abi_detect.hip): the event is looked at
-// now and then, so that a failed launch ends the wait with its error instead of hanging it.
+// Waits for the verdict by polling the pinned sequence word (await_pinned_seq, abi_frames.hip)
 int jpeg_await_verdict(Ctx* c, Ctx::JpegJob& B)
 {
-    for (unsigned it = 1;; it++) {
-        if (jpeg_verdict_here(B)) return ICELK_OK;
-        if ((it & 4095u) == 0) {
-            const hipError_t q = hipEventQuery(B.done);
-            if (q == hipSuccess) break;
-            if (q != hipErrorNotReady) HIPCHK(c, q);
-            (void)hipGetLastError();
-        }
-        __builtin_ia32_pause();
-    }
-    HIPCHK(c, hipEventSynchronize(B.done));
+    if (int rc = await_pinned_seq(c, reinterpret_cast<const int*>(B.h_verdict + JV_SEQ), (int)B.seq, B.done)) return rc;
     if (!jpeg_verdict_here(B)) FAIL(c, ICELK_EHIP, "the JPEG verdict did not arrive");
     return ICELK_OK;
 }

@@ -300,29 +300,27 @@ int icelk_seg_detect_prepare(icelk_t* h, int slot, int use_mask, int block_size)
 static int seg_stage(Ctx* c, int max_corners, int* out_n)
 {
     if (c->seg_staged) FAIL(c, ICELK_ESTATE, "a staged segment is waiting for icelk_seg_switch");
-    int n = 0;
     // the new segment goes into the set after the current one, on the tail stream right behind the corner list
     Ctx::SegBuf& nb = c->sb[(c->sb_cur + 1) % kSegSets];
-    bool tables_written = false, dev_done = false;
-    DetectJob job;
-    int rc = detect_finish(c, max_corners, c->max_pts, &n, &nb, &tables_written, &dev_done, &job);
+    DetectResult r;
+    int rc = detect_finish(c, max_corners, c->max_pts, &nb, &r);
     if (rc) return rc;
-    if (!dev_done) {
+    if (!r.order_written) {
         const hipStream_t ds = c->tail_stream;
-        if (!tables_written) {
+        if (!r.tables_written) {
             // launches that still touch that set (a segment closed several switches ago) must be through
             if (int rcw = wait_event(c, ds, nb.used)) return rcw;
-            launch_seg_init(ds, c->d_corners, n, nb.live, nb.alive, nb.tracks, kMaxVert);
+            launch_seg_init(ds, c->d_corners, r.n, nb.live, nb.alive, nb.tracks, kMaxVert);
         }
-        if (c->use_order) launch_seg_order(ds, c->d_corners, n, job.w, job.h, c->border_px, nb.order, nb.order_border);
+        if (c->use_order) launch_seg_order(ds, c->d_corners, r.n, r.w, r.h, c->border_px, nb.order, nb.order_border);
         rc = check_launch(c, "seg_init");
         if (rc) return rc;
         HIPCHK(c, hipEventRecord(c->corners_free, ds));
         HIPCHK(c, hipEventRecord(nb.ready, ds));
     }
     c->seg_staged = true;
-    c->staged_n = n;
-    if (out_n) *out_n = n;
+    c->staged_n = r.n;
+    if (out_n) *out_n = r.n;
     return ICELK_OK;
 }
 

@@ -251,26 +251,22 @@ struct Ctx {
     size_t ncell_cap = 0;
     // Output of the corner kernel (candidate regions, per-tile counts, masked maximum), triple buffered: the
     // candidates of a FUTURE detection frame can be produced (icelk_seg_detect_prepare, on eig_stream) while the
-    // min-distance stages of the detections in flight still read their own.  A detector set's D.raw / D.blk_count /
-    // D.max_key / D.src_* always mirror eo[its eo_active] (point_at_eig_out).
-    struct EigOut {
-        unsigned long long* raw = nullptr;
-        int* blk_count = nullptr;
-        unsigned* max_key = nullptr;
-        // scratch of the two-pass detector (DetectScratch::acand ...)
-        uint2* acand = nullptr;
-        int* acount = nullptr;
-        uint2* amaxc = nullptr;
-        int* amaxn = nullptr;
-        float* aemax = nullptr;
-        unsigned* fmax_key = nullptr;
-        unsigned* aties = nullptr;
-        double quality = 0;          // candidates below max * quality were never given their exact key (0: none were cut)
-        int nblk = 0, region = 0;
-        bool valid = false;          // holds the candidates of (slot, gen) for (block_size, use_mask, mask_gen)
+    // min-distance stages of the detections in flight still read their own.  A detector set's D.cb always mirrors
+    // eo[its eo_active].buf (activate_eig_out).
+    struct CandKey {   // whose candidates a buffer holds: a slot's frame as it was (gen), for one blockSize and one mask
         int slot = -1, block_size = 0, use_mask = 0;
         unsigned long long gen = 0, mask_gen = 0;
+        bool operator==(const CandKey& o) const
+        {
+            return slot == o.slot && gen == o.gen && block_size == o.block_size && use_mask == o.use_mask && mask_gen == o.mask_gen;
+        }
+    };
+    struct EigOut {
+        CandBuf buf{};
+        double quality = 0;          // candidates below max * quality were never given their exact key (0: none were cut)
         hipEvent_t done = nullptr;
+        bool valid = false;          // holds the prepared candidates `key` names
+        CandKey key;
     } eo[3];
     // Two detections may be in flight (begun, not finished): the min-distance stage of frame d+2 is issued before the
     // host round trip of frame d, so that the round trip finds kernels that had a whole tracker launch to finish
@@ -279,8 +275,8 @@ struct Ctx {
     struct DetSet {
         DetectScratch D{};                // D.eig (the full-frame map of icelk_min_eig_map) is shared by both sets
         DetectJob job{};
-        int* h_counts = nullptr;          // pinned, device-visible: {candidates, accepted, undecided, ...} of the job
-        int counts_seq = 0;               // h_counts[kCountsSeq] == counts_seq: the counts published last have arrived
+        int* h_counts = nullptr;          // pinned, device-visible: the job's counts, laid out by CountsWord (icelk_internal.h)
+        int counts_seq = 0;               // its word CW_SEQ == counts_seq: the counts published last have arrived
         hipEvent_t counts_ev = nullptr;   // h_counts holds the counts of this set's detection
         hipEvent_t tail_done = nullptr;   // the tail of this set's latest detection (sort, emit, counter reset) is through
         size_t reset_ncell = 0;           // the detector counters are known to be zero for grids up to this many cells
@@ -299,7 +295,7 @@ struct Ctx {
     int tail_force_status = 0;        // ICELK_TAIL_FORCE_STATUS=1|2: the device verdict is forced to "host's tail" (tests of that path)
     long long tails_dev = 0, tails_host = 0;   // segments staged by the device-driven tail / by the host's
     int last_candidates = 0, last_accepted = 0;   // of the latest detection
-    double prune_factor = 8.0;                    // candidates kept per corner wanted (top-K pruning, detect_begin)
+    double prune_factor = 8.0;                    // candidates kept per corner wanted (top-K pruning: new_job, update_prune_factor)
 
     // ---- abi_segments.hip: segment sets, template tables, the deferred pair, read-out buffers
     // Segment state, six sets (kSegSets).  More than one because, while the tracker launch of a detection frame still
@@ -553,6 +549,7 @@ size_t slot_bytes(int w, int h);
 int pyramid_top_level(int w, int h, int win_w, int win_h, int max_level);
 int check_slot(Ctx* c, int slot, bool need_image);
 int wait_event(Ctx* c, hipStream_t s, hipEvent_t e);
+int await_pinned_seq(Ctx* c, const int* word, int seq, hipEvent_t ev);
 int wait_slot(Ctx* c, int slot);
 int ensure_pyramid(Ctx* c, int slot, int top_level);
 Pyramid pyramid_of(const Slot& s);
@@ -675,8 +672,13 @@ void activate_eig_out(Ctx* c, Ctx::DetSet& S, int idx);
 int detect_prepare(Ctx* c, int slot, int use_mask, int block_size);
 int detect_begin(Ctx* c, int slot, int use_mask, int max_corners, double quality, double min_distance, int block_size,
                  bool for_segment);
-int detect_finish(Ctx* c, int max_corners, int cap, int* n_out, Ctx::SegBuf* seg = nullptr, bool* seg_done = nullptr,
-                  bool* dev_done = nullptr, DetectJob* finished = nullptr);
+// what detect_finish leaves behind; of a segment's tables and launch order the device-driven tail writes both, the host's the tables
+struct DetectResult {
+    int n = 0;   // corners
+    bool tables_written = false, order_written = false;
+    int w = 0, h = 0;   // of the frame the finished job detected on
+};
+int detect_finish(Ctx* c, int max_corners, int cap, Ctx::SegBuf* seg, DetectResult* out);
 int detect_counts_arrived(Ctx* c, bool* arrived);
 // abi_segments.hip
 int flush_deferred(Ctx* c);

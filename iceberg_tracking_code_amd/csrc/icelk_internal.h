@@ -375,9 +375,25 @@ int launch_lk(hipStream_t s, const Pyramid& I, const Pyramid& J, const LKBuffers
 bool launch_lk_pair(hipStream_t s, const LKJob& a, const LKJob& b, const LKParams& P);
 
 // Detector stages.
+// A candidate buffer: what the corner kernel writes (launch_candidates) and the stages behind it read.  Three exist
+// (Ctx::EigOut in icelk_ctx.h); a detector scratch carries a copy of the one it works on.
+struct CandBuf {
+    unsigned long long* raw;   // candidate regions written by the corner kernel
+    int* blk_count;        // candidates per producer workgroup (region layout, see k_corners.hip)
+    unsigned* max_key;     // 1 (order-preserving key of the masked maximum)
+    // two-pass detector (k_corners_fast.hip): what its integer pass hands to its exact passes -- per tile the pixels that can
+    // be a local maximum {y << 16 | x, upper bound} and those that can carry the maximum, the tile's largest upper bound,
+    // and the largest lower bound of the whole frame
+    uint2 *acand, *amaxc;
+    int *acount, *amaxn;
+    float* aemax;
+    unsigned* fmax_key;      // [0] largest lower bound of the frame, [1] entries in aties
+    unsigned* aties;         // pixels (y << 16 | x) whose neighbourhood the exact pass must look at; 0x80000000 | tile: whole tile
+    int nblk, region;        // geometry of the candidate regions the buffer holds
+};
 struct DetectScratch {
     float* eig;            // w*h
-    unsigned* max_key;     // 1 (order-preserving key of the masked maximum)
+    CandBuf cb;            // the candidate buffer of the detection in flight
     unsigned long long* cand;   // candidate keys (value bits << 32 | raster index)
     int* cand_count;       // 1
     int cand_cap;
@@ -390,24 +406,11 @@ struct DetectScratch {
     int* undecided;        // 1
     unsigned long long* acc;   // accepted keys
     unsigned long long* acc_sorted;
-    unsigned long long* raw;   // candidate regions written by the corner kernel (one of three buffers, see Ctx::EigOut in icelk_ctx.h)
     int* acc_count;        // 1
     void* sort_tmp;
     size_t sort_tmp_bytes;
-    int* blk_count;        // candidates per producer workgroup (region layout, see k_corners.hip)
     unsigned* key_hist;    // histogram of the response keys (top-K pruning); 65536 entries allocated
     unsigned* prune_key;   // 1: candidates with a smaller response key are ignored (0 = none)
-    int src_nblk, src_region;   // geometry of the candidate regions of the detection in flight
-    // two-pass detector (k_corners_fast.hip): what its integer pass hands to its exact passes -- per tile the pixels that can
-    // be a local maximum {y << 16 | x, upper bound} and those that can carry the maximum, the tile's largest upper bound,
-    // and the largest lower bound of the whole frame.  These belong to the candidate buffer (Ctx::EigOut), like raw.
-    uint2* acand;
-    int* acount;
-    uint2* amaxc;
-    int* amaxn;
-    float* aemax;
-    unsigned* fmax_key;      // [0] largest lower bound of the frame, [1] entries in aties
-    unsigned* aties;         // pixels (y << 16 | x) whose neighbourhood the exact pass must look at; 0x80000000 | tile: whole tile
     // device-driven tail (k_tail.hip): control words (TailCtl), response-bin histogram / offsets / cursors, histogram of the launch order
     int* tail_ctl;
     int* tail_resp;
@@ -415,8 +418,13 @@ struct DetectScratch {
 };
 // k_tail.hip: words of DetectScratch::tail_ctl
 enum TailCtl { TC_TICKET_GATHER = 0, TC_TICKET_RANK, TC_TICKET_ORDER, TC_NOUT, TC_STATUS, TC_CAND, TC_ACC, TC_UNDECIDED, TC_PRUNED, TC_WORDS_ = 16 };
-// verdict of the device-driven tail (h_counts[5]): anything but TAIL_OK leaves the tail to the host (detect_finish)
+// verdict of the device-driven tail (CW_STATUS): anything but TAIL_OK leaves the tail to the host (detect_finish)
 enum TailStatus { TAIL_OK = 0, TAIL_UNDECIDED = 1, TAIL_PRUNED_SHORT = 2, TAIL_OVERFLOW = 3, TAIL_SKEWED = 4 };
+// Words of a detector set's pinned counts (Ctx::DetSet::h_counts).  k_publish_counts (abi_detect.hip) writes the first four,
+// the last workgroup of k_tail_order (k_tail.hip) the first six; then either stores the publication's sequence number in
+// CW_SEQ, which the host polls.  CW_NOUT and CW_STATUS keep what the latest tail left there when k_publish_counts
+// publishes: the host looks at them only for a job whose dev_tail is set.
+enum CountsWord { CW_CAND = 0, CW_ACC, CW_UNDECIDED, CW_PRUNED, CW_NOUT, CW_STATUS, CW_SEQ = 8, CW_WORDS_ = 16 };
 constexpr int kTailOrderBins = 8192;
 constexpr int kTailRespBins = 4096;
 struct TailOrderGeo {   // cells of the launch order (k_tracks.hip k_seg_order): bin 0 = border features
@@ -443,14 +451,14 @@ void launch_tail_gather(hipStream_t s, DetectScratch& D, int ncell, double quali
 // rank + corner tables of the new segment + launch order + counter reset + counts to the host, all from device-side counts
 void launch_tail_device(hipStream_t s, DetectScratch& D, double quality, float* seg_xy, uint8_t* seg_alive, float* seg_tracks,
                         int max_vert, int* order, int* order_border, const TailOrderGeo& geo, const TailReset& rs,
-                        int* host_counts, int counts_seq_word, int seq);
+                        int* host_counts, int seq);
 void launch_min_eig(hipStream_t s, const Level& img, int block_size, float* eig, const uint8_t* mask,
                     int mask_pitch, unsigned* max_key, int variant = 0);
 bool fused_block_size(int bs);
-// mode: 0 = the cell grid and the counters; | 1 = the key histogram too; | 2 = and the masked maximum D.max_key (only where
+// mode: 0 = the cell grid and the counters; | 1 = the key histogram too; | 2 = and the masked maximum D.cb.max_key (only where
 // the candidate buffer behind it is known to be this detection's: it may have been handed on since)
 void launch_detect_reset(hipStream_t s, DetectScratch& D, int ncell, int mode);
-// K6+K7: local maxima into per-workgroup regions of D.raw (stream order, no host sync)
+// K6+K7: local maxima into per-workgroup regions of D.cb.raw (stream order, no host sync)
 void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int block_size, const uint8_t* mask,
                        int mask_pitch, double quality, bool use_generic, float* eig_out_or_null, int variant = 0);
 // K6 + K7 in two passes for blockSize 3 / 5 / 7 / 10 (integer bracket of the map, exact arithmetic at the possible maxima

@@ -1097,10 +1097,10 @@ void launch_min_eig(hipStream_t s, const Level& img, int block_size, float* eig,
 static CandSrc src_of(const DetectScratch& D)
 {
     CandSrc c;
-    c.keys = D.raw;
-    c.blk_count = D.blk_count;
-    c.nblk = D.src_nblk;
-    c.region = D.src_region;
+    c.keys = D.cb.raw;
+    c.blk_count = D.cb.blk_count;
+    c.nblk = D.cb.nblk;
+    c.region = D.cb.region;
     return c;
 }
 
@@ -1113,19 +1113,19 @@ void launch_detect_reset(hipStream_t s, DetectScratch& D, int ncell, int mode)
     if ((mode & 1) && blocks < KEY_BINS / CT) blocks = KEY_BINS / CT;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(k_detect_reset, dim3(blocks), dim3(CT), 0, s, D.cell_count, D.cell_fill, ncell, D.chunk_tot, D.undecided,
-                       D.acc_count, D.cand_count, D.max_key, D.key_hist, D.prune_key, mode);
+                       D.acc_count, D.cand_count, D.cb.max_key, D.key_hist, D.prune_key, mode);
 }
 
-// Candidate collection (K6+K7) into regions of D.raw (stream order, no host sync).
+// Candidate collection (K6+K7) into regions of D.cb.raw (stream order, no host sync).
 void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int block_size, const uint8_t* mask,
                        int mask_pitch, double quality, bool use_generic, float* eig_out_or_null, int variant)
 {
     if (variant) use_generic = true;     // the named variants live in the any-blockSize kernel only
-    unsigned long long* raw = D.raw;
+    unsigned long long* raw = D.cb.raw;
     CandSrc g_src{};
     // ICELK_TWO_PASS_CORNERS=1: the two-pass form (k_corners_fast.hip: integer bracket of the map + exact arithmetic at the
     // possible maxima) -- a third statement of the arithmetic, bit-identical, measured and not the default
-    const bool two_pass = D.acand != nullptr && getenv("ICELK_TWO_PASS_CORNERS") != nullptr;   // scratch: at icelk_create, under the same switch
+    const bool two_pass = D.cb.acand != nullptr && getenv("ICELK_TWO_PASS_CORNERS") != nullptr;   // scratch: at icelk_create, under the same switch
     if (two_pass && !use_generic && fused_block_size(block_size) && !eig_out_or_null &&
         launch_candidates_fast(s, D, img, block_size, mask, mask_pitch, quality))
         return;
@@ -1133,32 +1133,32 @@ void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int bl
         float k0, k1;
         sobel_scale(block_size, &k0, &k1);
         switch (block_size) {
-            case 3: launch_strip<3>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
-            case 5: launch_strip<5>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
-            case 7: launch_strip<7>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
-            default: launch_strip<10>(s, img, k0, k1, mask, mask_pitch, D.max_key, raw, D.blk_count, eig_out_or_null, &g_src); break;
+            case 3: launch_strip<3>(s, img, k0, k1, mask, mask_pitch, D.cb.max_key, raw, D.cb.blk_count, eig_out_or_null, &g_src); break;
+            case 5: launch_strip<5>(s, img, k0, k1, mask, mask_pitch, D.cb.max_key, raw, D.cb.blk_count, eig_out_or_null, &g_src); break;
+            case 7: launch_strip<7>(s, img, k0, k1, mask, mask_pitch, D.cb.max_key, raw, D.cb.blk_count, eig_out_or_null, &g_src); break;
+            default: launch_strip<10>(s, img, k0, k1, mask, mask_pitch, D.cb.max_key, raw, D.cb.blk_count, eig_out_or_null, &g_src); break;
         }
     } else {
-        launch_min_eig(s, img, block_size, D.eig, mask, mask_pitch, D.max_key, variant);
+        launch_min_eig(s, img, block_size, D.eig, mask, mask_pitch, D.cb.max_key, variant);
         g_src.keys = raw;
-        g_src.blk_count = D.blk_count;
+        g_src.blk_count = D.cb.blk_count;
         g_src.nblk = 0;
         g_src.region = 256 * NMS_ROWS;
         if (img.w >= 3 && img.h >= 3) {
             const dim3 grid = nms_grid(img.w, img.h);
-            hipLaunchKernelGGL(k_nms_collect, grid, dim3(256), 0, s, D.eig, img.w, img.h, mask, mask_pitch, D.max_key,
-                               quality, raw, D.blk_count);
+            hipLaunchKernelGGL(k_nms_collect, grid, dim3(256), 0, s, D.eig, img.w, img.h, mask, mask_pitch, D.cb.max_key,
+                               quality, raw, D.cb.blk_count);
             g_src.nblk = (int)(grid.x * grid.y);
         }
     }
-    D.src_nblk = g_src.nblk;
-    D.src_region = g_src.region;
+    D.cb.nblk = g_src.nblk;
+    D.cb.region = g_src.region;
 }
 
 // minDistance < 1: every candidate above the threshold, flat in D.cand / D.cand_count
 void launch_flatten(hipStream_t s, DetectScratch& D, double quality)
 {
-    hipLaunchKernelGGL(k_flatten, dim3(512), dim3(256), 0, s, src_of(D), D.max_key, quality, D.cand, D.cand_count);
+    hipLaunchKernelGGL(k_flatten, dim3(512), dim3(256), 0, s, src_of(D), D.cb.max_key, quality, D.cand, D.cand_count);
 }
 
 // Greedy-equivalent min-distance selection, fully enqueued (no host round trip): candidate regions ->
@@ -1212,14 +1212,14 @@ void launch_min_distance(hipStream_t s, DetectScratch& D, int w, int h, double m
     const int gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
     const int ncell = gw * gh;
     if (prune_want > 0) {
-        hipLaunchKernelGGL(k_key_hist, dim3(256), dim3(CT), 0, s, src_of(D), D.max_key, quality, D.key_hist);
-        hipLaunchKernelGGL(k_key_select, dim3(1), dim3(CT), 0, s, D.key_hist, (unsigned)prune_want, D.max_key, D.prune_key);
+        hipLaunchKernelGGL(k_key_hist, dim3(256), dim3(CT), 0, s, src_of(D), D.cb.max_key, quality, D.key_hist);
+        hipLaunchKernelGGL(k_key_select, dim3(1), dim3(CT), 0, s, D.key_hist, (unsigned)prune_want, D.cb.max_key, D.prune_key);
     }
-    hipLaunchKernelGGL(k_cell_count, dim3(4096), dim3(CT), 0, s, src_of(D), D.max_key, quality, D.prune_key, w, cell, gw,
+    hipLaunchKernelGGL(k_cell_count, dim3(4096), dim3(CT), 0, s, src_of(D), D.cb.max_key, quality, D.prune_key, w, cell, gw,
                        D.cell_count, D.chunk_tot);
     hipLaunchKernelGGL(k_scan, dim3((ncell + SCAN_CHUNK - 1) / SCAN_CHUNK), dim3(CT), 0, s, D.cell_count, D.chunk_tot,
                        D.cell_start, ncell);
-    hipLaunchKernelGGL(k_cell_fill, dim3(4096), dim3(CT), 0, s, src_of(D), D.max_key, quality, D.prune_key, w, cell, gw,
+    hipLaunchKernelGGL(k_cell_fill, dim3(4096), dim3(CT), 0, s, src_of(D), D.cb.max_key, quality, D.prune_key, w, cell, gw,
                        D.cell_start, D.cell_fill, D.cell_cand, D.state);
     suppress_launches(s, D, w, h, min_distance);
     if (!no_gather) gather_launch(s, D, ncell);
@@ -1247,7 +1247,7 @@ void launch_tail_fused(hipStream_t s, const unsigned long long* keys, int n, flo
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(k_tail, dim3(emit_blocks + blocks), dim3(CT), 0, s, keys, n, corners, seg_xy, seg_alive, seg_tracks,
                        max_vert, emit_blocks, D.cell_count, D.cell_fill, ncell, D.chunk_tot, D.undecided, D.acc_count,
-                       D.cand_count, D.max_key, D.key_hist, D.prune_key, mode);
+                       D.cand_count, D.cb.max_key, D.key_hist, D.prune_key, mode);
 }
 
 void launch_emit_corners(hipStream_t s, const unsigned long long* keys, int n, int w, float* xy)

@@ -658,16 +658,16 @@ void launch_fast(hipStream_t s, const DetectScratch& D, const Level& img, const 
     sobel_scale_f(BS, &k0, &k1);
     const int tx = (img.w + FT_TW - 1) / FT_TW, ty = (img.h + FT_TH - 1) / FT_TH;
     const int ntiles = tx * ty, ngroups = (ntiles + FT_G - 1) / FT_G;
-    hipMemsetAsync(D.fmax_key, 0, 3 * sizeof(unsigned), s);   // and the tie / kept counters behind it
+    hipMemsetAsync(D.cb.fmax_key, 0, 3 * sizeof(unsigned), s);   // and the tie / kept counters behind it
     hipLaunchKernelGGL((k_eig_approx<BS>), dim3(tx, ty), dim3(256), C::LDS_BYTES, s, img.ptr, img.w, img.h, img.pitch, mask,
-                       mask_pitch, D.max_key, D.fmax_key, D.acand, D.acount, D.amaxc, D.amaxn, D.aemax);
+                       mask_pitch, D.cb.max_key, D.cb.fmax_key, D.cb.acand, D.cb.acount, D.cb.amaxc, D.cb.amaxn, D.cb.aemax);
     hipLaunchKernelGGL((k_exact_max<BS>), dim3((ntiles * FT_KMAX * 4 + 63) / 64), dim3(64), 0, s, img.ptr, img.w, img.h, img.pitch, k0,
-                       k1, mask, mask_pitch, ntiles, tx, D.fmax_key, D.amaxc, D.amaxn, D.aemax, D.max_key);
-    int* tie_count = reinterpret_cast<int*>(D.fmax_key + 1);
+                       k1, mask, mask_pitch, ntiles, tx, D.cb.fmax_key, D.cb.amaxc, D.cb.amaxn, D.cb.aemax, D.cb.max_key);
+    int* tie_count = reinterpret_cast<int*>(D.cb.fmax_key + 1);
     hipLaunchKernelGGL((k_exact_cands<BS>), dim3(ngroups), dim3(64), 0, s, img.ptr, img.w, img.h, img.pitch, k0, k1, ntiles,
-                       D.max_key, quality, D.acand, D.acount, D.raw, D.blk_count, D.aties, tie_count);
+                       D.cb.max_key, quality, D.cb.acand, D.cb.acount, D.cb.raw, D.cb.blk_count, D.cb.aties, tie_count);
     hipLaunchKernelGGL((k_exact_ties<BS>), dim3(2048), dim3(64), 0, s, img.ptr, img.w, img.h, img.pitch, k0, k1, mask, mask_pitch,
-                       tx, D.aties, tie_count, D.raw, D.blk_count);
+                       tx, D.cb.aties, tie_count, D.cb.raw, D.cb.blk_count);
     *nblk = ngroups;
     *region = FT_G * FT_TW * FT_TH;
 }
@@ -682,7 +682,7 @@ size_t fast_max_entries(int w, int h) { return fast_tiles(w, h) * FT_KMAX; }
 size_t fast_key_capacity(int w, int h) { return ((fast_tiles(w, h) + FT_G - 1) / FT_G) * (size_t)(FT_G * FT_TW * FT_TH); }
 size_t fast_regions(int w, int h) { return (fast_tiles(w, h) + FT_G - 1) / FT_G; }
 
-// K6 + K7 in two passes (see the head of this file); D.max_key must have been zeroed by the caller.  quality <= 0: every
+// K6 + K7 in two passes (see the head of this file); D.cb.max_key must have been zeroed by the caller.  quality <= 0: every
 // local maximum gets its exact key (a later detection with any qualityLevel can adopt the result).
 bool launch_candidates_fast(hipStream_t s, DetectScratch& D, const Level& img, int block_size, const uint8_t* mask,
                             int mask_pitch, double quality)
@@ -695,8 +695,8 @@ bool launch_candidates_fast(hipStream_t s, DetectScratch& D, const Level& img, i
         case 10: launch_fast<10>(s, D, img, mask, mask_pitch, quality, &nblk, &region); break;
         default: return false;
     }
-    D.src_nblk = nblk;
-    D.src_region = region;
+    D.cb.nblk = nblk;
+    D.cb.region = region;
     return true;
 }
 

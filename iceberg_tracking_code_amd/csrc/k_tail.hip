@@ -21,8 +21,7 @@
 //                   histogram of the launch order; the workgroup that finishes last turns that into offsets
 //   k_tail_order    the launch order of the new segment (what k_seg_order does: border features first, then cells in
 //                   raster order), the reset of the detector set's counters for its next detection, and -- by the
-//                   workgroup that finishes last -- the counts for the host: {candidates, accepted, undecided, pruned,
-//                   corners, status} + the sequence word the host polls.
+//                   workgroup that finishes last -- the counts for the host and the sequence word it polls (CountsWord).
 // The host reads the counts when it adopts the segment (icelk_seg_detect_stage / _switch): nothing waits for it.  When the
 // device-side verdict is "not valid" -- the relaxation of the min-distance stage has not converged, a pruned candidate
 // set yielded fewer than maxCorners corners (k_corners.hip), the corners exceed the tables, or one response bin holds
@@ -253,7 +252,7 @@ __global__ __launch_bounds__(CT) void k_tail_rank(const unsigned long long* __re
 
 __global__ __launch_bounds__(CT) void k_tail_order(TailArgs A, const float* __restrict__ seg_xy, TailOrderGeo geo, int* bins,
                                                     int* __restrict__ order, int order_blocks, TailReset rs,
-                                                    int* __restrict__ host_counts, int counts_seq_word, int seq)
+                                                    int* __restrict__ host_counts, int seq)
 {
     const int lane = threadIdx.x;
     int* ctl = A.ctl;
@@ -286,24 +285,24 @@ __global__ __launch_bounds__(CT) void k_tail_order(TailArgs A, const float* __re
     if (bins)
         for (int b = lane; b <= geo.ncells + 1; b += CT) bins[b] = 0;   // for this set's next detection
     if (lane == 0) {
-        host_counts[0] = ctl[TC_CAND];
-        host_counts[1] = ctl[TC_ACC];
-        host_counts[2] = ctl[TC_UNDECIDED];
-        host_counts[3] = ctl[TC_PRUNED];
-        host_counts[4] = n_out;
-        host_counts[5] = status;
+        host_counts[CW_CAND] = ctl[TC_CAND];
+        host_counts[CW_ACC] = ctl[TC_ACC];
+        host_counts[CW_UNDECIDED] = ctl[TC_UNDECIDED];
+        host_counts[CW_PRUNED] = ctl[TC_PRUNED];
+        host_counts[CW_NOUT] = n_out;
+        host_counts[CW_STATUS] = status;
         ctl[TC_TICKET_GATHER] = 0;
         ctl[TC_TICKET_RANK] = 0;
         ctl[TC_TICKET_ORDER] = 0;
         __threadfence_system();
-        __hip_atomic_store(host_counts + counts_seq_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(host_counts + CW_SEQ, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
 TailArgs args_of(DetectScratch& D, double quality)
 {
     TailArgs A{};
-    A.max_key = D.max_key;
+    A.max_key = D.cb.max_key;
     A.prune_key = D.prune_key;
     A.quality = quality;
     A.ctl = D.tail_ctl;
@@ -349,7 +348,7 @@ void launch_tail_gather(hipStream_t s, DetectScratch& D, int ncell, double quali
 
 void launch_tail_device(hipStream_t s, DetectScratch& D, double quality, float* seg_xy, uint8_t* seg_alive, float* seg_tracks,
                         int max_vert, int* order, int* order_border, const TailOrderGeo& geo, const TailReset& rs,
-                        int* host_counts, int counts_seq_word, int seq)
+                        int* host_counts, int seq)
 {
     int* bins = order ? D.tail_bins : nullptr;
     const TailArgs A = args_of(D, quality);
@@ -362,7 +361,7 @@ void launch_tail_device(hipStream_t s, DetectScratch& D, double quality, float* 
     if (reset_blocks < 16) reset_blocks = 16;
     if (reset_blocks > 192) reset_blocks = 192;
     hipLaunchKernelGGL(k_tail_order, dim3(order_blocks + reset_blocks), dim3(CT), 0, s, A, seg_xy, geo, bins, order, order_blocks, rs,
-                       host_counts, counts_seq_word, seq);
+                       host_counts, seq);
 }
 
 }  // namespace icelk

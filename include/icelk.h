@@ -196,7 +196,10 @@ int icelk_seg_detect(icelk_t* h, int slot, int use_mask, int max_corners, double
  * at once; _finish waits for it and starts the new segment.  TWO detections may be in flight (a third _begin returns
  * ICELK_ESTATE); _finish / _stage take them in the order they were begun and wait for the kernels of that one only.
  * Beginning the detection of frame d+2 before staging the one of frame d lets the host round trip of a detection find
- * kernels that had a whole tracker launch to finish, instead of standing in a serial loop with them. */
+ * kernels that had a whole tracker launch to finish, instead of standing in a serial loop with them.
+ * _stage / _finish must be passed the max_corners their detection was begun with (ICELK_ESTATE otherwise): the cut has
+ * been made on the device by then.  A _stage / _finish that fails drops its detection; one begun after it is still in
+ * flight but can no longer be staged, so icelk_seg_detect_cancel comes next. */
 int icelk_seg_detect_begin(icelk_t* h, int slot, int use_mask, int max_corners, double quality_level,
                            double min_distance, int block_size);
 int icelk_seg_detect_finish(icelk_t* h, int max_corners, int* out_n);
@@ -206,7 +209,7 @@ int icelk_seg_detect_finish(icelk_t* h, int max_corners, int* out_n);
  * before they arrive: afterwards the one-call forms (icelk_good_features, icelk_seg_detect) work again. */
 int icelk_seg_detect_cancel(icelk_t* h);
 /* _finish in two halves, for loops that know their frames some steps ahead: _stage waits for the OLDEST detection in
- * flight and builds the new segment in the handle's next set of segment buffers (four rotate) while the current segment
+ * flight and builds the new segment in the handle's next set of segment buffers (six rotate) while the current segment
  * is still being tracked; icelk_seg_switch (no GPU work, no wait) makes the staged segment the current one.  One
  * segment can be staged at a time.  With the detection of frame c begun at step c-4 and staged at step c-2 (behind the
  * _switch of that step), the one host round trip of a detection is off the critical path: the tracker launch of
