@@ -21,6 +21,7 @@
 //     issued before the first one is waited for; divisions by the tile pitch are by constants.
 //   * the five sums are exact integers reduced through the DPP network (lk_common.h), no LDS round trips.
 #include "lk_fast_tiles.h"
+#include "lk_uniform_math.h"
 
 namespace icelk {
 
@@ -38,22 +39,20 @@ __device__ __forceinline__ float sum_to_float(long long t)
     return __fadd_rn(__fmul_rn((float)hi, 65536.f), (float)lo);
 }
 
-// floor of a wave-uniform coordinate as an int in a scalar register: v_floor, v_cvt, one readlane.  Written as
-// uni((int)floorf(x)), the compiler read the float back first, converted that in the vector unit and read the int back again.
-__device__ __forceinline__ int floor_uni(float x)
-{
-    int i = (int)floorf(x);
-    asm volatile("" : "+v"(i));
-    return uni(i);
-}
-// ... and floorf(x) itself, for the fraction x - fx of the bilinear weights: where the origin test has passed, the floor is a
-// small integer and x - fx is x - (float)floor_uni(x) without the conversion back (two vector instructions per origin)
+// floor of a wave-uniform coordinate as an int in a scalar register: one conversion that floors (lk_uniform_math.h) and one
+// readlane, where only the int is used (the staging origins and the residual error's origin) ...
+__device__ __forceinline__ int floor_uni(float x) { return uni(floor_to_int(x)); }
+// ... and with floorf(x) itself (v_floor beside the conversion, both straight from x), for the fraction x - fx of the
+// bilinear weights: where the origin test has passed, the floor is a small integer and x - fx is
+// x - (float)floor_uni(x) without the conversion back (two vector instructions per origin).
+// The int comes from the flooring conversion here too, although (int)fx costs the same: the two are equal for every float
+// but a NaN, which (int)fx turns into 0 -- an origin that passes origin_ok -- and the flooring conversion into INT_MAX,
+// which fails it, as the oracle's x86 conversion (INT_MIN) does.  A NaN can only come in with the point; its first floor
+// is this one, at the start of every level, so every level is skipped: status 0, err 0, the NaN carried to nextPts.
 __device__ __forceinline__ int floor_uni(float x, float& fx)
 {
     fx = floorf(x);
-    int i = (int)fx;
-    asm volatile("" : "+v"(i));
-    return uni(i);
+    return uni(floor_to_int(x));
 }
 
 // A template as it travels from the backward pass of one pair to the forward pass of the next (LKBuffers::tmpl_out):
@@ -424,7 +423,8 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
             if (level == 0) Rz.status = 0;
             continue;
         }
-        D = __fdiv_rn(1.f, D);
+        // D is finite (finite integer sums times 2^-20) and not below 2^-23 here: recip_exact's range (lk_uniform_math.h)
+        D = recip_exact(D);
 
         // ---- iterations ---------------------------------------------------------------------------
         // the previous step; NaN before the first one, so that the oscillation test below fails without a test of j
