@@ -27,6 +27,7 @@ from .plot import plot_glyph, plot_name, plot_overlay_host, plot_size, plot_stam
 from .velocity_map import (gist_rainbow_table, map_descriptor, map_glyph, map_inset_array, map_layout, map_name, map_overlay_host, map_picture,  # noqa: F401
                            map_insets, map_strings, map_texts, map_view, scaled_arrows)
 from .png import encode_png_host, png_bound, png_filter_host  # noqa: F401
+from .movie import MovieWriter, frame_host, movie_size, read_avi, resize_host  # noqa: F401
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

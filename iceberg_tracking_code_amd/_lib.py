@@ -170,7 +170,12 @@ SIGNATURES = {
     "icelk_png_encode_host": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "icelk_png_encode_rgb": (C.c_int, [handle_p, u8p, C.c_int, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "icelk_map_draw_png": (C.c_int, [handle_p, map_desc_p, map_inset_p, C.c_int, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
-    "icelk_set_gray_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
+    "icelk_movie_size": (C.c_int, [C.c_int, C.c_int, C.c_int, i32p, i32p]),
+    "icelk_resize_host": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
+    "icelk_resize_rgb": (C.c_int, [handle_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
+    "icelk_picture_size": (C.c_int, [handle_p, i32p, i32p]),
+    "icelk_picture_frame": (C.c_int, [handle_p, C.c_int, C.c_int, C.c_int, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_set_gray_device":(C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_host_alloc": (C.c_int, [C.POINTER(vp), C.c_uint64]),

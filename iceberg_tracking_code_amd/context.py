@@ -58,6 +58,7 @@ def _criteria(criteria):
 
 # bytes first offered for a file of each kind (`_file_call`); a map's PNG is about 1.6 x its JPEG (profiles/png_map.txt)
 FIRST_GUESSES = {"crop": 1 << 16, "resave": 1 << 16, "plot": 1 << 18, "map_jpeg": 1 << 18, "map_png": 1 << 18}
+FRAME_FIRST_GUESS = 1 << 19   # ... and for a movie frame (`Context.picture_frame`)
 
 
 def _file_call(guesses, key, call, what, handle=None, extra=0):
@@ -746,6 +747,37 @@ class Context:
         data = _file_call(self._guesses, "map_" + format, lambda out, cap, n: fn(self._h, C.byref(d), *head, rgb_ptr, stride, out, cap, n),
                           what, self._h)
         del keep   # what the descriptor points into: alive until the call has returned
+        return (data, rgb) if want_rgb else data
+
+    # -- the movie of the pictures (s1:452-473, s3:194-215) -------------------------------------
+    def resize_rgb(self, rgb, size):
+        """H x W x 3 uint8 -> its (oh, ow, 3) resampling to size = (ow, oh), larger or smaller, on the device
+        (icelk_resize_rgb): pixels up, pixels down.  Equal to `movie.resize_host`, that is to Pillow's
+        `Image.fromarray(rgb).resize(size, Image.BICUBIC)`."""
+        a = _rgb3(rgb)
+        ow, oh = (int(v) for v in size)
+        out = np.empty((max(oh, 1), max(ow, 1), 3), np.uint8)
+        self._ck(self._lib.icelk_resize_rgb(self._h, _u8(a), a.shape[1], a.shape[0], a.strides[0], ow, oh, _u8(out), out.strides[0]))
+        return out
+
+    def picture_size(self):
+        """(width, height) of the handle's most recent picture (`plot_tracks`, `seg_plot`, `map_draw`); IcelkError (code
+        ICELK_ESTATE) when it has drawn none."""
+        w, h = C.c_int(0), C.c_int(0)
+        self._ck(self._lib.icelk_picture_size(self._h, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def picture_frame(self, size, quality=90, want_rgb=False):
+        """The movie frame of the handle's most recent picture: its R G B, still on the device, resized to size = (ow, oh)
+        and coded there, as the bytes of a JPEG file (icelk_picture_frame) -- what
+        `Image.fromarray(rgb).resize(size, Image.BICUBIC).save(f, "JPEG", quality=quality)` writes for the picture's R G B.
+        want_rgb: (bytes, the frame's R G B (oh, ow, 3) uint8), for tests.  IcelkError (code ICELK_ESTATE) when the handle
+        has drawn no picture."""
+        ow, oh = (int(v) for v in size)
+        rgb, rgb_ptr, stride = _rgb_out(want_rgb, max(ow, 1), max(oh, 1))
+        self._guesses.setdefault("frame", FRAME_FIRST_GUESS)
+        data = _file_call(self._guesses, "frame", lambda out, cap, n: self._lib.icelk_picture_frame(
+            self._h, ow, oh, int(quality), rgb_ptr, stride, out, cap, n), "icelk_picture_frame", self._h)
         return (data, rgb) if want_rgb else data
 
     # -- measurement ----------------------------------------------------------------------------

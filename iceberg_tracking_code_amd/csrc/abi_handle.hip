@@ -16,6 +16,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "map_clear", "map_cells", "map_polyline", "map_arrows", "map_resolve",
     "jpeg_thumb", "map_inset",
     "png_filter", "png_parse", "png_scan", "png_pack", "png_adler",
+    "resize_rows", "resize_cols",
 };
 
 std::string g_create_err;
@@ -175,6 +176,7 @@ static void destroy_ctx(Ctx* c)
     map_destroy(c);
     picture_destroy(c);
     png_destroy(c);
+    movie_destroy(c);
     prof_drain(c);
     for (auto& e : c->evt_pool) {
         hipEventDestroy(e.a);

@@ -17,6 +17,7 @@ void picture_destroy(Ctx* c)
 {
     jpeg_resave_free(c->picture);
     c->picture = Ctx::JpegResave{};
+    c->picture_w = c->picture_h = 0;
 }
 
 static size_t pad4(size_t v) { return (v + 3) & ~(size_t)3; }
@@ -49,6 +50,7 @@ int picture_write(Ctx* c, hipStream_t st, const PictureFile& F, uint8_t* rgb, in
     Ctx::JpegResave& R = c->picture;
     const size_t row = 3 * (size_t)F.Wo;
     uint32_t nbytes = 0;   // PNG: the deflate block's
+    c->picture_w = F.Wo, c->picture_h = F.Ho;   // what icelk_picture_frame (abi_movie.hip) makes a movie frame of
     switch (F.format) {
     case PICTURE_JPEG:
         if (int rc = jpeg_fwd_on(c, st, R.d_rgb, R.d_rcoef, F.Wo, F.Ho, F.info)) return rc;

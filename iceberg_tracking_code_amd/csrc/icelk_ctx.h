@@ -193,6 +193,22 @@ struct Ctx {
     // handle's compute stream and has waited for the device when it returns: no two are ever in flight.  An asynchronous
     // picture call would break it: the next call would draw over, or grow() would free, what the first still reads
     JpegResave picture;
+    int picture_w = 0, picture_h = 0;   // of the picture d_rgb holds: the one picture_write saw last (0: none yet)
+
+    // ---- abi_movie.hip: the scaler and the movie frame, allocated at first use.  The two axes' tables stay on the device,
+    // keyed by (in, out): every frame of a movie has the same sizes and uploads nothing.  `frame` is the movie frame's own
+    // working set (its R G B, coefficients and coder), so a frame leaves the picture's R G B and file as they are
+    struct Movie {
+        struct Axis {                    // [0] horizontal, [1] vertical
+            resize::Axis host;           // what the upload reads: lives as long as the handle
+            int32_t* d = nullptr;        // first | count | k
+            size_t cap = 0;
+            bool valid = false;          // d holds host's table
+        } axis[2];
+        uint8_t *d_mid = nullptr, *d_src = nullptr, *d_out = nullptr;   // between the passes; icelk_resize_rgb's picture and result
+        size_t mid_cap = 0, src_cap = 0, out_cap = 0;
+        JpegResave frame;
+    } movie;
 
     // ---- abi_plot.hip: the segment picture's own buffers, allocated at first use
     struct Plot {
@@ -660,6 +676,8 @@ int picture_check(Ctx* c, int Wo, int Ho, PictureFormat format, int quality, con
 int picture_grow(Ctx* c, const PictureFile& F);
 int picture_write(Ctx* c, hipStream_t st, const PictureFile& F, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
                   uint64_t* len);
+// abi_movie.hip
+void movie_destroy(Ctx* c);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

@@ -12,6 +12,7 @@
 #include "png_enc.h"
 #include "map_raster.h"
 #include "thumb_raster.h"
+#include "resize.h"
 
 namespace icelk {
 
@@ -92,6 +93,8 @@ enum KernelId {
     K_PNG_SCAN,                // ... bit offset of every segment (k_jpeg_enc_scan)
     K_PNG_PACK,                // ... the deflate bits
     K_PNG_ADLER,               // ... the pieces joined
+    K_RESIZE_ROWS,             // the movie's scaler (k_resize.hip): the horizontal pass
+    K_RESIZE_COLS,             // ... the vertical pass
     K_COUNT_
 };
 
@@ -314,6 +317,19 @@ void launch_png_filter(hipStream_t s, const PngArgs& A);
 void launch_png_parse(hipStream_t s, const PngArgs& A);
 void launch_png_pack(hipStream_t s, const PngArgs& A);
 void launch_png_adler(hipStream_t s, const uint32_t* pieces, uint32_t n, uint32_t* value);
+
+// k_resize.hip: the movie's scaler (the arithmetic is resize.h).  An axis' table on the device: output o reads the source
+// samples first[o] .. first[o] + count[o] - 1 with the weights k[o * pitch + j]; 0 <= first, first + count <= the axis' `in`,
+// first and first + count never decrease with o
+struct ResizeAxis {
+    const int32_t *first, *count, *k;
+    int pitch;
+};
+// rows: the `rows` rows at src (src_pitch bytes apart, X.in pixels) -> ow pixels each at dst (dst_pitch bytes apart)
+// cols: ow pixels of each of oh rows at dst; output row y reads src rows first[y] - lo ..., lo the first source row src holds
+void launch_resize_rows(hipStream_t s, const uint8_t* src, size_t src_pitch, int rows, const ResizeAxis& X, int ow, uint8_t* dst, size_t dst_pitch);
+void launch_resize_cols(hipStream_t s, const uint8_t* src, size_t src_pitch, int lo, const ResizeAxis& Y, int ow, int oh, uint8_t* dst,
+                        size_t dst_pitch);
 
 // LK.  p_in/p_out etc. are device pointers.  fb = fused forward+backward.
 struct LKBuffers {

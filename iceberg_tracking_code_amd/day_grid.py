@@ -29,7 +29,10 @@ writes, with its name and exactly the rasterised pixels; with pl
 and each window's picture draws its group of them.  With `photos=directory` as well, the picture carries the cameras'
 photographs from the middle of the window (s3:593-626, s3:788-829): `closest_image` picks the file, the device decodes it
 and reduces it to a thumbnail that is pasted into the map with the camera's name.
-Not built: the movie of the plots, PNG files with dynamic Huffman codes (the PNG is one fixed-Huffman block), the xlsx readers (pass the rows pd.read_excel gives),
+With `movie=` as well, every map drawn also becomes a frame of the movie the reference makes of them (s3:194-215), scaled
+and coded on the device from the pixels the map left there: a Motion-JPEG AVI, 8 frames per second, 2000 pixels wide
+(movie.py); `utm_to_gridded_utm_days` writes one movie over all its days, as s3's main does.
+Not built: the reference's movie codec (msmpeg4v2), PNG files with dynamic Huffman codes (the PNG is one fixed-Huffman block), the xlsx readers (pass the rows pd.read_excel gives),
 s3:main's process pool.
 """
 import ctypes as C
@@ -44,6 +47,7 @@ from . import _lib
 from .context import Context
 from .gridding import cell_table, create_grid_across_fjord, pack_cells
 from .jpeg import UnsupportedJpeg, describe_jpeg
+from .movie import open_movie, velocities_movie_name
 from .velocity_map import MAP_QUALITY, MAP_WIDTH, map_insets, map_layout, map_name, map_picture, map_strings, map_text, map_view
 
 EPOCH = dt.datetime(1970, 1, 1)
@@ -384,6 +388,8 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
         as_png = maps.get("format", "jpeg") == "png"
         written.append((name, arrays, map_name(maps["dir"], start, end, ext=".png" if as_png else ".jpg", **when),
                         ctx.map_draw(picture, format="png" if as_png else "jpeg")))
+        if maps.get("movie") is not None:
+            maps["movie"].add_picture(ctx)
     if vectors:
         ctx.map_arrows_release()
     if maps is not None and maps.get("photos") is not None:
@@ -396,7 +402,8 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
 
 def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts, fjord, day,
                        time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None, plot_switch=1,
-                       speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None, plot_format="jpeg"):
+                       speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None, plot_format="jpeg",
+                       movie=None):
     """One day of hourly velocity files -> one gridded .npz per time window, as s3_utm_to_gridded_utm.utm_to_gridded_utm
     (s3:222-446) with plot_switch 0.
 
@@ -416,7 +423,14 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
     `photos`: the reference's source_path_photos, a directory with <camera>/<%Y%m%d>/<%Y%m%d-%H%M%S>.jpg; every picture then
     carries, for each camera with tracks in its window, the photograph closest to the middle of the window (less than
     300 s away, `closest_image`), reduced on the device and labelled with the camera's name.  It needs
-    `plots`; photos=None calls nothing of this."""
+    `plots`; photos=None calls nothing of this.
+
+    `movie`: with `plots`, every map drawn also becomes a frame of a Motion-JPEG AVI (8 frames per second, 2000 pixels wide:
+    `movie.MovieWriter`), in the order drawn, scaled and coded on the device whatever `plot_format` is.
+    True: 'velocities_utm_<minutes>min.avi', the reference's name (s3:211), in `plots`; a path: that file; a `MovieWriter`:
+    frames are added to it and it is left open.  The maps and the .npz files do not change.  movie=None calls nothing of this."""
+    if movie is not None and plots is None:
+        raise ValueError("movie needs plots: its frames are the windows' pictures")
     if plots is not None and plot_switch not in (1, 2):
         raise ValueError("plot_switch must be 1 or 2")
     if plot_format not in ("jpeg", "png"):
@@ -432,11 +446,17 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
     own = ctx is None
     if own:
         ctx = Context(64, 64, n_slots=1, max_pts=1 << 18)
+    film_own = False
+    if movie is not None:
+        os.makedirs(maps["dir"], exist_ok=True)
+        maps["movie"], film_own = open_movie(movie, maps["dir"], velocities_movie_name(time_window))
     try:
         written = _grid_day(ctx, plan, fjord, grid_size, observation_threshold, maps=maps)
     finally:
         if own:
             ctx.close()
+        if film_own:
+            maps["movie"].close()
     if maps is not None:
         os.makedirs(maps["dir"], exist_ok=True)
         for _, _, path, data in written:
@@ -452,12 +472,18 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
 def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts,
                             fjord, time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None,
                             plot_switch=1, speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None,
-                            plot_format="jpeg"):
+                            plot_format="jpeg", movie=None):
     """s3:main's loop over days (without its process pool), on one context: the files of every day, in order.  The plot
-    keywords are utm_to_gridded_utm's."""
+    keywords are utm_to_gridded_utm's; `movie` gives ONE movie over all the days' maps, as s3's main makes one."""
+    if movie is not None and plots is None:
+        raise ValueError("movie needs plots: its frames are the windows' pictures")
     own = ctx is None
     if own:
         ctx = Context(64, 64, n_slots=1, max_pts=1 << 18)
+    film, film_own = None, False
+    if movie is not None:
+        os.makedirs(str(plots), exist_ok=True)
+        film, film_own = open_movie(movie, plots, velocities_movie_name(time_window))
     try:
         out = []
         for day in days:
@@ -465,8 +491,10 @@ def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, 
                                       clock_drifts, fjord, day, time_window, grid_size, observation_threshold,
                                       ctx=ctx, save=save, plots=plots, plot_switch=plot_switch,
                                       speedthreshold_cbar=speedthreshold_cbar, cameras=cameras, out_width=out_width,
-                                      quality=quality, photos=photos, plot_format=plot_format)
+                                      quality=quality, photos=photos, plot_format=plot_format, movie=film)
         return out
     finally:
         if own:
             ctx.close()
+        if film_own:
+            film.close()

@@ -26,6 +26,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from .movie import open_movie, tracks_movie_name
 from .plot import PLOT_QUALITY, PLOT_WIDTH, plot_name, plot_stamp
 from .tracker import REF_FEATURE_PARAMS, REF_LK_PARAMS, SegmentTracker, npz_name, save_tracks, segment_time_ok
 
@@ -73,7 +74,7 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                          mask_polygon=None, feature_params=None, lk_params=None, decode_threads=4, decode_ahead=6,
                          gray_variant=4, device=0, on_segment=None, save=True, decoder="pil", huffman="host", pipeline=False,
                          n_slots=PIPELINE_SLOTS, resave=None, save_crops=None, plots=None, plot_width=PLOT_WIDTH,
-                         plot_quality=PLOT_QUALITY, resave_ahead=False):
+                         plot_quality=PLOT_QUALITY, resave_ahead=False, movie=None):
     """Track one day's photos.  Returns [(npz path, tracks (n, T+1, 2) f32, trackquality (n, T) f32)] of the
     segments that pass the time-gap rule, in order.
 
@@ -115,6 +116,13 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                    (s1:429) with .jpg for .png, at JPEG quality `plot_quality`.  With every decoder / huffman / pipeline /
                    resave / save_crops combination; the returned list and the .npz files do not change.  None: nothing
                    of it runs and nothing is allocated
+    movie          with plots: the movie the reference makes of the day's pictures (s1:452-473), a Motion-JPEG AVI at 8
+                   frames per second and 2000 pixels wide.  Every picture written also becomes a frame, in the order
+                   written, scaled and coded on the device from the pixels the picture left there (`movie.MovieWriter`,
+                   DESIGN.md 7.11).  True: 'tracks_oblique_<track_len * track_len_sec>sec.avi', the reference's name, in
+                   `plots`; a path: that file; a `MovieWriter`: frames are added to it and it is left open.  Without a
+                   picture no file is written.  The pictures, the returned list and the .npz files do not change.  None:
+                   nothing of it runs
     """
     if decoder not in ("pil", "device"):
         raise ValueError('decoder must be "pil" or "device"')
@@ -136,6 +144,8 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
         raise ValueError("save_crops is not available with pipeline=True (unless resave_ahead=True)")
     if pipeline and int(n_slots) < 5:
         raise ValueError("n_slots must be at least 5")
+    if movie is not None and plots is None:
+        raise ValueError("movie needs plots: its frames are the pictures")
     imagelist = [str(p) for p in imagelist]
     out = []
     if len(imagelist) <= track_len:                       # s1:267
@@ -156,6 +166,7 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
         os.makedirs(plots, exist_ok=True)
     written = set()                                       # photos whose crop has been written
     trk = None
+    film, film_own = (None, False) if movie is None else open_movie(movie, plots, tracks_movie_name(track_len, track_len_sec))
     try:
         with ThreadPoolExecutor(max_workers=max(1, int(decode_threads))) as pool:
             for start in startlist:
@@ -230,10 +241,14 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                     if plots is not None:
                         with open(plot_name(plots, seg_names[-1], track_len, track_len_sec), "wb") as f:
                             f.write(trk.plot_closed(plot_width, plot_stamp(seg_names[-1], track_len, track_len_sec), plot_quality))
+                        if film is not None:
+                            film.add_picture(trk.ctx)
                     if on_segment is not None:
                         on_segment(npz, tracks, quality)
                     out.append((npz, tracks, quality))
     finally:
         if trk is not None:
             trk.close()
+        if film_own:
+            film.close()
     return out

@@ -862,6 +862,41 @@ int icelk_png_encode_rgb(icelk_t* h, const uint8_t* rgb, int w, int h_, int stri
 int icelk_map_draw_png(icelk_t* h, const icelk_map_desc_t* d, const icelk_map_inset_t* insets_or_null, int n_insets, uint8_t* rgb_or_null,
                        int rgb_stride, uint8_t* file, uint64_t capacity, uint64_t* len);
 
+/* ---- the movie of the pictures (opt-in) ------------------------------------------
+ * The reference ends a day of s1 and a run of s3 with a movie of the pictures it drew (s1:452-473, s3:194-215: mencoder,
+ * 8 frames per second, scaled to 2000 pixels wide).  Here every frame is a baseline JPEG of the picture scaled on the
+ * device -- byte for byte Image.fromarray(rgb).resize((ow, oh), Image.BICUBIC).save(f, "JPEG", quality=quality) -- and
+ * the container, a Motion-JPEG AVI, is written by the Python package (movie.py).  The rule is csrc/resize.h, which the
+ * device, the host statement below and tests/movie_restatement.py compute byte for byte alike:
+ *   size     mw = movie_width (<= 0: the picture's own width), mh = max(16, (mw h div w + 8) div 16 * 16): the proportions
+ *            kept, the height rounded to the nearest multiple of 16
+ *   axis     `in` samples -> `out`: scale = in / out, fs = max(scale, 1), support = 2 fs; output xx has
+ *            center = (xx + 0.5) scale and reads samples max(0, (int)(center - support + 0.5)) up to, not including,
+ *            min(in, (int)(center + support + 0.5)) with the bicubic weights (a = -0.5) of (j + first - center + 0.5) (1 / fs),
+ *            divided by their sum and rounded to 22 fractional bits
+ *   sample   clip(0, 255, (2^21 + sum k_j s_j) >> 22) in 32-bit signed arithmetic; the horizontal pass first, rounded to
+ *            8 bits, then the vertical pass; a pass with in == out is skipped
+ * Every side (w, h, ow, oh) is in 1 .. 16384, else ICELK_EARG. */
+/* Host only, no handle, re-entrant. */
+int icelk_movie_size(int w, int h_, int movie_width, int* mw, int* mh);
+/* Host only, no handle, re-entrant: the w x h picture (R G B, stride bytes per row) resampled to ow x oh (out_stride bytes
+ * per row) by the code the device's tables come from, on the CPU. */
+int icelk_resize_host(const uint8_t* rgb, int w, int h_, int stride, int ow, int oh, uint8_t* out, int out_stride);
+/* The same on the device (k_resize_rows, k_resize_cols: csrc/k_resize.hip): host pixels up, pixels down.  Synchronous.  The
+ * two axes' tables stay on the device until other sizes are asked for.  Refusals come before anything is allocated or
+ * enqueued. */
+int icelk_resize_rgb(icelk_t* h, const uint8_t* rgb, int w, int h_, int stride, int ow, int oh, uint8_t* out, int out_stride);
+/* Host only: the size of the handle's most recent picture, what icelk_movie_size is asked with.  ICELK_ESTATE: none yet. */
+int icelk_picture_size(icelk_t* h, int* w, int* h_);
+/* The movie frame of the handle's most recent picture (icelk_plot_tracks, icelk_seg_plot, icelk_map_draw and its forms,
+ * JPEG or PNG): the picture's R G B, still resident on the device, resized to ow x oh into a buffer of the frame's own and
+ * coded by the writer's forward kernel and entropy coder on the handle's compute stream.  No pixel crosses PCIe.  The
+ * picture's own file and R G B are not touched, and neither is the "most recent re-save".  ow >= 3, quality 1 .. 100.
+ * ICELK_ESTATE: the handle has drawn no picture.  ICELK_ECAP: `file` is too small (or NULL), *len says what the file
+ * takes and the call can be repeated.  rgb_or_null: receives the frame's R G B (tests).  The call waits for the device. */
+int icelk_picture_frame(icelk_t* h, int ow, int oh, int quality, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
+                        uint64_t* len);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
