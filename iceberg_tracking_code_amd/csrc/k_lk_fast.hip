@@ -8,7 +8,8 @@
 // What the compile-time window buys:
 //   * lane = one ROW SEGMENT of the window (S <= 8 contiguous pixels of one window row): 21x21 -> 63
 //     segments of 7 px, one per lane.  A lane reads its pixels from LDS as aligned dwords and realigns
-//     them with v_alignbyte, 6 ds_read_b32 per iteration instead of 28 ds_read_u8.
+//     them with v_alignbyte, 6 ds_read_b32 per iteration instead of 28 ds_read_u8 -- and none in an iteration whose
+//     window origin has the pixel cell of the one before it: the widened rows are kept (one segment per lane).
 //   * pixels are widened to 16-bit PAIRS (v_perm_b32) and every bilinear tap pair is one
 //     v_dot2_i32_i16 against a packed weight pair (w00|w01, w10|w11): a sample costs 2 dot2 + 1 shift;
 //     the rounding constant and the template value ride in the dot2 accumulator.
@@ -219,8 +220,8 @@ __device__ __forceinline__ void chain_sums(const float* fsum, int planes, int wh
     else chain_sums_t<WW, WH, (WW & ~7)>(fsum, planes, pairwise, out, lane);
 }
 
-// fsum: LDS room for three planes of WW x WH float products when the launch runs under a "lk_sums" variant, else null
-template <int WW, int WH>
+// fsum: LDS room for three planes of WW x WH float products when the launch runs under a "lk_sums" variant (SM), else null
+template <int WW, int WH, bool SM = false>
 __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const Pyramid& PJ, float p0x, float p0y,
                                                         const LKParams& P, uint32_t* ldsI, uint32_t* ldsJ, int lane,
                                                         bool want_err, uint4* __restrict__ tio, int tmode, uint4* tlds,
@@ -429,41 +430,97 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
         // ---- iterations ---------------------------------------------------------------------------
         // the previous step; NaN before the first one, so that the oscillation test below fails without a test of j
         float pdx = __builtin_nanf(""), pdy = __builtin_nanf("");
+        // Same-cell arm (one segment per lane, default sums): the widened tile rows of the last iteration that fetched
+        // them, and the pixel cell (floor of the window origin) they belong to.  An iteration of the same level pass
+        // whose origin lies in that cell gets what it got: the origin passed origin_ok, the tile covers it (a restage happens only in the full arm,
+        // which refills the pairs), jb and the tile's bytes are what they were.  It goes from the weights straight to the
+        // samples.  The first iteration of a level pass always takes the full arm (no_cell, a flag of its own: any marker
+        // value for "no cell yet" is the floor of some float -- every int is one), and a new level means a new tile.
+        // The "lk_sums" kernels keep the other arm: the pairs would cost the 15x15 one its fifth wave.
+        constexpr bool kKeepPairs = C::TPL == 1 && !SM;
+        v2s cp[kKeepPairs ? S + 1 : 1];
+        // The pairs start every level pass as values of their own (an empty statement, no instruction).  Left undefined
+        // here, the compiler carries the previous level's pairs through the whole level pass as their initial value, and
+        // eight registers more are live at the kernel's peak, the template build: a spill at 21x21, a wave lost at 15x15.
+        if constexpr (kKeepPairs) {
+#pragma unroll
+            for (int q = 0; q <= S; q++) {
+                uint32_t v;
+                asm volatile("" : "=v"(v));
+                cp[q] = as_v2s(v);
+            }
+        }
+        int cell_x = 0, cell_y = 0, no_cell = 1;
         for (int j = 0; j < P.max_count; j++) {
             float fnx, fny;
             const int inx = floor_uni(nx, fnx), iny = floor_uni(ny, fny);
-            if (!origin_ok<WW, WH>(LJ, inx, iny)) {
-                if (level == 0) Rz.status = 0;
-                break;
-            }
-            if (!tile_covers(jx0, jy0, inx, iny)) {
-                jx0 = inx - R; jy0 = iny - R;
-                __syncthreads();
-                TileRegs<C::JPD, C::JTH> tj;
-                // the level's pitch as an opaque value here: otherwise the loads' per-lane offsets (row * pitch + 4 c) are
-                // hoisted into every level pass, while a restage inside the iterations is the exception
-                Level LR = LJ;
-                asm volatile("" : "+s"(LR.pitch));
-                if (tile_inside(LR, jx0, jy0, C::JTW, C::JTH)) tile_issue(tj, LR, jx0, jy0, lane);
-                else tile_issue_reflect(tj, LR, jx0, jy0, lane);
-                tile_commit(tj, ldsJ, lane);
-                __syncthreads();
-            }
-            Rz.iters++;
-            uint32_t wj0, wj1;
-            packed_weights<true>(nx - fnx, ny - fny, wj0, wj1);
-            const int jb = uni((iny - jy0) * (C::JPD * 4) + (jx0 & 3) + (inx - jx0));
             int b1, b2;
-            if constexpr (kPackSeg) {
-                int row_l[C::TPL], col_l[C::TPL], len_l[C::TPL], joff_l[C::TPL];
-                seg_rows_cols(row_l, col_l, len_l);
+            if constexpr (kKeepPairs) {
+                // wave-uniform, a real branch.  One value that is zero exactly when the pairs hold this cell's rows (two XORs,
+                // two ORs, one compare on the scalar unit): written as j == 0 || inx != cell_x || iny != cell_y the compiler
+                // formed three 64-bit lane masks and combined those, eleven scalar instructions in front of every iteration.
+                if (((inx ^ cell_x) | (iny ^ cell_y) | no_cell) != 0) {
+                    no_cell = 0;
+                    if (!origin_ok<WW, WH>(LJ, inx, iny)) {
+                        if (level == 0) Rz.status = 0;
+                        break;
+                    }
+                    if (!tile_covers(jx0, jy0, inx, iny)) {
+                        jx0 = inx - R; jy0 = iny - R;
+                        __syncthreads();
+                        TileRegs<C::JPD, C::JTH> tj;
+                        Level LR = LJ;               // the pitch as an opaque value: see the restage of the other arm
+                        asm volatile("" : "+s"(LR.pitch));
+                        if (tile_inside(LR, jx0, jy0, C::JTW, C::JTH)) tile_issue(tj, LR, jx0, jy0, lane);
+                        else tile_issue_reflect(tj, LR, jx0, jy0, lane);
+                        tile_commit(tj, ldsJ, lane);
+                        __syncthreads();
+                    }
+                    const int jb = uni((iny - jy0) * (C::JPD * 4) + (jx0 & 3) + (inx - jx0));
+                    segment_pairs<WW, WH>(ldsJ, jb + joff[0], cp);
+                    cell_x = inx; cell_y = iny;
+                }
+                Rz.iters++;
+                uint32_t wj0, wj1;
+                packed_weights<true>(nx - fnx, ny - fny, wj0, wj1);
+                b1 = 0; b2 = 0;
+                segment_residual<WW, WH, 1, 0, false>(T, 0, cp, (uint32_t)uni((int)wj0), (uint32_t)uni((int)wj1), tlen[0],
+                                                      b1, b2);
+            } else {
+                // two and three segments per lane (31x31, 35x35: the pairs would be 18 / 27 registers) and the "lk_sums"
+                // kernels: fetched and widened in every iteration
+                if (!origin_ok<WW, WH>(LJ, inx, iny)) {
+                    if (level == 0) Rz.status = 0;
+                    break;
+                }
+                if (!tile_covers(jx0, jy0, inx, iny)) {
+                    jx0 = inx - R; jy0 = iny - R;
+                    __syncthreads();
+                    TileRegs<C::JPD, C::JTH> tj;
+                    // the level's pitch as an opaque value here: otherwise the loads' per-lane offsets (row * pitch + 4 c)
+                    // are hoisted into every level pass, while a restage inside the iterations is the exception
+                    Level LR = LJ;
+                    asm volatile("" : "+s"(LR.pitch));
+                    if (tile_inside(LR, jx0, jy0, C::JTW, C::JTH)) tile_issue(tj, LR, jx0, jy0, lane);
+                    else tile_issue_reflect(tj, LR, jx0, jy0, lane);
+                    tile_commit(tj, ldsJ, lane);
+                    __syncthreads();
+                }
+                Rz.iters++;
+                uint32_t wj0, wj1;
+                packed_weights<true>(nx - fnx, ny - fny, wj0, wj1);
+                const int jb = uni((iny - jy0) * (C::JPD * 4) + (jx0 & 3) + (inx - jx0));
+                if constexpr (kPackSeg) {
+                    int row_l[C::TPL], col_l[C::TPL], len_l[C::TPL], joff_l[C::TPL];
+                    seg_rows_cols(row_l, col_l, len_l);
 #pragma unroll
-                for (int k = 0; k < C::TPL; k++) joff_l[k] = row_l[k] * (C::JPD * 4) + col_l[k];
+                    for (int k = 0; k < C::TPL; k++) joff_l[k] = row_l[k] * (C::JPD * 4) + col_l[k];
+                    residual_pixels<WW, WH, 1, 0, false>(T, ldsJ, jb, (uint32_t)uni((int)wj0),
+                                                         (uint32_t)uni((int)wj1), joff_l, len_l, b1, b2, fsum, row_l, col_l);
+                } else
                 residual_pixels<WW, WH, 1, 0, false>(T, ldsJ, jb, (uint32_t)uni((int)wj0),
-                                                     (uint32_t)uni((int)wj1), joff_l, len_l, b1, b2, fsum, row_l, col_l);
-            } else
-            residual_pixels<WW, WH, 1, 0, false>(T, ldsJ, jb, (uint32_t)uni((int)wj0),
-                                                 (uint32_t)uni((int)wj1), joff, tlen, b1, b2, fsum, trow, tcol);
+                                                     (uint32_t)uni((int)wj1), joff, tlen, b1, b2, fsum, trow, tcol);
+            }
             // |diff*Ix| <= 8160*4080 per pixel: 8-lane sums fit int32 while a lane holds <= 8 pixels
             // Narrow arm: b1 and b2 in [-2^25, 2^25) in every lane (lk_common.h has the proof that the totals then fit int32
             // and the float is the wide arm's bit for bit); on real content that is nearly every iteration.
@@ -611,7 +668,7 @@ __device__ __forceinline__ void lk_fast_body(const LKJobs& JJ, const LKParams& P
     if (lane == 0) stamp(B, 0);
     using IO = TmplIO<WW, WH>;
     const size_t t_off = (size_t)f * ((size_t)B.tmpl_levels * IO::LEVEL);   // pieces before this track's
-    const TrackResult r1 = track_point_fast<WW, WH>(J.I, J.J, p0x, p0y, P, ldsI, ldsJ, lane, B.err_fwd != nullptr,
+    const TrackResult r1 = track_point_fast<WW, WH, SM>(J.I, J.J, p0x, p0y, P, ldsI, ldsJ, lane, B.err_fwd != nullptr,
                                                     const_cast<uint4*>(static_cast<const uint4*>(B.tmpl_in)) + t_off,
                                                     !SM && B.tmpl_in ? 1 : 0, tlds, fsum);
     if (lane == 0) {
@@ -621,7 +678,7 @@ __device__ __forceinline__ void lk_fast_body(const LKJobs& JJ, const LKParams& P
         if (B.iters && !FB) B.iters[f] = (uint32_t)r1.iters;
     }
     if (FB) {
-        const TrackResult r2 = track_point_fast<WW, WH>(J.J, J.I, r1.x, r1.y, P, ldsI, ldsJ, lane, B.err_bwd != nullptr,
+        const TrackResult r2 = track_point_fast<WW, WH, SM>(J.J, J.I, r1.x, r1.y, P, ldsI, ldsJ, lane, B.err_bwd != nullptr,
                                                         static_cast<uint4*>(B.tmpl_out) + t_off, !SM && B.tmpl_out ? 2 : 0, tlds,
                                                         fsum);
         if (lane == 0) {

@@ -428,6 +428,70 @@ __device__ __forceinline__ void template_pixels(Template<WW, WH, F>& T, const ui
 // ERR = false: b1 = sum diff*Ix, b2 = sum diff*Iy.   ERR = true: b1 = sum |diff| over the real window pixels.
 // fsum != nullptr: the two products of every window pixel also go to LDS as floats (int32 -> float, as _mm_cvtepi32_ps),
 // in raster order (trow, tcol = the segments' window rows / first columns).
+//
+// Its two halves, for one segment.  fetch + widen: the segment's two tile rows out of LDS (row_dwords x 2)
+// and its S + 1 column pairs.  They depend on the byte offset `off` (= jb + the segment's own offset) and on what the tile
+// holds, not on the weights: an iteration whose window origin lies in the same pixel cell as the one before it, with
+// nothing restaged in between, gets the same pairs (k_lk_fast.hip keeps them for the windows with one segment per lane).
+template <int WW, int WH>
+__device__ __forceinline__ void segment_pairs(const uint32_t* ldsJ, int off, v2s (&cp)[Cfg<WW, WH>::S + 1])
+{
+    using C = Cfg<WW, WH>;
+    constexpr int S = C::S, NXJ = (S + 1 + 3) / 4;
+    uint32_t Y0[NXJ], Y1[NXJ];
+    row_dwords<NXJ>(ldsJ, off, Y0);
+    row_dwords<NXJ>(ldsJ + C::JPD, off, Y1);
+    static_for<S + 1>([&](auto qq) {
+        constexpr int q = qq;
+        cp[q] = col_pair<q, NXJ>(Y0, Y1);
+    });
+}
+
+// samples + products of segment k from its column pairs: added to b1, b2 (the caller zeroes them)
+template <int WW, int WH, int F, int FI, bool ERR>
+__device__ __forceinline__ void segment_residual(const Template<WW, WH, F>& T, int k, const v2s (&cp)[Cfg<WW, WH>::S + 1],
+                                                 uint32_t V0u, uint32_t V1v, int tlen_k, int& b1, int& b2,
+                                                 float* fsum = nullptr, int trow_k = 0, int tcol_k = 0)
+{
+    using C = Cfg<WW, WH>;
+    constexpr int S = C::S;
+    int diff[S];
+    static_for<S>([&](auto qq) {
+        constexpr int q = qq;
+        // ((J bilinear + 256) >> 9) - I, with 256 - (I << 9) as the accumulator seed
+        diff[q] = dot2(cp[q + 1], as_v2s(V1v), dot2_vsv(cp[q], V0u, T.Ineg[FI][k][q])) >> (W_BITS - 5);
+    });
+    if constexpr (ERR) {
+        static_for<S>([&](auto qq) {
+            constexpr int q = qq;
+            b1 += q < tlen_k ? (diff[q] < 0 ? -diff[q] : diff[q]) : 0;
+        });
+    } else {
+        if (fsum) {
+            constexpr int NPX = WW * WH;
+            static_for<S>([&](auto qq) {
+                constexpr int q = qq;
+                if (q < tlen_k) {
+                    const uint32_t gx = T.Ixp[FI][k][q / 2], gy = T.Iyp[FI][k][q / 2];
+                    const int ix = (q & 1) ? ((int)gx >> 16) : (int)(short)(gx & 0xffffu);
+                    const int iy = (q & 1) ? ((int)gy >> 16) : (int)(short)(gy & 0xffffu);
+                    const int idx = trow_k * WW + tcol_k + q;
+                    fsum[idx] = (float)(diff[q] * ix);
+                    fsum[NPX + idx] = (float)(diff[q] * iy);
+                }
+            });
+        }
+        static_for<(S + 1) / 2>([&](auto qq) {
+            constexpr int q = qq;
+            uint32_t dp;
+            if constexpr (2 * q + 1 < S) dp = pack16(diff[2 * q], diff[2 * q + 1]);
+            else dp = (uint32_t)diff[2 * q];   // the partner half of the gradient pair is zero
+            b1 = dot2(as_v2s(dp), as_v2s(T.Ixp[FI][k][q]), b1);
+            b2 = dot2(as_v2s(dp), as_v2s(T.Iyp[FI][k][q]), b2);
+        });
+    }
+}
+
 template <int WW, int WH, int F, int FI, bool ERR>
 __device__ __forceinline__ void residual_pixels(const Template<WW, WH, F>& T, const uint32_t* ldsJ, int jb, uint32_t V0u,
                                                 uint32_t V1u, const int (&joff)[Cfg<WW, WH>::TPL],
@@ -435,52 +499,14 @@ __device__ __forceinline__ void residual_pixels(const Template<WW, WH, F>& T, co
                                                 const int* trow = nullptr, const int* tcol = nullptr)
 {
     using C = Cfg<WW, WH>;
-    constexpr int S = C::S;
     const uint32_t V1v = V1u;   // one weight pair rides as a scalar, the other in a VGPR
     b1 = 0; b2 = 0;
 #pragma unroll
     for (int k = 0; k < C::TPL; k++) {
-        constexpr int NXJ = (S + 1 + 3) / 4;
-        uint32_t Y0[NXJ], Y1[NXJ];
-        const int off = jb + joff[k];
-        row_dwords<NXJ>(ldsJ, off, Y0);
-        row_dwords<NXJ>(ldsJ + C::JPD, off, Y1);
-        int diff[S];
-        static_for<S>([&](auto qq) {
-            constexpr int q = qq;
-            // ((J bilinear + 256) >> 9) - I, with 256 - (I << 9) as the accumulator seed
-            diff[q] = dot2(col_pair<q + 1, NXJ>(Y0, Y1), as_v2s(V1v), dot2_vsv(col_pair<q, NXJ>(Y0, Y1), V0u, T.Ineg[FI][k][q])) >>
-                      (W_BITS - 5);
-        });
-        if constexpr (ERR) {
-            static_for<S>([&](auto qq) {
-                constexpr int q = qq;
-                b1 += q < tlen[k] ? (diff[q] < 0 ? -diff[q] : diff[q]) : 0;
-            });
-        } else {
-            if (fsum) {
-                constexpr int NPX = WW * WH;
-                static_for<S>([&](auto qq) {
-                    constexpr int q = qq;
-                    if (q < tlen[k]) {
-                        const uint32_t gx = T.Ixp[FI][k][q / 2], gy = T.Iyp[FI][k][q / 2];
-                        const int ix = (q & 1) ? ((int)gx >> 16) : (int)(short)(gx & 0xffffu);
-                        const int iy = (q & 1) ? ((int)gy >> 16) : (int)(short)(gy & 0xffffu);
-                        const int idx = trow[k] * WW + tcol[k] + q;
-                        fsum[idx] = (float)(diff[q] * ix);
-                        fsum[NPX + idx] = (float)(diff[q] * iy);
-                    }
-                });
-            }
-            static_for<(S + 1) / 2>([&](auto qq) {
-                constexpr int q = qq;
-                uint32_t dp;
-                if constexpr (2 * q + 1 < S) dp = pack16(diff[2 * q], diff[2 * q + 1]);
-                else dp = (uint32_t)diff[2 * q];   // the partner half of the gradient pair is zero
-                b1 = dot2(as_v2s(dp), as_v2s(T.Ixp[FI][k][q]), b1);
-                b2 = dot2(as_v2s(dp), as_v2s(T.Iyp[FI][k][q]), b2);
-            });
-        }
+        v2s cp[C::S + 1];
+        segment_pairs<WW, WH>(ldsJ, jb + joff[k], cp);
+        segment_residual<WW, WH, F, FI, ERR>(T, k, cp, V0u, V1v, tlen[k], b1, b2, fsum, fsum ? trow[k] : 0,
+                                             fsum ? tcol[k] : 0);
     }
 }
 
