@@ -383,10 +383,10 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
             const bool wide3 = fsum != nullptr ||
                 __builtin_amdgcn_ballot_w64(((unsigned)a11 | (unsigned)a22 | ((unsigned)a12 + kSumGuardBias)) >= P.sum_guard) != 0;
             if (__builtin_expect_with_probability(!wide3, 1, 0.7)) {
-                const int n11 = dpp_all_steps(a11), n12 = dpp_all_steps(a12), n22 = dpp_all_steps(a22);
-                A11 = lane63_float_u32(n11) * FLT_SCALE;
+                // a11 and a22, never negative, as one chain (lk_common.h, "two guarded sums as one chain"); a12 on its own
+                const int n12 = dpp_all_steps(a12), nd = dpp_pair_steps(a11, a22);
+                lanes31_63_float_u32(nd, FLT_SCALE, A11, A22);
                 A12 = lane63_float_i32(n12) * FLT_SCALE;
-                A22 = lane63_float_u32(n22) * FLT_SCALE;
             } else {
                 long long s11, s12, s22;
                 if constexpr (kSmall) wave_sum_mat_i64(a11, a12, a22, s11, s12, s22);
@@ -528,9 +528,8 @@ __device__ __forceinline__ TrackResult track_point_fast(const Pyramid& PI, const
             const bool wide2 = fsum != nullptr ||
                 __builtin_amdgcn_ballot_w64((((unsigned)b1 + kSumGuardBias) | ((unsigned)b2 + kSumGuardBias)) >= P.sum_guard) != 0;
             if (__builtin_expect_with_probability(!wide2, 1, 0.7)) {
-                const int n1 = dpp_all_steps(b1), n2 = dpp_all_steps(b2);
-                fb1 = lane63_float_i32(n1) * FLT_SCALE;
-                fb2 = lane63_float_i32(n2) * FLT_SCALE;
+                // one chain for both (lk_common.h, "two guarded sums as one chain"): b1's total ends in lane 31, b2's in lane 63
+                lanes31_63_float_i32(dpp_pair_steps(b1, b2), FLT_SCALE, fb1, fb2);
             } else {
                 long long t1, t2;
                 wave_sum2_i64<kSmall ? 8 : 1>(b1, b2, t1, t2);

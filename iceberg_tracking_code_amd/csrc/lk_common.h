@@ -207,6 +207,50 @@ __device__ __forceinline__ float lane63_float_u32(int v)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int((float)(unsigned)v), 63));
 }
 
+// ---- two guarded sums as one chain (round 11) ----------------------------------------------------------------------------
+// v_permlane32_swap_b32 exchanges lanes 32-63 of its first register with lanes 0-31 of its second: after it x holds
+// (x[0..31], y[0..31]) and y holds (x[32..63], y[32..63]), and one add leaves the FOLDED register f with
+// f[l] = x[l] + x[l + 32] in lanes 0-31 and f[l] = y[l - 32] + y[l] in lanes 32-63.  The four row_shr steps form prefix sums
+// inside each row of 16, row_bcast:15 (rows 1 and 3 only) adds row 0's total to row 1 and row 2's to row 3: lane 31 ends
+// with the total of x, lane 63 with the total of y.  No row_bcast:31 step: the halves stay apart.  7 instructions for 12.
+// Under the unchanged per-lane guard of kSumGuard nothing wraps:
+//   signed pair (b1, b2): every lane partial lies in [-2^25, 2^25), so a folded lane lies in [-2^26, 2^26 - 2]; every value
+//   a later step forms is a sum of k <= 32 folded lanes = of 2k <= 64 lane partials of ONE input, in [-2k 2^25, 2k (2^25 - 1)],
+//   inside [-2^31, 2^31 - 64] -- the bound of the proof above, for the same sets of lanes taken in another order.
+//   unsigned pair (a11, a22): every lane partial lies in [0, 2^26), a folded lane in [0, 2^27 - 2], and k <= 32 of them stay
+//   at or below 32 (2^27 - 2) = 2^32 - 64: the adds read as unsigned do not wrap.
+// Lane 31 / 63 therefore hold the integers t1 / t2 that the six-step chain leaves in lane 63 and that the 64-bit network
+// gives: integer addition without wrap-around is associative, the order of the adds does not matter.  ONE v_cvt_f32_i32 (or
+// v_cvt_f32_u32) converts both lanes, each rounding its t once to nearest even, exactly as lane63_float_* does: the two
+// floats are the wide arm's, bit for bit.  Lanes other than 31 and 63 hold partial prefixes that are never read.
+__device__ __forceinline__ int dpp_pair_steps(int x, int y)
+{
+    const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)y, false, false);
+    unsigned v = sw[0] + sw[1];                                                    // the fold
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);  // row_shr:1
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);  // row_shr:2
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);  // row_shr:4
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);  // row_shr:8
+    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, true);  // row_bcast15 -> rows 1,3
+    return (int)v;
+}
+// one conversion in the lanes, then v_readlane of lane 31 (the first sum) and of lane 63 (the second).  The scale (a power of
+// two times the float: one IEEE multiply, the same product in the lane as on the value read out) is applied in the lanes
+// too: one v_mul_f32 for both sums, and no packed multiply of the two scalars afterwards, whose constant pair cost two
+// VGPRs at the kernels' register peak and the 15x15 kernel its seventh wave.
+__device__ __forceinline__ void lanes31_63_float_i32(int v, float scale, float& s0, float& s1)
+{
+    const int f = __float_as_int(__fmul_rn((float)v, scale));
+    s0 = __int_as_float(__builtin_amdgcn_readlane(f, 31));
+    s1 = __int_as_float(__builtin_amdgcn_readlane(f, 63));
+}
+__device__ __forceinline__ void lanes31_63_float_u32(int v, float scale, float& s0, float& s1)
+{
+    const int f = __float_as_int(__fmul_rn((float)(unsigned)v, scale));
+    s0 = __int_as_float(__builtin_amdgcn_readlane(f, 31));
+    s1 = __int_as_float(__builtin_amdgcn_readlane(f, 63));
+}
+
 // correctly rounded int64 -> float for |t| < 2^52, through one exact double
 __device__ __forceinline__ float i64_to_float(long long t)
 {

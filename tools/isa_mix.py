@@ -29,6 +29,8 @@ def classify(op):
     if op.startswith("v_"):
         if op.startswith(("v_readlane", "v_readfirstlane", "v_writelane")):
             return "valu_lane"
+        if op.startswith(("v_permlane32_swap", "v_permlane16_swap")):
+            return "valu_swap"        # exchanges halves of TWO registers, both written: a class of its own in valu_class_cost.json
         if "_f64" in op or op.startswith(("v_cvt_f64", "v_cvt_i32_f64", "v_cvt_u32_f64")):
             return "valu_f64"
         if op.startswith(("v_rcp", "v_rsq", "v_sqrt", "v_exp", "v_log", "v_sin", "v_cos")):

@@ -24,7 +24,7 @@ enum Op {
     OP_ADD_U32, OP_XAD_U32, OP_MUL_I24, OP_MAD_I24, OP_DOT2_I16, OP_PERM, OP_ALIGNBYTE, OP_PK_ADD_U16, OP_PK_MAD_U16,
     OP_PK_MUL_LO_U16, OP_MUL_LO_U32, OP_FMA_F32, OP_PK_FMA_F32, OP_ADD_DPP, OP_CNDMASK, OP_LSHRREV, OP_READLANE,
     OP_S_ADD, OP_DS_READ_B32, OP_ASHRREV, OP_CNDMASK_E64, OP_DOT2C, OP_MOV, OP_ADD3, OP_LSHL_OR, OP_RNDNE, OP_CVT_I32_F32,
-    OP_CVT_F64_I32, OP_ADD_F64, OP_MUL_F64, OP_CVT_F32_F64, OP_DS_READ_B64, OP_DS_READ2_B32, OP_AND_OR, OP_MAX_I32, OP_CMP_CND_VCC, OP_CMP_CND_SGPR, OP_CMP_VCC, OP_CMP_SGPR, OP_ALIGNBIT, OP_BFE, OP_MIN_U32, OP_SUB_U32, OP_AND, OP_OR, OP_LSHL_ADD, OP_MED3, OP_COUNT
+    OP_CVT_F64_I32, OP_ADD_F64, OP_MUL_F64, OP_CVT_F32_F64, OP_DS_READ_B64, OP_DS_READ2_B32, OP_AND_OR, OP_MAX_I32, OP_CMP_CND_VCC, OP_CMP_CND_SGPR, OP_CMP_VCC, OP_CMP_SGPR, OP_ALIGNBIT, OP_BFE, OP_MIN_U32, OP_SUB_U32, OP_AND, OP_OR, OP_LSHL_ADD, OP_MED3, OP_PERMLANE32_SWAP, OP_PERMLANE16_SWAP, OP_SUM_CHAIN_PAIR, OP_SUM_CHAIN_TWO, OP_COUNT
 };
 static const char* kNames[OP_COUNT] = {
     "v_add_u32", "v_xad_u32", "v_mul_i32_i24", "v_mad_i32_i24", "v_dot2_i32_i16", "v_perm_b32", "v_alignbyte_b32",
@@ -35,7 +35,8 @@ static const char* kNames[OP_COUNT] = {
     "v_cvt_f32_f64", "ds_read_b64 (+ wait per 16)", "ds_read2_b32 (+ wait per 16)", "v_and_or_b32", "v_max_i32",
     "v_cmp_gt_i32 vcc + v_cndmask vcc (per instruction)", "v_cmp_gt_i32 s[..] + v_cndmask s[..] (per instruction)",
     "v_cmp_gt_i32_e32 (-> vcc)", "v_cmp_gt_i32_e64 (-> SGPR pair)", "v_alignbit_b32", "v_bfe_u32", "v_min_u32", "v_sub_u32",
-    "v_and_b32", "v_or_b32", "v_lshl_add_u32", "v_med3_i32",
+    "v_and_b32", "v_or_b32", "v_lshl_add_u32", "v_med3_i32", "v_permlane32_swap_b32", "v_permlane16_swap_b32",
+    "pair chain: swap+add+5 DPP (per 16)", "two chains: 12 DPP, interleaved (per 16)",
 };
 
 template <int OP>
@@ -202,6 +203,45 @@ __global__ __launch_bounds__(256) void k(unsigned* out, unsigned long long* tick
             asm volatile(REP8(D) REP8(D)
                          : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7));
 #undef D
+        } else if constexpr (OP == OP_PERMLANE32_SWAP || OP == OP_PERMLANE16_SWAP) {
+            // both operands are written: 16 swaps over the 8 registers as 4 pairs, each pair 4 times
+#define SW(op, a, b) op " %" #a ", %" #b "\n"
+#define SW16(op) SW(op, 0, 1) SW(op, 2, 3) SW(op, 4, 5) SW(op, 6, 7) SW(op, 0, 1) SW(op, 2, 3) SW(op, 4, 5) SW(op, 6, 7) \
+                 SW(op, 0, 1) SW(op, 2, 3) SW(op, 4, 5) SW(op, 6, 7) SW(op, 0, 1) SW(op, 2, 3) SW(op, 4, 5) SW(op, 6, 7)
+            if constexpr (OP == OP_PERMLANE32_SWAP)
+                asm volatile(SW16("v_permlane32_swap_b32")
+                             : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7));
+            else
+                asm volatile(SW16("v_permlane16_swap_b32")
+                             : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7));
+#undef SW16
+#undef SW
+        } else if constexpr (OP == OP_SUM_CHAIN_PAIR) {
+            // The tracker's two forms of a pair of guarded sums, as the compiler emits them, wait states included, so the two
+            // rows compare as wholes: their "cycles per instruction" are per 16, i.e. cycles of the whole form / 16.
+            // This one: swap, fold add, four row_shr steps and row_bcast:15 on ONE register (7 vector instructions).
+            asm volatile("v_permlane32_swap_b32 %0, %1\n"
+                         "v_add_u32 %0, %0, %1\n"
+                         "s_nop 1\n"
+                         "v_add_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n"
+                         "s_nop 1\n"
+                         "v_add_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0\n"
+                         "s_nop 1\n"
+                         "v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0\n"
+                         "s_nop 1\n"
+                         "v_add_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0\n"
+                         "s_nop 1\n"
+                         "v_add_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n"
+                         : "+v"(r0), "+v"(r1));
+        } else if constexpr (OP == OP_SUM_CHAIN_TWO) {
+            // ... and the six steps on each of two registers, interleaved (12 vector instructions)
+#define ST(ctrl) "v_add_u32_dpp %0, %0, %0 " ctrl "\nv_add_u32_dpp %1, %1, %1 " ctrl "\ns_nop 0\n"
+            asm volatile("s_nop 1\n"
+                         ST("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0") ST("row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:0")
+                         ST("row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:0") ST("row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:0")
+                         ST("row_bcast:15 row_mask:0xa bank_mask:0xf") ST("row_bcast:31 row_mask:0xc bank_mask:0xf")
+                         : "+v"(r0), "+v"(r1));
+#undef ST
         } else if constexpr (OP == OP_READLANE) {
             unsigned s0, s1, s2, s3, s4, s5, s6, s7;
             asm volatile(
@@ -314,6 +354,10 @@ int main()
     run<OP_FMA_F32>(d_out, d_ticks, n_cu, clock_hz);
     run<OP_PK_FMA_F32>(d_out, d_ticks, n_cu, clock_hz);
     run<OP_ADD_DPP>(d_out, d_ticks, n_cu, clock_hz);
+    run<OP_PERMLANE32_SWAP>(d_out, d_ticks, n_cu, clock_hz);
+    run<OP_PERMLANE16_SWAP>(d_out, d_ticks, n_cu, clock_hz);
+    run<OP_SUM_CHAIN_PAIR>(d_out, d_ticks, n_cu, clock_hz);
+    run<OP_SUM_CHAIN_TWO>(d_out, d_ticks, n_cu, clock_hz);
     run<OP_READLANE>(d_out, d_ticks, n_cu, clock_hz);
     run<OP_S_ADD>(d_out, d_ticks, n_cu, clock_hz);
     run<OP_DS_READ_B32>(d_out, d_ticks, n_cu, clock_hz);
