@@ -245,7 +245,7 @@ static int begin_checks(Ctx* c, int slot, int use_mask, double quality, double m
     return ICELK_OK;
 }
 
-// The job of a detection begun now.  Top-K pruning (k_corners.hip) is worthwhile when maxCorners is a real cap: only the
+// The job of a detection begun now.  Top-K pruning (k_min_distance.hip) is worthwhile when maxCorners is a real cap: only the
 // strongest candidates can be among the first maxCorners accepted ones; how many to keep follows the share that survived
 // the minDistance rule in the detection before (update_prune_factor), and relax_on_host verifies that maxCorners came out
 static DetectJob new_job(const Ctx* c, const Slot& s, int max_corners, double quality, double min_distance, size_t ncell)

@@ -395,7 +395,7 @@ bool launch_lk_pair(hipStream_t s, const LKJob& a, const LKJob& b, const LKParam
 // (Ctx::EigOut in icelk_ctx.h); a detector scratch carries a copy of the one it works on.
 struct CandBuf {
     unsigned long long* raw;   // candidate regions written by the corner kernel
-    int* blk_count;        // candidates per producer workgroup (region layout, see k_corners.hip)
+    int* blk_count;        // candidates per producer workgroup (region layout, see k_corners.hip; corner_keys.h: the keys)
     unsigned* max_key;     // 1 (order-preserving key of the masked maximum)
     // two-pass detector (k_corners_fast.hip): what its integer pass hands to its exact passes -- per tile the pixels that can
     // be a local maximum {y << 16 | x, upper bound} and those that can carry the maximum, the tile's largest upper bound,
@@ -446,7 +446,7 @@ constexpr int kTailRespBins = 4096;
 struct TailOrderGeo {   // cells of the launch order (k_tracks.hip k_seg_order): bin 0 = border features
     int cw_shift, ch_shift, cells_x, ncells, w, h, border_px;
 };
-struct TailReset {      // the counters a detection leaves zeroed for the next one of its set (k_corners.hip k_detect_reset)
+struct DetectCounters {  // the counters of a detector set: what a detection leaves zeroed for the next one (corner_keys.h reset_counters)
     int* cell_count;
     int* cell_fill;
     int ncell;
@@ -454,19 +454,19 @@ struct TailReset {      // the counters a detection leaves zeroed for the next o
     int* undecided;
     int* acc_count;
     int* cand_count;
+    unsigned* max_key;
     unsigned* key_hist;
     unsigned* prune_key;
-    int scan_chunk, chunk_stride, key_bins;
 };
 TailOrderGeo tail_order_geometry(int w, int h, int border_px);
 size_t tail_resp_words();
-TailReset tail_reset_of(DetectScratch& D, int ncell);
+DetectCounters tail_reset_of(DetectScratch& D, int ncell);   // k_min_distance.hip
 // the accepted candidates -> D.acc (what k_gather_accepted does) + their response-bin histogram, bin offsets and the verdict
 void launch_tail_gather(hipStream_t s, DetectScratch& D, int ncell, double quality, int undecided_index, int max_corners,
                         int cap, int force_status);
 // rank + corner tables of the new segment + launch order + counter reset + counts to the host, all from device-side counts
 void launch_tail_device(hipStream_t s, DetectScratch& D, double quality, float* seg_xy, uint8_t* seg_alive, float* seg_tracks,
-                        int max_vert, int* order, int* order_border, const TailOrderGeo& geo, const TailReset& rs,
+                        int max_vert, int* order, int* order_border, const TailOrderGeo& geo, const DetectCounters& rs,
                         int* host_counts, int seq);
 void launch_min_eig(hipStream_t s, const Level& img, int block_size, float* eig, const uint8_t* mask,
                     int mask_pitch, unsigned* max_key, int variant = 0);
@@ -488,7 +488,7 @@ size_t fast_key_capacity(int w, int h);
 size_t fast_regions(int w, int h);
 size_t candidate_capacity(int w, int h);   // keys the region layout needs
 size_t candidate_blocks(int w, int h);
-// minDistance < 1: candidates above the threshold, flat in D.cand / D.cand_count
+// k_min_distance.hip.  minDistance < 1: candidates above the threshold, flat in D.cand / D.cand_count
 void launch_flatten(hipStream_t s, DetectScratch& D, double quality);
 // K8: regions -> D.acc / D.acc_count (unsorted accepted keys); candidates counted in D.cell_start[ncell];
 // D.undecided[suppress_launch_count()-1] != 0 afterwards means the relaxation has not converged yet: call

@@ -18,57 +18,22 @@
 //         (k_corners_fast.hip: the same candidates in two passes, ICELK_TWO_PASS_CORNERS=1.)
 //   K6, K7 separate (k_min_eig, k_nms_collect): any other blockSize, ICELK_GENERIC_CORNERS=1 and the arithmetic
 //         variants of icelk_set_variant.
-//   K8 min distance: OpenCV accepts candidates greedily in response order.  Equivalent parallel form: a
-//         candidate is accepted iff no ACCEPTED candidate of higher priority lies closer than minDistance;
-//         relax "reject if an accepted stronger neighbour exists / accept if every stronger neighbour is
-//         rejected" to the fixed point over a cell grid of round(minDistance) px (3x3 cell search, as OpenCV's
-//         grid).  Only the accepted set is sorted (k_sort.hip).
+//   K8, the selection among these candidates (min distance, top-K pruning, the corner list): k_min_distance.hip.
 // Candidates live in per-workgroup regions (region b = the local maxima of a 16-row band of a strip, or of a workgroup's
 // band of k_nms_collect; count in blk_count[b]):
 // no single-address atomics anywhere on the image-sized passes (one word saturates at ~90 atomics/us on
 // gfx950), and the masked maximum is published with a read-guarded atomicMax.
-// The whole detection is enqueued without host round trips; the host synchronises once, to learn the
-// number of accepted corners.
+// The key format, the quality threshold and the constants the stages share: corner_keys.h.
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
 
-#include "icelk_internal.h"
+#include "corner_keys.h"
 #include "strip_sqrt.h"
 
 namespace icelk {
 
 namespace {
-
-__device__ __forceinline__ int reflect101(int p, int n)
-{
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) p = p < 0 ? -p : 2 * n - 2 - p;
-    return p;
-}
-
-// order-preserving map float -> uint32 (larger float <=> larger key); 0 is below every float
-__device__ __forceinline__ unsigned ordered_key(float v)
-{
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_to_float(unsigned k)
-{
-    const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(b);
-}
-
-// low half of a candidate key: (y << 16) | x orders exactly like the raster address y*w + x (the tie-break of
-// OpenCV's greaterThanPtr) and needs no division to unpack; frames are < 65536 px on either side
-__device__ __forceinline__ unsigned pack_xy(int x, int y) { return ((unsigned)y << 16) | (unsigned)x; }
-
-__device__ __forceinline__ float threshold_of(const unsigned* max_key, double quality)
-{
-    const unsigned mk = *max_key;
-    const double max_val = mk ? (double)key_to_float(mk) : 0.0;
-    return (float)(max_val * quality);
-}
 
 // Sobel (ksize 3) pair scaled as cornerEigenValsVecs does, in OpenCV's operation order:
 //   Dx: row pass [-1 0 1] (exact), column pass (r0 + r2)*k1 + r1*k0
@@ -165,14 +130,6 @@ __device__ __forceinline__ void publish_max(unsigned* max_key, unsigned best, in
     }
     if ((tid & 63) == 0 && best > __atomic_load_n(max_key, __ATOMIC_RELAXED)) atomicMax(max_key, best);
 }
-
-// Candidate source: nblk regions of `region` keys each, blk_count[b] valid keys in region b.
-struct CandSrc {
-    const unsigned long long* keys;
-    const int* blk_count;
-    int nblk;
-    int region;
-};
 
 // ------------------------------------------------------------------------------------------------
 // K6+K7 in STRIPS (round 3; blockSize 3/5/7/10).  Round 2's tile kernel (removed) paid for its 64x16 tile twice: the Sobel
@@ -472,8 +429,7 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
                         if (mask && !mask[(size_t)y * mask_pitch + x]) continue;
                         const int sub = (c - 1) / C::SUB;
                         const int pos = atomicAdd(&s_cnt[sub], 1);
-                        raw[((size_t)bid * C::NSUB + sub) * (C::TW * C::SUB) + pos] =
-                            ((unsigned long long)ordered_key(v) << 32) | pack_xy(x, y);
+                        raw[((size_t)bid * C::NSUB + sub) * (C::TW * C::SUB) + pos] = cand_key(v, x, y);
                     }
                 }
             }
@@ -522,41 +478,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
         strip_body<BS, false, false>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
     else
         strip_body<BS, true, false>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
-}
-
-// workgroup-aggregated append: every thread offers at most one key per call; one global atomic per call
-__device__ __forceinline__ void block_append(bool keep, unsigned long long key, unsigned long long* out,
-                                             int* out_count, int* s_cnt, int* s_base)
-{
-    if (threadIdx.x == 0) *s_cnt = 0;
-    __syncthreads();
-    const int pos = keep ? atomicAdd(s_cnt, 1) : 0;
-    __syncthreads();
-    if (threadIdx.x == 0 && *s_cnt) *s_base = atomicAdd(out_count, *s_cnt);
-    __syncthreads();
-    if (keep) out[*s_base + pos] = key;
-    __syncthreads();
-}
-
-// regions -> flat list of the candidates above max * qualityLevel (minDistance < 1 path: everything is sorted)
-__global__ __launch_bounds__(256) void k_flatten(CandSrc src, const unsigned* __restrict__ max_key, double quality,
-                                                 unsigned long long* __restrict__ cand, int* __restrict__ cand_count)
-{
-    __shared__ int s_cnt, s_base;
-    const float thr = threshold_of(max_key, quality);
-    for (int b = blockIdx.x; b < src.nblk; b += gridDim.x) {
-        const int cnt = src.blk_count[b];
-        for (int i0 = 0; i0 < cnt; i0 += 256) {
-            const int i = i0 + threadIdx.x;
-            unsigned long long key = 0;
-            bool keep = false;
-            if (i < cnt) {
-                key = src.keys[(size_t)b * src.region + i];
-                keep = key_to_float((unsigned)(key >> 32)) > thr;
-            }
-            block_append(keep, key, cand, cand_count, &s_cnt, &s_base);
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -661,370 +582,22 @@ __global__ __launch_bounds__(256) void k_nms_collect(const float* __restrict__ e
                 m = q > m ? q : m;
             }
         if (v != m) continue;
-        region[atomicAdd(&list_n, 1)] = ((unsigned long long)ordered_key(v) << 32) | pack_xy(x, y);
+        region[atomicAdd(&list_n, 1)] = cand_key(v, x, y);
     }
     __syncthreads();
     if (tid == 0) blk_count[bid] = list_n;
 }
 
-// ------------------------------------------------------------------------------------------------
-// K8 helpers.
-// Every kernel of the min-distance stage is launched as ONE-WAVE workgroups (CT = 64 threads) with at most 8 KB of
-// LDS and no more than 128 VGPRs: that is the footprint of a single k_lk_fast wave, so while a tracker launch
-// owns the chip (it holds every VGPR) such a workgroup fits into the hole any retiring tracker wave leaves and
-// the stage progresses beside it; wider workgroups wait for the tracker's tail (tools/ubench/corun.hip:
-// 64 threads / 4 KB LDS 30-60 us beside a register-saturating kernel, >= 128 threads or 16 KB 250-340 us).
-// ------------------------------------------------------------------------------------------------
-constexpr int CT = 64;
-constexpr int SCAN_CHUNK = 2048;   // cells per workgroup of k_scan; k_cell_count also keeps per-chunk totals
-// The chunk totals are hot atomic targets: one per 128-byte line (atomics on one line serialise in its L2 channel,
-// ~90 per us), and a wave adds its contributions to a chunk with one atomic.
-constexpr int CHUNK_TOT_STRIDE = 32;
-
-__device__ __forceinline__ void chunk_add(int* __restrict__ chunk_tot, bool active, int chunk)
-{
-    unsigned long long pending = __ballot(active);
-    while (pending) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const int c = __shfl(chunk, leader);
-        const unsigned long long same = __ballot(active && chunk == c) & pending;
-        if ((int)threadIdx.x == leader) atomicAdd(&chunk_tot[c * CHUNK_TOT_STRIDE], __popcll(same));
-        pending &= ~same;
-    }
-}
-
-__global__ __launch_bounds__(CT) void k_cell_count(CandSrc src, const unsigned* __restrict__ max_key, double quality,
-                                                   const unsigned* __restrict__ prune_key, int w, int cell, int gw,
-                                                   int* __restrict__ cell_count, int* __restrict__ chunk_tot)
-{
-    const float thr = threshold_of(max_key, quality);
-    const unsigned pk = *prune_key;
-    for (int b = blockIdx.x; b < src.nblk; b += gridDim.x) {
-        const int cnt = src.blk_count[b];
-        for (int i0 = 0; i0 < cnt; i0 += CT) {
-            const int i = i0 + threadIdx.x;
-            bool keep = false;
-            int c = 0;
-            if (i < cnt) {
-                const unsigned long long key = src.keys[(size_t)b * src.region + i];
-                keep = (unsigned)(key >> 32) >= pk && key_to_float((unsigned)(key >> 32)) > thr;
-                const unsigned idx = (unsigned)key;
-                const int y = (int)(idx >> 16), x = (int)(idx & 0xffffu);
-                c = (y / cell) * gw + (x / cell);
-            }
-            if (keep) atomicAdd(&cell_count[c], 1);
-            chunk_add(chunk_tot, keep, c / SCAN_CHUNK);
-        }
-    }
-}
-
-// ---- top-K pruning when maxCorners caps the output ------------------------------------------------
-// Whether a candidate is accepted depends only on STRONGER candidates, so the accepted candidates among the K
-// strongest are exactly the greedy-accepted ones among them; if they number >= maxCorners, the weaker
-// candidates can never appear in the output and need not be binned, relaxed or sorted.  K is found from a
-// 16384-bin histogram of the response key (its top 14 bits); the host checks "accepted >= maxCorners" at its
-// one synchronisation point and reruns unpruned otherwise.
-constexpr int KEY_SHIFT = 18;                 // bin width: sign, exponent and 5 mantissa bits of the key
-constexpr int KEY_BINS = 2048;                // bins counted DOWN from the bin of the maximum: 64 octaves
-// Responses cluster in a few hundred bins, so a global-memory histogram would serialise on a handful of L2
-// atomic addresses: every workgroup histograms into LDS (8 KB) and flushes its non-empty bins.
-__device__ __forceinline__ int key_bin(unsigned key, unsigned max_key)
-{
-    const int b = (int)(max_key >> KEY_SHIFT) - (int)(key >> KEY_SHIFT);
-    return b < 0 ? 0 : (b >= KEY_BINS ? KEY_BINS - 1 : b);
-}
-
-__global__ __launch_bounds__(CT) void k_key_hist(CandSrc src, const unsigned* __restrict__ max_key, double quality,
-                                                 unsigned* __restrict__ hist)
-{
-    __shared__ unsigned lh[KEY_BINS];
-    for (int i = threadIdx.x; i < KEY_BINS; i += CT) lh[i] = 0;
-    __syncthreads();
-    const float thr = threshold_of(max_key, quality);
-    const unsigned mk = *max_key;
-    for (int b = blockIdx.x; b < src.nblk; b += gridDim.x) {
-        const int cnt = src.blk_count[b];
-        for (int i = threadIdx.x; i < cnt; i += CT) {
-            const unsigned k = (unsigned)(src.keys[(size_t)b * src.region + i] >> 32);
-            if (key_to_float(k) > thr) atomicAdd(&lh[key_bin(k, mk)], 1u);
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < KEY_BINS; i += CT) {
-        const unsigned v = lh[i];
-        if (v) atomicAdd(&hist[i], v);
-    }
-}
-
-// prune_key = lowest key of the strongest bins that together hold >= want candidates (0 = keep everything).
-// One wave; lane l owns bins [32 l, 32 l + 32), bin 0 being the strongest.
-__global__ __launch_bounds__(CT) void k_key_select(const unsigned* __restrict__ hist, unsigned want,
-                                                   const unsigned* __restrict__ max_key,
-                                                   unsigned* __restrict__ prune_key)
-{
-    constexpr int PER = KEY_BINS / CT;
-    const int lane = threadIdx.x;
-    unsigned s = 0;
-    for (int i = 0; i < PER; i++) s += hist[lane * PER + i];
-    unsigned incl = s;   // candidates in this lane's bins and all stronger ones
-#pragma unroll
-    for (int o = 1; o < CT; o <<= 1) {
-        const unsigned v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-    }
-    const unsigned total = __shfl(incl, CT - 1);
-    if (lane == 0 && total < want) *prune_key = 0u;
-    const unsigned above = incl - s;
-    if (above < want && incl >= want) {
-        unsigned run = above;
-        for (int i = 0; i < PER; i++) {
-            run += hist[lane * PER + i];
-            if (run >= want) {
-                const int bin = lane * PER + i;   // keep bins 0..bin
-                const int top = (int)(*max_key >> KEY_SHIFT);
-                // the last bin also collects everything weaker: keeping it means keeping all
-                *prune_key = (bin >= KEY_BINS - 1 || top - bin <= 0) ? 0u : (unsigned)(top - bin) << KEY_SHIFT;
-                break;
-            }
-        }
-    }
-}
-
-// exclusive scan of the cell counts, SCAN_CHUNK cells per one-wave workgroup: the offset of a chunk is the sum of the
-// chunk totals before it (kept by k_cell_count), inside the chunk 8 rounds of 4 cells per lane.  start[n] = total.
-__global__ __launch_bounds__(CT) void k_scan(const int* __restrict__ count, const int* __restrict__ chunk_tot,
-                                             int* __restrict__ start, int n)
-{
-    const int lane = threadIdx.x;
-    const int lo = blockIdx.x * SCAN_CHUNK;
-    int run = 0;
-    for (int c = lane; c < (int)blockIdx.x; c += CT) run += chunk_tot[c * CHUNK_TOT_STRIDE];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) run += __shfl_xor(run, o);
-    for (int r = 0; r < SCAN_CHUNK / (4 * CT); r++) {
-        const int i0 = lo + r * 4 * CT + 4 * lane;
-        int c[4], s = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            c[k] = i0 + k < n ? count[i0 + k] : 0;
-            s += c[k];
-        }
-        int inc = s;
-#pragma unroll
-        for (int o = 1; o < CT; o <<= 1) {
-            const int v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
-        int at = run + inc - s;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (i0 + k < n) start[i0 + k] = at;
-            at += c[k];
-            if (i0 + k == n - 1) start[n] = at;
-        }
-        run += __shfl(inc, CT - 1);
-    }
-    if (n == 0 && blockIdx.x == 0 && lane == 0) start[0] = 0;
-}
-
-__global__ __launch_bounds__(CT) void k_cell_fill(CandSrc src, const unsigned* __restrict__ max_key, double quality,
-                                                   const unsigned* __restrict__ prune_key, int w, int cell, int gw,
-                                                   const int* __restrict__ cell_start, int* __restrict__ cell_fill,
-                                                   unsigned long long* __restrict__ cell_cand,
-                                                   uint8_t* __restrict__ state)
-{
-    const float thr = threshold_of(max_key, quality);
-    const unsigned pk = *prune_key;
-    for (int b = blockIdx.x; b < src.nblk; b += gridDim.x) {
-        const int cnt = src.blk_count[b];
-        for (int i = threadIdx.x; i < cnt; i += CT) {
-            const unsigned long long key = src.keys[(size_t)b * src.region + i];
-            if ((unsigned)(key >> 32) < pk || !(key_to_float((unsigned)(key >> 32)) > thr)) continue;
-            const unsigned idx = (unsigned)key;
-            const int y = (int)(idx >> 16), x = (int)(idx & 0xffffu);
-            const int c = (y / cell) * gw + (x / cell);
-            const int pos = cell_start[c] + atomicAdd(&cell_fill[c], 1);
-            cell_cand[pos] = key;
-            state[pos] = 0;
-        }
-    }
-}
-
-// Relaxation.  A thread owns one candidate.  Its first look scans the 3x3 cells and keeps the indices of the
-// stronger candidates within minDistance that are still undecided (its "blockers") in LDS; after that it only
-// polls those.  States are read and written with L1-bypassing (system-scope relaxed) accesses and only ever
-// move 0 -> 1 or 0 -> 2 on final facts, so progress made by other workgroups is seen as it happens and a stale
-// read merely costs another poll.  Spins are bounded; launch_counters[r] = candidates still undecided after
-// launch r, and launch r+1 picks them up (it returns at once when that count is zero).
-constexpr int SUP_K = 24;
-constexpr int SUP_SPINS = 48;
-__global__ __launch_bounds__(CT) void k_suppress(const unsigned long long* __restrict__ cell_cand,
-                                                  const int* __restrict__ n_ptr, int cell, int gw, int gh,
-                                                  const int* __restrict__ cell_start, uint8_t* state, double md2,
-                                                  int* __restrict__ launch_counters, int r)
-{
-    __shared__ int blockers[SUP_K * CT];
-    if (r > 0 && launch_counters[r - 1] == 0) return;
-    const int n = *n_ptr;
-    int* mine = blockers + threadIdx.x;   // entry q at mine[q * CT]: conflict-free
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        if (__atomic_load_n(&state[i], __ATOMIC_RELAXED)) continue;
-        const unsigned long long key = cell_cand[i];
-        const unsigned idx = (unsigned)key;
-        const int y = (int)(idx >> 16), x = (int)(idx & 0xffffu);
-        const int xc = x / cell, yc = y / cell;
-        const int x1 = max(0, xc - 1), y1 = max(0, yc - 1), x2 = min(gw - 1, xc + 1), y2 = min(gh - 1, yc + 1);
-        int cnt = 0;
-        bool rejected = false, overflow = false;
-        for (int yy = y1; yy <= y2 && !rejected; yy++) {
-            const int b = cell_start[yy * gw + x1], e = cell_start[yy * gw + x2 + 1];  // the 3 cells are contiguous
-            for (int j = b; j < e; j++) {
-                const unsigned long long kj = cell_cand[j];
-                if (kj <= key) continue;  // only stronger candidates matter (keys are unique)
-                const unsigned ij = (unsigned)kj;
-                const int yj = (int)(ij >> 16), xj = (int)(ij & 0xffffu);
-                const float dx = (float)(x - xj), dy = (float)(y - yj);
-                if (!((double)(dx * dx + dy * dy) < md2)) continue;
-                const uint8_t sj = __atomic_load_n(&state[j], __ATOMIC_RELAXED);
-                if (sj == 1) { rejected = true; break; }
-                if (sj == 0) {
-                    if (cnt < SUP_K) mine[CT * cnt++] = j;
-                    else overflow = true;
-                }
-            }
-        }
-        bool decided = false;
-        if (rejected) { __atomic_store_n(&state[i], (uint8_t)2, __ATOMIC_RELAXED); decided = true; }
-        else if (cnt == 0 && !overflow) { __atomic_store_n(&state[i], (uint8_t)1, __ATOMIC_RELAXED); decided = true; }
-        for (int spin = 0; spin < SUP_SPINS && !decided && !overflow; spin++) {
-            __builtin_amdgcn_s_sleep(8);
-            int k = 0;
-            for (int q = 0; q < cnt; q++) {
-                const int j = mine[CT * q];
-                const uint8_t sj = __atomic_load_n(&state[j], __ATOMIC_RELAXED);
-                if (sj == 1) { rejected = true; break; }
-                if (sj == 0) mine[CT * k++] = j;
-            }
-            cnt = k;
-            if (rejected) { __atomic_store_n(&state[i], (uint8_t)2, __ATOMIC_RELAXED); decided = true; }
-            else if (cnt == 0) { __atomic_store_n(&state[i], (uint8_t)1, __ATOMIC_RELAXED); decided = true; }
-        }
-        if (!decided) atomicAdd(&launch_counters[r], 1);
-    }
-}
-
-// zero every counter a detection uses, in one launch (each hipMemsetAsync is a ~5 us kernel of its own)
-__global__ void k_detect_reset(int* __restrict__ cell_count, int* __restrict__ cell_fill, int ncell,
-                               int* __restrict__ chunk_tot, int* __restrict__ undecided, int* __restrict__ acc_count,
-                               int* __restrict__ cand_count, unsigned* __restrict__ max_key,
-                               unsigned* __restrict__ key_hist, unsigned* __restrict__ prune_key, int full)
-{
-    const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
-    for (int i = i0; i <= ncell; i += gridDim.x * blockDim.x) {
-        cell_count[i] = 0;
-        if (i < ncell) cell_fill[i] = 0;
-        if (i % SCAN_CHUNK == 0) chunk_tot[(i / SCAN_CHUNK) * CHUNK_TOT_STRIDE] = 0;
-    }
-    if (full & 1)
-        for (int i = i0; i < KEY_BINS; i += gridDim.x * blockDim.x) key_hist[i] = 0;
-    if (i0 < 8) undecided[i0] = 0;
-    if (i0 == 0) {
-        *acc_count = 0;
-        *cand_count = 0;
-        *prune_key = 0;
-        if (full & 2) *max_key = 0;
-    }
-}
-
-__global__ __launch_bounds__(CT) void k_gather_accepted(const unsigned long long* __restrict__ cell_cand,
-                                                         const int* __restrict__ n_ptr,
-                                                         const uint8_t* __restrict__ state,
-                                                         unsigned long long* __restrict__ acc,
-                                                         int* __restrict__ acc_count)
-{
-    __shared__ int s_cnt, s_base;
-    const int n = *n_ptr;
-    for (int i0 = blockIdx.x * CT; i0 < n; i0 += gridDim.x * CT) {
-        const int i = i0 + threadIdx.x;
-        const bool keep = i < n && state[i] == 1;
-        block_append(keep, keep ? cell_cand[i] : 0ull, acc, acc_count, &s_cnt, &s_base);
-    }
-}
-
-__global__ void k_emit(const unsigned long long* __restrict__ keys, int n, int w, float* __restrict__ xy)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned idx = (unsigned)keys[i];
-    const int y = (int)(idx >> 16), x = (int)(idx & 0xffffu);
-    xy[2 * i] = (float)x;
-    xy[2 * i + 1] = (float)y;
-}
-
-// The tail of a detection whose corners start a segment, in ONE launch instead of three (k_emit, k_detect_reset,
-// k_seg_init): every launch of the tail has to find room beside a tracker launch -- or beside a corner kernel that has the
-// chip to itself -- and the next tracker launch waits for the last of them.  Blocks [0, emit_blocks): corner i from its
-// sorted key -> the corner list AND the new segment's tables (position, alive flag, vertex 0 of its track); the blocks
-// behind them: the counters of the detector set for its next detection (mode as launch_detect_reset).
-__global__ __launch_bounds__(CT) void k_tail(const unsigned long long* __restrict__ keys, int n, float* __restrict__ corners,
-                                             float* __restrict__ seg_xy, uint8_t* __restrict__ seg_alive,
-                                             float* __restrict__ seg_tracks, int max_vert, int emit_blocks,
-                                             int* __restrict__ cell_count, int* __restrict__ cell_fill, int ncell,
-                                             int* __restrict__ chunk_tot, int* __restrict__ undecided,
-                                             int* __restrict__ acc_count, int* __restrict__ cand_count,
-                                             unsigned* __restrict__ max_key, unsigned* __restrict__ key_hist,
-                                             unsigned* __restrict__ prune_key, int full)
-{
-    if ((int)blockIdx.x < emit_blocks) {
-        const int i = blockIdx.x * CT + threadIdx.x;
-        if (i >= n) return;
-        const unsigned idx = (unsigned)keys[i];
-        const float x = (float)(int)(idx & 0xffffu), y = (float)(int)(idx >> 16);
-        corners[2 * i] = x; corners[2 * i + 1] = y;
-        seg_xy[2 * i] = x; seg_xy[2 * i + 1] = y;
-        seg_alive[i] = 1;
-        seg_tracks[((size_t)i * max_vert) * 2] = x;
-        seg_tracks[((size_t)i * max_vert) * 2 + 1] = y;
-        return;
-    }
-    const int i0 = ((int)blockIdx.x - emit_blocks) * CT + threadIdx.x, stride = ((int)gridDim.x - emit_blocks) * CT;
-    for (int i = i0; i <= ncell; i += stride) {
-        cell_count[i] = 0;
-        if (i < ncell) cell_fill[i] = 0;
-        if (i % SCAN_CHUNK == 0) chunk_tot[(i / SCAN_CHUNK) * CHUNK_TOT_STRIDE] = 0;
-    }
-    if (full & 1)
-        for (int i = i0; i < KEY_BINS; i += stride) key_hist[i] = 0;
-    if (i0 < 8) undecided[i0] = 0;
-    if (i0 == 0) {
-        *acc_count = 0;
-        *cand_count = 0;
-        *prune_key = 0;
-        if (full & 2) *max_key = 0;
-    }
-}
-
-void sobel_scale(int block_size, float* k0, float* k1)
-{
-    double scale = (double)(1 << 2) * block_size;
-    scale *= 255.0;
-    scale = 1.0 / scale;
-    *k1 = (float)(1.0 * scale);
-    *k0 = (float)(2.0 * scale);
-}
-
 template <int BS>
-void launch_strip(hipStream_t s, const Level& img, float k0, float k1, const uint8_t* mask, int mask_pitch,
-                  unsigned* max_key, unsigned long long* raw, int* blk_count, float* eig_out, CandSrc* src)
+void launch_strip(hipStream_t s, const Level& img, float k0, float k1, const uint8_t* mask, int mask_pitch, CandBuf& cb,
+                  float* eig_out)
 {
     using C = StripCfg<BS>;
     dim3 grid((img.w + C::TW - 1) / C::TW, (img.h + C::SH - 1) / C::SH);
     hipLaunchKernelGGL((k_eig_strip<BS>), grid, dim3(C::NT), C::LDS_BYTES, s, img.ptr, img.w, img.h, img.pitch, k0, k1, mask,
-                       mask_pitch, max_key, raw, blk_count, eig_out);
-    src->nblk = (int)(grid.x * grid.y) * C::NSUB;
-    src->region = C::TW * C::SUB;
-    src->keys = raw;
-    src->blk_count = blk_count;
+                       mask_pitch, cb.max_key, cb.raw, cb.blk_count, eig_out);
+    cb.nblk = (int)(grid.x * grid.y) * C::NSUB;
+    cb.region = C::TW * C::SUB;
 }
 
 // regions / keys the strip layout needs, whichever blockSize is asked for later
@@ -1094,35 +667,11 @@ void launch_min_eig(hipStream_t s, const Level& img, int block_size, float* eig,
                        mask, mask_pitch, max_key, variant);
 }
 
-static CandSrc src_of(const DetectScratch& D)
-{
-    CandSrc c;
-    c.keys = D.cb.raw;
-    c.blk_count = D.cb.blk_count;
-    c.nblk = D.cb.nblk;
-    c.region = D.cb.region;
-    return c;
-}
-
-// First launch of every detection: zero the counters (ncell = 0 when minDistance < 1).
-// full = also the response maximum and the key histogram (i.e. everything a NEW detection needs); !full = only
-// what a re-run of the min-distance stage on the same candidates needs.
-void launch_detect_reset(hipStream_t s, DetectScratch& D, int ncell, int mode)
-{
-    int blocks = (ncell + CT) / CT;
-    if ((mode & 1) && blocks < KEY_BINS / CT) blocks = KEY_BINS / CT;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_detect_reset, dim3(blocks), dim3(CT), 0, s, D.cell_count, D.cell_fill, ncell, D.chunk_tot, D.undecided,
-                       D.acc_count, D.cand_count, D.cb.max_key, D.key_hist, D.prune_key, mode);
-}
-
 // Candidate collection (K6+K7) into regions of D.cb.raw (stream order, no host sync).
 void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int block_size, const uint8_t* mask,
                        int mask_pitch, double quality, bool use_generic, float* eig_out_or_null, int variant)
 {
     if (variant) use_generic = true;     // the named variants live in the any-blockSize kernel only
-    unsigned long long* raw = D.cb.raw;
-    CandSrc g_src{};
     // ICELK_TWO_PASS_CORNERS=1: the two-pass form (k_corners_fast.hip: integer bracket of the map + exact arithmetic at the
     // possible maxima) -- a third statement of the arithmetic, bit-identical, measured and not the default
     const bool two_pass = D.cb.acand != nullptr && getenv("ICELK_TWO_PASS_CORNERS") != nullptr;   // scratch: at icelk_create, under the same switch
@@ -1133,127 +682,22 @@ void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int bl
         float k0, k1;
         sobel_scale(block_size, &k0, &k1);
         switch (block_size) {
-            case 3: launch_strip<3>(s, img, k0, k1, mask, mask_pitch, D.cb.max_key, raw, D.cb.blk_count, eig_out_or_null, &g_src); break;
-            case 5: launch_strip<5>(s, img, k0, k1, mask, mask_pitch, D.cb.max_key, raw, D.cb.blk_count, eig_out_or_null, &g_src); break;
-            case 7: launch_strip<7>(s, img, k0, k1, mask, mask_pitch, D.cb.max_key, raw, D.cb.blk_count, eig_out_or_null, &g_src); break;
-            default: launch_strip<10>(s, img, k0, k1, mask, mask_pitch, D.cb.max_key, raw, D.cb.blk_count, eig_out_or_null, &g_src); break;
+            case 3: launch_strip<3>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null); break;
+            case 5: launch_strip<5>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null); break;
+            case 7: launch_strip<7>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null); break;
+            default: launch_strip<10>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null); break;
         }
     } else {
         launch_min_eig(s, img, block_size, D.eig, mask, mask_pitch, D.cb.max_key, variant);
-        g_src.keys = raw;
-        g_src.blk_count = D.cb.blk_count;
-        g_src.nblk = 0;
-        g_src.region = 256 * NMS_ROWS;
+        D.cb.nblk = 0;
+        D.cb.region = 256 * NMS_ROWS;
         if (img.w >= 3 && img.h >= 3) {
             const dim3 grid = nms_grid(img.w, img.h);
             hipLaunchKernelGGL(k_nms_collect, grid, dim3(256), 0, s, D.eig, img.w, img.h, mask, mask_pitch, D.cb.max_key,
-                               quality, raw, D.cb.blk_count);
-            g_src.nblk = (int)(grid.x * grid.y);
+                               quality, D.cb.raw, D.cb.blk_count);
+            D.cb.nblk = (int)(grid.x * grid.y);
         }
     }
-    D.cb.nblk = g_src.nblk;
-    D.cb.region = g_src.region;
-}
-
-// minDistance < 1: every candidate above the threshold, flat in D.cand / D.cand_count
-void launch_flatten(hipStream_t s, DetectScratch& D, double quality)
-{
-    hipLaunchKernelGGL(k_flatten, dim3(512), dim3(256), 0, s, src_of(D), D.cb.max_key, quality, D.cand, D.cand_count);
-}
-
-// Greedy-equivalent min-distance selection, fully enqueued (no host round trip): candidate regions ->
-// D.acc (unsorted accepted keys), D.acc_count; the number of thresholded candidates ends in
-// D.cell_start[ncell].  D.undecided[kSuppressLaunches-1] != 0 afterwards means "not converged, call
-// continue_min_distance".
-// Three launches since round 4 (two before): one detection in a hundred left one or two candidates undecided after the
-// second (their blockers were decided in the same launch, after the last poll) and went through the host's tail
-// (detect_finish: more launches, a host round trip each, rocPRIM's sort) instead of the device's -- 300 us, and 8 ms the
-// first time in a process (profiles/r04_c3_stall.txt).  A third launch picks up what the second left and returns at once
-// when that is nothing; the follow-up launches use a small grid (a handful of candidates, every workgroup scans the list).
-constexpr int kSuppressLaunches = 3;
-static void suppress_launches(hipStream_t s, DetectScratch& D, int w, int h, double min_distance)
-{
-    const int cell = (int)lrint(min_distance);
-    const int gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
-    const double md2 = min_distance * min_distance;
-    for (int r = 0; r < kSuppressLaunches; r++)
-        hipLaunchKernelGGL(k_suppress, dim3(r < 2 ? 4096 : 512), dim3(CT), 0, s, D.cell_cand, D.cell_start + gw * gh, cell, gw, gh,
-                           D.cell_start, D.state, md2, D.undecided, r);
-}
-
-static void gather_launch(hipStream_t s, DetectScratch& D, int ncell)
-{
-    hipLaunchKernelGGL(k_gather_accepted, dim3(1024), dim3(CT), 0, s, D.cell_cand, D.cell_start + ncell, D.state, D.acc,
-                       D.acc_count);
-}
-
-TailReset tail_reset_of(DetectScratch& D, int ncell)
-{
-    TailReset r{};
-    r.cell_count = D.cell_count;
-    r.cell_fill = D.cell_fill;
-    r.ncell = ncell;
-    r.chunk_tot = D.chunk_tot;
-    r.undecided = D.undecided;
-    r.acc_count = D.acc_count;
-    r.cand_count = D.cand_count;
-    r.key_hist = D.key_hist;
-    r.prune_key = D.prune_key;
-    r.scan_chunk = SCAN_CHUNK;
-    r.chunk_stride = CHUNK_TOT_STRIDE;
-    r.key_bins = KEY_BINS;
-    return r;
-}
-
-void launch_min_distance(hipStream_t s, DetectScratch& D, int w, int h, double min_distance, double quality,
-                         int prune_want, bool no_gather)
-{
-    const int cell = (int)lrint(min_distance);
-    const int gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
-    const int ncell = gw * gh;
-    if (prune_want > 0) {
-        hipLaunchKernelGGL(k_key_hist, dim3(256), dim3(CT), 0, s, src_of(D), D.cb.max_key, quality, D.key_hist);
-        hipLaunchKernelGGL(k_key_select, dim3(1), dim3(CT), 0, s, D.key_hist, (unsigned)prune_want, D.cb.max_key, D.prune_key);
-    }
-    hipLaunchKernelGGL(k_cell_count, dim3(4096), dim3(CT), 0, s, src_of(D), D.cb.max_key, quality, D.prune_key, w, cell, gw,
-                       D.cell_count, D.chunk_tot);
-    hipLaunchKernelGGL(k_scan, dim3((ncell + SCAN_CHUNK - 1) / SCAN_CHUNK), dim3(CT), 0, s, D.cell_count, D.chunk_tot,
-                       D.cell_start, ncell);
-    hipLaunchKernelGGL(k_cell_fill, dim3(4096), dim3(CT), 0, s, src_of(D), D.cb.max_key, quality, D.prune_key, w, cell, gw,
-                       D.cell_start, D.cell_fill, D.cell_cand, D.state);
-    suppress_launches(s, D, w, h, min_distance);
-    if (!no_gather) gather_launch(s, D, ncell);
-}
-
-// more relaxation launches + a fresh gather (only when the first batch left candidates undecided)
-void continue_min_distance(hipStream_t s, DetectScratch& D, int w, int h, double min_distance)
-{
-    const int cell = (int)lrint(min_distance);
-    const int ncell = ((w + cell - 1) / cell) * ((h + cell - 1) / cell);
-    hipMemsetAsync(D.undecided, 0, sizeof(int) * 8, s);
-    hipMemsetAsync(D.acc_count, 0, sizeof(int), s);
-    suppress_launches(s, D, w, h, min_distance);
-    gather_launch(s, D, ncell);
-}
-
-int suppress_launch_count() { return kSuppressLaunches; }
-
-void launch_tail_fused(hipStream_t s, const unsigned long long* keys, int n, float* corners, float* seg_xy,
-                       uint8_t* seg_alive, float* seg_tracks, int max_vert, DetectScratch& D, int ncell, int mode)
-{
-    const int emit_blocks = (n + CT - 1) / CT;
-    int blocks = (ncell + CT) / CT;
-    if ((mode & 1) && blocks < KEY_BINS / CT) blocks = KEY_BINS / CT;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_tail, dim3(emit_blocks + blocks), dim3(CT), 0, s, keys, n, corners, seg_xy, seg_alive, seg_tracks,
-                       max_vert, emit_blocks, D.cell_count, D.cell_fill, ncell, D.chunk_tot, D.undecided, D.acc_count,
-                       D.cand_count, D.cb.max_key, D.key_hist, D.prune_key, mode);
-}
-
-void launch_emit_corners(hipStream_t s, const unsigned long long* keys, int n, int w, float* xy)
-{
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_emit, dim3((n + CT - 1) / CT), dim3(CT), 0, s, keys, n, w, xy);
 }
 
 }  // namespace icelk

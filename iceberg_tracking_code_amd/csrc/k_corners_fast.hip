@@ -51,6 +51,7 @@
 //   T = 0 (all derivatives of the window zero) means v = 0 exactly.  The tests compare the result with the one-pass kernel
 //   and with the oracle on every image they use, incl. the full BASELINE frames (tests/test_gpu_fullsize_oracle.py).
 #include "lk_fast_tiles.h"
+#include "corner_keys.h"   // behind lk_fast_tiles.h: that header's own calls of lk::reflect101 must not see a second one
 
 namespace icelk {
 
@@ -69,13 +70,6 @@ static_assert(FT_TH == 4 * FT_RY, "four waves cover the tile");
 
 constexpr float EPS_SQRT = 1.25e-3f, EPS_LIN = 1.0e-6f, EPS_N = 1.0e-6f;
 
-__device__ __forceinline__ int reflect101c(int p, int n)
-{
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) p = p < 0 ? -p : 2 * n - 2 - p;
-    return p;
-}
-
 // BORDER_REFLECT_101 runs through an image of n samples with period 2n - 2; on the odd half-periods it runs backwards.
 // A derivative formed on the reflected SAMPLES at such a position is the negative of the derivative AT the reflected
 // position (the smoothing taps are symmetric, so the other derivative is unchanged) -- and OpenCV's box filter reflects
@@ -87,17 +81,6 @@ __device__ __forceinline__ bool reflect_backwards(int p, int n)
     int q = p % period;
     if (q < 0) q += period;
     return q > n - 1;
-}
-
-__device__ __forceinline__ unsigned ordered_key_f(float v)
-{
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_to_float_f(unsigned k)
-{
-    const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(b);
 }
 
 __device__ __forceinline__ void atomic_max_guarded(unsigned* p, unsigned v)
@@ -242,7 +225,7 @@ __global__ __launch_bounds__(256) void k_eig_approx(const uint8_t* __restrict__ 
         uint8_t* Ub = reinterpret_cast<uint8_t*>(U);
         for (int i = tid; i < C::UW * C::UH; i += 256) {
             const int r = i / C::UW, c = i - r * C::UW;
-            Ub[r * C::UPD * 4 + cs + c] = img[(size_t)reflect101c(uy0 + r, h) * pitch + reflect101c(ux0 + c, w)];
+            Ub[r * C::UPD * 4 + cs + c] = img[(size_t)reflect101(uy0 + r, h) * pitch + reflect101(ux0 + c, w)];
         }
     }
     __syncthreads();
@@ -340,10 +323,10 @@ __global__ __launch_bounds__(256) void k_eig_approx(const uint8_t* __restrict__ 
         for (int k = 2; k <= FT_RY; k++) e = i == k ? E[k] : e;
         if ((sure >> i) & 1u) e = -e;          // the sign carries the flag (the bound itself is > 0)
         const int pos = atomicAdd(&s_ncand, 1);
-        if (pos < FT_CAP) acand[(size_t)tile * FT_CAP + pos] = make_uint2(((unsigned)(yb + i) << 16) | (unsigned)x, __float_as_uint(e));
+        if (pos < FT_CAP) acand[(size_t)tile * FT_CAP + pos] = make_uint2(pack_xy(x, yb + i), __float_as_uint(e));
     }
     // exactly-zero pixels publish their exact value themselves; the inexact ones a lower bound of the maximum
-    if (__builtin_amdgcn_ballot_w64((live & zero_bits) != 0u) != 0 && lane == 0) atomic_max_guarded(max_key, ordered_key_f(0.f));
+    if (__builtin_amdgcn_ballot_w64((live & zero_bits) != 0u) != 0 && lane == 0) atomic_max_guarded(max_key, ordered_key(0.f));
     const float wf = order_float(wave_max_i32(float_order(fbest))), we = order_float(wave_max_i32(float_order(ebest)));
     if (lane == 0) { s_wF[wv] = wf; s_wE[wv] = we; }
     __syncthreads();
@@ -359,7 +342,7 @@ __global__ __launch_bounds__(256) void k_eig_approx(const uint8_t* __restrict__ 
             for (int k = 2; k <= FT_RY; k++) e = i == k ? E[k] : e;
             if (e >= tileF) {
                 const int pos = atomicAdd(&s_nmax, 1);
-                if (pos < FT_KMAX) amaxc[(size_t)tile * FT_KMAX + pos] = make_uint2(((unsigned)(yb + i) << 16) | (unsigned)x, __float_as_uint(e));
+                if (pos < FT_KMAX) amaxc[(size_t)tile * FT_KMAX + pos] = make_uint2(pack_xy(x, yb + i), __float_as_uint(e));
             }
         }
     }
@@ -368,7 +351,7 @@ __global__ __launch_bounds__(256) void k_eig_approx(const uint8_t* __restrict__ 
         acount[tile] = s_ncand;
         amaxn[tile] = s_nmax;
         aemax[tile] = tileE;
-        if (tileF > -INFINITY) atomic_max_guarded(fmax_key, ordered_key_f(tileF));
+        if (tileF > -INFINITY) atomic_max_guarded(fmax_key, ordered_key(tileF));
     }
 }
 
@@ -456,15 +439,15 @@ __device__ __forceinline__ float exact_eig_quad(const uint8_t* __restrict__ img,
     } else {
 #pragma unroll 1
         for (int mm = 0; mm < n; mm++) {
-            const int ry = reflect101c(py0 + 1 + m0 + mm, h);
-            const uint8_t* r0 = img + (size_t)reflect101c(ry - 1, h) * pitch;
+            const int ry = reflect101(py0 + 1 + m0 + mm, h);
+            const uint8_t* r0 = img + (size_t)reflect101(ry - 1, h) * pitch;
             const uint8_t* r1 = img + (size_t)ry * pitch;
-            const uint8_t* r2 = img + (size_t)reflect101c(ry + 1, h) * pitch;
+            const uint8_t* r2 = img + (size_t)reflect101(ry + 1, h) * pitch;
             float dx[BS], dy[BS];
 #pragma unroll
             for (int i = 0; i < BS; i++) {
-                const int rx = reflect101c(px0 + 1 + i, w);
-                const int xm = reflect101c(rx - 1, w), xp = reflect101c(rx + 1, w);
+                const int rx = reflect101(px0 + 1 + i, w);
+                const int xm = reflect101(rx - 1, w), xp = reflect101(rx + 1, w);
                 const float a0 = (float)r0[xm], b0 = (float)r0[rx], c0 = (float)r0[xp];
                 const float a1 = (float)r1[xm], c1 = (float)r1[xp];
                 const float a2 = (float)r2[xm], b2 = (float)r2[rx], c2 = (float)r2[xp];
@@ -489,7 +472,7 @@ __global__ __launch_bounds__(64) void k_exact_max(const uint8_t* __restrict__ im
 {
     const unsigned fk = *fmax_key;
     if (fk == 0u) return;                        // no inexact pixel anywhere: the maximum is already exact (or nothing is masked in)
-    const float Fg = key_to_float_f(fk);
+    const float Fg = key_to_float(fk);
     // a quad of lanes per list entry (exact_eig_quad); every condition below is the same for the four lanes of a quad
     const int gid = blockIdx.x * 64 + threadIdx.x;
     const int ent = gid >> 2, q = gid & 3;
@@ -501,7 +484,7 @@ __global__ __launch_bounds__(64) void k_exact_max(const uint8_t* __restrict__ im
         if (slot < n) {
             const uint2 e = amaxc[(size_t)tile * FT_KMAX + slot];
             if (__uint_as_float(e.y) >= Fg)
-                best = ordered_key_f(exact_eig_quad<BS>(img, w, h, pitch, (int)(e.x & 0xffffu), (int)(e.x >> 16), k0, k1, q));
+                best = ordered_key(exact_eig_quad<BS>(img, w, h, pitch, xy_x(e.x), xy_y(e.x), k0, k1, q));
         }
     } else if (aemax[tile] >= Fg) {
         // more pixels of this tile tie for its maximum than the list holds (a plateau): walk the tile
@@ -509,7 +492,7 @@ __global__ __launch_bounds__(64) void k_exact_max(const uint8_t* __restrict__ im
         for (int p = slot; p < FT_TW * FT_TH; p += FT_KMAX) {
             const int x = tx * FT_TW + p % FT_TW, y = ty * FT_TH + p / FT_TW;
             if (x >= w || y >= h || (mask && !mask[(size_t)y * mask_pitch + x])) continue;
-            const unsigned k = ordered_key_f(exact_eig_quad<BS>(img, w, h, pitch, x, y, k0, k1, q));
+            const unsigned k = ordered_key(exact_eig_quad<BS>(img, w, h, pitch, x, y, k0, k1, q));
             best = k > best ? k : best;
         }
     }
@@ -532,9 +515,7 @@ __global__ __launch_bounds__(64) void k_exact_cands(const uint8_t* __restrict__ 
     __shared__ unsigned kept[FT_G * FT_CAP];
     const int g = blockIdx.x, lane = threadIdx.x;
     // v <= k1^2 (L + eps) (1 + 2^-22): nothing below the quality threshold needs the exact arithmetic (quality <= 0: no cut)
-    const unsigned mk = *max_key;
-    const double max_val = mk ? (double)key_to_float_f(mk) : 0.0;
-    const float thr_up = quality > 0 ? (float)((double)(float)(max_val * quality) / ((double)k1 * (double)k1 * 1.000001)) * 0.999999f
+    const float thr_up = quality > 0 ? (float)((double)quality_threshold(*max_key, quality) / ((double)k1 * (double)k1 * 1.000001)) * 0.999999f
                                      : -1.f;     // in pass A's units, rounded down
     int start[FT_G + 1];
     start[0] = 0;
@@ -587,9 +568,9 @@ __global__ __launch_bounds__(64) void k_exact_cands(const uint8_t* __restrict__ 
         bool keep = false;
         if (idx < nkept) {
             const unsigned xy = kept[idx];
-            const float v = exact_eig_quad<BS>(img, w, h, pitch, (int)(xy & 0xffffu), (int)(xy >> 16), k0, k1, q);
+            const float v = exact_eig_quad<BS>(img, w, h, pitch, xy_x(xy), xy_y(xy), k0, k1, q);
             keep = v > 0.f && q == 0;
-            key = ((unsigned long long)ordered_key_f(v) << 32) | xy;
+            key = cand_key(v, xy_x(xy), xy_y(xy));
         }
         const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
         if (keep) region[written + __popcll(bal & ((1ull << lane) - 1ull))] = key;
@@ -615,14 +596,13 @@ __global__ __launch_bounds__(64) void k_exact_ties(const uint8_t* __restrict__ i
         const float m = order_float(wave_max_i32(float_order(k9 == 4 ? -INFINITY : v)));
         if (lane == 0 && centre > 0.f && !(centre < m)) {
             const int g = ((y / FT_TH) * tiles_x + x / FT_TW) / FT_G;
-            raw[(size_t)g * (FT_G * FT_TW * FT_TH) + atomicAdd(&blk_count[g], 1)] =
-                ((unsigned long long)ordered_key_f(centre) << 32) | ((unsigned)y << 16) | (unsigned)x;
+            raw[(size_t)g * (FT_G * FT_TW * FT_TH) + atomicAdd(&blk_count[g], 1)] = cand_key(centre, x, y);
         }
     };
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const unsigned e = ties[i];
         if (!(e & 0x80000000u)) {
-            settle((int)(e & 0xffffu), (int)(e >> 16));
+            settle(xy_x(e), xy_y(e));
             continue;
         }
         // a whole tile (its list overflowed in pass A): every pixel that may hold a corner
@@ -632,15 +612,6 @@ __global__ __launch_bounds__(64) void k_exact_ties(const uint8_t* __restrict__ i
             if (x >= 1 && x <= w - 2 && y >= 1 && y <= h - 2 && (!mask || mask[(size_t)y * mask_pitch + x])) settle(x, y);
         }
     }
-}
-
-void sobel_scale_f(int block_size, float* k0, float* k1)
-{
-    double scale = (double)(1 << 2) * block_size;
-    scale *= 255.0;
-    scale = 1.0 / scale;
-    *k1 = (float)(1.0 * scale);
-    *k0 = (float)(2.0 * scale);
 }
 
 template <int BS>
@@ -655,7 +626,7 @@ void launch_fast(hipStream_t s, const DetectScratch& D, const Level& img, const 
         attr_set = true;
     }
     float k0, k1;
-    sobel_scale_f(BS, &k0, &k1);
+    sobel_scale(BS, &k0, &k1);
     const int tx = (img.w + FT_TW - 1) / FT_TW, ty = (img.h + FT_TH - 1) / FT_TH;
     const int ntiles = tx * ty, ngroups = (ntiles + FT_G - 1) / FT_G;
     hipMemsetAsync(D.cb.fmax_key, 0, 3 * sizeof(unsigned), s);   // and the tie / kept counters behind it

@@ -2,7 +2,7 @@
 //
 // This is the std::sort(tmpCorners, greaterThanPtr()) step of cv2.goodFeaturesToTrack
 // (s1_lucaskanade_tracking.py:437), applied only to the ACCEPTED corners (see
-// k_corners.hip).  It is the one place the library uses a ROCm header-only primitive
+// k_min_distance.hip).  It is the one place the library uses a ROCm header-only primitive
 // (rocPRIM device radix sort, compiled into libicelk.so; no runtime dependency): a <=10^5-key sort
 // once per detection frame is not on the per-pair critical path.  Kept in its own translation unit
 // so a hand-written segmented sort can replace it without touching the detector.

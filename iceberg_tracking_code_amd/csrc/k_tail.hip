@@ -24,29 +24,18 @@
 //                   workgroup that finishes last -- the counts for the host and the sequence word it polls (CountsWord).
 // The host reads the counts when it adopts the segment (icelk_seg_detect_stage / _switch): nothing waits for it.  When the
 // device-side verdict is "not valid" -- the relaxation of the min-distance stage has not converged, a pruned candidate
-// set yielded fewer than maxCorners corners (k_corners.hip), the corners exceed the tables, or one response bin holds
+// set yielded fewer than maxCorners corners (k_min_distance.hip), the corners exceed the tables, or one response bin holds
 // more than 65536 keys (a frame of identical corners: ranking inside it is quadratic) -- nothing is written and the host
 // runs the tail of before (detect_finish), which is also what ICELK_HOST_TAIL=1 selects.
-#include "icelk_internal.h"
+// The key format, the quality threshold and the reset of the counters are corner_keys.h's.
+#include "corner_keys.h"
 
 namespace icelk {
 
 namespace {
 
-constexpr int CT = 64;
 constexpr int NB = kTailRespBins;
 constexpr int kMaxBinKeys = 65536;
-
-__device__ __forceinline__ unsigned ordered_key(float v)
-{
-    const unsigned b = __float_as_uint(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_to_float(unsigned k)
-{
-    const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(b);
-}
 
 // Monotone map response key -> bin, bin 0 = strongest: NB equal slices of [lowest key a kept candidate can have, maximum]
 struct RespBins {
@@ -57,8 +46,7 @@ __device__ __forceinline__ RespBins resp_bins(const unsigned* max_key_p, const u
 {
     RespBins r;
     r.max_key = *max_key_p;
-    const double max_val = r.max_key ? (double)key_to_float(r.max_key) : 0.0;
-    unsigned lo = ordered_key((float)(max_val * quality));
+    unsigned lo = ordered_key(quality_threshold(r.max_key, quality));
     const unsigned pk = *prune_key_p;
     lo = pk > lo ? pk : lo;
     const unsigned span = r.max_key > lo ? r.max_key - lo : 0u;
@@ -68,7 +56,7 @@ __device__ __forceinline__ RespBins resp_bins(const unsigned* max_key_p, const u
 }
 __device__ __forceinline__ int resp_bin(const RespBins& r, unsigned long long key)
 {
-    const unsigned hk = (unsigned)(key >> 32);
+    const unsigned hk = cand_response_key(key);
     if (hk >= r.max_key) return 0;
     const unsigned b = (r.max_key - hk) >> r.shift;
     return b >= (unsigned)NB ? NB - 1 : (int)b;
@@ -231,8 +219,8 @@ __global__ __launch_bounds__(CT) void k_tail_rank(const unsigned long long* __re
             int above = lo;
             for (int q = lo; q < hi; q++) above += sorted[q] > key ? 1 : 0;
             if (above < n_out) {
-                const unsigned idx = (unsigned)key;
-                const float x = (float)(int)(idx & 0xffffu), y = (float)(int)(idx >> 16);
+                const unsigned xy = cand_xy(key);
+                const float x = (float)xy_x(xy), y = (float)xy_y(xy);
                 seg_xy[2 * above] = x;
                 seg_xy[2 * above + 1] = y;
                 seg_alive[above] = 1;
@@ -251,7 +239,7 @@ __global__ __launch_bounds__(CT) void k_tail_rank(const unsigned long long* __re
 }
 
 __global__ __launch_bounds__(CT) void k_tail_order(TailArgs A, const float* __restrict__ seg_xy, TailOrderGeo geo, int* bins,
-                                                    int* __restrict__ order, int order_blocks, TailReset rs,
+                                                    int* __restrict__ order, int order_blocks, DetectCounters rs,
                                                     int* __restrict__ host_counts, int seq)
 {
     const int lane = threadIdx.x;
@@ -264,22 +252,9 @@ __global__ __launch_bounds__(CT) void k_tail_order(TailArgs A, const float* __re
     } else {
         const int i0 = ((int)blockIdx.x - order_blocks) * CT + lane, stride = ((int)gridDim.x - order_blocks) * CT;
         for (int i = i0; i < NB; i += stride) A.hist[i] = 0;    // this file's own histogram: always
-        if (status == TAIL_OK) {
-            // the detector set's counters for its next detection (what k_detect_reset does); not when the host is going to
-            // run the tail itself: it needs them
-            for (int i = i0; i <= rs.ncell; i += stride) {
-                rs.cell_count[i] = 0;
-                if (i < rs.ncell) rs.cell_fill[i] = 0;
-                if (i % rs.scan_chunk == 0) rs.chunk_tot[(i / rs.scan_chunk) * rs.chunk_stride] = 0;
-            }
-            for (int i = i0; i < rs.key_bins; i += stride) rs.key_hist[i] = 0;
-            if (i0 < 8) rs.undecided[i0] = 0;
-            if (i0 == 0) {
-                *rs.acc_count = 0;
-                *rs.cand_count = 0;
-                *rs.prune_key = 0;
-            }
-        }
+        // the detector set's counters for its next detection, key histogram included, the masked maximum not (it is the
+        // candidate buffer's); not when the host is going to run the tail itself: it needs them
+        if (status == TAIL_OK) reset_counters(rs, i0, stride, 1);
     }
     if (!last_arriver(&ctl[TC_TICKET_ORDER], lane)) return;
     if (bins)
@@ -347,7 +322,7 @@ void launch_tail_gather(hipStream_t s, DetectScratch& D, int ncell, double quali
 }
 
 void launch_tail_device(hipStream_t s, DetectScratch& D, double quality, float* seg_xy, uint8_t* seg_alive, float* seg_tracks,
-                        int max_vert, int* order, int* order_border, const TailOrderGeo& geo, const TailReset& rs,
+                        int max_vert, int* order, int* order_border, const TailOrderGeo& geo, const DetectCounters& rs,
                         int* host_counts, int seq)
 {
     int* bins = order ? D.tail_bins : nullptr;

@@ -83,7 +83,7 @@ def stripes_dots(bs):
 
 
 def ordered_key(v):
-    """k_corners.hip's order-preserving key of a float32"""
+    """corner_keys.h's order-preserving key of a float32"""
     b = int(np.array([v], np.float32).view(np.uint32)[0])
     return (~b & 0xffffffff) if b & 0x80000000 else (b | 0x80000000)
 
