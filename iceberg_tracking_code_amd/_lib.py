@@ -193,6 +193,9 @@ SIGNATURES = {
     "icelk_fb_filter": (C.c_int, [handle_p, f32p, f32p, C.c_int, C.c_float, f32p, u8p]),
     "icelk_set_mask": (C.c_int, [handle_p, u8p, C.c_int, C.c_int, C.c_int]),
     "icelk_min_eig_map": (C.c_int, [handle_p, C.c_int, C.c_int, f32p, C.c_int]),
+    "icelk_harris_map": (C.c_int, [handle_p, C.c_int, C.c_int, C.c_double, f32p, C.c_int]),
+    "icelk_set_detector": (C.c_int, [handle_p, C.c_int, C.c_double]),
+    "icelk_get_detector": (C.c_int, [handle_p, i32p, C.POINTER(C.c_double)]),
     "icelk_good_features": (C.c_int, [handle_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, f32p,
                                       C.c_int, i32p]),
     "icelk_detect_stats": (C.c_int, [handle_p, i32p, i32p]),

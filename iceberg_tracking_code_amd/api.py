@@ -4,6 +4,8 @@
     calcOpticalFlowPyrLK(img0, img1, p0, None, **lk)      s1_lucaskanade_tracking.py:323,326
     goodFeaturesToTrack(gray, mask=mask, **feature)       s1_lucaskanade_tracking.py:437
 
+and the two response maps behind goodFeaturesToTrack, cornerMinEigenVal and cornerHarris (Sobel ksize 3 only).
+
 Same names, argument meaning, return shapes and None/empty behaviour as cv2, so the reference loop runs
 with `import iceberg_tracking_code_amd as cv2`.  Every call goes to the HIP library
 through a process-wide default Context; each call uploads its images, so this surface is PCIe-bound --
@@ -31,8 +33,9 @@ def set_gray_variant(variant):
 def set_variant(name, value):
     """A named build-dependent variant of OpenCV's arithmetic for the cv2-shaped calls of this module: "lk_sums" 0 | 1 | 2
     (exact / OpenCV 3.x SSE2 / 4.x CV_SIMD128 summation order of the LK sums), "sobel_fma" 0..3, "eig_fma" 0 | 1
-    (icelk_set_variant; DESIGN.md section 2 has how far apart they are).  0 = default."""
-    if name not in ("lk_sums", "sobel_fma", "eig_fma"):
+    (icelk_set_variant; DESIGN.md section 2 has how far apart they are), "harris_tail" 0 | 1 (the Harris response in
+    calcHarris' float lanes / as its scalar tail).  0 = default."""
+    if name not in ("lk_sums", "sobel_fma", "eig_fma", "harris_tail"):
         raise ValueError("unknown variant %r" % (name,))
     _default["variants"][name] = int(value)
     if _default["ctx"] is not None:
@@ -111,10 +114,11 @@ def calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts=None, status=None, e
 
 def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, corners=None, mask=None, blockSize=3,
                         useHarrisDetector=False, k=0.04):
-    """-> (M,1,2) float32, or None when nothing passes (the reference guards this at s1:445)."""
-    if useHarrisDetector:
-        raise ValueError("useHarrisDetector=True is not part of this path (the reference uses Shi-Tomasi)")
+    """-> (M,1,2) float32, or None when nothing passes (the reference guards this at s1:445).  useHarrisDetector=True ranks
+    by the Harris response det - k tr^2 instead of the smaller eigenvalue; a map whose masked maximum is <= 0 gives None."""
     img = _check_gray(image, "image")
+    if useHarrisDetector and not np.isfinite(k):
+        raise ValueError("goodFeaturesToTrack: k must be finite")
     if not (qualityLevel > 0) or minDistance < 0 or maxCorners < 0:
         raise ValueError("goodFeaturesToTrack: qualityLevel > 0, minDistance >= 0, maxCorners >= 0 required")
     h, w = img.shape
@@ -125,4 +129,30 @@ def goodFeaturesToTrack(image, maxCorners, qualityLevel, minDistance, corners=No
         if m.shape != img.shape:
             raise ValueError("mask size differs from the image")
         ctx.set_mask(m)
-    return ctx.good_features(0, maxCorners, qualityLevel, minDistance, use_mask=mask is not None, blockSize=blockSize)
+    return ctx.good_features(0, maxCorners, qualityLevel, minDistance, use_mask=mask is not None, blockSize=blockSize,
+                             useHarrisDetector=bool(useHarrisDetector), k=k)
+
+
+def _response_map_args(src, blockSize, ksize, name):
+    img = _check_gray(src, "src")
+    if ksize != 3:
+        raise ValueError("%s: only ksize 3 (the Sobel aperture of goodFeaturesToTrack) is part of this path" % name)
+    if int(blockSize) != blockSize or blockSize < 1:
+        raise ValueError("%s: blockSize must be a positive integer" % name)
+    h, w = img.shape
+    ctx = default_context(w, h)
+    ctx.upload_gray(0, img)
+    return ctx
+
+
+def cornerMinEigenVal(src, blockSize, ksize=3):
+    """-> (H, W) float32: the smaller eigenvalue of the blockSize x blockSize covariance sums, the map goodFeaturesToTrack
+    ranks by (BORDER_REFLECT_101, cv2's default)."""
+    return _response_map_args(src, blockSize, ksize, "cornerMinEigenVal").min_eig_map(0, int(blockSize))
+
+
+def cornerHarris(src, blockSize, ksize, k):
+    """-> (H, W) float32: det - k tr^2 of the same sums, the map goodFeaturesToTrack(useHarrisDetector=True) ranks by."""
+    if not np.isfinite(k):
+        raise ValueError("cornerHarris: k must be finite")
+    return _response_map_args(src, blockSize, ksize, "cornerHarris").harris_map(0, int(blockSize), float(k))

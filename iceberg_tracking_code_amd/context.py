@@ -3,6 +3,7 @@
 This is the host side of the hot path: everything here is argument marshalling around the C ABI of
 include/icelk.h.  One Context per process per GPU (see DESIGN.md "Multi-GPU").
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -506,13 +507,52 @@ class Context:
         self._ck(self._lib.icelk_min_eig_map(self._h, slot, blockSize, _f32(out), out.shape[1]))
         return out
 
-    def good_features(self, slot, maxCorners, qualityLevel, minDistance, use_mask=False, blockSize=3):
+    def harris_map(self, slot, blockSize=3, k=0.04):
+        """cv2.cornerHarris(frame, blockSize, 3, k) of the slot (icelk_harris_map).  k is this call's own: the detector
+        setting of the handle is neither read nor changed."""
+        lvl = self.download_level(slot, 0)
+        out = np.empty(lvl.shape, np.float32)
+        self._ck(self._lib.icelk_harris_map(self._h, slot, int(blockSize), float(k), _f32(out), out.shape[1]))
+        return out
+
+    # -- which response the detector ranks by ---------------------------------------------------
+    def set_detector(self, harris=False, k=0.04):
+        """cv2.goodFeaturesToTrack's useHarrisDetector / k for every detection enqueued from now on (icelk_set_detector).
+        harris=False: the smaller eigenvalue (Shi-Tomasi, the default; k is kept and not read).  A detection in flight,
+        and candidates prepared ahead, keep the detector they were enqueued under."""
+        self._ck(self._lib.icelk_set_detector(self._h, 1 if harris else 0, float(k)))
+
+    def get_detector(self):
+        """(harris, k) as set_detector left them."""
+        kind, k = C.c_int(0), C.c_double(0)
+        self._ck(self._lib.icelk_get_detector(self._h, C.byref(kind), C.byref(k)))
+        return bool(kind.value), k.value
+
+    @contextlib.contextmanager
+    def _detector_for_call(self, useHarrisDetector, k):
+        """The keyword arguments useHarrisDetector / k of the detector calls.  None (the default): the call runs under
+        set_detector's setting.  True / False: the Harris response with this k / the smaller eigenvalue for the candidate
+        stage the call enqueues -- the library snapshots the setting there -- and the handle's own setting is back when the
+        call returns."""
+        if useHarrisDetector is None:
+            yield
+            return
+        before = self.get_detector()
+        self.set_detector(bool(useHarrisDetector), k if useHarrisDetector else before[1])
+        try:
+            yield
+        finally:
+            self.set_detector(*before)
+
+    def good_features(self, slot, maxCorners, qualityLevel, minDistance, use_mask=False, blockSize=3,
+                      useHarrisDetector=None, k=0.04):
         cap = self.max_pts if maxCorners <= 0 else min(int(maxCorners), self.max_pts)
         out = np.empty((max(cap, 1), 2), np.float32)
         n = C.c_int(0)
-        self._ck(self._lib.icelk_good_features(self._h, slot, 1 if use_mask else 0, int(maxCorners),
-                                               float(qualityLevel), float(minDistance), int(blockSize), _f32(out), cap,
-                                               C.byref(n)))
+        with self._detector_for_call(useHarrisDetector, k):
+            self._ck(self._lib.icelk_good_features(self._h, slot, 1 if use_mask else 0, int(maxCorners),
+                                                   float(qualityLevel), float(minDistance), int(blockSize), _f32(out), cap,
+                                                   C.byref(n)))
         if n.value == 0:
             return None
         return out[:n.value].reshape(-1, 1, 2).copy()
@@ -535,21 +575,26 @@ class Context:
         return dict(candidates=a.value, accepted=b.value)
 
     # -- device-resident segment state ----------------------------------------------------------
-    def seg_detect(self, slot, maxCorners, qualityLevel, minDistance, use_mask=False, blockSize=3):
+    def seg_detect(self, slot, maxCorners, qualityLevel, minDistance, use_mask=False, blockSize=3,
+                   useHarrisDetector=None, k=0.04):
         n = C.c_int(0)
-        self._ck(self._lib.icelk_seg_detect(self._h, slot, 1 if use_mask else 0, int(maxCorners), float(qualityLevel),
-                                            float(minDistance), int(blockSize), C.byref(n)))
+        with self._detector_for_call(useHarrisDetector, k):
+            self._ck(self._lib.icelk_seg_detect(self._h, slot, 1 if use_mask else 0, int(maxCorners), float(qualityLevel),
+                                                float(minDistance), int(blockSize), C.byref(n)))
         return n.value
 
     def build_pyramid_ahead(self, slot, winSize=(21, 21), maxLevel=3):
         self._ck(self._lib.icelk_build_pyramid_ahead(self._h, slot, winSize[0], winSize[1], maxLevel))
 
-    def seg_detect_prepare(self, slot, use_mask=False, blockSize=3):
-        self._ck(self._lib.icelk_seg_detect_prepare(self._h, slot, 1 if use_mask else 0, int(blockSize)))
+    def seg_detect_prepare(self, slot, use_mask=False, blockSize=3, useHarrisDetector=None, k=0.04):
+        with self._detector_for_call(useHarrisDetector, k):
+            self._ck(self._lib.icelk_seg_detect_prepare(self._h, slot, 1 if use_mask else 0, int(blockSize)))
 
-    def seg_detect_begin(self, slot, maxCorners, qualityLevel, minDistance, use_mask=False, blockSize=3):
-        self._ck(self._lib.icelk_seg_detect_begin(self._h, slot, 1 if use_mask else 0, int(maxCorners),
-                                                  float(qualityLevel), float(minDistance), int(blockSize)))
+    def seg_detect_begin(self, slot, maxCorners, qualityLevel, minDistance, use_mask=False, blockSize=3,
+                         useHarrisDetector=None, k=0.04):
+        with self._detector_for_call(useHarrisDetector, k):
+            self._ck(self._lib.icelk_seg_detect_begin(self._h, slot, 1 if use_mask else 0, int(maxCorners),
+                                                      float(qualityLevel), float(minDistance), int(blockSize)))
 
     def seg_detect_finish(self, maxCorners):
         n = C.c_int(0)

@@ -108,10 +108,18 @@ static int det_free(const Ctx* c)
     return -1;
 }
 
-// what a candidate buffer must hold to serve a detection of `slot` as it is now
-static Ctx::CandKey eo_want(const Ctx* c, int slot, int use_mask, int block_size)
+// The detector as the handle has it set now: what a candidate stage enqueued now computes.  For the smaller eigenvalue k
+// and the Harris form are not part of it, so they do not tell two candidate buffers apart either
+static Response detector_now(const Ctx* c)
 {
-    return {slot, block_size, use_mask, c->slots[slot].gen, c->mask_gen};
+    if (c->detector_kind != ICELK_DETECTOR_HARRIS) return Response{};
+    return Response{ICELK_DETECTOR_HARRIS, c->detector_k, c->harris_tail};
+}
+
+// what a candidate buffer must hold to serve a detection of `slot` as it is now
+static Ctx::CandKey eo_want(const Ctx* c, int slot, int use_mask, int block_size, const Response& resp)
+{
+    return {slot, block_size, use_mask, c->slots[slot].gen, c->mask_gen, resp};
 }
 
 static bool eo_holds(const Ctx::EigOut& e, const Ctx::CandKey& want) { return e.valid && e.key == want; }
@@ -142,9 +150,10 @@ void activate_eig_out(Ctx* c, Ctx::DetSet& S, int idx)
 
 // Does the strip kernel produce this handle's candidates at block_size (else: the any-blockSize kernels, which serve no
 // prepare launch and no fused map)?  The switch is read at every call: it is set and cleared on a live handle.
-static bool strip_kernel_serves(const Ctx* c, int block_size)
+static bool strip_kernel_serves(const Ctx* c, int block_size, const Response& resp)
 {
-    return fused_block_size(block_size) && !getenv("ICELK_GENERIC_CORNERS") && !c->corner_variant;
+    return fused_block_size(block_size) && !getenv("ICELK_GENERIC_CORNERS") && !c->corner_variant &&
+           !(resp.kind == ICELK_DETECTOR_HARRIS && resp.tail);
 }
 
 static int next_counts_seq(Ctx::DetSet& S) { return S.counts_seq = (S.counts_seq + 1) & 0x3fffffff; }
@@ -188,17 +197,18 @@ static int pick_mask(Ctx* c, int use_mask, int w, int h, const uint8_t** mask)
 
 // Corner candidates of a frame ahead of its detection (strip kernel only; anything else is left to
 // detect_begin).  Runs on eig_stream into the spare buffer; detect_begin adopts it when slot, frame
-// generation, blockSize and mask still match.
+// generation, blockSize, mask and detector (kind, k) still match.
 int detect_prepare(Ctx* c, int slot, int use_mask, int block_size)
 {
     Range rg("icelk detect_prepare (corner candidates ahead)");
     int rc = check_slot(c, slot, true);
     if (rc) return rc;
-    if (!strip_kernel_serves(c, block_size)) return ICELK_OK;
+    const Response resp = detector_now(c);   // the snapshot: the buffer is keyed by it
+    if (!strip_kernel_serves(c, block_size, resp)) return ICELK_OK;
     Slot& s = c->slots[slot];
     const uint8_t* mask = nullptr;
     if ((rc = pick_mask(c, use_mask, s.w, s.h, &mask))) return rc;
-    const Ctx::CandKey want = eo_want(c, slot, use_mask, block_size);
+    const Ctx::CandKey want = eo_want(c, slot, use_mask, block_size, resp);
     Ctx::EigOut& e = c->eo[eo_free(c, want)];
     if (eo_holds(e, want)) return ICELK_OK;   // already there
     const hipStream_t es = c->eig_stream;
@@ -212,7 +222,7 @@ int detect_prepare(Ctx* c, int slot, int use_mask, int block_size)
     const double prep_quality = c->prep_quality;
     {
         ProfScope p(c, K_EIG, es);
-        launch_candidates(es, T, s.lv[0], block_size, mask, c->mask_pitch, prep_quality, false, nullptr);
+        launch_candidates(es, T, s.lv[0], block_size, mask, c->mask_pitch, prep_quality, false, nullptr, 0, resp);
     }
     if ((rc = check_launch(c, "corner candidates (prepared)"))) return rc;
     HIPCHK(c, hipEventRecord(e.done, es));
@@ -257,6 +267,7 @@ static DetectJob new_job(const Ctx* c, const Slot& s, int max_corners, double qu
     J.min_distance = min_distance;
     J.ncell = ncell;
     J.max_corners = max_corners;
+    J.resp = detector_now(c);   // the snapshot: whatever icelk_set_detector does from here on, this detection keeps it
     if (min_distance >= 1 && max_corners > 0 && max_corners <= (1 << 24) && !getenv("ICELK_NO_PRUNE"))
         J.prune_want = (int)std::min(8.0 * max_corners, std::ceil(c->prune_factor * max_corners));
     return J;
@@ -274,9 +285,9 @@ static int begin_candidates(Ctx* c, Ctx::DetSet& S, int slot, int use_mask, cons
     const hipStream_t ds = c->det_stream;
     if (int rcw = wait_event(c, ds, s.frame_ev)) return rcw;   // level 0 only (see detect_prepare)
     if (int rcw = wait_event(c, ds, S.tail_done)) return rcw;
-    const bool strip = strip_kernel_serves(c, block_size);
+    const bool strip = strip_kernel_serves(c, block_size, J.resp);
     const bool need_reset = !S.counters_clean || J.ncell > S.reset_ncell;
-    const Ctx::CandKey want = eo_want(c, slot, use_mask, block_size);
+    const Ctx::CandKey want = eo_want(c, slot, use_mask, block_size, J.resp);
     const int spare_idx = eo_free(c, want);
     Ctx::EigOut& spare = c->eo[spare_idx];
     const bool prepared = eo_holds(spare, want) && strip && spare.quality <= J.quality;
@@ -291,7 +302,7 @@ static int begin_candidates(Ctx* c, Ctx::DetSet& S, int slot, int use_mask, cons
         ProfScope p(c, K_EIG, ds);
         HIPCHK(c, hipMemsetAsync(spare.buf.max_key, 0, sizeof(unsigned), ds));
         if (need_reset) launch_detect_reset(ds, S.D, (int)J.ncell, 1);
-        launch_candidates(ds, S.D, s.lv[0], block_size, mask, c->mask_pitch, J.quality, !strip, nullptr, c->corner_variant);
+        launch_candidates(ds, S.D, s.lv[0], block_size, mask, c->mask_pitch, J.quality, !strip, nullptr, c->corner_variant, J.resp);
         HIPCHK(c, hipEventRecord(s.det_used, ds));   // nothing after this launch reads the frame
     }
     return check_launch(c, "corner candidates");
@@ -601,10 +612,9 @@ int icelk_download_mask(icelk_t* h, uint8_t* host_mask, int stride, int* w, int*
     return ICELK_OK;
 }
 
-int icelk_min_eig_map(icelk_t* h, int slot, int block_size, float* host_out, int stride_elems)
+// icelk_min_eig_map / icelk_harris_map: the response map of a slot's frame, by the kernel a detection would take
+static int response_map(Ctx* c, int slot, int block_size, const Response& resp, float* host_out, int stride_elems)
 {
-    if (!h) return ICELK_EARG;
-    Ctx* c = C(h);
     HIPCHK(c, hipSetDevice(c->device));
     int rc = check_slot(c, slot, true);
     if (rc) return rc;
@@ -624,10 +634,10 @@ int icelk_min_eig_map(icelk_t* h, int slot, int block_size, float* host_out, int
         ProfScope p(c, K_EIG);
         launch_detect_reset(c->stream, S.D, 0, 3);
         S.counters_clean = false;
-        if (strip_kernel_serves(c, block_size)) {
-            launch_candidates(c->stream, S.D, s.lv[0], block_size, nullptr, 0, 1.0, false, S.D.eig);
+        if (strip_kernel_serves(c, block_size, resp)) {
+            launch_candidates(c->stream, S.D, s.lv[0], block_size, nullptr, 0, 1.0, false, S.D.eig, 0, resp);
         } else {
-            launch_min_eig(c->stream, s.lv[0], block_size, S.D.eig, nullptr, 0, S.D.cb.max_key, c->corner_variant);
+            launch_min_eig(c->stream, s.lv[0], block_size, S.D.eig, nullptr, 0, S.D.cb.max_key, c->corner_variant, resp);
         }
     }
     rc = check_launch(c, "min_eig");
@@ -635,6 +645,41 @@ int icelk_min_eig_map(icelk_t* h, int slot, int block_size, float* host_out, int
     HIPCHK(c, hipMemcpy2DAsync(host_out, sizeof(float) * stride_elems, S.D.eig, sizeof(float) * s.w, sizeof(float) * s.w,
                                s.h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ICELK_OK;
+}
+
+int icelk_min_eig_map(icelk_t* h, int slot, int block_size, float* host_out, int stride_elems)
+{
+    if (!h) return ICELK_EARG;
+    return response_map(C(h), slot, block_size, Response{}, host_out, stride_elems);
+}
+
+int icelk_harris_map(icelk_t* h, int slot, int block_size, double k, float* host_out, int stride_elems)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (!std::isfinite(k)) FAIL(c, ICELK_EARG, "k is not finite");
+    return response_map(c, slot, block_size, Response{ICELK_DETECTOR_HARRIS, k, c->harris_tail}, host_out, stride_elems);
+}
+
+int icelk_set_detector(icelk_t* h, int kind, double k)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    if (kind != ICELK_DETECTOR_MIN_EIG && kind != ICELK_DETECTOR_HARRIS) FAIL(c, ICELK_EARG, "unknown detector kind");
+    if (!std::isfinite(k)) FAIL(c, ICELK_EARG, "k is not finite");
+    // nothing else: detections in flight carry their own copy (DetectJob::resp), prepared candidates theirs (CandKey::resp)
+    c->detector_kind = kind;
+    c->detector_k = k;
+    return ICELK_OK;
+}
+
+int icelk_get_detector(icelk_t* h, int* kind, double* k)
+{
+    if (!h) return ICELK_EARG;
+    const Ctx* c = C(h);
+    if (kind) *kind = c->detector_kind;
+    if (k) *k = c->detector_k;
     return ICELK_OK;
 }
 

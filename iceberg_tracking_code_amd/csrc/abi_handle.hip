@@ -459,6 +459,7 @@ int icelk_set_variant(icelk_t* h, const char* name, int value)
     else if (!strcmp(name, "lk_wide_sums") && (value == 0 || value == 1)) c->lk_wide_sums = value;
     else if (!strcmp(name, "sobel_fma") && value >= 0 && value <= 3) c->corner_variant = (c->corner_variant & 4) | value;
     else if (!strcmp(name, "eig_fma") && (value == 0 || value == 1)) c->corner_variant = (c->corner_variant & 3) | (value << 2);
+    else if (!strcmp(name, "harris_tail") && (value == 0 || value == 1)) c->harris_tail = value;
     else FAIL(c, ICELK_EARG, "unknown variant / value");
     for (auto& e : c->eo) e.valid = false;     // candidates prepared under another variant are not adopted
     return ICELK_OK;

@@ -26,6 +26,7 @@ struct DetectJob {
     size_t ncell = 0;
     const int* cand_count_ptr = nullptr;
     int prune_want = 0;   // > 0: top-K pruning is on for this job
+    Response resp;        // the detector as it was set when the candidate stage was enqueued (icelk_set_detector)
     unsigned long long seq = 0;   // order of icelk_seg_detect_begin calls: the oldest job in flight is finished first
     // device-driven tail (k_tail.hip): enqueued behind the min-distance stage by detect_begin; the corners of this detection
     // start a segment in set `seg_set`, cut at max_corners
@@ -46,6 +47,9 @@ struct Ctx {
     int lk_sum_mode = 0;                   // icelk_set_variant "lk_sums"
     int lk_wide_sums = 0;                  // icelk_set_variant "lk_wide_sums"
     int corner_variant = 0;                // icelk_set_variant "sobel_fma" (bits 0-1) | "eig_fma" (bit 2)
+    int harris_tail = 0;                   // icelk_set_variant "harris_tail"
+    int detector_kind = ICELK_DETECTOR_MIN_EIG;   // icelk_set_detector: read when a candidate stage is enqueued
+    double detector_k = 0.04;
     int lk_kernel_flags = 0;               // icelk_set_lk_kernel: ICELK_FLAG_GENERIC_KERNEL / _ONE_PER_WAVE or 0
     // diagnostics: ICELK_LK_STAMPS=<file> records entry / exit time and placement of every workgroup of the LAST
     // segment tracker launch and writes them to the file when the handle is destroyed (tools/lk_stamps.py reads it)
@@ -269,12 +273,14 @@ struct Ctx {
     // candidates of a FUTURE detection frame can be produced (icelk_seg_detect_prepare, on eig_stream) while the
     // min-distance stages of the detections in flight still read their own.  A detector set's D.cb always mirrors
     // eo[its eo_active].buf (activate_eig_out).
-    struct CandKey {   // whose candidates a buffer holds: a slot's frame as it was (gen), for one blockSize and one mask
+    struct CandKey {   // whose candidates a buffer holds: a slot's frame as it was (gen), for one blockSize, one mask, one detector
         int slot = -1, block_size = 0, use_mask = 0;
         unsigned long long gen = 0, mask_gen = 0;
+        Response resp;
         bool operator==(const CandKey& o) const
         {
-            return slot == o.slot && gen == o.gen && block_size == o.block_size && use_mask == o.use_mask && mask_gen == o.mask_gen;
+            return slot == o.slot && gen == o.gen && block_size == o.block_size && use_mask == o.use_mask && mask_gen == o.mask_gen &&
+                   resp == o.resp;
         }
     };
     struct EigOut {

@@ -468,15 +468,23 @@ void launch_tail_gather(hipStream_t s, DetectScratch& D, int ncell, double quali
 void launch_tail_device(hipStream_t s, DetectScratch& D, double quality, float* seg_xy, uint8_t* seg_alive, float* seg_tracks,
                         int max_vert, int* order, int* order_border, const TailOrderGeo& geo, const DetectCounters& rs,
                         int* host_counts, int seq);
+// The corner response a candidate stage computes (icelk_set_detector; k_corners.hip harris_of: the arithmetic)
+struct Response {
+    int kind = 0;     // ICELK_DETECTOR_MIN_EIG | ICELK_DETECTOR_HARRIS
+    double k = 0;     // Harris: the free parameter; not read for the smaller eigenvalue
+    int tail = 0;     // Harris: icelk_set_variant "harris_tail" (the any-blockSize kernel only)
+    bool operator==(const Response& o) const { return kind == o.kind && k == o.k && tail == o.tail; }
+};
 void launch_min_eig(hipStream_t s, const Level& img, int block_size, float* eig, const uint8_t* mask,
-                    int mask_pitch, unsigned* max_key, int variant = 0);
+                    int mask_pitch, unsigned* max_key, int variant = 0, const Response& resp = Response{});
 bool fused_block_size(int bs);
 // mode: 0 = the cell grid and the counters; | 1 = the key histogram too; | 2 = and the masked maximum D.cb.max_key (only where
 // the candidate buffer behind it is known to be this detection's: it may have been handed on since)
 void launch_detect_reset(hipStream_t s, DetectScratch& D, int ncell, int mode);
 // K6+K7: local maxima into per-workgroup regions of D.cb.raw (stream order, no host sync)
 void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int block_size, const uint8_t* mask,
-                       int mask_pitch, double quality, bool use_generic, float* eig_out_or_null, int variant = 0);
+                       int mask_pitch, double quality, bool use_generic, float* eig_out_or_null, int variant = 0,
+                       const Response& resp = Response{});
 // K6 + K7 in two passes for blockSize 3 / 5 / 7 / 10 (integer bracket of the map, exact arithmetic at the possible maxima
 // only): same regions, counts and max_key as launch_candidates' one-pass kernel.  quality <= 0: no threshold cut.
 bool launch_candidates_fast(hipStream_t s, DetectScratch& D, const Level& img, int block_size, const uint8_t* mask,

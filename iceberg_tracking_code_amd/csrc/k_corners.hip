@@ -1,4 +1,5 @@
-// k_corners.hip -- Shi-Tomasi corner detection for gfx950.
+// k_corners.hip -- corner detection for gfx950: the Shi-Tomasi response (smaller eigenvalue) or, under icelk_set_detector,
+// the Harris response det - k tr^2 of the same covariance sums (harris_of below: the two forms).
 //
 // Replaces cv2.goodFeaturesToTrack(frame_gray, mask=mask, **feature_params) at
 // s1_lucaskanade_tracking.py:437 (s0_1_test_lucaskanade_tracking.py:167).  Arithmetic restated from OpenCV's
@@ -14,7 +15,11 @@
 //         ~8 B per local maximum written.
 //         The quality threshold (max * qualityLevel) is applied to the candidate list afterwards
 //         (k_filter): for max > 0,  v > thr && v == dilate3x3(threshold_tozero(eig))  <=>  v > thr && v >= its
-//         8 raw neighbours; for max <= 0 OpenCV finds no corner either.
+//         8 raw neighbours; for max <= 0 OpenCV finds no corner either.  With the Harris response that case is an
+//         ordinary one (about half of a textured frame is negative, a pure ramp everywhere) and the cut
+//         quality_threshold() returns for it is negative, so it is the candidate kernels that keep it empty: the
+//         non-max test of the strip kernel -- one test for its FAST and non-FAST row phases -- lists v > 0 only, and
+//         k_nms_collect compares v with a dilated value that is never below 0.
 //         (k_corners_fast.hip: the same candidates in two passes, ICELK_TWO_PASS_CORNERS=1.)
 //   K6, K7 separate (k_min_eig, k_nms_collect): any other blockSize, ICELK_GENERIC_CORNERS=1 and the arithmetic
 //         variants of icelk_set_variant.
@@ -117,6 +122,32 @@ __device__ __forceinline__ float min_eig_of(double s0, double s1, double s2, int
     const float d = __fsub_rn(a, c);
     const float r = (variant & 4) ? fmaf(b, b, __fmul_rn(d, d)) : __fadd_rn(__fmul_rn(d, d), __fmul_rn(b, b));
     return __fsub_rn(__fadd_rn(a, c), sqrtf(r));
+}
+
+// The Harris response of the same three box sums, which are NOT halved as calcMinEigenVal halves them.  Every operation
+// is rounded to float32 and nothing is fused: calcHarris' float lanes,
+//     t = a + c;  R = (a c - b b) - (kf t) t;   kf = (float)k
+// tail (icelk_set_variant "harris_tail" 1, the any-blockSize kernel only): OpenCV's scalar tail, where k stays a double,
+//     R = (float)((double)(fl(a c) - fl(b b)) - (k (double)fl(a + c)) (double)fl(a + c))
+// Both are written from knowledge of upstream OpenCV; like the rest of the detector, parity with OpenCV is unpinned
+// (DESIGN.md 2).  tests/harris_restatement.py states both in numpy.
+__device__ __forceinline__ float harris_of(float a, float b, float c, float kf)
+{
+    const float t = __fadd_rn(a, c);
+    return __fsub_rn(__fsub_rn(__fmul_rn(a, c), __fmul_rn(b, b)), __fmul_rn(__fmul_rn(kf, t), t));
+}
+__device__ __forceinline__ float harris_tail_of(float a, float b, float c, double k)
+{
+    const double t = (double)__fadd_rn(a, c);
+    const double det = (double)__fsub_rn(__fmul_rn(a, c), __fmul_rn(b, b));
+    return (float)__dsub_rn(det, __dmul_rn(__dmul_rn(k, t), t));
+}
+// what the any-blockSize kernel computes at a pixel: resp.kind picks the response, resp.tail the Harris form
+__device__ __forceinline__ float response_of(double s0, double s1, double s2, int variant, const Response& resp)
+{
+    if (resp.kind != ICELK_DETECTOR_HARRIS) return min_eig_of(s0, s1, s2, variant);
+    return resp.tail ? harris_tail_of((float)s0, (float)s1, (float)s2, resp.k)
+                     : harris_of((float)s0, (float)s1, (float)s2, (float)resp.k);
 }
 
 // wave-reduce `best` and publish it; the atomic is skipped when the published maximum is already as large
@@ -247,8 +278,12 @@ __device__ __forceinline__ void min_eig_strip(const double (&Sm)[3][N], float (&
     }
 }
 
-template <int BS, bool FRESH, bool FAST>
-__device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int w, int h, int pitch, float k0, float k1,
+// HARRIS: the row task takes harris_of (four multiplications, three additions or subtractions, no square root, so no band
+// and no wave-wide test) in place of the smaller eigenvalue; kf is read by that arm only.  Everything else -- the roll, the
+// sums, the map, the masked maximum, the non-max test -- is the same text for both responses, and the !HARRIS
+// instantiations are the code they were before the parameter existed.
+template <int BS, bool FRESH, bool FAST, bool HARRIS>
+__device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int w, int h, int pitch, float k0, float k1, float kf,
                                            const uint8_t* __restrict__ mask, int mask_pitch, unsigned* __restrict__ max_key,
                                            unsigned long long* __restrict__ raw, int* __restrict__ blk_count,
                                            float* __restrict__ eig_out, uint8_t* smem, int* s_cnt)
@@ -375,7 +410,12 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
                 // blockSize 3 keeps sqrtf: measured alone, its kernel is 69-71 us with sqrtf and 75-77 with the band form (the
                 // parent: 75-76), though the band form issues fewer instructions -- its row phase is the short one (two additions
                 // per output and plane) and the wave-wide test and branch sit in the middle of it
-                min_eig_strip<C::RX, BS != 3>(Sm, e);
+                if constexpr (HARRIS) {
+#pragma unroll
+                    for (int k = 0; k < C::RX; k++) e[k] = harris_of((float)Sm[0][k], (float)Sm[1][k], (float)Sm[2][k], kf);
+                } else {
+                    min_eig_strip<C::RX, BS != 3>(Sm, e);
+                }
                 *reinterpret_cast<float4*>(Er + (er & 7) * C::NT + C::RX * g) = make_float4(e[0], e[1], e[2], e[3]);
                 const int y = y0 - 1 + er;
                 if constexpr (FAST) {
@@ -457,6 +497,11 @@ __device__ __forceinline__ void strip_body(const uint8_t* __restrict__ img, int 
 // Round 8 (profiles/r08_corner_resources.json): 148 at blockSize 10, three waves, no scratch; blockSize 7 now needs exactly the 128
 // of a fourth wave, so a change of compiler or of this body can cost blockSize 7 that wave -- look at the resource remarks
 // (-Rpass-analysis=kernel-resource-usage) after either.
+// The response is a compile-time parameter of the body, and each response has an entry point of its own: k_eig_strip keeps its
+// name, its argument list and with them its kernel-argument layout, so its code object is the one it was before the Harris
+// response existed (tools/isa_compare.py against the parent); k_harris_strip, below, is the same text with kf = (float)k
+// behind the same arguments.  TWO COPIES of the dispatch (rolling / inside_x / the three arms): a change to one is a change
+// to both.  (One helper for both was tried: the Shi-Tomasi instantiations then came out with another register allocation.)
 template <int BS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_eig_strip(const uint8_t* __restrict__ img, int w, int h, int pitch, float k0,
                                                     float k1, const uint8_t* __restrict__ mask, int mask_pitch,
@@ -473,11 +518,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
     // all TW output columns of the strip are inside the frame (every strip but a narrower last one)
     const bool inside_x = ((int)blockIdx.x + 1) * C::TW <= w;
     if (rolling && inside_x && !mask && !eig_out)
-        strip_body<BS, false, true>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
+        strip_body<BS, false, true, false>(img, w, h, pitch, k0, k1, 0.f, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
     else if (rolling)
-        strip_body<BS, false, false>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
+        strip_body<BS, false, false, false>(img, w, h, pitch, k0, k1, 0.f, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
     else
-        strip_body<BS, true, false>(img, w, h, pitch, k0, k1, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
+        strip_body<BS, true, false, false>(img, w, h, pitch, k0, k1, 0.f, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
+}
+
+// Registers (the compiler's resource remarks, profiles/harris_strip_resources.json): 84 / 112 / 134 / 148 VGPRs at blockSize
+// 3 / 5 / 7 / 10 against k_eig_strip's 83 / 110 / 128 / 148, no scratch, no spill.  blockSize 7 is over the 128 of a fourth
+// wave per SIMD, which k_eig_strip<7> holds exactly: three waves here.  The body below is k_eig_strip's, copied: keep the
+// two in step.
+template <int BS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void k_harris_strip(const uint8_t* __restrict__ img, int w, int h, int pitch, float k0,
+                                                    float k1, const uint8_t* __restrict__ mask, int mask_pitch,
+                                                    unsigned* __restrict__ max_key,
+                                                    unsigned long long* __restrict__ raw, int* __restrict__ blk_count,
+                                                    float* __restrict__ eig_out, float kf)
+{
+    using C = StripCfg<BS>;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    __shared__ int s_cnt[C::NSUB];
+    const int ys = (int)blockIdx.y * C::SH - 1 - C::AN;
+    // pixel rows ys - 1 .. ys + NROWS are read by the rolling form: such a strip has all its output rows inside the frame
+    const bool rolling = ys - 1 >= 0 && ys + C::NROWS <= h - 1;
+    // all TW output columns of the strip are inside the frame (every strip but a narrower last one)
+    const bool inside_x = ((int)blockIdx.x + 1) * C::TW <= w;
+    if (rolling && inside_x && !mask && !eig_out)
+        strip_body<BS, false, true, true>(img, w, h, pitch, k0, k1, kf, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
+    else if (rolling)
+        strip_body<BS, false, false, true>(img, w, h, pitch, k0, k1, kf, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
+    else
+        strip_body<BS, true, false, true>(img, w, h, pitch, k0, k1, kf, mask, mask_pitch, max_key, raw, blk_count, eig_out, smem, s_cnt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -489,7 +561,7 @@ constexpr int EIG_TH = 16;
 __global__ __launch_bounds__(256) void k_min_eig(const uint8_t* __restrict__ img, int w, int h, int pitch, int bs,
                                                  float k0, float k1, float* __restrict__ eig,
                                                  const uint8_t* __restrict__ mask, int mask_pitch,
-                                                 unsigned* __restrict__ max_key, int variant)
+                                                 unsigned* __restrict__ max_key, int variant, Response resp)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int anchor = bs / 2;
@@ -540,7 +612,7 @@ __global__ __launch_bounds__(256) void k_min_eig(const uint8_t* __restrict__ img
             s1 += r[eh * EIG_TW + k * EIG_TW];
             s2 += r[2 * eh * EIG_TW + k * EIG_TW];
         }
-        const float v = min_eig_of(s0, s1, s2, variant);
+        const float v = response_of(s0, s1, s2, variant, resp);
         eig[(size_t)y * w + x] = v;
         if (!mask || mask[(size_t)y * mask_pitch + x]) {
             const unsigned k = ordered_key(v);
@@ -572,6 +644,8 @@ __global__ __launch_bounds__(256) void k_nms_collect(const float* __restrict__ e
         const float v = eig[(size_t)y * w + x];
         if (!(v > thr) || v == 0.f) continue;
         if (mask && !mask[(size_t)y * mask_pitch + x]) continue;
+        // m >= 0 whatever the map holds, so a negative v -- which passes v > thr when the masked maximum, and with it thr, is
+        // negative (the Harris response over a ramp) -- never equals it: max <= 0 lists nothing
         float m = 0.f;  // dilate of the TOZERO-thresholded map (includes the centre)
 #pragma unroll
         for (int dy = -1; dy <= 1; dy++)
@@ -590,12 +664,16 @@ __global__ __launch_bounds__(256) void k_nms_collect(const float* __restrict__ e
 
 template <int BS>
 void launch_strip(hipStream_t s, const Level& img, float k0, float k1, const uint8_t* mask, int mask_pitch, CandBuf& cb,
-                  float* eig_out)
+                  float* eig_out, const Response& resp)
 {
     using C = StripCfg<BS>;
     dim3 grid((img.w + C::TW - 1) / C::TW, (img.h + C::SH - 1) / C::SH);
-    hipLaunchKernelGGL((k_eig_strip<BS>), grid, dim3(C::NT), C::LDS_BYTES, s, img.ptr, img.w, img.h, img.pitch, k0, k1, mask,
-                       mask_pitch, cb.max_key, cb.raw, cb.blk_count, eig_out);
+    if (resp.kind == ICELK_DETECTOR_HARRIS)
+        hipLaunchKernelGGL((k_harris_strip<BS>), grid, dim3(C::NT), C::LDS_BYTES, s, img.ptr, img.w, img.h, img.pitch, k0, k1,
+                           mask, mask_pitch, cb.max_key, cb.raw, cb.blk_count, eig_out, (float)resp.k);
+    else
+        hipLaunchKernelGGL((k_eig_strip<BS>), grid, dim3(C::NT), C::LDS_BYTES, s, img.ptr, img.w, img.h, img.pitch, k0, k1, mask,
+                           mask_pitch, cb.max_key, cb.raw, cb.blk_count, eig_out);
     cb.nblk = (int)(grid.x * grid.y) * C::NSUB;
     cb.region = C::TW * C::SUB;
 }
@@ -651,7 +729,7 @@ size_t candidate_blocks(int w, int h)
 
 // K6 alone, writing the map with the any-blockSize kernel.
 void launch_min_eig(hipStream_t s, const Level& img, int block_size, float* eig, const uint8_t* mask,
-                    int mask_pitch, unsigned* max_key, int variant)
+                    int mask_pitch, unsigned* max_key, int variant, const Response& resp)
 {
     float k0, k1;
     sobel_scale(block_size, &k0, &k1);
@@ -664,31 +742,34 @@ void launch_min_eig(hipStream_t s, const Level& img, int block_size, float* eig,
     }
     dim3 grid((img.w + EIG_TW - 1) / EIG_TW, (img.h + EIG_TH - 1) / EIG_TH);
     hipLaunchKernelGGL(k_min_eig, grid, dim3(256), lds, s, img.ptr, img.w, img.h, img.pitch, block_size, k0, k1, eig,
-                       mask, mask_pitch, max_key, variant);
+                       mask, mask_pitch, max_key, variant, resp);
 }
 
 // Candidate collection (K6+K7) into regions of D.cb.raw (stream order, no host sync).
 void launch_candidates(hipStream_t s, DetectScratch& D, const Level& img, int block_size, const uint8_t* mask,
-                       int mask_pitch, double quality, bool use_generic, float* eig_out_or_null, int variant)
+                       int mask_pitch, double quality, bool use_generic, float* eig_out_or_null, int variant, const Response& resp)
 {
-    if (variant) use_generic = true;     // the named variants live in the any-blockSize kernel only
+    const bool harris = resp.kind == ICELK_DETECTOR_HARRIS;
+    if (variant || (harris && resp.tail)) use_generic = true;     // the named variants live in the any-blockSize kernel only
     // ICELK_TWO_PASS_CORNERS=1: the two-pass form (k_corners_fast.hip: integer bracket of the map + exact arithmetic at the
     // possible maxima) -- a third statement of the arithmetic, bit-identical, measured and not the default
     const bool two_pass = D.cb.acand != nullptr && getenv("ICELK_TWO_PASS_CORNERS") != nullptr;   // scratch: at icelk_create, under the same switch
-    if (two_pass && !use_generic && fused_block_size(block_size) && !eig_out_or_null &&
+    // its bracket eps(p) is derived for the smaller eigenvalue and does not hold for det - k tr^2: with the Harris response
+    // the switch is ignored and the one-pass strip kernel runs
+    if (two_pass && !harris && !use_generic && fused_block_size(block_size) && !eig_out_or_null &&
         launch_candidates_fast(s, D, img, block_size, mask, mask_pitch, quality))
         return;
     if (!use_generic && fused_block_size(block_size)) {
         float k0, k1;
         sobel_scale(block_size, &k0, &k1);
         switch (block_size) {
-            case 3: launch_strip<3>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null); break;
-            case 5: launch_strip<5>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null); break;
-            case 7: launch_strip<7>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null); break;
-            default: launch_strip<10>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null); break;
+            case 3: launch_strip<3>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null, resp); break;
+            case 5: launch_strip<5>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null, resp); break;
+            case 7: launch_strip<7>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null, resp); break;
+            default: launch_strip<10>(s, img, k0, k1, mask, mask_pitch, D.cb, eig_out_or_null, resp); break;
         }
     } else {
-        launch_min_eig(s, img, block_size, D.eig, mask, mask_pitch, D.cb.max_key, variant);
+        launch_min_eig(s, img, block_size, D.eig, mask, mask_pitch, D.cb.max_key, variant, resp);
         D.cb.nblk = 0;
         D.cb.region = 256 * NMS_ROWS;
         if (img.w >= 3 && img.h >= 3) {

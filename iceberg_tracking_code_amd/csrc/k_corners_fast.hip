@@ -9,6 +9,9 @@
 // (DESIGN.md 4.2 has the numbers and the reason), because a textured frame has 2.6 * 10^5 local maxima above
 // max * qualityLevel that all need their exact value before the top-K pruning of the min-distance stage can drop 2/3 of
 // them.  It is kept because the bracket is the tool for that next step (pruning on the bounds, before the exact pass).
+// Shi-Tomasi only: the bracket eps(p) below is derived for the smaller eigenvalue and does not hold for the Harris response
+// det - k tr^2, and no bound has been derived for that.  With the Harris detector selected (icelk_set_detector) the switch is
+// ignored and the one-pass strip kernel runs (launch_candidates, k_corners.hip).
 //
 // Idea.  A one-pass kernel evaluates OpenCV's float pipeline at every pixel (round 2's tile kernel: 243 lane-operations per
 // pixel at blockSize 10 -- Sobel in float, three planes of double-precision box sums with a 9-px halo, a correctly rounded

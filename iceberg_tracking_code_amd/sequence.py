@@ -82,6 +82,8 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
     crop           (left, top, right, bottom) of the calibration workbook (camtools.py:147-150) or None
     mask           H x W uint8 array (255 = detect here), or
     mask_polygon   (maskpoly, cropleft, croptop): rasterised on the device as s1:285-291 / camtools.py:184-211 do
+    feature_params cv2.goodFeaturesToTrack's keywords (default: the reference's, s1:240-244); `useHarrisDetector` (False)
+                   and `k` (0.04) are among them and go with every detection, those prepared ahead included
     startlist      offsets into the list, each walked separately (s1:304)
     on_segment     optional callback(npz path, tracks, trackquality), e.g. a projection step
     decoder        "pil": photos are decoded on the host; "device": only their Huffman decoding is (see above) -- same

@@ -60,6 +60,10 @@ class SegmentTracker:
 
     Frames are given as host arrays (`push`), as device pointers (`push_device`) or generated on the
     device (`push_synth`).  Three slots rotate: previous frame, current frame, and one being uploaded.
+
+    feature_params are cv2.goodFeaturesToTrack's: maxCorners, qualityLevel, minDistance, blockSize and, optional,
+    useHarrisDetector (default False: Shi-Tomasi) and k (default 0.04; read with the Harris detector only).  They go with
+    every detection the tracker starts or prepares ahead.
     """
 
     def __init__(self, width, height, track_len, feature_params=None, lk_params=None, mask=None, max_pts=1 << 18,
@@ -271,7 +275,15 @@ class SegmentTracker:
     # -- the loop body (s1:313-450) -------------------------------------------------------------
     def _detect_begin(self, slot):
         self.ctx.seg_detect_begin(slot, self.fp["maxCorners"], self.fp["qualityLevel"], self.fp["minDistance"],
-                                  self.use_mask, self.fp.get("blockSize", 3))
+                                  self.use_mask, self.fp.get("blockSize", 3), **self._detector_kw())
+
+    def _detector_kw(self):
+        """feature_params' useHarrisDetector / k as the keywords of the detector calls.  Parameters that do not name the
+        detector give none: the calls are then the very ones they were, under the handle's own setting (Shi-Tomasi unless
+        Context.set_detector said otherwise)"""
+        if "useHarrisDetector" not in self.fp:
+            return {}
+        return dict(useHarrisDetector=bool(self.fp["useHarrisDetector"]), k=float(self.fp.get("k", 0.04)))
 
     MAX_AHEAD = 6
 
@@ -412,7 +424,7 @@ class SegmentTracker:
             self._begun_upto = d
         d = max(self._begun_upto, self._prep_upto, c) // T * T + T
         if self._prep_upto <= self._begun_upto and 1 <= d - c <= self.prepare_ahead and slot_of.get(d - c) is not None:
-            self.ctx.seg_detect_prepare(slot_of[d - c], self.use_mask, self.fp.get("blockSize", 3))
+            self.ctx.seg_detect_prepare(slot_of[d - c], self.use_mask, self.fp.get("blockSize", 3), **self._detector_kw())
             self._prep_upto = d
 
     def plot_closed(self, width=PLOT_WIDTH, stamp="", quality=PLOT_QUALITY):

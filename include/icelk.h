@@ -90,6 +90,10 @@ int icelk_set_fb_distance(icelk_t* h, int form);
  *                        1e-3 px between the forms, none changes status)
  *   "sobel_fma"  bit 0   the Sobel column pass fused (4.x SymmColumnSmallVec_32f in an FMA3 build); bit 1: the row pass fused
  *   "eig_fma"    1       calcMinEigenVal's (a-c)^2 + b^2 as one fused multiply-add
+ *   "harris_tail" 1      the Harris response (icelk_set_detector) as calcHarris' scalar tail computes it, k kept a double:
+ *                        (float)((double)(fl(a c) - fl(b b)) - (k (double)fl(a + c)) (double)fl(a + c)); 0 = its float lanes.
+ *                        Read only while the Harris detector is selected (and by icelk_harris_map); on the test frames the two
+ *                        forms differ in the last bit of about half the map and give the same corner list.
  * (the corner SET is the same under all of them on the test frames, the order of near-equal corners changes.)
  * A cv2 cross-check that finds one of them to be what the reference's OpenCV build does flips this switch.
  * One name is a testing aid and changes no result:
@@ -167,7 +171,29 @@ int icelk_set_mask_polygon(icelk_t* h, const double* poly_xy, int n, double crop
 int icelk_download_mask(icelk_t* h, uint8_t* host_mask, int stride, int* w, int* h_);
 /* cornerMinEigenVal map of the slot (debug / parity). */
 int icelk_min_eig_map(icelk_t* h, int slot, int block_size, float* host_out, int stride_elems);
-/* Shi-Tomasi corners in response order.  max_corners <= 0 = unlimited (up to max_pts).
+/* Which corner response the detector ranks by: cv2.goodFeaturesToTrack's useHarrisDetector / k.
+ *   ICELK_DETECTOR_MIN_EIG  the smaller eigenvalue of the blockSize x blockSize covariance sums (Shi-Tomasi; the default; k is
+ *                           ignored and kept as given)
+ *   ICELK_DETECTOR_HARRIS   det - k tr^2 of the same sums a = S dx^2, b = S dx dy, c = S dy^2, which are NOT halved as
+ *                           calcMinEigenVal halves them.  Default form, calcHarris' float lanes: every operation rounded to
+ *                           float32, nothing fused,  t = a + c;  R = (a c - b b) - (kf t) t,  kf = (float)k.  The build-dependent
+ *                           alternative is icelk_set_variant "harris_tail" 1.  Both forms are written from knowledge of upstream
+ *                           OpenCV; as for the rest of the detector, parity with OpenCV is unpinned, a numpy
+ *                           restatement (tests/harris_restatement.py) pins them.
+ * The setting is snapshotted when a detection's candidate stage is enqueued (icelk_good_features, icelk_seg_detect, _begin,
+ * _prepare): a detection in flight keeps the detector it was begun with, whatever is set afterwards, and _begin adopts
+ * prepared candidates only if kind and k match too.  A map whose masked maximum is <= 0 yields no corner (with Harris a real
+ * case: a pure ramp is negative everywhere).  The opt-in two-pass candidate kernel (ICELK_TWO_PASS_CORNERS) serves the smaller
+ * eigenvalue only: with Harris selected the switch is ignored.  ICELK_EARG for an unknown kind or a non-finite k, before any
+ * GPU work. */
+#define ICELK_DETECTOR_MIN_EIG 0
+#define ICELK_DETECTOR_HARRIS 1
+int icelk_set_detector(icelk_t* h, int kind, double k);
+int icelk_get_detector(icelk_t* h, int* kind, double* k); /* either pointer may be NULL */
+/* cv2.cornerHarris(src, blockSize, 3, k) of the slot: the twin of icelk_min_eig_map.  k is this call's own; the handle's
+ * detector setting is neither read nor changed ("harris_tail" is read). */
+int icelk_harris_map(icelk_t* h, int slot, int block_size, double k, float* host_out, int stride_elems);
+/* Corners in response order (Shi-Tomasi, or Harris under icelk_set_detector).  max_corners <= 0 = unlimited (up to max_pts).
  * *out_n == 0 corresponds to cv2 returning None (guarded at s1:445). */
 int icelk_good_features(icelk_t* h, int slot, int use_mask, int max_corners, double quality_level,
                         double min_distance, int block_size, float* out_xy, int cap, int* out_n);
@@ -180,7 +206,7 @@ int icelk_detect_stats(icelk_t* h, int* n_candidates, int* n_accepted);
  * handed to the 3x3 tie pass, [4] pixels listed as possible carriers of the maximum, [5] tiles whose such list overflowed,
  * [6] longest tile list, [7] listed pixels that got their exact value in the one-pixel pass (certain, above the cut). */
 int icelk_detect_fast_stats(icelk_t* h, int frame_w, int frame_h, long long* out);
-/* The masked maximum of the eigenvalue map as the candidate stage of the latest detection (or icelk_min_eig_map) on this
+/* The masked maximum of the response map (eigenvalue or Harris) as the candidate stage of the latest detection (or icelk_min_eig_map / icelk_harris_map) on this
  * handle published it: the order-preserving key of the float (sign set: ~bits, else bits | 0x80000000), 0 if no pixel
  * counted (diagnostics and tests; waits for the device). */
 int icelk_detect_max_key(icelk_t* h, unsigned* out_key);
@@ -225,7 +251,7 @@ int icelk_seg_switch(icelk_t* h);
 /* Optional, ahead of _begin: produce the corner candidates (min-eigenvalue map + non-max test, the part of
  * s1:437 that depends on nothing but the frame and blockSize) of a frame that is already in `slot`, on a stream of
  * its own and into a spare buffer (three exist: two detections in flight + one prepared), while earlier detections are
- * still in their min-distance stage.  A later _begin for the same slot/frame/blockSize/mask adopts the result;
+ * still in their min-distance stage.  A later _begin for the same slot/frame/blockSize/mask/detector adopts the result;
  * otherwise it is dropped.  Results are identical either way. */
 int icelk_seg_detect_prepare(icelk_t* h, int slot, int use_mask, int block_size);
 int icelk_seg_track(icelk_t* h, int slot_prev, int slot_next, int win_w, int win_h, int max_level,
