@@ -159,6 +159,8 @@ def test_ramp_gives_no_corner_and_no_candidate(hctx):
     assert want.max() <= 0
     assert hctx.good_features(0, 0, 0.01, 5, False, 5, useHarrisDetector=True, k=0.04) is None
     assert hctx.detect_stats()["candidates"] == 0
+    # ... and the maximum they publish, from signed extremes of the bits in place of keys, is the map's negative maximum
+    assert want.max() < 0 and hctx.detect_max_key() == _key(want.max()) and hctx.detect_max_key() < 0x80000000
 
 
 @pytest.mark.parametrize("bs", [3, 4])
