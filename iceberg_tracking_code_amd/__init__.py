@@ -16,7 +16,7 @@ from .tracker import (REF_FB_THRESHOLD, REF_FEATURE_PARAMS, REF_LK_PARAMS, Segme
 from .utm import CameraModel, REF_UTM_FILTER, cam_to_utm, project_segment, project_tracks, utm_name  # noqa: F401
 from .sequence import track_image_sequence  # noqa: F401
 from .crop import crop_image_sequence  # noqa: F401
-from .gridding import bin_velocities, create_grid_across_fjord, points_in_polygon  # noqa: F401
+from .gridding import bin_velocities, create_grid_across_fjord, grid_cell_stats_host, points_in_polygon  # noqa: F401
 from .day_grid import closest_image, utm_to_gridded_utm, utm_to_gridded_utm_days  # noqa: F401
 from .postprocess import (VelocityCube, average_periods, average_spatially_temporally, combine_npzs,  # noqa: F401
                           daily_averages, npz_to_csv, npz_to_mat, save_csv, velocities_to_regular_grid)

@@ -51,6 +51,14 @@ class JpegCropStats(C.Structure):
     _fields_ = [("huff", JpegHuffStats), ("route", C.c_uint32), ("blocks", C.c_uint32), ("budget", C.c_uint64), ("stream_len", C.c_uint64)]
 
 
+class GridStats(C.Structure):
+    """icelk_grid_stats_t: six host float64 arrays laid out as mean_u is"""
+    _fields_ = [(k, f64p) for k in ("std_u", "std_v", "median_u", "median_v", "mad_u", "mad_v")]
+
+
+grid_stats_p = C.POINTER(GridStats)
+
+
 class MapPanel(C.Structure):
     """icelk_map_panel_t"""
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("bar_x0", C.c_int32), ("bar_w", C.c_int32),
@@ -236,6 +244,13 @@ SIGNATURES = {
     "icelk_grid_bin_windows": (C.c_int, [handle_p, f64p, f64p, f64p, f64p, f64p, C.c_int, i64p, i32p, i32p, i32p,
                                          C.c_int, i64p, i64p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                          C.c_int, C.c_int, u8p, i32p, f64p, f64p, f64p, i32p, f64p, f64p, f64p]),
+    "icelk_grid_bin_stats": (C.c_int, [handle_p, f64p, f64p, f64p, f64p, C.c_int, C.c_double, C.c_double, C.c_double,
+                                       C.c_int, C.c_int, u8p, i32p, f64p, f64p, f64p, grid_stats_p]),
+    "icelk_grid_bin_windows_stats": (C.c_int, [handle_p, f64p, f64p, f64p, f64p, f64p, C.c_int, i64p, i32p, i32p, i32p,
+                                               C.c_int, i64p, i64p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                               C.c_double, C.c_int, C.c_int, u8p, i32p, f64p, f64p, f64p, i32p, f64p,
+                                               f64p, f64p, grid_stats_p]),
+    "icelk_grid_cell_stats_host": (C.c_int, [f64p, C.c_int, f64p, f64p, f64p]),
     "icelk_cube_set": (C.c_int, [handle_p, f64p, f64p, f64p, C.c_int, C.c_int]),
     "icelk_cube_release": (C.c_int, [handle_p]),
     "icelk_cube_average": (C.c_int, [handle_p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, f64p, f64p, f64p, f64p,

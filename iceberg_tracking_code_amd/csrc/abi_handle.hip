@@ -17,6 +17,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "jpeg_thumb", "map_inset",
     "png_filter", "png_parse", "png_scan", "png_pack", "png_adler",
     "resize_rows", "resize_cols",
+    "grid_segments", "grid_std", "grid_select",
 };
 
 std::string g_create_err;

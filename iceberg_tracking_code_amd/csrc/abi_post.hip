@@ -2,6 +2,7 @@
 // the velocity cube and its averages.
 #include "icelk_ctx.h"
 #include "cube_means.h"
+#include "grid_stats.h"
 
 namespace icelk {
 
@@ -15,6 +16,10 @@ struct GridDev {
     void* sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
     int key_cap = 0, nseg = 0, key_bits = 0;
+    // only with statistics (alloc_stats): the segment table, the select's staged order keys (u, then v), the six outputs
+    int *seg_begin = nullptr, *seg_count = nullptr;               // nseg each
+    unsigned long long* stat_keys = nullptr;                      // 2 * key_cap
+    icelk_grid_stats_t d_stats = {};                              // nseg each; null members: no statistics
 
     void alloc(DevBufs& B, int key_cap_, int nseg_)
     {
@@ -28,6 +33,14 @@ struct GridDev {
         d_mv = B.get<double>((size_t)nseg);
         d_sp = B.get<double>((size_t)nseg);
     }
+    void alloc_stats(DevBufs& B)
+    {
+        seg_begin = B.get<int>((size_t)nseg);
+        seg_count = B.get<int>((size_t)nseg);
+        stat_keys = B.get<unsigned long long>(2 * (size_t)key_cap);
+        for (double** q : {&d_stats.std_u, &d_stats.std_v, &d_stats.median_u, &d_stats.median_v, &d_stats.mad_u, &d_stats.mad_v})
+            *q = B.get<double>((size_t)nseg);
+    }
     // the sort's scratch, for key_cap keys: nothing is allocated between the kernels (the day gridder times them)
     void alloc_sort(DevBufs& B, hipStream_t s)
     {
@@ -38,12 +51,13 @@ struct GridDev {
 };
 
 // Zero the key counter, assign (the caller's launch, with whatever it enqueues in front of it), read the key count back,
-// sort, reduce, and enqueue the copies of the four per-segment outputs; the caller synchronises.  t, if given: t[0]
-// ends behind the assign launch (the caller records its start), t[1] goes around sort + reduce -- the read-back between
-// them is not timed.
+// sort, reduce, and enqueue the copies of the four per-segment outputs; the caller synchronises.  With `stats` (the
+// host's six arrays; G.alloc_stats has run) the segment table, the standard deviations and the selections follow the
+// reduce on the same stream and their outputs are copied too.  t, if given: t[0] ends behind the assign launch (the
+// caller records its start), t[1] goes around sort + reduce (+ statistics) -- the read-back between them is not timed.
 template <typename Assign>
 static int grid_core(Ctx* c, const GridDev& G, Assign assign, const char* assign_name, EvPair* t, int* count,
-                     double* mean_u, double* mean_v, double* speed)
+                     double* mean_u, double* mean_v, double* speed, const icelk_grid_stats_t* stats)
 {
     const hipStream_t s = c->stream;
     HIPCHK(c, hipMemsetAsync(G.d_key_count, 0, sizeof(int), s));
@@ -68,12 +82,46 @@ static int grid_core(Ctx* c, const GridDev& G, Assign assign, const char* assign
     launch_grid_reduce(s, sorted, G.d_key_count, G.du, G.dv, G.nseg, G.d_count, G.d_mu, G.d_mv, G.d_sp);
     rc = check_launch(c, "grid_reduce");
     if (rc) return rc;
+    if (stats) {
+        {
+            ProfScope p(c, K_GRID_SEGMENTS);
+            launch_grid_segments(s, sorted, G.d_key_count, G.nseg, G.seg_begin, G.seg_count, G.d_stats);
+        }
+        {
+            ProfScope p(c, K_GRID_STD);
+            launch_grid_std(s, sorted, G.seg_begin, G.seg_count, G.du, G.dv, G.nseg, G.d_mu, G.d_mv, G.d_stats);
+        }
+        {
+            ProfScope p(c, K_GRID_SELECT);
+            launch_grid_select(s, sorted, G.seg_begin, G.seg_count, G.du, G.dv, G.nseg, G.stat_keys, (size_t)G.key_cap,
+                               G.d_stats);
+        }
+        rc = check_launch(c, "grid statistics");
+        if (rc) return rc;
+    }
     if (t) HIPCHK(c, hipEventRecord(t[1].b, s));
     HIPCHK(c, copy_n(count, G.d_count, (size_t)G.nseg, kD2H, s));
     HIPCHK(c, copy_n(mean_u, G.d_mu, (size_t)G.nseg, kD2H, s));
     HIPCHK(c, copy_n(mean_v, G.d_mv, (size_t)G.nseg, kD2H, s));
     HIPCHK(c, copy_n(speed, G.d_sp, (size_t)G.nseg, kD2H, s));
+    if (stats) {
+        double* const host[6] = {stats->std_u, stats->std_v, stats->median_u, stats->median_v, stats->mad_u, stats->mad_v};
+        const icelk_grid_stats_t& d = G.d_stats;
+        const double* const dev[6] = {d.std_u, d.std_v, d.median_u, d.median_v, d.mad_u, d.mad_v};
+        for (int k = 0; k < 6; k++) HIPCHK(c, copy_n(host[k], dev[k], (size_t)G.nseg, kD2H, s));
+    }
     return ICELK_OK;
+}
+
+// element t of a host array (grid_stats.h on the CPU: icelk_grid_cell_stats_host)
+struct PlainAt {
+    const double* a;
+    double operator()(int t) const { return a[t]; }
+};
+
+static bool stats_complete(const icelk_grid_stats_t* st)
+{
+    return st && st->std_u && st->std_v && st->median_u && st->median_v && st->mad_u && st->mad_v;
 }
 
 // run the projection kernel over `n` gathered tracks sitting in d_tracks_in and bring the results to the host
@@ -114,14 +162,6 @@ int check_projection_args(Ctx* c, const icelk_camera_t* cam, const icelk_utm_fil
     if (!cam || !filt) FAIL(c, ICELK_EARG, "camera / filter missing");
     if (!(filt->interval_s > 0)) FAIL(c, ICELK_EARG, "tracking interval must be positive");
     return ICELK_OK;
-}
-
-static double from_order_key(unsigned long long k)
-{
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double d;
-    memcpy(&d, &b, sizeof d);
-    return d;
 }
 
 static void cube_free(Ctx* c)
@@ -183,13 +223,15 @@ int icelk_points_in_polygon(icelk_t* h, const double* poly_xy, int n_poly, const
     return ICELK_OK;
 }
 
-int icelk_grid_bin(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n, double left,
-                   double top, double spacing, int cols, int rows, const uint8_t* cell_on, int* count, double* mean_u,
-                   double* mean_v, double* speed)
+// icelk_grid_bin, and with `stats` icelk_grid_bin_stats
+static int grid_bin(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n, double left,
+                    double top, double spacing, int cols, int rows, const uint8_t* cell_on, int* count, double* mean_u,
+                    double* mean_v, double* speed, const icelk_grid_stats_t* stats)
 {
     if (!h) return ICELK_EARG;
     Ctx* c = C(h);
     HIPCHK(c, hipSetDevice(c->device));
+    if (stats && !stats_complete(stats)) FAIL(c, ICELK_EARG, "a member of the statistics struct is null");
     if (n < 0 || cols <= 0 || rows <= 0 || !(spacing > 0) || !cell_on || !count || !mean_u || !mean_v || !speed ||
         (n > 0 && (!x || !y || !u || !v)))
         FAIL(c, ICELK_EARG, "bad gridding arguments");
@@ -207,6 +249,7 @@ int icelk_grid_bin(icelk_t* h, const double* x, const double* y, const double* u
     uint8_t* d_on = B.get<uint8_t>((size_t)ncells);
     const hipStream_t s = c->stream;
     G.alloc(B, key_cap, ncells);
+    if (stats) G.alloc_stats(B);
     G.alloc_sort(B, s);
     if (!B.ok()) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
     G.du = du;
@@ -222,22 +265,40 @@ int icelk_grid_bin(icelk_t* h, const double* x, const double* y, const double* u
         launch_grid_assign(s, dx, dy, n, left, top, spacing, cols, rows, d_on, G.keys, G.d_key_count, key_cap);
         return ICELK_OK;
     };
-    int rc = grid_core(c, G, assign, "grid_assign", nullptr, count, mean_u, mean_v, speed);
+    int rc = grid_core(c, G, assign, "grid_assign", nullptr, count, mean_u, mean_v, speed, stats);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(s));
     return ICELK_OK;
 }
 
-int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
-                           const double* t, int n, const int64_t* file_offset, const int* file_cam, const int* win_f0,
-                           const int* win_f1, int nfiles, const int64_t* t_lo, const int64_t* t_hi, int ncam, int nw,
-                           double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
-                           int* count, double* mean_u, double* mean_v, double* speed, int* sel_count, double* t_min,
-                           double* t_max, double* device_ms)
+int icelk_grid_bin(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n, double left,
+                   double top, double spacing, int cols, int rows, const uint8_t* cell_on, int* count, double* mean_u,
+                   double* mean_v, double* speed)
+{
+    return grid_bin(h, x, y, u, v, n, left, top, spacing, cols, rows, cell_on, count, mean_u, mean_v, speed, nullptr);
+}
+
+int icelk_grid_bin_stats(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n,
+                         double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
+                         int* count, double* mean_u, double* mean_v, double* speed, const icelk_grid_stats_t* stats)
+{
+    if (!h) return ICELK_EARG;
+    if (!stats) FAIL(C(h), ICELK_EARG, "the statistics struct is null");
+    return grid_bin(h, x, y, u, v, n, left, top, spacing, cols, rows, cell_on, count, mean_u, mean_v, speed, stats);
+}
+
+// icelk_grid_bin_windows, and with `stats` icelk_grid_bin_windows_stats
+static int grid_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                            const double* t, int n, const int64_t* file_offset, const int* file_cam, const int* win_f0,
+                            const int* win_f1, int nfiles, const int64_t* t_lo, const int64_t* t_hi, int ncam, int nw,
+                            double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
+                            int* count, double* mean_u, double* mean_v, double* speed, int* sel_count, double* t_min,
+                            double* t_max, double* device_ms, const icelk_grid_stats_t* stats)
 {
     if (!h) return ICELK_EARG;
     Ctx* c = C(h);
     HIPCHK(c, hipSetDevice(c->device));
+    if (stats && !stats_complete(stats)) FAIL(c, ICELK_EARG, "a member of the statistics struct is null");
     if (n < 0 || nfiles < 1 || ncam < 1 || nw < 1 || cols <= 0 || rows <= 0 || !(spacing > 0) || !file_offset ||
         !file_cam || !win_f0 || !win_f1 || !t_lo || !t_hi || !cell_on || !count || !mean_u || !mean_v || !speed ||
         !sel_count || !t_min || !t_max || (n > 0 && (!x || !y || !u || !v || !t)))
@@ -270,6 +331,9 @@ int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const d
     memset(sel_count, 0, sizeof(int) * nslot);
     memset(t_min, 0, sizeof(double) * nslot);
     memset(t_max, 0, sizeof(double) * nslot);
+    if (stats)
+        for (double* q : {stats->std_u, stats->std_v, stats->median_u, stats->median_v, stats->mad_u, stats->mad_v})
+            std::fill(q, q + nseg, __builtin_nan(""));
     if (device_ms) *device_ms = 0.0;
     if (n == 0) return ICELK_OK;
     DevBufs B;
@@ -288,6 +352,7 @@ int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const d
     long long* d_hi = B.get<long long>((size_t)nslot);
     uint8_t* d_on = B.get<uint8_t>((size_t)ncells);
     G.alloc(B, key_cap, nseg);
+    if (stats) G.alloc_stats(B);
     int* d_sel = B.get<int>((size_t)nslot);
     unsigned long long* d_tmin = B.get<unsigned long long>((size_t)nslot);
     unsigned long long* d_tmax = B.get<unsigned long long>((size_t)nslot);
@@ -324,7 +389,7 @@ int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const d
                                spacing, cols, rows, d_on, G.keys, G.d_key_count, key_cap, d_sel, d_tmin, d_tmax);
         return ICELK_OK;
     };
-    int rc = grid_core(c, G, assign, "grid_day_assign", device_ms ? timer : nullptr, count, mean_u, mean_v, speed);
+    int rc = grid_core(c, G, assign, "grid_day_assign", device_ms ? timer : nullptr, count, mean_u, mean_v, speed, stats);
     if (rc) return rc;
     HIPCHK(c, copy_n(sel_count, d_sel, (size_t)nslot, kD2H, s));
     std::vector<unsigned long long> kmin(nslot), kmax(nslot);
@@ -342,6 +407,40 @@ int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const d
         HIPCHK(c, hipEventElapsedTime(&b, timer[1].a, timer[1].b));
         *device_ms = (double)a + (double)b;
     }
+    return ICELK_OK;
+}
+
+int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                           const double* t, int n, const int64_t* file_offset, const int* file_cam, const int* win_f0,
+                           const int* win_f1, int nfiles, const int64_t* t_lo, const int64_t* t_hi, int ncam, int nw,
+                           double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
+                           int* count, double* mean_u, double* mean_v, double* speed, int* sel_count, double* t_min,
+                           double* t_max, double* device_ms)
+{
+    return grid_bin_windows(h, x, y, u, v, t, n, file_offset, file_cam, win_f0, win_f1, nfiles, t_lo, t_hi, ncam, nw,
+                            left, top, spacing, cols, rows, cell_on, count, mean_u, mean_v, speed, sel_count, t_min,
+                            t_max, device_ms, nullptr);
+}
+
+int icelk_grid_bin_windows_stats(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                                 const double* t, int n, const int64_t* file_offset, const int* file_cam,
+                                 const int* win_f0, const int* win_f1, int nfiles, const int64_t* t_lo,
+                                 const int64_t* t_hi, int ncam, int nw, double left, double top, double spacing,
+                                 int cols, int rows, const uint8_t* cell_on, int* count, double* mean_u, double* mean_v,
+                                 double* speed, int* sel_count, double* t_min, double* t_max, double* device_ms,
+                                 const icelk_grid_stats_t* stats)
+{
+    if (!h) return ICELK_EARG;
+    if (!stats) FAIL(C(h), ICELK_EARG, "the statistics struct is null");
+    return grid_bin_windows(h, x, y, u, v, t, n, file_offset, file_cam, win_f0, win_f1, nfiles, t_lo, t_hi, ncam, nw,
+                            left, top, spacing, cols, rows, cell_on, count, mean_u, mean_v, speed, sel_count, t_min,
+                            t_max, device_ms, stats);
+}
+
+int icelk_grid_cell_stats_host(const double* a, int n, double* out_std, double* out_median, double* out_mad)
+{
+    if (n < 0 || (n > 0 && !a) || !out_std || !out_median || !out_mad) return ICELK_EARG;
+    cell_stats(PlainAt{a}, n, out_std, out_median, out_mad);
     return ICELK_OK;
 }
 

@@ -95,6 +95,9 @@ enum KernelId {
     K_PNG_ADLER,               // ... the pieces joined
     K_RESIZE_ROWS,             // the movie's scaler (k_resize.hip): the horizontal pass
     K_RESIZE_COLS,             // ... the vertical pass
+    K_GRID_SEGMENTS,           // the per-cell statistics (k_grid.hip): begin and count of every segment
+    K_GRID_STD,                // ... np.std(ddof=1), one thread per segment
+    K_GRID_SELECT,             // ... median and MAD, one workgroup per segment and array
     K_COUNT_
 };
 
@@ -536,6 +539,16 @@ void launch_grid_day_assign(hipStream_t s, const double* x, const double* y, con
                             unsigned long long* t_min, unsigned long long* t_max);
 void launch_grid_reduce(hipStream_t s, const unsigned long long* keys, const int* key_count, const double* u,
                         const double* v, int ncells, int* count, double* mean_u, double* mean_v, double* speed);
+// per-segment std, median and MAD (grid_stats.h): the segment table, then one thread / one workgroup per segment.  `out`
+// holds device pointers; scratch: 2 * scratch_stride keys, scratch_stride >= the key count
+void launch_grid_segments(hipStream_t s, const unsigned long long* keys, const int* key_count, int nseg, int* seg_begin,
+                          int* seg_count, const icelk_grid_stats_t& out);
+void launch_grid_std(hipStream_t s, const unsigned long long* keys, const int* seg_begin, const int* seg_count,
+                     const double* u, const double* v, int nseg, const double* mean_u, const double* mean_v,
+                     const icelk_grid_stats_t& out);
+void launch_grid_select(hipStream_t s, const unsigned long long* keys, const int* seg_begin, const int* seg_count,
+                        const double* u, const double* v, int nseg, unsigned long long* scratch, size_t scratch_stride,
+                        const icelk_grid_stats_t& out);
 // averages of the velocity cube (k_cube.hip): the cube [window][cell], the periods' windows as CSR offsets + indices
 void launch_cube_temporal(hipStream_t s, const double* u, const double* v, const double* cnt, int ncells,
                           const int* sel_offset, const int* sel_index, int nperiods, double* mean_u, double* mean_v,

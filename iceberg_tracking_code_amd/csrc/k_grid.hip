@@ -11,8 +11,10 @@
 // radix sort, k_sort.hip), which restores the point order inside every cell, and one thread per cell adds its
 // velocities in numpy's pairwise order (blocks of 128, 8 accumulators, halves aligned to 8; beyond 8192 terms in the
 // chunks of numpy's iterator buffer, np_sums.h) -- float64, bit for bit what np.sum gives -- and takes the hypot (glibc's algorithm, see k_utm.hip).
+// Asked for, the sorted runs also give every cell's np.std(ddof=1), np.median and median absolute deviation
+// (k_grid_segments, k_grid_std, k_grid_select below; the rules are grid_stats.h's).
 #include "icelk_internal.h"
-#include "np_sums.h"
+#include "grid_stats.h"
 
 namespace icelk {
 
@@ -142,13 +144,6 @@ struct DayTables {
     int nfiles, ncam, nw;
 };
 
-// float64 -> uint64 with the same order (negative values flipped, positive ones above them)
-__device__ __forceinline__ unsigned long long order_key(double d)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
 __global__ __launch_bounds__(256) void k_grid_day_assign(const double* __restrict__ x, const double* __restrict__ y,
                                                          const double* __restrict__ t, int n, DayTables D, GridGeom g,
                                                          const uint8_t* __restrict__ cell_on, int ncells,
@@ -261,6 +256,156 @@ __global__ __launch_bounds__(64) void k_grid_reduce(const unsigned long long* __
     speed[c] = sp;
 }
 
+// ---- per-cell spread and robust centre (icelk_grid_bin_stats; the rules are grid_stats.h's) ----------------------------
+// The segment table: where each segment's run of sorted keys begins and how long it is, searched once for the two
+// kernels below.  An empty segment gets its six NaN here and is touched by neither of them.
+__global__ __launch_bounds__(64) void k_grid_segments(const unsigned long long* __restrict__ keys,
+                                                      const int* __restrict__ key_count, int nseg,
+                                                      int* __restrict__ seg_begin, int* __restrict__ seg_count,
+                                                      icelk_grid_stats_t out)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= nseg) return;
+    const int total = *key_count;
+    const int b = lower_bound(keys, total, (unsigned long long)(unsigned)c << 32);
+    const int n = lower_bound(keys, total, (unsigned long long)(unsigned)(c + 1) << 32) - b;
+    seg_begin[c] = b;
+    seg_count[c] = n;
+    if (n > 0) return;
+    const double nan = __builtin_nan("");
+    out.std_u[c] = out.std_v[c] = out.median_u[c] = out.median_v[c] = out.mad_u[c] = out.mad_v[c] = nan;
+}
+
+// np.std(ddof=1) per segment around the mean k_grid_reduce left, one thread per segment as there
+__global__ __launch_bounds__(64) void k_grid_std(const unsigned long long* __restrict__ keys,
+                                                 const int* __restrict__ seg_begin, const int* __restrict__ seg_count,
+                                                 const double* __restrict__ u, const double* __restrict__ v, int nseg,
+                                                 const double* __restrict__ mean_u, const double* __restrict__ mean_v,
+                                                 double* __restrict__ std_u, double* __restrict__ std_v)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= nseg) return;
+    const int n = seg_count[c];
+    if (n <= 0) return;
+    const int b = seg_begin[c];
+    std_u[c] = np_std_ddof1(KeyedAt{keys, u, b}, n, mean_u[c]);
+    std_v[c] = np_std_ddof1(KeyedAt{keys, v, b}, n, mean_v[c]);
+}
+
+static_assert(kSelectBins == 256, "k_grid_select: one thread per histogram bin");
+
+struct SelectLds {
+    int hist[kSelectBins];
+    int wave_tot[4];
+    int bin, before, in_bin;          // the pass's verdict, from the thread that owns the bin
+    unsigned long long above;
+};
+
+// select_bin of grid_stats.h by the workgroup: thread x owns bin x, an exclusive scan of the counts (wave shuffles, then
+// the four wave totals) tells it the ranks its bin holds, and the one thread whose bin holds rank k says so.  k is below
+// the number of counted terms, so there is exactly one.
+__device__ __forceinline__ int wg_select_bin(SelectLds* L, int* k, int* below, int* in_bin)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int mine = L->hist[threadIdx.x];
+    int inc = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o);
+        if (lane >= o) inc += up;
+    }
+    if (lane == 63) L->wave_tot[wave] = inc;
+    __syncthreads();
+    int before = inc - mine;
+    for (int w = 0; w < wave; w++) before += L->wave_tot[w];
+    if (*k >= before && *k < before + mine) {
+        L->bin = threadIdx.x;
+        L->before = before;
+        L->in_bin = mine;
+    }
+    __syncthreads();
+    *k -= L->before;
+    *below += L->before;
+    *in_bin = L->in_bin;
+    return L->bin;
+}
+
+// np.median of the n >= 1 terms whose order keys are sk[0 .. n), none from a NaN, by the whole workgroup: select_rank
+// of grid_stats.h with each pass's histogram counted by 256 threads in LDS.  Every thread walks the same t it staged,
+// reads the same verdict and so carries the same prefix, rank and count; eight passes and at most one more.  A pass's
+// verdict is written two barriers after the last one was read, and a thread zeroes only the bin it alone has read.
+__device__ __forceinline__ double wg_median(const unsigned long long* __restrict__ sk, int n, SelectLds* L)
+{
+    int k = median_rank(n), below = 0, in_bin = 0;
+    unsigned long long prefix = 0;
+    for (int pass = 0; pass < kSelectPasses; pass++) {
+        const int shift = 56 - 8 * pass;
+        L->hist[threadIdx.x] = 0;
+        __syncthreads();
+        for (int t = threadIdx.x; t < n; t += 256) {
+            const unsigned long long key = sk[t];
+            if (select_matches(key, prefix, shift)) atomicAdd(&L->hist[(key >> shift) & 255], 1);
+        }
+        __syncthreads();
+        const int bin = wg_select_bin(L, &k, &below, &in_bin);
+        prefix |= (unsigned long long)bin << shift;
+    }
+    unsigned long long upper = prefix;
+    unsigned long long* s_min = &L->above;
+    if (!(n & 1) && !upper_middle_is_same(below + in_bin, n)) {     // the smallest term above the lower middle
+        if (threadIdx.x == 0) *s_min = ~0ull;
+        __syncthreads();
+        unsigned long long best = ~0ull;
+        for (int t = threadIdx.x; t < n; t += 256) {
+            const unsigned long long q = sk[t];
+            if (q > prefix && q < best) best = q;
+        }
+        if (best != ~0ull) atomicMin(s_min, best);
+        __syncthreads();
+        upper = *s_min;
+    }
+    return median_of_middle(from_order_key(prefix), from_order_key(upper), n);
+}
+
+// Median and MAD of one segment's u (blockIdx.y 0) or v (1): one workgroup of 256.  The values are gathered through
+// the sorted keys once and staged as order keys in the segment's own stretch of `scratch` (scratch_stride per array);
+// thread x stages and later reads terms x, x + 256, ... only, so no thread reads another's store.  The MAD's terms
+// fabs(a - med) overwrite them in place.  NaN is seen while the terms are staged.
+__global__ __launch_bounds__(256) void k_grid_select(const unsigned long long* __restrict__ keys,
+                                                     const int* __restrict__ seg_begin,
+                                                     const int* __restrict__ seg_count, const double* __restrict__ u,
+                                                     const double* __restrict__ v,
+                                                     unsigned long long* __restrict__ scratch, size_t scratch_stride,
+                                                     icelk_grid_stats_t out)
+{
+    __shared__ SelectLds lds;
+    const int c = blockIdx.x;
+    const int n = seg_count[c];
+    if (n <= 0) return;
+    const int b = seg_begin[c];
+    const double* __restrict__ a = blockIdx.y ? v : u;
+    unsigned long long* __restrict__ sk = scratch + blockIdx.y * scratch_stride + b;
+    const double nan = __builtin_nan("");
+    int has_nan = 0;
+    for (int t = threadIdx.x; t < n; t += 256) {
+        const double x = a[(unsigned)keys[b + t]];
+        has_nan |= x != x;
+        sk[t] = order_key(x);
+    }
+    const double med = __syncthreads_or(has_nan) ? nan : wg_median(sk, n, &lds);
+    has_nan = 0;
+    for (int t = threadIdx.x; t < n; t += 256) {
+        const double d = fabs(from_order_key(sk[t]) - med);
+        has_nan |= d != d;
+        sk[t] = order_key(d);
+    }
+    const double mad = __syncthreads_or(has_nan) ? nan : wg_median(sk, n, &lds);
+    if (threadIdx.x == 0) {
+        (blockIdx.y ? out.median_v : out.median_u)[c] = med;
+        (blockIdx.y ? out.mad_v : out.mad_u)[c] = mad;
+    }
+}
+
 }  // namespace
 
 void launch_points_in_polygon(hipStream_t s, const double* poly, int n, const double* pts, int m, uint8_t* out)
@@ -298,6 +443,32 @@ void launch_grid_reduce(hipStream_t s, const unsigned long long* keys, const int
     if (ncells <= 0) return;
     hipLaunchKernelGGL(k_grid_reduce, dim3((ncells + 63) / 64), dim3(64), 0, s, keys, key_count, u, v, ncells, count,
                        mean_u, mean_v, speed);
+}
+
+void launch_grid_segments(hipStream_t s, const unsigned long long* keys, const int* key_count, int nseg, int* seg_begin,
+                          int* seg_count, const icelk_grid_stats_t& out)
+{
+    if (nseg <= 0) return;
+    hipLaunchKernelGGL(k_grid_segments, dim3((nseg + 63) / 64), dim3(64), 0, s, keys, key_count, nseg, seg_begin,
+                       seg_count, out);
+}
+
+void launch_grid_std(hipStream_t s, const unsigned long long* keys, const int* seg_begin, const int* seg_count,
+                     const double* u, const double* v, int nseg, const double* mean_u, const double* mean_v,
+                     const icelk_grid_stats_t& out)
+{
+    if (nseg <= 0) return;
+    hipLaunchKernelGGL(k_grid_std, dim3((nseg + 63) / 64), dim3(64), 0, s, keys, seg_begin, seg_count, u, v, nseg,
+                       mean_u, mean_v, out.std_u, out.std_v);
+}
+
+void launch_grid_select(hipStream_t s, const unsigned long long* keys, const int* seg_begin, const int* seg_count,
+                        const double* u, const double* v, int nseg, unsigned long long* scratch, size_t scratch_stride,
+                        const icelk_grid_stats_t& out)
+{
+    if (nseg <= 0) return;
+    hipLaunchKernelGGL(k_grid_select, dim3(nseg, 2), dim3(256), 0, s, keys, seg_begin, seg_count, u, v, scratch,
+                       scratch_stride, out);
 }
 
 }  // namespace icelk

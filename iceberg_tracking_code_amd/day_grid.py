@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _lib
 from .context import Context
-from .gridding import cell_table, create_grid_across_fjord, pack_cells
+from .gridding import STATS_KEYS, CellStats, cell_table, create_grid_across_fjord, pack_cells
 from .jpeg import UnsupportedJpeg, describe_jpeg
 from .movie import open_movie, velocities_movie_name
 from .velocity_map import MAP_QUALITY, MAP_WIDTH, map_insets, map_layout, map_name, map_picture, map_strings, map_text, map_view
@@ -310,11 +310,12 @@ def window_insets(ctx, photos, names, when, plot_switch, fjord, out_width):
     return out
 
 
-def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, maps=None):
+def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, maps=None, stats=False):
     """Loads the plan's files, runs the device pass, and packs every window that selected a point.  `timing`: a dict
     that receives the seconds of each stage and the kernels' milliseconds (tools/grid_day_bench.py).  `maps`: None, or
     what the windows' pictures need (utm_to_gridded_utm's plot keywords); the written list then carries each picture's
-    name and bytes as a third and fourth entry."""
+    name and bytes as a third and fourth entry.  `stats`: every window's arrays also carry gridding.STATS_KEYS, from
+    `icelk_grid_bin_windows_stats`; without it that entry point is not called."""
     clock = time.perf_counter
     t0 = clock()
     vectors = maps is not None and maps["plot_switch"] == 2
@@ -343,10 +344,14 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
     i32 = lambda a: a.ctypes.data_as(_lib.i32p)               # noqa: E731
     i64 = lambda a: a.ctypes.data_as(_lib.i64p)               # noqa: E731
     device_ms = C.c_double(0.0)
-    ctx._ck(ctx._lib.icelk_grid_bin_windows(
-        ctx._h, f64(x), f64(y), f64(u), f64(v), f64(t), n, i64(off), i32(fcam), i32(wf0), i32(wf1), len(parts),
-        i64(lo), i64(hi), ncam, nw, left, top, float(grid_size), cols, rows, on.ctypes.data_as(_lib.u8p), i32(cnt),
-        f64(mu), f64(mv), f64(sp), i32(sel), f64(tmin), f64(tmax), C.byref(device_ms) if timing is not None else None))
+    args = (ctx._h, f64(x), f64(y), f64(u), f64(v), f64(t), n, i64(off), i32(fcam), i32(wf0), i32(wf1), len(parts),
+            i64(lo), i64(hi), ncam, nw, left, top, float(grid_size), cols, rows, on.ctypes.data_as(_lib.u8p), i32(cnt),
+            f64(mu), f64(mv), f64(sp), i32(sel), f64(tmin), f64(tmax), C.byref(device_ms) if timing is not None else None)
+    cs = CellStats(nw * ncells) if stats else None
+    if stats:
+        ctx._ck(ctx._lib.icelk_grid_bin_windows_stats(*args, C.byref(cs.struct)))
+    else:
+        ctx._ck(ctx._lib.icelk_grid_bin_windows(*args))
     t2 = clock()
     sel, tmin, tmax = sel.reshape(nw, ncam), tmin.reshape(nw, ncam), tmax.reshape(nw, ncam)
     if maps is not None:
@@ -365,9 +370,9 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
         if not sel[w].any():
             continue
         s = slice(w * ncells, (w + 1) * ncells)
-        r = pack_cells(grid, idx, cnt[s], mu[s], mv[s], sp[s], observation_threshold)
+        r = pack_cells(grid, idx, cnt[s], mu[s], mv[s], sp[s], observation_threshold, stats=cs.window(s) if stats else None)
         r.update(grid_size=grid_size, topleft=topleft, rows=rows, cols=cols)
-        arrays = {k: np.asanyarray(r[k]) for k in SAVED_KEYS}        # what np.savez makes of s3's lists
+        arrays = {k: np.asanyarray(r[k]) for k in SAVED_KEYS + (STATS_KEYS if stats else ())}   # what np.savez makes of s3's lists
         name = plan.name(w, [float(a) if k else None for a, k in zip(tmin[w], sel[w])],
                          [float(a) if k else None for a, k in zip(tmax[w], sel[w])])
         if maps is None:
@@ -403,7 +408,7 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
 def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts, fjord, day,
                        time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None, plot_switch=1,
                        speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None, plot_format="jpeg",
-                       movie=None):
+                       movie=None, stats=False):
     """One day of hourly velocity files -> one gridded .npz per time window, as s3_utm_to_gridded_utm.utm_to_gridded_utm
     (s3:222-446) with plot_switch 0.
 
@@ -428,7 +433,12 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
     `movie`: with `plots`, every map drawn also becomes a frame of a Motion-JPEG AVI (8 frames per second, 2000 pixels wide:
     `movie.MovieWriter`), in the order drawn, scaled and coded on the device whatever `plot_format` is.
     True: 'velocities_utm_<minutes>min.avi', the reference's name (s3:211), in `plots`; a path: that file; a `MovieWriter`:
-    frames are added to it and it is left open.  The maps and the .npz files do not change.  movie=None calls nothing of this."""
+    frames are added to it and it is left open.  The maps and the .npz files do not change.  movie=None calls nothing of this.
+
+    `stats`: every window file also carries, over its measured cells, u_std, v_std (np.std(ddof=1) of the cell's velocities),
+    u_median, v_median, speed_median (np.hypot of the two), u_mad, v_mad (the median absolute deviation) -- numpy's bits,
+    selected on the device; every other key is what it is without.  The maps still draw the means.
+    stats=False calls nothing of this."""
     if movie is not None and plots is None:
         raise ValueError("movie needs plots: its frames are the windows' pictures")
     if plots is not None and plot_switch not in (1, 2):
@@ -451,7 +461,7 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
         os.makedirs(maps["dir"], exist_ok=True)
         maps["movie"], film_own = open_movie(movie, maps["dir"], velocities_movie_name(time_window))
     try:
-        written = _grid_day(ctx, plan, fjord, grid_size, observation_threshold, maps=maps)
+        written = _grid_day(ctx, plan, fjord, grid_size, observation_threshold, maps=maps, stats=stats)
     finally:
         if own:
             ctx.close()
@@ -472,9 +482,9 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
 def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts,
                             fjord, time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None,
                             plot_switch=1, speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None,
-                            plot_format="jpeg", movie=None):
+                            plot_format="jpeg", movie=None, stats=False):
     """s3:main's loop over days (without its process pool), on one context: the files of every day, in order.  The plot
-    keywords are utm_to_gridded_utm's; `movie` gives ONE movie over all the days' maps, as s3's main makes one."""
+    keywords and `stats` are utm_to_gridded_utm's; `movie` gives ONE movie over all the days' maps, as s3's main makes one."""
     if movie is not None and plots is None:
         raise ValueError("movie needs plots: its frames are the windows' pictures")
     own = ctx is None
@@ -491,7 +501,8 @@ def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, 
                                       clock_drifts, fjord, day, time_window, grid_size, observation_threshold,
                                       ctx=ctx, save=save, plots=plots, plot_switch=plot_switch,
                                       speedthreshold_cbar=speedthreshold_cbar, cameras=cameras, out_width=out_width,
-                                      quality=quality, photos=photos, plot_format=plot_format, movie=film)
+                                      quality=quality, photos=photos, plot_format=plot_format, movie=film,
+                                      stats=stats)
         return out
     finally:
         if own:

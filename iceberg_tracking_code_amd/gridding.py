@@ -60,10 +60,39 @@ def cell_table(grid, fjord):
     return float(min(fx)), float(max(fy)), on, idx
 
 
-def bin_velocities(ctx, x, y, u, v, fjord, spacing, observation_threshold, grid=None):
+STATS_KEYS = ("u_std", "v_std", "u_median", "v_median", "speed_median", "u_mad", "v_mad")
+_STATS_FIELDS = ("std_u", "std_v", "median_u", "median_v", "mad_u", "mad_v")          # icelk_grid_stats_t's members
+_STATS_OF_KEY = dict(u_std="std_u", v_std="std_v", u_median="median_u", v_median="median_v", u_mad="mad_u", v_mad="mad_v")
+
+
+class CellStats:
+    """The six per-cell arrays of icelk_grid_stats_t for `nseg` cells (or windows x cells), and the struct over them."""
+
+    def __init__(self, nseg):
+        self.arrays = {k: np.zeros(nseg, np.float64) for k in _STATS_FIELDS}
+        self.struct = _lib.GridStats(*[_f64(self.arrays[k]) for k in _STATS_FIELDS])
+
+    def window(self, s):
+        """what `pack_cells` takes as `stats`, for the cells of slice s"""
+        return {k: a[s] for k, a in self.arrays.items()}
+
+
+def grid_cell_stats_host(a):
+    """(std, median, mad) of one cell's values by the library's host statement of the rules (csrc/grid_stats.h,
+    `icelk_grid_cell_stats_host`): np.std(a, ddof=1), np.median(a), np.median(np.abs(a - np.median(a))), bit for bit
+    numpy 2.2's; all NaN for an empty cell.  No GPU."""
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    out = [C.c_double(0.0) for _ in range(3)]
+    _lib.check(_lib.load().icelk_grid_cell_stats_host(_f64(a), len(a), *[C.byref(o) for o in out]))
+    return tuple(np.float64(o.value) for o in out)
+
+
+def bin_velocities(ctx, x, y, u, v, fjord, spacing, observation_threshold, grid=None, stats=False):
     """The loop of s3:391-421 for one time window.  Returns the dict the reference saves (s3:441-445, without
     `grid_size` / `topleft` / `rows` / `cols`, which the caller has): grid_id, i, j, x, y, u, v, speed, count,
-    measured, not_measured."""
+    measured, not_measured.  With `stats` also, as lists over the measured cells, u_std, v_std (np.std(ddof=1) of the
+    cell's velocities), u_median, v_median, speed_median (their np.hypot), u_mad, v_mad (median absolute deviation),
+    from `icelk_grid_bin_stats`."""
     if grid is None:
         grid = create_grid_across_fjord(ctx, fjord, spacing)
     rows, cols = grid[4], grid[5]
@@ -72,16 +101,32 @@ def bin_velocities(ctx, x, y, u, v, fjord, spacing, observation_threshold, grid=
     n = len(a[0])
     cnt = np.zeros(cols * rows, np.int32)
     mu, mv, sp = (np.zeros(cols * rows, np.float64) for _ in range(3))
-    ctx._ck(ctx._lib.icelk_grid_bin(ctx._h, _f64(a[0]), _f64(a[1]), _f64(a[2]), _f64(a[3]), n, left, top,
-                                    float(spacing), cols, rows, on.ctypes.data_as(_lib.u8p),
-                                    cnt.ctypes.data_as(_lib.i32p), _f64(mu), _f64(mv), _f64(sp)))
-    return pack_cells(grid, idx, cnt, mu, mv, sp, observation_threshold)
+    args = (ctx._h, _f64(a[0]), _f64(a[1]), _f64(a[2]), _f64(a[3]), n, left, top, float(spacing), cols, rows,
+            on.ctypes.data_as(_lib.u8p), cnt.ctypes.data_as(_lib.i32p), _f64(mu), _f64(mv), _f64(sp))
+    if not stats:
+        ctx._ck(ctx._lib.icelk_grid_bin(*args))
+        return pack_cells(grid, idx, cnt, mu, mv, sp, observation_threshold)
+    cs = CellStats(cols * rows)
+    ctx._ck(ctx._lib.icelk_grid_bin_stats(*args, C.byref(cs.struct)))
+    return pack_cells(grid, idx, cnt, mu, mv, sp, observation_threshold, stats=cs.arrays)
 
 
-def pack_cells(grid, idx, cnt, mu, mv, sp, observation_threshold):
-    """The lists s3:391-421 fills, from per-cell results indexed i * rows + j (idx: that index of every kept cell)."""
+def hypot_of_medians(median_u, median_v):
+    """speed_median: np.hypot of the two medians, as the reference forms `speed` from the two means (numpy's hypot is the
+    one csrc/np_sums.h's hypot_np restates)"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.hypot(median_u, median_v)
+
+
+def pack_cells(grid, idx, cnt, mu, mv, sp, observation_threshold, stats=None):
+    """The lists s3:391-421 fills, from per-cell results indexed i * rows + j (idx: that index of every kept cell).
+    `stats`: the six per-cell arrays std_u, std_v, median_u, median_v, mad_u, mad_v indexed likewise; the dict then
+    also has the lists of STATS_KEYS over the measured cells."""
     polygons, centers, indices = grid[:3]
     out = {k: [] for k in ("grid_id", "i", "j", "x", "y", "u", "v", "speed", "count", "measured", "not_measured")}
+    if stats is not None:
+        out.update({k: [] for k in STATS_KEYS})
+        speed_median = hypot_of_medians(stats["median_u"], stats["median_v"])
     for counter, (poly, center, index, c) in enumerate(zip(polygons, centers, indices, idx)):
         nobs = int(cnt[c])
         if nobs > observation_threshold:                                   # s3:400
@@ -95,6 +140,10 @@ def pack_cells(grid, idx, cnt, mu, mv, sp, observation_threshold):
             out["speed"].append(sp[c])
             out["count"].append(nobs)
             out["measured"].append(poly)
+            if stats is not None:
+                for key, field in _STATS_OF_KEY.items():
+                    out[key].append(stats[field][c])
+                out["speed_median"].append(speed_median[c])
         else:
             out["not_measured"].append(poly)
     out["counts_all"] = cnt[idx].astype(np.int64)

@@ -51,12 +51,18 @@ def epoch_to_datetime(seconds):
     return dt.timedelta(seconds=seconds) + EPOCH
 
 
-def velocities_to_regular_grid(npz):
+def velocities_to_regular_grid(npz, extra=()):
     """One window file of s3 -> rasters (s4:120-168): [x_ras, y_ras, u_ras, v_ras, speed_ras, count_ras, xx, yy, ii,
-    jj, cols, rows].  Raster index is [j, i]; cells the file does not list are NaN."""
+    jj, cols, rows].  Raster index is [j, i]; cells the file does not list are NaN.  `extra`: names of further per-cell
+    fields of the file (the statistics of day_grid's stats=True, say); their rasters follow as a thirteenth entry, a
+    dict by name.  A file without one of them raises ValueError."""
+    extra = tuple(extra)
     with np.load(npz) as z:
+        missing = [k for k in extra if k not in z.files]
+        if missing:
+            raise ValueError("%s has no %s" % (npz, ", ".join(missing)))
         i, j = z["i"], z["j"]
-        fields = [z[k] for k in ("x", "y", "u", "v", "speed", "count")]
+        fields = [z[k] for k in ("x", "y", "u", "v", "speed", "count") + extra]
         grid_size, topleft, cols, rows = z["grid_size"], z["topleft"], z["cols"], z["rows"]
     rasters = [_nan(rows, cols) for _ in fields]
     if len(i):          # a window with points and no kept cell stores empty float64 i, j: nothing to place
@@ -67,21 +73,30 @@ def velocities_to_regular_grid(npz):
     xx, yy = np.meshgrid(x, y, indexing="xy")
     yy = np.flipud(yy)
     ii, jj = np.meshgrid(range(0, rows), range(0, cols), indexing="ij")
-    return rasters + [xx, yy, ii, jj, cols, rows]
+    out = rasters[:6] + [xx, yy, ii, jj, cols, rows]
+    return out + [dict(zip(extra, rasters[6:]))] if extra else out
 
 
-def combine_npzs(folder, npz_workspace, npz_combined_name, save=True):
+def combine_npzs(folder, npz_workspace, npz_combined_name, save=True, extra=()):
     """The window files of `folder` (sorted) stacked into the run's cube (s4:170-210): a dict with x, y, i, j, u, v,
     speed, count (rows, cols, n_files), time (epoch seconds), time_matlab; written with np.savez when `save`.  Rows
-    and cols are the first file's; a file of another shape raises ValueError."""
+    and cols are the first file's; a file of another shape raises ValueError.  `extra`: names of further per-cell fields
+    of the window files, stacked like u into (rows, cols, n_files) NaN-filled arrays beside the cube's own; a file that
+    lacks one raises ValueError.  They stay on the host: the averages of the device cube do not take them."""
+    extra = tuple(extra)
+    if set(extra) & {"x", "y", "i", "j", "u", "v", "speed", "count", "time", "time_matlab"}:
+        raise ValueError("extra names a field the cube already has")
     npzs = sorted(glob.glob(os.path.join(folder, "*.npz")))
-    first = velocities_to_regular_grid(npzs[0])
+    first = velocities_to_regular_grid(npzs[0], extra)
     cols, rows = first[10], first[11]
     n = len(npzs)
     u, v, speed, count = (_nan(rows, cols, n) for _ in range(4))
     time, time_matlab = _nan(n), _nan(n)
+    more = {name: _nan(rows, cols, n) for name in extra}
     for k, path in enumerate(npzs):
-        _, _, u_ras, v_ras, speed_ras, count_ras, xx, yy, ii, jj, _, _ = velocities_to_regular_grid(path)
+        _, _, u_ras, v_ras, speed_ras, count_ras, xx, yy, ii, jj, _, _, *extra_ras = velocities_to_regular_grid(path, extra)
+        for name in extra:
+            more[name][:, :, k] = extra_ras[0][name]
         u[:, :, k] = u_ras
         v[:, :, k] = v_ras
         speed[:, :, k] = speed_ras
@@ -89,7 +104,7 @@ def combine_npzs(folder, npz_workspace, npz_combined_name, save=True):
         stamp = dt.datetime.strptime(os.path.basename(path).split("-")[0], STAMP)
         time[k] = epoch_seconds(stamp)
         time_matlab[k] = datetime_to_matlab(stamp)
-    cube = dict(x=xx, y=yy, i=ii, j=jj, u=u, v=v, speed=speed, count=count, time=time, time_matlab=time_matlab)
+    cube = dict(x=xx, y=yy, i=ii, j=jj, u=u, v=v, speed=speed, count=count, time=time, time_matlab=time_matlab, **more)
     if save:
         np.savez(os.path.join(npz_workspace, npz_combined_name), **cube)
     return cube

@@ -377,6 +377,36 @@ int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const d
                            double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
                            int* count, double* mean_u, double* mean_v, double* speed, int* sel_count, double* t_min,
                            double* t_max, double* device_ms);
+/* Spread and robust centre per cell, beside the mean: the two calls above with six more outputs (host float64, laid
+ * out as mean_u is: per cell, or per (window w, cell k) at w * cols * rows + k).  With u_sel a cell's velocities in
+ * the order the mean adds them, bit for bit what numpy 2.2 answers:
+ *   std_u    = np.std(u_sel, ddof=1): m = np.sum(u_sel) / n (the mean above), d = (u_sel - m) * (u_sel - m) with every
+ *              operation rounded once, sqrt(np.sum(d) / (n - 1)), both sums in numpy's order; one point gives NaN;
+ *   median_u = np.median(u_sel): NaN if a term is NaN; else with s the sorted terms (0.0 + s[n / 2]) / 1.0 for odd n,
+ *              ((0.0 + s[n / 2 - 1]) + s[n / 2]) / 2.0 for even n -- so the median of [-0.0] is +0.0, of
+ *              [1e308, 1e308] inf, of [-inf, inf] NaN;
+ *   mad_u    = np.median(np.abs(u_sel - median_u)): the same median over fabs(u_sel - median_u), one rounding; a NaN
+ *              or infinite median propagates by IEEE rules;
+ * and std_v, median_v, mad_v likewise.  A cell without points has NaN in all six (the sign of a NaN is not numpy's
+ * everywhere).  count, mean_u, mean_v, speed and the other outputs are those of the call without statistics, and
+ * device_ms covers the kernels of the statistics too.  `stats` and its six members must not be null: ICELK_EARG,
+ * checked with every other argument before anything is allocated or enqueued. */
+typedef struct icelk_grid_stats {
+    double *std_u, *std_v, *median_u, *median_v, *mad_u, *mad_v;
+} icelk_grid_stats_t;
+int icelk_grid_bin_stats(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n,
+                         double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
+                         int* count, double* mean_u, double* mean_v, double* speed, const icelk_grid_stats_t* stats);
+int icelk_grid_bin_windows_stats(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                                 const double* t, int n, const int64_t* file_offset, const int* file_cam,
+                                 const int* win_f0, const int* win_f1, int nfiles, const int64_t* t_lo,
+                                 const int64_t* t_hi, int ncam, int nw, double left, double top, double spacing,
+                                 int cols, int rows, const uint8_t* cell_on, int* count, double* mean_u, double* mean_v,
+                                 double* speed, int* sel_count, double* t_min, double* t_max, double* device_ms,
+                                 const icelk_grid_stats_t* stats);
+/* The three rules on the host, for one cell's n terms (n >= 0; a may be NULL when n == 0): the statement the kernels
+ * are tested against.  No handle and no GPU.  ICELK_EARG for n < 0 or a null pointer. */
+int icelk_grid_cell_stats_host(const double* a, int n, double* out_std, double* out_median, double* out_mad);
 
 /* ---- averages of the run-wide velocity cube (s4_postprocess_gridded_utm.py:264-343) -------------------------
  * The stacked gridded windows of a run: u, v, count (host float64, NaN where a window has no entry for a cell), laid

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate of the s3 day driver (day_grid.utm_to_gridded_utm) on one synthetic day -> profiles/r07_grid_day.txt.
 
-    python tools/grid_day_bench.py [--cams 4] [--hours 12] [--per-hour 250000] [--repeat 3] [--out PATH]
+    python tools/grid_day_bench.py [--cams 4] [--hours 12] [--per-hour 250000] [--repeat 3] [--out PATH] [--stats]
 
 The day: --cams cameras x --hours hourly files of --per-hour velocities (int64 epoch times, 10 % of each file in the
 neighbouring hours, a quarter of the points on cell edges), clock drifts of tens of seconds, 30-minute windows, 200 m
@@ -11,6 +11,10 @@ cells over a ~7 x 5 km fjord.  Reported, each the best of --repeat runs:
                 read-back, packing -- split into its stages;
   per window    bin_velocities once per window on that window's points (selected with numpy beforehand, not timed),
                 the way a loop around the one-window entry point runs.
+With --stats (-> profiles/grid_stats.txt) instead: the device pass without and with the per-cell statistics (std, median,
+MAD: icelk_grid_bin_windows_stats), every run listed; the statistics' kernels one by one (HIP events of the profiling
+table); and the numpy route on the same points -- per (window, cell) np.std(ddof=1), np.median and the MAD expression for
+u and v on one core, the points of every cell selected beforehand and not timed.
 """
 import argparse
 import datetime as dt
@@ -29,6 +33,7 @@ from iceberg_tracking_code_amd.gridding import create_grid_across_fjord  # noqa:
 
 DAY = dt.datetime(2022, 7, 12)
 SPACING = 200
+STATS_KERNELS = ("grid_segments", "grid_std", "grid_select")
 
 
 def make_day(root, cams, hours, per_hour):
@@ -60,19 +65,98 @@ def make_day(root, cams, hours, per_hour):
     return names, schedule, drifts, fjord
 
 
+def cells_of_the_day(plan, fjord):
+    """The day's points as _grid_day loads them, split by (window, cell): [(u, v)] in concatenation order.  The cell is
+    the floor index, so a point on an edge lies in one cell here where the gridder may put it in two or none: good for a
+    timing, not for a comparison."""
+    parts = [day_grid._load_hour_file(f["path"]) for f in plan.files]
+    x, y, u, v, t = (np.concatenate([p[k] for p in parts]) for k in range(5))
+    off = np.zeros(len(parts) + 1, np.int64)
+    off[1:] = np.cumsum([len(p[0]) for p in parts])
+    fcam = np.array([f["cam"] for f in plan.files], np.int32)
+    lo, hi = (np.array([c[k] for c in plan.cameras], np.int64) for k in ("lo", "hi"))
+    wf0, wf1 = (np.array([c[k] for c in plan.cameras], np.int32) for k in ("f0", "f1"))
+    w = day_grid.window_of_points(t, off, fcam, lo, hi, wf0, wf1).astype(np.int64)
+    left, top = min(fjord["x"]), max(fjord["y"])
+    i, j = np.floor((x - left) / SPACING).astype(np.int64), np.floor((top - y) / SPACING).astype(np.int64)
+    rows = int(j.max()) + 1
+    seg = (w * (int(i.max()) + 1) + i) * rows + j
+    keep = np.flatnonzero(w >= 0)
+    order = keep[np.argsort(seg[keep], kind="stable")]
+    cuts = np.flatnonzero(np.diff(seg[order])) + 1
+    return list(zip(np.split(u[order], cuts), np.split(v[order], cuts)))
+
+
+def numpy_route(cells):
+    t = time.perf_counter()
+    for pair in cells:
+        for a in pair:
+            if len(a) > 1:
+                np.std(a, ddof=1)
+            m = np.median(a)
+            np.median(np.abs(a - m))
+    return time.perf_counter() - t
+
+
+def stats_report(ctx, a, say, names, tmp, schedule, drifts, fjord):
+    def one_pass(stats):
+        timing = {}
+        p = day_grid.plan_day(names, tmp, "utm", schedule, drifts, DAY, 0.5, SPACING)
+        day_grid._grid_day(ctx, p, fjord, SPACING, 5, timing, stats=stats)
+        return timing
+
+    one_pass(False)                                          # warm-up: allocations, code objects
+    one_pass(True)
+    off = [one_pass(False)["kernels_ms"] for _ in range(a.repeat)]
+    say("device pass without statistics (assign, sort, reduce; HIP events), %d runs: %s ms"
+        % (a.repeat, ", ".join("%.2f" % x for x in off)))
+    on = []
+    ctx.prof_enable(True)
+    try:
+        for _ in range(a.repeat):
+            ctx.prof_reset()
+            timing = one_pass(True)
+            ctx.sync()
+            table = ctx.prof_table()
+            on.append((timing["kernels_ms"], [table[k]["total_ms"] for k in STATS_KERNELS]))
+    finally:
+        ctx.prof_enable(False)
+    npts = timing["points"]
+    say("device pass with statistics (+ segments, std, select), %d runs: %s ms" % (a.repeat, ", ".join("%.2f" % x for x, _ in on)))
+    for k, name in enumerate(STATS_KERNELS):
+        say("  %-14s %s ms" % (name, ", ".join("%.3f" % per[k] for _, per in on)))
+    best_on, best_off = min(x for x, _ in on), min(off)
+    say("statistics add %.2f ms to %.2f ms (best of each): %.3g points/s with them" % (best_on - best_off, best_off, npts / (best_on * 1e-3)))
+    plan = day_grid.plan_day(names, tmp, "utm", schedule, drifts, DAY, 0.5, SPACING)
+    cells = cells_of_the_day(plan, fjord)
+    sizes = np.array([len(u) for u, _ in cells])
+    say("segments with points: %d; points per segment: median %d, 99th percentile %d, largest %d"
+        % (len(cells), np.median(sizes), np.percentile(sizes, 99), sizes.max()))
+    host = min(numpy_route(cells) for _ in range(a.repeat))
+    say("numpy route on one core (np.std, np.median, MAD per segment for u and v; selection not timed): %.3f s" % host)
+    say("numpy route vs the statistics' kernels: %.1fx" % (host / ((best_on - best_off) * 1e-3)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cams", type=int, default=4)
     ap.add_argument("--hours", type=int, default=12)
     ap.add_argument("--per-hour", type=int, default=250000)
     ap.add_argument("--repeat", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_grid_day.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--stats", action="store_true")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "grid_stats.txt" if a.stats else "r07_grid_day.txt")
     lines = []
 
     def say(s):
         print(s, flush=True)
         lines.append(s)
+
+    def write_out():
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
     ctx = Context(64, 64, n_slots=1, max_pts=1 << 18)
     try:
@@ -85,6 +169,9 @@ def main():
             grid = create_grid_across_fjord(ctx, fjord, SPACING)
             say("windows %d, hour files loaded %d, kept cells %d of %d" % (len(plan.windows), len(plan.files),
                                                                           len(grid[0]), grid[4] * grid[5]))
+            if a.stats:
+                stats_report(ctx, a, say, names, tmp, schedule, drifts, fjord)
+                return write_out()
             # the driver, stage by stage, and the device pass alone
             stages, walls, first = [], [], None
             for _ in range(a.repeat):
@@ -134,9 +221,7 @@ def main():
             say("device pass vs per-window loop: %.1fx" % (min(loop) / (kern * 1e-3)))
     finally:
         ctx.close()
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    write_out()
 
 
 if __name__ == "__main__":
