@@ -18,6 +18,8 @@ from .sequence import track_image_sequence  # noqa: F401
 from .crop import crop_image_sequence  # noqa: F401
 from .gridding import bin_velocities, create_grid_across_fjord, grid_cell_stats_host, points_in_polygon  # noqa: F401
 from .day_grid import closest_image, utm_to_gridded_utm, utm_to_gridded_utm_days  # noqa: F401
+from .transect import (BoxSet, azimuth_transect, bin_boxes, create_squares_along_transect, create_squares_around_mooring,  # noqa: F401
+                       create_squares_rot, locate_points_along_transect, utm_to_transect, utm_to_transect_days)
 from .postprocess import (VelocityCube, average_periods, average_spatially_temporally, combine_npzs,  # noqa: F401
                           daily_averages, npz_to_csv, npz_to_mat, save_csv, velocities_to_regular_grid)
 from .calibration import CalibrationResult, ShorelineScene, calibrate, run_calibration  # noqa: F401

@@ -59,6 +59,23 @@ class GridStats(C.Structure):
 grid_stats_p = C.POINTER(GridStats)
 
 
+class Boxes(C.Structure):
+    """icelk_boxes_t: nboxes polygons, box b's vertices at xy[2 * offset[b]] .. xy[2 * offset[b + 1])"""
+    _fields_ = [("xy", f64p), ("offset", i32p), ("nboxes", C.c_int)]
+
+
+boxes_p = C.POINTER(Boxes)
+
+
+class DayTables(C.Structure):
+    """icelk_day_tables_t: the file and window tables of icelk_grid_bin_windows"""
+    _fields_ = [("file_offset", i64p), ("file_cam", i32p), ("win_f0", i32p), ("win_f1", i32p), ("nfiles", C.c_int),
+                ("t_lo", i64p), ("t_hi", i64p), ("ncam", C.c_int), ("nw", C.c_int)]
+
+
+day_tables_p = C.POINTER(DayTables)
+
+
 class MapPanel(C.Structure):
     """icelk_map_panel_t"""
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("bar_x0", C.c_int32), ("bar_w", C.c_int32),
@@ -251,6 +268,11 @@ SIGNATURES = {
                                                C.c_double, C.c_int, C.c_int, u8p, i32p, f64p, f64p, f64p, i32p, f64p,
                                                f64p, f64p, grid_stats_p]),
     "icelk_grid_cell_stats_host": (C.c_int, [f64p, C.c_int, f64p, f64p, f64p]),
+    "icelk_boxes_check": (C.c_int, [boxes_p]),
+    "icelk_boxes_bin": (C.c_int, [handle_p, f64p, f64p, f64p, f64p, C.c_int, boxes_p, f64p, i32p, f64p, f64p, f64p,
+                                  grid_stats_p]),
+    "icelk_boxes_bin_windows": (C.c_int, [handle_p, f64p, f64p, f64p, f64p, f64p, C.c_int, day_tables_p, boxes_p, f64p,
+                                          i32p, f64p, f64p, f64p, grid_stats_p, i32p, f64p, f64p, f64p]),
     "icelk_cube_set": (C.c_int, [handle_p, f64p, f64p, f64p, C.c_int, C.c_int]),
     "icelk_cube_release": (C.c_int, [handle_p]),
     "icelk_cube_average": (C.c_int, [handle_p, i32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, f64p, f64p, f64p, f64p,

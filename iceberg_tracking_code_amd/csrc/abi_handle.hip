@@ -18,6 +18,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "png_filter", "png_parse", "png_scan", "png_pack", "png_adler",
     "resize_rows", "resize_cols",
     "grid_segments", "grid_std", "grid_select",
+    "boxes_assign", "boxes_day_assign", "grid_day_assign",
 };
 
 std::string g_create_err;

@@ -1,5 +1,5 @@
-// abi_post.hip -- after the frame loop: projection, point-in-polygon, gridding (one set / a day of windows),
-// the velocity cube and its averages.
+// abi_post.hip -- after the frame loop: projection, point-in-polygon, gridding (one set / a day of windows), binning
+// into transect and mooring boxes (likewise), the velocity cube and its averages.
 #include "icelk_ctx.h"
 #include "cube_means.h"
 #include "grid_stats.h"
@@ -70,7 +70,7 @@ static int grid_core(Ctx* c, const GridDev& G, Assign assign, const char* assign
     int total = 0;
     HIPCHK(c, hipMemcpyAsync(&total, G.d_key_count, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    if (total > G.key_cap) FAIL(c, ICELK_ECAP, "more than two cells per point on average (all points on cell edges?)");
+    if (total > G.key_cap) FAIL(c, ICELK_ECAP, "more than two cells or boxes per point on average (all points on cell edges, or boxes that overlap?)");
     if (t) HIPCHK(c, hipEventRecord(t[1].a, s));
     const unsigned long long* sorted = G.keys;
     if (total > 1) {
@@ -122,6 +122,137 @@ struct PlainAt {
 static bool stats_complete(const icelk_grid_stats_t* st)
 {
     return st && st->std_u && st->std_v && st->median_u && st->median_v && st->mad_u && st->mad_v;
+}
+
+// ---- the day's file and window tables (icelk_grid_bin_windows, icelk_boxes_bin_windows) ------------------------------
+static bool day_tables_complete(const icelk_day_tables_t& T)
+{
+    return T.nfiles >= 1 && T.ncam >= 1 && T.nw >= 1 && T.file_offset && T.file_cam && T.win_f0 && T.win_f1 && T.t_lo && T.t_hi;
+}
+
+// the rules of include/icelk.h for complete tables over n points
+static int check_day_tables(Ctx* c, const icelk_day_tables_t& T, int n)
+{
+    const int nfiles = T.nfiles, ncam = T.ncam, nw = T.nw;
+    if (T.file_offset[0] != 0 || T.file_offset[nfiles] != n) FAIL(c, ICELK_EARG, "file offsets must span 0 .. n");
+    for (int f = 0; f < nfiles; f++)
+        if (T.file_offset[f + 1] < T.file_offset[f] || T.file_cam[f] < 0 || T.file_cam[f] >= ncam ||
+            (f > 0 && T.file_cam[f] < T.file_cam[f - 1]))
+            FAIL(c, ICELK_EARG, "bad file table");
+    for (int k = 0; k < ncam; k++)
+        for (int w = 0; w < nw; w++) {
+            const size_t sl = (size_t)k * nw + w;
+            if (T.t_lo[sl] > T.t_hi[sl] || (w + 1 < nw && T.t_hi[sl] > T.t_lo[sl + 1]))
+                FAIL(c, ICELK_EARG, "window bounds must be ascending and disjoint per camera");
+            if (T.win_f0[sl] <= T.win_f1[sl] && (T.win_f0[sl] < 0 || T.win_f1[sl] >= nfiles || T.file_cam[T.win_f0[sl]] != k ||
+                                                 T.file_cam[T.win_f1[sl]] != k))
+                FAIL(c, ICELK_EARG, "a window loads files of another camera");
+        }
+    return ICELK_OK;
+}
+
+// the tables on the device, with the per-(window, camera) selection count and time range the assign kernel fills
+struct DayDev {
+    long long *off = nullptr, *lo = nullptr, *hi = nullptr;
+    int *fcam = nullptr, *wf0 = nullptr, *wf1 = nullptr, *sel = nullptr;
+    unsigned long long *tmin = nullptr, *tmax = nullptr;
+    int nfiles = 0, nslot = 0;
+
+    void alloc(DevBufs& B, const icelk_day_tables_t& T)
+    {
+        nfiles = T.nfiles;
+        nslot = T.nw * T.ncam;
+        off = B.get<long long>((size_t)nfiles + 1);
+        fcam = B.get<int>((size_t)nfiles);
+        wf0 = B.get<int>((size_t)nslot);
+        wf1 = B.get<int>((size_t)nslot);
+        lo = B.get<long long>((size_t)nslot);
+        hi = B.get<long long>((size_t)nslot);
+        sel = B.get<int>((size_t)nslot);
+        tmin = B.get<unsigned long long>((size_t)nslot);
+        tmax = B.get<unsigned long long>((size_t)nslot);
+    }
+    int upload(Ctx* c, const icelk_day_tables_t& T, hipStream_t s) const
+    {
+        HIPCHK(c, copy_n(off, T.file_offset, (size_t)nfiles + 1, kH2D, s));
+        HIPCHK(c, copy_n(fcam, T.file_cam, (size_t)nfiles, kH2D, s));
+        HIPCHK(c, copy_n(wf0, T.win_f0, (size_t)nslot, kH2D, s));
+        HIPCHK(c, copy_n(wf1, T.win_f1, (size_t)nslot, kH2D, s));
+        HIPCHK(c, copy_n(lo, T.t_lo, (size_t)nslot, kH2D, s));
+        HIPCHK(c, copy_n(hi, T.t_hi, (size_t)nslot, kH2D, s));
+        return ICELK_OK;
+    }
+    // in front of the assign kernel: nothing selected, the range empty
+    int reset(Ctx* c, hipStream_t s) const
+    {
+        HIPCHK(c, hipMemsetAsync(sel, 0, sizeof(int) * nslot, s));
+        HIPCHK(c, hipMemsetAsync(tmin, 0xff, sizeof(unsigned long long) * nslot, s));
+        HIPCHK(c, hipMemsetAsync(tmax, 0, sizeof(unsigned long long) * nslot, s));
+        return ICELK_OK;
+    }
+    // waits for the stream; t_min / t_max keep their 0 where nothing was selected
+    int read_back(Ctx* c, hipStream_t s, int* sel_count, double* t_min, double* t_max) const
+    {
+        HIPCHK(c, copy_n(sel_count, sel, (size_t)nslot, kD2H, s));
+        std::vector<unsigned long long> kmin(nslot), kmax(nslot);
+        HIPCHK(c, copy_n(kmin.data(), tmin, (size_t)nslot, kD2H, s));
+        HIPCHK(c, copy_n(kmax.data(), tmax, (size_t)nslot, kD2H, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        for (int k = 0; k < nslot; k++)
+            if (sel_count[k] > 0) {
+                t_min[k] = from_order_key(kmin[k]);
+                t_max[k] = from_order_key(kmax[k]);
+            }
+        return ICELK_OK;
+    }
+};
+
+// the sum of the two timed stretches of grid_core
+static int elapsed_ms(Ctx* c, const EvPair* timer, double* device_ms)
+{
+    float a = 0.0f, b = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&a, timer[0].a, timer[0].b));
+    HIPCHK(c, hipEventElapsedTime(&b, timer[1].a, timer[1].b));
+    *device_ms = (double)a + (double)b;
+    return ICELK_OK;
+}
+
+// what a day call answers when no point reaches a segment or a slot: zeros, NaN statistics
+static void clear_day_outputs(int nseg, int nslot, int* count, double* mean_u, double* mean_v, double* speed,
+                              const icelk_grid_stats_t* stats, int* sel_count, double* t_min, double* t_max, double* device_ms)
+{
+    memset(count, 0, sizeof(int) * nseg);
+    memset(mean_u, 0, sizeof(double) * nseg);
+    memset(mean_v, 0, sizeof(double) * nseg);
+    memset(speed, 0, sizeof(double) * nseg);
+    memset(sel_count, 0, sizeof(int) * nslot);
+    memset(t_min, 0, sizeof(double) * nslot);
+    memset(t_max, 0, sizeof(double) * nslot);
+    if (stats)
+        for (double* q : {stats->std_u, stats->std_v, stats->median_u, stats->median_v, stats->mad_u, stats->mad_v})
+            std::fill(q, q + nseg, __builtin_nan(""));
+    if (device_ms) *device_ms = 0.0;
+}
+
+// ---- the box list of icelk_boxes_bin / icelk_boxes_bin_windows ------------------------------------------------------
+constexpr int kMaxBoxes = 1024, kMaxBoxVertices = 2048;   // 32 KB of vertices in LDS (k_grid.hip)
+
+// ICELK_OK, or the refusal and its text
+static int check_boxes(const icelk_boxes_t* b, const char** why)
+{
+    *why = "";
+    if (!b || !b->xy || !b->offset || b->nboxes < 1) return *why = "box list missing or empty", ICELK_EARG;
+    if (b->nboxes > kMaxBoxes) return *why = "more than 1024 boxes", ICELK_ECAP;
+    if (b->offset[0] != 0) return *why = "box offsets must start at 0", ICELK_EARG;
+    for (int k = 0; k < b->nboxes; k++) {
+        if (b->offset[k + 1] < b->offset[k]) return *why = "box offsets must ascend", ICELK_EARG;
+        if (b->offset[k + 1] - b->offset[k] < 3) return *why = "a polygon of fewer than three vertices", ICELK_EARG;
+        if (b->offset[k + 1] > kMaxBoxVertices) return *why = "more than 2048 box vertices", ICELK_ECAP;
+    }
+    const int nvert = b->offset[b->nboxes];
+    for (int k = 0; k < 2 * nvert; k++)
+        if (!std::isfinite(b->xy[k])) return *why = "a box vertex is not finite", ICELK_EARG;
+    return ICELK_OK;
 }
 
 // run the projection kernel over `n` gathered tracks sitting in d_tracks_in and bring the results to the host
@@ -308,54 +439,25 @@ static int grid_bin_windows(icelk_t* h, const double* x, const double* y, const 
     // the 2 n + 1024 key slots are int
     if (ncells_ll > (1 << 24) || ncells_ll * nw > 0x7fffffffLL || n > (1 << 30))
         FAIL(c, ICELK_ECAP, "grid x windows or point set too large");
-    if (file_offset[0] != 0 || file_offset[nfiles] != n) FAIL(c, ICELK_EARG, "file offsets must span 0 .. n");
-    for (int f = 0; f < nfiles; f++)
-        if (file_offset[f + 1] < file_offset[f] || file_cam[f] < 0 || file_cam[f] >= ncam ||
-            (f > 0 && file_cam[f] < file_cam[f - 1]))
-            FAIL(c, ICELK_EARG, "bad file table");
-    for (int k = 0; k < ncam; k++)
-        for (int w = 0; w < nw; w++) {
-            const size_t sl = (size_t)k * nw + w;
-            if (t_lo[sl] > t_hi[sl] || (w + 1 < nw && t_hi[sl] > t_lo[sl + 1]))
-                FAIL(c, ICELK_EARG, "window bounds must be ascending and disjoint per camera");
-            if (win_f0[sl] <= win_f1[sl] && (win_f0[sl] < 0 || win_f1[sl] >= nfiles || file_cam[win_f0[sl]] != k ||
-                                             file_cam[win_f1[sl]] != k))
-                FAIL(c, ICELK_EARG, "a window loads files of another camera");
-        }
-    const int ncells = (int)ncells_ll, nseg = ncells * nw, nslot = nw * ncam;
+    const icelk_day_tables_t T{file_offset, file_cam, win_f0, win_f1, nfiles, t_lo, t_hi, ncam, nw};
+    if (int rct = check_day_tables(c, T, n)) return rct;
+    const int ncells = (int)ncells_ll, nseg = ncells * nw;
     const int key_cap = (int)std::min<long long>(2LL * n + 1024, 0x7fffffffLL);
-    memset(count, 0, sizeof(int) * nseg);
-    memset(mean_u, 0, sizeof(double) * nseg);
-    memset(mean_v, 0, sizeof(double) * nseg);
-    memset(speed, 0, sizeof(double) * nseg);
-    memset(sel_count, 0, sizeof(int) * nslot);
-    memset(t_min, 0, sizeof(double) * nslot);
-    memset(t_max, 0, sizeof(double) * nslot);
-    if (stats)
-        for (double* q : {stats->std_u, stats->std_v, stats->median_u, stats->median_v, stats->mad_u, stats->mad_v})
-            std::fill(q, q + nseg, __builtin_nan(""));
-    if (device_ms) *device_ms = 0.0;
+    clear_day_outputs(nseg, nw * ncam, count, mean_u, mean_v, speed, stats, sel_count, t_min, t_max, device_ms);
     if (n == 0) return ICELK_OK;
     DevBufs B;
     GridDev G;
+    DayDev D;
     const size_t nn = (size_t)n;
     double* dx = B.get<double>(nn);
     double* dy = B.get<double>(nn);
     double* du = B.get<double>(nn);
     double* dv = B.get<double>(nn);
     double* dt = B.get<double>(nn);
-    long long* d_off = B.get<long long>((size_t)nfiles + 1);
-    int* d_fcam = B.get<int>((size_t)nfiles);
-    int* d_wf0 = B.get<int>((size_t)nslot);
-    int* d_wf1 = B.get<int>((size_t)nslot);
-    long long* d_lo = B.get<long long>((size_t)nslot);
-    long long* d_hi = B.get<long long>((size_t)nslot);
+    D.alloc(B, T);
     uint8_t* d_on = B.get<uint8_t>((size_t)ncells);
     G.alloc(B, key_cap, nseg);
     if (stats) G.alloc_stats(B);
-    int* d_sel = B.get<int>((size_t)nslot);
-    unsigned long long* d_tmin = B.get<unsigned long long>((size_t)nslot);
-    unsigned long long* d_tmax = B.get<unsigned long long>((size_t)nslot);
     const hipStream_t s = c->stream;
     G.alloc_sort(B, s);
     if (!B.ok()) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
@@ -366,48 +468,122 @@ static int grid_bin_windows(icelk_t* h, const double* x, const double* y, const 
     HIPCHK(c, copy_n(du, u, nn, kH2D, s));
     HIPCHK(c, copy_n(dv, v, nn, kH2D, s));
     HIPCHK(c, copy_n(dt, t, nn, kH2D, s));
-    HIPCHK(c, copy_n(d_off, file_offset, (size_t)nfiles + 1, kH2D, s));
-    HIPCHK(c, copy_n(d_fcam, file_cam, (size_t)nfiles, kH2D, s));
-    HIPCHK(c, copy_n(d_wf0, win_f0, (size_t)nslot, kH2D, s));
-    HIPCHK(c, copy_n(d_wf1, win_f1, (size_t)nslot, kH2D, s));
-    HIPCHK(c, copy_n(d_lo, t_lo, (size_t)nslot, kH2D, s));
-    HIPCHK(c, copy_n(d_hi, t_hi, (size_t)nslot, kH2D, s));
+    if (int rct = D.upload(c, T, s)) return rct;
     HIPCHK(c, copy_n(d_on, cell_on, (size_t)ncells, kH2D, s));
     // device_ms: assign, then sort + reduce; the key-count read-back between them is not counted
     EvPair timer[2];
     auto assign = [&]() -> int {
-        HIPCHK(c, hipMemsetAsync(d_sel, 0, sizeof(int) * nslot, s));
-        HIPCHK(c, hipMemsetAsync(d_tmin, 0xff, sizeof(unsigned long long) * nslot, s));
-        HIPCHK(c, hipMemsetAsync(d_tmax, 0, sizeof(unsigned long long) * nslot, s));
+        if (int rct = D.reset(c, s)) return rct;
         if (device_ms) {
             int rct = timer[0].create(c);
             if (!rct) rct = timer[1].create(c);
             if (rct) return rct;
             HIPCHK(c, hipEventRecord(timer[0].a, s));
         }
-        launch_grid_day_assign(s, dx, dy, dt, n, d_off, d_fcam, d_wf0, d_wf1, nfiles, d_lo, d_hi, ncam, nw, left, top,
-                               spacing, cols, rows, d_on, G.keys, G.d_key_count, key_cap, d_sel, d_tmin, d_tmax);
+        ProfScope p(c, K_GRID_DAY_ASSIGN);
+        launch_grid_day_assign(s, dx, dy, dt, n, D.off, D.fcam, D.wf0, D.wf1, nfiles, D.lo, D.hi, ncam, nw, left, top,
+                               spacing, cols, rows, d_on, G.keys, G.d_key_count, key_cap, D.sel, D.tmin, D.tmax);
         return ICELK_OK;
     };
     int rc = grid_core(c, G, assign, "grid_day_assign", device_ms ? timer : nullptr, count, mean_u, mean_v, speed, stats);
     if (rc) return rc;
-    HIPCHK(c, copy_n(sel_count, d_sel, (size_t)nslot, kD2H, s));
-    std::vector<unsigned long long> kmin(nslot), kmax(nslot);
-    HIPCHK(c, copy_n(kmin.data(), d_tmin, (size_t)nslot, kD2H, s));
-    HIPCHK(c, copy_n(kmax.data(), d_tmax, (size_t)nslot, kD2H, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    for (int k = 0; k < nslot; k++)
-        if (sel_count[k] > 0) {
-            t_min[k] = from_order_key(kmin[k]);
-            t_max[k] = from_order_key(kmax[k]);
-        }
-    if (device_ms) {
-        float a = 0.0f, b = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&a, timer[0].a, timer[0].b));
-        HIPCHK(c, hipEventElapsedTime(&b, timer[1].a, timer[1].b));
-        *device_ms = (double)a + (double)b;
+    rc = D.read_back(c, s, sel_count, t_min, t_max);
+    if (rc) return rc;
+    return device_ms ? elapsed_ms(c, timer, device_ms) : ICELK_OK;
+}
+
+// icelk_boxes_bin (T null) and icelk_boxes_bin_windows: the points against the box list, then grid_core with
+// nseg = boxes, or windows * boxes
+static int boxes_bin(icelk_t* h, const double* x, const double* y, const double* u, const double* v, const double* t,
+                     int n, const icelk_day_tables_t* T, const icelk_boxes_t* boxes, const double* rot, int* count,
+                     double* mean_u, double* mean_v, double* speed, const icelk_grid_stats_t* stats, int* sel_count,
+                     double* t_min, double* t_max, double* device_ms)
+{
+    if (!h) return ICELK_EARG;
+    Ctx* c = C(h);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (stats && !stats_complete(stats)) FAIL(c, ICELK_EARG, "a member of the statistics struct is null");
+    if (n < 0 || !count || !mean_u || !mean_v || !speed || (n > 0 && (!x || !y || !u || !v)))
+        FAIL(c, ICELK_EARG, "bad binning arguments");
+    if (T && (!day_tables_complete(*T) || !sel_count || !t_min || !t_max || (n > 0 && !t)))
+        FAIL(c, ICELK_EARG, "bad binning arguments");
+    if (rot && !(std::isfinite(rot[0]) && std::isfinite(rot[1]))) FAIL(c, ICELK_EARG, "the rotation is not finite");
+    const char* why = "";
+    if (int rcb = check_boxes(boxes, &why)) FAIL(c, rcb, why);
+    const int nb = boxes->nboxes, nvert = boxes->offset[nb], nw = T ? T->nw : 1;
+    // keys hold (window * nboxes + box) in their high 32 bits; a point may lie in every box, and the key counter is an int
+    if ((long long)nb * nw > 0x7fffffffLL || (long long)nb * n > 0x7fffffffLL || n > (T ? 1 << 30 : 1 << 27))
+        FAIL(c, ICELK_ECAP, "boxes x windows, boxes x points or point set too large");
+    if (T)
+        if (int rct = check_day_tables(c, *T, n)) return rct;
+    const int nseg = nb * nw;
+    const int key_cap = (int)std::min<long long>(2LL * n + 1024, 0x7fffffffLL);
+    if (T) {
+        clear_day_outputs(nseg, nw * T->ncam, count, mean_u, mean_v, speed, stats, sel_count, t_min, t_max, device_ms);
+        if (n == 0) return ICELK_OK;
     }
-    return ICELK_OK;
+    DevBufs B;
+    GridDev G;
+    DayDev D;
+    const size_t nn = (size_t)n;
+    double* dx = B.get<double>(nn);
+    double* dy = B.get<double>(nn);
+    double* du = B.get<double>(nn);
+    double* dv = B.get<double>(nn);
+    double* dur = rot ? B.get<double>(nn) : nullptr;             // the velocities in the boxes' frame (the assign kernel's)
+    double* dvr = rot ? B.get<double>(nn) : nullptr;
+    double* dt = T ? B.get<double>(nn) : nullptr;
+    double* d_bxy = B.get<double>(2 * (size_t)nvert);
+    int* d_boff = B.get<int>((size_t)nb + 1);
+    if (T) D.alloc(B, *T);
+    G.alloc(B, key_cap, nseg);
+    if (stats) G.alloc_stats(B);
+    const hipStream_t s = c->stream;
+    G.alloc_sort(B, s);
+    if (!B.ok()) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
+    G.du = rot ? dur : du;
+    G.dv = rot ? dvr : dv;
+    if (n > 0) {
+        HIPCHK(c, copy_n(dx, x, nn, kH2D, s));
+        HIPCHK(c, copy_n(dy, y, nn, kH2D, s));
+        HIPCHK(c, copy_n(du, u, nn, kH2D, s));
+        HIPCHK(c, copy_n(dv, v, nn, kH2D, s));
+        if (T) HIPCHK(c, copy_n(dt, t, nn, kH2D, s));
+    }
+    HIPCHK(c, copy_n(d_bxy, boxes->xy, 2 * (size_t)nvert, kH2D, s));
+    HIPCHK(c, copy_n(d_boff, boxes->offset, (size_t)nb + 1, kH2D, s));
+    if (T)
+        if (int rct = D.upload(c, *T, s)) return rct;
+    EvPair timer[2];
+    auto assign = [&]() -> int {
+        if (!T) {
+            ProfScope p(c, K_BOXES_ASSIGN);
+            launch_boxes_assign(s, dx, dy, n, d_bxy, d_boff, nb, nvert, du, dv, dur, dvr, rot, G.keys, G.d_key_count, key_cap);
+            return ICELK_OK;
+        }
+        if (int rct = D.reset(c, s)) return rct;
+        if (device_ms) {
+            int rct = timer[0].create(c);
+            if (!rct) rct = timer[1].create(c);
+            if (rct) return rct;
+            HIPCHK(c, hipEventRecord(timer[0].a, s));
+        }
+        ProfScope p(c, K_BOXES_DAY_ASSIGN);
+        launch_boxes_day_assign(s, dx, dy, dt, n, D.off, D.fcam, D.wf0, D.wf1, T->nfiles, D.lo, D.hi, T->ncam, nw, d_bxy,
+                                d_boff, nb, nvert, du, dv, dur, dvr, rot, G.keys, G.d_key_count, key_cap, D.sel, D.tmin,
+                                D.tmax);
+        return ICELK_OK;
+    };
+    int rc = grid_core(c, G, assign, T ? "boxes_day_assign" : "boxes_assign", T && device_ms ? timer : nullptr, count, mean_u,
+                       mean_v, speed, stats);
+    if (rc) return rc;
+    if (!T) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        return ICELK_OK;
+    }
+    rc = D.read_back(c, s, sel_count, t_min, t_max);
+    if (rc) return rc;
+    return device_ms ? elapsed_ms(c, timer, device_ms) : ICELK_OK;
 }
 
 int icelk_grid_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
@@ -435,6 +611,32 @@ int icelk_grid_bin_windows_stats(icelk_t* h, const double* x, const double* y, c
     return grid_bin_windows(h, x, y, u, v, t, n, file_offset, file_cam, win_f0, win_f1, nfiles, t_lo, t_hi, ncam, nw,
                             left, top, spacing, cols, rows, cell_on, count, mean_u, mean_v, speed, sel_count, t_min,
                             t_max, device_ms, stats);
+}
+
+int icelk_boxes_check(const icelk_boxes_t* boxes)
+{
+    const char* why = "";
+    return check_boxes(boxes, &why);
+}
+
+int icelk_boxes_bin(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n,
+                    const icelk_boxes_t* boxes, const double* rot, int* count, double* mean_u, double* mean_v,
+                    double* speed, const icelk_grid_stats_t* stats)
+{
+    return boxes_bin(h, x, y, u, v, nullptr, n, nullptr, boxes, rot, count, mean_u, mean_v, speed, stats, nullptr, nullptr,
+                     nullptr, nullptr);
+}
+
+int icelk_boxes_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                            const double* t, int n, const icelk_day_tables_t* day, const icelk_boxes_t* boxes,
+                            const double* rot, int* count, double* mean_u, double* mean_v, double* speed,
+                            const icelk_grid_stats_t* stats, int* sel_count, double* t_min, double* t_max,
+                            double* device_ms)
+{
+    if (!h) return ICELK_EARG;
+    if (!day) FAIL(C(h), ICELK_EARG, "the day tables are null");
+    return boxes_bin(h, x, y, u, v, t, n, day, boxes, rot, count, mean_u, mean_v, speed, stats, sel_count, t_min, t_max,
+                     device_ms);
 }
 
 int icelk_grid_cell_stats_host(const double* a, int n, double* out_std, double* out_median, double* out_mad)

@@ -98,6 +98,9 @@ enum KernelId {
     K_GRID_SEGMENTS,           // the per-cell statistics (k_grid.hip): begin and count of every segment
     K_GRID_STD,                // ... np.std(ddof=1), one thread per segment
     K_GRID_SELECT,             // ... median and MAD, one workgroup per segment and array
+    K_BOXES_ASSIGN,            // transect / mooring boxes (k_grid.hip): every point against every box, one window
+    K_BOXES_DAY_ASSIGN,        // ... a whole day of windows
+    K_GRID_DAY_ASSIGN,         // the day gridder's assign kernel, for comparison with the one above
     K_COUNT_
 };
 
@@ -537,6 +540,19 @@ void launch_grid_day_assign(hipStream_t s, const double* x, const double* y, con
                             double top, double spacing, int cols, int rows, const uint8_t* cell_on,
                             unsigned long long* keys, int* key_count, int key_cap, int* sel_count,
                             unsigned long long* t_min, unsigned long long* t_max);
+// boxes that are no lattice (transects, moorings): nboxes polygons, box b's nvert-in-all vertices at box_xy[2 * box_off[b]]
+// .. ; key segment = box, or window * nboxes + box.  rot: NULL, or {cos, sin} -- then the kernel also writes u c + v s and
+// v c - u s of every point into ur, vr (what the reduce is then given); dynamic LDS: 16 nvert + 20 nboxes + 4 bytes
+void launch_boxes_assign(hipStream_t s, const double* x, const double* y, int n, const double* box_xy, const int* box_off,
+                         int nboxes, int nvert, const double* u, const double* v, double* ur, double* vr, const double* rot,
+                         unsigned long long* keys, int* key_count, int key_cap);
+void launch_boxes_day_assign(hipStream_t s, const double* x, const double* y, const double* t, int n,
+                             const long long* file_off, const int* file_cam, const int* win_f0, const int* win_f1,
+                             int nfiles, const long long* t_lo, const long long* t_hi, int ncam, int nw,
+                             const double* box_xy, const int* box_off, int nboxes, int nvert, const double* u,
+                             const double* v, double* ur, double* vr, const double* rot, unsigned long long* keys,
+                             int* key_count, int key_cap, int* sel_count, unsigned long long* t_min,
+                             unsigned long long* t_max);
 void launch_grid_reduce(hipStream_t s, const unsigned long long* keys, const int* key_count, const double* u,
                         const double* v, int ncells, int* count, double* mean_u, double* mean_v, double* speed);
 // per-segment std, median and MAD (grid_stats.h): the segment table, then one thread / one workgroup per segment.  `out`

@@ -13,6 +13,8 @@
 // chunks of numpy's iterator buffer, np_sums.h) -- float64, bit for bit what np.sum gives -- and takes the hypot (glibc's algorithm, see k_utm.hip).
 // Asked for, the sorted runs also give every cell's np.std(ddof=1), np.median and median absolute deviation
 // (k_grid_segments, k_grid_std, k_grid_select below; the rules are grid_stats.h's).
+// Boxes that form no lattice -- along a transect, around a mooring (imports/tracking_misc.py:76-185) -- have assign kernels
+// of their own (k_boxes_assign, k_boxes_day_assign: every point against every box) and share everything behind them.
 #include "icelk_internal.h"
 #include "grid_stats.h"
 
@@ -83,14 +85,12 @@ __device__ __forceinline__ unsigned hit_mask(const GridGeom& g, const uint8_t* _
     return m;
 }
 
-// writes the keys ((seg_base + cell) << 32) | p of the cells in hit mask m, one block-wide scan for the slots
-__device__ __forceinline__ void append_keys(unsigned m, int i0, int j0, unsigned seg_base, int rows, int p,
-                                            unsigned long long* __restrict__ keys, int* __restrict__ key_count,
-                                            int key_cap)
+// the first of the cnt key slots of this thread: one block-wide scan of the counts, one atomic per workgroup.  Every
+// thread of the 256 calls it, once per kernel.
+__device__ __forceinline__ int key_slots(int cnt, int* __restrict__ key_count)
 {
     __shared__ int wave_tot[4];
     __shared__ int s_base;
-    const int cnt = __popc(m);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int inc = cnt;
 #pragma unroll
@@ -107,7 +107,15 @@ __device__ __forceinline__ void append_keys(unsigned m, int i0, int j0, unsigned
     }
     if (threadIdx.x == 0) s_base = total ? atomicAdd(key_count, total) : 0;
     __syncthreads();
-    int at = s_base + wbase + inc - cnt;
+    return s_base + wbase + inc - cnt;
+}
+
+// writes the keys ((seg_base + cell) << 32) | p of the cells in hit mask m
+__device__ __forceinline__ void append_keys(unsigned m, int i0, int j0, unsigned seg_base, int rows, int p,
+                                            unsigned long long* __restrict__ keys, int* __restrict__ key_count,
+                                            int key_cap)
+{
+    int at = key_slots(__popc(m), key_count);
     for (int k = 0; k < 9; k++)
         if (m & (1u << k)) {
             const int i = i0 + (k % 3) - 1, j = j0 + (k / 3) - 1;
@@ -144,41 +152,41 @@ struct DayTables {
     int nfiles, ncam, nw;
 };
 
-__global__ __launch_bounds__(256) void k_grid_day_assign(const double* __restrict__ x, const double* __restrict__ y,
-                                                         const double* __restrict__ t, int n, DayTables D, GridGeom g,
-                                                         const uint8_t* __restrict__ cell_on, int ncells,
-                                                         unsigned long long* __restrict__ keys,
-                                                         int* __restrict__ key_count, int key_cap,
-                                                         int* __restrict__ sel_count,
-                                                         unsigned long long* __restrict__ t_min,
-                                                         unsigned long long* __restrict__ t_max)
+// the window of point p, -1 for none; *cam its camera and *tp its time (both set whenever p < n)
+__device__ __forceinline__ int day_window(const DayTables& D, const double* __restrict__ t, int p, int n, int* cam,
+                                          double* tp)
 {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    int w = -1, cam = 0;
-    double tp = 0.0;
-    if (p < n) {
-        int f = 0, hi = D.nfiles - 1;                       // last file starting at or before p (empty files skipped)
-        while (f < hi) {
-            const int mid = (f + hi + 1) >> 1;
-            if (D.file_off[mid] <= p) f = mid;
-            else hi = mid - 1;
-        }
-        cam = D.file_cam[f];
-        tp = t[p];
-        const long long* lo = D.t_lo + (size_t)cam * D.nw;
-        int a = 0, b = D.nw;                                // windows starting at or before tp
-        while (a < b) {
-            const int mid = (a + b) >> 1;
-            if ((double)lo[mid] <= tp) a = mid + 1;
-            else b = mid;
-        }
-        const int wc = a - 1;
-        const size_t sl = (size_t)cam * D.nw + wc;
-        if (wc >= 0 && f >= D.win_f0[sl] && f <= D.win_f1[sl] && tp < (double)D.t_hi[sl]) w = wc;
+    *cam = 0;
+    *tp = 0.0;
+    if (p >= n) return -1;
+    int f = 0, hi = D.nfiles - 1;                       // last file starting at or before p (empty files skipped)
+    while (f < hi) {
+        const int mid = (f + hi + 1) >> 1;
+        if (D.file_off[mid] <= p) f = mid;
+        else hi = mid - 1;
     }
-    // selected count and time range per (window, camera): lanes of one slot are combined first -- a wave's points are
-    // consecutive, so nearly always one slot per wave and one set of atomics
-    const int slot = w >= 0 ? w * D.ncam + cam : -1;
+    *cam = D.file_cam[f];
+    *tp = t[p];
+    const long long* lo = D.t_lo + (size_t)*cam * D.nw;
+    int a = 0, b = D.nw;                                // windows starting at or before tp
+    while (a < b) {
+        const int mid = (a + b) >> 1;
+        if ((double)lo[mid] <= *tp) a = mid + 1;
+        else b = mid;
+    }
+    const int wc = a - 1;
+    const size_t sl = (size_t)*cam * D.nw + wc;
+    if (wc >= 0 && f >= D.win_f0[sl] && f <= D.win_f1[sl] && *tp < (double)D.t_hi[sl]) return wc;
+    return -1;
+}
+
+// selected count and time range per (window, camera) slot (-1: the point is in none): lanes of one slot are combined
+// first -- a wave's points are consecutive, so nearly always one slot per wave and one set of atomics.  Called by every
+// lane of the wave.
+__device__ __forceinline__ void day_slot_reduce(int slot, double tp, int* __restrict__ sel_count,
+                                                unsigned long long* __restrict__ t_min,
+                                                unsigned long long* __restrict__ t_max)
+{
     const unsigned long long tk = order_key(tp);
     unsigned long long pending = __ballot(slot >= 0);
     while (pending) {
@@ -201,9 +209,147 @@ __global__ __launch_bounds__(256) void k_grid_day_assign(const double* __restric
         }
         pending &= ~__ballot(mine);
     }
+}
+
+__global__ __launch_bounds__(256) void k_grid_day_assign(const double* __restrict__ x, const double* __restrict__ y,
+                                                         const double* __restrict__ t, int n, DayTables D, GridGeom g,
+                                                         const uint8_t* __restrict__ cell_on, int ncells,
+                                                         unsigned long long* __restrict__ keys,
+                                                         int* __restrict__ key_count, int key_cap,
+                                                         int* __restrict__ sel_count,
+                                                         unsigned long long* __restrict__ t_min,
+                                                         unsigned long long* __restrict__ t_max)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    int cam = 0;
+    double tp = 0.0;
+    const int w = day_window(D, t, p, n, &cam, &tp);
+    day_slot_reduce(w >= 0 ? w * D.ncam + cam : -1, tp, sel_count, t_min, t_max);
     int i0 = 0, j0 = 0;
     const unsigned m = w >= 0 ? hit_mask(g, cell_on, x[p], y[p], &i0, &j0) : 0u;
     append_keys(m, i0, j0, (unsigned)w * (unsigned)ncells, g.rows, p, keys, key_count, key_cap);
+}
+
+// ---- boxes that are no lattice: transects and moorings (icelk_boxes_bin, icelk_boxes_bin_windows) ----------------------
+// B polygons of three or more vertices each, box b's vertices at xy[2 * off[b]] .. xy[2 * off[b + 1]) as (x, y) pairs.
+// The boxes of a transect meet along edges that are no grid lines, so no index arithmetic finds a point's boxes: every
+// thread tests its point against every box, with contains_poly on the vertices as they were given, and a point lies in
+// none, one or several of them.  The list is staged once per workgroup in LDS (all lanes read the same vertex at the same
+// time: a broadcast), with every box's smallest and largest y beside it.
+// A box is skipped without the crossing test only where ty lies outside [min y, max y]: then y_k >= ty has the same
+// answer at every vertex, no edge has f0 != f1 and nothing toggles -- also for a NaN ty, which compares false everywhere.
+// The same shortcut on x is not taken: the side test is a rounded expression, and a point beyond the box's x range on
+// an edge's level is decided by that rounding, not by the range.
+struct BoxList {
+    const double* xy;
+    const int* off;
+    int nboxes, nvert;
+};
+
+// velocities turned into the boxes' frame: u' = u c + v s along, v' = v c - u s across; every operation rounded once
+struct BoxRot {
+    const double* u;
+    const double* v;
+    double* ur;
+    double* vr;
+    double c, s;
+    int on;
+};
+
+struct BoxLds {
+    double* xy;      // 2 * nvert
+    double* ylo;     // nboxes
+    double* yhi;     // nboxes
+    int* off;        // nboxes + 1
+};
+
+__device__ __forceinline__ BoxLds stage_boxes(const BoxList& L, double* lds)
+{
+    BoxLds S{lds, lds + 2 * L.nvert, lds + 2 * L.nvert + L.nboxes, (int*)(lds + 2 * L.nvert + 2 * L.nboxes)};
+    for (int k = threadIdx.x; k < 2 * L.nvert; k += 256) S.xy[k] = L.xy[k];
+    for (int k = threadIdx.x; k <= L.nboxes; k += 256) S.off[k] = L.off[k];
+    __syncthreads();
+    for (int b = threadIdx.x; b < L.nboxes; b += 256) {
+        double lo = S.xy[2 * S.off[b] + 1], hi = lo;
+        for (int k = S.off[b] + 1; k < S.off[b + 1]; k++) {
+            const double yk = S.xy[2 * k + 1];
+            lo = yk < lo ? yk : lo;
+            hi = yk > hi ? yk : hi;
+        }
+        S.ylo[b] = lo;
+        S.yhi[b] = hi;
+    }
+    __syncthreads();
+    return S;
+}
+
+__device__ __forceinline__ bool in_box(const BoxLds& S, int b, double tx, double ty)
+{
+    if (!(ty >= S.ylo[b] && ty <= S.yhi[b])) return false;
+    return contains_poly(S.xy + 2 * S.off[b], S.off[b + 1] - S.off[b], tx, ty);
+}
+
+// The keys ((seg_base + b) << 32) | p of every box b that holds (tx, ty); `live` false: none.  A thread may have any
+// number of hits, so they are counted first (the first and the last hit remembered), the counts scanned (key_slots),
+// and the boxes from the first hit to the last walked again to write -- for a point in one box that is one test.
+__device__ __forceinline__ void append_box_keys(const BoxLds& S, int nboxes, bool live, double tx, double ty,
+                                                unsigned seg_base, int p, unsigned long long* __restrict__ keys,
+                                                int* __restrict__ key_count, int key_cap)
+{
+    int cnt = 0, first = 0, last = -1;
+    if (live)
+        for (int b = 0; b < nboxes; b++)
+            if (in_box(S, b, tx, ty)) {
+                if (!cnt) first = b;
+                last = b;
+                cnt++;
+            }
+    int at = key_slots(cnt, key_count);
+    for (int b = first; b <= last; b++)
+        if (b == first || b == last || in_box(S, b, tx, ty)) {
+            if (at >= 0 && at < key_cap) keys[at] = ((unsigned long long)(seg_base + (unsigned)b) << 32) | (unsigned)p;
+            at++;
+        }
+}
+
+__device__ __forceinline__ void rotate_velocity(const BoxRot& R, int p)
+{
+    const double u = R.u[p], v = R.v[p];
+    R.ur[p] = u * R.c + v * R.s;
+    R.vr[p] = v * R.c - u * R.s;
+}
+
+__global__ __launch_bounds__(256) void k_boxes_assign(const double* __restrict__ x, const double* __restrict__ y, int n,
+                                                      BoxList L, BoxRot R, unsigned long long* __restrict__ keys,
+                                                      int* __restrict__ key_count, int key_cap)
+{
+    extern __shared__ double box_lds[];
+    const BoxLds S = stage_boxes(L, box_lds);
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const bool live = p < n;
+    if (live && R.on) rotate_velocity(R, p);
+    append_box_keys(S, L.nboxes, live, live ? x[p] : 0.0, live ? y[p] : 0.0, 0u, p, keys, key_count, key_cap);
+}
+
+__global__ __launch_bounds__(256) void k_boxes_day_assign(const double* __restrict__ x, const double* __restrict__ y,
+                                                          const double* __restrict__ t, int n, DayTables D, BoxList L,
+                                                          BoxRot R, unsigned long long* __restrict__ keys,
+                                                          int* __restrict__ key_count, int key_cap,
+                                                          int* __restrict__ sel_count,
+                                                          unsigned long long* __restrict__ t_min,
+                                                          unsigned long long* __restrict__ t_max)
+{
+    extern __shared__ double box_lds[];
+    const BoxLds S = stage_boxes(L, box_lds);
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    int cam = 0;
+    double tp = 0.0;
+    const int w = day_window(D, t, p, n, &cam, &tp);
+    day_slot_reduce(w >= 0 ? w * D.ncam + cam : -1, tp, sel_count, t_min, t_max);
+    if (p < n && R.on) rotate_velocity(R, p);
+    const bool live = w >= 0;
+    append_box_keys(S, L.nboxes, live, live ? x[p] : 0.0, live ? y[p] : 0.0, (unsigned)w * (unsigned)L.nboxes, p, keys,
+                    key_count, key_cap);
 }
 
 // element t of the velocities keyed by keys[start + t] (np_sums.h: numpy's pairwise order)
@@ -435,6 +581,38 @@ void launch_grid_day_assign(hipStream_t s, const double* x, const double* y, con
     const DayTables D{file_off, file_cam, win_f0, win_f1, t_lo, t_hi, nfiles, ncam, nw};
     hipLaunchKernelGGL(k_grid_day_assign, dim3((n + 255) / 256), dim3(256), 0, s, x, y, t, n, D, g, cell_on,
                        cols * rows, keys, key_count, key_cap, sel_count, t_min, t_max);
+}
+
+static size_t box_lds_bytes(int nboxes, int nvert)
+{
+    return sizeof(double) * (2 * (size_t)nvert + 2 * (size_t)nboxes) + sizeof(int) * ((size_t)nboxes + 1);
+}
+
+void launch_boxes_assign(hipStream_t s, const double* x, const double* y, int n, const double* box_xy, const int* box_off,
+                         int nboxes, int nvert, const double* u, const double* v, double* ur, double* vr, const double* rot,
+                         unsigned long long* keys, int* key_count, int key_cap)
+{
+    if (n <= 0) return;
+    const BoxList L{box_xy, box_off, nboxes, nvert};
+    const BoxRot R{u, v, ur, vr, rot ? rot[0] : 1.0, rot ? rot[1] : 0.0, rot ? 1 : 0};
+    hipLaunchKernelGGL(k_boxes_assign, dim3((n + 255) / 256), dim3(256), box_lds_bytes(nboxes, nvert), s, x, y, n, L, R,
+                       keys, key_count, key_cap);
+}
+
+void launch_boxes_day_assign(hipStream_t s, const double* x, const double* y, const double* t, int n,
+                             const long long* file_off, const int* file_cam, const int* win_f0, const int* win_f1,
+                             int nfiles, const long long* t_lo, const long long* t_hi, int ncam, int nw,
+                             const double* box_xy, const int* box_off, int nboxes, int nvert, const double* u,
+                             const double* v, double* ur, double* vr, const double* rot, unsigned long long* keys,
+                             int* key_count, int key_cap, int* sel_count, unsigned long long* t_min,
+                             unsigned long long* t_max)
+{
+    if (n <= 0) return;
+    const DayTables D{file_off, file_cam, win_f0, win_f1, t_lo, t_hi, nfiles, ncam, nw};
+    const BoxList L{box_xy, box_off, nboxes, nvert};
+    const BoxRot R{u, v, ur, vr, rot ? rot[0] : 1.0, rot ? rot[1] : 0.0, rot ? 1 : 0};
+    hipLaunchKernelGGL(k_boxes_day_assign, dim3((n + 255) / 256), dim3(256), box_lds_bytes(nboxes, nvert), s, x, y, t, n,
+                       D, L, R, keys, key_count, key_cap, sel_count, t_min, t_max);
 }
 
 void launch_grid_reduce(hipStream_t s, const unsigned long long* keys, const int* key_count, const double* u,

@@ -201,6 +201,25 @@ def _load_hour_file(path, with_speed=False):
     return x, y, u, v, t
 
 
+def load_day(plan, with_speed=False):
+    """The plan's hour files as the device passes take them (`icelk_grid_bin_windows`, `icelk_boxes_bin_windows`): x, y, u,
+    v, t concatenated camera by camera, hour by hour; off (file f holds points off[f] .. off[f + 1]), fcam (its camera);
+    lo, hi (cameras x windows, the int64 epoch bounds), wf0, wf1 (the files each window loads); parts, the files'
+    own arrays (with their speed when asked for).  An unreadable file holds no point.  None when no file holds one."""
+    empty = (np.zeros(0),) * (6 if with_speed else 5)
+    parts = [_load_hour_file(f["path"], with_speed) or empty for f in plan.files]
+    if sum(len(p[0]) for p in parts) == 0:
+        return None
+    out = {k: np.concatenate([p[i] for p in parts]) for i, k in enumerate(("x", "y", "u", "v", "t"))}
+    out["off"] = np.zeros(len(parts) + 1, np.int64)
+    out["off"][1:] = np.cumsum([len(p[0]) for p in parts])
+    out["fcam"] = np.array([f["cam"] for f in plan.files], np.int32)
+    out["lo"], out["hi"] = (np.array([c[k] for c in plan.cameras], np.int64) for k in ("lo", "hi"))
+    out["wf0"], out["wf1"] = (np.array([c[k] for c in plan.cameras], np.int32) for k in ("f0", "f1"))
+    out["parts"] = parts
+    return out
+
+
 def tracking_interval(workspace, day_str):
     """The camera's tracking interval in seconds, from the name of its first file of the day (s3:318,340)."""
     npzs = sorted(glob.glob(os.path.join(workspace, day_str + "*utm.npz")))
@@ -319,17 +338,12 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
     clock = time.perf_counter
     t0 = clock()
     vectors = maps is not None and maps["plot_switch"] == 2
-    empty = (np.zeros(0),) * (6 if vectors else 5)
-    parts = [_load_hour_file(f["path"], vectors) or empty for f in plan.files]        # an unreadable file holds no point
-    n = sum(len(p[0]) for p in parts)
-    if n == 0:
+    loaded = load_day(plan, vectors)
+    if loaded is None:
         return []
-    x, y, u, v, t = (np.concatenate([p[k] for p in parts]) for k in range(5))
-    off = np.zeros(len(parts) + 1, np.int64)
-    off[1:] = np.cumsum([len(p[0]) for p in parts])
-    fcam = np.array([f["cam"] for f in plan.files], np.int32)
-    lo, hi = (np.array([c[k] for c in plan.cameras], np.int64) for k in ("lo", "hi"))
-    wf0, wf1 = (np.array([c[k] for c in plan.cameras], np.int32) for k in ("f0", "f1"))
+    x, y, u, v, t, off, fcam, lo, hi, wf0, wf1, parts = (loaded[k] for k in ("x", "y", "u", "v", "t", "off", "fcam", "lo", "hi",
+                                                                             "wf0", "wf1", "parts"))
+    n = len(x)
     ncam, nw = lo.shape
     grid = create_grid_across_fjord(ctx, fjord, grid_size)
     topleft, rows, cols = grid[3], grid[4], grid[5]

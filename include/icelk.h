@@ -408,6 +408,51 @@ int icelk_grid_bin_windows_stats(icelk_t* h, const double* x, const double* y, c
  * are tested against.  No handle and no GPU.  ICELK_EARG for n < 0 or a null pointer. */
 int icelk_grid_cell_stats_host(const double* a, int n, double* out_std, double* out_median, double* out_mad);
 
+/* ---- binning into transect and mooring boxes (imports/tracking_misc.py:76-185) ---------------------------------
+ * The same products as the gridder's -- count, mean_u, mean_v, speed and, asked for, the six statistics above -- for a
+ * list of polygons that form no lattice: the rotated boxes along a transect or around a mooring.  Box b has the vertices
+ * xy[2 * offset[b]] .. xy[2 * offset[b + 1]) as (x, y) pairs, tested as given by contains_points' rule; the boxes may
+ * overlap and share edges, so a point counts in none, one or several of them.  A box's velocities are added in the
+ * order of the points, as Path(poly).contains_points(points) selects them.
+ * offset[0] = 0, ascending, three or more vertices per polygon, finite vertices: else ICELK_EARG.  nboxes in 1 .. 1024
+ * and at most 2048 vertices in all: else ICELK_ECAP. */
+typedef struct icelk_boxes {
+    const double* xy;
+    const int* offset; /* nboxes + 1 */
+    int nboxes;
+} icelk_boxes_t;
+/* Host only, no handle and no GPU: ICELK_OK for a list the two calls below take, else what they would return for it. */
+int icelk_boxes_check(const icelk_boxes_t* boxes);
+/* One window.  rot: NULL, or {cos a, sin a} -- every point's velocity is then first turned into the frame of a transect of
+ * azimuth a, u' = u cos + v sin (along), v' = v cos - u sin (across), each product and sum rounded once, and the outputs are
+ * those of u', v'.  Out, per box: count, mean_u, mean_v, speed; stats may be NULL, else its six members are filled as
+ * icelk_grid_bin_stats fills them (a null member: ICELK_EARG).  Every argument is checked before anything is allocated.
+ * ICELK_ECAP also when n * nboxes does not fit 31 bits, n > 2^27, or -- seen after the boxes were tested -- the points lie
+ * in more than 2 n + 1024 boxes altogether; the handle stays usable. */
+int icelk_boxes_bin(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n,
+                    const icelk_boxes_t* boxes, const double* rot, int* count, double* mean_u, double* mean_v,
+                    double* speed, const icelk_grid_stats_t* stats);
+/* The file and window tables of icelk_grid_bin_windows, under the same rules. */
+typedef struct icelk_day_tables {
+    const int64_t* file_offset; /* nfiles + 1 */
+    const int* file_cam;        /* nfiles */
+    const int* win_f0;          /* ncam * nw */
+    const int* win_f1;
+    int nfiles;
+    const int64_t* t_lo; /* ncam * nw */
+    const int64_t* t_hi;
+    int ncam, nw;
+} icelk_day_tables_t;
+/* Every time window of a day in one pass: for window w what icelk_boxes_bin gives on the points icelk_grid_bin_windows
+ * would select for it, bit for bit, per (window w, box b) at w * nboxes + b.  sel_count, t_min, t_max (per (window,
+ * camera) at w * ncam + c) and device_ms (may be NULL) are that call's.  ICELK_ECAP when nw * nboxes or n * nboxes does
+ * not fit 31 bits or n > 2^30, and for more than 2 n + 1024 keys as above. */
+int icelk_boxes_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                            const double* t, int n, const icelk_day_tables_t* day, const icelk_boxes_t* boxes,
+                            const double* rot, int* count, double* mean_u, double* mean_v, double* speed,
+                            const icelk_grid_stats_t* stats, int* sel_count, double* t_min, double* t_max,
+                            double* device_ms);
+
 /* ---- averages of the run-wide velocity cube (s4_postprocess_gridded_utm.py:264-343) -------------------------
  * The stacked gridded windows of a run: u, v, count (host float64, NaN where a window has no entry for a cell), laid
  * out [window][cell] with cell = row * cols + col -- nt planes of ncells values.  icelk_cube_set uploads them; they
