@@ -31,6 +31,8 @@ from .velocity_map import (gist_rainbow_table, map_descriptor, map_glyph, map_in
                            map_insets, map_strings, map_texts, map_view, scaled_arrows)
 from .png import encode_png_host, png_bound, png_filter_host  # noqa: F401
 from .movie import MovieWriter, frame_host, movie_size, read_avi, resize_host  # noqa: F401
+from .orthophoto import (ortho_coords_host, ortho_movie_name, ortho_raster, orthophoto, orthophoto_host, orthophoto_sequence,  # noqa: F401
+                         read_world_file, world_file)
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

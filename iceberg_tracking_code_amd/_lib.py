@@ -114,6 +114,21 @@ class MapInsetPixels(C.Structure):
 map_inset_p = C.POINTER(MapInset)
 MAP_INSETS_MAX = 8
 
+
+class OrthoRaster(C.Structure):
+    """icelk_ortho_raster_t"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("res", C.c_double), ("width", C.c_int), ("height", C.c_int)]
+
+
+class OrthoOpts(C.Structure):
+    """icelk_ortho_opts_t"""
+    _fields_ = [("max_range", C.c_double), ("sampling", C.c_int), ("fill", C.c_uint8 * 3)]
+
+
+ortho_raster_p = C.POINTER(OrthoRaster)
+ortho_opts_p = C.POINTER(OrthoOpts)
+ORTHO_MAX_INDEX = 254
+
 JPEG_CROP_ROUTES = ("device", "host-huffman", "over-budget")   # ICELK_JPEG_CROP_*
 JPEG_TABLE_BYTES = 11328
 JPEG_FALLBACK_NONE, JPEG_FALLBACK_BOUND, JPEG_FALLBACK_STREAM, JPEG_FALLBACK_SIZE = 0, 1, 2, 3
@@ -200,6 +215,15 @@ SIGNATURES = {
     "icelk_resize_rgb": (C.c_int, [handle_p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
     "icelk_picture_size": (C.c_int, [handle_p, i32p, i32p]),
     "icelk_picture_frame": (C.c_int, [handle_p, C.c_int, C.c_int, C.c_int, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_ortho_coords_host": (C.c_int, [vp, ortho_raster_p, C.c_int, C.c_int, C.c_double, f64p, f64p, f64p, u8p]),
+    "icelk_ortho_begin_host": (C.c_int, [ortho_raster_p, ortho_opts_p, u8p, C.c_int, u8p, C.c_int, f64p]),
+    "icelk_ortho_add_host": (C.c_int, [ortho_raster_p, ortho_opts_p, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_int, u8p,
+                                       C.c_int, f64p]),
+    "icelk_ortho_begin": (C.c_int, [handle_p, ortho_raster_p, ortho_opts_p]),
+    "icelk_ortho_add_pixels": (C.c_int, [handle_p, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "icelk_ortho_add_jpeg_file": (C.c_int, [handle_p, vp, C.c_int, vp, C.c_uint64]),
+    "icelk_ortho_add_slot": (C.c_int, [handle_p, vp, C.c_int, C.c_int]),
+    "icelk_ortho_write": (C.c_int, [handle_p, C.c_int, C.c_int, u8p, C.c_int, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "icelk_set_gray_device":(C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

@@ -12,6 +12,7 @@ from . import _lib
 from ._lib import check, f32p, u8p
 from .plot import PLOT_QUALITY, PLOT_WIDTH, _stamp_arg, _tracks3, plot_size
 from .velocity_map import _resident_args, map_descriptor, map_inset_array
+from .orthophoto import FORMATS as ORTHO_FORMATS, _source_array, _source_bytes, opts_struct, raster_struct
 from .jpeg import (UnsupportedJpeg, _comment_args, _encode_call, _rgb3, _stats_dict, describe_jpeg, resave_coefficients,
                    resave_quality, thumbnail_host, thumbnail_size)
 
@@ -60,6 +61,7 @@ def _criteria(criteria):
 # bytes first offered for a file of each kind (`_file_call`); a map's PNG is about 1.6 x its JPEG (profiles/png_map.txt)
 FIRST_GUESSES = {"crop": 1 << 16, "resave": 1 << 16, "plot": 1 << 18, "map_jpeg": 1 << 18, "map_png": 1 << 18}
 FRAME_FIRST_GUESS = 1 << 19   # ... and for a movie frame (`Context.picture_frame`)
+ORTHO_FIRST_GUESS = 1 << 18   # ... and for an orthophoto (`Context.ortho_write`)
 
 
 def _file_call(guesses, key, call, what, handle=None, extra=0):
@@ -87,6 +89,7 @@ class Context:
         self.max_w, self.max_h, self.n_slots, self.max_pts, self.device = max_w, max_h, n_slots, max_pts, device
         check(self._lib.icelk_create(device, max_w, max_h, n_slots, max_pts, C.byref(self._h)), None)
         self._guesses = dict(FIRST_GUESSES)
+        self._ortho_size = None   # (width, height) of the mosaic `ortho_begin` began
 
     # -- lifetime -----------------------------------------------------------------------------
     def close(self):
@@ -824,6 +827,60 @@ class Context:
         data = _file_call(self._guesses, "frame", lambda out, cap, n: self._lib.icelk_picture_frame(
             self._h, ow, oh, int(quality), rgb_ptr, stride, out, cap, n), "icelk_picture_frame", self._h)
         return (data, rgb) if want_rgb else data
+
+    # -- the orthophoto --------------------------------------------------------
+    def ortho_begin(self, raster, max_range=0.0, sampling="bilinear", fill=(255, 255, 255)):
+        """Begins a mosaic on `raster` (a dict of `orthophoto.ortho_raster`, or (x0, y0, res, width, height)): every pixel
+        the fill colour, seen by no camera (icelk_ortho_begin).  One mosaic is in progress per Context, in the picture
+        writer's R G B: drawing another kind of picture ends it."""
+        r, o = raster_struct(raster), opts_struct(max_range, sampling, fill)
+        self._ck(self._lib.icelk_ortho_begin(self._h, C.byref(r), C.byref(o)))
+        self._ortho_size = (r.width, r.height)
+
+    def ortho_add(self, camera, index, source):
+        """Adds a camera's photograph to the mosaic under `index` (0 .. 254): where the camera sees a pixel from nearer
+        than every camera added so far, the pixel takes its sample (k_ortho_add).  `source`: the bytes of a JPEG file or a
+        path to one (decoded on the device; `UnsupportedJpeg` for a file its decoder refuses), an (h, w) or (h, w, 3) uint8
+        array, or ("slot", k)."""
+        cam = camera.struct()
+        if isinstance(source, tuple) and len(source) == 2 and source[0] == "slot":
+            self._ck(self._lib.icelk_ortho_add_slot(self._h, C.byref(cam), int(index), int(source[1])))
+            return
+        a = _source_array(source)
+        if a is not None:
+            self._ck(self._lib.icelk_ortho_add_pixels(self._h, C.byref(cam), int(index), a.ctypes.data, a.shape[1], a.shape[0],
+                                                      1 if a.ndim == 2 else 3, a.strides[0]))
+            return
+        data = _source_bytes(source)
+        if data is None:
+            raise ValueError("a source is JPEG bytes, a path, a uint8 array or ('slot', k)")
+        self._ck_jpeg(self._lib.icelk_ortho_add_jpeg_file(self._h, C.byref(cam), int(index), data, len(data)))
+
+    def ortho_write(self, format=None, quality=90):
+        """The mosaic as dict(rgb (height, width, 3) uint8, cover (height, width) uint8, file): `file` the bytes of a PNG
+        ("png": exactly the pixels) or of a JPEG ("jpeg": what `Image.fromarray(rgb).save(f, "JPEG", quality=quality)`
+        writes), coded on the device by the picture writer (icelk_ortho_write); None with format=None.  The mosaic stays:
+        further cameras can be added and it can be written again."""
+        if format is not None and format not in ORTHO_FORMATS:
+            raise ValueError("format is None, 'jpeg' or 'png'")
+        if self._ortho_size is None:
+            raise _lib.IcelkError("icelk error %d: no orthophoto has been begun (ortho_begin)" % _lib.ESTATE)
+        w, h = self._ortho_size
+        rgb, cover = np.empty((h, w, 3), np.uint8), np.empty((h, w), np.uint8)
+
+        def call(out, cap, n):
+            return self._lib.icelk_ortho_write(self._h, ORTHO_FORMATS[format or "png"], int(quality), _u8(rgb), rgb.strides[0],
+                                               _u8(cover), cover.strides[0], out, cap, n)
+        if format is None:
+            # no file wanted: none is offered room, and "it takes *len bytes" is the expected answer
+            n = C.c_uint64(0)
+            rc = call(None, 0, C.byref(n))
+            if rc != _lib.ECAP:
+                self._ck(rc)
+            return dict(rgb=rgb, cover=cover, file=None)
+        self._guesses.setdefault("ortho_" + format, ORTHO_FIRST_GUESS)
+        data = _file_call(self._guesses, "ortho_" + format, call, "icelk_ortho_write", self._h)
+        return dict(rgb=rgb, cover=cover, file=data)
 
     # -- measurement ----------------------------------------------------------------------------
     def prof_enable(self, on=True):

@@ -18,6 +18,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "png_filter", "png_parse", "png_scan", "png_pack", "png_adler",
     "resize_rows", "resize_cols",
     "grid_segments", "grid_std", "grid_select",
+    "ortho_fill", "ortho_add",
     "boxes_assign", "boxes_day_assign", "grid_day_assign",
 };
 
@@ -176,6 +177,7 @@ static void destroy_ctx(Ctx* c)
     jpeg_enc_destroy(c);
     plot_destroy(c);
     map_destroy(c);
+    ortho_destroy(c);
     picture_destroy(c);
     png_destroy(c);
     movie_destroy(c);

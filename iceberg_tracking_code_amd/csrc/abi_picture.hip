@@ -38,6 +38,7 @@ int picture_check(Ctx* c, int Wo, int Ho, PictureFormat format, int quality, con
 int picture_grow(Ctx* c, const PictureFile& F)
 {
     Ctx::JpegResave& R = c->picture;
+    c->picture_draws++;   // whoever draws next draws over what d_rgb holds (abi_ortho.hip: the mosaic in progress)
     if (int rc = grow(c, &R.d_rgb, &R.rgb_cap, 3 * F.px)) return rc;
     if (F.format == PICTURE_PNG) return png_grow(c, F.Wo, F.Ho);
     return grow(c, &R.d_rcoef, &R.rcoef_cap, (size_t)F.info.coef_count);

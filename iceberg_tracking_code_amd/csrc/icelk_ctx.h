@@ -252,6 +252,21 @@ struct Ctx {
         size_t src_cap = 0, F_cap = 0, tok_cap = 0, seg_cap = 0, adler_cap = 0, stream_cap = 0;   // elements
     } png;
 
+    // ---- abi_ortho.hip: the mosaic in progress, allocated at first use.  Its R G B is the picture writer's d_rgb (one
+    // picture at a time: `draws` is picture_draws as the mosaic's own calls left it, and another kind of picture drawn
+    // in between ends the mosaic); cover and best are planes of the raster's width x height
+    struct Ortho {
+        uint8_t* d_cover = nullptr;
+        double* d_best = nullptr;
+        uint8_t* d_src = nullptr;       // the pixels of icelk_ortho_add_pixels
+        size_t cover_cap = 0, best_cap = 0, src_cap = 0;
+        bool active = false;
+        unsigned long long draws = 0;
+        icelk_ortho_raster_t raster{};
+        icelk_ortho_opts_t opts{};
+    } ortho;
+    unsigned long long picture_draws = 0;   // picture_grow calls: every picture drawn into picture.d_rgb makes one first
+
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
     float *d_p0 = nullptr, *d_p1 = nullptr, *d_p0r = nullptr, *d_err_f = nullptr, *d_err_b = nullptr, *d_dist = nullptr;
     uint8_t *d_st_f = nullptr, *d_st_b = nullptr, *d_valid = nullptr;
@@ -684,6 +699,8 @@ int picture_write(Ctx* c, hipStream_t st, const PictureFile& F, uint8_t* rgb_or_
                   uint64_t* len);
 // abi_movie.hip
 void movie_destroy(Ctx* c);
+// abi_ortho.hip
+void ortho_destroy(Ctx* c);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);

@@ -13,6 +13,7 @@
 #include "map_raster.h"
 #include "thumb_raster.h"
 #include "resize.h"
+#include "ortho.h"
 
 namespace icelk {
 
@@ -98,6 +99,9 @@ enum KernelId {
     K_GRID_SEGMENTS,           // the per-cell statistics (k_grid.hip): begin and count of every segment
     K_GRID_STD,                // ... np.std(ddof=1), one thread per segment
     K_GRID_SELECT,             // ... median and MAD, one workgroup per segment and array
+    // (new entries go in front of the three box entries, which tests/test_transect_host.py holds to be the table's last)
+    K_ORTHO_FILL,              // the orthophoto (k_ortho.hip): a mosaic begun -- fill colour, cover 0, best +inf
+    K_ORTHO_ADD,               // ... a camera's photograph gathered into the raster
     K_BOXES_ASSIGN,            // transect / mooring boxes (k_grid.hip): every point against every box, one window
     K_BOXES_DAY_ASSIGN,        // ... a whole day of windows
     K_GRID_DAY_ASSIGN,         // the day gridder's assign kernel, for comparison with the one above
@@ -301,6 +305,12 @@ void launch_map_resolve(hipStream_t s, const map::Scene* d_scene, int Wo, int Ho
 // Wt x Ht thumbnail (R G B, dst_pitch bytes per row); ncomp 1 or 3.  I.px: device memory; rgb: the map's R G B, 3 Wo bytes per row
 void launch_jpeg_thumb(hipStream_t s, const JpegOutArgs& A, int ncomp, int Wt, int Ht);
 void launch_map_inset(hipStream_t s, const thumb::Inset& I, int Wo, int Ho, uint8_t* rgb);
+
+// k_ortho.hip: the orthophoto (the arithmetic is ortho.h).  rgb: rows 3 R.width bytes apart, cover: R.width bytes, best:
+// R.width doubles, all R.height rows, device memory; S.px device memory
+void launch_ortho_fill(hipStream_t s, int width, int height, const uint8_t* fill, uint8_t* rgb, uint8_t* cover, double* best);
+void launch_ortho_add(hipStream_t s, const icelk_camera_t& cam, const icelk_ortho_raster_t& R, const ortho::Source& S, double max_range,
+                      int sampling, int index, uint8_t* rgb, uint8_t* cover, double* best);
 
 // k_png.hip: the PNG writer (the arithmetic is png_enc.h).  All pointers are device memory; F and tok are allocated in
 // whole segments (png::segments_of(n) * png::kSegment elements), stream is zero before pack and holds

@@ -71,6 +71,51 @@ class CameraModel:
                     half_w=self.pic["width"] / 2.0, half_h=self.pic["height"] / 2.0,
                     crop_left=self.pic["cropleft"], crop_top=self.pic["croptop"])
 
+    # -- numpy mirrors of the reference's Camera methods (camtools.py:286-430), products in its order.  The device's
+    # counterparts: k_project_tracks for photo_to_utm, k_ortho_add (csrc/ortho.h) for utm_to_photo
+    def photo_to_utm(self, x, y):
+        """Photo coordinates of the UNCROPPED photo -> [tx, ty] at sea level (camtools.py:286-332)."""
+        sigma, H, E, N = self.cam["sigma"], self.cam["H"], self.cam["E"], self.cam["N"]
+        X, U, V = self.direction_vectors()
+        xi = x - self.pic["width"] / 2.0
+        yi = y - self.pic["height"] / 2.0
+        tx = H * (sigma * X[0] + xi * U[0] + yi * V[0]) / (sigma * X[2] + xi * U[2] + yi * V[2])
+        ty = H * (sigma * X[1] + xi * U[1] + yi * V[1]) / (sigma * X[2] + xi * U[2] + yi * V[2])
+        return [tx + E, ty + N]
+
+    def utm_to_photo(self, tx, ty):
+        """Map coordinates at sea level -> [x, y] on the UNCROPPED photo (camtools.py:334-392).  The formula also answers
+        for points behind the camera (their mirror points); `orthophoto.ortho_coords_host` says which are seen."""
+        sigma, H, E, N = self.cam["sigma"], self.cam["H"], self.cam["E"], self.cam["N"]
+        X, U, V = self.direction_vectors()
+        tx = tx - E
+        ty = ty - N
+        a = U[2] / H * tx - U[0]
+        b = V[2] / H * tx - V[0]
+        c = U[2] / H * ty - U[1]
+        d = V[2] / H * ty - V[1]
+        p = sigma * (X[0] - X[2] / H * tx)
+        q = sigma * (X[1] - X[2] / H * ty)
+        xi = (d * p - b * q) / (a * d - b * c)
+        yi = (-c * p + a * q) / (a * d - b * c)
+        return [xi + self.pic["width"] / 2.0, yi + self.pic["height"] / 2.0]
+
+    def project_vectorfield_to_utm(self, x, y, u, v):
+        """A vector field in photo coordinates -> [x_utm, y_utm, u_utm, v_utm] (camtools.py:394-412): every vector's two
+        ends, half a vector either side of its position, projected."""
+        x_utm, y_utm = self.photo_to_utm(x, y)
+        x_start, y_start = self.photo_to_utm(x - 0.5 * u, y - 0.5 * v)
+        x_end, y_end = self.photo_to_utm(x + 0.5 * u, y + 0.5 * v)
+        return [x_utm, y_utm, x_end - x_start, y_end - y_start]
+
+    def photocords_cropped_to_uncropped(self, x, y):
+        """camtools.py:414-421"""
+        return [x + self.pic["cropleft"], y + self.pic["croptop"]]
+
+    def photocords_uncropped_to_cropped(self, x, y):
+        """camtools.py:423-430"""
+        return [x - self.pic["cropleft"], y - self.pic["croptop"]]
+
     def struct(self):
         d = self.as_dict()
         s = CameraStruct()

@@ -998,6 +998,67 @@ int icelk_picture_size(icelk_t* h, int* w, int* h_);
 int icelk_picture_frame(icelk_t* h, int ow, int oh, int quality, uint8_t* rgb_or_null, int rgb_stride, uint8_t* file, uint64_t capacity,
                         uint64_t* len);
 
+/* ---- the orthophoto (opt-in) -----------------------------------------------------
+ * The inverse direction of the projection above: every cell of a map raster is projected into a camera's photograph by
+ * Camera.utm_to_photo (imports/camtools.py:334-392) and the crop offsets (camtools.py:423-430), sampled there, and the
+ * cameras are merged into one mosaic in which the nearest camera wins.  The rule is csrc/ortho.h, which the device
+ * (k_ortho_add, csrc/k_ortho.hip), the host statements below and tests/ortho_restatement.py compute byte for byte alike:
+ *   raster   (x0, y0) is the map position of the centre of pixel (0, 0), the top-left one; res > 0 metres; pixel (i, j)
+ *            is at tx = x0 + i res, ty = y0 - j res (northing decreases with the row)
+ *   seen     pixel (i, j) is seen by a camera with a source of sw x sh samples iff the projection's denominator is
+ *            non-zero, the point lies in front of the camera (sigma X2 + xi U2 + yi V2 has the sign of H), its squared
+ *            distance d2 is at most max_range^2 when max_range > 0, and 0 <= xs <= sw - 1, 0 <= ys <= sh - 1
+ *   sample   fx = floor(256 xs), ix = fx >> 8, ax = fx & 255, ix1 = min(ix + 1, sw - 1), likewise y; bilinear with the
+ *            16-bit weights (256 - ax)(256 - ay) ..., + 32768, >> 16; nearest: ((fx + 128) >> 8, (fy + 128) >> 8).  One
+ *            channel is replicated to R, G, B
+ *   mosaic   begun with the fill colour, cover 0, best +inf; adding camera `index` (0 .. 254) changes a pixel iff it is
+ *            seen and d2 < best: the sample, cover = index + 1, best = d2
+ * A source is at most 65535 samples a side. */
+typedef struct icelk_ortho_raster {
+    double x0, y0, res;
+    int width, height;
+} icelk_ortho_raster_t;
+typedef struct icelk_ortho_opts {
+    double max_range;          /* metres; <= 0: no limit */
+    int sampling;              /* 0 bilinear, 1 nearest */
+    uint8_t fill[3];
+} icelk_ortho_opts_t;
+/* Host only, no handle, re-entrant.  The cropped frame's coordinates, the squared distance and `seen` of every pixel of the
+ * raster, row-major (width * height entries each; any of the four may be NULL).  xs, ys are the reference's numbers bit for
+ * bit wherever it computes finite ones, seen or not.  ICELK_EARG: a null camera or raster, res <= 0, a non-finite number,
+ * sides below 1 or sw, sh outside 1 .. 65535. */
+int icelk_ortho_coords_host(const icelk_camera_t* cam, const icelk_ortho_raster_t* raster, int sw, int sh, double max_range, double* xs,
+                            double* ys, double* d2, uint8_t* seen);
+/* Host only, no handle, re-entrant: the statement on the caller's planes.  rgb: rows rgb_stride >= 3 width bytes apart,
+ * cover: rows cover_stride >= width bytes apart, best: width * height doubles.  opts NULL: no range limit, bilinear, white. */
+int icelk_ortho_begin_host(const icelk_ortho_raster_t* raster, const icelk_ortho_opts_t* opts_or_null, uint8_t* rgb, int rgb_stride,
+                           uint8_t* cover, int cover_stride, double* best);
+int icelk_ortho_add_host(const icelk_ortho_raster_t* raster, const icelk_ortho_opts_t* opts_or_null, const icelk_camera_t* cam, int index,
+                         const uint8_t* img, int sw, int sh, int channels, int stride, uint8_t* rgb, int rgb_stride, uint8_t* cover,
+                         int cover_stride, double* best);
+/* The same on the device.  icelk_ortho_begin starts a mosaic in the picture writer's R G B (k_ortho_fill); it refuses,
+ * before anything is allocated, what the PNG writer refuses for a width x height picture (sides 1 .. 16384, height *
+ * (1 + 3 width) <= 2^28: the stricter upper limits of the two formats; the JPEG writer's lower limit, width >= 3, is
+ * icelk_ortho_write's to refuse for a JPEG alone, so that a narrow raster can still be read back or written as a PNG),
+ * res <= 0, non-finite numbers and a sampling other than 0 and 1: ICELK_EARG.  The add calls run k_ortho_add on the
+ * handle's compute stream and wait for it; ICELK_ESTATE before a begin, ICELK_EARG for an index outside 0 .. 254, a null
+ * pointer or a non-finite camera.
+ *   _add_pixels     host pixels up (channels 1 or 3, stride >= sw * channels, else ICELK_EARG)
+ *   _add_jpeg_file  a JPEG file given as bytes: decoded on the device as icelk_jpeg_decode_rgb_file does (the same files,
+ *                   the same error codes, the host's Huffman decoder inside the call where the device's gives up); a gray
+ *                   file is sampled from its luma plane
+ *   _add_slot       level 0 of the frame `slot` holds (ICELK_ESTATE when it holds none)
+ * icelk_ortho_write: the mosaic through the picture writer (format 0: JPEG at `quality`, 1: PNG), so icelk_picture_frame
+ * makes a movie frame of it.  rgb_or_null / cover_or_null receive the R G B (rgb_stride >= 3 width) and the cover plane
+ * (cover_stride >= width).  ICELK_ECAP: `file` is too small (or NULL), *len says what the file takes, and the call is
+ * simply repeated; the mosaic stays as it is and further cameras can be added after a write.  The call waits for the device. */
+int icelk_ortho_begin(icelk_t* h, const icelk_ortho_raster_t* raster, const icelk_ortho_opts_t* opts_or_null);
+int icelk_ortho_add_pixels(icelk_t* h, const icelk_camera_t* cam, int index, const uint8_t* img, int sw, int sh, int channels, int stride);
+int icelk_ortho_add_jpeg_file(icelk_t* h, const icelk_camera_t* cam, int index, const uint8_t* data, uint64_t len);
+int icelk_ortho_add_slot(icelk_t* h, const icelk_camera_t* cam, int index, int slot);
+int icelk_ortho_write(icelk_t* h, int format, int quality, uint8_t* rgb_or_null, int rgb_stride, uint8_t* cover_or_null, int cover_stride,
+                      uint8_t* file, uint64_t capacity, uint64_t* len);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
