@@ -33,6 +33,8 @@ from .png import encode_png_host, png_bound, png_filter_host  # noqa: F401
 from .movie import MovieWriter, frame_host, movie_size, read_avi, resize_host  # noqa: F401
 from .orthophoto import (ortho_coords_host, ortho_movie_name, ortho_raster, orthophoto, orthophoto_host, orthophoto_sequence,  # noqa: F401
                          read_world_file, world_file)
+from .stabilize import (STAB_DEGENERATE, STAB_LOST, STAB_NOT_CONVERGED, STAB_TOO_FEW, anchor_flags, stabilize_tracks,  # noqa: F401
+                        stabilize_tracks_host)
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

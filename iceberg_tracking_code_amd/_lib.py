@@ -129,6 +129,18 @@ ortho_raster_p = C.POINTER(OrthoRaster)
 ortho_opts_p = C.POINTER(OrthoOpts)
 ORTHO_MAX_INDEX = 254
 
+
+
+class StabParams(C.Structure):
+    """icelk_stab_params_t"""
+    _fields_ = [("model", C.c_int), ("rounds", C.c_int), ("min_anchors", C.c_int), ("reserved", C.c_int), ("threshold", C.c_double),
+                ("start_gate", C.c_double), ("min_spread", C.c_double)]
+
+
+stab_params_p = C.POINTER(StabParams)
+STAB_TOO_FEW, STAB_LOST, STAB_DEGENERATE, STAB_NOT_CONVERGED = 1, 2, 4, 8
+STAB_MAX_VERTICES = 17
+
 JPEG_CROP_ROUTES = ("device", "host-huffman", "over-budget")   # ICELK_JPEG_CROP_*
 JPEG_TABLE_BYTES = 11328
 JPEG_FALLBACK_NONE, JPEG_FALLBACK_BOUND, JPEG_FALLBACK_STREAM, JPEG_FALLBACK_SIZE = 0, 1, 2, 3
@@ -224,6 +236,12 @@ SIGNATURES = {
     "icelk_ortho_add_jpeg_file": (C.c_int, [handle_p, vp, C.c_int, vp, C.c_uint64]),
     "icelk_ortho_add_slot": (C.c_int, [handle_p, vp, C.c_int, C.c_int]),
     "icelk_ortho_write": (C.c_int, [handle_p, C.c_int, C.c_int, u8p, C.c_int, u8p, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "icelk_stab_tracks_host": (C.c_int, [f32p, u8p, C.c_int, C.c_int, stab_params_p, f32p, f64p, i32p, f64p, i32p, i32p, i32p]),
+    "icelk_stab_anchor_flags_host": (C.c_int, [f32p, C.c_int, C.c_int, u8p, C.c_int, C.c_int, C.c_int, u8p]),
+    "icelk_stab_tracks": (C.c_int, [handle_p, f32p, u8p, C.c_int, C.c_int, stab_params_p, f32p, f64p, i32p, f64p, i32p, i32p, i32p]),
+    "icelk_stab_set_anchor_mask": (C.c_int, [handle_p, u8p, C.c_int, C.c_int, C.c_int]),
+    "icelk_seg_stab_read": (C.c_int, [handle_p, C.c_int, stab_params_p, f32p, f32p, u8p, C.c_int, C.c_int, i32p, i32p, f64p, i32p, f64p,
+                                      i32p, i32p, i32p]),
     "icelk_set_gray_device":(C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

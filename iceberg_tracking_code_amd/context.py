@@ -13,6 +13,7 @@ from ._lib import check, f32p, u8p
 from .plot import PLOT_QUALITY, PLOT_WIDTH, _stamp_arg, _tracks3, plot_size
 from .velocity_map import _resident_args, map_descriptor, map_inset_array
 from .orthophoto import FORMATS as ORTHO_FORMATS, _source_array, _source_bytes, opts_struct, raster_struct
+from . import stabilize as _stab
 from .jpeg import (UnsupportedJpeg, _comment_args, _encode_call, _rgb3, _stats_dict, describe_jpeg, resave_coefficients,
                    resave_quality, thumbnail_host, thumbnail_size)
 
@@ -694,6 +695,18 @@ class Context:
             self._ck(fn(self._h, _f32(tracks), _f32(quality), n.value, nv.value, C.byref(n),
                                               C.byref(nv)))
         return tracks, quality
+
+    # -- camera shake fitted to land anchors (stabilize.py) ---------------------
+    def stab_set_anchor_mask(self, anchor_mask):
+        """The anchor mask of `seg_stabilize` (non-zero = static ground): uploaded once, resident until replaced or released
+        (None).  icelk_stab_set_anchor_mask."""
+        _stab.set_anchor_mask(self, anchor_mask)
+
+    def seg_stabilize(self, closed=False, **params):
+        """`seg_read` with the stabilisation in between (icelk_seg_stab_read): the segment's rows are flagged from the
+        resident anchor mask, the camera's motion is fitted to the anchors and every row is corrected, on the device.
+        Returns the dict of `stabilize.stabilize_tracks` plus `trackquality`.  IcelkError (ICELK_ESTATE) without a mask."""
+        return _stab.seg_stabilize(self, closed, **params)
 
     # -- the picture of a segment (s1:397-434) --------------------------------------------------
     def _plot_call(self, slot, width, want_rgb, call, what):

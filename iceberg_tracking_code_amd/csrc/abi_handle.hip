@@ -19,6 +19,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "resize_rows", "resize_cols",
     "grid_segments", "grid_std", "grid_select",
     "ortho_fill", "ortho_add",
+    "stab_flags", "stab_compact", "stab_median", "stab_rounds", "stab_apply",
     "boxes_assign", "boxes_day_assign", "grid_day_assign",
 };
 
@@ -178,6 +179,7 @@ static void destroy_ctx(Ctx* c)
     plot_destroy(c);
     map_destroy(c);
     ortho_destroy(c);
+    stab_destroy(c);
     picture_destroy(c);
     png_destroy(c);
     movie_destroy(c);

@@ -562,6 +562,19 @@ int icelk::seg_gather_packed(Ctx* c, bool closed, int* out_n, int* out_vertices)
     return check_launch(c, "seg_gather");
 }
 
+// The same without the wait: the rows are counted on the device (*dev_count, written on the compute stream), *out_upper
+// bounds them.  What a consumer that needs no host look in between starts from (abi_stab.hip).
+int icelk::seg_gather_counted(Ctx* c, bool closed, int* dev_count, int* out_upper, int* out_vertices)
+{
+    int set = 0;
+    if (int rc = seg_pick(c, closed, &set)) return rc;
+    Ctx::SegBuf& S = c->sb[set];
+    *out_upper = S.upper;
+    *out_vertices = S.vert;
+    launch_seg_gather(c->stream, S.alive, S.upper, S.tracks, S.quality, S.vert, kMaxVert, c->d_out_tracks, c->d_out_quality, dev_count);
+    return check_launch(c, "seg_gather");
+}
+
 extern "C" {
 
 int icelk_seg_read(icelk_t* h, float* tracks, float* quality, int cap, int max_vertices, int* out_n, int* out_vertices)

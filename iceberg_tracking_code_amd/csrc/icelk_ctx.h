@@ -265,6 +265,20 @@ struct Ctx {
         icelk_ortho_raster_t raster{};
         icelk_ortho_opts_t opts{};
     } ortho;
+    // ---- abi_stab.hip: the anchor mask (resident until released) and the scratch of a stabilisation, allocated at first use
+    // for max_pts rows; keys and w are sized by the vertices seen so far
+    struct Stab {
+        uint8_t* d_mask = nullptr;      // mask_w x mask_h bytes, rows mask_w apart
+        int mask_w = 0, mask_h = 0;
+        float* d_tracks = nullptr;      // the caller's table (icelk_stab_tracks)
+        uint8_t *d_flags = nullptr, *d_anchor = nullptr, *d_w = nullptr;
+        int* d_idx = nullptr;           // max_pts row numbers
+        unsigned long long* d_keys = nullptr;
+        double* d_med = nullptr;        // 2 (kMaxVert - 1)
+        StabOut* d_out = nullptr;       // the per-vertex results and the counts
+        size_t tracks_cap = 0, keys_cap = 0, w_cap = 0;
+        bool ready = false;
+    } stab;
     unsigned long long picture_draws = 0;   // picture_grow calls: every picture drawn into picture.d_rgb makes one first
 
     // ---- abi_lk.hip: point buffers of the plain LK entry points (the segment tracker's diagnostic arrays too)
@@ -701,6 +715,8 @@ int picture_write(Ctx* c, hipStream_t st, const PictureFile& F, uint8_t* rgb_or_
 void movie_destroy(Ctx* c);
 // abi_ortho.hip
 void ortho_destroy(Ctx* c);
+// abi_stab.hip
+void stab_destroy(Ctx* c);
 // abi_lk.hip
 int make_lk_params(Ctx* c, int w, int h, int win_w, int win_h, int max_level, int crit_type, int max_count,
                    double epsilon, int flags, double min_eig_thr, float fb_thr, LKParams* P);
@@ -725,6 +741,7 @@ int detect_counts_arrived(Ctx* c, bool* arrived);
 int flush_deferred(Ctx* c);
 int flush_deferred_slot(Ctx* c, int slot);
 int seg_gather_packed(Ctx* c, bool closed, int* out_n, int* out_vertices);
+int seg_gather_counted(Ctx* c, bool closed, int* dev_count, int* out_upper, int* out_vertices);
 // abi_post.hip
 int check_projection_args(Ctx* c, const icelk_camera_t* cam, const icelk_utm_filter_t* filt);
 int project_core(Ctx* c, const float* d_tracks_in, int n, int nv, const icelk_camera_t* cam, const icelk_utm_filter_t* filt,

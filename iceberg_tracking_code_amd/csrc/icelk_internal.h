@@ -14,6 +14,7 @@
 #include "thumb_raster.h"
 #include "resize.h"
 #include "ortho.h"
+#include "stab.h"
 
 namespace icelk {
 
@@ -102,6 +103,11 @@ enum KernelId {
     // (new entries go in front of the three box entries, which tests/test_transect_host.py holds to be the table's last)
     K_ORTHO_FILL,              // the orthophoto (k_ortho.hip): a mosaic begun -- fill colour, cover 0, best +inf
     K_ORTHO_ADD,               // ... a camera's photograph gathered into the raster
+    K_STAB_FLAGS,              // camera shake (k_stab.hip): flags and anchors of every row
+    K_STAB_COMPACT,            // ... the anchors' row numbers, in row order
+    K_STAB_MEDIAN,             // ... the start shift of every vertex
+    K_STAB_ROUNDS,             // ... the robust fit, one workgroup per vertex
+    K_STAB_APPLY,              // ... every row mapped back through its vertex's fit
     K_BOXES_ASSIGN,            // transect / mooring boxes (k_grid.hip): every point against every box, one window
     K_BOXES_DAY_ASSIGN,        // ... a whole day of windows
     K_GRID_DAY_ASSIGN,         // the day gridder's assign kernel, for comparison with the one above
@@ -305,6 +311,31 @@ void launch_map_resolve(hipStream_t s, const map::Scene* d_scene, int Wo, int Ho
 // Wt x Ht thumbnail (R G B, dst_pitch bytes per row); ncomp 1 or 3.  I.px: device memory; rgb: the map's R G B, 3 Wo bytes per row
 void launch_jpeg_thumb(hipStream_t s, const JpegOutArgs& A, int ncomp, int Wt, int Ht);
 void launch_map_inset(hipStream_t s, const thumb::Inset& I, int Wo, int Ho, uint8_t* rgb);
+
+// k_stab.hip: camera shake fitted to land anchors (the rules are stab.h's; the bounds are stated at the head of k_stab.hip).
+// The five kernels of one stabilisation, launched in this order on one stream; K_STAB_FLAGS + step is the step's profiling id
+enum StabStep { STAB_FLAGS, STAB_COMPACT, STAB_MEDIAN, STAB_ROUNDS, STAB_APPLY, STAB_STEPS };
+struct StabOut {               // what one copy brings back
+    stab::VertexResult res[stab::kMaxVert - 1];
+    int n_a, n;                // anchors; rows of a gathered segment
+};
+struct StabArgs {
+    float* tracks;             // (n, V, 2), corrected in place
+    int n, V;                  // n: the rows, or their upper bound when n_ptr says how many there are
+    const int* n_ptr;          // NULL, or the device's count of the rows (<= n)
+    const uint8_t* in_flags;   // n bytes, or NULL: the flags come from the mask
+    const uint8_t* mask;       // mask_w x mask_h bytes, rows mask_w apart
+    int mask_w, mask_h;
+    uint8_t *flags, *anchor;   // n bytes each (flags may be in_flags)
+    int *idx, *n_a;
+    unsigned long long* keys;  // 2 (V - 1) stretches of `stride`
+    uint8_t* w;                // V - 1 stretches of `stride`
+    size_t stride;             // >= n
+    double* med;               // 2 (V - 1)
+    stab::VertexResult* res;   // V - 1
+    icelk_stab_params_t P;
+};
+void launch_stab_step(hipStream_t s, const StabArgs& A, int step);
 
 // k_ortho.hip: the orthophoto (the arithmetic is ortho.h).  rgb: rows 3 R.width bytes apart, cover: R.width bytes, best:
 // R.width doubles, all R.height rows, device memory; S.px device memory

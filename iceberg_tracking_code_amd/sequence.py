@@ -74,7 +74,7 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                          mask_polygon=None, feature_params=None, lk_params=None, decode_threads=4, decode_ahead=6,
                          gray_variant=4, device=0, on_segment=None, save=True, decoder="pil", huffman="host", pipeline=False,
                          n_slots=PIPELINE_SLOTS, resave=None, save_crops=None, plots=None, plot_width=PLOT_WIDTH,
-                         plot_quality=PLOT_QUALITY, resave_ahead=False, movie=None):
+                         plot_quality=PLOT_QUALITY, resave_ahead=False, movie=None, anchor_mask=None, stabilize=None):
     """Track one day's photos.  Returns [(npz path, tracks (n, T+1, 2) f32, trackquality (n, T) f32)] of the
     segments that pass the time-gap rule, in order.
 
@@ -125,6 +125,19 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                    `plots`; a path: that file; a `MovieWriter`: frames are added to it and it is left open.  Without a
                    picture no file is written.  The pictures, the returned list and the .npz files do not change.  None:
                    nothing of it runs
+    anchor_mask, stabilize   the opt-in stabilising stage (stabilize.py): `anchor_mask` is an H x W array of
+                   the cropped frame, non-zero = static ground; `stabilize` is True or a dict of `stabilize_tracks`'
+                   keywords and needs `anchor_mask`.  The camera's motion since a segment's first frame is fitted to the
+                   tracks that start under the anchor mask, and every track is mapped back through it on the device
+                   (`SegmentTracker(anchor_mask=, stabilize=)`).  `tracks` / `trackquality` are then saved, handed to
+                   on_segment and returned WITHOUT the anchor rows, in the coordinates of the segment's first frame, so
+                   that land points never reach s2; the file also holds `anchor_tracks`, `anchor_trackquality` (the anchor
+                   rows, corrected like the rest) and, per vertex after the first, `camera_motion` (a, b, tx, ty),
+                   `camera_inliers`, `camera_rms` and `camera_status`.  With every decoder / pipeline / resave / plots
+                   combination; the segment picture keeps drawing the raw tracks, anchors included.  A detector mask becomes
+                   mask OR anchor mask, and the detector's quality threshold is relative to the maximum over the joined
+                   mask: the water corners can therefore differ from a run without anchors.  None: nothing of it runs
+                   or is allocated, and every file is what it was
     """
     if decoder not in ("pil", "device"):
         raise ValueError('decoder must be "pil" or "device"')
@@ -178,7 +191,8 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                 # a fresh loop state per start offset (the reference carries the last frame of the previous pass
                 # into the first step of the next one; nothing is saved from that pair, s1:362-363)
                 trk = SegmentTracker(w, h, track_len, feature_params=fp, lk_params=lk, mask=mask,
-                                     mask_polygon=mask_polygon, device=device, n_slots=int(n_slots) if pipeline else 3)
+                                     mask_polygon=mask_polygon, device=device, n_slots=int(n_slots) if pipeline else 3,
+                                     anchor_mask=anchor_mask, stabilize=stabilize)
                 pending = [pool.submit(load, p) for p in names[:decode_ahead]]
                 fed = 0                                   # pipeline=True: frames handed to the tracker's prefetch queue
                 ahead_kw = {}                             # ... and the options each of those in flight was handed with
@@ -238,8 +252,15 @@ def track_image_sequence(imagelist, target_dir, track_len, track_len_sec, startl
                     if not segment_time_ok(seg_names, track_len_sec):        # s1:364-390
                         continue
                     npz = os.path.join(target_dir, npz_name(os.path.basename(seg_names[0]), track_len, track_len_sec))
+                    more = {}
+                    if trk.stabilize is not None:
+                        st = trk.last_stabilization
+                        land = st["anchors"]
+                        more = dict(anchor_tracks=tracks[land], anchor_trackquality=quality[land], camera_motion=st["motion"],
+                                    camera_inliers=st["inliers"], camera_rms=st["rms"], camera_status=st["status"])
+                        tracks, quality = tracks[~land], quality[~land]
                     if save:
-                        save_tracks(npz, tracks, quality)
+                        save_tracks(npz, tracks, quality, **more)
                     if plots is not None:
                         with open(plot_name(plots, seg_names[-1], track_len, track_len_sec), "wb") as f:
                             f.write(trk.plot_closed(plot_width, plot_stamp(seg_names[-1], track_len, track_len_sec), plot_quality))

@@ -40,9 +40,10 @@ def segment_time_ok(names, track_len_sec):
     return True
 
 
-def save_tracks(npzname, tracks, trackquality):
-    """np.savez(npzname, tracks=tracks, trackquality=trackquality) (s1:395)."""
-    np.savez(npzname, tracks=tracks, trackquality=trackquality)
+def save_tracks(npzname, tracks, trackquality, **more):
+    """np.savez(npzname, tracks=tracks, trackquality=trackquality) (s1:395).  `more`: further arrays of the same file (the
+    stabilising stage's: sequence.track_image_sequence)."""
+    np.savez(npzname, tracks=tracks, trackquality=trackquality, **more)
 
 
 class _Ahead:
@@ -64,11 +65,22 @@ class SegmentTracker:
     feature_params are cv2.goodFeaturesToTrack's: maxCorners, qualityLevel, minDistance, blockSize and, optional,
     useHarrisDetector (default False: Shi-Tomasi) and k (default 0.04; read with the Harris detector only).  They go with
     every detection the tracker starts or prepares ahead.
+
+    anchor_mask, stabilize: the opt-in stabilising stage (stabilize.py).  `anchor_mask` is an H x W array,
+    non-zero = static ground; `stabilize` is True for the default parameters or a dict of `stabilize_tracks`' keywords, and
+    needs `anchor_mask`.  The tracks that start under the anchor mask are the anchors: the camera's motion since the segment's
+    first frame is fitted to them and every track is mapped back through it, so the segment a push returns -- the same
+    3-tuple, anchors included, all rows corrected -- is in the coordinates of its first frame (`Context.seg_stabilize` in
+    place of `seg_read`); `last_stabilization` holds the rest of that call's dict (`anchors`, `motion`, `inliers`, `rms`,
+    `status`, `rounds_used`, `n_anchors`).  Where a detector mask is in use it becomes mask OR anchor mask, so that corners
+    are found on the anchors' ground (a `mask_polygon` is rasterised, downloaded once, joined on the host and set again).
+    The detector's quality threshold is relative to the maximum response over the joined mask: the water corners can
+    therefore differ from a run without anchors.  Without `stabilize` nothing of this runs or is allocated.
     """
 
     def __init__(self, width, height, track_len, feature_params=None, lk_params=None, mask=None, max_pts=1 << 18,
                  device=0, fb_threshold=REF_FB_THRESHOLD, ctx=None, n_slots=3, lookahead=True, mask_polygon=None,
-                 pair_launch=True):
+                 pair_launch=True, anchor_mask=None, stabilize=None):
         self.track_len = int(track_len)
         if self.track_len < 1 or self.track_len > 16:
             raise ValueError("track_len must be in 1..16")
@@ -76,6 +88,7 @@ class SegmentTracker:
         self.lk = dict(REF_LK_PARAMS if lk_params is None else lk_params)
         self.fb_threshold = float(fb_threshold)
         self.w, self.h = width, height
+        self.stabilize, self.last_stabilization = self._stabilize_arg(stabilize, anchor_mask, width, height), None
         self.ctx = ctx if ctx is not None else Context(width, height, n_slots=n_slots, max_pts=max_pts, device=device)
         self.n_slots = self.ctx.n_slots
         self.ctx.seg_track_len_hint(track_len)    # the last pair of a segment leaves no templates behind
@@ -84,8 +97,12 @@ class SegmentTracker:
             # (maskpoly, cropleft, croptop): the mask of s1:285-291 rasterised on the device (camtools.py:184-211)
             poly, crop_left, crop_top = mask_polygon
             self.ctx.set_mask_polygon(poly, crop_left, crop_top, width, height)
+            if self.stabilize is not None:
+                self.ctx.set_mask(self._joined(self.ctx.download_mask(), anchor_mask))
         elif mask is not None:
-            self.ctx.set_mask(mask)
+            self.ctx.set_mask(mask if self.stabilize is None else self._joined(mask, anchor_mask))
+        if self.stabilize is not None:
+            self.ctx.stab_set_anchor_mask(anchor_mask)
         self.counter = 0          # frames consumed
         self.cur = -1             # slot of the newest frame
         self.seg_first = 0
@@ -111,6 +128,38 @@ class SegmentTracker:
         self._reset_ahead()
         self.pairs_launched = 0   # frame pairs handed to the tracker kernels so far (a joint launch carries two)
         self._closed_now = False  # the latest step closed a segment: `plot_closed` may draw it on that step's frame
+
+    @staticmethod
+    def _stabilize_arg(stabilize, anchor_mask, width, height):
+        """The stabilising stage's parameters as a dict, None when it is off.  Refused before a handle is made."""
+        if stabilize is None or stabilize is False:
+            if anchor_mask is not None:
+                raise ValueError("anchor_mask is read by the stabilising stage alone: pass stabilize=True or its parameters")
+            return None
+        if anchor_mask is None:
+            raise ValueError("stabilize needs anchor_mask")
+        if np.shape(anchor_mask) != (height, width):
+            raise ValueError("anchor_mask must be %d x %d like the frames, not %r" % (height, width, np.shape(anchor_mask)))
+        from .stabilize import params_struct
+        params = {} if stabilize is True else dict(stabilize)
+        params_struct(**params)                   # unknown keywords and values no struct can hold raise here
+        return params
+
+    @staticmethod
+    def _joined(mask, anchor_mask):
+        """The detector's mask with the anchors' ground added: 255 where either is non-zero."""
+        if np.shape(mask) != np.shape(anchor_mask):
+            raise ValueError("mask and anchor_mask differ in size")
+        return np.where((np.asarray(mask) != 0) | (np.asarray(anchor_mask) != 0), 255, 0).astype(np.uint8)
+
+    def _read_segment(self):
+        """What a push returns of the finished (still current) segment: read as it is, or through the stabilising stage."""
+        if self.stabilize is None:
+            return self.ctx.seg_read()
+        r = self.ctx.seg_stabilize(**self.stabilize)
+        tracks, quality = r.pop("tracks"), r.pop("trackquality")
+        self.last_stabilization = r
+        return tracks, quality
 
     def _reset_ahead(self):
         """Nothing is under way for the frames after `counter - 1`."""
@@ -390,7 +439,7 @@ class SegmentTracker:
         for the push to return if the caller waits); then the switch, or else the end of frame c's detection, the oldest."""
         if c > 0 and self.on_close is not None:
             self.on_close(self.seg_first, False)
-        out = (self.seg_first, *self.ctx.seg_read()) if c > 0 and wait else None
+        out = (self.seg_first, *self._read_segment()) if c > 0 and wait else None
         if staged_now:
             self.ctx.seg_switch()
             self._enter_segment(c, self._staged[1])

@@ -1059,6 +1059,67 @@ int icelk_ortho_add_slot(icelk_t* h, const icelk_camera_t* cam, int index, int s
 int icelk_ortho_write(icelk_t* h, int format, int quality, uint8_t* rgb_or_null, int rgb_stride, uint8_t* cover_or_null, int cover_stride,
                       uint8_t* file, uint64_t capacity, uint64_t* len);
 
+/* ---- camera shake fitted to land anchors (opt-in) ---------------------------------
+ * A stage between tracking and saving.  The tracks of a segment that start on static ground (inside an anchor mask) are the
+ * anchors; for every vertex k >= 1 the motion of the picture from the segment's first frame to frame k is fitted to them, a
+ * robust translation or similarity, and every track's vertex k is mapped back through the fit: the table comes out in the
+ * coordinates of the segment's first frame.  The rules are csrc/stab.h, which the kernels (csrc/k_stab.hip), the host
+ * statement below and tests/stab_restatement.py compute bit for bit alike:
+ *   anchors  rows with flags != 0 whose 2 V coordinates are all finite, in row order; x, y = vertex 0, X, Y = vertex k
+ *   start    (a, b, tx, ty) = (1, 0, median(X - x), median(Y - y)), gate g = max(threshold, start_gate)
+ *   inlier   ex = X - ((a x - b y) + tx), ey = Y - ((b x + a y) + ty), ex ex + ey ey <= g g
+ *   rounds   at most `rounds`: fewer than min_anchors inliers: LOST; fit to the inliers (numpy-ordered sums); g halves down to
+ *            the threshold; converged when the inlier set and the gate both stay
+ *   fit      translation: the mean shift of the inliers.  Similarity: least squares about the centroids; when the inliers'
+ *            spread sum((x - mx)^2 + (y - my)^2) is not >= n_in min_spread^2: the translation fit and DEGENERATE
+ *   apply    x' = (a (X - tx) + b (Y - ty)) / (a a + b b), y' = (a (Y - ty) - b (X - tx)) / (a a + b b), to every row; vertex
+ *            0 and the vertices of a TOO_FEW or LOST fit are copied bit for bit; a NaN result is stored as 0x7fc00000
+ * threshold is the reference's forward-backward bound (s1:333); start_gate, rounds, min_anchors and min_spread are policy
+ * defaults, not measurements.  Results per vertex k = 1 .. V - 1 (entry k - 1): motion (a, b, tx, ty), inliers, rms of the
+ * inliers (NaN without a model), status bits, rounds_used (fits made). */
+#define ICELK_STAB_TOO_FEW 1
+#define ICELK_STAB_LOST 2
+#define ICELK_STAB_DEGENERATE 4
+#define ICELK_STAB_NOT_CONVERGED 8
+typedef struct icelk_stab_params {
+    int model;                 /* 0 translation, 1 similarity */
+    int rounds;                /* 1 .. 16 */
+    int min_anchors;           /* >= 2 */
+    int reserved;
+    double threshold;          /* inlier distance, px, > 0 */
+    double start_gate;         /* first gate, px */
+    double min_spread;         /* px, >= 0 */
+} icelk_stab_params_t;
+/* Host only, no handle, no GPU, re-entrant: the statement the kernels are tested against.  tracks: (n, n_vertices, 2) with
+ * 2 <= n_vertices <= 17, flags: n bytes, out_tracks: as tracks (may be tracks itself); motion 4 (V - 1) doubles, the other
+ * four V - 1 entries; *n_anchors: the anchors found.  params NULL: translation, 1.0, 8.0, 8 rounds, 10 anchors, 64.0.
+ * ICELK_EARG: a null pointer, n < 0, n_vertices outside 2 .. 17 or a parameter outside its range. */
+int icelk_stab_tracks_host(const float* tracks, const uint8_t* flags, int n, int n_vertices, const icelk_stab_params_t* params_or_null,
+                           float* out_tracks, double* motion, int32_t* inliers, double* rms, int32_t* status, int32_t* rounds_used,
+                           int* n_anchors);
+/* Host only: flags[i] = mask[iy, ix] != 0 with ix = (int)floor(x0 + 0.5), iy likewise (doubles of row i's vertex 0), 0
+ * outside the w x h_ mask (rows `stride` >= w bytes apart). */
+int icelk_stab_anchor_flags_host(const float* tracks, int n, int n_vertices, const uint8_t* mask, int w, int h_, int stride, uint8_t* flags);
+/* The same through the device, a host table up and down like icelk_project_tracks: k_stab_flags, k_stab_compact,
+ * k_stab_median, k_stab_rounds, k_stab_apply on the handle's compute stream, one wait at the end.  ICELK_ECAP: more rows
+ * than the handle's max_pts.  Bad parameters are ICELK_EARG before anything is enqueued. */
+int icelk_stab_tracks(icelk_t* h, const float* tracks, const uint8_t* flags, int n, int n_vertices, const icelk_stab_params_t* params_or_null,
+                      float* out_tracks, double* motion, int32_t* inliers, double* rms, int32_t* status, int32_t* rounds_used,
+                      int* n_anchors);
+/* The anchor mask of icelk_seg_stab_read: w x h_ bytes (rows `stride` apart), non-zero = static ground; uploaded once and
+ * resident until replaced, released (host_mask NULL) or the handle is destroyed.  ICELK_EARG: a mask larger than the
+ * handle's frames or a stride below w. */
+int icelk_stab_set_anchor_mask(icelk_t* h, const uint8_t* host_mask, int w, int h_, int stride);
+/* icelk_seg_read (closed != 0: icelk_seg_read_closed) with the stabilisation in between: the segment's surviving tracks are
+ * gathered, flagged from the resident anchor mask, fitted and corrected on the device, and come back with their quality,
+ * their flags (n bytes, 1 = under the mask) and the per-vertex results.  Sizing as icelk_seg_read: with tracks NULL only
+ * *out_n and *out_vertices are set.  The call with buffers waits for the device once: the rows are counted there, min(cap,
+ * corners of the segment) rows are copied (rows behind *out_n hold no result) and a count above cap is ICELK_ECAP after the
+ * fact.  ICELK_ESTATE without an anchor mask or before the segment's first pair. */
+int icelk_seg_stab_read(icelk_t* h, int closed, const icelk_stab_params_t* params_or_null, float* tracks, float* quality, uint8_t* flags,
+                        int cap, int max_vertices, int* out_n, int* out_vertices, double* motion, int32_t* inliers, double* rms,
+                        int32_t* status, int32_t* rounds_used, int* n_anchors);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
