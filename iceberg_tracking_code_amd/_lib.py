@@ -141,7 +141,27 @@ stab_params_p = C.POINTER(StabParams)
 STAB_TOO_FEW, STAB_LOST, STAB_DEGENERATE, STAB_NOT_CONVERGED = 1, 2, 4, 8
 STAB_MAX_VERTICES = 17
 
-JPEG_CROP_ROUTES = ("device", "host-huffman", "over-budget")   # ICELK_JPEG_CROP_*
+class ValidateLattice(C.Structure):
+    """icelk_validate_lattice_t"""
+    _fields_ = [("left", C.c_double), ("top", C.c_double), ("side", C.c_double), ("cols", C.c_int), ("rows", C.c_int)]
+
+
+class ValidateParams(C.Structure):
+    """icelk_validate_params_t"""
+    _fields_ = [("threshold", C.c_double), ("eps", C.c_double), ("min_neighbours", C.c_int), ("reserved", C.c_int)]
+
+
+class ValidateCells(C.Structure):
+    """icelk_validate_cells_t: five host arrays per (group, cell)"""
+    _fields_ = [("pool_n", i32p), ("med_u", f64p), ("med_v", f64p), ("mad_u", f64p), ("mad_v", f64p)]
+
+
+validate_lattice_p = C.POINTER(ValidateLattice)
+validate_params_p = C.POINTER(ValidateParams)
+validate_cells_p = C.POINTER(ValidateCells)
+VALIDATE_KEPT, VALIDATE_REJECTED, VALIDATE_FEW_NEIGHBOURS, VALIDATE_NOT_JUDGED = 0, 1, 2, 3
+
+JPEG_CROP_ROUTES =("device", "host-huffman", "over-budget")   # ICELK_JPEG_CROP_*
 JPEG_TABLE_BYTES = 11328
 JPEG_FALLBACK_NONE, JPEG_FALLBACK_BOUND, JPEG_FALLBACK_STREAM, JPEG_FALLBACK_SIZE = 0, 1, 2, 3
 jpeg_stats_p = C.POINTER(JpegHuffStats)
@@ -242,6 +262,14 @@ SIGNATURES = {
     "icelk_stab_set_anchor_mask": (C.c_int, [handle_p, u8p, C.c_int, C.c_int, C.c_int]),
     "icelk_seg_stab_read": (C.c_int, [handle_p, C.c_int, stab_params_p, f32p, f32p, u8p, C.c_int, C.c_int, i32p, i32p, f64p, i32p, f64p,
                                       i32p, i32p, i32p]),
+    "icelk_validate": (C.c_int, [handle_p, f64p, f64p, f64p, f64p, C.c_int, i32p, C.c_int, validate_lattice_p, validate_params_p, u8p,
+                                 f64p, validate_cells_p]),
+    "icelk_validate_host": (C.c_int, [f64p, f64p, f64p, f64p, C.c_int, i32p, C.c_int, validate_lattice_p, validate_params_p, u8p, f64p,
+                                      validate_cells_p]),
+    "icelk_grid_bin_windows_validated": (C.c_int, [handle_p, f64p, f64p, f64p, f64p, f64p, C.c_int, i64p, i32p, i32p, i32p,
+                                                   C.c_int, i64p, i64p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                   C.c_double, C.c_int, C.c_int, u8p, i32p, f64p, f64p, f64p, i32p, f64p,
+                                                   f64p, f64p, grid_stats_p, validate_lattice_p, validate_params_p, u8p, i32p]),
     "icelk_set_gray_device":(C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

@@ -19,6 +19,7 @@ static const char* kKernelNames[K_COUNT_] = {
     "resize_rows", "resize_cols",
     "grid_segments", "grid_std", "grid_select",
     "ortho_fill", "ortho_add",
+    "validate_assign", "validate_pools", "validate_judge",
     "stab_flags", "stab_compact", "stab_median", "stab_rounds", "stab_apply",
     "boxes_assign", "boxes_day_assign", "grid_day_assign",
 };

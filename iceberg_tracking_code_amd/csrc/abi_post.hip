@@ -3,6 +3,7 @@
 #include "icelk_ctx.h"
 #include "cube_means.h"
 #include "grid_stats.h"
+#include "validate.h"
 
 namespace icelk {
 
@@ -418,18 +419,21 @@ int icelk_grid_bin_stats(icelk_t* h, const double* x, const double* y, const dou
     return grid_bin(h, x, y, u, v, n, left, top, spacing, cols, rows, cell_on, count, mean_u, mean_v, speed, stats);
 }
 
-// icelk_grid_bin_windows, and with `stats` icelk_grid_bin_windows_stats
+// icelk_grid_bin_windows, with `stats` icelk_grid_bin_windows_stats, with `val` icelk_grid_bin_windows_validated: the
+// normalised median test runs on the uploaded points in front of the gridder, with the day tables' windows as groups, and
+// turns the device copy of t into NaN at every rejected point -- which day_window then finds in no window
 static int grid_bin_windows(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
                             const double* t, int n, const int64_t* file_offset, const int* file_cam, const int* win_f0,
                             const int* win_f1, int nfiles, const int64_t* t_lo, const int64_t* t_hi, int ncam, int nw,
                             double left, double top, double spacing, int cols, int rows, const uint8_t* cell_on,
                             int* count, double* mean_u, double* mean_v, double* speed, int* sel_count, double* t_min,
-                            double* t_max, double* device_ms, const icelk_grid_stats_t* stats)
+                            double* t_max, double* device_ms, const icelk_grid_stats_t* stats, const ValidateDay* val = nullptr)
 {
     if (!h) return ICELK_EARG;
     Ctx* c = C(h);
     HIPCHK(c, hipSetDevice(c->device));
     if (stats && !stats_complete(stats)) FAIL(c, ICELK_EARG, "a member of the statistics struct is null");
+    if (val && (!val->L || !val->rejected || (n > 0 && !val->status))) FAIL(c, ICELK_EARG, "the lattice or an output of the validation is null");
     if (n < 0 || nfiles < 1 || ncam < 1 || nw < 1 || cols <= 0 || rows <= 0 || !(spacing > 0) || !file_offset ||
         !file_cam || !win_f0 || !win_f1 || !t_lo || !t_hi || !cell_on || !count || !mean_u || !mean_v || !speed ||
         !sel_count || !t_min || !t_max || (n > 0 && (!x || !y || !u || !v || !t)))
@@ -441,13 +445,20 @@ static int grid_bin_windows(icelk_t* h, const double* x, const double* y, const 
         FAIL(c, ICELK_ECAP, "grid x windows or point set too large");
     const icelk_day_tables_t T{file_offset, file_cam, win_f0, win_f1, nfiles, t_lo, t_hi, ncam, nw};
     if (int rct = check_day_tables(c, T, n)) return rct;
+    if (val) {
+        const int rcv = validate::check(*val->L, val->P, n, nw);
+        if (rcv == ICELK_ECAP) FAIL(c, rcv, "validation: more than 2^27 points, or windows x cols x rows of the lattice does not fit 31 bits");
+        if (rcv) FAIL(c, rcv, "validation: threshold, eps and side must be positive and finite, min_neighbours, cols and rows at least 1");
+    }
     const int ncells = (int)ncells_ll, nseg = ncells * nw;
     const int key_cap = (int)std::min<long long>(2LL * n + 1024, 0x7fffffffLL);
     clear_day_outputs(nseg, nw * ncam, count, mean_u, mean_v, speed, stats, sel_count, t_min, t_max, device_ms);
+    if (val) std::fill(val->rejected, val->rejected + nw, 0);
     if (n == 0) return ICELK_OK;
     DevBufs B;
     GridDev G;
     DayDev D;
+    ValidateDev V;
     const size_t nn = (size_t)n;
     double* dx = B.get<double>(nn);
     double* dy = B.get<double>(nn);
@@ -460,6 +471,7 @@ static int grid_bin_windows(icelk_t* h, const double* x, const double* y, const 
     if (stats) G.alloc_stats(B);
     const hipStream_t s = c->stream;
     G.alloc_sort(B, s);
+    if (val) V.alloc(B, n, nw, *val->L, val->P, s);
     if (!B.ok()) FAIL(c, ICELK_ENOMEM, "hipMalloc failed");
     G.du = du;
     G.dv = dv;
@@ -470,6 +482,21 @@ static int grid_bin_windows(icelk_t* h, const double* x, const double* y, const 
     HIPCHK(c, copy_n(dt, t, nn, kH2D, s));
     if (int rct = D.upload(c, T, s)) return rct;
     HIPCHK(c, copy_n(d_on, cell_on, (size_t)ncells, kH2D, s));
+    EvPair vtimer[2];
+    if (val) {
+        if (device_ms) {
+            int rct = vtimer[0].create(c);
+            if (!rct) rct = vtimer[1].create(c);
+            if (rct) return rct;
+        }
+        V.A.x = dx, V.A.y = dy, V.A.u = du, V.A.v = dv, V.A.t_kill = dt;
+        auto vassign = [&] {
+            launch_validate_day_assign(s, V.A, dt, D.off, D.fcam, D.wf0, D.wf1, nfiles, D.lo, D.hi, ncam, nw);
+        };
+        if (int rct = validate_run(c, V, vassign, device_ms ? vtimer : nullptr)) return rct;
+        HIPCHK(c, copy_n(val->status, V.A.status, nn, kD2H, s));
+        HIPCHK(c, copy_n(val->rejected, V.A.rejected, (size_t)nw, kD2H, s));
+    }
     // device_ms: assign, then sort + reduce; the key-count read-back between them is not counted
     EvPair timer[2];
     auto assign = [&]() -> int {
@@ -489,7 +516,13 @@ static int grid_bin_windows(icelk_t* h, const double* x, const double* y, const 
     if (rc) return rc;
     rc = D.read_back(c, s, sel_count, t_min, t_max);
     if (rc) return rc;
-    return device_ms ? elapsed_ms(c, timer, device_ms) : ICELK_OK;
+    if (!device_ms) return ICELK_OK;
+    rc = elapsed_ms(c, timer, device_ms);
+    if (rc || !val) return rc;
+    double validation_ms = 0.0;
+    rc = elapsed_ms(c, vtimer, &validation_ms);
+    *device_ms += validation_ms;
+    return rc;
 }
 
 // icelk_boxes_bin (T null) and icelk_boxes_bin_windows: the points against the box list, then grid_core with
@@ -611,6 +644,21 @@ int icelk_grid_bin_windows_stats(icelk_t* h, const double* x, const double* y, c
     return grid_bin_windows(h, x, y, u, v, t, n, file_offset, file_cam, win_f0, win_f1, nfiles, t_lo, t_hi, ncam, nw,
                             left, top, spacing, cols, rows, cell_on, count, mean_u, mean_v, speed, sel_count, t_min,
                             t_max, device_ms, stats);
+}
+
+int icelk_grid_bin_windows_validated(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                                     const double* t, int n, const int64_t* file_offset, const int* file_cam,
+                                     const int* win_f0, const int* win_f1, int nfiles, const int64_t* t_lo,
+                                     const int64_t* t_hi, int ncam, int nw, double left, double top, double spacing,
+                                     int cols, int rows, const uint8_t* cell_on, int* count, double* mean_u, double* mean_v,
+                                     double* speed, int* sel_count, double* t_min, double* t_max, double* device_ms,
+                                     const icelk_grid_stats_t* stats_or_null, const icelk_validate_lattice_t* lattice,
+                                     const icelk_validate_params_t* params, uint8_t* status, int32_t* rejected)
+{
+    const ValidateDay val{lattice, params ? *params : validate::default_params(), status, rejected};
+    return grid_bin_windows(h, x, y, u, v, t, n, file_offset, file_cam, win_f0, win_f1, nfiles, t_lo, t_hi, ncam, nw,
+                            left, top, spacing, cols, rows, cell_on, count, mean_u, mean_v, speed, sel_count, t_min,
+                            t_max, device_ms, stats_or_null, &val);
 }
 
 int icelk_boxes_check(const icelk_boxes_t* boxes)

@@ -50,7 +50,10 @@ __device__ __forceinline__ int wg_select_bin(SelectLds* L, int* k, int* below, i
 // of grid_stats.h with each pass's histogram counted by 256 threads in LDS.  Every thread walks the same t it staged,
 // reads the same verdict and so carries the same prefix, rank and count; eight passes and at most one more.  A pass's
 // verdict is written two barriers after the last one was read, and a thread zeroes only the bin it alone has read.
-__device__ __forceinline__ double wg_median(const unsigned long long* __restrict__ sk, int n, SelectLds* L)
+// `sk[t]` is whatever the caller's Keys answers for term t -- an array in global memory (wg_median below), keys staged in
+// LDS or computed on the way (k_validate.hip); it is asked for the same t up to ten times and must answer alike.
+template <typename Keys>
+__device__ __forceinline__ double wg_median_of(const Keys& sk, int n, SelectLds* L)
 {
     int k = median_rank(n), below = 0, in_bin = 0;
     unsigned long long prefix = 0;
@@ -81,6 +84,17 @@ __device__ __forceinline__ double wg_median(const unsigned long long* __restrict
         upper = *s_min;
     }
     return median_of_middle(from_order_key(prefix), from_order_key(upper), n);
+}
+
+// order keys in an array
+struct KeyArray {
+    const unsigned long long* __restrict__ p;
+    __device__ __forceinline__ unsigned long long operator[](int t) const { return p[t]; }
+};
+
+__device__ __forceinline__ double wg_median(const unsigned long long* __restrict__ sk, int n, SelectLds* L)
+{
+    return wg_median_of(KeyArray{sk}, n, L);
 }
 
 }  // namespace icelk

@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <memory>
 #include <mutex>
 
@@ -587,6 +588,29 @@ struct EvPair {
         HIPCHK(c, hipEventCreate(&b));
         return ICELK_OK;
     }
+};
+
+// ---- the normalised median test's device side (abi_validate.hip), shared by icelk_validate and the validated day gridder
+// The working arrays of one pass over n points and ngroups groups: keys, sorted keys, the sort's scratch, status, r2, the
+// per-(group, cell) records, the groups' rejected counts.  The caller sets A.x, A.y, A.u, A.v (and A.group, A.t_kill).
+struct ValidateDev {
+    ValidateArgs A{};
+    unsigned long long* keys_sorted = nullptr;
+    void* sort_tmp = nullptr;
+    size_t sort_tmp_bytes = 0, nseg = 0;
+    int key_bits = 0;
+    void alloc(DevBufs& B, int n, int ngroups, const icelk_validate_lattice_t& L, const icelk_validate_params_t& P, hipStream_t s);
+};
+// Counters zeroed, `assign` (the caller's launch of one of the two assign kernels), the judged count read back -- the one
+// wait --, sort, pools, judge; the results stay on the device.  t, if given: t[0] goes around the assign kernel, t[1] around
+// the rest, as grid_core's.
+int validate_run(Ctx* c, ValidateDev& V, const std::function<void()>& assign, EvPair* t);
+// the lattice, the parameters and the outputs the validated day gridder takes (abi_post.hip)
+struct ValidateDay {
+    const icelk_validate_lattice_t* L;
+    icelk_validate_params_t P;
+    uint8_t* status;
+    int32_t* rejected;
 };
 
 // ---- helpers that cross a stage boundary (each defined in the file named) -------------------------------------------

@@ -103,6 +103,10 @@ enum KernelId {
     // (new entries go in front of the three box entries, which tests/test_transect_host.py holds to be the table's last)
     K_ORTHO_FILL,              // the orthophoto (k_ortho.hip): a mosaic begun -- fill colour, cover 0, best +inf
     K_ORTHO_ADD,               // ... a camera's photograph gathered into the raster
+    // (... and in front of the five stab entries, which tests/test_stab_host.py holds to stand right before those)
+    K_VALIDATE_ASSIGN,         // the normalised median test (k_validate.hip): keys of the judged points (both assign forms)
+    K_VALIDATE_POOLS,         // ... median and MAD of every pool, one workgroup per (group, cell) and component
+    K_VALIDATE_JUDGE,          // ... status and r2 of every keyed point, rejected counts
     K_STAB_FLAGS,              // camera shake (k_stab.hip): flags and anchors of every row
     K_STAB_COMPACT,            // ... the anchors' row numbers, in row order
     K_STAB_MEDIAN,             // ... the start shift of every vertex
@@ -606,6 +610,34 @@ void launch_grid_std(hipStream_t s, const unsigned long long* keys, const int* s
 void launch_grid_select(hipStream_t s, const unsigned long long* keys, const int* seg_begin, const int* seg_count,
                         const double* u, const double* v, int nseg, unsigned long long* scratch, size_t scratch_stride,
                         const icelk_grid_stats_t& out);
+// the normalised median test (k_validate.hip; the rules are validate.h's).  Device pointers throughout: x, y, u, v, status, r2
+// and keys n each; `sorted` the keys in ascending order (the caller's sort; `keys` itself for fewer than two); cells' five
+// arrays ngroups * cols * rows each; rejected ngroups, zeroed by the caller; group NULL: group 0 (the day form takes the
+// window of the day tables instead); t_kill NULL, or the times that become NaN at every rejected point.  `total`: the judged
+// points, what key_count holds after the assign kernel.
+struct ValidateArgs {
+    const double *x, *y, *u, *v;
+    int n;
+    const int32_t* group;
+    int ngroups;
+    icelk_validate_lattice_t L;
+    icelk_validate_params_t P;
+    unsigned long long* keys;
+    const unsigned long long* sorted;
+    int* key_count;
+    uint8_t* status;
+    double* r2;
+    icelk_validate_cells_t cells;
+    int32_t* rejected;
+    double* t_kill;
+};
+void launch_validate_assign(hipStream_t s, const ValidateArgs& A);
+void launch_validate_day_assign(hipStream_t s, const ValidateArgs& A, const double* t, const long long* file_off, const int* file_cam,
+                                const int* win_f0, const int* win_f1, int nfiles, const long long* t_lo, const long long* t_hi, int ncam,
+                                int nw);
+void launch_validate_pools(hipStream_t s, const ValidateArgs& A, int total);
+void launch_validate_judge(hipStream_t s, const ValidateArgs& A, int total);
+int validate_pool_lds_terms();   // the largest pool whose order keys are staged in LDS
 // averages of the velocity cube (k_cube.hip): the cube [window][cell], the periods' windows as CSR offsets + indices
 void launch_cube_temporal(hipStream_t s, const double* u, const double* v, const double* cnt, int ncells,
                           const int* sel_offset, const int* sel_index, int nperiods, double* mean_u, double* mean_v,

@@ -48,6 +48,7 @@ from .context import Context
 from .gridding import STATS_KEYS, CellStats, cell_table, create_grid_across_fjord, pack_cells
 from .jpeg import UnsupportedJpeg, describe_jpeg
 from .movie import open_movie, velocities_movie_name
+from .validate import lattice_struct, params_struct, validate_options, validation_array, validation_lattice
 from .velocity_map import MAP_QUALITY, MAP_WIDTH, map_insets, map_layout, map_name, map_picture, map_strings, map_text, map_view
 
 EPOCH = dt.datetime(1970, 1, 1)
@@ -329,12 +330,14 @@ def window_insets(ctx, photos, names, when, plot_switch, fjord, out_width):
     return out
 
 
-def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, maps=None, stats=False):
+def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, maps=None, stats=False, validate=None):
     """Loads the plan's files, runs the device pass, and packs every window that selected a point.  `timing`: a dict
     that receives the seconds of each stage and the kernels' milliseconds (tools/grid_day_bench.py).  `maps`: None, or
     what the windows' pictures need (utm_to_gridded_utm's plot keywords); the written list then carries each picture's
     name and bytes as a third and fourth entry.  `stats`: every window's arrays also carry gridding.STATS_KEYS, from
-    `icelk_grid_bin_windows_stats`; without it that entry point is not called."""
+    `icelk_grid_bin_windows_stats`; without it that entry point is not called.  `validate`: None, or what
+    validate.validate_options returns: the pass is `icelk_grid_bin_windows_validated`, every window's arrays also carry
+    `rejected` and `validation`, and `timing` receives the per-point `status`."""
     clock = time.perf_counter
     t0 = clock()
     vectors = maps is not None and maps["plot_switch"] == 2
@@ -362,7 +365,13 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
             i64(lo), i64(hi), ncam, nw, left, top, float(grid_size), cols, rows, on.ctypes.data_as(_lib.u8p), i32(cnt),
             f64(mu), f64(mv), f64(sp), i32(sel), f64(tmin), f64(tmax), C.byref(device_ms) if timing is not None else None)
     cs = CellStats(nw * ncells) if stats else None
-    if stats:
+    if validate is not None:
+        lattice = lattice_struct(validation_lattice(fjord, validate["side"]))
+        params = params_struct(validate["threshold"], validate["eps"], validate["min_neighbours"])
+        status, rejected = np.zeros(n, np.uint8), np.zeros(nw, np.int32)
+        ctx._ck(ctx._lib.icelk_grid_bin_windows_validated(*args, C.byref(cs.struct) if stats else None, C.byref(lattice), C.byref(params),
+                                                          status.ctypes.data_as(_lib.u8p), i32(rejected)))
+    elif stats:
         ctx._ck(ctx._lib.icelk_grid_bin_windows_stats(*args, C.byref(cs.struct)))
     else:
         ctx._ck(ctx._lib.icelk_grid_bin_windows(*args))
@@ -387,6 +396,8 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
         r = pack_cells(grid, idx, cnt[s], mu[s], mv[s], sp[s], observation_threshold, stats=cs.window(s) if stats else None)
         r.update(grid_size=grid_size, topleft=topleft, rows=rows, cols=cols)
         arrays = {k: np.asanyarray(r[k]) for k in SAVED_KEYS + (STATS_KEYS if stats else ())}   # what np.savez makes of s3's lists
+        if validate is not None:
+            arrays.update(rejected=np.asanyarray(int(rejected[w])), validation=validation_array(validate))
         name = plan.name(w, [float(a) if k else None for a, k in zip(tmin[w], sel[w])],
                          [float(a) if k else None for a, k in zip(tmax[w], sel[w])])
         if maps is None:
@@ -416,13 +427,15 @@ def _grid_day(ctx, plan, fjord, grid_size, observation_threshold, timing=None, m
     if timing is not None:
         timing.update(points=n, load_s=t1 - t0, device_call_s=t2 - t1, kernels_ms=device_ms.value,
                       pack_s=clock() - t2)
+        if validate is not None:
+            timing.update(status=status, rejected=rejected)
     return written
 
 
 def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts, fjord, day,
                        time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None, plot_switch=1,
                        speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None, plot_format="jpeg",
-                       movie=None, stats=False):
+                       movie=None, stats=False, validate=None):
     """One day of hourly velocity files -> one gridded .npz per time window, as s3_utm_to_gridded_utm.utm_to_gridded_utm
     (s3:222-446) with plot_switch 0.
 
@@ -452,7 +465,17 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
     `stats`: every window file also carries, over its measured cells, u_std, v_std (np.std(ddof=1) of the cell's velocities),
     u_median, v_median, speed_median (np.hypot of the two), u_mad, v_mad (the median absolute deviation) -- numpy's bits,
     selected on the device; every other key is what it is without.  The maps still draw the means.
-    stats=False calls nothing of this."""
+    stats=False calls nothing of this.
+
+    `validate`: None, True (threshold 2.0, eps 0.01 m/s, min_neighbours 8, a lattice side of 2 * grid_size -- policy, not
+    measurements) or a dict of those four: the normalised median test (validate.py) runs on the device
+    between the upload and the gridder, every window's points against the pools of that window, all cameras together.  A
+    rejected vector is in no window: it is neither binned, counted nor part of a window's time range, so a window whose
+    every vector is rejected writes no file.  Every window file carries two more keys, `rejected` (int, the window's
+    count) and `validation` (threshold, eps, min_neighbours, side as float64); everything else is computed from the
+    surviving points.  The all-vectors panel of plot_switch 2 keeps drawing every vector, the rejected ones too.
+    validate=None calls nothing of this, and every file is what it was."""
+    validate = validate_options(validate, grid_size)
     if movie is not None and plots is None:
         raise ValueError("movie needs plots: its frames are the windows' pictures")
     if plots is not None and plot_switch not in (1, 2):
@@ -475,7 +498,7 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
         os.makedirs(maps["dir"], exist_ok=True)
         maps["movie"], film_own = open_movie(movie, maps["dir"], velocities_movie_name(time_window))
     try:
-        written = _grid_day(ctx, plan, fjord, grid_size, observation_threshold, maps=maps, stats=stats)
+        written = _grid_day(ctx, plan, fjord, grid_size, observation_threshold, maps=maps, stats=stats, validate=validate)
     finally:
         if own:
             ctx.close()
@@ -496,9 +519,9 @@ def utm_to_gridded_utm(camnames, source_path_head, source_path_tail, target_path
 def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, target_path, schedule, clock_drifts,
                             fjord, time_window, grid_size, observation_threshold, ctx=None, save=True, plots=None,
                             plot_switch=1, speedthreshold_cbar=0.5, cameras=None, out_width=MAP_WIDTH, quality=MAP_QUALITY, photos=None,
-                            plot_format="jpeg", movie=None, stats=False):
+                            plot_format="jpeg", movie=None, stats=False, validate=None):
     """s3:main's loop over days (without its process pool), on one context: the files of every day, in order.  The plot
-    keywords and `stats` are utm_to_gridded_utm's; `movie` gives ONE movie over all the days' maps, as s3's main makes one."""
+    keywords, `stats` and `validate` are utm_to_gridded_utm's; `movie` gives ONE movie over all the days' maps, as s3's main makes one."""
     if movie is not None and plots is None:
         raise ValueError("movie needs plots: its frames are the windows' pictures")
     own = ctx is None
@@ -516,7 +539,7 @@ def utm_to_gridded_utm_days(days, camnames, source_path_head, source_path_tail, 
                                       ctx=ctx, save=save, plots=plots, plot_switch=plot_switch,
                                       speedthreshold_cbar=speedthreshold_cbar, cameras=cameras, out_width=out_width,
                                       quality=quality, photos=photos, plot_format=plot_format, movie=film,
-                                      stats=stats)
+                                      stats=stats, validate=validate)
         return out
     finally:
         if own:

@@ -87,12 +87,25 @@ def grid_cell_stats_host(a):
     return tuple(np.float64(o.value) for o in out)
 
 
-def bin_velocities(ctx, x, y, u, v, fjord, spacing, observation_threshold, grid=None, stats=False):
+def bin_velocities(ctx, x, y, u, v, fjord, spacing, observation_threshold, grid=None, stats=False, validate=None):
     """The loop of s3:391-421 for one time window.  Returns the dict the reference saves (s3:441-445, without
     `grid_size` / `topleft` / `rows` / `cols`, which the caller has): grid_id, i, j, x, y, u, v, speed, count,
     measured, not_measured.  With `stats` also, as lists over the measured cells, u_std, v_std (np.std(ddof=1) of the
     cell's velocities), u_median, v_median, speed_median (their np.hypot), u_mad, v_mad (median absolute deviation),
-    from `icelk_grid_bin_stats`."""
+    from `icelk_grid_bin_stats`.  `validate`: None, True or a dict (validate.validate_options): the normalised median test
+    (`validate_velocities`, one group, a lattice over the fjord's box) runs first, everything is computed from the
+    surviving points, and the dict also has `rejected` (their number), `validation` (threshold, eps, min_neighbours, side)
+    and `status` (per point).  validate=None calls nothing of it."""
+    if validate is not None and validate is not False:
+        from .validate import validate_options, validate_velocities, validation_array, validation_lattice
+        opt = validate_options(validate, spacing)
+        res = validate_velocities(ctx, x, y, u, v, validation_lattice(fjord, opt["side"]), opt["threshold"], opt["eps"],
+                                  opt["min_neighbours"])
+        keep = res["keep"]
+        out = bin_velocities(ctx, *[np.asarray(q, np.float64).ravel()[keep] for q in (x, y, u, v)], fjord, spacing,
+                             observation_threshold, grid=grid, stats=stats)
+        out.update(rejected=int((~keep).sum()), validation=validation_array(opt), status=res["status"])
+        return out
     if grid is None:
         grid = create_grid_across_fjord(ctx, fjord, spacing)
     rows, cols = grid[4], grid[5]

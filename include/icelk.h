@@ -1120,6 +1120,59 @@ int icelk_seg_stab_read(icelk_t* h, int closed, const icelk_stab_params_t* param
                         int cap, int max_vertices, int* out_n, int* out_vertices, double* motion, int32_t* inliers, double* rms,
                         int32_t* status, int32_t* rounds_used, int* n_anchors);
 
+/* ---- validation of projected velocities: the normalised median test ------------ */
+/* A spatial-coherence check between projection and gridding (Westerweel & Scarano 2005), stated in csrc/validate.h.
+ * Lattice: a point's cell is i = floor((x - left) / side), j = floor((top - y) / side); it is judged if x, y, u, v are
+ * finite, 0 <= i < cols, 0 <= j < rows and its group lies in 0 .. ngroups - 1.  The pool of (group, cell) is every judged
+ * point of the group in the 3 x 3 cells around it, clipped at the lattice edge, the point under test included (the paper
+ * leaves it out: a declared difference).  med_u, mad_u, med_v, mad_v are np.median's bits (icelk_grid_stats_t's rules) of
+ * the pool's u, of fabs(u - med_u), and likewise for v.  With ru = fabs(u - med_u) / (mad_u + eps), rv likewise and r2 =
+ * ru * ru + rv * rv, every operation rounded once, the point is rejected iff r2 > threshold * threshold (a NaN r2 keeps it).
+ * status: 0 judged and kept, 1 rejected, 2 a pool of fewer than min_neighbours + 1 terms (kept, r2 NaN), 3 not judged
+ * (not finite, outside the lattice, in no group; r2 NaN).
+ * The defaults -- threshold 2.0, eps 0.01 m/s, min_neighbours 8 -- are policy, not measurements. */
+typedef struct icelk_validate_lattice {
+    double left, top, side;
+    int cols, rows;
+} icelk_validate_lattice_t;
+typedef struct icelk_validate_params {
+    double threshold, eps;
+    int min_neighbours, reserved;
+} icelk_validate_params_t;
+/* per (group g, cell i, j) at g * cols * rows + j * cols + i: the pool's size and statistics; 0 and four NaN for a cell
+ * without a point of its own.  All five members or none. */
+typedef struct icelk_validate_cells {
+    int32_t* pool_n;
+    double *med_u, *med_v, *mad_u, *mad_v;
+} icelk_validate_cells_t;
+/* x, y, u, v (float64, n); group: NULL (one group, ngroups must be 1) or n group numbers (int32; outside 0 .. ngroups - 1:
+ * in no group); params: NULL for the defaults; status (uint8, n), r2 (float64, n); cells: NULL or the five arrays.
+ * Kernels of csrc/k_validate.hip: assign, the gridder's sort, pool statistics, judge; one wait for the key count.
+ * ICELK_EARG: a null pointer, a threshold, eps or side that is not positive and finite, min_neighbours < 1, cols or rows
+ * < 1, ngroups < 1.  ICELK_ECAP: n > 2^27 or ngroups * cols * rows >= 2^31; the handle stays usable.  Everything is
+ * checked before anything is allocated. */
+int icelk_validate(icelk_t* h, const double* x, const double* y, const double* u, const double* v, int n, const int32_t* group,
+                   int ngroups, const icelk_validate_lattice_t* lattice, const icelk_validate_params_t* params, uint8_t* status,
+                   double* r2, const icelk_validate_cells_t* cells);
+/* The same statement on the CPU: no handle, no GPU, re-entrant.  The kernels are tested against it bit for bit. */
+int icelk_validate_host(const double* x, const double* y, const double* u, const double* v, int n, const int32_t* group, int ngroups,
+                        const icelk_validate_lattice_t* lattice, const icelk_validate_params_t* params, uint8_t* status, double* r2,
+                        const icelk_validate_cells_t* cells);
+/* icelk_grid_bin_windows_stats with `stats` nullable and the validation in front of the gridder: the points are uploaded
+ * once, the validation runs with the day tables' windows as groups (all cameras of a window share its pools), the DEVICE
+ * copy of t becomes NaN at every rejected point, and the unchanged gridder chain runs on that copy -- "NaN lies in no
+ * window", so a rejected point is neither selected, counted in sel_count / t_min / t_max, nor binned.  The caller's arrays
+ * are not written.  Out also: status (uint8, n) and rejected (int32, nw: the window's rejected points).  device_ms covers
+ * the validation's kernels too.  Refusals are those of the two calls it joins, all before anything is allocated. */
+int icelk_grid_bin_windows_validated(icelk_t* h, const double* x, const double* y, const double* u, const double* v,
+                                     const double* t, int n, const int64_t* file_offset, const int* file_cam,
+                                     const int* win_f0, const int* win_f1, int nfiles, const int64_t* t_lo,
+                                     const int64_t* t_hi, int ncam, int nw, double left, double top, double spacing,
+                                     int cols, int rows, const uint8_t* cell_on, int* count, double* mean_u, double* mean_v,
+                                     double* speed, int* sel_count, double* t_min, double* t_max, double* device_ms,
+                                     const icelk_grid_stats_t* stats_or_null, const icelk_validate_lattice_t* lattice,
+                                     const icelk_validate_params_t* params, uint8_t* status, int32_t* rejected);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
