@@ -36,6 +36,7 @@ from .orthophoto import (ortho_coords_host, ortho_movie_name, ortho_raster, orth
 from .stabilize import (STAB_DEGENERATE, STAB_LOST, STAB_NOT_CONVERGED, STAB_TOO_FEW, anchor_flags, stabilize_tracks,  # noqa: F401
                         stabilize_tracks_host)
 from .validate import validate_velocities, validate_velocities_host, validation_lattice  # noqa: F401
+from .tides import CONSTITUENTS, TideFit, fit_tides, fit_tides_host, load_tides, tide_basis  # noqa: F401
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

@@ -270,6 +270,11 @@ SIGNATURES = {
                                                    C.c_int, i64p, i64p, C.c_int, C.c_int, C.c_double, C.c_double,
                                                    C.c_double, C.c_int, C.c_int, u8p, i32p, f64p, f64p, f64p, i32p, f64p,
                                                    f64p, f64p, grid_stats_p, validate_lattice_p, validate_params_p, u8p, i32p]),
+    "icelk_cube_tide_fit": (C.c_int, [handle_p, f64p, C.c_int, C.c_int, C.c_double, C.c_int, f64p, f64p, f64p, f64p, f64p, f64p, i32p, i32p,
+                                      i32p, i32p, f64p, f64p, f64p]),
+    "icelk_cube_tide_predict": (C.c_int, [handle_p, f64p, f64p, i32p, C.c_int, C.c_int, f64p, C.c_int, f64p, f64p]),
+    "icelk_tide_fit_host": (C.c_int, [f64p, f64p, f64p, C.c_int, C.c_int, f64p, C.c_int, C.c_double, C.c_int, f64p, f64p, f64p, f64p, f64p,
+                                      f64p, i32p, i32p, i32p, i32p, f64p, f64p]),
     "icelk_set_gray_device":(C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

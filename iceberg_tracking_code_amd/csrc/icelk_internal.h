@@ -645,6 +645,31 @@ void launch_cube_temporal(hipStream_t s, const double* u, const double* v, const
 void launch_cube_spatial(hipStream_t s, const double* mean_u, const double* mean_v, const double* count_sum, int rows,
                          int cols, int coarseness, int nperiods, double* out_u, double* out_v, double* out_speed,
                          double* out_count);
+// the per-cell harmonic fit of the cube (k_tides.hip; the rules are tides.h's).  Device pointers throughout.  u, v, count: the
+// cube [window][cell]; basis [nt][m]; part [sum][chunk][cell], ipart [n | first | last][chunk][cell], tot [sum][cell], mean [u |
+// v][cell], part2 [res u | res v | tot u | tot v][chunk][cell]; coef [cell][m]; the other outputs one per cell; res_u, res_v
+// NULL or [window][cell].
+struct TideArgs {
+    const double *u, *v, *count;
+    int ncells, nt;
+    const double* basis;
+    int m;
+    double min_count;
+    int min_samples;
+    double* part;
+    int32_t* ipart;
+    double *tot, *mean, *part2;
+    double *coef_u, *coef_v, *rms_u, *rms_v, *explained_u, *explained_v;
+    int32_t *n, *first, *last, *status;
+    double *res_u, *res_v;
+};
+void launch_tide_normal(hipStream_t s, const TideArgs& A);
+void launch_tide_solve(hipStream_t s, const TideArgs& A);
+void launch_tide_residual(hipStream_t s, const TideArgs& A);
+void launch_tide_finish(hipStream_t s, const TideArgs& A);
+// out_u, out_v [ntp][cell] from coef [cell][m], status [cell] and basis [ntp][m]; NaN where status != 0
+void launch_tide_predict(hipStream_t s, const double* coef_u, const double* coef_v, const int32_t* status, int ncells, int m,
+                         const double* basis, int ntp, double* out_u, double* out_v);
 // the calibration misfit (k_calib.hip): candidates of 11 doubles (X, U, V, sigma in pixels, H), shoreline points
 // (xi, yi) relative to the image centre, waterline vertices (x, y); out_tx / out_ty may be null
 void launch_calib_residuals(hipStream_t s, const double* cand, int P, const double* shore, int M, const double* water,

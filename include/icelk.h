@@ -1173,6 +1173,37 @@ int icelk_grid_bin_windows_validated(icelk_t* h, const double* x, const double* 
                                      const icelk_grid_stats_t* stats_or_null, const icelk_validate_lattice_t* lattice,
                                      const icelk_validate_params_t* params, uint8_t* status, int32_t* rejected);
 
+/* ---- tidal harmonics of the velocity cube, per cell ---------------------------- */
+/* A least-squares fit of m terms -- a mean, cosine and sine of some tidal constituents, perhaps a trend -- to the samples of
+ * every cell, stated in csrc/tides.h.  basis: float64 [nt][m], row t the m terms at window t, made by the caller: no sine or
+ * cosine is evaluated here.  Window t is a sample of a cell iff u and v are finite and count >= min_count (false for a NaN
+ * count).  Normal equations summed in chunks of 256 windows (ascending inside a chunk, chunk totals ascending), Cholesky with
+ * the pivot test s > 2^-30 * A[j][j], forward and back substitution, every operation rounded once.
+ * Out, per cell: coef_u, coef_v [cell][m]; rms = sqrt(ss_res / (n - m)), NaN for n == m; explained = 1 - ss_res / ss_tot; n
+ * (samples), first, last (window index of the first and last sample, -1 without one); status 0 fitted, 1 fewer than
+ * max(min_samples, m) samples, 2 rank deficient -- coefficients, rms, explained and residuals are NaN for status != 0.
+ * residual_u_or_null, residual_v_or_null: NULL or [window][cell], u - prediction at a sample, NaN elsewhere.
+ * device_ms_or_null: the kernels' time by HIP events.
+ * icelk_cube_tide_fit runs the kernels of csrc/k_tides.hip on the cube icelk_cube_set left on the device and leaves it as it
+ * was.  ICELK_ESTATE without a cube; ICELK_EARG for a null pointer, an nt that is not the cube's, m < 1 or min_samples < 0;
+ * ICELK_ECAP for m > 18 or when (m (m + 1) / 2 + 2 m + 2) * ceil(nt / 256) * ncells does not fit 31 bits.  Everything is
+ * checked before anything is allocated or issued. */
+int icelk_cube_tide_fit(icelk_t* h, const double* basis, int nt, int m, double min_count, int min_samples, double* coef_u,
+                        double* coef_v, double* rms_u, double* rms_v, double* explained_u, double* explained_v, int32_t* n,
+                        int32_t* first, int32_t* last, int32_t* status, double* residual_u_or_null, double* residual_v_or_null,
+                        double* device_ms_or_null);
+/* out_u, out_v [ntp][cell]: coef[cell][0] * basis[t][0] + coef[cell][1] * basis[t][1] + ... in that order, NaN for a cell
+ * whose status is not 0.  basis [ntp][m] of any length.  Needs no cube.  ICELK_EARG for a null pointer or ncells, m or ntp
+ * < 1; ICELK_ECAP for m > 18 or when ncells * ntp does not fit 31 bits. */
+int icelk_cube_tide_predict(icelk_t* h, const double* coef_u, const double* coef_v, const int32_t* status, int ncells, int m,
+                            const double* basis, int ntp, double* out_u, double* out_v);
+/* icelk_cube_tide_fit on host arrays u, v, count [nt][ncells], by the same csrc/tides.h: no handle, no GPU, re-entrant.  The
+ * kernels are tested against it bit for bit. */
+int icelk_tide_fit_host(const double* u, const double* v, const double* count, int ncells, int nt, const double* basis, int m,
+                        double min_count, int min_samples, double* coef_u, double* coef_v, double* rms_u, double* rms_v,
+                        double* explained_u, double* explained_v, int32_t* n, int32_t* first, int32_t* last, int32_t* status,
+                        double* residual_u_or_null, double* residual_v_or_null);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
