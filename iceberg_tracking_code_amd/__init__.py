@@ -37,6 +37,7 @@ from .stabilize import (STAB_DEGENERATE, STAB_LOST, STAB_NOT_CONVERGED, STAB_TOO
                         stabilize_tracks_host)
 from .validate import validate_velocities, validate_velocities_host, validation_lattice  # noqa: F401
 from .tides import CONSTITUENTS, TideFit, fit_tides, fit_tides_host, load_tides, tide_basis  # noqa: F401
+from .drift import (DriftResult, drift, drift_host, drift_lattice, drift_schedule, load_drift, seed_line, seed_nodes)  # noqa: F401
 from ._lib import IcelkError  # noqa: F401
 
 __version__ = "0.1.0"

@@ -161,6 +161,27 @@ validate_params_p = C.POINTER(ValidateParams)
 validate_cells_p = C.POINTER(ValidateCells)
 VALIDATE_KEPT, VALIDATE_REJECTED, VALIDATE_FEW_NEIGHBOURS, VALIDATE_NOT_JUDGED = 0, 1, 2, 3
 
+
+class DriftLattice(C.Structure):
+    """icelk_drift_lattice_t"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("rows", C.c_int), ("cols", C.c_int)]
+
+
+class DriftParams(C.Structure):
+    """icelk_drift_params_t"""
+    _fields_ = [("step", C.c_double), ("nsteps", C.c_int), ("every", C.c_int), ("order", C.c_int), ("min_nodes", C.c_int)]
+
+
+class DriftOut(C.Structure):
+    """icelk_drift_out_t: host arrays"""
+    _fields_ = [(k, f64p) for k in ("x", "y", "last_x", "last_y", "length")] + [(k, i32p) for k in ("status", "stop_step", "visits")]
+
+
+drift_lattice_p = C.POINTER(DriftLattice)
+drift_params_p = C.POINTER(DriftParams)
+drift_out_p = C.POINTER(DriftOut)
+DRIFT_ALIVE, DRIFT_LEFT, DRIFT_TOO_FEW, DRIFT_NO_FIELD, DRIFT_NEVER_RELEASED = 0, 1, 2, 3, 4
+
 JPEG_CROP_ROUTES =("device", "host-huffman", "over-budget")   # ICELK_JPEG_CROP_*
 JPEG_TABLE_BYTES = 11328
 JPEG_FALLBACK_NONE, JPEG_FALLBACK_BOUND, JPEG_FALLBACK_STREAM, JPEG_FALLBACK_SIZE = 0, 1, 2, 3
@@ -275,6 +296,12 @@ SIGNATURES = {
     "icelk_cube_tide_predict": (C.c_int, [handle_p, f64p, f64p, i32p, C.c_int, C.c_int, f64p, C.c_int, f64p, f64p]),
     "icelk_tide_fit_host": (C.c_int, [f64p, f64p, f64p, C.c_int, C.c_int, f64p, C.c_int, C.c_double, C.c_int, f64p, f64p, f64p, f64p, f64p,
                                       f64p, i32p, i32p, i32p, i32p, f64p, f64p]),
+    "icelk_cube_drift": (C.c_int, [handle_p, drift_lattice_p, drift_params_p, i32p, i32p, f64p, i32p, C.c_double, f64p, f64p, i32p, C.c_int,
+                                   drift_out_p, f64p]),
+    "icelk_drift_tide": (C.c_int, [handle_p, drift_lattice_p, drift_params_p, f64p, f64p, i32p, C.c_int, f64p, f64p, f64p, i32p, C.c_int,
+                                   drift_out_p, f64p]),
+    "icelk_drift_host": (C.c_int, [drift_lattice_p, drift_params_p, f64p, f64p, f64p, C.c_int, i32p, i32p, f64p, i32p, C.c_double, f64p, f64p,
+                                   i32p, C.c_int, f64p, f64p, f64p, i32p, C.c_int, drift_out_p]),
     "icelk_set_gray_device":(C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),
     "icelk_cvt_bgr_device": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "icelk_upload_gray_async": (C.c_int, [handle_p, C.c_int, vp, C.c_int, C.c_int, C.c_int]),

@@ -16,8 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "obj")
 LIB = os.path.join(HERE, "libicelk.so")
-SOURCES = ["abi_handle.hip", "abi_frames.hip", "abi_lk.hip", "abi_detect.hip", "abi_segments.hip", "abi_post.hip", "abi_calib.hip", "abi_jpeg.hip", "abi_jpeg_ingest.hip", "abi_jpeg_job.hip", "abi_jpeg_async.hip", "abi_jpeg_resave.hip", "abi_jpeg_enc.hip", "abi_jpeg_crop.hip", "abi_plot.hip", "abi_map.hip", "abi_picture.hip", "abi_thumb.hip", "abi_png.hip", "abi_movie.hip", "abi_ortho.hip", "abi_stab.hip", "abi_validate.hip", "abi_tides.hip",
-           "k_image.hip", "k_pyramid.hip", "k_lk.hip", "k_lk_fast.hip", "k_lk_multi.hip", "k_corners.hip", "k_corners_fast.hip", "k_min_distance.hip", "k_sort.hip", "k_tail.hip", "k_tracks.hip", "k_utm.hip", "k_mask.hip", "k_grid.hip", "k_cube.hip", "k_calib.hip", "k_jpeg.hip", "k_jpeg_huff.hip", "k_jpeg_fwd.hip", "k_jpeg_enc.hip", "k_plot.hip", "k_map.hip", "k_thumb.hip", "k_png.hip", "k_resize.hip", "k_ortho.hip", "k_stab.hip", "k_validate.hip", "k_tides.hip"]
+SOURCES = ["abi_handle.hip", "abi_frames.hip", "abi_lk.hip", "abi_detect.hip", "abi_segments.hip", "abi_post.hip", "abi_calib.hip", "abi_jpeg.hip", "abi_jpeg_ingest.hip", "abi_jpeg_job.hip", "abi_jpeg_async.hip", "abi_jpeg_resave.hip", "abi_jpeg_enc.hip", "abi_jpeg_crop.hip", "abi_plot.hip", "abi_map.hip", "abi_picture.hip", "abi_thumb.hip", "abi_png.hip", "abi_movie.hip", "abi_ortho.hip", "abi_stab.hip", "abi_validate.hip", "abi_tides.hip", "abi_drift.hip",
+           "k_image.hip", "k_pyramid.hip", "k_lk.hip", "k_lk_fast.hip", "k_lk_multi.hip", "k_corners.hip", "k_corners_fast.hip", "k_min_distance.hip", "k_sort.hip", "k_tail.hip", "k_tracks.hip", "k_utm.hip", "k_mask.hip", "k_grid.hip", "k_cube.hip", "k_calib.hip", "k_jpeg.hip", "k_jpeg_huff.hip", "k_jpeg_fwd.hip", "k_jpeg_enc.hip", "k_plot.hip", "k_map.hip", "k_thumb.hip", "k_png.hip", "k_resize.hip", "k_ortho.hip", "k_stab.hip", "k_validate.hip", "k_tides.hip", "k_drift.hip"]
 # every header under csrc/ plus the public one: a new header cannot be forgotten by the staleness check
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(HERE, "..", "include", "icelk.h")]
 ARCH = "gfx950"

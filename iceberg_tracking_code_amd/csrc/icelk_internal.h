@@ -670,6 +670,24 @@ void launch_tide_finish(hipStream_t s, const TideArgs& A);
 // out_u, out_v [ntp][cell] from coef [cell][m], status [cell] and basis [ntp][m]; NaN where status != 0
 void launch_tide_predict(hipStream_t s, const double* coef_u, const double* coef_v, const int32_t* status, int ncells, int m,
                          const double* basis, int ntp, double* out_u, double* out_v);
+// virtual drifters (k_drift.hip; the rule and the fields are drift.h's).  Device pointers throughout: the field's tables, the
+// seeds and release steps of the n drifters, the outputs x, y [n_out][n] and one per drifter.
+namespace drift {
+struct CubeField;
+struct TideField;
+struct Out;
+}  // namespace drift
+struct DriftSeeds {
+    const double *x, *y;
+    const int32_t* release;
+    int n;
+};
+void launch_drift_cube(hipStream_t s, const icelk_drift_lattice_t& L, const icelk_drift_params_t& P, const drift::CubeField& F,
+                       const DriftSeeds& S, const drift::Out& O);
+void launch_drift_tide(hipStream_t s, const icelk_drift_lattice_t& L, const icelk_drift_params_t& P, const drift::TideField& F,
+                       const DriftSeeds& S, const drift::Out& O);
+// visits [rows][cols], zeroed by the caller: += 1 at the nearest node of every finite sample of x, y [samples]
+void launch_drift_visits(hipStream_t s, const icelk_drift_lattice_t& L, const double* x, const double* y, int samples, int32_t* visits);
 // the calibration misfit (k_calib.hip): candidates of 11 doubles (X, U, V, sigma in pixels, H), shoreline points
 // (xi, yi) relative to the image centre, waterline vertices (x, y); out_tx / out_ty may be null
 void launch_calib_residuals(hipStream_t s, const double* cand, int P, const double* shore, int M, const double* water,

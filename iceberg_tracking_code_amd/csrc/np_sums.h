@@ -98,7 +98,7 @@ ICELK_SUMS_FN double np_sum(const At& at, int n)
 ICELK_SUMS_INLINE_FN double hypot_np(double x, double y)
 {
     double ax = fabs(x), ay = fabs(y);
-    if (isinf(ax) || isinf(ay)) return HUGE_VAL;
+    if (ax == HUGE_VAL || ay == HUGE_VAL) return HUGE_VAL;   // not isinf: hipcc's host pass has no host isinf in this scope
     if (ax != ax || ay != ay) return ax + ay;
     if (ax < ay) { const double t = ax; ax = ay; ay = t; }
     if (ay <= ax * 0x1p-54) return ax + ay;

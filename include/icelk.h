@@ -1204,6 +1204,55 @@ int icelk_tide_fit_host(const double* u, const double* v, const double* count, i
                         double* explained_u, double* explained_v, int32_t* n, int32_t* first, int32_t* last, int32_t* status,
                         double* residual_u_or_null, double* residual_v_or_null);
 
+/* ---- virtual drifters through the gridded velocities ---------------------------- */
+/* Particles advected through the velocity cube, or through a tidal fit of it, by the rule of csrc/drift.h: bilinear in
+ * space, linear in time, a fixed step, Euler, midpoint or classical Runge-Kutta.  Everything is double. */
+typedef struct {
+    double x0, y0, dx, dy;   /* node (j, i) lies at (x0 + i * dx, y0 + j * dy); cell = j * cols + i */
+    int rows, cols;          /* at least 2 x 2 */
+} icelk_drift_lattice_t;
+typedef struct {
+    double step;             /* seconds, finite, not 0; negative: the field runs backwards */
+    int nsteps, every;       /* steps 0 .. nsteps; positions are recorded at the steps 0, every, 2 * every, ... */
+    int order, min_nodes;    /* 1, 2 or 4; 1 .. 4 measured nodes a sample needs */
+} icelk_drift_params_t;
+typedef struct {
+    double *x, *y;           /* [nsteps / every + 1][n]; NaN before the release and after the stop */
+    double *last_x, *last_y, *length;   /* per drifter: the last position (NaN if never released), the path's length */
+    int32_t *status;         /* ICELK_DRIFT_* */
+    int32_t *stop_step;      /* the step that failed; nsteps for a drifter alive at the end, -1 if never released */
+    int32_t *visits_or_null; /* [rows][cols]: recorded finite samples per nearest node */
+} icelk_drift_out_t;
+enum { ICELK_DRIFT_ALIVE = 0, ICELK_DRIFT_LEFT = 1, ICELK_DRIFT_TOO_FEW = 2, ICELK_DRIFT_NO_FIELD = 3, ICELK_DRIFT_NEVER_RELEASED = 4 };
+/* The schedule table has 2 * nsteps + 1 rows, row r the time start + r * step / 2, and is made by the caller: no time axis
+ * is searched and no sine is evaluated here.
+ * icelk_cube_drift: the cube icelk_cube_set left on the device, which stays as it was.  Per row the windows k0 <= k1 that
+ * bracket its time, the weight a of k1 and a flag, 0 for "no field at that time".  A window's node is measured iff u, v are
+ * finite and count >= min_count.  lattice->rows * cols must be the cube's ncells.
+ * icelk_drift_tide: coef_u, coef_v [cell][m] and status [cell] as icelk_cube_tide_predict takes them, basis [2 * nsteps +
+ * 1][m].  Needs no cube.
+ * seed_x, seed_y, release: one per drifter; a drifter exists from step release[p] on iff its seed is finite and 0 <=
+ * release[p] < nsteps.
+ * ICELK_ESTATE without a cube (icelk_cube_drift); ICELK_EARG for a null pointer, a lattice below 2 x 2 or with a spacing
+ * that is 0 or not finite or, for the cube, of another cell count, n < 1, step 0 or not finite, nsteps < 1, every < 1, an
+ * order not in {1, 2, 4}, min_nodes outside 1 .. 4, m < 1, a k0 or k1 outside the cube's windows; ICELK_ECAP when n *
+ * (nsteps / every + 1) or (2 * nsteps + 1) * m does not fit 31 bits, or m > 18.  Everything is checked before anything is
+ * allocated or issued.  device_ms_or_null: the kernels' time by HIP events. */
+int icelk_cube_drift(icelk_t* h, const icelk_drift_lattice_t* lattice, const icelk_drift_params_t* params, const int32_t* k0,
+                     const int32_t* k1, const double* a, const int32_t* flag, double min_count, const double* seed_x,
+                     const double* seed_y, const int32_t* release, int n, const icelk_drift_out_t* out, double* device_ms_or_null);
+int icelk_drift_tide(icelk_t* h, const icelk_drift_lattice_t* lattice, const icelk_drift_params_t* params, const double* coef_u,
+                     const double* coef_v, const int32_t* status, int m, const double* basis, const double* seed_x,
+                     const double* seed_y, const int32_t* release, int n, const icelk_drift_out_t* out, double* device_ms_or_null);
+/* Both sources on host arrays by the same csrc/drift.h: no handle, no GPU, re-entrant.  The cube source when u is given
+ * (u, v, count [nt][rows * cols] with k0, k1, a, flag), the tide source when coef_u is (with coef_v, status, m, basis);
+ * exactly one of the two, the other's pointers NULL.  The kernels are tested against it bit for bit. */
+int icelk_drift_host(const icelk_drift_lattice_t* lattice, const icelk_drift_params_t* params, const double* u, const double* v,
+                     const double* count, int nt, const int32_t* k0, const int32_t* k1, const double* a, const int32_t* flag,
+                     double min_count, const double* coef_u, const double* coef_v, const int32_t* status, int m,
+                     const double* basis, const double* seed_x, const double* seed_y, const int32_t* release, int n,
+                     const icelk_drift_out_t* out);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 /* Per-kernel HIP-event timing on the handle's streams (bench.py's roofline leg).  on = 1: every kernel; on = 2: the
  * tracker launches only (each timed kernel costs two event records on its stream, which the chains of short detector
